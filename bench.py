@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """Headline benchmark: NTTs/sec/GPU at logN=16, L=30 limbs (+ cc_mult_evk ops/sec), % of HBM roofline.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: launched by torch.distributed.run, one rank per GPU, RCCL)
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, ms_per_step, ...).
+--dump-outputs DIR: a fixed, seeded sample of what the last timed step computed, as DIR/*.npy (dump_outputs()).
+--full: everything below besides the headline: the parity spot check, the roofline / clock / power legs, the other
+presets and engine ops, the CPU baselines and the RCCL legs.
 
 One "step" = one forward negacyclic NTT (ntt_cuda.ntt semantics, bit-exact lazy outputs) of a batch of
 B polynomials x 30 RNS limbs at logN = 16 — the gold preset's with-special row set at level 9 (25 scale
@@ -13,7 +18,8 @@ reports that form beside the metric).  B = 128 by default (3.75 GiB-class workin
 tiled pass is 10 block rounds instead of 80).  Inputs are synthetic (splitmix64 -> mod 2q), resident in HBM before the timed region.
 Polynomials are independent, so ranks shard them with no data-path collective: weak scaling.
 
-The JSON line also carries
+Under --full the JSON line also carries
+  parity_spot_check : one polynomial of one more step, two of its limbs word for word against the C oracle (exit 4 on a mismatch);
   roofline     : the dominant kernel (ntt_pass16_fwd_seq_ws: the tiled pass of all 30 limbs, the second of the two
                  launches of a transform, 11 of its 16 stages) against the 8 TB/s HBM peak; algorithmic bytes
                  per launch = 8*N*limbs (a transform is 16*N bytes per limb, SURVEY.md §8d, spread over its two
@@ -844,6 +850,23 @@ def run_rccl_world1(timeout=420):
     return block
 
 
+DUMP_SAMPLE_WORDS = 1 << 20
+DUMP_SEED = 20261016
+
+
+def dump_outputs(out_dir, x):
+    """What the timed step hands its caller: the [B, 30, N] int64 words lf_ntt_ws leaves in place, after the last timed step.
+    The whole stack is GiBs, so a fixed sample of positions is written (drawn from DUMP_SEED, the same for every run of the
+    same arguments): ntt_out_index.npy (flat positions), ntt_out_lo31.npy / ntt_out_hi31.npy (bits 0..30 and 31..62 of each
+    word).  All float64 and exact: positions < 2^53, halves < 2^32."""
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    idx = np.unique(rng.integers(0, x.numel(), size=DUMP_SAMPLE_WORDS, dtype=np.int64))
+    words = x.reshape(-1)[torch.from_numpy(idx).to(x.device)].cpu().numpy()
+    for name, arr in (("ntt_out_index", idx), ("ntt_out_lo31", words & ((1 << 31) - 1)), ("ntt_out_hi31", words >> 31)):
+        np.save(os.path.join(out_dir, name + ".npy"), arr.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -855,7 +878,14 @@ def main():
                     help="N > 1: skip the limb-sharded gold cc_mult / rotate legs (RCCL broadcast + all-gather), timed by default")
     ap.add_argument("--leg-timeout", type=float, default=300.0,
                     help="N > 1: seconds after which the multi-GPU engine legs are abandoned and the line is printed without them")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: parity spot check, roofline, clocks / power, the other presets and engine ops, "
+                         "CPU baselines, RCCL legs (off: set up, warm up, time the steps, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float64, a fixed seeded sample)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
@@ -867,7 +897,7 @@ def main():
     # communicator of one rank under the engine's sharded code path, both exchange forms, graphs on and off, the stream-ordering
     # semantics of work.wait(); its JSON becomes comm.rccl_world1 of the line.
     rccl_world1 = None
-    if world == 1 and not args.no_extra and os.environ.get("LF_BENCH_RCCL_WORLD1", "1") != "0" and torch.cuda.device_count() >= 1:
+    if world == 1 and args.full and not args.no_extra and os.environ.get("LF_BENCH_RCCL_WORLD1", "1") != "0" and torch.cuda.device_count() >= 1:
         import __graft_entry__ as g0
         g0.build()                      # (hipcc cross-compiles without touching the GPU: the child must load THIS tree's library)
         rccl_world1 = run_rccl_world1()
@@ -983,6 +1013,34 @@ def main():
     ms_per_step = wall / args.steps * 1e3
 
     value = world * B / (wall / args.steps)                         # poly-NTT(30)/s, whole job
+
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, x)
+    head = {
+        "metric": "NTTs/sec (forward negacyclic poly-NTT, logN=16, L=30 limbs, bit-exact vs reference semantics)",
+        "value": value, "unit": "poly-NTT/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "int64", "data": "synthetic"}
+    config = {"workload": f"gold preset (logN=16), rows {lo}..{total - 1} of the prime chain (25 scale + base + 4 special"
+                          f" primes = 30 limbs), {B} polynomials per GPU per step, forward NTT via "
+                          + ("lf_ntt (C ABI, strictly in place)" if in_place else "lf_ntt_ws (C ABI: lf_ntt through a resident workspace of the operands' size)"),
+              "workspace_bytes": None if ws is None else int(ws.numel()) * 8,
+              "batch_per_gpu": B, "limbs": L_LIMBS, "logN": LOGN, "parallelism": f"replicas x{world} (independent polynomials)"}
+    extra = {"limb_ntt_per_s": value * L_LIMBS, "device_ms_per_step": dev_ms,
+             "whole_step_frac_of_achievable_6300": 16 * N * L_LIMBS * B / (dev_ms * 1e-3) / 1e9 / HBM_ACHIEVABLE_GBS}
+    if rehearse:
+        extra["REHEARSAL"] = "all ranks on cuda:0 over gloo: not a measurement"
+    if not args.full:
+        # a plain run: the headline and nothing else (the checks and the other legs below run under --full)
+        if rank == 0:
+            print(json.dumps(dict(head, config=config, extra=extra)), flush=True)
+        if world > 1:
+            try:
+                dist.barrier()
+                dist.destroy_process_group()
+            except Exception:
+                pass
+        return
 
     # Parity spot check of what the timed kernel computes, on THIS box, outside the timed region: polynomial 0 is reloaded
     # from its seed, the whole batch goes through one more step, and two of its limbs — the first integer-class one (a
@@ -1157,20 +1215,13 @@ def main():
             "wave_instr_per_step": valu + cols_valu,
             "note": "min time = VALU wave-instructions (PMC, this build) / (1024 SIMDs x measured shader clock / 4 cycles)"}
 
-    result = {
-        "metric": "NTTs/sec (forward negacyclic poly-NTT, logN=16, L=30 limbs, bit-exact vs reference semantics)",
-        "value": value, "unit": "poly-NTT/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "int64", "data": "synthetic",
+    result = dict(
+        head,
         # one polynomial of one more (untimed) step, an integer-class and an fp64-class limb, word for word vs the C oracle
-        "parity_spot_check": spot,
-        "config": {"workload": f"gold preset (logN=16), rows {lo}..{total - 1} of the prime chain (25 scale + base + 4 special"
-                               f" primes = 30 limbs), {B} polynomials per GPU per step, forward NTT via "
-                               + ("lf_ntt (C ABI, strictly in place)" if in_place else "lf_ntt_ws (C ABI: lf_ntt through a resident workspace of the operands' size)"),
-                   "workspace_bytes": None if ws is None else int(ws.numel()) * 8,
-                   "batch_per_gpu": B, "limbs": L_LIMBS, "logN": LOGN, "parallelism": f"replicas x{world} (independent polynomials)",
-                   # repeated here because drivers keep `config` verbatim: "ok" = the timed kernel's words equal the oracle's
-                   "parity_spot_check": spot},
+        parity_spot_check=spot,
+        # repeated here because drivers keep `config` verbatim: "ok" = the timed kernel's words equal the oracle's
+        config=dict(config, parity_spot_check=spot))
+    result.update({
         # What bounds the dominant kernel is VALU instruction issue, not HBM (the bytes would take half the time): `frac`
         # stays the algorithmic-bytes fraction of the 8 TB/s HBM peak the contract asks for, `issue_frac` is the measured
         # utilisation of the pipe that actually limits it (PMC; null when the counters were not taken on this build)
@@ -1197,12 +1248,8 @@ def main():
                      "valu": None if valu is None else {
                          "wave_instr_per_launch": valu, "wave_instr_G_per_s": valu / (k_ms * 1e-3) / 1e9,
                          "busy_frac_pmc": valu_busy, "source": pmc_source}},
-    }
-    extra = {"limb_ntt_per_s": value * L_LIMBS, "device_ms_per_step": dev_ms,
-             "whole_step_frac_of_achievable_6300": 16 * N * L_LIMBS * B / (dev_ms * 1e-3) / 1e9 / HBM_ACHIEVABLE_GBS}
+    })
     result["extra"] = extra
-    if rehearse:
-        extra["REHEARSAL"] = "all ranks on cuda:0 over gloo: not a measurement"
     if rank == 0 and world == 1 and not args.no_extra:
         if ws is not None:      # the same step strictly in place (lf_ntt), for the record of what the workspace buys
             for _ in range(3):

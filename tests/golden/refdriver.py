@@ -1,7 +1,7 @@
 """Import the reference's Python layers in the BUILD container and drive them on CPU.
 
-Only used by tests/golden/make_golden.py (fixture generation) and by tests that are skipped when
-/root/reference is absent (it never exists on the GPU box).  The reference's five CUDA extension
+Only used by the fixture generators tests/golden/make_golden*.py; the tests read what they recorded and
+never import the reference.  The reference's five CUDA extension
 modules cannot be built here; this module registers stand-ins for them:
 
   * liberate.ntt.ntt_cuda                -> the C oracle (oracle/ckks_oracle.c) behind the

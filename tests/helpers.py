@@ -2,6 +2,8 @@
 from __future__ import annotations
 
 import hashlib
+import json
+import os
 
 import numpy as np
 
@@ -151,3 +153,66 @@ class SeededCsprng:
         fl = np.floor(c)
         r = fl + (self.g.random(c.shape) < (c - fl))
         return self.torch.from_numpy(r.astype(np.int64)).to(dev)
+
+
+def fingerprint(x):
+    """A JSON-able summary of a result that is equal exactly when the results are: ints, floats, strings and None as they are,
+    tensors and arrays as shape + SHA-256 of their words (int64 for integer data, float64 / complex128 otherwise), data_struct
+    objects as their flags plus their data.  numpy scalars count as the Python numbers they equal."""
+    import torch
+    if hasattr(x, "origin") and hasattr(x, "data") and hasattr(x, "level"):
+        return {"origin": x.origin, "level": int(x.level), "include_special": bool(x.include_special),
+                "ntt_state": bool(x.ntt_state), "montgomery_state": bool(x.montgomery_state), "data": fingerprint(x.data)}
+    if isinstance(x, torch.Tensor):
+        x = x.detach().cpu().numpy()
+    if isinstance(x, np.ndarray):
+        kind = np.int64 if x.dtype.kind in "biu" else (np.complex128 if x.dtype.kind == "c" else np.float64)
+        return {"shape": list(x.shape), "sha256": sha(x.astype(kind))}
+    if isinstance(x, (list, tuple)):
+        return [fingerprint(v) for v in x]
+    if isinstance(x, dict):
+        return {str(k): fingerprint(v) for k, v in sorted(x.items(), key=lambda kv: str(kv[0]))}
+    if isinstance(x, (bool, np.bool_)):
+        return bool(x)
+    if isinstance(x, (int, np.integer)):
+        return int(x)
+    if isinstance(x, (float, np.floating)):
+        return float(x)
+    if x is None or isinstance(x, str):
+        return x
+    raise TypeError(f"no fingerprint for {type(x).__name__}")
+
+
+class Recorded:
+    """Results the reference produced for one test, recorded by tests/golden/make_golden_reference.py into
+    tests/golden/reference_results.json: `check(key, value)` asserts that `value` equals the reference's result under
+    `key`.  Made with `record=True` (the generator), it stores the fingerprints instead."""
+
+    PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_results.json")
+    _store = None
+
+    def __init__(self, test, record=False):
+        if Recorded._store is None:
+            Recorded._store = json.load(open(self.PATH)) if os.path.exists(self.PATH) else {}
+        self.test, self.record = test, record
+        if record:
+            Recorded._store[test] = {}
+        self.expected = Recorded._store.get(test, {})
+
+    def check(self, key, value):
+        got = fingerprint(value)
+        text = json.dumps(got, sort_keys=True)
+        if len(text) > 200:         # a long fingerprint is kept as its digest
+            got = "sha256:" + hashlib.sha256(text.encode()).hexdigest()
+        if self.record:
+            assert key not in self.expected, f"{self.test}: key {key!r} recorded twice"
+            self.expected[key] = got
+            return
+        assert key in self.expected, f"{self.test}: nothing recorded under {key!r} (run tests/golden/make_golden_reference.py)"
+        assert got == self.expected[key], f"{self.test}: {key} differs from the reference's result"
+
+    @classmethod
+    def save(cls):
+        with open(cls.PATH, "w") as f:
+            json.dump(cls._store, f, indent=1, sort_keys=True)
+            f.write("\n")

@@ -11,7 +11,7 @@ import torch
 
 from oracle import csprng_oracle as co
 from tests import csprng_streams as cs
-from tests.golden import refdriver as rd
+from tests.helpers import Recorded
 from tests.oracle_csprng import oracle_csprng_class
 
 GOLD = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "csprng_golden.json")))
@@ -187,18 +187,19 @@ def test_product_samplers_refuse_cpu_tensors():
         r.discrete_gaussian(repeats=1)
 
 
-@pytest.mark.reference
-@pytest.mark.skipif(not rd.reference_available(), reason="needs /root/reference")
+def check_class_live(r, rec):
+    """State layout, initial states and every call of the stream script (csprng_streams.stream_calls) of a Csprng."""
+    rec.check("inc L shares", [r.inc, r.L, r.shares])
+    rec.check("states", list(r.states))
+    for label, method, kw in cs.stream_calls(cs.STREAM_CONFIGS["small"]):
+        rec.check(label, list(getattr(r, method)(**kw)))
+
+
 def test_host_logic_equals_reference_class_live():
+    """The product class over the checker's kernels against the reference's class over the same kernels (recorded by
+    tests/golden/make_golden_reference.py)."""
     cfg = cs.STREAM_CONFIGS["small"]
-    ref = rd.reference_csprng(cfg["num_coefs"], cfg["num_channels"], cfg["num_repeating_channels"], cfg["n_dev"],
-                              cs.STREAM_KEY, cs.STREAM_NONCE)
     me = oracle_csprng_class()(cfg["num_coefs"], cfg["num_channels"], cfg["num_repeating_channels"],
                                devices=["cpu"] * cfg["n_dev"], seed=cs.STREAM_KEY, nonce=cs.STREAM_NONCE,
                                reference_counter_layout=True)
-    assert me.inc == ref.inc and me.L == ref.L and me.shares == ref.shares
-    for a, b in zip(ref.states, me.states):
-        assert torch.equal(a, b)
-    for label, method, kw in cs.stream_calls(cfg):
-        for a, b in zip(getattr(ref, method)(**kw), getattr(me, method)(**kw)):
-            assert torch.equal(a, b), label
+    check_class_live(me, Recorded("csprng_class_live"))

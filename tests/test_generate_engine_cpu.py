@@ -2,12 +2,13 @@
 for every (logN, scale_bits) in {14,15,16} x {20,25,..,45} with the default security settings.  The
 reference's shipped prime tables have too few 20-bit (and, at logN 16, 25-bit) NTT primes for those
 rings, where its constructor raises NotEnoughPrimes; the expected chain lengths below were recorded from
-the reference's ckks_context (and are re-checked live against it where /root/reference exists)."""
+the reference's ckks_context, and its chains themselves by tests/golden/make_golden_reference.py."""
 import warnings
 
+import numpy as np
 import pytest
 
-from tests.golden import refdriver as rd
+from tests.helpers import Recorded, sha
 
 warnings.filterwarnings("ignore", category=UserWarning)
 
@@ -41,34 +42,37 @@ def test_make_engine(logN, scale_bits):
     assert all(q % (2 * eng.ctx.N) == 1 for q in eng.ctx.q)
 
 
-@pytest.mark.reference
-@pytest.mark.skipif(not rd.reference_available(), reason="/root/reference not present")
+def chain(make):
+    """The prime chain of the context `make()` builds, or the name of the exception it raises."""
+    try:
+        return [int(x) for x in make().q]
+    except Exception as e:
+        return type(e).__name__
+
+
+def scale_pool_digest(pool):
+    """None for an entry that is not a pool (the reference's "not enough primes" strings), else a digest of its primes."""
+    return None if pool is None or isinstance(pool, str) else sha(np.array([int(p) for p in pool], dtype=np.int64))
+
+
 @pytest.mark.parametrize("logN,scale_bits", sorted(EXPECTED))
 def test_chain_equals_reference_context(logN, scale_bits):
     from liberate_fhe_amd.fhe.context.ckks_context import ckks_context
-    outcome = []
-    for make in (lambda: rd.reference_context(**ctx_params(logN, scale_bits)),
-                 lambda: ckks_context(**ctx_params(logN, scale_bits))):
-        try:
-            outcome.append([int(x) for x in make().q])
-        except Exception as e:
-            outcome.append(type(e).__name__)
-    assert outcome[0] == outcome[1]
-    assert (None if isinstance(outcome[1], str) else len(outcome[1])) == EXPECTED[logN, scale_bits]
+    got = chain(lambda: ckks_context(**ctx_params(logN, scale_bits)))
+    Recorded(f"chain[{logN},{scale_bits}]").check("q", got)
+    assert (None if isinstance(got, str) else len(got)) == EXPECTED[logN, scale_bits]
 
 
-@pytest.mark.reference
-@pytest.mark.skipif(not rd.reference_available(), reason="/root/reference not present")
 def test_scale_prime_pools_equal_shipped_table():
     """Every entry of the reference's scale_primes.pkl — 240 (scale_bits, N) pairs, including the truncated
     pools and the two "not enough primes" entries — is reproduced by the on-demand generator."""
-    import pickle
     from liberate_fhe_amd.fhe.context import primes
-    table = pickle.load(open("/root/reference/src/liberate/fhe/cache/resources/scale_primes.pkl", "rb"))
-    assert len(table) == 240
-    for (sb, N), want in table.items():
+    rec = Recorded("scale_prime_pools")
+    assert len(rec.expected) == 240
+    for key in rec.expected:
+        sb, N = (int(v) for v in key.split(","))
         try:
             got = list(primes.scale_prime_pool(sb, N))
         except LookupError:
             got = None
-        assert got == (None if isinstance(want, str) else want), (sb, N)
+        rec.check(key, scale_pool_digest(got))

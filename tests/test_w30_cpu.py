@@ -1,13 +1,13 @@
 """The reference's 30-bit / int32 word mode (ckks_context.py:213-216; K.cu templates over scalar_t) on the CPU side: the
 oracle's int32 instantiation against big-integer definitions, this package's 30-bit context against the reference's
-(when /root/reference is present), and the engine's refusal of a mode the reference's own engine cannot run."""
+(recorded by tests/golden/make_golden_reference.py), and the engine's refusal of a mode the reference's own engine cannot run."""
 import random
 
 import numpy as np
 import pytest
 
 from oracle import oracle as orc
-from tests.helpers import Limbs, pick_primes30
+from tests.helpers import Limbs, Recorded, pick_primes30
 from liberate_fhe_amd.fhe.context.ckks_context import bit_reverse_indices, stage_butterfly_indices
 
 R30 = 1 << 30
@@ -80,22 +80,24 @@ def test_compact_and_table_driven_ntt30_agree(logN):
     assert (a == b).all()
 
 
-def test_context30_equals_the_reference_context():
-    """ckks_context(buffer_bit_length = 30): primes, Montgomery constants and twiddles equal the imported reference's."""
-    from tests.golden import refdriver
-    if not refdriver.reference_available():
-        pytest.skip("reference not present (GPU box): the comparison runs in the build container")
-    from liberate_fhe_amd.fhe.context.ckks_context import ckks_context
+CONTEXT30 = dict(buffer_bit_length=30, scale_bits=24, logN=12, num_scales=4, num_special_primes=2, is_secured=False)
+
+
+def check_context30(ctx, rec):
     import torch
-    kw = dict(buffer_bit_length=30, scale_bits=24, logN=12, num_scales=4, num_special_primes=2, is_secured=False)
-    ref = refdriver.reference_context(**kw)
-    mine = ckks_context(**kw)
-    assert mine.torch_dtype == ref.torch_dtype == torch.int32 and mine.numpy_dtype == ref.numpy_dtype == np.int32
+    assert ctx.torch_dtype == torch.int32 and ctx.numpy_dtype == np.int32
     for name in ("q", "R", "R_square", "q_lower_bits", "q_higher_bits", "q_double", "R_inv", "k", "k_lower_bits", "k_higher_bits", "N_inv",
                  "half_buffer_bit_length", "lower_bits_mask", "full_bits_mask", "message_bits"):
-        assert getattr(mine, name) == getattr(ref, name), name
-    assert (np.asarray(mine.forward_psi) == np.asarray(ref.forward_psi)).all()
-    assert (np.asarray(mine.backward_psi_inv) == np.asarray(ref.backward_psi_inv)).all()
+        rec.check(name, getattr(ctx, name))
+    rec.check("forward_psi", np.asarray(ctx.forward_psi))
+    rec.check("backward_psi_inv", np.asarray(ctx.backward_psi_inv))
+
+
+def test_context30_equals_the_reference_context():
+    """ckks_context(buffer_bit_length = 30): primes, Montgomery constants and twiddles equal the reference's (recorded by
+    tests/golden/make_golden_reference.py)."""
+    from liberate_fhe_amd.fhe.context.ckks_context import ckks_context
+    check_context30(ckks_context(**CONTEXT30), Recorded("context30"))
 
 
 def test_engine_refuses_the_word_mode_the_reference_engine_cannot_run():

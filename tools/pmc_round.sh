@@ -4,7 +4,7 @@
 set -u
 TAG=${1:-r06}
 export TMPDIR=/tmp
-OUT=$PWD/gpurun_out; mkdir -p $OUT; REPO=$PWD
+OUT=${OUT:-$PWD/out}; mkdir -p $OUT; REPO=$PWD
 # build ONCE, unprofiled: a profiled process must never spawn the compiler (the profiler's preload would ride along into hipcc,
 # and the minutes of compilation would sit inside a counter run)
 python3 -c 'import __graft_entry__ as g; g.build()' > $OUT/build_$TAG.log 2>&1 || { echo "build failed"; tail -5 $OUT/build_$TAG.log; exit 1; }
@@ -12,7 +12,7 @@ run() {  # tag, counters..., then "--", then program args
   local TAG=$1; shift; local CNT=(); while [ "$1" != "--" ]; do CNT+=("$1"); shift; done; shift
   cd /tmp && rocprofv3 --pmc "${CNT[@]}" --kernel-trace -d $OUT/pmc2_$TAG -o p -- python3 "$@" > $OUT/pmc2_$TAG.log 2>&1; cd $REPO
 }
-B="$REPO/bench.py --no-extra --steps 5 --warmup 2"
+B="$REPO/bench.py --full --no-extra --steps 5 --warmup 2"
 run bench_fetch FETCH_SIZE -- $B
 run bench_write WRITE_SIZE -- $B
 run bench_valu SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAIT_INST_ANY -- $B
@@ -34,6 +34,6 @@ for OP in rotate_batch cc_mult_batch; do
   run ${T}_valu SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAIT_INST_ANY -- $C
 done
 # kernel stats of the bench command itself (the file the roofline numbers are checked against)
-cd /tmp && rocprofv3 --kernel-trace --stats -d $OUT/prof_$TAG -o stats -- python3 $REPO/bench.py --no-extra > $OUT/prof_$TAG.log 2>&1; cd $REPO
-python3 bench.py --no-extra > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err; tail -c 400 $OUT/bench_$TAG.json   # (round_profiles.sh replaces it by the full line)
+cd /tmp && rocprofv3 --kernel-trace --stats -d $OUT/prof_$TAG -o stats -- python3 $REPO/bench.py --full --no-extra > $OUT/prof_$TAG.log 2>&1; cd $REPO
+python3 bench.py --full --no-extra > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err; tail -c 400 $OUT/bench_$TAG.json   # (round_profiles.sh replaces it by the full line)
 ls $OUT | grep pmc2 | head -20

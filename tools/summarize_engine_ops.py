@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag = sys.argv[1] if len(sys.argv) > 1 else "r04"
 sys.path.insert(0, ROOT)
 import __graft_entry__ as _g   # noqa: E402
-src = os.path.join(ROOT, "gpurun_out")
+src = os.environ.get("OUT", os.path.join(ROOT, "out"))   # tools/profile_engine_ops.sh wrote there
 N_OPS = 10
 lines, summary = [], {}
 for preset in ("silver", "gold"):

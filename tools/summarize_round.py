@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""gpurun_out/ of tools/pmc_round.sh <tag> -> the tracked summaries under profiles/ (python3 tools/summarize_round.py <tag>):
+"""The output folder ($OUT, default out/) of tools/pmc_round.sh <tag> -> the tracked summaries under profiles/ (python3 tools/summarize_round.py <tag>):
 
-  <tag>_bench_kernel_stats.txt   rocprofv3 --kernel-trace --stats of `python3 bench.py --no-extra`
+  <tag>_bench_kernel_stats.txt   rocprofv3 --kernel-trace --stats of `python3 bench.py --full --no-extra`
   <tag>_bench_pmc.txt          FETCH_SIZE / WRITE_SIZE / SQ passes over the same command (separate runs)
   traffic_<tag>.json           what bench.py folds into its roofline block (bytes and VALU figures per launch)
   <tag>_engine_ops_pmc.txt       the same counters per kernel of gold / silver cc_mult (+relinearize)
@@ -12,7 +12,7 @@ half its bytes (MI355X_MICROARCH.md, HBM section) -> doubled.  SQ_ACTIVE_INST_VA
 import collections, json, os, sqlite3, sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-src, out = os.path.join(ROOT, "gpurun_out"), os.path.join(ROOT, "profiles")
+src, out = os.environ.get("OUT", os.path.join(ROOT, "out")), os.path.join(ROOT, "profiles")
 TAG = sys.argv[1] if len(sys.argv) > 1 else "r05"
 sys.path.insert(0, ROOT)
 import __graft_entry__ as _g   # noqa: E402
@@ -42,7 +42,7 @@ def counters(tag):
 
 
 # ---- bench: kernel stats -------------------------------------------------------------------------------------------
-lines = [f"# rocprofv3 --kernel-trace --stats -- python3 bench.py --no-extra   ({TAG})",
+lines = [f"# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-extra   ({TAG})",
          "# columns: kernel | calls | total_us | avg_us | % of GPU time", ""]
 for name, calls, total, avg, pct in q(os.path.join(src, f"prof_{TAG}", "stats_results.db"),
                                       "select name,total_calls,total_duration,average,percentage from top_kernels"):
@@ -64,7 +64,7 @@ print("\n".join(lines[:12]))
 
 # ---- bench: PMC ----------------------------------------------------------------------------------------------------
 f, w, v = counters("bench_fetch"), counters("bench_write"), counters("bench_valu")
-pm = [f"# rocprofv3 --pmc <counters> --kernel-trace -- python3 bench.py --no-extra --steps 5 --warmup 2   ({TAG}); one run per line group",
+pm = [f"# rocprofv3 --pmc <counters> --kernel-trace -- python3 bench.py --full --no-extra --steps 5 --warmup 2   ({TAG}); one run per line group",
       "# kernel/grid | us | FETCH_SIZE KiB (raw) | read MB (x2, gfx950) | WRITE_SIZE KiB | write MB | moved TB/s | VALU wave-instr | VALU busy | CU busy", ""]
 traffic = {"batch_per_gpu": 128, "library_digest": DIGEST}
 for key in sorted(f):

@@ -135,10 +135,14 @@ int lf_mont_sub(const int64_t *a, const int64_t *b, int64_t *c, int rows, int64_
  * without q_host returns LF_ERR_ARG before anything is launched: lf_twiddle_dp lays each auxiliary row out by the
  * size of its prime, so the launch must know the primes to read it.
  * flags: LF_NTT_RELAXED = the caller only needs the result modulo q (outputs are then canonical
- * residues instead of the reference's lazy representatives) — for fused internal use, never for the
+ * residues instead of the reference's lazy representatives; exception: the integer-class limbs of a relaxed FORWARD
+ * transform at logN <= 12, one pass, come out as lazy words in [0, 2q)) — for fused internal use, never for the
  * drop-in ops.  A relaxed FORWARD transform accepts the reference's signed-lazy words (|a| < 2q); a relaxed
- * INVERSE transform takes non-negative words: below 2^52 on fp64-class limbs, lazy words in [0, 2q) on integer-class
- * limbs (what lf_tensor / lf_ks_inner / the fused core write). */
+ * INVERSE transform takes non-negative words: below 2^46 on fp64-class limbs, lazy words in [0, 2q) on integer-class
+ * limbs (what lf_tensor / lf_ks_inner / the fused core write).  The fp64 bound: the words enter as doubles unreduced,
+ * every stage of the inverse at most doubles them, and the schedule folds them (dp_reduce_bal, exact for |x| < 2^52)
+ * only after every second radix-8 step, so six stages run between folds: 2^6 * (2^46 - 1) < 2^52.  Larger words
+ * leave the exact integer range of fp64 before the first fold (tests/test_class_edges_gpu.py holds the bound). */
 #define LF_NTT_RELAXED 1
 /* with LF_NTT_RELAXED: fp64-class limbs stay in the PLAIN domain — lf_ntt applies Rs to integer-class limbs
  * only, lf_intt (tail >= 2) multiplies fp64-class limbs by N^-1 instead of N^-1 R^-1.  Used by the fused

@@ -272,7 +272,10 @@ __global__ void __launch_bounds__(256) ks_moddown_kernel(PtrBatch pb, int ell, i
             for (int pi = 0; pi < KS_MAX_K; ++pi) {
                 if (pi < K) {
                     const double ph = (double)(pv[pi] >> 31), pl = (double)(pv[pi] & 0x7fffffffll);
-                    // pivot mod q (< 3q after the two terms), then (x - pivot) * P^-1 mod q
+                    // pivot mod q, then (x - pivot) * P^-1 mod q.  The two terms sum below q + 2^31: under 3q when q > 2^30,
+                    // so the two subtractions leave pm canonical.  For smaller q (scale_bits 20 .. 30) pm stays a multiple of
+                    // q above its residue (< 2^31) and x - pm + q may be negative: dp_mulmod_q takes signed operands
+                    // (here |x - pm + q| < 2^32) and returns the canonical product all the same (the sb20 engine digests hold it)
                     double pm = dp_mulmod_q(ph, two31, q, qinv) + pl;
                     pm = pm >= q ? pm - q : pm;
                     pm = pm >= q ? pm - q : pm;

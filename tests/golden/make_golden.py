@@ -31,9 +31,18 @@ CONFIGS = {
     "silver": dict(logN=15, num_special_primes=2),
     "gold": dict(logN=16, num_special_primes=4),
     "platinum": dict(logN=17, num_special_primes=6),
-    # other word widths of the scale primes: 30-bit (fp64 class, far below 2^41) and 45-bit (integer class: >= 2^41)
+    # other word widths of the scale primes.  The two arithmetic classes of the kernels split at SMALL_PRIME_LIMIT = 2^41
+    # (csrc/ckks_ntt_core.h): primes below it run on fp64 FMA arithmetic, larger ones on 64-bit integers.
+    #   sb30: fp64 class, far below 2^41;  sb45: integer class only;
+    #   sb41: the chain alternates between the classes row by row, starting at 2^41 - 65535 (the top of the fp64 class;
+    #         the lazy-REDC fix window of the fp64 path is widest there) and 2^41 + 311297;
+    #   sb41_16: the same edge at logN 16 with K = 4 special primes in the mod-down (GPU digest only, like gold);
+    #   sb20: the smallest fp64-class primes (18 .. 22 bits), every one of the 8 the pool holds at logN 13.
     "sb30": dict(logN=13, scale_bits=30, num_scales=6, num_special_primes=2, is_secured=False),
     "sb45": dict(logN=13, scale_bits=45, num_scales=6, num_special_primes=2, is_secured=False),
+    "sb41": dict(logN=13, scale_bits=41, num_scales=6, num_special_primes=2, is_secured=False),
+    "sb41_16": dict(logN=16, scale_bits=41, num_scales=8, num_special_primes=4, is_secured=False),
+    "sb20": dict(logN=13, scale_bits=20, num_scales=8, num_special_primes=2, is_secured=False),
 }
 
 

@@ -102,6 +102,88 @@ def pick_primes(logN, n40=2, n60=1):
     return out
 
 
+SMALL_PRIME_LIMIT = 1 << 41     # csrc/ckks_ntt_core.h: rows whose prime is below it run the fp64 class, the others the integer class
+
+
+def pick_edge_primes(logN, n_top=2, n_bottom=2, n_small=1, n60=1):
+    """NTT-friendly primes (q = 1 mod 2N) at the edges of the two arithmetic classes, interleaved by class row by row:
+    the `n_top` largest below 2^41 (top of the fp64 class) alternating with the `n_bottom` smallest above 2^41 (bottom of
+    the integer class), then `n_small` fp64-class primes from just above 2^20 and `n60` just below 2^60."""
+    M = 2 << logN
+    top, q = [], SMALL_PRIME_LIMIT - 1
+    for _ in range(n_top):
+        q = P.next_ntt_prime(q, M, up=False)
+        top.append(q)
+        q -= 2
+    bottom, q = [], SMALL_PRIME_LIMIT + 1
+    for _ in range(n_bottom):
+        q = P.next_ntt_prime(q, M, up=True)
+        bottom.append(q)
+        q += 2
+    out = []
+    for i in range(max(n_top, n_bottom)):
+        out += top[i:i + 1] + bottom[i:i + 1]
+    q = (1 << 20) + 1
+    for _ in range(n_small):
+        q = P.next_ntt_prime(q, M, up=True)
+        out.append(q)
+        q += 2
+    q = (1 << 60) - 1
+    for _ in range(n60):
+        q = P.next_ntt_prime(q, M, up=False)
+        out.append(q)
+        q -= 2
+    return out
+
+
+def thue_morse(N):
+    """0 / 1 per index: the parity of its number of set bits.  Every butterfly pair (j, j + 2^k with bit k of j clear)
+    of every stage holds one index of each parity."""
+    j = np.arange(N, dtype=np.int64)
+    par = np.zeros(N, dtype=np.int64)
+    while j.any():
+        par ^= j & 1
+        j >>= 1
+    return par
+
+
+EDGE_PATTERNS = ("2q-1", "2q-1|0", "q-1", "lazy")
+
+
+def edge_operand(lim, pattern, seed=0, signed=False):
+    """[rows, N] int64 words that drive the transforms to their proven bounds:
+      "2q-1"    every word 2q - 1 (the largest forward and inverse sums);
+      "2q-1|0"  2q - 1 and 0 by the Thue-Morse parity of the index (the largest difference in every butterfly);
+      "q-1"     every word q - 1;
+      "lazy"    uniform random lazy words in [0, 2q).
+    signed=True (entries that accept the reference's signed-lazy words): the words of "2q-1" and "2q-1|0" become
+    +-(2q - 1) by the Thue-Morse parity, "lazy" uniform in (-2q, 2q)."""
+    rng = np.random.default_rng(seed)
+    tm = thue_morse(lim.N)
+    rows = []
+    for q in lim.q:
+        top = 2 * q - 1
+        if pattern == "2q-1":
+            v = np.where(tm == 1, -top, top) if signed else np.full(lim.N, top, dtype=np.int64)
+        elif pattern == "2q-1|0":
+            v = np.where(tm == 1, -top if signed else 0, top)
+        elif pattern == "q-1":
+            v = np.full(lim.N, q - 1, dtype=np.int64)
+        elif pattern == "lazy":
+            v = rng.integers(-top if signed else 0, 2 * q, size=lim.N, dtype=np.int64)
+        else:
+            raise ValueError(pattern)
+        rows.append(v.astype(np.int64))
+    return np.stack(rows)
+
+
+def redc62(x, q):
+    """The reference's lazy REDC62 of a non-negative integer x < q 2^62, in Python integers: (x + ((x k) mod R) q) / R
+    with k = -q^-1 mod R; the result lies in [0, 2q) and is congruent to x R^-1."""
+    k = (R * pow(R, -1, q) - 1) // q
+    return (x + ((x * k) % R) * q) >> 62
+
+
 def sha(arr) -> str:
     return hashlib.sha256(np.ascontiguousarray(arr).tobytes()).hexdigest()
 

@@ -273,3 +273,39 @@ def test_hot_kernels_use_no_scratch_memory_and_the_tracked_table_is_current():
     stale = {k: (sorted(tracked.get(k, [])), sorted({(r["vgprs"], r["scratch"], r["occupancy"]) for r in by[k]})) for k in seen
              if len(k) <= 57 and tracked.get(k) != {(r["vgprs"], r["scratch"], r["occupancy"]) for r in by[k]}}
     assert not stale, f"profiles/r06_kernel_resources.txt is stale (python tools/kernel_resources.py r06): {stale}"
+
+
+def test_stack_planes_class_split_at_two_to_the_41():
+    """The library splits the arithmetic classes at SMALL_PRIME_LIMIT = 2^41 exactly where the engine's Python does
+    (q >= 2^41: integer class): 2^41 - 65535 is fp64 class, 2^41 + 311297 integer class, on either side of a 60-bit prime."""
+    import numpy as np
+    from liberate_fhe_amd._native import lib
+    from tests.helpers import SMALL_PRIME_LIMIT
+    top, bottom, low2, p60 = (1 << 41) - 65535, (1 << 41) + 311297, (1 << 41) - 901119, 1152921504606830593
+    q = lambda *v: np.array(v, dtype=np.int64)
+    for logN in (13, 14, 16):
+        assert lib.lf_stack_planes(logN, 2, q(top, p60).ctypes.data) == 1
+        assert lib.lf_stack_planes(logN, 2, q(p60, top).ctypes.data) == 1
+        assert lib.lf_stack_planes(logN, 2, q(bottom, p60).ctypes.data) == 0         # both integer class
+        assert lib.lf_stack_planes(logN, 2, q(top, low2).ctypes.data) == 0           # both fp64 class
+        assert lib.lf_stack_planes(logN, 2, q(top, bottom).ctypes.data) == 1
+        assert lib.lf_stack_planes(logN, 2, q(SMALL_PRIME_LIMIT - 1, SMALL_PRIME_LIMIT).ctypes.data) == 1
+        assert lib.lf_stack_planes(logN, 2, q(SMALL_PRIME_LIMIT, SMALL_PRIME_LIMIT + 1).ctypes.data) == 0
+    assert top < SMALL_PRIME_LIMIT <= bottom and SMALL_PRIME_LIMIT == 1 << 41
+
+
+def test_edge_primes_sit_at_the_class_edges_and_interleave():
+    """tests/helpers.py:pick_edge_primes: NTT primes for the ring, the top of the fp64 class alternating with the bottom of
+    the integer class (nothing of either class between them and 2^41), then a ~2^20 prime and a 60-bit one."""
+    from liberate_fhe_amd.fhe.context import primes as P
+    from tests.helpers import SMALL_PRIME_LIMIT, pick_edge_primes
+    for logN in (12, 13, 14, 16, 17):
+        M = 2 << logN
+        got = pick_edge_primes(logN)
+        assert len(set(got)) == len(got) == 6 and all((x - 1) % M == 0 and P.is_prime(x) for x in got)
+        assert got[0] == P.next_ntt_prime(SMALL_PRIME_LIMIT - 1, M, up=False)
+        assert got[1] == P.next_ntt_prime(SMALL_PRIME_LIMIT + 1, M, up=True)
+        assert [x < SMALL_PRIME_LIMIT for x in got[:4]] == [True, False, True, False]
+        assert got[2] < got[0] < SMALL_PRIME_LIMIT < got[1] < got[3]
+        assert got[4] == P.next_ntt_prime((1 << 20) + 1, M, up=True) < (1 << 23) and (1 << 59) < got[5] < (1 << 60)
+    assert pick_edge_primes(13)[0] == pick_edge_primes(14)[0] == (1 << 41) - 65535

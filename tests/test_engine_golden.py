@@ -47,7 +47,7 @@ def check_config(engine, rec):
         assert digest(engine.cc_mult(prod, prod, evk)) == ops["cc_mult(prod,prod,evk)"]
 
 
-@pytest.mark.parametrize("name", ["small", "small_x2", "bronze", "silver", "sb30", "sb45"])
+@pytest.mark.parametrize("name", ["small", "small_x2", "bronze", "silver", "sb30", "sb45", "sb41", "sb20"])
 def test_checker_engine_reproduces_reference_digests(name):
     from liberate_fhe_amd.fhe import ckks_engine
     from tests.oracle_backend import OracleBackend
@@ -57,11 +57,14 @@ def test_checker_engine_reproduces_reference_digests(name):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", ["small", "small_x2", "bronze", "silver", "gold", "gold_x8", "platinum", "sb30", "sb45"])
+@pytest.mark.parametrize("name", ["small", "small_x2", "bronze", "silver", "gold", "gold_x8", "platinum", "sb30", "sb45",
+                                  "sb41", "sb41_16", "sb20"])
 def test_hip_engine_reproduces_reference_digests(name):
     """All four presets (platinum: logN 17, 6 special primes, a five-stage strided pass — the LDS-tiled fallback
     of the column kernels) and the other scale-prime widths: sb30 = 30-bit scale primes (fp64 class), sb45 =
-    45-bit scale primes (>= 2^41: the integer class for every limb)."""
+    45-bit scale primes (>= 2^41: the integer class for every limb), sb41 / sb41_16 = 41-bit scale primes that alternate
+    between the classes row by row at their edge (2^41 - 65535, 2^41 + 311297, ...; logN 13 and logN 16 with K = 4),
+    sb20 = the smallest fp64-class primes (18 .. 22 bits)."""
     from liberate_fhe_amd.fhe import ckks_engine
     rec = GOLD[name]
     eng = ckks_engine(devices=["cuda:0"] * rec["n_devices"], **rec["params"])
@@ -198,12 +201,13 @@ def test_ops_of_one_engine_alternating_between_two_streams_are_ordered_not_raced
 
 
 @pytest.mark.gpu
-def test_compact_key_halves_a_keys_memory_and_changes_no_result():
+@pytest.mark.parametrize("name", ["silver", "sb41"])
+def test_compact_key_halves_a_keys_memory_and_changes_no_result(name):
     """engine.compact_key(): the raw pack of a key the engine made is freed (the fused key switch reads the planes copy only);
     expand_key() restores it from the planes — integer-class rows byte for byte, fp64-class rows as the canonical residues of the
-    lazy words they held.  Same cc_mult / rotate words before, while compact, and after."""
+    lazy words they held.  Same cc_mult / rotate words before, while compact, and after.  sb41: the classes alternate row by row."""
     from liberate_fhe_amd.fhe import ckks_engine
-    eng = ckks_engine(devices=["cuda:0"], **GOLD["silver"]["params"])
+    eng = ckks_engine(devices=["cuda:0"], **GOLD[name]["params"])
     sk = eng.create_secret_key()
     evk = eng.create_evk(sk)
     rotk = eng.create_rotation_key(sk, 1)
@@ -313,6 +317,47 @@ def test_hip_engine_equals_checker_engine_on_fresh_seeds(name, n_dev):
         outs.append([digest(x) for x in (prod, deep, eng.rotate_single(deep, rotk), eng.conjugate(a, conjk),
                                          eng.rescale(a), eng.cc_sub(a, b), eng.cc_mult(a, b, evk, relin=False))])
     assert outs[0] == outs[1]
+
+
+def _class_edge_results(eng, levels):
+    """Digests of every hot op at each level of `levels`: cc_mult with and without relinearization, rotate_single, conjugate,
+    rescale and the two batched entries.  The last level of each chain keeps one fp64-class scale limb beside integer-class rows."""
+    evk, rotk = synth.key_switch_key(eng, 113), synth.key_switch_key(eng, 114, origin="rotation key:5")
+    conjk = synth.key_switch_key(eng, 115, origin="conjugation key")
+    out = []
+    for level in levels:
+        a, b = synth.ciphertext(eng, 120 + level, level), synth.ciphertext(eng, 140 + level, level)
+        res = [eng.rotate_single(a, rotk), eng.conjugate(b, conjk)] + eng.rotate_single_batch([a, b, b], rotk)
+        if level < eng.num_levels - 1:          # the last level has no multiplication left
+            res += [eng.cc_mult(a, b, evk), eng.cc_mult(a, b, evk, relin=False), eng.rescale(a)]
+            res += eng.cc_mult_batch([(a, b), (b, a), (a, a)], evk)
+        out.append([digest(x) for x in res])
+    return out
+
+
+# sb41: scale primes alternate 2^41 - 65535 (fp64 class), 2^41 + 311297 (integer class), ...; level 4 leaves q4 (fp64) beside
+# q5 and the base prime, the last level with an fp64-class row.  sb20: 18 .. 22-bit scale primes (fp64 class); level 7 (the
+# last) leaves q7 beside the base prime, level 6 is the last one with a multiplication.
+CLASS_EDGE_LEVELS = {"sb41": (0, 2, 4), "sb20": (0, 3, 6, 7)}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["sb41", "sb20"])
+@pytest.mark.parametrize("n_dev", [1, 2])
+def test_hip_engine_equals_checker_engine_at_the_class_edges(name, n_dev):
+    """Fresh seeds on the class-edge chains: HIP engine vs the oracle composition, on one and on two logical devices (the
+    partition then splits the interleaved rows between them)."""
+    from liberate_fhe_amd.fhe import ckks_engine
+    from tests.oracle_backend import OracleBackend
+    params = GOLD[name]["params"]
+    hip = ckks_engine(devices=["cuda:0"] * n_dev, **params)
+    chk = ckks_engine(devices=["cpu"] * n_dev, backend=OracleBackend(), **params)
+    levels = CLASS_EDGE_LEVELS[name]
+    assert levels[-1] == hip.num_levels - (2 if name == "sb41" else 1)
+    assert hip.ctx.q[levels[-1]] < (1 << 41) and all(q >= (1 << 41) for q in hip.ctx.q[levels[-1] + 1:])
+    got, want = _class_edge_results(hip, levels), _class_edge_results(chk, levels)
+    for level, g, w in zip(levels, got, want):
+        assert g == w, level
 
 
 @pytest.mark.gpu
@@ -678,7 +723,7 @@ def test_c3_silver_cc_mult_decode_within_2_pow_minus_30_of_the_checker():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", ["silver", "sb45"])
+@pytest.mark.parametrize("name", ["silver", "sb45", "sb41"])
 def test_hip_native_op_entries_equal_the_step_by_step_engine(name):
     """lf_cc_mult_evk / lf_switch_key (one native call per op over an lf_ks_plan) against the same engine with the entries
     switched off, i.e. the Python orchestration of the individual steps — levels 0, 1 and a deep one, rotate and conjugate, and
@@ -879,7 +924,7 @@ def test_key_switch_extension_in_horner_form_equals_the_sum_form(params):
 @pytest.mark.gpu
 @pytest.mark.parametrize("params", [dict(logN=13, num_scales=9, num_special_primes=2, is_secured=False), dict(logN=14), dict(logN=15, num_special_primes=2),
                                     dict(logN=16, num_special_primes=4), dict(logN=13, scale_bits=45, num_scales=6, num_special_primes=4, is_secured=False),
-                                    dict(logN=17, num_scales=11, num_special_primes=3, is_secured=False)])
+                                    dict(logN=17, num_scales=11, num_special_primes=3, is_secured=False), GOLD["sb41"]["params"]])
 def test_extended_digits_in_planes_format_equal_raw_words(params):
     """Between the halves of a key switch the fp64-class rows of the scratch hold 6-byte words in two planes (lf_tune
     LF_TUNE_DIGIT_PLANES = 1, the default: ks_ext_cols or the LDS-tiled ks_ext_pass1 (logN 17; LF_TUNE_KS_EXT_COLS_MAX = 0) ->
@@ -893,10 +938,13 @@ def test_extended_digits_in_planes_format_equal_raw_words(params):
     try:
         # (more: LF_TUNE_MORE_PLANES — bit 0 the sums between inner product, tiled inverse pass and column pass, bit 1 cc_mult's
         # operand stack between the rescale-NTT, the product pass and the inner product's fold — 6-byte words there as well)
-        for planes, cols_max, more in ((1, 5, 3), (0, 5, 3), (1, 0, 3), (0, 0, 0), (1, 5, 0), (1, 5, 1), (1, 5, 2), (1, 0, 1), (1, 5, 3)):
+        # (digits: LF_TUNE_INTT_DIGITS — the digits of x1 * y1 formed inside the last inverse pass or in two launches)
+        for planes, cols_max, more, digits in ((1, 5, 3, 1), (0, 5, 3, 1), (1, 0, 3, 1), (0, 0, 0, 1), (1, 5, 0, 1), (1, 5, 1, 1),
+                                               (1, 5, 2, 1), (1, 0, 1, 1), (1, 5, 3, 0), (0, 0, 0, 0), (1, 5, 3, 1)):
             assert lib.lf_tune(3, planes) in (0, 1)
             lib.lf_tune(1, cols_max)
             assert lib.lf_tune(5, more) in (0, 1, 2, 3)
+            assert lib.lf_tune(2, digits) in (0, 1)
             res = []
             for level in (0, 2):
                 a, b = synth.ciphertext(eng, 50 + level, level), synth.ciphertext(eng, 60 + level, level)
@@ -907,6 +955,7 @@ def test_extended_digits_in_planes_format_equal_raw_words(params):
         lib.lf_tune(3, 1)
         lib.lf_tune(1, 5)
         lib.lf_tune(5, 3)
+        lib.lf_tune(2, 1)
     assert all(o == outs[0] for o in outs)
     assert lib.lf_tune(3, -1) == 1 and lib.lf_tune(3, 2) == 1 and lib.lf_tune(3, -1) == 1      # query; out of range: unchanged
 

@@ -163,7 +163,8 @@ int lf_mont_sub(const int64_t *a, const int64_t *b, int64_t *c, int rows, int64_
 #define LF_NTT_PLANES 16
 #define LF_STACK_PLANES 4
 /* 1 when internal stacks of the rows [0, rows) of q_host (HOST) keep fp64-class rows as planes: lf_tune(LF_TUNE_DIGIT_PLANES)
- * is on, 13 <= logN <= 24, and the rows hold primes of both arithmetic classes.  (The engine-op entries ask this themselves.) */
+ * is on, 13 <= logN <= 17 (a column pass of at most 5 stages: the ring degrees where lf_rescale_ntt accepts LF_NTT_PLANES), and
+ * the rows hold primes of both arithmetic classes; 0 otherwise.  (The engine-op entries ask this themselves.) */
 int lf_stack_planes(int logN, int rows, const int64_t *q_host);
 
 /* The auxiliary table from the Montgomery-form compact table mont[rows][N]: out[rows][2N] (8-byte words).
@@ -225,7 +226,8 @@ int lf_intt(int64_t *a, int batch, int rows, int logN, const int64_t *ipsi_br, c
  *   dst[p] = intt(a[p] * b[p]),  polynomial p of `a` / `b` at a + p * a_stride / b + p * b_stride (words), dst [batch][rows][N].
  * cc_mult's third tensor component x1 * y1 (ckks_engine.py:1099-1101, 1129) enters the key switch this way.  Requires
  * LF_NTT_RELAXED (tail >= 2) and logN >= 13; with LF_NTT_PLAIN the fp64-class limbs hold plain residues and get a plain
- * product, integer-class limbs Montgomery-form words (below 2q) and the REDC62 product — lf_tensor's d2 (plain = 1). */
+ * product, integer-class limbs Montgomery-form words (below 2q) and the REDC62 product — lf_tensor's d2 (plain = 1).
+ * LF_NTT_PLANES (factors in the planes format) at logN <= 17 only, like lf_stack_planes. */
 int lf_intt_mul(int64_t *dst, const int64_t *a, int64_t a_stride, const int64_t *b, int64_t b_stride, int batch, int rows, int logN,
                 const int64_t *ipsi_br, const double *ipsi_dp, const int64_t *q_host, const int64_t *Ninv, int tail, int flags,
                 const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, int device, void *stream);
@@ -285,7 +287,8 @@ int lf_ks_moddown(const int64_t *s, int64_t *out, const int64_t *addend, int ell
                   const int64_t *PiR, const double *PiP, const int64_t *Rs, const int64_t *ql, const int64_t *qh, const int64_t *kl,
                   const int64_t *kh, int device, void *stream);
 
-/* Fused key-switch core for two-pass ring degrees (logN >= 13): extend + NTT + inner product with the key +
+/* Fused key-switch core for two-pass ring degrees up to a column pass of 5 stages (13 <= logN <= 17; any other logN: LF_ERR_ARG,
+ * nothing launched — the same holds for lf_ks_core_batch, lf_ks_fwd, lf_ks_tail and lf_relin_*): extend + NTT + inner product with the key +
  * sum over digits + inverse NTT to canonical coefficients, i.e. lf_ks_extend -> lf_ntt -> lf_ks_inner ->
  * lf_intt(tail 2) (ckks_engine.py:707-743, 919, 931-934, 832-848) without materialising the extended digits.
  *   state      [*, N] Garner digits in storage order (output of lf_ks_digits, gathered)
@@ -436,7 +439,7 @@ int lf_intt_mul_digits(int64_t *scratch, const int64_t *a, int64_t a_stride, con
 
 /* cc_mult's opening (ckks_engine.py:1085-1093): rescale `count` (<= 8) polynomials and transform them, i.e.
  * lf_rescale_batch(in, row0, {x + i*rows*N}, ...) followed by lf_ntt(x, count, ...) with the same constants.
- * For two-pass ring degrees (logN 13..16) the rescale is evaluated inside the first NTT pass: no launch and no
+ * For two-pass ring degrees (logN 13..17) the rescale is evaluated inside the first NTT pass: no launch and no
  * trip through HBM of its own; other degrees run the two steps one after the other.  Same results either way. */
 int lf_rescale_ntt(const int64_t *const *in, const int64_t *const *row0, int count, int64_t *x, int rows, int logN,
                    const int64_t *scales, int64_t round_at, const int64_t *psi_br, const double *psi_dp,
@@ -449,7 +452,8 @@ int lf_rescale_ntt(const int64_t *const *in, const int64_t *const *row0, int cou
  * native call fills an lf_ks_plan once per (device, level) — everything that does not change from call to call — and
  * hands the operands and the key per call.  The entries enqueue exactly the steps above (lf_rescale_ntt, lf_intt_mul,
  * lf_ks_digits(_galois), lf_relin_core_batch / lf_ks_core, lf_ks_moddown_ws) on `stream` and return the first failure.
- * They apply when every limb of the level lives on this device (no exchange between the digits and their extension).
+ * They apply when every limb of the level lives on this device (no exchange between the digits and their extension), at the
+ * key switch's ring degrees 13 <= logN <= 17: a plan with another logN gets LF_ERR_ARG before anything is launched.
  * `rows` = ell + K limbs, ordinary first: the per-row vectors and twiddle tables are those of lf_ks_core.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct lf_ks_plan {

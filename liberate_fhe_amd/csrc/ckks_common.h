@@ -23,6 +23,9 @@ typedef __int128 i128;
 #define MAX_LIST_ROWS 250    // limb rows per call
 #define LF_BATCH_MAX 8       // operand sets per batched call
 #define NTT_TILE_LOG_MAX 12  // log2 of the largest LDS tile; transforms go up to logN = 2 * NTT_TILE_LOG_MAX
+// largest ring degree whose column pass has at most 5 stages: the planes stack (lf_stack_planes), the key-switch entries
+// (lf_ks_* / lf_relin_*) and the engine ops (lf_cc_mult_evk*, lf_switch_key*) go up to it and refuse larger ones
+#define KS_LOGN_MAX (NTT_TILE_LOG_MAX + 5)
 
 // ------------------------------------------------------------------------------------------------
 // Scalar arithmetic

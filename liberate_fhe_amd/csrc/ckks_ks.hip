@@ -153,7 +153,7 @@ __device__ __forceinline__ void ks_ext_body(i64 *sm, int b, const i64 *__restric
             longlong2 o;
             o.x = dp_to_word(dp_reduce(smd[PAD(L)], c.d.q, c.d.qinv));
             o.y = dp_to_word(dp_reduce(smd[PAD(L + 1)], c.d.q, c.d.qinv));
-            const i64 j = tile_gaddr(g, tile, L);   // even: words j, j + 1 are neighbours
+            const i64 j = tile_gaddr(g, tile, L);   // even: words j, j + 1 are neighbours (logC >= 7: the entries stop at KS_LOGN_MAX)
             if (kg.planes) {   // 8 + 4 bytes for the pair (digit_planes(): fwd_tile16<.., PLN> and the inner product read planes)
                 const lf_u2_t lo = {(unsigned)o.x, (unsigned)o.y};
                 *reinterpret_cast<lf_u2_t *>(reinterpret_cast<unsigned *>(row) + j) = lo;
@@ -724,7 +724,7 @@ bool digit_planes(int logN, const RowList &dp, const RowList &in) {
 
 }  // namespace
 extern "C" int lf_stack_planes(int logN, int rows, const int64_t *q_host) {
-    if (!g_digit_planes || !(g_more_planes & 2) || logN <= NTT_TILE_LOG_MAX || logN > 2 * NTT_TILE_LOG_MAX || !q_host || rows < 1) return 0;
+    if (!g_digit_planes || !(g_more_planes & 2) || logN <= NTT_TILE_LOG_MAX || logN > KS_LOGN_MAX || !q_host || rows < 1) return 0;
     int small = 0, large = 0;
     for (int r = 0; r < rows; ++r) ((uint64_t)q_host[r] < SMALL_PRIME_LIMIT ? small : large)++;
     return small && large ? 1 : 0;
@@ -929,7 +929,7 @@ int lf_ks_core_batch(const int64_t *state, int64_t state_stride, int nct, int np
                      int64_t row_off, int key_format, int64_t *tmp, int64_t *s, const int64_t *psi_br, const double *psi_dp,
                      const int64_t *ipsi_br, const double *ipsi_dp, const int64_t *Ninv, const int64_t *q_host, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, int device,
                      void *stream) {
-    if (nparts < 1 || rows < 1 || rows > MAX_LIST_ROWS || logN <= NTT_TILE_LOG_MAX || logN > 2 * NTT_TILE_LOG_MAX ||
+    if (nparts < 1 || rows < 1 || rows > MAX_LIST_ROWS || logN <= NTT_TILE_LOG_MAX || logN > KS_LOGN_MAX ||
         !q_host || !psi_dp || !ipsi_dp || !Ed || (nct != 1 && nct != 2 && nct != 4))
         return LF_ERR_ARG;
     if (int e = lf_set_device(device)) return e;
@@ -948,7 +948,7 @@ int lf_ks_core_batch(const int64_t *state, int64_t state_stride, int nct, int np
 int lf_ks_fwd(const int64_t *state, int nparts, int rows, int logN, const int64_t *desc, const int64_t *E, const double *Ed,
               int64_t *tmp, const int64_t *psi_br, const double *psi_dp, const int64_t *q_host, const int64_t *ql,
               const int64_t *qh, const int64_t *kl, const int64_t *kh, int device, void *stream) {
-    if (nparts < 0 || rows < 1 || rows > MAX_LIST_ROWS || logN <= NTT_TILE_LOG_MAX || logN > 2 * NTT_TILE_LOG_MAX ||
+    if (nparts < 0 || rows < 1 || rows > MAX_LIST_ROWS || logN <= NTT_TILE_LOG_MAX || logN > KS_LOGN_MAX ||
         !q_host || !psi_dp || !Ed)
         return LF_ERR_ARG;
     if (nparts == 0) return 0;
@@ -960,7 +960,7 @@ int lf_ks_tail(int nparts, int rows, int logN, const int64_t *ksk, int64_t part_
                int key_format, int64_t *tmp, int64_t *s, const int64_t *ipsi_br, const double *ipsi_dp, const int64_t *Ninv,
                const int64_t *q_host, const int64_t *ql, const int64_t *qh, const int64_t *kl,
                const int64_t *kh, int device, void *stream) {
-    if (nparts < 1 || rows < 1 || rows > MAX_LIST_ROWS || logN <= NTT_TILE_LOG_MAX || logN > 2 * NTT_TILE_LOG_MAX ||
+    if (nparts < 1 || rows < 1 || rows > MAX_LIST_ROWS || logN <= NTT_TILE_LOG_MAX || logN > KS_LOGN_MAX ||
         !q_host || !ipsi_dp)
         return LF_ERR_ARG;
     if (int e = lf_set_device(device)) return e;
@@ -977,7 +977,7 @@ int lf_relin_core_batch(const int64_t *state, int64_t state_stride, int nct, int
                         const int64_t *ipsi_br, const double *ipsi_dp, const int64_t *Ninv, const int64_t *x, int64_t x_ct_stride,
                         const int64_t *PR, int ell, const uint8_t *own, const int64_t *q_host,
                         const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, int device, void *stream) {
-    if (nparts < 1 || nparts > 254 || rows < 1 || rows > MAX_LIST_ROWS || logN <= NTT_TILE_LOG_MAX || logN > 2 * NTT_TILE_LOG_MAX ||
+    if (nparts < 1 || nparts > 254 || rows < 1 || rows > MAX_LIST_ROWS || logN <= NTT_TILE_LOG_MAX || logN > KS_LOGN_MAX ||
         !q_host || !psi_dp || !ipsi_dp || !Ed || (nct != 1 && nct != 2 && nct != 4) || !x || !PR || ell < 0 || ell > rows)
         return LF_ERR_ARG;
     if (int e = lf_set_device(device)) return e;
@@ -998,7 +998,7 @@ int lf_relin_fwd(const int64_t *state, int first, int nparts, int rows, int logN
                  const int64_t *q_host, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, int device,
                  void *stream) {
     if (first < 0 || nparts < 0 || first + nparts > 254 || rows < 1 || rows > MAX_LIST_ROWS || logN <= NTT_TILE_LOG_MAX ||
-        logN > 2 * NTT_TILE_LOG_MAX || !q_host || !psi_dp || !Ed)
+        logN > KS_LOGN_MAX || !q_host || !psi_dp || !Ed)
         return LF_ERR_ARG;
     if (nparts == 0) return 0;
     if (int e = lf_set_device(device)) return e;
@@ -1010,7 +1010,7 @@ int lf_relin_tail(int nparts, int rows, int logN, const int64_t *ksk, int64_t pa
                   int key_format, int64_t *tmp, int64_t *s, const int64_t *ipsi_br, const double *ipsi_dp, const int64_t *Ninv,
                   const int64_t *x, const int64_t *PR, int ell, const uint8_t *own, const int64_t *q_host, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, int device,
                   void *stream) {
-    if (nparts < 1 || nparts > 254 || rows < 1 || rows > MAX_LIST_ROWS || logN <= NTT_TILE_LOG_MAX || logN > 2 * NTT_TILE_LOG_MAX ||
+    if (nparts < 1 || nparts > 254 || rows < 1 || rows > MAX_LIST_ROWS || logN <= NTT_TILE_LOG_MAX || logN > KS_LOGN_MAX ||
         !q_host || !ipsi_dp || !x || !PR || ell < 0 || ell > rows)
         return LF_ERR_ARG;
     if (int e = lf_set_device(device)) return e;

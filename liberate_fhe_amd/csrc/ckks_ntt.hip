@@ -453,8 +453,10 @@ static int intt_impl(int64_t *a, const int64_t *src, const MulSrc *ms, int batch
     const bool mixed = dp.n && in.n;   // both classes in one launch per pass
     // LF_NTT_PLANES (product-on-load only): the factors are stacks whose fp64-class rows are planes (lf_rescale_ntt with the flag)
     const bool mpl = (flags & LF_NTT_PLANES) != 0;
-    if (mpl && !(ms && relaxed && plain && mixed && SB >= 1 && tl == NTT_TILE_LOG_MAX)) return LF_ERR_ARG;
-    if (ms) {
+    if (mpl && !(ms && relaxed && plain && mixed && SB >= 1 && tl == NTT_TILE_LOG_MAX && logN <= KS_LOGN_MAX)) return LF_ERR_ARG;
+    // above KS_LOGN_MAX no producer writes a planes stack (lf_stack_planes says 0): there is no other format to refuse, and a
+    // note there could only be a stale one on recycled memory
+    if (ms && logN <= KS_LOGN_MAX) {
         const int want = mpl ? LF_FMT_PLANES : LF_FMT_RAW;
         for (int t = 0; t < batch; ++t) {
             if (int e = lf_fmt_expect(src + t * ms->a_stride, ((size_t)rows << logN) * 8, want)) return e;

@@ -108,16 +108,37 @@ __device__ __forceinline__ void block_coords(const PassGeom &g, const RowList &r
 
 #define NTT_PRE ((1 << NTT_TILE_LOG_MAX) / (NTT_THREADS * 2))   // 16-byte prefetch registers per thread
 
+// Tile words L and L + 1 (L even) in global memory.  They are neighbours in the row — one 16-byte access — except in a
+// strided tile of ONE column (logC = 0: the column pass of logN 24, 12 stages), where word L + 1 lies a strided row
+// further on: two 8-byte accesses there (a block-uniform branch).
+__device__ __forceinline__ bool tile_pairs_split(const PassGeom &g) { return g.strided && g.logC == 0; }
+
+__device__ __forceinline__ longlong2 load_tile_pair(const i64 *row, const PassGeom &g, int tile, int L) {
+    if (tile_pairs_split(g)) {
+        longlong2 v;
+        v.x = row[tile_gaddr(g, tile, L)];
+        v.y = row[tile_gaddr(g, tile, L + 1)];
+        return v;
+    }
+    return *reinterpret_cast<const longlong2 *>(row + tile_gaddr(g, tile, L));
+}
+
+__device__ __forceinline__ void store_tile_pair(i64 *row, const PassGeom &g, int tile, int L, const longlong2 &v) {
+    if (tile_pairs_split(g)) {
+        row[tile_gaddr(g, tile, L)] = v.x;
+        row[tile_gaddr(g, tile, L + 1)] = v.y;
+        return;
+    }
+    *reinterpret_cast<longlong2 *>(row + tile_gaddr(g, tile, L)) = v;
+}
+
 // issue the global loads of one tile into registers (16 B per lane); consumed by stash_tile()
 __device__ __forceinline__ void prefetch_tile(longlong2 (&pre)[NTT_PRE], const i64 *row, const PassGeom &g, int tile) {
     const int T = 1 << g.tl;
 #pragma unroll
     for (int v = 0; v < NTT_PRE; ++v) {
         const int L = (threadIdx.x + v * NTT_THREADS) * 2;
-        if (L < T) {
-            const i64 *src = row + tile_gaddr(g, tile, L);
-            pre[v] = *reinterpret_cast<const longlong2 *>(src);
-        }
+        if (L < T) pre[v] = load_tile_pair(row, g, tile, L);
     }
 }
 
@@ -663,14 +684,14 @@ __device__ __forceinline__ RowDp make_dp(const RowMod &m) {
     return d;
 }
 
-// LDS tile -> global, 16 B per lane
+// LDS tile -> global, 16 B per lane (store_tile_pair)
 __device__ __forceinline__ void store_tile_raw(const i64 *sm, i64 *row, const PassGeom &g, int tile) {
     const int T = 1 << g.tl;
     for (int L = threadIdx.x * 2; L < T; L += NTT_THREADS * 2) {
         longlong2 v;
         v.x = sm[PAD(L)];
         v.y = sm[PAD(L + 1)];
-        *reinterpret_cast<longlong2 *>(row + tile_gaddr(g, tile, L)) = v;
+        store_tile_pair(row, g, tile, L, v);
     }
 }
 
@@ -1010,7 +1031,7 @@ __device__ __forceinline__ void fwd_pass_body(i64 *sm, int b, i64 *__restrict__ 
                 longlong2 o;
                 o.x = dp_to_word(dp_reduce(smd[PAD(L)], md, mi));
                 o.y = dp_to_word(dp_reduce(smd[PAD(L + 1)], md, mi));
-                *reinterpret_cast<longlong2 *>(row + tile_gaddr(g, cur_tile, L)) = o;
+                store_tile_pair(row, g, cur_tile, L, o);
             }
         } else {
             // integer class (or a signed-lazy tile of the fp64 class)
@@ -1518,7 +1539,7 @@ __device__ __forceinline__ void inv_pass_body(i64 *sm, int b, const i64 *src, i6
                 longlong2 ov;
                 ov.x = o[0];
                 ov.y = o[1];
-                *reinterpret_cast<longlong2 *>(row + tile_gaddr(g, cur_tile, L)) = ov;
+                store_tile_pair(row, g, cur_tile, L, ov);
             }
         } else {
             if (odd || DP) run_inv_stages<ArithInt<true>, false>(sm, g, cur_tile, c);   // rare: compact stage-by-stage loop
@@ -1539,7 +1560,7 @@ __device__ __forceinline__ void inv_pass_body(i64 *sm, int b, const i64 *src, i6
                 longlong2 v;
                 v.x = t[0];
                 v.y = t[1];
-                *reinterpret_cast<longlong2 *>(row + tile_gaddr(g, cur_tile, L)) = v;
+                store_tile_pair(row, g, cur_tile, L, v);
             }
         }
     }

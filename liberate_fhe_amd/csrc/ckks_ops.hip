@@ -15,7 +15,7 @@ extern int lf_g_intt_digits;   // ckks_ks.hip (lf_tune)
 extern "C" {
 
 static int plan_ok(const lf_ks_plan *p) {
-    return p && p->logN > NTT_TILE_LOG_MAX && p->logN <= 2 * NTT_TILE_LOG_MAX && p->ell >= 1 && p->K >= 1 && p->K <= KS_MAX_K &&
+    return p && p->logN > NTT_TILE_LOG_MAX && p->logN <= KS_LOGN_MAX && p->ell >= 1 && p->K >= 1 && p->K <= KS_MAX_K &&
            p->nparts >= 1 && p->dig_nparts >= 0 && p->max_nct >= 1 && p->ql && p->qh && p->kl && p->kh && p->_2q && p->Rs && p->Ninv && p->q_host &&
            p->psi && p->ipsi && p->psi_dp && p->ipsi_dp && p->dig_desc && p->dig_tab && p->ext_desc && p->E && p->Ed && p->PiR &&
            p->state && p->ext && p->sum && p->md_ws;

@@ -61,6 +61,19 @@ class Limbs:
             self._mont = (psi, ipsi)
         return self._mont
 
+    def select(self, idx):
+        """The limb set of the rows `idx` of this one (no table is recomputed: rows are independent)."""
+        import copy
+        idx = list(idx)
+        sub = copy.copy(self)
+        sub.q, sub.k, sub.root = ([v[i] for i in idx] for v in (self.q, self.k, self.root))
+        sub.rows = len(idx)
+        for name in ("ql", "qh", "kl", "kh", "_2q", "Rs", "Ninv", "psi_plain", "ipsi_plain"):
+            if getattr(self, name) is not None:
+                setattr(sub, name, np.ascontiguousarray(getattr(self, name)[idx]))
+        sub._mont = None if self._mont is None else tuple(np.ascontiguousarray(t[idx]) for t in self._mont)
+        return sub
+
     def mont_args(self):
         return self.ql, self.qh, self.kl, self.kh
 

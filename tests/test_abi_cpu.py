@@ -206,6 +206,63 @@ def test_stack_planes_query_follows_the_primes_and_the_knobs():
         lib.lf_tune(3, 1)
         lib.lf_tune(5, 3)
     assert lib.lf_stack_planes(16, 3, q(mixed)) == 1
+    # only where lf_rescale_ntt accepts LF_NTT_PLANES: a column pass of at most 5 stages (logN <= 17)
+    assert lib.lf_stack_planes(17, 3, q(mixed)) == 1
+    for logN in range(18, lib.lf_limits(4) + 1):
+        assert lib.lf_stack_planes(logN, 3, q(mixed)) == 0, logN
+    assert lib.lf_stack_planes(lib.lf_limits(4) + 1, 3, q(mixed)) == 0
+
+
+def test_engine_ops_and_key_switch_refuse_ring_degrees_above_17():
+    """The key switch and the engine ops built on it run at 13 <= logN <= 17 (csrc/ckks_common.h KS_LOGN_MAX: the extension
+    pass moves words in neighbouring pairs, and cc_mult's stack planes need a column pass of at most 5 stages).  At logN 18 ..
+    24 — ring degrees lf_ntt does accept — every such entry returns LF_ERR_ARG from its arguments alone, before anything is
+    launched: checked here without a GPU, on pointers that are never dereferenced (a plan with every pointer non-null and
+    consistent counts, so that only its logN can fail the check; no call here is one that would pass it)."""
+    import ctypes
+    import numpy as np
+    from liberate_fhe_amd._native import lib, KsPlan
+    LF_ERR_ARG = 10001
+    assert lib.lf_limits(4) == 24
+    dummy = ctypes.c_void_p(64)
+    arr = (ctypes.c_void_p * 4)(64, 64, 64, 64)
+    q_host = np.array([(1 << 41) - 65535, (1 << 60) - 93, (1 << 60) - 173], dtype=np.int64)
+    ell, K = 2, 1
+    for logN in (18, 20, 24):
+        plan = KsPlan()
+        plan.logN, plan.ell, plan.K, plan.nparts, plan.dig_nparts, plan.max_nct = logN, ell, K, 2, 2, 4
+        for name, typ in KsPlan._fields_:
+            if typ is ctypes.c_void_p:
+                setattr(plan, name, 64)
+        plan.q_host = q_host.ctypes.data
+        assert all(getattr(plan, n) for n, t in KsPlan._fields_ if t is ctypes.c_void_p)
+        p = ctypes.byref(plan)
+        assert lib.lf_cc_mult_evk(p, arr, arr, dummy, 0, 0, 0, 0, dummy, dummy, None) == LF_ERR_ARG, logN
+        assert lib.lf_cc_mult_evk_batch(p, 2, arr, arr, dummy, 0, 0, 0, 0, arr, arr, None) == LF_ERR_ARG, logN
+        assert lib.lf_cc_mult_evk_pre(p, arr, arr, 3, None) == LF_ERR_ARG, logN
+        assert lib.lf_cc_mult_evk_post(p, dummy, 0, 0, 0, 0, dummy, dummy, 3, None) == LF_ERR_ARG, logN
+        assert lib.lf_switch_key(p, dummy, dummy, 0, 0, dummy, 0, 0, 0, 0, dummy, dummy, None) == LF_ERR_ARG, logN
+        assert lib.lf_switch_key_batch(p, 2, arr, arr, 0, 0, dummy, 0, 0, 0, 0, arr, arr, None) == LF_ERR_ARG, logN
+        assert lib.lf_switch_key_pre(p, dummy, 0, 0, None) == LF_ERR_ARG, logN
+        assert lib.lf_switch_key_post(p, dummy, 0, 0, dummy, 0, 0, 0, 0, dummy, dummy, 3, None) == LF_ERR_ARG, logN
+        assert lib.lf_ks_plan_fwd(p, dummy, 0, 1, 1, None) == LF_ERR_ARG, logN
+        # the key switch's own entries
+        rows, qh = ell + K, q_host.ctypes.data
+        assert lib.lf_ks_fwd(dummy, 1, rows, logN, dummy, dummy, dummy, dummy, dummy, dummy, qh, dummy, dummy, dummy, dummy,
+                             0, None) == LF_ERR_ARG, logN
+        assert lib.lf_ks_tail(1, rows, logN, dummy, 0, 0, 0, 0, dummy, dummy, dummy, dummy, dummy, qh, dummy, dummy, dummy,
+                              dummy, 0, None) == LF_ERR_ARG, logN
+        assert lib.lf_ks_core(dummy, 1, rows, logN, dummy, dummy, dummy, dummy, 0, 0, 0, 0, dummy, dummy, dummy, dummy, dummy,
+                              dummy, dummy, qh, dummy, dummy, dummy, dummy, 0, None) == LF_ERR_ARG, logN
+        assert lib.lf_ks_core_batch(dummy, 0, 1, 1, rows, logN, dummy, dummy, dummy, dummy, 0, 0, 0, 0, dummy, dummy, dummy,
+                                    dummy, dummy, dummy, dummy, qh, dummy, dummy, dummy, dummy, 0, None) == LF_ERR_ARG, logN
+        assert lib.lf_relin_fwd(dummy, 0, 1, rows, logN, dummy, dummy, dummy, dummy, dummy, dummy, dummy, qh, dummy, dummy,
+                                dummy, dummy, 0, None) == LF_ERR_ARG, logN
+        assert lib.lf_relin_tail(1, rows, logN, dummy, 0, 0, 0, 0, dummy, dummy, dummy, dummy, dummy, dummy, dummy, ell,
+                                 dummy, qh, dummy, dummy, dummy, dummy, 0, None) == LF_ERR_ARG, logN
+        assert lib.lf_relin_core_batch(dummy, 0, 1, 1, rows, logN, dummy, dummy, dummy, dummy, 0, 0, 0, 0, dummy, dummy,
+                                       dummy, dummy, dummy, dummy, dummy, dummy, 0, dummy, ell, dummy, qh, dummy, dummy, dummy,
+                                       dummy, 0, None) == LF_ERR_ARG, logN
 
 
 def test_clock_probe_checks_its_arguments_on_the_host():

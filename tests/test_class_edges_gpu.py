@@ -221,8 +221,14 @@ def test_relaxed_forward_on_signed_lazy_words(logN):
     +-(2q - 1): residues equal to the oracle's transform mod q (PLAIN: fp64-class rows skip Rs), as canonical words — lazy
     words below 2q on the integer-class rows of a one-pass (logN 12) transform."""
     lim = edge_limbs(logN)
-    s = Setup(lim)
-    x = edge_batch(lim, 40 + logN, signed=True)
+    check_relaxed_forward(Setup(lim), edge_batch(lim, 40 + logN, signed=True), EDGE_PATTERNS)
+
+
+def check_relaxed_forward(s, x, names):
+    """The body of test_relaxed_forward_on_signed_lazy_words on the operands x [batch, rows, N], polynomial b named names[b]
+    (also run at the ring degrees above 17 by tests/test_large_rings_gpu.py)."""
+    lim = s.lim
+    logN = lim.logN
     canon = _mod_rows(x, s.q_host)
     small = s.q_host < SMALL_PRIME_LIMIT
     # canonical words, except the integer-class rows of a one-pass transform (logN <= 12): lazy words in [0, 2q)
@@ -230,11 +236,11 @@ def test_relaxed_forward_on_signed_lazy_words(logN):
     limit = np.where(small | (logN > 12), s.q_host, 2 * s.q_host)[None, :, None]
     got = s.ntt(x, flags=LF_NTT_RELAXED)
     assert (got >= 0).all() and (got < limit).all()
-    for b, p in enumerate(EDGE_PATTERNS):
+    for b, p in enumerate(names):
         assert (_mod_rows(got[b], s.q_host) == _mod_rows(s.o_ntt(canon[b]), s.q_host)).all(), f"relaxed {p}"
     got = s.ntt(x, Rs=s.Rs, flags=LF_NTT_RELAXED | LF_NTT_PLAIN)
     assert (got >= 0).all() and (got < limit).all()
-    for b, p in enumerate(EDGE_PATTERNS):
+    for b, p in enumerate(names):
         want = np.where(small[:, None], s.o_ntt(canon[b]), s.o_ntt(canon[b], enter=True))
         assert (_mod_rows(got[b], s.q_host) == _mod_rows(want, s.q_host)).all(), f"relaxed | plain {p}"
 
@@ -244,14 +250,21 @@ def test_relaxed_inverse_at_the_documented_input_bound(logN):
     """A relaxed inverse transform (tails 2 and 3) on the largest words include/ckks_hip.h promises: 2^46 - 1 on fp64-class
     rows (every word, and alternating with 0 by the Thue-Morse parity), 2q - 1 on integer-class rows: the oracle's chain
     of the residues."""
-    lim = edge_limbs(logN)
-    s = Setup(lim)
+    check_relaxed_inverse(Setup(edge_limbs(logN)), seed=logN)
+
+
+def check_relaxed_inverse(s, seed, kinds=(0, 1, 2)):
+    """The body of test_relaxed_inverse_at_the_documented_input_bound, on the operands `kinds` of: 0 every word at the bound,
+    1 the bound alternating with 0 by the Thue-Morse parity, 2 uniform random words below it (also run at the ring degrees
+    above 17 by tests/test_large_rings_gpu.py)."""
+    lim = s.lim
     small = s.q_host < SMALL_PRIME_LIMIT
     top = np.where(small, RELAXED_INV_DP_BOUND - 1, 2 * s.q_host - 1)[:, None]
     tm = thue_morse(lim.N)[None, :]
-    rng = np.random.default_rng(logN)
-    rnd = np.stack([rng.integers(0, int(t), size=lim.N, dtype=np.int64) for t in top[:, 0]])
-    x = np.stack([np.broadcast_to(top, (lim.rows, lim.N)), np.where(tm == 1, 0, top), rnd]).astype(np.int64)
+    rng = np.random.default_rng(seed)
+    make = (lambda: np.broadcast_to(top, (lim.rows, lim.N)), lambda: np.where(tm == 1, 0, top),
+            lambda: np.stack([rng.integers(0, int(t), size=lim.N, dtype=np.int64) for t in top[:, 0]]))
+    x = np.stack([make[k]() for k in kinds]).astype(np.int64)
     canon = _mod_rows(x, s.q_host)
     for tail in (2, 3):
         got = s.intt(x, tail, flags=LF_NTT_RELAXED)

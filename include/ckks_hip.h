@@ -505,6 +505,25 @@ int lf_cc_mult_evk_batch(const lf_ks_plan *plan, int nct, const int64_t *const *
                          int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format, int64_t *const *out0,
                          int64_t *const *out1, void *stream);
 
+/* Hoisted rotations: ONE ciphertext (c0, c1) rotated under nr >= 1 keys, key i with the odd exponent p_host[i] < 2N (HOST array;
+ * ksk / out0 / out1: HOST arrays of nr device pointers, keys addressed as in lf_ks_inner, all with the same strides and format).
+ * X -> X^p permutes the NTT slots: NTT(a(X^p))[k] = NTT(a)[pi_p(k)], pi_p(k) = brev(((2 brev(k) + 1) p mod 2N - 1) / 2).  So the
+ * digits of c1 are formed, extended and transformed ONCE; rotation i reads them gathered by pi_{p_i}.  Result i has exactly the words
+ * of: c1' = c1 made canonical (gal_canonical: make_unsigned + reduce_2q; no permutation) -> per digit pre_extend, extend, exact
+ * forward NTT -> gathered by pi_{p_i} -> mont_mult with key i's part, mont_add over the digits, intt_exit_reduce -> mod-down with
+ * addend c0(X^{p_i}) made canonical as rotate_single does.  These are NOT rotate_single's words (extending the digits does not
+ * commute with the sign flips of X -> X^p: the two differ by key-switch noise and decrypt alike), except for p = 1, where they are.
+ * Enqueued: lf_ks_digits_galois (gal_pinv = 1) and lf_ks_fwd once, then per group of 4, 2 or 1 keys one inner-product launch over
+ * the shared digits and the inverse NTT of the group's sums (plan->sum holds max_nct pairs: groups of up to min(4, max_nct) keys),
+ * and one mod-down per rotation.  The digits stay in the plan's first ext slot for every group; the sums' inverse transform
+ * passes through the ext slots behind it, or, where they are too small (two digits and four keys, a plan of max_nct 1),
+ * through `ws` of at least lf_rotate_hoisted_ws_words(plan) words (0: ws may be NULL).  LF_ERR_ARG before any launch for a
+ * plan lf_switch_key refuses, nr < 1, a NULL pointer, an even exponent or one outside (0, 2N), or a workspace too small. */
+int64_t lf_rotate_hoisted_ws_words(const lf_ks_plan *plan);
+int lf_rotate_hoisted(const lf_ks_plan *plan, const int64_t *c0, const int64_t *c1, int nr, const int64_t *p_host, int gal_canonical,
+                      const int64_t *const *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format, int64_t *ws,
+                      int64_t ws_words, int64_t *const *out0, int64_t *const *out1, void *stream);
+
 /* The halves of an op around the digit exchange of a limb-sharded engine (one process per GPU; the reference gathers every
  * digit on every GPU through the host before it extends any, ckks_engine.py:778-829).  The plan describes THIS rank's rows
  * at the level (dig_nparts = the digits it owns, nparts = all digits, state = its own digit rows):

@@ -704,6 +704,120 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NCT ==
     }
 }
 
+// ---- K3 of hoisted rotations (lf_rotate_hoisted): ONE ciphertext's extended digits, NR keys with an exponent each ----------
+// X -> X^p permutes the NTT slots: NTT(a(X^p))[k] = NTT(a)[pi_p(k)], pi_p(k) = brev(((2 brev(k) + 1) p mod 2N - 1) / 2) (the forward
+// transform stores the evaluation at psi^(2 brev(k) + 1) at index k).  So the digits of c1, extended and transformed ONCE, serve every
+// rotation: key i reads them gathered by pi_{p_i}.  pi maps every aligned block of 2^m slots onto an aligned block, permuted inside:
+// the thread's pair (j0, j0 + 1) is the pair at pi(j0) & ~1, its two words swapped where pi(j0) is odd, and the 64 pairs of a wave
+// are one aligned run of 128 slots under every p — the NR keys of a group read the same runs, and ext crosses HBM about once per group.
+// pi is computed in registers (two bit reversals, a multiply, a mask per pair and key: issue slots this HBM-bound launch has spare).
+struct HoistKeys {
+    const i64 *ksk[4];   // key i, at its first part (row_off and the part / component strides are those of every key)
+    unsigned p[4];       // its exponent (odd, < 2N)
+};
+
+template <int NR, bool PLANES, bool DPL>   // DPL: fp64-class rows of `ext` in planes format (digit_planes())
+__global__ void __launch_bounds__(256) ks_inner_hoist_kernel(const i64 *__restrict__ ext, HoistKeys hk, i64 part_stride, i64 comp_stride,
+                                                             i64 row_off, i64 *__restrict__ s, int nparts, int rows, int logN, int spl,
+                                                             const i64 *__restrict__ ql, const i64 *__restrict__ qh,
+                                                             const i64 *__restrict__ kl, const i64 *__restrict__ kh) {
+    const int r = blockIdx.y;
+    const i64 N = (i64)1 << logN;
+    const i64 j0 = (i64)blockIdx.x * 512 + threadIdx.x * 2;
+    if (j0 >= N) return;
+    const RowMod m = load_mod(ql, qh, kl, kh, r);
+    const unsigned sh = 32u - (unsigned)logN, mask = (2u << logN) - 1u;
+    const unsigned bj = (2u * (__builtin_bitreverse32((unsigned)j0) >> sh) + 1u);
+    unsigned src[NR];   // first slot of the source pair of key i
+    bool sw[NR];        // its words swapped
+#pragma unroll
+    for (int i = 0; i < NR; ++i) {
+        const unsigned t = (bj * hk.p[i]) & mask;   // (2 brev(j0) + 1) p mod 2N: odd
+        const unsigned mi = __builtin_bitreverse32((t - 1u) >> 1) >> sh;
+        src[i] = mi & ~1u;
+        sw[i] = (mi & 1u) != 0;
+    }
+    const i64 ct_s = 2 * (i64)rows * N;   // words between the keys' output pairs
+    const i64 krow = (row_off + r) * N;
+    if (m.q < SMALL_PRIME_LIMIT) {
+        const RowDp d = make_dp(m);
+        double acc[NR][2][2];
+#pragma unroll
+        for (int i = 0; i < NR; ++i) acc[i][0][0] = acc[i][0][1] = acc[i][1][0] = acc[i][1][1] = 0.0;
+#pragma unroll KI_UNROLL
+        for (int p = 0; p < nparts; ++p) {
+            const i64 *er = ext + ((i64)p * rows + r) * N;
+#pragma unroll
+            for (int i = 0; i < NR; ++i) {
+                double xa, xb;
+                ld_pair_dp(er, (i64)src[i], N, DPL ? 1 : 0, xa, xb);
+                const double x0 = sw[i] ? xb : xa, x1 = sw[i] ? xa : xb;
+                const i64 *kr = hk.ksk[i] + krow + (i64)p * part_stride;
+                double k0x, k0y, k1x, k1y;
+                if (PLANES) {   // 16 + 8 bytes for both components (see lf_key_planes)
+                    const lf_u4_t l = __builtin_nontemporal_load(reinterpret_cast<const lf_u4_t *>(reinterpret_cast<const unsigned *>(kr) + 2 * j0));
+                    const lf_u2_t h = __builtin_nontemporal_load(reinterpret_cast<const lf_u2_t *>(reinterpret_cast<const unsigned *>(kr + comp_stride) + j0));
+                    k0x = dp_from_planes(l.x, h.x & 0xffffu), k0y = dp_from_planes(l.y, h.x >> 16);
+                    k1x = dp_from_planes(l.z, h.y & 0xffffu), k1y = dp_from_planes(l.w, h.y >> 16);
+                } else {
+                    const longlong2 k0 = ld_nt(kr + j0);
+                    const longlong2 k1 = ld_nt(kr + j0 + comp_stride);
+                    k0x = dp_from_word(k0.x), k0y = dp_from_word(k0.y), k1x = dp_from_word(k1.x), k1y = dp_from_word(k1.y);
+                }
+                acc[i][0][0] += dp_mulmod_bal(x0, k0x, d);
+                acc[i][0][1] += dp_mulmod_bal(x1, k0y, d);
+                acc[i][1][0] += dp_mulmod_bal(x0, k1x, d);
+                acc[i][1][1] += dp_mulmod_bal(x1, k1y, d);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < NR; ++i)
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                longlong2 o;
+                o.x = dp_to_word(dp_reduce(acc[i][c][0], d.q, d.qinv));
+                o.y = dp_to_word(dp_reduce(acc[i][c][1], d.q, d.qinv));
+                i64 *srow = s + i * ct_s + ((i64)c * rows + r) * N;
+                if (spl) {
+                    const lf_u2_t l = {(unsigned)o.x, (unsigned)o.y};
+                    *reinterpret_cast<lf_u2_t *>(reinterpret_cast<unsigned *>(srow) + j0) = l;
+                    *reinterpret_cast<unsigned *>(reinterpret_cast<unsigned short *>(srow + (N >> 1)) + j0) =
+                        (unsigned)((u64)o.x >> 32) | ((unsigned)((u64)o.y >> 32) << 16);
+                } else {
+                    *reinterpret_cast<longlong2 *>(srow + j0) = o;
+                }
+            }
+    } else {
+        i64 acc[NR][2][2];
+#pragma unroll
+        for (int i = 0; i < NR; ++i) acc[i][0][0] = acc[i][0][1] = acc[i][1][0] = acc[i][1][1] = 0;
+        for (int p = 0; p < nparts; ++p) {
+            const i64 *er = ext + ((i64)p * rows + r) * N;
+#pragma unroll
+            for (int i = 0; i < NR; ++i) {
+                const longlong2 v = *reinterpret_cast<const longlong2 *>(er + src[i]);
+                const u64 x0 = (u64)(sw[i] ? v.y : v.x), x1 = (u64)(sw[i] ? v.x : v.y);
+                const i64 *kr = hk.ksk[i] + krow + (i64)p * part_stride + j0;
+                const longlong2 k0 = ld_nt(kr);
+                const longlong2 k1 = ld_nt(kr + comp_stride);
+                acc[i][0][0] = csub(acc[i][0][0] + mm62u(x0, (u64)k0.x, m.q, m.k), m.q2);
+                acc[i][0][1] = csub(acc[i][0][1] + mm62u(x1, (u64)k0.y, m.q, m.k), m.q2);
+                acc[i][1][0] = csub(acc[i][1][0] + mm62u(x0, (u64)k1.x, m.q, m.k), m.q2);
+                acc[i][1][1] = csub(acc[i][1][1] + mm62u(x1, (u64)k1.y, m.q, m.k), m.q2);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < NR; ++i)
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                longlong2 o;
+                o.x = acc[i][c][0];
+                o.y = acc[i][c][1];
+                *reinterpret_cast<longlong2 *>(s + i * ct_s + ((i64)c * rows + r) * N + j0) = o;
+            }
+    }
+}
+
 // largest number of leading stages (logN - 12) whose extension + strided pass runs as the column kernel (lf_tune).
 // With the digit loop as a runtime loop (R loads in flight, 100 VGPRs at R = 16) the column form also wins at logN 16:
 // gold cc_mult 2 104-2 130 -> 2 168-2 183 ops/s, rotate 2 653-2 695 -> 2 733-2 763, 64 rotations under one key
@@ -789,6 +903,58 @@ int ks_forward(const int64_t *state, int64_t state_stride, int nct, int nparts, 
     return (int)hipGetLastError();
 }
 
+// K4: inverse transform of inv_polys sums [inv_polys][rows][N] -> canonical coefficients (relaxed, tail 2), in place on s;
+// spl: the sums' fp64-class rows arrive as planes and the tiled pass carries them through tmp (room for inv_polys polynomials)
+int ks_inv_sums(int inv_polys, int rows, int logN, bool spl, bool cols_last, bool mixed, const RowList &in, const RowList &dp,
+                i64 *tmp, i64 *s, const int64_t *ipsi_br, const double *ipsi_dp, const int64_t *Ninv, const int64_t *ql,
+                const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st) {
+    const int tl = NTT_TILE_LOG_MAX, S1 = logN - tl;
+    const unsigned per_row2 = (unsigned)inv_polys << (logN - tl);
+    for (int pass = 0; pass < 2; ++pass) {
+        PassGeom g = pass == 0 ? PassGeom{logN, tl, 0, tl, 0, 0, rows, inv_polys, 1, 0, 0}
+                               : PassGeom{logN, tl, 1, S1, tl, tl - S1, rows, inv_polys, 1, 1, 0};
+        if (pass == 0) {
+            launch_pass16(true, 1, inv_polys, st, (const i64 *)s, spl ? (i64 *)tmp : (i64 *)s, g, in, dp, (const i64 *)ipsi_br, ipsi_dp,
+                          (const i64 *)ql, (const i64 *)qh, (const i64 *)kl, (const i64 *)kh, nullptr, spl);
+            continue;
+        }
+        if (pass == 1 && cols_last) {   // (logN 17: the column form of both ends goes with the knob)
+            if (spl) {
+                g.pln = PLN_IN;
+                g.pln_src = (const i64 *)tmp;
+            }
+            if (mixed) {
+                launch_inv_cols_mixed(S1, inv_polys, st, (i64 *)s, g, in, dp, (const i64 *)ipsi_br, ipsi_dp, (const i64 *)Ninv, 2,
+                                      (const i64 *)ql, (const i64 *)qh, (const i64 *)kl, (const i64 *)kh);
+                continue;
+            }
+            if (dp.n)
+                launch_inv_cols<true>(S1, inv_polys, st, (i64 *)s, g, dp, (const i64 *)ipsi_br, ipsi_dp, (const i64 *)Ninv, 2,
+                                      (const i64 *)ql, (const i64 *)qh, (const i64 *)kl, (const i64 *)kh);
+            if (in.n)
+                launch_inv_cols<false>(S1, inv_polys, st, (i64 *)s, g, in, (const i64 *)ipsi_br, ipsi_dp, (const i64 *)Ninv, 2,
+                                       (const i64 *)ql, (const i64 *)qh, (const i64 *)kl, (const i64 *)kh);
+            continue;
+        }
+        if (mixed) {
+            const ClassLists cl = class_lists(in, dp, per_row2 * (unsigned)in.n);
+            hipLaunchKernelGGL((ntt_inv_pass_mixed<true>), dim3((unsigned)cl.in_blocks + per_row2 * dp.n), dim3(NTT_THREADS), 0, st,
+                               (const i64 *)s, (i64 *)s, g, cl, (const i64 *)ipsi_br, ipsi_dp, (const i64 *)Ninv,
+                               pass == 1 ? 2 : TAIL_NONE, (const i64 *)ql, (const i64 *)qh, (const i64 *)kl, (const i64 *)kh);
+            continue;
+        }
+        if (dp.n)
+            hipLaunchKernelGGL((ntt_inv_pass_io<true, true>), dim3(per_row2 * dp.n), dim3(NTT_THREADS), 0, st, (const i64 *)s, (i64 *)s,
+                               g, dp, (const i64 *)ipsi_br, ipsi_dp, (const i64 *)Ninv, pass == 1 ? 2 : TAIL_NONE,
+                               (const i64 *)ql, (const i64 *)qh, (const i64 *)kl, (const i64 *)kh);
+        if (in.n)
+            hipLaunchKernelGGL((ntt_inv_pass_io<false, true>), dim3(per_row2 * in.n), dim3(NTT_THREADS), 0, st, (const i64 *)s, (i64 *)s,
+                               g, in, (const i64 *)ipsi_br, ipsi_dp, (const i64 *)Ninv, pass == 1 ? 2 : TAIL_NONE,
+                               (const i64 *)ql, (const i64 *)qh, (const i64 *)kl, (const i64 *)kh);
+    }
+    return (int)hipGetLastError();
+}
+
 // K3 + K4: inner product of the nparts extended digits with the key, inverse transform to canonical coefficients
 int ks_tail(int nct, int nparts, int rows, int logN, const int64_t *ksk, int64_t part_stride, int64_t comp_stride,
             int64_t row_off, int64_t *tmp, int64_t *s, const int64_t *ipsi_br, const double *ipsi_dp,
@@ -840,54 +1006,57 @@ int ks_tail(int nct, int nparts, int rows, int logN, const int64_t *ksk, int64_t
 #undef LF_INNER_CASE
     }
     // K4: inverse transform -> canonical coefficients (relaxed, tail 2), in place on s
-    const int inv_polys = 2 * nct;
-    const unsigned per_row2 = (unsigned)inv_polys << (logN - tl);
-    for (int pass = 0; pass < 2; ++pass) {
-        PassGeom g = pass == 0 ? PassGeom{logN, tl, 0, tl, 0, 0, rows, inv_polys, 1, 0, 0}
-                               : PassGeom{logN, tl, 1, S1, tl, tl - S1, rows, inv_polys, 1, 1, 0};
-        if (pass == 0) {
-            launch_pass16(true, 1, inv_polys, st, (const i64 *)s, spl ? (i64 *)tmp : (i64 *)s, g, in, dp, (const i64 *)ipsi_br, ipsi_dp,
-                          (const i64 *)ql, (const i64 *)qh, (const i64 *)kl, (const i64 *)kh, nullptr, spl);
-            continue;
-        }
-        if (pass == 1 && cols_last) {   // (logN 17: the column form of both ends goes with the knob)
-            if (spl) {
-                g.pln = PLN_IN;
-                g.pln_src = (const i64 *)tmp;
-            }
-            if (mixed) {
-                launch_inv_cols_mixed(S1, inv_polys, st, (i64 *)s, g, in, dp, (const i64 *)ipsi_br, ipsi_dp, (const i64 *)Ninv, 2,
-                                      (const i64 *)ql, (const i64 *)qh, (const i64 *)kl, (const i64 *)kh);
-                continue;
-            }
-            if (dp.n)
-                launch_inv_cols<true>(S1, inv_polys, st, (i64 *)s, g, dp, (const i64 *)ipsi_br, ipsi_dp, (const i64 *)Ninv, 2,
-                                      (const i64 *)ql, (const i64 *)qh, (const i64 *)kl, (const i64 *)kh);
-            if (in.n)
-                launch_inv_cols<false>(S1, inv_polys, st, (i64 *)s, g, in, (const i64 *)ipsi_br, ipsi_dp, (const i64 *)Ninv, 2,
-                                       (const i64 *)ql, (const i64 *)qh, (const i64 *)kl, (const i64 *)kh);
-            continue;
-        }
-        if (mixed) {
-            const ClassLists cl = class_lists(in, dp, per_row2 * (unsigned)in.n);
-            hipLaunchKernelGGL((ntt_inv_pass_mixed<true>), dim3((unsigned)cl.in_blocks + per_row2 * dp.n), dim3(NTT_THREADS), 0, st,
-                               (const i64 *)s, (i64 *)s, g, cl, (const i64 *)ipsi_br, ipsi_dp, (const i64 *)Ninv,
-                               pass == 1 ? 2 : TAIL_NONE, (const i64 *)ql, (const i64 *)qh, (const i64 *)kl, (const i64 *)kh);
-            continue;
-        }
-        if (dp.n)
-            hipLaunchKernelGGL((ntt_inv_pass_io<true, true>), dim3(per_row2 * dp.n), dim3(NTT_THREADS), 0, st, (const i64 *)s, (i64 *)s,
-                               g, dp, (const i64 *)ipsi_br, ipsi_dp, (const i64 *)Ninv, pass == 1 ? 2 : TAIL_NONE,
-                               (const i64 *)ql, (const i64 *)qh, (const i64 *)kl, (const i64 *)kh);
-        if (in.n)
-            hipLaunchKernelGGL((ntt_inv_pass_io<false, true>), dim3(per_row2 * in.n), dim3(NTT_THREADS), 0, st, (const i64 *)s, (i64 *)s,
-                               g, in, (const i64 *)ipsi_br, ipsi_dp, (const i64 *)Ninv, pass == 1 ? 2 : TAIL_NONE,
-                               (const i64 *)ql, (const i64 *)qh, (const i64 *)kl, (const i64 *)kh);
-    }
-    return (int)hipGetLastError();
+    return ks_inv_sums(2 * nct, rows, logN, spl, cols_last, mixed, in, dp, (i64 *)tmp, (i64 *)s, ipsi_br, ipsi_dp, Ninv, ql, qh, kl, kh, st);
 }
 
 }  // namespace
+
+// The key-dependent half of nr (1, 2 or 4) hoisted rotations of ONE ciphertext (lf_rotate_hoisted, ckks_ops.hip): inner product of
+// the extended digits `ext` [nparts][rows][N] (lf_ks_fwd) gathered by pi_{p_i} with key i, then the inverse transform of the
+// 2 nr sums s [nr][2][rows][N].  `ext` is only read, so it serves every group; the sums' planes pass through `scratch`
+// (scratch_words >= 2 nr rows N, else the sums stay raw words: same outputs).  Internal: ckks_ops.hip checks the arguments.
+int lf_ks_tail_hoisted(int nr, const unsigned *p, int nparts, int rows, int logN, const int64_t *const *ksk, int64_t part_stride,
+                       int64_t comp_stride, int64_t row_off, int key_format, const int64_t *ext, int64_t *s, int64_t *scratch,
+                       int64_t scratch_words, const int64_t *ipsi_br, const double *ipsi_dp, const int64_t *Ninv, const int64_t *q_host,
+                       const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st) {
+    if (!ipsi_dp || (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES) || (nr != 1 && nr != 2 && nr != 4)) return LF_ERR_ARG;
+    HoistKeys hk{};
+    for (int i = 0; i < nr; ++i) {
+        if (!ksk[i]) return LF_ERR_ARG;
+        if (key_format == LF_KEY_PLANES && ((((uintptr_t)ksk[i] | (uintptr_t)(part_stride * 8) | (uintptr_t)(comp_stride * 8)) & 15)))
+            return LF_ERR_ARG;
+        hk.ksk[i] = (const i64 *)ksk[i];
+        hk.p[i] = (unsigned)p[i];
+    }
+    const int tl = NTT_TILE_LOG_MAX, S1 = logN - tl;
+    RowList dp, in;
+    classify_rows(rows, q_host, dp, in);
+    const bool mixed = dp.n && in.n;
+    const bool dplanes = digit_planes(logN, dp, in);
+    const bool cols_last = S1 <= 4 || (S1 == 5 && mixed && g_ks_ext_cols_max > 4);
+    // the digits must be in the format this half reads (see ks_tail)
+    if (int e = lf_fmt_expect(ext, ((size_t)nparts * rows << logN) * 8, dplanes ? LF_FMT_PLANES : LF_FMT_RAW)) return e;
+    const bool spl = dplanes && (g_more_planes & 1) && cols_last && scratch && scratch_words >= ((int64_t)2 * nr * rows << logN);
+    const i64 N = (i64)1 << logN;
+    const dim3 grid((unsigned)((N + 511) / 512), (unsigned)rows);
+#define LF_HOIST_LAUNCH(NR, PL, DPLB)                                                                                       \
+    hipLaunchKernelGGL((ks_inner_hoist_kernel<NR, PL, DPLB>), grid, dim3(256), 0, st, (const i64 *)ext, hk, (i64)part_stride, \
+                       (i64)comp_stride, (i64)row_off, (i64 *)s, nparts, rows, logN, spl ? 1 : 0, (const i64 *)ql, (const i64 *)qh, \
+                       (const i64 *)kl, (const i64 *)kh)
+#define LF_HOIST_CASE(NR)                                                                                                  \
+    case NR:                                                                                                               \
+        if (planes && dplanes) LF_HOIST_LAUNCH(NR, true, true);                                                           \
+        else if (planes) LF_HOIST_LAUNCH(NR, true, false);                                                                \
+        else if (dplanes) LF_HOIST_LAUNCH(NR, false, true);                                                               \
+        else LF_HOIST_LAUNCH(NR, false, false);                                                                           \
+        break;
+    const bool planes = key_format == LF_KEY_PLANES;
+    switch (nr) { LF_HOIST_CASE(1) LF_HOIST_CASE(2) LF_HOIST_CASE(4) }
+#undef LF_HOIST_LAUNCH
+#undef LF_HOIST_CASE
+    return ks_inv_sums(2 * nr, rows, logN, spl, cols_last, mixed, in, dp, (i64 *)scratch, (i64 *)s, ipsi_br, ipsi_dp, Ninv, ql, qh, kl,
+                       kh, st);
+}
 
 // cc_mult's product -> digits in one launch behind the tiled pass where it qualifies (ckks_ops.hip: product_digits): 0 = never
 int lf_g_intt_digits = 1;

@@ -11,6 +11,11 @@
 #include "ckks_common.h"
 
 extern int lf_g_intt_digits;   // ckks_ks.hip (lf_tune)
+// ckks_ks.hip: the key-dependent half of lf_rotate_hoisted (gathered inner product of up to 4 keys + inverse NTT of their sums)
+int lf_ks_tail_hoisted(int nr, const unsigned *p, int nparts, int rows, int logN, const int64_t *const *ksk, int64_t part_stride,
+                       int64_t comp_stride, int64_t row_off, int key_format, const int64_t *ext, int64_t *s, int64_t *scratch,
+                       int64_t scratch_words, const int64_t *ipsi_br, const double *ipsi_dp, const int64_t *Ninv, const int64_t *q_host,
+                       const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st);
 
 extern "C" {
 
@@ -105,6 +110,68 @@ int lf_switch_key(const lf_ks_plan *p, const int64_t *c0, const int64_t *c1, int
     int64_t *outs[2] = {out0, out1};
     const int64_t *adds[2] = {c0, nullptr};
     return moddown_any(p, ss, outs, adds, 2, gal_pinv, g2q, stream);
+}
+
+/* ---- hoisted rotations: ONE ciphertext under nr keys, the digits of c1 extended and transformed once (include/ckks_hip.h) ---- */
+// groups of up to 4 keys share one inner-product launch; their 2 x group sums sit in the plan's sum pairs
+static int hoist_group_max(const lf_ks_plan *p) { return p->max_nct >= 4 ? 4 : p->max_nct; }
+
+// where the sums of a group pass through their tiled inverse pass: the plan's ext slots behind the first (nct > 1 plans), else `ws`
+static int64_t hoist_need(const lf_ks_plan *p) { return ((int64_t)2 * hoist_group_max(p) * (p->ell + p->K)) << p->logN; }
+static int64_t hoist_spare(const lf_ks_plan *p) { return ((int64_t)(p->max_nct - 1) * p->nparts * (p->ell + p->K)) << p->logN; }
+
+int64_t lf_rotate_hoisted_ws_words(const lf_ks_plan *p) {
+    if (!plan_ok(p) || p->max_nct < 1) return 0;
+    return hoist_spare(p) >= hoist_need(p) ? 0 : hoist_need(p);
+}
+
+int lf_rotate_hoisted(const lf_ks_plan *p, const int64_t *c0, const int64_t *c1, int nr, const int64_t *p_host, int gal_canonical,
+                      const int64_t *const *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format, int64_t *ws,
+                      int64_t ws_words, int64_t *const *out0, int64_t *const *out1, void *stream) {
+    if (!plan_ok(p) || nr < 1 || !c0 || !c1 || !p_host || !ksk || !out0 || !out1 || (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES))
+        return LF_ERR_ARG;
+    const int rows = p->ell + p->K, logN = p->logN, dev = p->device;
+    const int64_t N = (int64_t)1 << logN, twoN = 2 * N;
+    for (int i = 0; i < nr; ++i) {
+        if (!ksk[i] || !out0[i] || !out1[i] || p_host[i] <= 0 || p_host[i] >= twoN || !(p_host[i] & 1)) return LF_ERR_ARG;
+        if (key_format == LF_KEY_PLANES && ((((uintptr_t)ksk[i] | (uintptr_t)(part_stride * 8) | (uintptr_t)(comp_stride * 8)) & 15)))
+            return LF_ERR_ARG;   // (the planes loads are 16 bytes wide)
+    }
+    const int64_t need = lf_rotate_hoisted_ws_words(p);
+    if (need && (!ws || ws_words < need)) return LF_ERR_ARG;
+    int64_t *scratch = need ? ws : p->ext + ((int64_t)p->nparts * rows << logN);
+    const int64_t scratch_words = need ? ws_words : hoist_spare(p);
+    const int64_t *g2q = gal_canonical ? p->_2q : nullptr;
+    // 1. digits of c1, made canonical as rotate_single makes c1(X^p) (gal_pinv = 1: the identity map)
+    if (int e = lf_ks_digits_galois(c1, p->state, p->dig_nparts, p->dig_desc, p->dig_tab, N, 1, g2q, p->ql, p->qh, p->kl, p->kh, dev,
+                                    stream))
+        return e;
+    // 2. extension + forward NTT of every digit, once, into the first ext slot
+    if (int e = lf_ks_fwd(p->state, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, p->ext, p->psi, p->psi_dp, p->q_host, p->ql, p->qh,
+                          p->kl, p->kh, dev, stream))
+        return e;
+    // 3. per group of 4, 2 or 1 keys: gathered inner product + inverse NTT, then one mod-down per rotation with c0(X^p_i)
+    for (int i0 = 0; i0 < nr;) {
+        const int left = nr - i0, gmax = hoist_group_max(p);
+        const int g = left >= 4 && gmax >= 4 ? 4 : left >= 2 && gmax >= 2 ? 2 : 1;
+        unsigned pe[4];
+        for (int t = 0; t < g; ++t) pe[t] = (unsigned)p_host[i0 + t];
+        if (int e = lf_ks_tail_hoisted(g, pe, p->nparts, rows, logN, ksk + i0, part_stride, comp_stride, row_off, key_format, p->ext, p->sum,
+                                       scratch, scratch_words, p->ipsi, p->ipsi_dp, p->Ninv, p->q_host, p->ql, p->qh, p->kl, p->kh,
+                                       (hipStream_t)stream))
+            return e;
+        for (int t = 0; t < g; ++t) {
+            uint64_t x = (uint64_t)p_host[i0 + t], inv = x;   // p^-1 mod 2^64 by Newton's iteration (p odd), then mod 2N
+            for (int k = 0; k < 6; ++k) inv *= 2 - x * inv;
+            const int64_t pinv = (int64_t)(inv & (uint64_t)(twoN - 1));
+            const int64_t *ss[2] = {p->sum + (int64_t)(2 * t) * rows * N, p->sum + (int64_t)(2 * t + 1) * rows * N};
+            int64_t *outs[2] = {out0[i0 + t], out1[i0 + t]};
+            const int64_t *adds[2] = {c0, nullptr};
+            if (int e = moddown_any(p, ss, outs, adds, 2, pinv, g2q, stream)) return e;
+        }
+        i0 += g;
+    }
+    return 0;
 }
 
 /* ---- batches under one key: nct = 1, 2 or 4 ciphertexts per launch set (plan->max_nct >= nct; scratch of ciphertext t at

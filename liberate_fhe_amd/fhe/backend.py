@@ -397,6 +397,46 @@ class HipBackend:
         check(lib.lf_switch_key(ctypes.byref(plan), _p(c0), _p(c1), pinv, 1 if canonical else 0, base, part_stride, comp_stride,
                                 row_off, self._kfmt(key), out.data_ptr(), out.data_ptr() + plane, st), "lf_switch_key")
 
+    @staticmethod
+    def rotate_hoisted_ws_words(plan):
+        return int(lib.lf_rotate_hoisted_ws_words(ctypes.byref(plan)))
+
+    def rotate_hoisted_native(self, plan, c0, c1, exponents, keys, first_part, row_off, out, ws=None):
+        """One ciphertext under len(keys) rotation keys as ONE native call (lf_rotate_hoisted): the digits of c1 are extended and
+        transformed once, rotation i gathers them by pi_{exponents[i]}.  keys: packed key tensors of one format and shape;
+        out [n, 2, ell, N]; ws: >= rotate_hoisted_ws_words(plan) words (None when that is 0)."""
+        dev, st = _ds(out)
+        n = len(keys)
+        bases = (ctypes.c_void_p * n)()
+        for i, key in enumerate(keys):
+            bases[i], ps, cs = self._key_args(key, first_part)
+        fmt = {self._kfmt(k) for k in keys}
+        if len(fmt) != 1:
+            raise ValueError("rotate_hoisted_native: the keys of one call must share one format")
+        exps = (ctypes.c_int64 * n)(*exponents)
+        check(lib.lf_rotate_hoisted(ctypes.byref(plan), _p(c0), _p(c1), n, exps, 1, bases, ps, cs, row_off, fmt.pop(),
+                                    _p(ws), 0 if ws is None else ws.numel(), _parr([out[i][0] for i in range(n)]),
+                                    _parr([out[i][1] for i in range(n)]), st), "lf_rotate_hoisted")
+
+    def ks_gather(self, ext, dst, index, rows, logN, c: Consts):
+        """dst[p][r][k] = ext[p][r][index[k]] for extended digits as ks_fwd leaves them: fp64-class rows of a mixed stack in the
+        planes format (u32 low words at byte 0, u16 high halves at byte 4 N of the row: LF_TUNE_DIGIT_PLANES), other rows raw
+        words.  torch gathers, no kernel of its own (the orchestrated form of hoisted rotations; the native op gathers in registers)."""
+        q = c.q_host[:rows]
+        small = torch.as_tensor(q < (1 << 41))
+        planes = logN > 12 and bool(small.any()) and not bool(small.all()) and lib.lf_tune(3, -1) == 1
+        if not planes:
+            torch.index_select(ext, ext.dim() - 1, index, out=dst)
+            return
+        N = 1 << logN
+        sm = torch.nonzero(small).flatten().to(ext.device)
+        bg = torch.nonzero(~small).flatten().to(ext.device)
+        dst[:, bg] = ext[:, bg].index_select(2, index)
+        e32, d32 = ext.view(torch.int32), dst.view(torch.int32)
+        e16, d16 = ext.view(torch.int16), dst.view(torch.int16)
+        d32[:, sm, :N] = e32[:, sm, :N].index_select(2, index)
+        d16[:, sm, 2 * N:3 * N] = e16[:, sm, 2 * N:3 * N].index_select(2, index)
+
     ks_batch_sizes = (4, 2)   # ciphertexts per lf_ks_core_batch call (largest first)
 
     def ks_core_batch(self, states, nparts, rows, logN, desc, E, Ed, key, first_part, row_off, tmp, s, psi, ipsi, Ninv,

@@ -1464,6 +1464,27 @@ class ckks_engine(EvaluatorOps):
             out[t] = (buf, [(None, 0, nparts)])
         return out
 
+    def _ks_digits_exchanged(self, a, level, exit_ntt=False, galois=None):
+        """Steps 1-2 of a key switch of `a` (one tensor per local device): the mixed-radix digits of the local parts
+        (galois: of a(X^p), see create_switcher), then their exchange (_exchange_digits)."""
+        tabs = self._ks_tables(level)
+        N, logN = self.ctx.N, self.ctx.logN
+        states = {}
+        for i, d in enumerate(self._loc(level)):
+            src = a[i]
+            rows = self._rows(d, level, False)
+            if exit_ntt:
+                src = src.clone()
+                self.backend.intt(src, 1, rows, logN, self._tw(d, level, False, True), self._vec("Ninv", d, level, False),
+                                  2, self._consts(d, level, False))
+            st = self._ws("ks_state", (rows, N), d)
+            nparts, desc, tab = tabs[("digits", d)]
+            gal = None if galois is None else (galois[0], self._vec("_2q", d, level, False) if galois[1] else None)
+            self.backend.ks_digits(src, st, nparts, desc, tab, self._consts(d, level, False), galois=gal)
+            states[d] = st
+        # asynchronous, one batch of point-to-point messages between the alive ranks
+        return self._exchange_digits(states, level, tabs)
+
     def create_switcher(self, a: list[torch.Tensor], ksk: data_struct, level, exit_ntt=False, addends=None,
                         galois=None, fold=None) -> tuple:
         """Key-switch the coefficient-domain polynomial `a` (one tensor per local device) under `ksk`.
@@ -1479,22 +1500,8 @@ class ckks_engine(EvaluatorOps):
         packs = self._key_pack(ksk)
         loc0 = self._loc(0, special=True)
 
-        # 1. mixed-radix digits of the local parts
-        states = {}
-        for i, d in enumerate(loc):
-            src = a[i]
-            rows = self._rows(d, level, False)
-            if exit_ntt:
-                src = src.clone()
-                self.backend.intt(src, 1, rows, logN, self._tw(d, level, False, True), self._vec("Ninv", d, level, False),
-                                  2, self._consts(d, level, False))
-            st = self._ws("ks_state", (rows, N), d)
-            nparts, desc, tab = tabs[("digits", d)]
-            gal = None if galois is None else (galois[0], self._vec("_2q", d, level, False) if galois[1] else None)
-            self.backend.ks_digits(src, st, nparts, desc, tab, self._consts(d, level, False), galois=gal)
-            states[d] = st
-        # 2. digit exchange: asynchronous, one batch of point-to-point messages between the alive ranks
-        digits = self._exchange_digits(states, level, tabs)
+        # 1. mixed-radix digits of the local parts, 2. their exchange
+        digits = self._ks_digits_exchanged(a, level, exit_ntt, galois)
 
         nparts = len(tabs["order"])
         c0, c1 = [], []
@@ -1723,6 +1730,107 @@ class ckks_engine(EvaluatorOps):
                 for i, r in zip(sel, res):
                     out[i] = r
         return out
+
+    def rotate_hoisted(self, ct: data_struct, rotks: list) -> list:
+        """Rotations of ONE ciphertext by many steps, the digits of c1 shared ("hoisted" rotations; the reference has no such
+        entry).  Returns one ciphertext per key of `rotks`, in key order (a key may repeat).  X -> X^p permutes the NTT slots
+        (encdec.ntt_galois_index), so c1's digits are formed, extended and transformed ONCE and rotation i reads them gathered by
+        pi_{p_i}.  Result i has exactly the words of: c1 made canonical (no permutation) -> per part pre_extend, extend, exact
+        forward NTT -> gathered by pi_{p_i} -> mont_mult with key i's part, mont_add over the parts, intt_exit_reduce -> mod-down
+        with the addend c0(X^{p_i}) made canonical as in rotate_single.  Not rotate_single's words (the extension of the digits
+        does not commute with the sign flips of X -> X^p; both decrypt to the rotated message), except for a step-0 key.
+        One native call (lf_rotate_hoisted) where every limb of the level is on one device of this process; otherwise the same
+        words through the engine's steps.  Coefficient-domain ciphertexts without special limbs only."""
+        if ct.origin != types.origins["ct"]:
+            raise errors.NotMatchType(origin=ct.origin, to=types.origins["ct"])
+        for k in rotks:
+            if types.origins["rotk"] not in k.origin:
+                raise errors.NotMatchType(origin=k.origin, to=types.origins["rotk"])
+        if not rotks:
+            return []
+        if ct.ntt_state or ct.include_special:
+            raise NotImplementedError("rotate_hoisted: coefficient-domain ciphertexts without special limbs only (rotate_single "
+                                      "handles the others)")
+        level, N, logN = ct.level, self.ctx.N, self.ctx.logN
+        exps = [encdec.galois_exponent(N, int(k.origin.split(":")[-1])) for k in rotks]
+
+        def wrap(c0, c1):
+            return data_struct(data=(c0, c1), include_special=False, ntt_state=False, montgomery_state=ct.montgomery_state,
+                               origin=types.origins["ct"], level=level, hash=self.hash)
+
+        d = self._native_level(level)
+        if d is not None and hasattr(self.backend, "rotate_hoisted_native") and \
+                ct.data[0][0].is_contiguous() and ct.data[1][0].is_contiguous():
+            # the whole set as ONE native call over the plan of groups of 4
+            plan, _, first_part, row_off = self._op_plan(level, d, 4)
+            i0 = self._loc(0, special=True).index(d)
+            keys = [self._key_pack(k)[i0] for k in rotks]
+            words = self.backend.rotate_hoisted_ws_words(plan)
+            ws = self._ws("hoisted_ws", (words,), d) if words else None
+            out = torch.empty((len(rotks), 2, plan.ell, N), dtype=torch.int64, device=self.ntt.devices[d])
+            self.backend.rotate_hoisted_native(plan, ct.data[0][0], ct.data[1][0], exps, keys, first_part, row_off, out, ws)
+            return [wrap([out[i][0]], [out[i][1]]) for i in range(len(rotks))]
+
+        # orchestrated: digits of c1 (canonical, no permutation) and their exchange once; extension + forward NTT once per device
+        tabs = self._ks_tables(level)
+        loc, loc0 = self._loc(level), self._loc(0, special=True)
+        K = self.ntt.num_special_primes
+        digits = self._ks_digits_exchanged(ct.data[1], level, galois=(1, True))
+        nparts = len(tabs["order"])
+        fused = logN >= self.backend.fused_ks_min_logN
+        gather = getattr(self.backend, "ks_gather", None)
+        res = [([], []) for _ in rotks]
+        for i, d in enumerate(loc):
+            rows, ell = self._rows(d, level, True), self._rows(d, level, False)
+            cs = self._consts(d, level, True)
+            desc, E, Ed = tabs[("extend", d)]
+            tw, itw, ninv = self._tw(d, level, True), self._tw(d, level, True, True), self._vec("Ninv", d, level, True)
+            ext = self._ws("ks_ext", (nparts, rows, N), d)
+            dig, ready = digits[d]
+            for handle, first, count in ready:
+                if handle is not None:
+                    handle.wait()
+                if fused:
+                    self.backend.ks_fwd(dig, first, count, rows, logN, desc, E, Ed, ext, tw, cs)
+            if not fused:
+                self.backend.ks_extend(dig, ext, nparts, rows, desc, E, cs)
+                self.backend.ntt(ext, nparts, rows, logN, tw, None, cs, relaxed=True)
+            # the transformed digits aside; each key's gather lands in `ext`, the buffer the forward half has just noted in the
+            # current digit format (lf_ks_tail checks that note, and uses `ext` as scratch for the sums' inverse transform)
+            src = self._ws("ks_ext_hoisted", (nparts, rows, N), d)
+            src.copy_(ext)
+            s = self._ws("ks_sum", (2, rows, N), d)
+            add = ct.data[0][i] if ct.data[0][i].is_contiguous() else ct.data[0][i].contiguous()
+            g2q = self._vec("_2q", d, level, False)
+            for j, (key, p) in enumerate(zip(rotks, exps)):
+                # ext gathered by pi_p along N, the key's inner product, the inverse NTT, the mod-down with c0(X^p)
+                idx = self._galois_index(p, d)
+                if gather is not None:
+                    gather(src, ext, idx, rows, logN, cs)
+                else:
+                    torch.index_select(src, 2, idx, out=ext)
+                kp = self._key_pack(key)[loc0.index(d)]
+                if fused:
+                    self.backend.ks_tail(nparts, rows, logN, kp, tabs["first_part"], self.ntt.starts[level][d], ext, s, itw, ninv, cs)
+                else:
+                    self.backend.ks_inner(ext, kp, tabs["first_part"], self.ntt.starts[level][d], s[0], s[1], nparts, rows, cs)
+                    self.backend.intt(s, 2, rows, logN, itw, ninv, 2, cs, relaxed=True)
+                out = torch.empty((2, ell, N), dtype=torch.int64, device=self.ntt.devices[d])
+                ws, one = self._moddown_ws("ks_moddown", 2, ell, K, d, tabs, cs)
+                mkw = {"one_launch": True} if one else {}
+                self.backend.ks_moddown_ws([s[0], s[1]], [out[0], out[1]], [add, None], ell, K, ws, tabs[("pir", d)],
+                                           self._vec("Rs", d, level, True), cs, PiP=tabs[("pip", d)],
+                                           galois=(pow(p, -1, 2 * N), g2q), **mkw)
+                res[j][0].append(out[0]); res[j][1].append(out[1])
+        return [wrap(c0, c1) for c0, c1 in res]
+
+    def _galois_index(self, p, d):
+        """encdec.ntt_galois_index(logN, p) on device d (cached)."""
+        key = ("galidx", p, d)
+        hit = self._tables.get(key)
+        if hit is None:
+            hit = self._tables[key] = torch.from_numpy(encdec.ntt_galois_index(self.ctx.logN, p)).to(self.ntt.devices[d])
+        return hit
 
     def _prepare_ks(self, key, level):
         """Build, on the CURRENT stream, every lazily built piece of shared state a key switch at `level` under

@@ -114,3 +114,21 @@ def galois_exponent(N: int, delta: int) -> int:
 def conjugation_exponent(N: int) -> int:
     """Complex conjugation of the slots is X -> X^(2N-1) (encdec.py:249-253)."""
     return 2 * N - 1
+
+
+def ntt_galois_index(logN: int, p: int) -> np.ndarray:
+    """pi_p as an int64 index array: NTT(a(X^p))[k] = NTT(a)[pi_p(k)] for the forward transform's order (index k holds the
+    evaluation at psi^(2 brev(k) + 1)), pi_p(k) = brev(((2 brev(k) + 1) p mod 2N - 1) / 2).  A pure permutation (p odd):
+    hoisted rotations gather the extended digits of one ciphertext by it, once per rotation (ckks_engine.rotate_hoisted)."""
+    N = 1 << logN
+    if p % 2 == 0 or not 0 < p < 2 * N:
+        raise ValueError(f"ntt_galois_index: the exponent must be odd and in (0, 2N), got {p}")
+
+    def brev(x):
+        r = np.zeros_like(x)
+        for b in range(logN):
+            r |= ((x >> b) & 1) << (logN - 1 - b)
+        return r
+
+    t = ((2 * brev(np.arange(N, dtype=np.int64)) + 1) * p) % (2 * N)
+    return brev((t - 1) // 2)

@@ -311,3 +311,269 @@ class Recorded:
         with open(cls.PATH, "w") as f:
             json.dump(cls._store, f, indent=1, sort_keys=True)
             f.write("\n")
+
+
+# ---- operands for the fused engine kernels (tests/test_engine_edges_*.py) ------------------------------------------------
+ENGINE_EDGE_PATTERNS = ("top", "top|0", "top|1", "half", "mixed", "random")
+_MIXED_ROTATION = ("top", "top|0", "half", "top|1")
+
+
+class _Rows:
+    """The two attributes edge_operand reads of a limb set."""
+
+    def __init__(self, q, N):
+        self.q, self.N = [int(x) for x in q], N
+
+
+def edge_rows(q_list, N, pattern, seed=0, lazy=False, ids=None):
+    """[len(q_list), N] int64 words that sit on the range bounds of the coefficient-wise engine kernels:
+      "top"     every word q - 1 (2q - 1 when lazy);
+      "top|0"   top and 0 by the Thue-Morse parity of the index;
+      "top|1"   top and 1 by the same parity;
+      "half"    q // 2 and q // 2 + 1 alternating: the seam of the balanced representation;
+      "mixed"   row i takes one of the four above, rotated by its id, so that the integer the rows represent jointly is
+                not a small number (all rows at q_i - 1 are the integer -1);
+      "random"  uniform words below q (2q when lazy), seeded per row id.
+    `ids`: the identity of each row (its prime index: rotation of "mixed", seed of "random"), default 0, 1, ..; the words of
+    a prime then do not depend on which device holds it."""
+    q_list = [int(q) for q in q_list]
+    ids = list(range(len(q_list))) if ids is None else list(ids)
+    tm = thue_morse(N)
+    odd = np.arange(N, dtype=np.int64) & 1
+    out = np.empty((len(q_list), N), dtype=np.int64)
+    for r, (q, i) in enumerate(zip(q_list, ids)):
+        pat = _MIXED_ROTATION[i % 4] if pattern == "mixed" else pattern
+        one = _Rows([q], N)
+        if pat == "top":
+            out[r] = edge_operand(one, "2q-1" if lazy else "q-1")[0]
+        elif pat == "top|0":
+            out[r] = edge_operand(one, "2q-1|0")[0] if lazy else np.where(tm == 1, 0, q - 1)
+        elif pat == "top|1":
+            out[r] = np.where(tm == 1, 1, (2 * q if lazy else q) - 1)
+        elif pat == "half":
+            out[r] = q // 2 + odd
+        elif pat == "random":
+            out[r] = np.random.default_rng([seed, i]).integers(0, (2 if lazy else 1) * q, size=N, dtype=np.int64)
+        else:
+            raise ValueError(pattern)
+    return out
+
+
+def rounder_row0(q_drop, N, shift=0):
+    """[N] words of a dropped limb that hold the five values the rescale rounder [row0 > q_drop // 2] turns on —
+    0, round_at - 1, round_at, round_at + 1, q_drop - 1 — one after the other along the coefficient index.  The period is
+    odd, so each value falls on both lanes of every 16-byte pair."""
+    at = int(q_drop) // 2
+    vals = np.array([0, at - 1, at, at + 1, int(q_drop) - 1], dtype=np.int64)
+    return vals[(np.arange(N) + shift) % 5]
+
+
+def _edge_ids(engine):
+    return getattr(engine, "local_ids", None) or list(range(engine.ntt.num_devices))
+
+
+def _edge_ct(engine, data, level):
+    from liberate_fhe_amd.utils.synth import _data_struct
+    return _data_struct(engine)(data=tuple(data), include_special=False, ntt_state=False, montgomery_state=False,
+                                origin="cipher text", level=level, hash=engine.hash, version=engine.version)
+
+
+def edge_ciphertext(engine, level, pattern, seed=0):
+    """utils.synth.ciphertext with the words of edge_rows: component 1 takes the next pattern of the list, so that a
+    product never multiplies a row by itself."""
+    import torch
+    q, N = engine.ctx.q, engine.ctx.N
+    dest = engine.ntt.p.destination_arrays[level]
+    data = []
+    for comp in range(2):
+        pat = pattern if comp == 0 or pattern in ("mixed", "random") else \
+            ENGINE_EDGE_PATTERNS[(ENGINE_EDGE_PATTERNS.index(pattern) + 1) % 4]
+        rows = []
+        for d in _edge_ids(engine):
+            if d < len(dest):
+                ids = [i + comp for i in dest[d]] if pattern == "mixed" else dest[d]
+                w = edge_rows([q[i] for i in dest[d]], N, pat, seed * 2 + comp, ids=ids)
+                rows.append(torch.from_numpy(w).to(engine.ntt.devices[d]))
+        data.append(rows)
+    return _edge_ct(engine, data, level)
+
+
+def edge_key(engine, pattern, seed=0, origin="key switch key"):
+    """utils.synth.key_switch_key (same layout, _remember_pack called the same way) with the lazy words of
+    edge_rows(.., lazy=True): "top" is 2q - 1 everywhere."""
+    import torch
+    from liberate_fhe_amd.utils.synth import _data_struct
+    ds_type = _data_struct(engine)
+    q, N, p = engine.ctx.q, engine.ctx.N, engine.ntt.p
+    nparts = p.num_partitions + 1
+    packs = []
+    for d in _edge_ids(engine):
+        dest = p.destination_arrays_with_special[0][d]
+        pack = np.empty((nparts, 2, len(dest), N), dtype=np.int64)
+        for gid in range(nparts):
+            for comp in range(2):
+                pack[gid, comp] = edge_rows([q[i] for i in dest], N, pattern, seed * 4096 + gid * 2 + comp, lazy=True,
+                                            ids=[i + gid + comp for i in dest] if pattern == "mixed" else dest)
+        packs.append(torch.from_numpy(pack).to(engine.ntt.devices[d]))
+    parts = []
+    for gid in range(nparts):
+        parts.append(ds_type(data=([pk[gid, 0] for pk in packs], [pk[gid, 1] for pk in packs]), include_special=True,
+                             ntt_state=True, montgomery_state=True, origin=f"key switch key part index {gid}",
+                             level=0, hash=engine.hash, version=engine.version))
+    out = ds_type(data=parts, include_special=True, ntt_state=True, montgomery_state=True, origin=origin,
+                  level=0, hash=engine.hash, version=engine.version)
+    if hasattr(engine, "_remember_pack"):
+        engine._remember_pack(out, packs, own=True)
+    return out
+
+
+def pre_rescale_rows(q_rows, q_drop, target_rows, row0):
+    """The words a_i = ((t_i - rho) q_drop + r) mod q_i whose rescale (a_i - r) q_drop^-1 + rho is t_i, with r = row0 the
+    dropped limb's words and rho = [r > q_drop // 2]; Python integers."""
+    q_drop = int(q_drop)
+    r = [int(x) for x in row0]
+    rho = [int(x > q_drop // 2) for x in r]
+    out = np.empty((len(q_rows), len(r)), dtype=np.int64)
+    for i, q in enumerate(q_rows):
+        q = int(q)
+        out[i] = [((int(t) - h) * q_drop + x) % q for t, h, x in zip(target_rows[i], rho, r)]
+    return out
+
+
+def pre_rescale(engine, level, target_rows, row0):
+    """One polynomial of a level-`level` ciphertext — a list of [rows, N] arrays, one per device alive at `level`, in the
+    engine's layout — whose rescale to level + 1 leaves the words target_rows[d] ([surviving rows of device d, N]) when the
+    dropped limb holds row0 ([N] words below the dropped prime).  A ciphertext of edge words does not survive the rescale
+    cc_mult opens with (all limbs at q_i - 1 are the integer -1 and rescale to zero), so the operands of every case that
+    goes through a rescale are built backwards with this."""
+    q = engine.ctx.q
+    dest = engine.ntt.p.destination_arrays[level]
+    owner = engine.ntt.p.rescaler_loc[level]
+    q_drop = q[dest[owner][0]]
+    out = []
+    for d in range(len(dest)):
+        keep = dest[d][1:] if d == owner else dest[d]
+        t = np.asarray(target_rows[d]) if len(keep) else np.empty((0, len(row0)), dtype=np.int64)
+        body = pre_rescale_rows([q[i] for i in keep], q_drop, t, row0)
+        out.append(np.concatenate([np.asarray(row0, dtype=np.int64)[None, :], body]) if d == owner else body)
+    return out
+
+
+def pre_rescale_ciphertext(engine, level, pattern, seed=0, shift=0):
+    """A level-`level` ciphertext whose rescale leaves edge_rows(pattern) at level + 1 (see edge_ciphertext for the second
+    component), with rounder_row0 in the dropped limb of both components."""
+    import torch
+    q, N = engine.ctx.q, engine.ctx.N
+    dest = engine.ntt.p.destination_arrays[level]
+    owner = engine.ntt.p.rescaler_loc[level]
+    q_drop = q[dest[owner][0]]
+    data = []
+    for comp in range(2):
+        # (the words are Python-integer work: the HIP engine and the checker engine of one test share them)
+        key = (engine.hash, len(dest), str(dest), level, pattern, seed, shift, comp)
+        rows = _PRE_RESCALE_CACHE.get(key)
+        if rows is None:
+            pat = pattern if comp == 0 or pattern in ("mixed", "random") else \
+                ENGINE_EDGE_PATTERNS[(ENGINE_EDGE_PATTERNS.index(pattern) + 1) % 4]
+            targets = []
+            for d in range(len(dest)):
+                keep = dest[d][1:] if d == owner else dest[d]
+                ids = [i + comp for i in keep] if pattern == "mixed" else keep
+                targets.append(edge_rows([q[i] for i in keep], N, pat, seed * 2 + comp, ids=ids))
+            rows = _PRE_RESCALE_CACHE[key] = pre_rescale(engine, level, targets, rounder_row0(q_drop, N, shift + 2 * comp))
+        data.append([torch.from_numpy(rows[d].copy()).to(engine.ntt.devices[d]) for d in _edge_ids(engine) if d < len(dest)])
+    return _edge_ct(engine, data, level)
+
+
+_PRE_RESCALE_CACHE = {}
+
+
+# ---- the engine's step kernels on hand-made operands ------------------------------------------------------------------
+def edge_param_sets():
+    """name -> engine parameters of tests/test_engine_edges_*.py (the ring is small: the point is arithmetic, not size)."""
+    base = dict(logN=13, is_secured=False)
+    sets = {f"sb40_K{K}": dict(base, scale_bits=40, num_scales=9, num_special_primes=K) for K in (1, 5, 7, 8)}
+    sets.update({f"sb41_K{K}": dict(base, scale_bits=41, num_scales=6, num_special_primes=K) for K in (2, 4)})
+    sets["sb45_K4"] = dict(base, scale_bits=45, num_scales=6, num_special_primes=4)
+    sets["sb45_K8"] = dict(base, scale_bits=45, num_scales=9, num_special_primes=8)     # 9 scales: a digit of 8 wide limbs
+    sets["sb20"] = dict(base, scale_bits=20, num_scales=8, num_special_primes=2)
+    return sets
+
+
+class StepTables:
+    """What the backend's step methods take, from an engine's own per-level tables (one device)."""
+
+    def __init__(self, eng, level, d=0):
+        self.eng, self.level, self.d = eng, level, d
+        self.dev = eng.ntt.devices[d]
+        self.N, self.logN, self.K = eng.ctx.N, eng.ctx.logN, eng.ntt.num_special_primes
+        self.rows, self.ell = eng._rows(d, level, True), eng._rows(d, level, False)
+        self.c_ord, self.c_all = eng._consts(d, level, False), eng._consts(d, level, True)
+        tabs = self.tabs = eng._ks_tables(level)
+        self.n_digits, self.d_desc, self.d_tab = tabs[("digits", d)]
+        self.e_desc, self.E, self.Ed = tabs[("extend", d)]
+        self.nparts, self.first_part, self.row_off = len(tabs["order"]), tabs["first_part"], eng.ntt.starts[level][d]
+        self.pir, self.pip, self.own = tabs[("pir", d)], tabs[("pip", d)], tabs[("own", d)]
+        self.Rs_all, self.Rs_ord = eng._vec("Rs", d, level, True), eng._vec("Rs", d, level, False)
+        self.q2_ord = eng._vec("_2q", d, level, False)
+        self.psi, self.ipsi = eng._tw(d, level, True), eng._tw(d, level, True, True)
+        self.psi_ord, self.ipsi_ord = eng._tw(d, level, False), eng._tw(d, level, False, True)
+        self.ninv, self.ninv_ord = eng._vec("Ninv", d, level, True), eng._vec("Ninv", d, level, False)
+        ids = eng.ntt.p.destination_arrays_with_special[level][d]
+        self.ids_all, self.ids_ord = list(ids), list(ids[:self.ell])
+        self.q_all = [int(eng.ctx.q[i]) for i in ids]
+        self.q_ord = self.q_all[:self.ell]
+        self.order = [(rows, [int(eng.ctx.q[i]) for i in primes]) for _, rows, primes in tabs["order"]]
+
+    def put(self, x):
+        import torch
+        return torch.from_numpy(np.ascontiguousarray(x)).to(self.dev)
+
+    def new(self, *shape):
+        """An output buffer pre-filled with -1 with one guard entry behind the last one along the first dimension (a row of
+        a polynomial, a polynomial of a stack): `body` is what the call gets, `guard_ok` is asked afterwards."""
+        import torch
+        return torch.full((shape[0] + 1,) + tuple(shape[1:]), -1, dtype=torch.int64, device=self.dev)
+
+
+def body(buf):
+    return buf[:-1]
+
+
+def guard_ok(buf):
+    return bool((buf[-1] == -1).all())
+
+
+DIGIT_WORD_BOUND = (1 << 43) - 1      # csrc/ckks_ks.hip: "signed digit words (|y| < 2^43)" of digits made of fp64-class limbs
+
+
+def step_operands(T, pattern, key_pattern, seed, N=None):
+    """The operands of one case of the step kernels, as host arrays (the HIP side and the checker side get copies):
+      a         [ell, N]  canonical coefficient words: the polynomial a key switch decomposes
+      x         [4, ell, N] lazy NTT-domain words: the operands of the tensor product (x0, x1, y0, y1)
+      state_hi  [ell, N]  digit words AT the bound the extension kernels document: +-(2^43 - 1) by the Thue-Morse parity in
+                digits whose limbs are all below 2^41, +-(2q - 1) in the others
+      ext       [nparts, rows, N] lazy words: extended digits in the NTT domain, Montgomery form
+      key       [parts, 2, rows0, N] lazy key words (key_pattern)
+      s         [2, rows, N] canonical words: the sums a mod-down divides by P
+      add       [2, ell, N] canonical addends"""
+    N = T.N if N is None else N
+    op = {"a": edge_rows(T.q_ord, N, pattern, seed, ids=T.ids_ord),
+          "x": np.stack([edge_rows(T.q_ord, N, pattern, seed + 1 + i, lazy=True, ids=[j + i for j in T.ids_ord]) for i in range(4)]),
+          "ext": np.stack([edge_rows(T.q_all, N, pattern, seed + 10 + p, lazy=True, ids=[j + p for j in T.ids_all])
+                           for p in range(T.nparts)]),
+          "s": np.stack([edge_rows(T.q_all, N, pattern, seed + 30 + c, ids=[j + c for j in T.ids_all]) for c in range(2)]),
+          "add": np.stack([edge_rows(T.q_ord, N, pattern, seed + 40 + c, ids=[j + 1 + c for j in T.ids_ord]) for c in range(2)])}
+    q0 = T.eng.ctx.q
+    ids0 = T.eng.ntt.p.destination_arrays_with_special[0][T.d]
+    nk = T.eng.ntt.p.num_partitions + 1
+    op["key"] = np.stack([np.stack([edge_rows([q0[i] for i in ids0], N, key_pattern, seed + 50 + 2 * g + c, lazy=True,
+                                              ids=[j + g + c for j in ids0]) for c in range(2)]) for g in range(nk)])
+    sign = 1 - 2 * thue_morse(N)
+    hi = np.empty((T.ell, N), dtype=np.int64)
+    for rows, primes in T.order:
+        small = all(m < SMALL_PRIME_LIMIT for m in primes)
+        for r, m in zip(rows, primes):
+            hi[r] = sign * (DIGIT_WORD_BOUND if small else 2 * m - 1)
+    op["state_hi"] = hi
+    return op

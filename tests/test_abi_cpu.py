@@ -111,6 +111,26 @@ def test_limits_are_exported_and_checked_by_the_engine():
         ckks_engine(devices=["cpu"], backend=ob, logN=14, num_special_primes=10, num_scales=10, is_secured=False)
 
 
+def test_the_advertised_limits_admit_the_edge_parameter_sets():
+    """Exactly at the limits: 8 special primes with a digit of 8 limbs pass the engine's check (the kernels are run there by
+    tests/test_engine_edges_gpu.py), 9 do not; every parameter set of that file passes."""
+    import pytest
+    from liberate_fhe_amd.fhe import ckks_engine
+    from liberate_fhe_amd.fhe.backend import HipBackend
+    from liberate_fhe_amd.fhe.presets import errors
+    from tests.helpers import edge_param_sets
+    from tests.oracle_backend import OracleBackend
+    ob = OracleBackend()
+    ob.limits = HipBackend.limits
+    for name, params in edge_param_sets().items():
+        eng = ckks_engine(devices=["cpu"], backend=ob, **params)
+        assert eng.ntt.num_special_primes == params["num_special_primes"], name
+    eng = ckks_engine(devices=["cpu"], backend=ob, **edge_param_sets()["sb45_K8"])
+    assert max(len(part) for part in eng.ntt.p.p[0][0]) == 8 == HipBackend.limits["digit_limbs"]
+    with pytest.raises(errors.KernelLimitExceeded):
+        ckks_engine(devices=["cpu"], backend=ob, **dict(edge_param_sets()["sb40_K8"], num_special_primes=9, num_scales=10))
+
+
 def test_unpickler_refuses_foreign_globals(tmp_path):
     """load() resolves only the container class and the tensor / array reconstructors."""
     import io

@@ -524,6 +524,32 @@ int lf_rotate_hoisted(const lf_ks_plan *plan, const int64_t *c0, const int64_t *
                       const int64_t *const *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format, int64_t *ws,
                       int64_t ws_words, int64_t *const *out0, int64_t *const *out1, void *stream);
 
+/* Linear transform by the diagonal method ("double hoisting"): out = rescale(moddown(sum_i pt_i * (ks_i + P c0(X^p_i)))), the
+ * ciphertext that decrypts to sum_i diag_i * rot(m, step_i) one level below (c0, c1).  nr >= 0 keys with odd exponents p_host[i]
+ * < 2N (HOST arrays as lf_rotate_hoisted); pt: the nr encoded diagonals in key order, pt + i * pt_stride = [ell + K][N] words in
+ * the NTT domain and Montgomery form over the ordinary AND the special rows; pt0: the diagonal of step 0 or NULL — that term
+ * needs no key (nr = 0 with pt0 is legal).  Multiplication by a plaintext and addition commute with the mod-down, so the diagonals
+ * are multiplied in while the key-switch sums are still in the NTT domain over Q P and everything behind the inner product happens
+ * once.  The result has exactly the words of: c0, c1 made canonical; E = per digit pre_extend(c1), extend, exact forward NTT;
+ * c^ = P * enter_ntt(c) on the ordinary rows; per key t_c = sum over the digits of E gathered by pi_{p_i} times the key part
+ * (mont_mult, mont_add), t_0 += c^0 gathered by pi_{p_i} on the ordinary rows; step 0: t_c = c^c, zero on the special rows;
+ * S_c = sum_i mont_mult(pt_i, t_c); intt_exit_reduce, mod-down (no addend), ckks_engine.rescale.  Only the residues of S_c reach
+ * the result, so the kernels use the relaxed arithmetic of the other fused ops.
+ * Enqueued: a canonical copy of c0 (c1 with pt0), ONE forward NTT of it (enter_ntt) on the ell ordinary rows and the product with
+ * plan->PR; lf_ks_digits_galois (gal_pinv = 1) and lf_ks_fwd once (nr > 0); per group of 4, 2 or 1 keys one launch of
+ * ks_inner_lt_kernel, all groups adding into the ONE pair plan->sum (nr = 0: one launch without keys); one inverse NTT of the
+ * pair (its planes pass through plan->ext, which is spent by then); one mod-down; one lf_rescale_batch with rescale_scales /
+ * round_at of the level the ciphertext leaves ([ell - 1] words q_l^-1 R; plan->rescale_scales is the level's INCOMING one) into
+ * out0 / out1 [ell - 1][N].  P c^ and the mod-down's [2][ell][N] result live in plan->x4 (free during this op) or, with
+ * plan->x4 = NULL, in `ws` of at least lf_linear_transform_ws_words(plan) words (0: ws may be NULL).
+ * LF_ERR_ARG before any launch for everything lf_rotate_hoisted refuses (nr < 0 instead of nr < 1), a NULL pt with nr > 0,
+ * nr = 0 without pt0, a NULL rescale_scales, plan->PR = NULL and ell < 2 (no level left to rescale into). */
+int64_t lf_linear_transform_ws_words(const lf_ks_plan *plan);
+int lf_linear_transform(const lf_ks_plan *plan, const int64_t *c0, const int64_t *c1, int nr, const int64_t *p_host,
+                        const int64_t *const *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format,
+                        const int64_t *pt, int64_t pt_stride, const int64_t *pt0, const int64_t *rescale_scales, int64_t round_at,
+                        int64_t *ws, int64_t ws_words, int64_t *out0, int64_t *out1, void *stream);
+
 /* The halves of an op around the digit exchange of a limb-sharded engine (one process per GPU; the reference gathers every
  * digit on every GPU through the host before it extends any, ckks_engine.py:778-829).  The plan describes THIS rank's rows
  * at the level (dig_nparts = the digits it owns, nparts = all digits, state = its own digit rows):

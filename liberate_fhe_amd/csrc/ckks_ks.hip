@@ -818,6 +818,174 @@ __global__ void __launch_bounds__(256) ks_inner_hoist_kernel(const i64 *__restri
     }
 }
 
+// ---- K3 of a linear transform (lf_linear_transform): sum_i pt_i * (key switch sums of rotation i + P c0(X^p_i)) in Q P ----------
+// The hoisted inner product above, with the rotations never leaving the NTT domain over the extended basis: per key the sums
+// over the digits as there; on the ordinary rows + P c0 gathered by the same pi (the fold moddown(s) + d = moddown(s + P d));
+// both components times the key's encoded diagonal (NTT domain, Montgomery form, all rows) and added into ONE running pair
+// shared by every key.  The first group adds the step-0 term pt0 * P (c0, c1) (ordinary rows, no key); later groups add the
+// pair the previous group left in `s`.  The pair leaves in the format the sums' inverse pass reads (spl).
+// fp64 class: the sums t R are balanced; the diagonal's Montgomery word m R goes through one REDC to the plain m, so that
+// (t R) m is the Montgomery-form product; |running sums| <= (NR + 2) q, inside dp_reduce's 64 q.
+struct LtArgs {
+    HoistKeys hk;
+    const i64 *pt[4];    // encoded diagonal of key i, [rows][N]
+    const i64 *pt0;      // step-0 diagonal or nullptr (read by the first group only)
+    const i64 *chat;     // P NTT(c0), P NTT(c1): [2][ell][N], Montgomery form, words below 2q
+    int ell;             // ordinary rows (the first `ell` of the rows)
+    int first;           // first group: `s` is not read
+};
+
+template <int NR, bool PLANES, bool DPL>
+__global__ void __launch_bounds__(256) ks_inner_lt_kernel(const i64 *__restrict__ ext, LtArgs la, i64 part_stride, i64 comp_stride,
+                                                          i64 row_off, i64 *__restrict__ s, int nparts, int rows, int logN, int spl,
+                                                          const i64 *__restrict__ ql, const i64 *__restrict__ qh,
+                                                          const i64 *__restrict__ kl, const i64 *__restrict__ kh) {
+    constexpr int NA = NR ? NR : 1;
+    const int r = blockIdx.y;
+    const i64 N = (i64)1 << logN;
+    const i64 j0 = (i64)blockIdx.x * 512 + threadIdx.x * 2;
+    if (j0 >= N) return;
+    const RowMod m = load_mod(ql, qh, kl, kh, r);
+    const unsigned sh = 32u - (unsigned)logN, mask = (2u << logN) - 1u;
+    const unsigned bj = (2u * (__builtin_bitreverse32((unsigned)j0) >> sh) + 1u);
+    unsigned src[NA];
+    bool sw[NA];
+#pragma unroll
+    for (int i = 0; i < NR; ++i) {
+        const unsigned t = (bj * la.hk.p[i]) & mask;
+        const unsigned mi = __builtin_bitreverse32((t - 1u) >> 1) >> sh;
+        src[i] = mi & ~1u;
+        sw[i] = (mi & 1u) != 0;
+    }
+    const i64 krow = (row_off + r) * N;
+    const bool ord = r < la.ell;
+    const i64 *c0row = la.chat + (i64)r * N, *c1row = c0row + (i64)la.ell * N;   // (read on ordinary rows only)
+    i64 *srow0 = s + (i64)r * N, *srow1 = s + ((i64)rows + r) * N;
+    if (m.q < SMALL_PRIME_LIMIT) {
+        const RowDp d = make_dp(m);
+        double acc[NA][2][2];
+#pragma unroll
+        for (int i = 0; i < NR; ++i) acc[i][0][0] = acc[i][0][1] = acc[i][1][0] = acc[i][1][1] = 0.0;
+#pragma unroll KI_UNROLL
+        for (int p = 0; p < nparts; ++p) {
+            const i64 *er = ext + ((i64)p * rows + r) * N;
+#pragma unroll
+            for (int i = 0; i < NR; ++i) {
+                double xa, xb;
+                ld_pair_dp(er, (i64)src[i], N, DPL ? 1 : 0, xa, xb);
+                const double x0 = sw[i] ? xb : xa, x1 = sw[i] ? xa : xb;
+                const i64 *kr = la.hk.ksk[i] + krow + (i64)p * part_stride;
+                double k0x, k0y, k1x, k1y;
+                if (PLANES) {   // 16 + 8 bytes for both components (see lf_key_planes)
+                    const lf_u4_t l = __builtin_nontemporal_load(reinterpret_cast<const lf_u4_t *>(reinterpret_cast<const unsigned *>(kr) + 2 * j0));
+                    const lf_u2_t h = __builtin_nontemporal_load(reinterpret_cast<const lf_u2_t *>(reinterpret_cast<const unsigned *>(kr + comp_stride) + j0));
+                    k0x = dp_from_planes(l.x, h.x & 0xffffu), k0y = dp_from_planes(l.y, h.x >> 16);
+                    k1x = dp_from_planes(l.z, h.y & 0xffffu), k1y = dp_from_planes(l.w, h.y >> 16);
+                } else {
+                    const longlong2 k0 = ld_nt(kr + j0);
+                    const longlong2 k1 = ld_nt(kr + j0 + comp_stride);
+                    k0x = dp_from_word(k0.x), k0y = dp_from_word(k0.y), k1x = dp_from_word(k1.x), k1y = dp_from_word(k1.y);
+                }
+                acc[i][0][0] += dp_mulmod_bal(x0, k0x, d);
+                acc[i][0][1] += dp_mulmod_bal(x1, k0y, d);
+                acc[i][1][0] += dp_mulmod_bal(x0, k1x, d);
+                acc[i][1][1] += dp_mulmod_bal(x1, k1y, d);
+            }
+        }
+        double S[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
+        if (!la.first) {   // the pair the previous group left (canonical words)
+            ld_pair_dp(srow0, j0, N, spl, S[0][0], S[0][1]);
+            ld_pair_dp(srow1, j0, N, spl, S[1][0], S[1][1]);
+        } else if (la.pt0 != nullptr && ord) {
+            const longlong2 w = ld_nt(la.pt0 + (i64)r * N + j0);
+            const double wa = dp_from_word(mm62u((u64)w.x, 1ull, m.q, m.k)), wb = dp_from_word(mm62u((u64)w.y, 1ull, m.q, m.k));
+            double a0, b0, a1, b1;
+            ld_pair_dp(c0row, j0, N, 0, a0, b0);
+            ld_pair_dp(c1row, j0, N, 0, a1, b1);
+            S[0][0] = dp_mulmod_bal(a0, wa, d), S[0][1] = dp_mulmod_bal(b0, wb, d);
+            S[1][0] = dp_mulmod_bal(a1, wa, d), S[1][1] = dp_mulmod_bal(b1, wb, d);
+        }
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {
+            if (ord) {
+                double ca, cb;
+                ld_pair_dp(c0row, (i64)src[i], N, 0, ca, cb);
+                acc[i][0][0] += sw[i] ? cb : ca;
+                acc[i][0][1] += sw[i] ? ca : cb;
+            }
+            const longlong2 w = ld_nt(la.pt[i] + (i64)r * N + j0);
+            const double wa = dp_from_word(mm62u((u64)w.x, 1ull, m.q, m.k)), wb = dp_from_word(mm62u((u64)w.y, 1ull, m.q, m.k));
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                S[c][0] += dp_mulmod_bal(dp_reduce_bal(acc[i][c][0], d), wa, d);
+                S[c][1] += dp_mulmod_bal(dp_reduce_bal(acc[i][c][1], d), wb, d);
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            longlong2 o;
+            o.x = dp_to_word(dp_reduce(S[c][0], d.q, d.qinv));
+            o.y = dp_to_word(dp_reduce(S[c][1], d.q, d.qinv));
+            i64 *srow = c ? srow1 : srow0;
+            if (spl) {
+                const lf_u2_t l = {(unsigned)o.x, (unsigned)o.y};
+                *reinterpret_cast<lf_u2_t *>(reinterpret_cast<unsigned *>(srow) + j0) = l;
+                *reinterpret_cast<unsigned *>(reinterpret_cast<unsigned short *>(srow + (N >> 1)) + j0) =
+                    (unsigned)((u64)o.x >> 32) | ((unsigned)((u64)o.y >> 32) << 16);
+            } else {
+                *reinterpret_cast<longlong2 *>(srow + j0) = o;
+            }
+        }
+    } else {
+        i64 acc[NA][2][2];
+#pragma unroll
+        for (int i = 0; i < NR; ++i) acc[i][0][0] = acc[i][0][1] = acc[i][1][0] = acc[i][1][1] = 0;
+        for (int p = 0; p < nparts; ++p) {
+            const i64 *er = ext + ((i64)p * rows + r) * N;
+#pragma unroll
+            for (int i = 0; i < NR; ++i) {
+                const longlong2 v = *reinterpret_cast<const longlong2 *>(er + src[i]);
+                const u64 x0 = (u64)(sw[i] ? v.y : v.x), x1 = (u64)(sw[i] ? v.x : v.y);
+                const i64 *kr = la.hk.ksk[i] + krow + (i64)p * part_stride + j0;
+                const longlong2 k0 = ld_nt(kr);
+                const longlong2 k1 = ld_nt(kr + comp_stride);
+                acc[i][0][0] = csub(acc[i][0][0] + mm62u(x0, (u64)k0.x, m.q, m.k), m.q2);
+                acc[i][0][1] = csub(acc[i][0][1] + mm62u(x1, (u64)k0.y, m.q, m.k), m.q2);
+                acc[i][1][0] = csub(acc[i][1][0] + mm62u(x0, (u64)k1.x, m.q, m.k), m.q2);
+                acc[i][1][1] = csub(acc[i][1][1] + mm62u(x1, (u64)k1.y, m.q, m.k), m.q2);
+            }
+        }
+        i64 S[2][2] = {{0, 0}, {0, 0}};   // lazy words below 2q throughout
+        if (!la.first) {
+            const longlong2 a = *reinterpret_cast<const longlong2 *>(srow0 + j0), b = *reinterpret_cast<const longlong2 *>(srow1 + j0);
+            S[0][0] = a.x, S[0][1] = a.y, S[1][0] = b.x, S[1][1] = b.y;
+        } else if (la.pt0 != nullptr && ord) {
+            const longlong2 w = ld_nt(la.pt0 + (i64)r * N + j0);
+            const longlong2 a = *reinterpret_cast<const longlong2 *>(c0row + j0), b = *reinterpret_cast<const longlong2 *>(c1row + j0);
+            S[0][0] = mm62u((u64)a.x, (u64)w.x, m.q, m.k), S[0][1] = mm62u((u64)a.y, (u64)w.y, m.q, m.k);
+            S[1][0] = mm62u((u64)b.x, (u64)w.x, m.q, m.k), S[1][1] = mm62u((u64)b.y, (u64)w.y, m.q, m.k);
+        }
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {
+            if (ord) {
+                const longlong2 v = *reinterpret_cast<const longlong2 *>(c0row + src[i]);
+                acc[i][0][0] = csub(acc[i][0][0] + (sw[i] ? v.y : v.x), m.q2);
+                acc[i][0][1] = csub(acc[i][0][1] + (sw[i] ? v.x : v.y), m.q2);
+            }
+            const longlong2 w = ld_nt(la.pt[i] + (i64)r * N + j0);
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                S[c][0] = csub(S[c][0] + mm62u((u64)acc[i][c][0], (u64)w.x, m.q, m.k), m.q2);
+                S[c][1] = csub(S[c][1] + mm62u((u64)acc[i][c][1], (u64)w.y, m.q, m.k), m.q2);
+            }
+        }
+        longlong2 o0, o1;
+        o0.x = S[0][0], o0.y = S[0][1], o1.x = S[1][0], o1.y = S[1][1];
+        *reinterpret_cast<longlong2 *>(srow0 + j0) = o0;
+        *reinterpret_cast<longlong2 *>(srow1 + j0) = o1;
+    }
+}
+
 // largest number of leading stages (logN - 12) whose extension + strided pass runs as the column kernel (lf_tune).
 // With the digit loop as a runtime loop (R loads in flight, 100 VGPRs at R = 16) the column form also wins at logN 16:
 // gold cc_mult 2 104-2 130 -> 2 168-2 183 ops/s, rotate 2 653-2 695 -> 2 733-2 763, 64 rotations under one key
@@ -1056,6 +1224,64 @@ int lf_ks_tail_hoisted(int nr, const unsigned *p, int nparts, int rows, int logN
 #undef LF_HOIST_CASE
     return ks_inv_sums(2 * nr, rows, logN, spl, cols_last, mixed, in, dp, (i64 *)scratch, (i64 *)s, ipsi_br, ipsi_dp, Ninv, ql, qh, kl,
                        kh, st);
+}
+
+// The key-dependent part of lf_linear_transform (ckks_ops.hip): per group of up to 4 keys ONE launch of ks_inner_lt_kernel over
+// the shared extended digits `ext` (nr = 0: the step-0 term alone, one launch without keys), all of them adding into the one
+// pair of sums s [2][rows][N]; then the inverse transform of that pair.  `scratch` (>= 2 rows N words, or NULL: the sums stay
+// raw words, same outputs) carries the sums' planes through the tiled inverse pass; it may be `ext` itself, which is spent
+// once the last group has read it.  chat = P NTT(c0), P NTT(c1) on the `ell` ordinary rows.  Internal: ckks_ops.hip checks the
+// arguments (nr >= 0, odd exponents below 2N, pt0 != NULL when nr == 0).
+int lf_ks_tail_lt(int nr, const int64_t *p_host, int nparts, int rows, int ell, int logN, const int64_t *const *ksk, int64_t part_stride,
+                  int64_t comp_stride, int64_t row_off, int key_format, const int64_t *pt, int64_t pt_stride, const int64_t *pt0,
+                  const int64_t *chat, const int64_t *ext, int64_t *s, int64_t *scratch, int64_t scratch_words, const int64_t *ipsi_br,
+                  const double *ipsi_dp, const int64_t *Ninv, const int64_t *q_host, const int64_t *ql, const int64_t *qh,
+                  const int64_t *kl, const int64_t *kh, hipStream_t st) {
+    if (!ipsi_dp || (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES) || nr < 0 || (nr == 0 && !pt0) || !chat || ell < 0 || ell > rows)
+        return LF_ERR_ARG;
+    for (int i = 0; i < nr; ++i)
+        if (!ksk[i] || !pt || (key_format == LF_KEY_PLANES && ((((uintptr_t)ksk[i] | (uintptr_t)(part_stride * 8) | (uintptr_t)(comp_stride * 8)) & 15))))
+            return LF_ERR_ARG;
+    const int tl = NTT_TILE_LOG_MAX, S1 = logN - tl;
+    RowList dp, in;
+    classify_rows(rows, q_host, dp, in);
+    const bool mixed = dp.n && in.n;
+    const bool dplanes = digit_planes(logN, dp, in);
+    const bool cols_last = S1 <= 4 || (S1 == 5 && mixed && g_ks_ext_cols_max > 4);
+    if (nr)   // the digits must be in the format the groups read (see ks_tail)
+        if (int e = lf_fmt_expect(ext, ((size_t)nparts * rows << logN) * 8, dplanes ? LF_FMT_PLANES : LF_FMT_RAW)) return e;
+    const bool spl = dplanes && (g_more_planes & 1) && cols_last && scratch && scratch_words >= ((int64_t)2 * rows << logN);
+    const dim3 grid((unsigned)((((i64)1 << logN) + 511) / 512), (unsigned)rows);
+    const bool planes = key_format == LF_KEY_PLANES;
+#define LF_LT_LAUNCH(NR, PL, DPLB)                                                                                         \
+    hipLaunchKernelGGL((ks_inner_lt_kernel<NR, PL, DPLB>), grid, dim3(256), 0, st, (const i64 *)ext, la, (i64)part_stride,  \
+                       (i64)comp_stride, (i64)row_off, (i64 *)s, nparts, rows, logN, spl ? 1 : 0, (const i64 *)ql, (const i64 *)qh, \
+                       (const i64 *)kl, (const i64 *)kh)
+#define LF_LT_CASE(NR)                                                                                                     \
+    case NR:                                                                                                               \
+        if (planes && dplanes) LF_LT_LAUNCH(NR, true, true);                                                              \
+        else if (planes) LF_LT_LAUNCH(NR, true, false);                                                                   \
+        else if (dplanes) LF_LT_LAUNCH(NR, false, true);                                                                  \
+        else LF_LT_LAUNCH(NR, false, false);                                                                              \
+        break;
+    for (int i0 = 0; i0 < nr || i0 == 0;) {
+        const int left = nr - i0, g = left >= 4 ? 4 : left >= 2 ? 2 : left;
+        LtArgs la{};
+        for (int t = 0; t < g; ++t) {
+            la.hk.ksk[t] = (const i64 *)ksk[i0 + t];
+            la.hk.p[t] = (unsigned)p_host[i0 + t];
+            la.pt[t] = (const i64 *)pt + (i64)(i0 + t) * pt_stride;
+        }
+        la.pt0 = (const i64 *)pt0, la.chat = (const i64 *)chat, la.ell = ell, la.first = i0 == 0;
+        switch (g) {
+            LF_LT_CASE(1) LF_LT_CASE(2) LF_LT_CASE(4)
+            case 0: LF_LT_LAUNCH(0, false, false); break;
+        }
+        i0 += g ? g : 1;
+    }
+#undef LF_LT_LAUNCH
+#undef LF_LT_CASE
+    return ks_inv_sums(2, rows, logN, spl, cols_last, mixed, in, dp, (i64 *)scratch, (i64 *)s, ipsi_br, ipsi_dp, Ninv, ql, qh, kl, kh, st);
 }
 
 // cc_mult's product -> digits in one launch behind the tiled pass where it qualifies (ckks_ops.hip: product_digits): 0 = never

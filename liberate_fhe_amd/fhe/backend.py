@@ -418,6 +418,30 @@ class HipBackend:
                                     _p(ws), 0 if ws is None else ws.numel(), _parr([out[i][0] for i in range(n)]),
                                     _parr([out[i][1] for i in range(n)]), st), "lf_rotate_hoisted")
 
+    @staticmethod
+    def linear_transform_ws_words(plan):
+        return int(lib.lf_linear_transform_ws_words(ctypes.byref(plan)))
+
+    def linear_transform_native(self, plan, c0, c1, exponents, keys, first_part, row_off, pt, pt0, scales, round_at, out, ws=None):
+        """sum_i pt[i] * rot_i(c0, c1) (+ pt0 * (c0, c1)), mod-down and rescale as ONE native call (lf_linear_transform).
+        keys: packed key tensors of one format and shape, exponents their Galois exponents; pt [len(keys), rows, N] the encoded
+        diagonals in key order (None without keys), pt0 [rows, N] the step-0 diagonal or None; scales / round_at: the rescale
+        constants of the level the ciphertext leaves; out [2, ell - 1, N]."""
+        dev, st = _ds(out)
+        n = len(keys)
+        bases = (ctypes.c_void_p * max(n, 1))()
+        ps = cs = 0
+        for i, key in enumerate(keys):
+            bases[i], ps, cs = self._key_args(key, first_part)
+        fmt = {self._kfmt(k) for k in keys}
+        if len(fmt) > 1:
+            raise ValueError("linear_transform_native: the keys of one call must share one format")
+        exps = (ctypes.c_int64 * max(n, 1))(*exponents)
+        check(lib.lf_linear_transform(ctypes.byref(plan), _p(c0), _p(c1), n, exps, bases, ps, cs, row_off, fmt.pop() if fmt else 0,
+                                      _p(pt), 0 if pt is None else pt.stride(0), _p(pt0), _p(scales), round_at, _p(ws),
+                                      0 if ws is None else ws.numel(), out.data_ptr(), out.data_ptr() + out.stride(0) * 8, st),
+              "lf_linear_transform")
+
     def ks_gather(self, ext, dst, index, rows, logN, c: Consts):
         """dst[p][r][k] = ext[p][r][index[k]] for extended digits as ks_fwd leaves them: fp64-class rows of a mixed stack in the
         planes format (u32 low words at byte 0, u16 high halves at byte 4 N of the row: LF_TUNE_DIGIT_PLANES), other rows raw

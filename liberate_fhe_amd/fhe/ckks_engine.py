@@ -1832,6 +1832,205 @@ class ckks_engine(EvaluatorOps):
             hit = self._tables[key] = torch.from_numpy(encdec.ntt_galois_index(self.ctx.logN, p)).to(self.ntt.devices[d])
         return hit
 
+    # =============================================================================================
+    # linear transform: sum of diagonals times rotations ("double hoisting"; the reference has no such entry)
+    # =============================================================================================
+    def encode_diagonals(self, diagonals, level: int) -> data_struct:
+        """The plaintext side of linear_transform, built once and applied to many ciphertexts of `level`.  diagonals: {step:
+        vector} (steps taken mod num_slots; vectors as encode takes them).  Per step m * sqrt(deviations[level + 1]) encoded at
+        level 0 as mc_mult does, tiled over the ordinary rows of `level` AND the special rows, NTT domain, Montgomery form.  ONE
+        pack [k, rows, N] per local device, steps ascending; `data` = per step the per-device [rows, N] views of it; the origin
+        carries the steps ("plain diagonals:0,1,5,700")."""
+        if level + 1 >= self.num_levels:
+            raise errors.MaximumLevelError(level=level, level_max=self.num_levels)
+        by_step = {}
+        for delta, m in dict(diagonals).items():
+            step = int(delta) % self.num_slots
+            if step in by_step:
+                raise ValueError(f"encode_diagonals: step {delta} given twice (steps are taken mod {self.num_slots})")
+            by_step[step] = m
+        if not by_step:
+            raise ValueError("encode_diagonals: no diagonal given")
+        steps = sorted(by_step)
+        packs = None
+        for j, step in enumerate(steps):
+            m = np.array(by_step[step]) * np.sqrt(self.deviations[level + 1])
+            pt = self.ntt.tile_unsigned(self.encode(m, 0), level, -2)
+            self.ntt.enter_ntt(pt, level, -2)
+            if packs is None:
+                packs = [torch.empty((len(steps),) + tuple(t.shape), dtype=torch.int64, device=t.device) for t in pt]
+            for pk, t in zip(packs, pt):
+                pk[j].copy_(t)
+        out = self._new([[pk[j] for pk in packs] for j in range(len(steps))],
+                        types.origins["diag"] + ",".join(str(s) for s in steps), level=level, include_special=True,
+                        ntt_state=True, montgomery_state=True)
+        self._remember_diag_pack(out, packs, own=True)
+        return out
+
+    @staticmethod
+    def diagonal_steps(diags) -> list:
+        """The steps of an encode_diagonals object, in the order of its data."""
+        return [int(s) for s in diags.origin.split(":", 1)[1].split(",")]
+
+    def _remember_diag_pack(self, diags, packs, own):
+        anchor = diags.data[0][0]
+        key = ("diag", id(anchor))
+        self._key_packs[key] = {"ref": weakref.ref(anchor), "packs": packs,
+                                "versions": None if own else tuple(t._version for row in diags.data for t in row)}
+        weakref.finalize(anchor, self._key_packs.pop, key, None)
+        return packs
+
+    def _diag_pack(self, diags):
+        """Per local device the [k, rows, N] pack of an encode_diagonals object.  encode_diagonals' own object is a set of views
+        of its packs; one whose tensors no longer share a pack (after load / cuda) is packed once and cached, the way _key_pack
+        treats a foreign key (rebuilt when a tensor has been modified in place since)."""
+        anchor = diags.data[0][0]
+        hit = self._key_packs.get(("diag", id(anchor)))
+        if hit is not None and hit["ref"]() is anchor and \
+                (hit["versions"] is None or hit["versions"] == tuple(t._version for row in diags.data for t in row)):
+            return hit["packs"]
+        packs = [torch.stack([row[i] for row in diags.data]).contiguous() for i in range(len(diags.data[0]))]
+        return self._remember_diag_pack(diags, packs, own=False)
+
+    def linear_transform(self, ct: data_struct, diags, rotks) -> data_struct:
+        """sum over the steps of diags of diag_step * rotate(ct, step) as ONE ciphertext at ct.level + 1: decrypts to
+        sum diag_step * np.roll(m, step) (rotate_single's direction).  diags: what encode_diagonals returned (a plain {step:
+        vector} mapping is encoded here, at ct.level); rotks: a list or mapping of rotation keys, looked up by the step in their
+        origin; step 0 needs no key.  Multiplication by a plaintext and addition commute with the mod-down, so the diagonals are
+        multiplied in while the key-switch sums are still in the NTT domain over Q P, summed there and brought down once: per
+        diagonal only the gathered inner product with its key remains.  The words are those of: c0, c1 made canonical; E = per
+        part pre_extend(c1) -> extend -> exact forward NTT (rotate_hoisted's shared half); c^ = P * enter_ntt(c) on the ordinary
+        rows; per key t_c = sum over the parts of E gathered by pi_p times the key part, t_0 += c^0 gathered by pi_p on the
+        ordinary rows (step 0: t_c = c^c, zero on the special rows); S_c = sum of mont_mult(pt_step, t_c); intt_exit_reduce,
+        mod-down, rescale.  One native call (lf_linear_transform) where every limb of the level is on one device of this process;
+        otherwise the same words through the engine's steps.  Coefficient-domain ciphertexts without special limbs only."""
+        if ct.origin != types.origins["ct"]:
+            raise errors.NotMatchType(origin=ct.origin, to=types.origins["ct"])
+        keys = list(rotks.values()) if isinstance(rotks, dict) else list(rotks)
+        by_step = {}
+        for k in keys:
+            if not is_struct(k) or types.origins["rotk"] not in k.origin:
+                raise errors.NotMatchType(origin=getattr(k, "origin", type(k).__name__), to=types.origins["rotk"])
+            by_step.setdefault(int(k.origin.split(":")[-1]) % self.num_slots, k)
+        if ct.ntt_state or ct.include_special:
+            raise NotImplementedError("linear_transform: coefficient-domain ciphertexts without special limbs only")
+        level, N, logN = ct.level, self.ctx.N, self.ctx.logN
+        if level + 1 >= self.num_levels:
+            raise errors.MaximumLevelError(level=level, level_max=self.num_levels)
+        if not is_struct(diags):
+            diags = self.encode_diagonals(diags, level)
+        if not diags.origin.startswith(types.origins["diag"]):
+            raise errors.NotMatchType(origin=diags.origin, to=types.origins["diag"])
+        if diags.level != level:
+            raise errors.NotMatchDataStructState(origin=f"{diags.origin} at level {diags.level}, ciphertext at level {level}")
+        steps = self.diagonal_steps(diags)
+        for s in steps:
+            if s and s not in by_step:
+                raise errors.NotMatchType(origin=f"no key for step {s}", to=types.origins["rotk"] + str(s))
+        j0 = steps.index(0) if 0 in steps else None
+        sel = [j for j, s in enumerate(steps) if s]                       # rows of the pack that need a key, in pack order
+        rkeys = [by_step[steps[j]] for j in sel]
+        exps = [encdec.galois_exponent(N, steps[j]) for j in sel]
+        owner = self.ntt.p.rescaler_loc[level]
+        round_at = self.ctx.q[self.ntt.p.destination_arrays[level][owner][0]] // 2
+
+        d = self._native_level(level)
+        if d is not None and hasattr(self.backend, "linear_transform_native") and \
+                ct.data[0][0].is_contiguous() and ct.data[1][0].is_contiguous():
+            plan, _, first_part, row_off = self._op_plan(level, d)
+            i0 = self._loc(0, special=True).index(d)
+            pack = self._diag_pack(diags)[self.local_ids.index(d)]
+            pt = None
+            if sel:   # step 0 sorts first: the keyed diagonals are one slice of the pack (any other order: a copy)
+                pt = pack[sel[0]:sel[-1] + 1] if sel[-1] - sel[0] + 1 == len(sel) else pack[sel].contiguous()
+            words = self.backend.linear_transform_ws_words(plan)
+            ws = self._ws("lt_ws", (words,), d) if words else None
+            out = torch.empty((2, plan.ell - 1, N), dtype=torch.int64, device=self.ntt.devices[d])
+            self.backend.linear_transform_native(plan, ct.data[0][0], ct.data[1][0], exps, [self._key_pack(k)[i0] for k in rkeys],
+                                                 first_part, row_off, pt, None if j0 is None else pack[j0],
+                                                 self.rescale_scales[level][d], round_at, out, ws)
+            return self._new(([out[0]], [out[1]]), types.origins["ct"], level=level + 1)
+
+        # orchestrated: the same words through the engine's steps.  Digits of c1 and their exchange once, extension + forward
+        # NTT once per device (rotate_hoisted's shared half), c^ per device on its own rows; per key the gather, the key's inner
+        # product (through the fused tail where the key pack is in the planes format: its inverse NTT is undone by an exact
+        # forward one — the same residues), the products with the diagonal; ONE inverse NTT, mod-down and rescale per device
+        tabs = self._ks_tables(level)
+        loc, loc0 = self._loc(level), self._loc(0, special=True)
+        K, n = self.ntt.num_special_primes, self.ntt
+        nparts = len(tabs["order"])
+        fused = logN >= self.backend.fused_ks_min_logN
+        gather = getattr(self.backend, "ks_gather", None)
+        digits = self._ks_digits_exchanged(ct.data[1], level, galois=(1, True)) if sel else {}
+        c0o, c1o = [], []
+        for i, d in enumerate(loc):
+            li = self.local_ids.index(d)
+            rows, ell = self._rows(d, level, True), self._rows(d, level, False)
+            cs, cso = self._consts(d, level, True), self._consts(d, level, False)
+            tw, itw, ninv = self._tw(d, level, True), self._tw(d, level, True, True), self._vec("Ninv", d, level, True)
+            mont = [x[li:li + 1] for x in n.mont_prepack[-2][level][0]]
+            _2q = [n._2q_prepack[-2][level][0][li]]
+            g2q = self._vec("_2q", d, level, False)
+            dev = self.ntt.devices[d]
+            # c^0, c^1 = P * enter_ntt(canonical c) on the ordinary rows
+            chat = torch.empty((2, ell, N), dtype=torch.int64, device=dev)
+            for comp in range(2):
+                src = ct.data[comp][i] if ct.data[comp][i].is_contiguous() else ct.data[comp][i].contiguous()
+                self.backend.galois(src, chat[comp], ell, logN, 1, g2q)
+                self.backend.ntt(chat[comp], 1, ell, logN, self._tw(d, level, False), self._vec("Rs", d, level, False), cso)
+                n.ops.mont_enter([chat[comp]], [self._PR(d, level)], *[x[li:li + 1] for x in n.mont_prepack[-1][level][0]])
+            S = [None, None]
+
+            def accumulate(t, ptj):
+                for comp in range(2):
+                    prod = n.ops.mont_mult([ptj], [t[comp]], *mont)[0]
+                    S[comp] = prod if S[comp] is None else n.ops.mont_add([S[comp]], [prod], _2q)[0]
+
+            if j0 is not None:
+                t = torch.zeros((2, rows, N), dtype=torch.int64, device=dev)
+                t[:, :ell] = chat
+                accumulate(t, diags.data[j0][li])
+            if sel:
+                desc, E, Ed = tabs[("extend", d)]
+                ext = self._ws("ks_ext", (nparts, rows, N), d)
+                dig, ready = digits[d]
+                for handle, first, count in ready:
+                    if handle is not None:
+                        handle.wait()
+                    if fused:
+                        self.backend.ks_fwd(dig, first, count, rows, logN, desc, E, Ed, ext, tw, cs)
+                if not fused:
+                    self.backend.ks_extend(dig, ext, nparts, rows, desc, E, cs)
+                    self.backend.ntt(ext, nparts, rows, logN, tw, None, cs, relaxed=True)
+                src = self._ws("ks_ext_hoisted", (nparts, rows, N), d)   # (see rotate_hoisted: `ext` receives each key's gather)
+                src.copy_(ext)
+                s = self._ws("ks_sum", (2, rows, N), d)
+                Rs = self._vec("Rs", d, level, True)
+                for j, key, p in zip(sel, rkeys, exps):
+                    idx = self._galois_index(p, d)
+                    if gather is not None:
+                        gather(src, ext, idx, rows, logN, cs)
+                    else:
+                        torch.index_select(src, 2, idx, out=ext)
+                    kp = self._key_pack(key)[loc0.index(d)]
+                    if fused:
+                        self.backend.ks_tail(nparts, rows, logN, kp, tabs["first_part"], self.ntt.starts[level][d], ext, s, itw, ninv, cs)
+                        self.backend.ntt(s, 2, rows, logN, tw, Rs, cs)     # back into the NTT domain, Montgomery form
+                    else:
+                        self.backend.ks_inner(ext, kp, tabs["first_part"], self.ntt.starts[level][d], s[0], s[1], nparts, rows, cs)
+                    t = s.clone()
+                    t[0, :ell] = n.ops.mont_add([t[0, :ell]], [chat[0].index_select(1, idx)], [_2q[0][:ell]])[0]
+                    accumulate(t, diags.data[j][li])
+            s2 = torch.stack(S).contiguous()
+            self.backend.intt(s2, 2, rows, logN, itw, ninv, 2, cs)         # intt_exit_reduce: canonical coefficients
+            out = torch.empty((2, ell, N), dtype=torch.int64, device=dev)
+            ws, one = self._moddown_ws("ks_moddown", 2, ell, K, d, tabs, cs)
+            mkw = {"one_launch": True} if one else {}
+            self.backend.ks_moddown_ws([s2[0], s2[1]], [out[0], out[1]], [None, None], ell, K, ws, tabs[("pir", d)],
+                                       self._vec("Rs", d, level, True), cs, PiP=tabs[("pip", d)], **mkw)
+            c0o.append(out[0]); c1o.append(out[1])
+        return self.rescale(self._new((c0o, c1o), types.origins["ct"], level=level))
+
     def _prepare_ks(self, key, level):
         """Build, on the CURRENT stream, every lazily built piece of shared state a key switch at `level` under
         `key` reads: the packed key, the per-level descriptor tables, the fp64 twins of the twiddle tables."""

@@ -116,6 +116,22 @@ def conjugation_exponent(N: int) -> int:
     return 2 * N - 1
 
 
+def matrix_diagonals(M) -> dict:
+    """The non-zero generalized diagonals of a square matrix, {step: vector} with diag_step[i] = M[i][(i - step) mod n]: the
+    convention in which M @ v = sum_step diag_step * np.roll(v, step), i.e. what ckks_engine.linear_transform evaluates."""
+    M = np.asarray(M)
+    if M.ndim != 2 or M.shape[0] != M.shape[1]:
+        raise ValueError(f"matrix_diagonals: a square matrix is required, got shape {M.shape}")
+    n = M.shape[0]
+    i = np.arange(n)
+    out = {}
+    for step in range(n):
+        dg = M[i, (i - step) % n]
+        if np.any(dg != 0):
+            out[step] = dg
+    return out
+
+
 def ntt_galois_index(logN: int, p: int) -> np.ndarray:
     """pi_p as an int64 index array: NTT(a(X^p))[k] = NTT(a)[pi_p(k)] for the forward transform's order (index k holds the
     evaluation at psi^(2 brev(k) + 1)), pi_p(k) = brev(((2 brev(k) + 1) p mod 2N - 1) / 2).  A pure permutation (p odd):

@@ -9,4 +9,5 @@ origins = dict(
     conjk="conjugation key",
     ct="cipher text",
     ctt="cipher text triplet",
+    diag="plain diagonals:",   # ckks_engine.encode_diagonals: followed by the steps, as a rotation key's tag by its step
 )

@@ -81,6 +81,27 @@ def key_switch_key(engine, seed: int, origin: str = "key switch key", ds_type=No
     return out
 
 
+def diagonals(engine, seed: int, level: int, steps, ds_type=None):
+    """What ckks_engine.encode_diagonals returns for the (ascending) `steps`, with synthetic words: per step lazy NTT /
+    Montgomery words over the ordinary rows of `level` and the special rows, one pack [k, rows, N] per local device."""
+    ds_type = ds_type or _data_struct(engine)
+    q, N, p = engine.ctx.q, engine.ctx.N, engine.ntt.p
+    steps = sorted(int(s) for s in steps)
+    packs = []
+    for d in _ids(engine):
+        dest = p.destination_arrays_with_special[level][d]
+        pack = np.empty((len(steps), len(dest), N), dtype=np.int64)
+        for j, s in enumerate(steps):
+            pack[j] = uniform_rows(seed * 8192 + s, dest, q, N, lazy=True)
+        packs.append(torch.from_numpy(pack).to(engine.ntt.devices[d]))
+    out = ds_type(data=[[pk[j] for pk in packs] for j in range(len(steps))], include_special=True, ntt_state=True,
+                  montgomery_state=True, origin="plain diagonals:" + ",".join(str(s) for s in steps), level=level,
+                  hash=engine.hash, version=engine.version)
+    if hasattr(engine, "_remember_diag_pack"):
+        engine._remember_diag_pack(out, packs, own=True)   # the rows are views of the packs
+    return out
+
+
 def _data_struct(engine):
     import importlib
     mod = importlib.import_module(type(engine).__module__.rsplit(".", 1)[0] + ".data_struct")

@@ -550,6 +550,38 @@ int lf_linear_transform(const lf_ks_plan *plan, const int64_t *c0, const int64_t
                         const int64_t *pt, int64_t pt_stride, const int64_t *pt0, const int64_t *rescale_scales, int64_t round_at,
                         int64_t *ws, int64_t ws_words, int64_t *out0, int64_t *out1, void *stream);
 
+/* Linear transform by the diagonal method in its baby-step / giant-step form: out decrypts to
+ *     sum_g rot( sum_b diag_{g+b}(rolled by -g) * rot(m, b), g )        b = step mod n1, g = step - b,
+ * so that k diagonals need about n1 + k / n1 rotation keys (and key streams) instead of k.  nb >= 0 baby keys with odd
+ * exponents bp_host[i] < 2N and ng >= 1 giant steps (HOST arrays): gp_host[i] is the exponent of giant step i and gksk[i] its
+ * key, or gp_host[i] = 0 for the giant step 0, which has no key (gksk[i] is not read), comes first and at most once.  Baby SLOT
+ * 0 is the ciphertext itself (baby step 0, no key), slot 1 + i is baby key i.  pt: the pack of encoded diagonals as
+ * ckks_engine.encode_diagonals(.., bsgs=n1) lays it out — [ell + K][N] words each at stride pt_stride, NTT domain, Montgomery
+ * form, giant step after giant step: gcount[i] >= 1 diagonals belong to giant step i, and bidx holds, in pack order, the baby
+ * slot of every diagonal (0 .. nb, strictly ascending inside a giant step).
+ * The result has exactly the words of: c0, c1 made canonical; E and c^ as lf_linear_transform forms them; per baby key
+ * u^b_c = sum over the digits of E gathered by pi_b times the key part, u^b_0 += c^0 gathered on the ordinary rows (slot 0:
+ * u_c = c^c, zero on the special rows); per giant step S^g_c = sum_b mont_mult(pt_{g,b}, u^b_c); giant step 0: S joins the
+ * accumulator A; else w = mod-down (no addend) of intt_exit_reduce(S^g_1), made canonical, E^g its digits extended and
+ * transformed, v_c = sum over the digits of E^g gathered by pi_g times key g's part, v_0 += S^g_0 gathered on ALL ell + K rows
+ * (S^g_0 stays in Q P), A += v; intt_exit_reduce(A), mod-down (no addend), ckks_engine.rescale.  The gather stands before the
+ * key product because rotation keys here switch s(X^p) -> s.  Only residues of u, S, v and A reach the result.
+ * Enqueued: the canonical copies, enter_ntt and the product with plan->PR of c0 and c1 into slot 0; lf_ks_digits_galois and
+ * lf_ks_fwd once (nb > 0) and per group of 4, 2 or 1 baby keys one launch of ks_inner_baby_kernel; per group of 4, 2 or 1 giant
+ * steps one launch of lt_diag_products_kernel (the baby pairs cross HBM once per launch), then per keyed giant step the inverse
+ * NTT of S^g_1, lf_ks_moddown_ws for one polynomial, lf_ks_digits_galois (gal_pinv = 1), lf_ks_fwd and one launch of
+ * ks_inner_giant_kernel into A; one inverse NTT of A, one mod-down, one lf_rescale_batch into out0 / out1 [ell - 1][N].
+ * The baby pairs, four S pairs, A, w and the mod-down's buffers do not fit the plan's scratch: `ws` of at least
+ * lf_linear_transform_bsgs_ws_words(plan, nb) words is lent by the caller (0 for a plan or an nb the entry refuses).
+ * LF_ERR_ARG before any launch for everything lf_linear_transform refuses, nb < 0 or > 63, ng < 1, a baby slot out of range or
+ * not ascending inside its giant step, a giant step without diagonals, a second or a late giant step 0, a workspace too small. */
+int64_t lf_linear_transform_bsgs_ws_words(const lf_ks_plan *plan, int nb);
+int lf_linear_transform_bsgs(const lf_ks_plan *plan, const int64_t *c0, const int64_t *c1, int nb, const int64_t *bp_host,
+                             const int64_t *const *bksk, int ng, const int64_t *gp_host, const int64_t *const *gksk,
+                             int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format, const int64_t *pt,
+                             int64_t pt_stride, const int64_t *gcount, const int64_t *bidx, const int64_t *rescale_scales,
+                             int64_t round_at, int64_t *ws, int64_t ws_words, int64_t *out0, int64_t *out1, void *stream);
+
 /* The halves of an op around the digit exchange of a limb-sharded engine (one process per GPU; the reference gathers every
  * digit on every GPU through the host before it extends any, ckks_engine.py:778-829).  The plan describes THIS rank's rows
  * at the level (dig_nparts = the digits it owns, nparts = all digits, state = its own digit rows):

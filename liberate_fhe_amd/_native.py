@@ -110,6 +110,8 @@ _SIGNATURES["lf_rotate_hoisted_ws_words"] = [_PL]
 _SIGNATURES["lf_rotate_hoisted"] = [_PL, _P, _P, _I, _P, _I, _P, _L, _L, _L, _I, _P, _L, _P, _P, _P]
 _SIGNATURES["lf_linear_transform_ws_words"] = [_PL]
 _SIGNATURES["lf_linear_transform"] = [_PL, _P, _P, _I, _P, _P, _L, _L, _L, _I, _P, _L, _P, _P, _L, _P, _L, _P, _P, _P]
+_SIGNATURES["lf_linear_transform_bsgs_ws_words"] = [_PL, _I]
+_SIGNATURES["lf_linear_transform_bsgs"] = [_PL, _P, _P, _I, _P, _P, _I, _P, _P, _L, _L, _L, _I, _P, _L, _P, _P, _P, _L, _P, _L, _P, _P, _P]
 
 # the 30-bit / int32 word mode of the ntt_cuda surface (csrc/ckks_w30.hip)
 _SIGNATURES.update({

@@ -986,6 +986,254 @@ __global__ void __launch_bounds__(256) ks_inner_lt_kernel(const i64 *__restrict_
     }
 }
 
+// ---- baby-step / giant-step linear transform (lf_linear_transform_bsgs): y = sum_g rot(sum_b pt_{g,b} * rot(x, b), g) ------------
+// Three launches on the grid, the pi computation and the key / digit formats of the two kernels above, under names of their own:
+//   ks_inner_baby_kernel     per group of 4 / 2 / 1 baby keys the gathered sums over the digits, + P c0 gathered on the ordinary
+//                            rows, written out as one pair PER KEY (the flat kernel's t_c, kept instead of multiplied and summed);
+//   lt_diag_products_kernel  S^g_c = sum_b pt_{g,b} * u^b_c for up to 4 giant steps per launch, pure streaming;
+//   ks_inner_giant_kernel    one key, the digits of the giant step's polynomial gathered by pi_g, + S^g_0 gathered on ALL rows
+//                            (it lives in Q P and never comes down), read - add - write into the accumulator pair.
+// Every buffer between them holds raw 8-byte words whose residues are the Montgomery-form words of the orchestrated steps:
+// canonical from the fp64-class rows (the balanced sums reduced once), lazy below 2q from the integer rows.  Only residues
+// reach the result: each pair next meets a product, a sum, or the exact inverse transform.
+
+// the gathered sums over the digits of NR keys for the thread's pair (j0, j0 + 1) of row r: fp64 class (balanced sums) ...
+template <int NR, bool PLANES, bool DPL>
+static __device__ __forceinline__ void gathered_sums_dp(const i64 *__restrict__ ext, const HoistKeys &hk, const unsigned (&src)[NR],
+                                                        const bool (&sw)[NR], i64 part_stride, i64 comp_stride, i64 krow, i64 j0,
+                                                        int nparts, int rows, int r, i64 N, const RowDp &d, double (&acc)[NR][2][2]) {
+#pragma unroll
+    for (int i = 0; i < NR; ++i) acc[i][0][0] = acc[i][0][1] = acc[i][1][0] = acc[i][1][1] = 0.0;
+#pragma unroll KI_UNROLL
+    for (int p = 0; p < nparts; ++p) {
+        const i64 *er = ext + ((i64)p * rows + r) * N;
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {
+            double xa, xb;
+            ld_pair_dp(er, (i64)src[i], N, DPL ? 1 : 0, xa, xb);
+            const double x0 = sw[i] ? xb : xa, x1 = sw[i] ? xa : xb;
+            const i64 *kr = hk.ksk[i] + krow + (i64)p * part_stride;
+            double k0x, k0y, k1x, k1y;
+            if (PLANES) {   // 16 + 8 bytes for both components (see lf_key_planes)
+                const lf_u4_t l = __builtin_nontemporal_load(reinterpret_cast<const lf_u4_t *>(reinterpret_cast<const unsigned *>(kr) + 2 * j0));
+                const lf_u2_t h = __builtin_nontemporal_load(reinterpret_cast<const lf_u2_t *>(reinterpret_cast<const unsigned *>(kr + comp_stride) + j0));
+                k0x = dp_from_planes(l.x, h.x & 0xffffu), k0y = dp_from_planes(l.y, h.x >> 16);
+                k1x = dp_from_planes(l.z, h.y & 0xffffu), k1y = dp_from_planes(l.w, h.y >> 16);
+            } else {
+                const longlong2 k0 = ld_nt(kr + j0);
+                const longlong2 k1 = ld_nt(kr + j0 + comp_stride);
+                k0x = dp_from_word(k0.x), k0y = dp_from_word(k0.y), k1x = dp_from_word(k1.x), k1y = dp_from_word(k1.y);
+            }
+            acc[i][0][0] += dp_mulmod_bal(x0, k0x, d);
+            acc[i][0][1] += dp_mulmod_bal(x1, k0y, d);
+            acc[i][1][0] += dp_mulmod_bal(x0, k1x, d);
+            acc[i][1][1] += dp_mulmod_bal(x1, k1y, d);
+        }
+    }
+}
+
+// ... and integer class (lazy words below 2q)
+template <int NR>
+static __device__ __forceinline__ void gathered_sums_int(const i64 *__restrict__ ext, const HoistKeys &hk, const unsigned (&src)[NR],
+                                                         const bool (&sw)[NR], i64 part_stride, i64 comp_stride, i64 krow, i64 j0,
+                                                         int nparts, int rows, int r, i64 N, const RowMod &m, i64 (&acc)[NR][2][2]) {
+#pragma unroll
+    for (int i = 0; i < NR; ++i) acc[i][0][0] = acc[i][0][1] = acc[i][1][0] = acc[i][1][1] = 0;
+    for (int p = 0; p < nparts; ++p) {
+        const i64 *er = ext + ((i64)p * rows + r) * N;
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {
+            const longlong2 v = *reinterpret_cast<const longlong2 *>(er + src[i]);
+            const u64 x0 = (u64)(sw[i] ? v.y : v.x), x1 = (u64)(sw[i] ? v.x : v.y);
+            const i64 *kr = hk.ksk[i] + krow + (i64)p * part_stride + j0;
+            const longlong2 k0 = ld_nt(kr);
+            const longlong2 k1 = ld_nt(kr + comp_stride);
+            acc[i][0][0] = csub(acc[i][0][0] + mm62u(x0, (u64)k0.x, m.q, m.k), m.q2);
+            acc[i][0][1] = csub(acc[i][0][1] + mm62u(x1, (u64)k0.y, m.q, m.k), m.q2);
+            acc[i][1][0] = csub(acc[i][1][0] + mm62u(x0, (u64)k1.x, m.q, m.k), m.q2);
+            acc[i][1][1] = csub(acc[i][1][1] + mm62u(x1, (u64)k1.y, m.q, m.k), m.q2);
+        }
+    }
+}
+
+struct BabyArgs {
+    HoistKeys hk;
+    i64 *u[4];           // key i's pair [2][rows][N]
+    const i64 *chat0;    // P NTT(c0): [ell][N], Montgomery form, words below 2q
+    int ell;             // ordinary rows (the first `ell` of the rows)
+};
+
+template <int NR, bool PLANES, bool DPL>
+__global__ void __launch_bounds__(256) ks_inner_baby_kernel(const i64 *__restrict__ ext, BabyArgs ba, i64 part_stride, i64 comp_stride,
+                                                            i64 row_off, int nparts, int rows, int logN,
+                                                            const i64 *__restrict__ ql, const i64 *__restrict__ qh,
+                                                            const i64 *__restrict__ kl, const i64 *__restrict__ kh) {
+    const int r = blockIdx.y;
+    const i64 N = (i64)1 << logN;
+    const i64 j0 = (i64)blockIdx.x * 512 + threadIdx.x * 2;
+    if (j0 >= N) return;
+    const RowMod m = load_mod(ql, qh, kl, kh, r);
+    const unsigned sh = 32u - (unsigned)logN, mask = (2u << logN) - 1u;
+    const unsigned bj = (2u * (__builtin_bitreverse32((unsigned)j0) >> sh) + 1u);
+    unsigned src[NR];
+    bool sw[NR];
+#pragma unroll
+    for (int i = 0; i < NR; ++i) {
+        const unsigned t = (bj * ba.hk.p[i]) & mask;
+        const unsigned mi = __builtin_bitreverse32((t - 1u) >> 1) >> sh;
+        src[i] = mi & ~1u;
+        sw[i] = (mi & 1u) != 0;
+    }
+    const i64 krow = (row_off + r) * N;
+    const bool ord = r < ba.ell;
+    const i64 *c0row = ba.chat0 + (i64)r * N;   // (read on ordinary rows only)
+    const i64 o0 = (i64)r * N + j0, o1 = ((i64)rows + r) * N + j0;
+    if (m.q < SMALL_PRIME_LIMIT) {
+        const RowDp d = make_dp(m);
+        double acc[NR][2][2];
+        gathered_sums_dp<NR, PLANES, DPL>(ext, ba.hk, src, sw, part_stride, comp_stride, krow, j0, nparts, rows, r, N, d, acc);
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {
+            if (ord) {
+                double ca, cb;
+                ld_pair_dp(c0row, (i64)src[i], N, 0, ca, cb);
+                acc[i][0][0] += sw[i] ? cb : ca;
+                acc[i][0][1] += sw[i] ? ca : cb;
+            }
+            longlong2 a, b;
+            a.x = dp_to_word(dp_reduce(acc[i][0][0], d.q, d.qinv)), a.y = dp_to_word(dp_reduce(acc[i][0][1], d.q, d.qinv));
+            b.x = dp_to_word(dp_reduce(acc[i][1][0], d.q, d.qinv)), b.y = dp_to_word(dp_reduce(acc[i][1][1], d.q, d.qinv));
+            *reinterpret_cast<longlong2 *>(ba.u[i] + o0) = a;
+            *reinterpret_cast<longlong2 *>(ba.u[i] + o1) = b;
+        }
+    } else {
+        i64 acc[NR][2][2];
+        gathered_sums_int<NR>(ext, ba.hk, src, sw, part_stride, comp_stride, krow, j0, nparts, rows, r, N, m, acc);
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {
+            if (ord) {
+                const longlong2 v = *reinterpret_cast<const longlong2 *>(c0row + src[i]);
+                acc[i][0][0] = csub(acc[i][0][0] + (sw[i] ? v.y : v.x), m.q2);
+                acc[i][0][1] = csub(acc[i][0][1] + (sw[i] ? v.x : v.y), m.q2);
+            }
+            longlong2 a, b;
+            a.x = acc[i][0][0], a.y = acc[i][0][1], b.x = acc[i][1][0], b.y = acc[i][1][1];
+            *reinterpret_cast<longlong2 *>(ba.u[i] + o0) = a;
+            *reinterpret_cast<longlong2 *>(ba.u[i] + o1) = b;
+        }
+    }
+}
+
+// S^g_c = sum_b pt_{g,b} * u^b_c for NG giant steps: every row in the integer arithmetic (REDC62 holds for the small primes
+// too, and the launch streams: per slot one baby pair, per diagonal 16 bytes per thread).  The baby pairs are read once per
+// launch, whatever NG; a slot no giant step of the launch uses is not read.
+struct DiagArgs {
+    const i64 *u;                  // baby pairs [slots][2][rows][N] (slot 0: P NTT(c0), P NTT(c1), zero on the special rows)
+    const i64 *pt[4];              // giant step i: the first diagonal of its slice of the pack, ascending slots
+    unsigned long long slots[4];   // bit t: giant step i has a diagonal for baby slot t
+    i64 *out[4];                   // its pair [2][rows][N] (giant step 0: the accumulator)
+    i64 pt_stride;                 // words between the diagonals of the pack
+    int nslots;
+};
+
+template <int NG>
+__global__ void __launch_bounds__(256) lt_diag_products_kernel(DiagArgs da, int rows, int logN, const i64 *__restrict__ ql,
+                                                               const i64 *__restrict__ qh, const i64 *__restrict__ kl,
+                                                               const i64 *__restrict__ kh) {
+    const int r = blockIdx.y;
+    const i64 N = (i64)1 << logN;
+    const i64 j0 = (i64)blockIdx.x * 512 + threadIdx.x * 2;
+    if (j0 >= N) return;
+    const RowMod m = load_mod(ql, qh, kl, kh, r);
+    const i64 o0 = (i64)r * N + j0, pair = 2 * (i64)rows * N;
+    i64 S[NG][2][2];
+    const i64 *pt[NG];
+    unsigned long long any = 0;
+#pragma unroll
+    for (int i = 0; i < NG; ++i) {
+        S[i][0][0] = S[i][0][1] = S[i][1][0] = S[i][1][1] = 0;
+        pt[i] = da.pt[i] + o0;
+        any |= da.slots[i];
+    }
+    for (int t = 0; t < da.nslots; ++t) {
+        if (!((any >> t) & 1ull)) continue;   // (wave-uniform: kernel arguments)
+        const i64 *ur = da.u + (i64)t * pair + o0;
+        const longlong2 u0 = *reinterpret_cast<const longlong2 *>(ur);
+        const longlong2 u1 = *reinterpret_cast<const longlong2 *>(ur + (i64)rows * N);
+#pragma unroll
+        for (int i = 0; i < NG; ++i) {
+            if (!((da.slots[i] >> t) & 1ull)) continue;
+            const longlong2 w = ld_nt(pt[i]);
+            pt[i] += da.pt_stride;
+            S[i][0][0] = csub(S[i][0][0] + mm62u((u64)u0.x, (u64)w.x, m.q, m.k), m.q2);
+            S[i][0][1] = csub(S[i][0][1] + mm62u((u64)u0.y, (u64)w.y, m.q, m.k), m.q2);
+            S[i][1][0] = csub(S[i][1][0] + mm62u((u64)u1.x, (u64)w.x, m.q, m.k), m.q2);
+            S[i][1][1] = csub(S[i][1][1] + mm62u((u64)u1.y, (u64)w.y, m.q, m.k), m.q2);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < NG; ++i) {
+        longlong2 a, b;
+        a.x = S[i][0][0], a.y = S[i][0][1], b.x = S[i][1][0], b.y = S[i][1][1];
+        *reinterpret_cast<longlong2 *>(da.out[i] + o0) = a;
+        *reinterpret_cast<longlong2 *>(da.out[i] + o0 + (i64)rows * N) = b;
+    }
+}
+
+struct GiantArgs {
+    HoistKeys hk;        // (one key)
+    const i64 *s0;       // S^g_0: [rows][N], raw words below 2q
+    i64 *acc;            // the accumulator pair [2][rows][N]: read, added to, written
+};
+
+template <bool PLANES, bool DPL>   // (the waves asked for are those of ks_inner_lt_kernel<1, PLANES, DPL>: one VGPR over 64 without)
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PLANES ? 6 : 8))) ks_inner_giant_kernel(const i64 *__restrict__ ext, GiantArgs ga, i64 part_stride, i64 comp_stride,
+                                                             i64 row_off, int nparts, int rows, int logN,
+                                                             const i64 *__restrict__ ql, const i64 *__restrict__ qh,
+                                                             const i64 *__restrict__ kl, const i64 *__restrict__ kh) {
+    const int r = blockIdx.y;
+    const i64 N = (i64)1 << logN;
+    const i64 j0 = (i64)blockIdx.x * 512 + threadIdx.x * 2;
+    if (j0 >= N) return;
+    const RowMod m = load_mod(ql, qh, kl, kh, r);
+    const unsigned sh = 32u - (unsigned)logN, mask = (2u << logN) - 1u;
+    const unsigned bj = (2u * (__builtin_bitreverse32((unsigned)j0) >> sh) + 1u);
+    const unsigned t = (bj * ga.hk.p[0]) & mask;
+    const unsigned mi = __builtin_bitreverse32((t - 1u) >> 1) >> sh;
+    const unsigned src[1] = {mi & ~1u};
+    const bool sw[1] = {(mi & 1u) != 0};
+    const i64 krow = (row_off + r) * N;
+    const i64 *s0row = ga.s0 + (i64)r * N;
+    i64 *a0 = ga.acc + (i64)r * N + j0, *a1 = ga.acc + ((i64)rows + r) * N + j0;
+    if (m.q < SMALL_PRIME_LIMIT) {
+        const RowDp d = make_dp(m);
+        double acc[1][2][2];
+        gathered_sums_dp<1, PLANES, DPL>(ext, ga.hk, src, sw, part_stride, comp_stride, krow, j0, nparts, rows, r, N, d, acc);
+        double ca, cb, x0, y0, x1, y1;
+        ld_pair_dp(s0row, (i64)src[0], N, 0, ca, cb);
+        ld_pair_dp(a0, 0, N, 0, x0, y0);
+        ld_pair_dp(a1, 0, N, 0, x1, y1);
+        longlong2 a, b;   // |sums| < (digits / 2 + 4) q, inside dp_reduce's 64 q
+        a.x = dp_to_word(dp_reduce(acc[0][0][0] + (sw[0] ? cb : ca) + x0, d.q, d.qinv));
+        a.y = dp_to_word(dp_reduce(acc[0][0][1] + (sw[0] ? ca : cb) + y0, d.q, d.qinv));
+        b.x = dp_to_word(dp_reduce(acc[0][1][0] + x1, d.q, d.qinv));
+        b.y = dp_to_word(dp_reduce(acc[0][1][1] + y1, d.q, d.qinv));
+        *reinterpret_cast<longlong2 *>(a0) = a;
+        *reinterpret_cast<longlong2 *>(a1) = b;
+    } else {
+        i64 acc[1][2][2];
+        gathered_sums_int<1>(ext, ga.hk, src, sw, part_stride, comp_stride, krow, j0, nparts, rows, r, N, m, acc);
+        const longlong2 v = *reinterpret_cast<const longlong2 *>(s0row + src[0]);
+        longlong2 a = *reinterpret_cast<const longlong2 *>(a0), b = *reinterpret_cast<const longlong2 *>(a1);
+        a.x = csub(a.x + csub(acc[0][0][0] + (sw[0] ? v.y : v.x), m.q2), m.q2);
+        a.y = csub(a.y + csub(acc[0][0][1] + (sw[0] ? v.x : v.y), m.q2), m.q2);
+        b.x = csub(b.x + acc[0][1][0], m.q2);
+        b.y = csub(b.y + acc[0][1][1], m.q2);
+        *reinterpret_cast<longlong2 *>(a0) = a;
+        *reinterpret_cast<longlong2 *>(a1) = b;
+    }
+}
+
 // largest number of leading stages (logN - 12) whose extension + strided pass runs as the column kernel (lf_tune).
 // With the digit loop as a runtime loop (R loads in flight, 100 VGPRs at R = 16) the column form also wins at logN 16:
 // gold cc_mult 2 104-2 130 -> 2 168-2 183 ops/s, rotate 2 653-2 695 -> 2 733-2 763, 64 rotations under one key
@@ -1282,6 +1530,106 @@ int lf_ks_tail_lt(int nr, const int64_t *p_host, int nparts, int rows, int ell, 
 #undef LF_LT_LAUNCH
 #undef LF_LT_CASE
     return ks_inv_sums(2, rows, logN, spl, cols_last, mixed, in, dp, (i64 *)scratch, (i64 *)s, ipsi_br, ipsi_dp, Ninv, ql, qh, kl, kh, st);
+}
+
+// ---- the launches of lf_linear_transform_bsgs (ckks_ops.hip checks the arguments and owns the order) ----
+namespace {
+bool key_args_ok(const int64_t *ksk, int64_t part_stride, int64_t comp_stride, int key_format) {
+    if (!ksk || (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES)) return false;
+    return key_format != LF_KEY_PLANES || !((((uintptr_t)ksk | (uintptr_t)(part_stride * 8) | (uintptr_t)(comp_stride * 8)) & 15));
+}
+}  // namespace
+
+// baby steps: key i's gathered sums over the shared digits `ext`, + chat0 gathered on the ordinary rows, into u + i * 2 rows N
+int lf_ks_baby_sums(int nr, const int64_t *p_host, int nparts, int rows, int ell, int logN, const int64_t *const *ksk, int64_t part_stride,
+                    int64_t comp_stride, int64_t row_off, int key_format, const int64_t *chat0, const int64_t *ext, int64_t *u,
+                    const int64_t *q_host, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st) {
+    if (nr < 0 || !chat0 || !u || ell < 0 || ell > rows) return LF_ERR_ARG;
+    for (int i = 0; i < nr; ++i)
+        if (!key_args_ok(ksk[i], part_stride, comp_stride, key_format)) return LF_ERR_ARG;
+    if (!nr) return 0;
+    RowList dp, in;
+    classify_rows(rows, q_host, dp, in);
+    const bool dplanes = digit_planes(logN, dp, in);
+    if (int e = lf_fmt_expect(ext, ((size_t)nparts * rows << logN) * 8, dplanes ? LF_FMT_PLANES : LF_FMT_RAW)) return e;
+    const dim3 grid((unsigned)((((i64)1 << logN) + 511) / 512), (unsigned)rows);
+    const bool planes = key_format == LF_KEY_PLANES;
+    const i64 pair = (i64)2 * rows << logN;
+#define LF_BABY_LAUNCH(NR, PL, DPLB)                                                                                        \
+    hipLaunchKernelGGL((ks_inner_baby_kernel<NR, PL, DPLB>), grid, dim3(256), 0, st, (const i64 *)ext, ba, (i64)part_stride, \
+                       (i64)comp_stride, (i64)row_off, nparts, rows, logN, (const i64 *)ql, (const i64 *)qh, (const i64 *)kl, \
+                       (const i64 *)kh)
+#define LF_BABY_CASE(NR)                                                                                                   \
+    case NR:                                                                                                               \
+        if (planes && dplanes) LF_BABY_LAUNCH(NR, true, true);                                                            \
+        else if (planes) LF_BABY_LAUNCH(NR, true, false);                                                                 \
+        else if (dplanes) LF_BABY_LAUNCH(NR, false, true);                                                                \
+        else LF_BABY_LAUNCH(NR, false, false);                                                                            \
+        break;
+    for (int i0 = 0; i0 < nr;) {
+        const int left = nr - i0, g = left >= 4 ? 4 : left >= 2 ? 2 : 1;
+        BabyArgs ba{};
+        for (int t = 0; t < g; ++t) {
+            ba.hk.ksk[t] = (const i64 *)ksk[i0 + t];
+            ba.hk.p[t] = (unsigned)p_host[i0 + t];
+            ba.u[t] = (i64 *)u + (i64)(i0 + t) * pair;
+        }
+        ba.chat0 = (const i64 *)chat0, ba.ell = ell;
+        switch (g) { LF_BABY_CASE(1) LF_BABY_CASE(2) LF_BABY_CASE(4) }
+        i0 += g;
+    }
+#undef LF_BABY_LAUNCH
+#undef LF_BABY_CASE
+    return (int)hipGetLastError();
+}
+
+// diagonal products of ng (1, 2 or 4) giant steps: out[i] = sum over the set bits t of slots[i] of pt[i][k-th diagonal] * u[t]
+int lf_lt_diag_products(int ng, const int64_t *u, int nslots, const int64_t *const *pt, const unsigned long long *slots, int64_t pt_stride,
+                        int64_t *const *out, int rows, int logN, const int64_t *ql, const int64_t *qh, const int64_t *kl,
+                        const int64_t *kh, hipStream_t st) {
+    if ((ng != 1 && ng != 2 && ng != 4) || !u || nslots < 1 || nslots > 64) return LF_ERR_ARG;
+    DiagArgs da{};
+    da.u = (const i64 *)u, da.pt_stride = (i64)pt_stride, da.nslots = nslots;
+    for (int i = 0; i < ng; ++i) {
+        if (!pt[i] || !out[i] || !slots[i]) return LF_ERR_ARG;
+        da.pt[i] = (const i64 *)pt[i], da.slots[i] = slots[i], da.out[i] = (i64 *)out[i];
+    }
+    const dim3 grid((unsigned)((((i64)1 << logN) + 511) / 512), (unsigned)rows);
+#define LF_DIAG_LAUNCH(NG)                                                                                                 \
+    hipLaunchKernelGGL((lt_diag_products_kernel<NG>), grid, dim3(256), 0, st, da, rows, logN, (const i64 *)ql, (const i64 *)qh, \
+                       (const i64 *)kl, (const i64 *)kh)
+    switch (ng) {
+        case 1: LF_DIAG_LAUNCH(1); break;
+        case 2: LF_DIAG_LAUNCH(2); break;
+        case 4: LF_DIAG_LAUNCH(4); break;
+    }
+#undef LF_DIAG_LAUNCH
+    return (int)hipGetLastError();
+}
+
+// giant step: acc += (sum over the parts of `ext` gathered by pi_p times the key part, + s0 gathered on all rows on component 0)
+int lf_ks_giant_sums(int64_t p, int nparts, int rows, int logN, const int64_t *ksk, int64_t part_stride, int64_t comp_stride,
+                     int64_t row_off, int key_format, const int64_t *ext, const int64_t *s0, int64_t *acc, const int64_t *q_host,
+                     const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st) {
+    if (!key_args_ok(ksk, part_stride, comp_stride, key_format) || !s0 || !acc) return LF_ERR_ARG;
+    RowList dp, in;
+    classify_rows(rows, q_host, dp, in);
+    const bool dplanes = digit_planes(logN, dp, in);
+    if (int e = lf_fmt_expect(ext, ((size_t)nparts * rows << logN) * 8, dplanes ? LF_FMT_PLANES : LF_FMT_RAW)) return e;
+    GiantArgs ga{};
+    ga.hk.ksk[0] = (const i64 *)ksk, ga.hk.p[0] = (unsigned)p, ga.s0 = (const i64 *)s0, ga.acc = (i64 *)acc;
+    const dim3 grid((unsigned)((((i64)1 << logN) + 511) / 512), (unsigned)rows);
+    const bool planes = key_format == LF_KEY_PLANES;
+#define LF_GIANT_LAUNCH(PL, DPLB)                                                                                          \
+    hipLaunchKernelGGL((ks_inner_giant_kernel<PL, DPLB>), grid, dim3(256), 0, st, (const i64 *)ext, ga, (i64)part_stride,   \
+                       (i64)comp_stride, (i64)row_off, nparts, rows, logN, (const i64 *)ql, (const i64 *)qh, (const i64 *)kl, \
+                       (const i64 *)kh)
+    if (planes && dplanes) LF_GIANT_LAUNCH(true, true);
+    else if (planes) LF_GIANT_LAUNCH(true, false);
+    else if (dplanes) LF_GIANT_LAUNCH(false, true);
+    else LF_GIANT_LAUNCH(false, false);
+#undef LF_GIANT_LAUNCH
+    return (int)hipGetLastError();
 }
 
 // cc_mult's product -> digits in one launch behind the tiled pass where it qualifies (ckks_ops.hip: product_digits): 0 = never

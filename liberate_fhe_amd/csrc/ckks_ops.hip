@@ -24,6 +24,17 @@ int lf_ks_tail_lt(int nr, const int64_t *p_host, int nparts, int rows, int ell, 
                   const double *ipsi_dp, const int64_t *Ninv, const int64_t *q_host, const int64_t *ql, const int64_t *qh,
                   const int64_t *kl, const int64_t *kh, hipStream_t st);
 
+// ckks_ks.hip: the launches of lf_linear_transform_bsgs
+int lf_ks_baby_sums(int nr, const int64_t *p_host, int nparts, int rows, int ell, int logN, const int64_t *const *ksk, int64_t part_stride,
+                    int64_t comp_stride, int64_t row_off, int key_format, const int64_t *chat0, const int64_t *ext, int64_t *u,
+                    const int64_t *q_host, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st);
+int lf_lt_diag_products(int ng, const int64_t *u, int nslots, const int64_t *const *pt, const unsigned long long *slots, int64_t pt_stride,
+                        int64_t *const *out, int rows, int logN, const int64_t *ql, const int64_t *qh, const int64_t *kl,
+                        const int64_t *kh, hipStream_t st);
+int lf_ks_giant_sums(int64_t p, int nparts, int rows, int logN, const int64_t *ksk, int64_t part_stride, int64_t comp_stride,
+                     int64_t row_off, int key_format, const int64_t *ext, const int64_t *s0, int64_t *acc, const int64_t *q_host,
+                     const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st);
+
 extern "C" {
 
 static int plan_ok(const lf_ks_plan *p) {
@@ -236,6 +247,127 @@ int lf_linear_transform(const lf_ks_plan *p, const int64_t *c0, const int64_t *c
         return e;
     // 4. one mod-down, one rescale into the caller's [ell - 1][N] pair
     const int64_t *ss[2] = {p->sum, p->sum + (int64_t)rows * N};
+    int64_t *mds[2] = {md, md + poly};
+    if (int e = moddown_any(p, ss, mds, nullptr, 2, 0, nullptr, stream)) return e;
+    const int64_t *ins[2] = {md + N, md + poly + N}, *row0[2] = {md, md + poly};
+    int64_t *outs[2] = {out0, out1};
+    return lf_rescale_batch(ins, row0, outs, 2, ell - 1, N, rescale_scales, round_at, p->ql + 1, p->qh + 1, p->kl + 1, p->kh + 1, dev, stream);
+}
+
+/* ---- linear transform, baby-step / giant-step: y = sum_g rot(sum_b pt_{g,b} * rot(x, b), g) (include/ckks_hip.h) ---- */
+#define LF_BSGS_MAX_BABY_KEYS 63   // slots 0 .. 63 are the bits of lt_diag_products_kernel's masks
+#define LF_BSGS_S_PAIRS 4          // giant steps per launch of the diagonal products
+
+int64_t lf_linear_transform_bsgs_ws_words(const lf_ks_plan *p, int nb) {
+    if (!plan_ok(p) || nb < 0 || nb > LF_BSGS_MAX_BABY_KEYS) return 0;
+    const int64_t N = (int64_t)1 << p->logN, pair = 2 * (int64_t)(p->ell + p->K) * N, poly = (int64_t)p->ell * N;
+    // baby pairs (slot 0: the ciphertext), the S pairs of one launch, the accumulator A, w, the final mod-down's result, the
+    // workspace of the one-polynomial mod-down (the plan's own is primed for pairs)
+    return pair * (nb + 1 + LF_BSGS_S_PAIRS + 1) + poly + 2 * poly + lf_ks_moddown_ws_words(1, p->ell, p->K, N);
+}
+
+int lf_linear_transform_bsgs(const lf_ks_plan *p, const int64_t *c0, const int64_t *c1, int nb, const int64_t *bp_host,
+                             const int64_t *const *bksk, int ng, const int64_t *gp_host, const int64_t *const *gksk,
+                             int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format, const int64_t *pt,
+                             int64_t pt_stride, const int64_t *gcount, const int64_t *bidx, const int64_t *rescale_scales,
+                             int64_t round_at, int64_t *ws, int64_t ws_words, int64_t *out0, int64_t *out1, void *stream) {
+    if (!plan_ok(p) || !p->PR || p->ell < 2 || nb < 0 || nb > LF_BSGS_MAX_BABY_KEYS || ng < 1 || !c0 || !c1 || !rescale_scales || !out0 ||
+        !out1 || !pt || !gp_host || !gksk || !gcount || !bidx || (nb && (!bp_host || !bksk)) ||
+        (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES))
+        return LF_ERR_ARG;
+    const int ell = p->ell, rows = p->ell + p->K, logN = p->logN, dev = p->device;
+    const int64_t N = (int64_t)1 << logN, twoN = 2 * N, poly = (int64_t)ell * N, pair = 2 * (int64_t)rows * N;
+    if (pt_stride < (int64_t)rows * N) return LF_ERR_ARG;
+    auto key_ok = [&](const int64_t *k, int64_t e) {
+        if (!k || e <= 0 || e >= twoN || !(e & 1)) return false;
+        return key_format != LF_KEY_PLANES || !((((uintptr_t)k | (uintptr_t)(part_stride * 8) | (uintptr_t)(comp_stride * 8)) & 15));
+    };
+    for (int i = 0; i < nb; ++i)
+        if (!key_ok(bksk[i], bp_host[i])) return LF_ERR_ARG;
+    int64_t ndiag = 0;
+    for (int i = 0; i < ng; ++i) {
+        if (gp_host[i] == 0 ? i != 0 : !key_ok(gksk[i], gp_host[i])) return LF_ERR_ARG;   // (giant step 0: first, so at most once)
+        if (gcount[i] < 1 || gcount[i] > nb + 1) return LF_ERR_ARG;
+        for (int64_t k = 0; k < gcount[i]; ++k) {
+            const int64_t slot = bidx[ndiag + k];
+            if (slot < 0 || slot > nb || (k && slot <= bidx[ndiag + k - 1])) return LF_ERR_ARG;
+        }
+        ndiag += gcount[i];
+    }
+    const int64_t need = lf_linear_transform_bsgs_ws_words(p, nb);
+    if (!ws || ws_words < need) return LF_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    int64_t *u = ws, *S = u + (nb + 1) * pair, *A = S + LF_BSGS_S_PAIRS * pair, *w = A + pair, *md = w + poly, *md1 = md + 2 * poly;
+    const int64_t md1_words = lf_ks_moddown_ws_words(1, ell, p->K, N);
+    if (int e = lf_set_device(dev)) return e;
+    // 1. slot 0 = P NTT(c0), P NTT(c1) on the ordinary rows (canonical copy, enter_ntt, times P R), zero on the special rows
+    {
+        const int64_t *srcs[2] = {c0, c1};
+        int64_t *dsts[2] = {u, u + (int64_t)rows * N};
+        if (int e = lf_galois_batch(srcs, dsts, 2, ell, logN, 1, p->_2q, dev, stream)) return e;
+        for (int c = 0; c < 2; ++c) {
+            if (int e = lf_ntt(dsts[c], 1, ell, logN, p->psi, p->psi_dp, p->q_host, p->Rs, 0, p->_2q, p->ql, p->qh, p->kl, p->kh, dev, stream))
+                return e;
+            if (int e = lf_mont_enter(dsts[c], p->PR, ell, N, p->ql, p->qh, p->kl, p->kh, dev, stream)) return e;
+            if (hipError_t e = hipMemsetAsync(dsts[c] + poly, 0, (size_t)p->K * N * 8, st)) return (int)e;
+        }
+    }
+    // 2. baby steps: the digits of c1 extended and transformed once, per group of keys one launch into the slots 1 .. nb
+    if (nb) {
+        if (int e = lf_ks_digits_galois(c1, p->state, p->dig_nparts, p->dig_desc, p->dig_tab, N, 1, p->_2q, p->ql, p->qh, p->kl, p->kh, dev,
+                                        stream))
+            return e;
+        if (int e = lf_ks_fwd(p->state, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, p->ext, p->psi, p->psi_dp, p->q_host, p->ql, p->qh,
+                              p->kl, p->kh, dev, stream))
+            return e;
+        if (int e = lf_ks_baby_sums(nb, bp_host, p->nparts, rows, ell, logN, bksk, part_stride, comp_stride, row_off, key_format, u, p->ext,
+                                    u + pair, p->q_host, p->ql, p->qh, p->kl, p->kh, st))
+            return e;
+    }
+    // 3. giant steps, LF_BSGS_S_PAIRS per launch of the diagonal products; giant step 0 writes the accumulator itself
+    if (gp_host[0] != 0)
+        if (hipError_t e = hipMemsetAsync(A, 0, (size_t)pair * 8, st)) return (int)e;
+    int64_t first = 0;   // first diagonal of the giant step in the pack
+    for (int i0 = 0; i0 < ng;) {
+        const int left = ng - i0, g = left >= 4 ? 4 : left >= 2 ? 2 : 1;
+        const int64_t *pts[4];
+        int64_t *outs[4];
+        unsigned long long slots[4];
+        for (int t = 0; t < g; ++t) {
+            pts[t] = pt + first * pt_stride;
+            slots[t] = 0;
+            for (int64_t k = 0; k < gcount[i0 + t]; ++k) slots[t] |= 1ull << bidx[first + k];
+            outs[t] = gp_host[i0 + t] == 0 ? A : S + t * pair;
+            first += gcount[i0 + t];
+        }
+        if (int e = lf_lt_diag_products(g, u, nb + 1, pts, slots, pt_stride, outs, rows, logN, p->ql, p->qh, p->kl, p->kh, st)) return e;
+        for (int t = 0; t < g; ++t) {
+            if (gp_host[i0 + t] == 0) continue;
+            int64_t *S0 = S + t * pair, *S1 = S0 + (int64_t)rows * N;
+            // S^g_1 down to Q: inverse NTT, mod-down of the one polynomial, its digits (canonical), extended and transformed
+            if (int e = lf_intt(S1, 1, rows, logN, p->ipsi, p->ipsi_dp, p->q_host, p->Ninv, 2, 0, p->_2q, p->ql, p->qh, p->kl, p->kh, dev, stream))
+                return e;
+            const int64_t *ss[1] = {S1};
+            int64_t *ws1[1] = {w};
+            if (int e = lf_ks_moddown_ws(ss, ws1, nullptr, 1, ell, p->K, N, md1, md1_words, p->PiR, p->PiP, p->Rs, 0, nullptr, p->ql, p->qh,
+                                         p->kl, p->kh, dev, stream))
+                return e;
+            if (int e = lf_ks_digits_galois(w, p->state, p->dig_nparts, p->dig_desc, p->dig_tab, N, 1, p->_2q, p->ql, p->qh, p->kl, p->kh, dev,
+                                            stream))
+                return e;
+            if (int e = lf_ks_fwd(p->state, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, p->ext, p->psi, p->psi_dp, p->q_host, p->ql,
+                                  p->qh, p->kl, p->kh, dev, stream))
+                return e;
+            if (int e = lf_ks_giant_sums(gp_host[i0 + t], p->nparts, rows, logN, gksk[i0 + t], part_stride, comp_stride, row_off, key_format,
+                                         p->ext, S0, A, p->q_host, p->ql, p->qh, p->kl, p->kh, st))
+                return e;
+        }
+        i0 += g;
+    }
+    // 4. one exact inverse NTT of the accumulator (intt_exit_reduce), one mod-down, one rescale into the caller's [ell - 1][N] pair
+    if (int e = lf_intt(A, 2, rows, logN, p->ipsi, p->ipsi_dp, p->q_host, p->Ninv, 2, 0, p->_2q, p->ql, p->qh, p->kl, p->kh, dev, stream))
+        return e;
+    const int64_t *ss[2] = {A, A + (int64_t)rows * N};
     int64_t *mds[2] = {md, md + poly};
     if (int e = moddown_any(p, ss, mds, nullptr, 2, 0, nullptr, stream)) return e;
     const int64_t *ins[2] = {md + N, md + poly + N}, *row0[2] = {md, md + poly};

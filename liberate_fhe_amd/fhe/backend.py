@@ -442,6 +442,36 @@ class HipBackend:
                                       0 if ws is None else ws.numel(), out.data_ptr(), out.data_ptr() + out.stride(0) * 8, st),
               "lf_linear_transform")
 
+    @staticmethod
+    def linear_transform_bsgs_ws_words(plan, nb):
+        return int(lib.lf_linear_transform_bsgs_ws_words(ctypes.byref(plan), nb))
+
+    def linear_transform_bsgs_native(self, plan, c0, c1, baby_exps, baby_keys, giant_exps, giant_keys, first_part, row_off, pack,
+                                     counts, slots, scales, round_at, out, ws):
+        """The baby-step / giant-step linear transform as ONE native call (lf_linear_transform_bsgs).  baby_keys / baby_exps: the
+        packed keys of the non-zero baby steps and their Galois exponents; giant_keys / giant_exps: per giant step its key and
+        exponent (None and 0 for the giant step 0, which comes first); pack [k, rows, N]: the encoded diagonals in (giant, baby)
+        order; counts: diagonals per giant step; slots: per diagonal its baby slot (0: the ciphertext, 1 + i: baby key i);
+        out [2, ell - 1, N]; ws: at least linear_transform_bsgs_ws_words(plan, len(baby_keys)) words."""
+        dev, st = _ds(out)
+        nb, ng = len(baby_keys), len(giant_keys)
+        keyed = list(baby_keys) + [k for k in giant_keys if k is not None]
+        fmt = {self._kfmt(k) for k in keyed}
+        if len(fmt) > 1:
+            raise ValueError("linear_transform_bsgs_native: the keys of one call must share one format")
+        ps = cs = 0
+        bb, gb = (ctypes.c_void_p * max(nb, 1))(), (ctypes.c_void_p * max(ng, 1))()
+        for i, key in enumerate(baby_keys):
+            bb[i], ps, cs = self._key_args(key, first_part)
+        for i, key in enumerate(giant_keys):
+            if key is not None:
+                gb[i], ps, cs = self._key_args(key, first_part)
+        i64 = lambda v: (ctypes.c_int64 * max(len(v), 1))(*v)
+        check(lib.lf_linear_transform_bsgs(ctypes.byref(plan), _p(c0), _p(c1), nb, i64(baby_exps), bb, ng, i64(giant_exps), gb, ps, cs,
+                                           row_off, fmt.pop() if fmt else 0, _p(pack), pack.stride(0), i64(counts), i64(slots),
+                                           _p(scales), round_at, _p(ws), ws.numel(), out.data_ptr(),
+                                           out.data_ptr() + out.stride(0) * 8, st), "lf_linear_transform_bsgs")
+
     def ks_gather(self, ext, dst, index, rows, logN, c: Consts):
         """dst[p][r][k] = ext[p][r][index[k]] for extended digits as ks_fwd leaves them: fp64-class rows of a mixed stack in the
         planes format (u32 low words at byte 0, u16 high halves at byte 4 N of the row: LF_TUNE_DIGIT_PLANES), other rows raw

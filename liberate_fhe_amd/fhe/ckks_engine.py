@@ -1835,12 +1835,19 @@ class ckks_engine(EvaluatorOps):
     # =============================================================================================
     # linear transform: sum of diagonals times rotations ("double hoisting"; the reference has no such entry)
     # =============================================================================================
-    def encode_diagonals(self, diagonals, level: int) -> data_struct:
+    def encode_diagonals(self, diagonals, level: int, bsgs=None) -> data_struct:
         """The plaintext side of linear_transform, built once and applied to many ciphertexts of `level`.  diagonals: {step:
         vector} (steps taken mod num_slots; vectors as encode takes them).  Per step m * sqrt(deviations[level + 1]) encoded at
         level 0 as mc_mult does, tiled over the ordinary rows of `level` AND the special rows, NTT domain, Montgomery form.  ONE
         pack [k, rows, N] per local device, steps ascending; `data` = per step the per-device [rows, N] views of it; the origin
-        carries the steps ("plain diagonals:0,1,5,700")."""
+        carries the steps ("plain diagonals:0,1,5,700").
+        bsgs=n1 (an integer >= 1) encodes for the baby-step / giant-step form of linear_transform: step = g + b with
+        b = step mod n1; the padded vector is rolled by -g (np.roll(v, -g)) before it is encoded, since the giant rotation by g is
+        applied to the whole inner sum.  The pack is in (g, b) order, which is the ascending order of the steps, so a giant
+        step's diagonals are one slice of it; the origin carries n1 and the steps ("plain diagonals bsgs:4;0,1,5,700")."""
+        n1 = None
+        if bsgs is not None:
+            n1 = encdec.bsgs_split([0], self.num_slots, bsgs)[0]      # (ValueError for anything but an integer >= 1)
         if level + 1 >= self.num_levels:
             raise errors.MaximumLevelError(level=level, level_max=self.num_levels)
         by_step = {}
@@ -1855,22 +1862,33 @@ class ckks_engine(EvaluatorOps):
         packs = None
         for j, step in enumerate(steps):
             m = np.array(by_step[step]) * np.sqrt(self.deviations[level + 1])
+            if n1 is not None:
+                m = np.roll(self.padding(m), -(step - step % n1))
             pt = self.ntt.tile_unsigned(self.encode(m, 0), level, -2)
             self.ntt.enter_ntt(pt, level, -2)
             if packs is None:
                 packs = [torch.empty((len(steps),) + tuple(t.shape), dtype=torch.int64, device=t.device) for t in pt]
             for pk, t in zip(packs, pt):
                 pk[j].copy_(t)
+        tag = types.origins["diag"] if n1 is None else types.origins["diag_bsgs"] + f"{n1};"
         out = self._new([[pk[j] for pk in packs] for j in range(len(steps))],
-                        types.origins["diag"] + ",".join(str(s) for s in steps), level=level, include_special=True,
+                        tag + ",".join(str(s) for s in steps), level=level, include_special=True,
                         ntt_state=True, montgomery_state=True)
         self._remember_diag_pack(out, packs, own=True)
         return out
 
     @staticmethod
     def diagonal_steps(diags) -> list:
-        """The steps of an encode_diagonals object, in the order of its data."""
-        return [int(s) for s in diags.origin.split(":", 1)[1].split(",")]
+        """The steps of an encode_diagonals object (flat or baby-step / giant-step), in the order of its data."""
+        return [int(s) for s in diags.origin.split(":", 1)[1].split(";")[-1].split(",")]
+
+    def bsgs_steps(self, diags) -> tuple:
+        """(n1, baby steps, giant steps) of an encode_diagonals(.., bsgs=n1) object, both sorted, 0 included where present:
+        linear_transform needs a rotation key for every non-zero baby step and every non-zero giant step."""
+        if not is_struct(diags) or not diags.origin.startswith(types.origins["diag_bsgs"]):
+            raise errors.NotMatchType(origin=getattr(diags, "origin", type(diags).__name__), to=types.origins["diag_bsgs"])
+        n1 = int(diags.origin.split(":", 1)[1].split(";")[0])
+        return encdec.bsgs_split(self.diagonal_steps(diags), self.num_slots, n1)
 
     def _remember_diag_pack(self, diags, packs, own):
         anchor = diags.data[0][0]
@@ -1903,7 +1921,9 @@ class ckks_engine(EvaluatorOps):
         rows; per key t_c = sum over the parts of E gathered by pi_p times the key part, t_0 += c^0 gathered by pi_p on the
         ordinary rows (step 0: t_c = c^c, zero on the special rows); S_c = sum of mont_mult(pt_step, t_c); intt_exit_reduce,
         mod-down, rescale.  One native call (lf_linear_transform) where every limb of the level is on one device of this process;
-        otherwise the same words through the engine's steps.  Coefficient-domain ciphertexts without special limbs only."""
+        otherwise the same words through the engine's steps.  Coefficient-domain ciphertexts without special limbs only.
+        Diagonals from encode_diagonals(.., bsgs=n1) take the baby-step / giant-step form (_linear_transform_bsgs): the same
+        transform from the keys of the non-zero baby and giant steps (bsgs_steps) alone, with words of its own."""
         if ct.origin != types.origins["ct"]:
             raise errors.NotMatchType(origin=ct.origin, to=types.origins["ct"])
         keys = list(rotks.values()) if isinstance(rotks, dict) else list(rotks)
@@ -1919,10 +1939,13 @@ class ckks_engine(EvaluatorOps):
             raise errors.MaximumLevelError(level=level, level_max=self.num_levels)
         if not is_struct(diags):
             diags = self.encode_diagonals(diags, level)
-        if not diags.origin.startswith(types.origins["diag"]):
+        bsgs = diags.origin.startswith(types.origins["diag_bsgs"])
+        if not bsgs and not diags.origin.startswith(types.origins["diag"]):
             raise errors.NotMatchType(origin=diags.origin, to=types.origins["diag"])
         if diags.level != level:
             raise errors.NotMatchDataStructState(origin=f"{diags.origin} at level {diags.level}, ciphertext at level {level}")
+        if bsgs:
+            return self._linear_transform_bsgs(ct, diags, by_step)
         steps = self.diagonal_steps(diags)
         for s in steps:
             if s and s not in by_step:
@@ -2024,6 +2047,171 @@ class ckks_engine(EvaluatorOps):
             s2 = torch.stack(S).contiguous()
             self.backend.intt(s2, 2, rows, logN, itw, ninv, 2, cs)         # intt_exit_reduce: canonical coefficients
             out = torch.empty((2, ell, N), dtype=torch.int64, device=dev)
+            ws, one = self._moddown_ws("ks_moddown", 2, ell, K, d, tabs, cs)
+            mkw = {"one_launch": True} if one else {}
+            self.backend.ks_moddown_ws([s2[0], s2[1]], [out[0], out[1]], [None, None], ell, K, ws, tabs[("pir", d)],
+                                       self._vec("Rs", d, level, True), cs, PiP=tabs[("pip", d)], **mkw)
+            c0o.append(out[0]); c1o.append(out[1])
+        return self.rescale(self._new((c0o, c1o), types.origins["ct"], level=level))
+
+    def _linear_transform_bsgs(self, ct, diags, by_step):
+        """linear_transform on encode_diagonals(.., bsgs=n1) diagonals: y = sum_g rot(sum_b pt_{g,b} * rot(x, b), g), so that k
+        diagonals need about n1 + k / n1 keys instead of k.  The words are those of: c0, c1 made canonical, E and c^ as in the flat
+        form; per baby step b != 0 u^b_c = sum over the parts of E gathered by pi_b times key b's part, u^b_0 += c^0 gathered on the
+        ordinary rows (b = 0: u^0_c = c^c, zero on the special rows); per giant step S^g_c = sum_b mont_mult(pt_{g,b}, u^b_c);
+        g = 0: S^0 joins the accumulator A; g != 0: w = mod-down of intt_exit_reduce(S^g_1), made canonical, E^g its digits
+        extended and transformed, v_c = sum over the parts of E^g gathered by pi_g times key g's part, v_0 += S^g_0 gathered on
+        ALL rows (S^g_0 stays in Q P), A += v; intt_exit_reduce(A), mod-down, rescale.  Every non-linear step starts from
+        canonical words, so only residues of u, S, v and A reach the result.  One native call (lf_linear_transform_bsgs) where
+        every limb of the level is on one device of this process; otherwise the same words through the engine's steps."""
+        level, N, logN = ct.level, self.ctx.N, self.ctx.logN
+        n1, babies, giants = self.bsgs_steps(diags)
+        steps = self.diagonal_steps(diags)
+        for s in babies + giants:
+            if s and s not in by_step:
+                raise errors.NotMatchType(origin=f"no key for step {s}", to=types.origins["rotk"] + str(s))
+        kb = [b for b in babies if b]                                    # keyed baby steps: slot 1 + index (slot 0: the ciphertext)
+        slot = {b: 1 + i for i, b in enumerate(kb)}
+        slot[0] = 0
+        groups = {g: [] for g in giants}                                 # giant step -> [(row of the pack, baby step)], ascending b
+        for j, s in enumerate(steps):
+            groups[s - s % n1].append((j, s % n1))
+        owner = self.ntt.p.rescaler_loc[level]
+        round_at = self.ctx.q[self.ntt.p.destination_arrays[level][owner][0]] // 2
+
+        d = self._native_level(level)
+        if d is not None and hasattr(self.backend, "linear_transform_bsgs_native") and len(kb) < 63 and \
+                steps == sorted(steps) and ct.data[0][0].is_contiguous() and ct.data[1][0].is_contiguous():
+            plan, _, first_part, row_off = self._op_plan(level, d)
+            i0 = self._loc(0, special=True).index(d)
+            pack = self._diag_pack(diags)[self.local_ids.index(d)]
+            ws = self._ws("lt_bsgs_ws", (self.backend.linear_transform_bsgs_ws_words(plan, len(kb)),), d)
+            out = torch.empty((2, plan.ell - 1, N), dtype=torch.int64, device=self.ntt.devices[d])
+            self.backend.linear_transform_bsgs_native(
+                plan, ct.data[0][0], ct.data[1][0], [encdec.galois_exponent(N, b) for b in kb],
+                [self._key_pack(by_step[b])[i0] for b in kb], [encdec.galois_exponent(N, g) if g else 0 for g in giants],
+                [self._key_pack(by_step[g])[i0] if g else None for g in giants], first_part, row_off, pack,
+                [len(groups[g]) for g in giants], [slot[b] for g in giants for _, b in groups[g]],
+                self.rescale_scales[level][d], round_at, out, ws)
+            return self._new(([out[0]], [out[1]]), types.origins["ct"], level=level + 1)
+
+        # orchestrated: the same words through the engine's steps (see linear_transform's own orchestration for the pieces)
+        tabs = self._ks_tables(level)
+        loc, loc0 = self._loc(level), self._loc(0, special=True)
+        K, n = self.ntt.num_special_primes, self.ntt
+        nparts = len(tabs["order"])
+        fused = logN >= self.backend.fused_ks_min_logN
+        gather = getattr(self.backend, "ks_gather", None)
+
+        def forward(d, digits):
+            """extension + forward NTT of the exchanged digits on device d, kept aside in the buffer the keys gather from"""
+            rows, cs, tw = self._rows(d, level, True), self._consts(d, level, True), self._tw(d, level, True)
+            desc, E, Ed = tabs[("extend", d)]
+            ext = self._ws("ks_ext", (nparts, rows, N), d)
+            dig, ready = digits[d]
+            for handle, first, count in ready:
+                if handle is not None:
+                    handle.wait()
+                if fused:
+                    self.backend.ks_fwd(dig, first, count, rows, logN, desc, E, Ed, ext, tw, cs)
+            if not fused:
+                self.backend.ks_extend(dig, ext, nparts, rows, desc, E, cs)
+                self.backend.ntt(ext, nparts, rows, logN, tw, None, cs, relaxed=True)
+            self._ws("ks_ext_hoisted", (nparts, rows, N), d).copy_(ext)
+
+        def inner(d, idx, key):
+            """sum over the parts of (the digits gathered by idx) times the key part: [2, rows, N], NTT domain, Montgomery form"""
+            rows, cs = self._rows(d, level, True), self._consts(d, level, True)
+            ext, src = self._ws("ks_ext", (nparts, rows, N), d), self._ws("ks_ext_hoisted", (nparts, rows, N), d)
+            s = self._ws("ks_sum", (2, rows, N), d)
+            if gather is not None:
+                gather(src, ext, idx, rows, logN, cs)
+            else:
+                torch.index_select(src, 2, idx, out=ext)
+            kp = self._key_pack(key)[loc0.index(d)]
+            if fused:
+                self.backend.ks_tail(nparts, rows, logN, kp, tabs["first_part"], self.ntt.starts[level][d], ext, s,
+                                     self._tw(d, level, True, True), self._vec("Ninv", d, level, True), cs)
+                self.backend.ntt(s, 2, rows, logN, self._tw(d, level, True), self._vec("Rs", d, level, True), cs)
+            else:
+                self.backend.ks_inner(ext, kp, tabs["first_part"], self.ntt.starts[level][d], s[0], s[1], nparts, rows, cs)
+            return s.clone()
+
+        # baby steps: u^b per device, kept for every giant step
+        digits = self._ks_digits_exchanged(ct.data[1], level, galois=(1, True)) if kb else {}
+        u = []
+        for i, d in enumerate(loc):
+            li = self.local_ids.index(d)
+            rows, ell = self._rows(d, level, True), self._rows(d, level, False)
+            cso, g2q = self._consts(d, level, False), self._vec("_2q", d, level, False)
+            dev = self.ntt.devices[d]
+            chat = torch.empty((2, ell, N), dtype=torch.int64, device=dev)
+            for comp in range(2):
+                src = ct.data[comp][i] if ct.data[comp][i].is_contiguous() else ct.data[comp][i].contiguous()
+                self.backend.galois(src, chat[comp], ell, logN, 1, g2q)
+                self.backend.ntt(chat[comp], 1, ell, logN, self._tw(d, level, False), self._vec("Rs", d, level, False), cso)
+                n.ops.mont_enter([chat[comp]], [self._PR(d, level)], *[x[li:li + 1] for x in n.mont_prepack[-1][level][0]])
+            ud = {}
+            if 0 in babies:
+                ud[0] = torch.zeros((2, rows, N), dtype=torch.int64, device=dev)
+                ud[0][:, :ell] = chat
+            if kb:
+                forward(d, digits)
+                _2q = n._2q_prepack[-2][level][0][li]
+                for b in kb:
+                    idx = self._galois_index(encdec.galois_exponent(N, b), d)
+                    t = inner(d, idx, by_step[b])
+                    t[0, :ell] = n.ops.mont_add([t[0, :ell]], [chat[0].index_select(1, idx)], [_2q[:ell]])[0]
+                    ud[b] = t
+            u.append(ud)
+
+        # giant steps: the products with the diagonals; past g = 0 one polynomial comes down to Q and is key-switched by key g
+        A = [[None, None] for _ in loc]
+        for g in giants:
+            Sg = []
+            for i, d in enumerate(loc):
+                li = self.local_ids.index(d)
+                mont = [x[li:li + 1] for x in n.mont_prepack[-2][level][0]]
+                _2q = [n._2q_prepack[-2][level][0][li]]
+                S = [None, None]
+                for j, b in groups[g]:
+                    for comp in range(2):
+                        prod = n.ops.mont_mult([diags.data[j][li]], [u[i][b][comp]], *mont)[0]
+                        S[comp] = prod if S[comp] is None else n.ops.mont_add([S[comp]], [prod], _2q)[0]
+                Sg.append(S)
+            if g:
+                w = []
+                for i, d in enumerate(loc):
+                    rows, ell = self._rows(d, level, True), self._rows(d, level, False)
+                    cs = self._consts(d, level, True)
+                    s1 = Sg[i][1].contiguous()
+                    self.backend.intt(s1, 1, rows, logN, self._tw(d, level, True, True), self._vec("Ninv", d, level, True), 2, cs)
+                    wd = torch.empty((ell, N), dtype=torch.int64, device=self.ntt.devices[d])
+                    ws, one = self._moddown_ws("ks_moddown_one_poly", 1, ell, K, d, tabs, cs)
+                    mkw = {"one_launch": True} if one else {}
+                    self.backend.ks_moddown_ws([s1], [wd], [None], ell, K, ws, tabs[("pir", d)], self._vec("Rs", d, level, True), cs,
+                                               PiP=tabs[("pip", d)], **mkw)
+                    w.append(wd)
+                digits = self._ks_digits_exchanged(w, level, galois=(1, True))
+                for i, d in enumerate(loc):
+                    li = self.local_ids.index(d)
+                    forward(d, digits)
+                    idx = self._galois_index(encdec.galois_exponent(N, g), d)
+                    v = inner(d, idx, by_step[g])
+                    v0 = n.ops.mont_add([v[0]], [Sg[i][0].index_select(1, idx)], [n._2q_prepack[-2][level][0][li]])[0]
+                    Sg[i] = [v0, v[1]]
+            for i, d in enumerate(loc):
+                _2q = [n._2q_prepack[-2][level][0][self.local_ids.index(d)]]
+                for comp in range(2):
+                    A[i][comp] = Sg[i][comp] if A[i][comp] is None else n.ops.mont_add([A[i][comp]], [Sg[i][comp]], _2q)[0]
+
+        c0o, c1o = [], []
+        for i, d in enumerate(loc):
+            rows, ell = self._rows(d, level, True), self._rows(d, level, False)
+            cs = self._consts(d, level, True)
+            s2 = torch.stack(A[i]).contiguous()
+            self.backend.intt(s2, 2, rows, logN, self._tw(d, level, True, True), self._vec("Ninv", d, level, True), 2, cs)
+            out = torch.empty((2, ell, N), dtype=torch.int64, device=self.ntt.devices[d])
             ws, one = self._moddown_ws("ks_moddown", 2, ell, K, d, tabs, cs)
             mkw = {"one_launch": True} if one else {}
             self.backend.ks_moddown_ws([s2[0], s2[1]], [out[0], out[1]], [None, None], ell, K, ws, tabs[("pir", d)],

@@ -132,6 +132,39 @@ def matrix_diagonals(M) -> dict:
     return out
 
 
+def bsgs_split(steps, num_slots: int, n1=None) -> tuple:
+    """Baby-step / giant-step split of the rotation steps of a linear transform: every step (taken mod num_slots) is g + b with
+    b = step mod n1 and g = step - b.  Returns (n1, babies, giants), both sorted and with 0 where it occurs: a transform over
+    `steps` needs one rotation key per non-zero baby step and one per non-zero giant step.  n1=None picks the power of two that
+    minimises that number of keys (ties: the larger n1, giant steps being the dearer ones)."""
+    reduced = sorted({int(s) % num_slots for s in steps})
+    if not reduced:
+        raise ValueError("bsgs_split: no step given")
+
+    def split(n):
+        return sorted({s % n for s in reduced}), sorted({s - s % n for s in reduced})
+
+    if n1 is None:
+        best = None
+        n = 1
+        while n <= num_slots:
+            babies, giants = split(n)
+            cost = sum(1 for b in babies if b) + sum(1 for g in giants if g)
+            if best is None or cost <= best[0]:
+                best = (cost, n)
+            n *= 2
+        n1 = best[1]
+    try:
+        ok = int(n1) == n1 and int(n1) >= 1 and not isinstance(n1, bool)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"bsgs_split: n1 must be an integer >= 1, got {n1!r}")
+    n1 = int(n1)
+    babies, giants = split(n1)
+    return n1, babies, giants
+
+
 def ntt_galois_index(logN: int, p: int) -> np.ndarray:
     """pi_p as an int64 index array: NTT(a(X^p))[k] = NTT(a)[pi_p(k)] for the forward transform's order (index k holds the
     evaluation at psi^(2 brev(k) + 1)), pi_p(k) = brev(((2 brev(k) + 1) p mod 2N - 1) / 2).  A pure permutation (p odd):

@@ -10,4 +10,5 @@ origins = dict(
     ct="cipher text",
     ctt="cipher text triplet",
     diag="plain diagonals:",   # ckks_engine.encode_diagonals: followed by the steps, as a rotation key's tag by its step
+    diag_bsgs="plain diagonals bsgs:",   # encode_diagonals(bsgs=n1): followed by "n1;steps", the pack in (giant, baby) order
 )

@@ -102,6 +102,14 @@ def diagonals(engine, seed: int, level: int, steps, ds_type=None):
     return out
 
 
+def diagonals_bsgs(engine, seed: int, level: int, steps, n1: int, ds_type=None):
+    """What ckks_engine.encode_diagonals(.., bsgs=n1) returns for `steps`: the words `diagonals` gives each step (the same
+    per-step seed), packed in (giant, baby) order — ascending steps — under the baby-step / giant-step tag."""
+    out = diagonals(engine, seed, level, [int(s) % engine.num_slots for s in steps], ds_type)
+    # (the pack is remembered under the first tensor of the data, which the retagged object shares)
+    return out._replace(origin=f"plain diagonals bsgs:{int(n1)};" + out.origin.split(":", 1)[1])
+
+
 def _data_struct(engine):
     import importlib
     mod = importlib.import_module(type(engine).__module__.rsplit(".", 1)[0] + ".data_struct")

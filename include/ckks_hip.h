@@ -582,6 +582,31 @@ int lf_linear_transform_bsgs(const lf_ks_plan *plan, const int64_t *c0, const in
                              int64_t pt_stride, const int64_t *gcount, const int64_t *bidx, const int64_t *rescale_scales,
                              int64_t round_at, int64_t *ws, int64_t ws_words, int64_t *out0, int64_t *out1, void *stream);
 
+/* Sum of ciphertext products under ONE relinearisation ("lazy relinearisation"): out decrypts to sum_i a_i * b_i, level l -> l + 1.
+ * np >= 1 pairs; in / row0: HOST arrays of 4 np device pointers, four per pair in the order of lf_cc_mult_evk (first surviving
+ * row resp. dropped row of a_i.c0, a_i.c1, b_i.c0, b_i.c1; the same polynomial may appear any number of times); the plan
+ * describes level l + 1; key as for lf_cc_mult_evk; out0 / out1 [ell][N] canonical.
+ * The result has exactly the words of ckks_engine's
+ *     t = cc_mult(a_0, b_0, relin=False);  t = cc_add_triplet(t, cc_mult(a_i, b_i, relin=False)) for i >= 1;  relinearize(t, evk)
+ * i.e. per pair rescale, exact forward NTT, tensor product (d0, d1, d2); mont_add of the triplets; intt_exit_reduce of the three
+ * sums; key switch of d2 with the addends d0, d1.  np = 1: lf_cc_mult_evk's words.  Everything but the tensor products is linear
+ * in the triplet and runs once, on the sum; only the residues of the summed triplet T reach the result (its consumers — the
+ * inverse transform of T2 and the folded inner product — reduce), so T is kept in the relaxed representation of the other
+ * fused ops: plain canonical residues on fp64-class rows, Montgomery-form words below 2q on integer-class rows.
+ * Enqueued: per chunk of 4, 2 or 1 pairs (at most plan->max_nct) lf_rescale_ntt of up to 8 polynomials per call into plan->x4
+ * (RELAXED | PLAIN, PLANES where lf_stack_planes says so) and ONE launch of dot_tensor_kernel adding the chunk's triplets into
+ * T = [3][ell][N] (the first chunk writes; the last also leaves a copy of T2 in plan->d2); lf_intt (tail 2, relaxed, plain) of
+ * that copy and lf_ks_digits into plan->state; the extension + forward NTT of the digits (own-limb pairs skipped, as
+ * lf_relin_fwd) and ONE launch of ks_inner2_presum_kernel — the inner product with the key whose sums receive P T0 and P T1 on
+ * the ordinary rows and whose own-limb digit words are T2's — with the inverse NTT of plan->sum; one mod-down, no addend.
+ * T lives in `ws` of at least lf_cc_dot_ws_words(plan) = 3 ell N words, lent by the caller (0 for a plan the entry refuses).
+ * LF_ERR_ARG before any launch for everything lf_cc_mult_evk refuses, np < 1, a NULL among the 4 np pointers of in or row0, a
+ * key_format that is neither LF_KEY_RAW nor LF_KEY_PLANES (or a planes key not 16-byte aligned), ws NULL or too small. */
+int64_t lf_cc_dot_ws_words(const lf_ks_plan *plan);
+int lf_cc_dot(const lf_ks_plan *plan, int np, const int64_t *const *in, const int64_t *const *row0, const int64_t *ksk,
+              int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format, int64_t *ws, int64_t ws_words, int64_t *out0,
+              int64_t *out1, void *stream);
+
 /* The halves of an op around the digit exchange of a limb-sharded engine (one process per GPU; the reference gathers every
  * digit on every GPU through the host before it extends any, ckks_engine.py:778-829).  The plan describes THIS rank's rows
  * at the level (dig_nparts = the digits it owns, nparts = all digits, state = its own digit rows):

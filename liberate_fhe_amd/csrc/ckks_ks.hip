@@ -510,198 +510,105 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NCT ==
                                                         int nparts, int rows, i64 N, RelinFold fold, int spl,
                                                         const i64 *__restrict__ ql, const i64 *__restrict__ qh,
                                                         const i64 *__restrict__ kl, const i64 *__restrict__ kh) {
-    // spl: the sums of fp64-class rows leave as planes (the inverse passes behind read them so: ks_tail)
-    // each thread owns KI_V 16-byte column pairs 4 KiB apart: every block streams KI_V x 4 KiB contiguous runs
-    // from 3 x nparts arrays, enough bytes in flight to keep HBM busy
-    constexpr int KI_V = KI_COLS;
+    constexpr bool PRESUM = false;
+#include "ckks_ks_inner2.h"
+}
+
+// the pre-summed form of the fold (ckks_ks_inner2.h: PRESUM): the relinearising key switch of cc_dot, one triplet
+template <bool PLANES, bool DPL>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) ks_inner2_presum_kernel(const i64 *__restrict__ ext, const i64 *__restrict__ ksk,
+                                                        i64 part_stride, i64 comp_stride, i64 row_off, i64 *__restrict__ s,
+                                                        int nparts, int rows, i64 N, RelinFold fold, int spl,
+                                                        const i64 *__restrict__ ql, const i64 *__restrict__ qh,
+                                                        const i64 *__restrict__ kl, const i64 *__restrict__ kh) {
+    constexpr int NCT = 1;
+    constexpr bool FOLD = true, PRESUM = true;
+#include "ckks_ks_inner2.h"
+}
+
+// ---- cc_dot: the tensor products of G ciphertext pairs, summed into ONE triplet T = [3][ell][N] -----------------------------
+// x = [G][4][ell][N]: x0, x1, y0, y1 per pair as lf_rescale_ntt(RELAXED | PLAIN) leaves them (xpl: fp64-class rows as planes).
+//     T0 += sum x0 y0,   T1 += sum (x0 y1 + x1 y0),   T2 += sum x1 y1
+// grid = (N / 512, ell) as ks_inner2_kernel; a thread owns one 16-byte column pair: it reads the 4 G operand words of each of
+// its two coefficients once, sums the 3 G products in registers and makes one read-modify-write of T (first: the first chunk
+// writes without reading).  Only the residues of T reach the result (the pre-summed fold above and the inverse transform of T2
+// reduce), so the words are kept in the cheapest form that stays in range:
+//   fp64-class rows  balanced products (|.| <= q / 2); a coefficient's sum is at most 4 pairs x 2 balanced terms plus the one
+//                    canonical word read back, |.| < 4 q + q < 2^44 for q < 2^41 — far inside the exact range 2^53 of fp64 and
+//                    dp_reduce's |x| < 64 q; stored as the plain canonical residue;
+//   integer rows     REDC62 products, a conditional subtraction after every addition: Montgomery form below 2q throughout,
+//                    the range of the existing fold's own-digit words.
+// t2: where the launch of the LAST chunk leaves a second copy of T2 (its inverse transform runs in place there, while the fold
+// still reads the NTT-domain words in T); nullptr otherwise.
+template <int G>
+__global__ void __launch_bounds__(256) dot_tensor_kernel(const i64 *__restrict__ x, i64 ct_stride, i64 *__restrict__ T, i64 *__restrict__ t2,
+                                                         int ell, i64 N, int xpl, int first, const i64 *__restrict__ ql,
+                                                         const i64 *__restrict__ qh, const i64 *__restrict__ kl, const i64 *__restrict__ kh) {
     const int r = blockIdx.y;
-    const i64 j0 = (i64)blockIdx.x * (512 * KI_V) + threadIdx.x * 2;
+    const i64 j0 = (i64)blockIdx.x * 512 + threadIdx.x * 2;
     if (j0 >= N) return;
     const RowMod m = load_mod(ql, qh, kl, kh, r);
-    const RowDp d = make_dp(m);
-    const i64 *e = ext + (i64)r * N + j0;
-    const i64 *k = ksk + (row_off + r) * N + j0;
-    const i64 ct_ext = (i64)nparts * rows * N;   // words between the ciphertexts' extended digits
-    const i64 ct_s = 2 * (i64)rows * N;          // .. and between their output pairs
+    const i64 pstride = (i64)ell * N;
+    i64 *t = T + (i64)r * N + j0;
+    longlong2 o[3];
     if (m.q < SMALL_PRIME_LIMIT) {
-        double acc[NCT][2][2];
+        const RowDp d = make_dp(m);
+        double a[3][2] = {{0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}};
 #pragma unroll
-        for (int t = 0; t < NCT; ++t) acc[t][0][0] = acc[t][0][1] = acc[t][1][0] = acc[t][1][1] = 0.0;
-        const int p_own = (FOLD && fold.own != nullptr && r < fold.ell) ? (int)fold.own[r] : -1;
-        const unsigned bo_lo = (unsigned)j0 * 4u, bo_hi = (unsigned)j0 * 2u;   // DPL: byte offsets of the thread's pair in the planes
-        // the own digit's words: x1 * y1, plain canonical.  SCALAR arrays, selected by value below: a choice between a 16-byte
-        // struct in registers and one in global memory is compiled to a load through select(private address, global address),
-        // and an array whose address is taken that way lives in scratch memory (48 .. 128 bytes per lane in the batched kernels
-        // until round 6; profiles/r06_kernel_resources.txt)
-        i64 xo_x[NCT], xo_y[NCT];
-        if (p_own >= 0) {
+        for (int g = 0; g < G; ++g) {
+            const i64 *xs = x + g * ct_stride + (i64)r * N;
+            double x0[2], x1[2], y0[2], y1[2];
+            ld_pair_dp(xs, j0, N, xpl, x0[0], x0[1]);
+            ld_pair_dp(xs + pstride, j0, N, xpl, x1[0], x1[1]);
+            ld_pair_dp(xs + 2 * pstride, j0, N, xpl, y0[0], y0[1]);
+            ld_pair_dp(xs + 3 * pstride, j0, N, xpl, y1[0], y1[1]);
 #pragma unroll
-            for (int t = 0; t < NCT; ++t) {
-                const i64 *xs = fold.x + t * fold.ct_stride + (i64)r * N + (i64)fold.ell * N;
-                double x1a, x1b, y1a, y1b;
-                ld_pair_dp(xs, j0, N, fold.xpl, x1a, x1b);
-                ld_pair_dp(xs + 2 * (i64)fold.ell * N, j0, N, fold.xpl, y1a, y1b);
-                xo_x[t] = dp_to_word(dp_mulmod(x1a, y1a, d));
-                xo_y[t] = dp_to_word(dp_mulmod(x1b, y1b, d));
-                if constexpr (DPL) {   // in the register form of a pair read from the planes: one conversion for every digit
-                    const u64 a = (u64)xo_x[t], b = (u64)xo_y[t];
-                    xo_x[t] = (i64)((a & 0xffffffffull) | (b << 32));
-                    xo_y[t] = (i64)((a >> 32) | ((b >> 32) << 16));
-                }
-            }
-        }
-#pragma unroll KI_UNROLL
-        for (int p = 0; p < nparts; ++p) {
-            longlong2 x[NCT];   // DPL: .x = the two low words, low half of .y = the two high halves (8 + 4 bytes, fwd_tile16<.., PLN>)
-            if constexpr (DPL) {   // SGPR row base + one per-thread byte offset per plane
-#pragma unroll
-                for (int t = 0; t < NCT; ++t) {
-                    const char *er = reinterpret_cast<const char *>(uniform_ptr(ext + (((i64)t * nparts + p) * rows + r) * N));
-                    if (p == p_own) {
-                        x[t].x = xo_x[t], x[t].y = xo_y[t];
-                    } else {
-                        x[t].x = *reinterpret_cast<const i64 *>(er + bo_lo);
-                        x[t].y = (i64)*reinterpret_cast<const unsigned *>(er + 4 * N + bo_hi);
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int t = 0; t < NCT; ++t) {
-                    if (p == p_own) {
-                        x[t].x = xo_x[t], x[t].y = xo_y[t];
-                    } else {
-                        const longlong2 v = *reinterpret_cast<const longlong2 *>(e + t * ct_ext + (i64)p * rows * N);
-                        x[t].x = v.x, x[t].y = v.y;
-                    }
-                }
-            }
-            double k0x, k0y, k1x, k1y;
-            if (PLANES) {   // 16 + 8 bytes for both components (see lf_key_planes)
-                const i64 *kr = k - j0 + (i64)p * part_stride;
-                const lf_u4_t l = __builtin_nontemporal_load(reinterpret_cast<const lf_u4_t *>(reinterpret_cast<const unsigned *>(kr) + 2 * j0));
-                const lf_u2_t h = __builtin_nontemporal_load(reinterpret_cast<const lf_u2_t *>(reinterpret_cast<const unsigned *>(kr + comp_stride) + j0));
-                k0x = dp_from_planes(l.x, h.x & 0xffffu), k0y = dp_from_planes(l.y, h.x >> 16);
-                k1x = dp_from_planes(l.z, h.y & 0xffffu), k1y = dp_from_planes(l.w, h.y >> 16);
-            } else {
-                const longlong2 k0 = ld_nt(k + (i64)p * part_stride);
-                const longlong2 k1 = ld_nt(k + (i64)p * part_stride + comp_stride);
-                k0x = dp_from_word(k0.x), k0y = dp_from_word(k0.y), k1x = dp_from_word(k1.x), k1y = dp_from_word(k1.y);
-            }
-#pragma unroll
-            for (int t = 0; t < NCT; ++t) {
-                double x0, x1;
-                if constexpr (DPL) {
-                    const unsigned h = (unsigned)x[t].y;
-                    x0 = dp_from_planes((unsigned)x[t].x, h & 0xffffu);
-                    x1 = dp_from_planes((unsigned)((u64)x[t].x >> 32), h >> 16);
-                } else {
-                    x0 = dp_from_word(x[t].x), x1 = dp_from_word(x[t].y);
-                }
-                acc[t][0][0] += dp_mulmod_bal(x0, k0x, d);
-                acc[t][0][1] += dp_mulmod_bal(x1, k0y, d);
-                acc[t][1][0] += dp_mulmod_bal(x0, k1x, d);
-                acc[t][1][1] += dp_mulmod_bal(x1, k1y, d);
-            }
-        }
-        if (FOLD && r < fold.ell) {
-            const double pr = dp_from_word(fold.PR[r]);
-            const i64 pstride = (i64)fold.ell * N;
-#pragma unroll
-            for (int t = 0; t < NCT; ++t) {
-                const i64 *xs = fold.x + t * fold.ct_stride + (i64)r * N;
-                double x0[2], x1[2], y0[2], y1[2];
-                ld_pair_dp(xs, j0, N, fold.xpl, x0[0], x0[1]);
-                ld_pair_dp(xs + pstride, j0, N, fold.xpl, x1[0], x1[1]);
-                ld_pair_dp(xs + 2 * pstride, j0, N, fold.xpl, y0[0], y0[1]);
-                ld_pair_dp(xs + 3 * pstride, j0, N, fold.xpl, y1[0], y1[1]);
-#pragma unroll
-                for (int e = 0; e < 2; ++e) {   // balanced terms: |d0| <= q / 2, |d1| <= q
-                    const double d0 = dp_mulmod_bal(x0[e], y0[e], d);
-                    const double d1 = dp_mulmod_bal(x0[e], y1[e], d) + dp_mulmod_bal(x1[e], y0[e], d);
-                    acc[t][0][e] += dp_mulmod_bal(d0, pr, d);
-                    acc[t][1][e] += dp_mulmod_bal(d1, pr, d);
-                }
+            for (int e = 0; e < 2; ++e) {
+                a[0][e] += dp_mulmod_bal(x0[e], y0[e], d);
+                a[1][e] += dp_mulmod_bal(x0[e], y1[e], d) + dp_mulmod_bal(x1[e], y0[e], d);
+                a[2][e] += dp_mulmod_bal(x1[e], y1[e], d);
             }
         }
 #pragma unroll
-        for (int t = 0; t < NCT; ++t)
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                longlong2 o;
-                o.x = dp_to_word(dp_reduce(acc[t][c][0], d.q, d.qinv));
-                o.y = dp_to_word(dp_reduce(acc[t][c][1], d.q, d.qinv));
-                i64 *srow = s + t * ct_s + ((i64)c * rows + r) * N;
-                if (spl) {
-                    const lf_u2_t l = {(unsigned)o.x, (unsigned)o.y};
-                    *reinterpret_cast<lf_u2_t *>(reinterpret_cast<unsigned *>(srow) + j0) = l;
-                    *reinterpret_cast<unsigned *>(reinterpret_cast<unsigned short *>(srow + (N >> 1)) + j0) =
-                        (unsigned)((u64)o.x >> 32) | ((unsigned)((u64)o.y >> 32) << 16);
-                } else {
-                    *reinterpret_cast<longlong2 *>(srow + j0) = o;
-                }
+        for (int c = 0; c < 3; ++c) {
+            if (!first) {
+                const longlong2 v = *reinterpret_cast<const longlong2 *>(t + c * pstride);
+                a[c][0] += dp_from_word(v.x), a[c][1] += dp_from_word(v.y);
             }
+            o[c].x = dp_to_word(dp_reduce(a[c][0], d.q, d.qinv));
+            o[c].y = dp_to_word(dp_reduce(a[c][1], d.q, d.qinv));
+        }
     } else {
-        i64 acc[NCT][2][2];
+        i64 a[3][2];
 #pragma unroll
-        for (int t = 0; t < NCT; ++t) acc[t][0][0] = acc[t][0][1] = acc[t][1][0] = acc[t][1][1] = 0;
-        const int p_own = (FOLD && fold.own != nullptr && r < fold.ell) ? (int)fold.own[r] : -1;
-        i64 xo_x[NCT], xo_y[NCT];   // the own digit's words: REDC62(x1 * y1), Montgomery form below 2q (scalars: see above)
-        if (p_own >= 0) {
+        for (int g = 0; g < G; ++g) {
+            const i64 *xs = x + g * ct_stride + (i64)r * N + j0;
+            const longlong2 X0 = *reinterpret_cast<const longlong2 *>(xs), X1 = *reinterpret_cast<const longlong2 *>(xs + pstride);
+            const longlong2 Y0 = *reinterpret_cast<const longlong2 *>(xs + 2 * pstride), Y1 = *reinterpret_cast<const longlong2 *>(xs + 3 * pstride);
+            const u64 x0[2] = {(u64)X0.x, (u64)X0.y}, x1[2] = {(u64)X1.x, (u64)X1.y};
+            const u64 y0[2] = {(u64)Y0.x, (u64)Y0.y}, y1[2] = {(u64)Y1.x, (u64)Y1.y};
 #pragma unroll
-            for (int t = 0; t < NCT; ++t) {
-                const i64 *xs = fold.x + t * fold.ct_stride + (i64)r * N + j0 + (i64)fold.ell * N;
-                const longlong2 X1 = *reinterpret_cast<const longlong2 *>(xs), Y1 = *reinterpret_cast<const longlong2 *>(xs + 2 * (i64)fold.ell * N);
-                xo_x[t] = mm62u((u64)X1.x, (u64)Y1.x, m.q, m.k);
-                xo_y[t] = mm62u((u64)X1.y, (u64)Y1.y, m.q, m.k);
-            }
-        }
-        for (int p = 0; p < nparts; ++p) {
-            const longlong2 k0 = ld_nt(k + (i64)p * part_stride);
-            const longlong2 k1 = ld_nt(k + (i64)p * part_stride + comp_stride);
-#pragma unroll
-            for (int t = 0; t < NCT; ++t) {
-                longlong2 x;
-                if (p == p_own) {
-                    x.x = xo_x[t], x.y = xo_y[t];
-                } else {
-                    const longlong2 v = *reinterpret_cast<const longlong2 *>(e + t * ct_ext + (i64)p * rows * N);
-                    x.x = v.x, x.y = v.y;
-                }
-                acc[t][0][0] = csub(acc[t][0][0] + mm62u((u64)x.x, (u64)k0.x, m.q, m.k), m.q2);
-                acc[t][0][1] = csub(acc[t][0][1] + mm62u((u64)x.y, (u64)k0.y, m.q, m.k), m.q2);
-                acc[t][1][0] = csub(acc[t][1][0] + mm62u((u64)x.x, (u64)k1.x, m.q, m.k), m.q2);
-                acc[t][1][1] = csub(acc[t][1][1] + mm62u((u64)x.y, (u64)k1.y, m.q, m.k), m.q2);
-            }
-        }
-        if (FOLD && r < fold.ell) {
-            const u64 pr = (u64)fold.PR[r];
-            const i64 pstride = (i64)fold.ell * N;
-#pragma unroll
-            for (int t = 0; t < NCT; ++t) {
-                const i64 *xs = fold.x + t * fold.ct_stride + (i64)r * N + j0;
-                const longlong2 X0 = *reinterpret_cast<const longlong2 *>(xs), X1 = *reinterpret_cast<const longlong2 *>(xs + pstride);
-                const longlong2 Y0 = *reinterpret_cast<const longlong2 *>(xs + 2 * pstride), Y1 = *reinterpret_cast<const longlong2 *>(xs + 3 * pstride);
-                const u64 x0[2] = {(u64)X0.x, (u64)X0.y}, x1[2] = {(u64)X1.x, (u64)X1.y};
-                const u64 y0[2] = {(u64)Y0.x, (u64)Y0.y}, y1[2] = {(u64)Y1.x, (u64)Y1.y};
-#pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    const i64 d0 = mm62u(x0[e], y0[e], m.q, m.k);
-                    const i64 d1 = csub(mm62u(x0[e], y1[e], m.q, m.k) + mm62u(x1[e], y0[e], m.q, m.k), m.q2);
-                    acc[t][0][e] = csub(acc[t][0][e] + mm62u((u64)d0, pr, m.q, m.k), m.q2);
-                    acc[t][1][e] = csub(acc[t][1][e] + mm62u((u64)d1, pr, m.q, m.k), m.q2);
-                }
+            for (int e = 0; e < 2; ++e) {
+                const i64 d0 = mm62u(x0[e], y0[e], m.q, m.k);
+                const i64 d1 = csub(mm62u(x0[e], y1[e], m.q, m.k) + mm62u(x1[e], y0[e], m.q, m.k), m.q2);
+                const i64 d2 = mm62u(x1[e], y1[e], m.q, m.k);
+                a[0][e] = g == 0 ? d0 : csub(a[0][e] + d0, m.q2);
+                a[1][e] = g == 0 ? d1 : csub(a[1][e] + d1, m.q2);
+                a[2][e] = g == 0 ? d2 : csub(a[2][e] + d2, m.q2);
             }
         }
 #pragma unroll
-        for (int t = 0; t < NCT; ++t)
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                longlong2 o;
-                o.x = acc[t][c][0];
-                o.y = acc[t][c][1];
-                *reinterpret_cast<longlong2 *>(s + t * ct_s + ((i64)c * rows + r) * N + j0) = o;
+        for (int c = 0; c < 3; ++c) {
+            if (!first) {
+                const longlong2 v = *reinterpret_cast<const longlong2 *>(t + c * pstride);
+                a[c][0] = csub(a[c][0] + v.x, m.q2), a[c][1] = csub(a[c][1] + v.y, m.q2);
             }
+            o[c].x = a[c][0], o[c].y = a[c][1];
+        }
     }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) *reinterpret_cast<longlong2 *>(t + c * pstride) = o[c];
+    if (t2 != nullptr) *reinterpret_cast<longlong2 *>(t2 + (i64)r * N + j0) = o[2];
 }
 
 // ---- K3 of hoisted rotations (lf_rotate_hoisted): ONE ciphertext's extended digits, NR keys with an exponent each ----------
@@ -1375,8 +1282,8 @@ int ks_inv_sums(int inv_polys, int rows, int logN, bool spl, bool cols_last, boo
 int ks_tail(int nct, int nparts, int rows, int logN, const int64_t *ksk, int64_t part_stride, int64_t comp_stride,
             int64_t row_off, int64_t *tmp, int64_t *s, const int64_t *ipsi_br, const double *ipsi_dp,
             const int64_t *Ninv, const int64_t *q_host, const int64_t *ql, const int64_t *qh, const int64_t *kl,
-            const int64_t *kh, hipStream_t st, const RelinFold *fold = nullptr, int key_format = LF_KEY_RAW) {
-    if (!ipsi_dp || (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES)) return LF_ERR_ARG;
+            const int64_t *kh, hipStream_t st, const RelinFold *fold = nullptr, int key_format = LF_KEY_RAW, bool presum = false) {
+    if (!ipsi_dp || (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES) || (presum && (!fold || nct != 1))) return LF_ERR_ARG;
     if (key_format == LF_KEY_PLANES && ((((uintptr_t)ksk | (uintptr_t)(part_stride * 8) | (uintptr_t)(comp_stride * 8)) & 15)))
         return LF_ERR_ARG;
     const int tl = NTT_TILE_LOG_MAX, S1 = logN - tl;
@@ -1414,9 +1321,20 @@ int ks_tail(int nct, int nparts, int rows, int logN, const int64_t *ksk, int64_t
         else LF_INNER_DPL(NCT, false, false, nofold);                                                                  \
         break;
         const bool planes = key_format == LF_KEY_PLANES;
+#define LF_PRESUM_LAUNCH(PL, DPLB)                                                                                     \
+    hipLaunchKernelGGL((ks_inner2_presum_kernel<PL, DPLB>), grid, dim3(256), 0, st, (const i64 *)tmp, (const i64 *)ksk,  \
+                       (i64)part_stride, (i64)comp_stride, (i64)row_off, (i64 *)s, nparts, rows, N, *fold, spl ? 1 : 0, (const i64 *)ql, \
+                       (const i64 *)qh, (const i64 *)kl, (const i64 *)kh)
+        if (presum) {   // cc_dot: the fold reads a triplet already summed (one ciphertext)
+            if (planes && dplanes) LF_PRESUM_LAUNCH(true, true);
+            else if (planes) LF_PRESUM_LAUNCH(true, false);
+            else if (dplanes) LF_PRESUM_LAUNCH(false, true);
+            else LF_PRESUM_LAUNCH(false, false);
+        } else
         switch (nct) {
             LF_INNER_CASE(1) LF_INNER_CASE(2) LF_INNER_CASE(4)
         }
+#undef LF_PRESUM_LAUNCH
 #undef LF_INNER_LAUNCH
 #undef LF_INNER_DPL
 #undef LF_INNER_CASE
@@ -1426,6 +1344,43 @@ int ks_tail(int nct, int nparts, int rows, int logN, const int64_t *ksk, int64_t
 }
 
 }  // namespace
+
+// The launches of lf_cc_dot that are its own (ckks_ops.hip checks the arguments).
+// lf_dot_tensor: the tensor products of g (1, 2 or 4) pairs' operand stacks x = [g][4][ell][N] (pair stride 4 ell N; xpl: fp64-class
+// rows as planes) added into T = [3][ell][N] (first: written); t2 (may be NULL): a second copy of the new T2.
+int lf_dot_tensor(int g, const int64_t *x, int64_t *T, int64_t *t2, int ell, int logN, int xpl, int first, const int64_t *ql,
+                  const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st) {
+    if ((g != 1 && g != 2 && g != 4) || !x || !T || ell < 1 || ell > 65535 || logN < 9) return LF_ERR_ARG;
+    const i64 N = (i64)1 << logN;
+    const dim3 grid((unsigned)(N / 512), (unsigned)ell);
+#define LF_DOT_CASE(GG)                                                                                                 \
+    case GG:                                                                                                            \
+        hipLaunchKernelGGL((dot_tensor_kernel<GG>), grid, dim3(256), 0, st, (const i64 *)x, (i64)4 * ell * N, (i64 *)T, (i64 *)t2, ell, N, \
+                           xpl, first, (const i64 *)ql, (const i64 *)qh, (const i64 *)kl, (const i64 *)kh);            \
+        break;
+    switch (g) { LF_DOT_CASE(1) LF_DOT_CASE(2) LF_DOT_CASE(4) }
+#undef LF_DOT_CASE
+    return (int)hipGetLastError();
+}
+
+// lf_dot_relin: lf_relin_core_batch (one ciphertext) whose fold reads the summed triplet T instead of an operand stack: the
+// digits in `state` are those of T2's inverse transform; the (digit, own limb) pairs are not extended, the inner product takes
+// T2's words for them; the sums receive P T0 and P T1 on the ordinary rows.
+int lf_dot_relin(const int64_t *state, int nparts, int rows, int logN, const int64_t *desc, const int64_t *E, const double *Ed,
+                 const int64_t *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format, int64_t *tmp, int64_t *s,
+                 const int64_t *psi_br, const double *psi_dp, const int64_t *ipsi_br, const double *ipsi_dp, const int64_t *Ninv,
+                 const int64_t *T, const int64_t *PR, int ell, const uint8_t *own, const int64_t *q_host, const int64_t *ql,
+                 const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st) {
+    if (nparts < 1 || nparts > 254 || rows < 1 || rows > MAX_LIST_ROWS || logN <= NTT_TILE_LOG_MAX || logN > KS_LOGN_MAX || !q_host ||
+        !psi_dp || !ipsi_dp || !Ed || !T || !PR || ell < 0 || ell > rows)
+        return LF_ERR_ARG;
+    if (int e = ks_forward(state, 0, 1, nparts, rows, logN, desc, E, Ed, tmp, psi_br, psi_dp, q_host, ql, qh, kl, kh, st,
+                           (const unsigned char *)own, 0))
+        return e;
+    const RelinFold fold{(const i64 *)T, 0, (const i64 *)PR, ell, (const unsigned char *)own, 0};
+    return ks_tail(1, nparts, rows, logN, ksk, part_stride, comp_stride, row_off, tmp, s, ipsi_br, ipsi_dp, Ninv, q_host, ql, qh, kl, kh,
+                   st, &fold, key_format, true);
+}
 
 // The key-dependent half of nr (1, 2 or 4) hoisted rotations of ONE ciphertext (lf_rotate_hoisted, ckks_ops.hip): inner product of
 // the extended digits `ext` [nparts][rows][N] (lf_ks_fwd) gathered by pi_{p_i} with key i, then the inverse transform of the

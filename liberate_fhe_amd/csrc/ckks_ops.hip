@@ -35,6 +35,15 @@ int lf_ks_giant_sums(int64_t p, int nparts, int rows, int logN, const int64_t *k
                      int64_t row_off, int key_format, const int64_t *ext, const int64_t *s0, int64_t *acc, const int64_t *q_host,
                      const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st);
 
+// ckks_ks.hip: the launches of lf_cc_dot that are its own
+int lf_dot_tensor(int g, const int64_t *x, int64_t *T, int64_t *t2, int ell, int logN, int xpl, int first, const int64_t *ql,
+                  const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st);
+int lf_dot_relin(const int64_t *state, int nparts, int rows, int logN, const int64_t *desc, const int64_t *E, const double *Ed,
+                 const int64_t *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format, int64_t *tmp, int64_t *s,
+                 const int64_t *psi_br, const double *psi_dp, const int64_t *ipsi_br, const double *ipsi_dp, const int64_t *Ninv,
+                 const int64_t *T, const int64_t *PR, int ell, const uint8_t *own, const int64_t *q_host, const int64_t *ql,
+                 const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st);
+
 extern "C" {
 
 static int plan_ok(const lf_ks_plan *p) {
@@ -106,6 +115,68 @@ int lf_cc_mult_evk(const lf_ks_plan *p, const int64_t *const *in, const int64_t 
                                     row_off, key_format | (xpl ? LF_STACK_PLANES : 0), p->ext, p->sum, p->psi, p->psi_dp, p->ipsi, p->ipsi_dp, p->Ninv, p->x4, 0, p->PR, ell,
                                     p->own, p->q_host, p->ql, p->qh, p->kl, p->kh, dev, stream))
         return e;
+    const int64_t *ss[2] = {p->sum, p->sum + (int64_t)rows * N};
+    int64_t *outs[2] = {out0, out1};
+    return moddown_any(p, ss, outs, nullptr, 2, 0, nullptr, stream);
+}
+
+/* ---- cc_dot: sum_i a_i * b_i under ONE relinearisation (include/ckks_hip.h).  Everything of a cc_mult but the tensor products is
+ * linear in the triplet (d0, d1, d2), so the triplets are summed in the NTT domain and the inverse transform, the digits, their
+ * extension, the inner product with the key, the sums' inverse transform and the mod-down run once, on the sum. ---- */
+static int dot_ok(const lf_ks_plan *p) { return plan_ok(p) && p->rescale_scales && p->PR && p->x4 && p->d2; }
+
+// the accumulated triplet T = [3][ell][N]
+int64_t lf_cc_dot_ws_words(const lf_ks_plan *p) {
+    if (!dot_ok(p)) return 0;
+    return ((int64_t)3 * p->ell) << p->logN;
+}
+
+int lf_cc_dot(const lf_ks_plan *p, int np, const int64_t *const *in, const int64_t *const *row0, const int64_t *ksk,
+              int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format, int64_t *ws, int64_t ws_words, int64_t *out0,
+              int64_t *out1, void *stream) {
+    if (!dot_ok(p) || np < 1 || !in || !row0 || !ksk || !out0 || !out1 || (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES))
+        return LF_ERR_ARG;
+    if (key_format == LF_KEY_PLANES && ((((uintptr_t)ksk | (uintptr_t)(part_stride * 8) | (uintptr_t)(comp_stride * 8)) & 15)))
+        return LF_ERR_ARG;
+    for (int64_t i = 0; i < (int64_t)4 * np; ++i)
+        if (!in[i] || !row0[i]) return LF_ERR_ARG;
+    const int64_t need = lf_cc_dot_ws_words(p);
+    if (need && (!ws || ws_words < need)) return LF_ERR_ARG;
+    const int ell = p->ell, rows = p->ell + p->K, logN = p->logN, dev = p->device;
+    const int64_t N = (int64_t)1 << logN, poly = (int64_t)ell * N;
+    const int xpl = stack_planes(p);
+    const int relaxed_plain = LF_NTT_RELAXED | LF_NTT_PLAIN | (xpl ? LF_NTT_PLANES : 0);
+    const int gmax = p->max_nct >= 4 ? 4 : p->max_nct >= 2 ? 2 : 1;
+    if (int e = lf_set_device(dev)) return e;
+    int64_t *T = ws;
+    for (int i0 = 0; i0 < np;) {
+        const int left = np - i0;
+        const int g = left >= 4 && gmax >= 4 ? 4 : left >= 2 && gmax >= 2 ? 2 : 1;
+        // 1. x0, x1, y0, y1 of the chunk's pairs: rescale inside the forward transform, two pairs (8 polynomials) per call
+        for (int t0 = 0; t0 < g; t0 += 2) {
+            const int n = g - t0 < 2 ? g - t0 : 2;
+            if (int e = lf_rescale_ntt(in + 4 * (i0 + t0), row0 + 4 * (i0 + t0), 4 * n, p->x4 + (int64_t)t0 * 4 * poly, ell, logN,
+                                       p->rescale_scales, p->round_at, p->psi, p->psi_dp, p->q_host, p->Rs, relaxed_plain, p->_2q, p->ql,
+                                       p->qh, p->kl, p->kh, dev, stream))
+                return e;
+        }
+        // 2. their tensor products into the one triplet; the last launch leaves a copy of T2 where its inverse transform runs
+        if (int e = lf_dot_tensor(g, p->x4, T, i0 + g == np ? p->d2 : nullptr, ell, logN, xpl, i0 == 0, p->ql, p->qh, p->kl, p->kh,
+                                  (hipStream_t)stream))
+            return e;
+        i0 += g;
+    }
+    // 3. T2 -> canonical coefficients (the words lf_intt_mul leaves for one pair), its digits
+    if (int e = lf_intt(p->d2, 1, ell, logN, p->ipsi, p->ipsi_dp, p->q_host, p->Ninv, 2, LF_NTT_RELAXED | LF_NTT_PLAIN, p->_2q, p->ql, p->qh,
+                        p->kl, p->kh, dev, stream))
+        return e;
+    if (int e = lf_ks_digits(p->d2, p->state, p->dig_nparts, p->dig_desc, p->dig_tab, N, p->ql, p->qh, p->kl, p->kh, dev, stream)) return e;
+    // 4. the key switch of T2 with P T0, P T1 folded into its sums, own-limb digit words from T2
+    if (int e = lf_dot_relin(p->state, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, ksk, part_stride, comp_stride, row_off, key_format,
+                             p->ext, p->sum, p->psi, p->psi_dp, p->ipsi, p->ipsi_dp, p->Ninv, T, p->PR, ell, p->own, p->q_host, p->ql,
+                             p->qh, p->kl, p->kh, (hipStream_t)stream))
+        return e;
+    // 5. one mod-down, no addend
     const int64_t *ss[2] = {p->sum, p->sum + (int64_t)rows * N};
     int64_t *outs[2] = {out0, out1};
     return moddown_any(p, ss, outs, nullptr, 2, 0, nullptr, stream);

@@ -398,6 +398,19 @@ class HipBackend:
                                 row_off, self._kfmt(key), out.data_ptr(), out.data_ptr() + plane, st), "lf_switch_key")
 
     @staticmethod
+    def cc_dot_ws_words(plan):
+        return int(lib.lf_cc_dot_ws_words(ctypes.byref(plan)))
+
+    def cc_dot_native(self, plan, ins, row0s, key, first_part, row_off, out, ws):
+        """sum of len(ins) / 4 ciphertext products under one relinearisation as ONE native call (lf_cc_dot).  ins / row0s:
+        ctypes arrays of 4 device pointers per pair, in cc_mult_evk's order; out [2, ell, N]; ws: at least
+        cc_dot_ws_words(plan) words (the summed triplet)."""
+        dev, st = _ds(out)
+        base, ps, cs = self._key_args(key, first_part)
+        check(lib.lf_cc_dot(ctypes.byref(plan), len(ins) // 4, ins, row0s, base, ps, cs, row_off, self._kfmt(key), _p(ws),
+                            0 if ws is None else ws.numel(), out.data_ptr(), out.data_ptr() + out.stride(0) * 8, st), "lf_cc_dot")
+
+    @staticmethod
     def rotate_hoisted_ws_words(plan):
         return int(lib.lf_rotate_hoisted_ws_words(ctypes.byref(plan)))
 

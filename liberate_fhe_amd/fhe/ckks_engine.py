@@ -1323,6 +1323,63 @@ class ckks_engine(EvaluatorOps):
             return torch.as_strided(t0, (len(ts),) + tuple(t0.shape), (t0.numel(),) + tuple(t0.stride()))
         return None
 
+    def cc_dot(self, pairs: list, evk: data_struct, relin=True) -> data_struct:
+        """sum of a_i * b_i over the ciphertext pairs (a_i, b_i) as ONE ciphertext at level + 1, under one relinearisation
+        ("lazy relinearisation"; the reference has no such entry).  Everything of a cc_mult but the tensor product is linear in
+        the triplet (d0, d1, d2), so the triplets are summed and the inverse transforms, the digits, the key switch and the
+        mod-down run once, on the sum: one key stream and one key-switch noise instead of len(pairs).  The result has exactly the
+        words of
+            t = cc_mult(a_0, b_0, evk, relin=False); t = cc_add_triplet(t, cc_mult(a_i, b_i, evk, relin=False)) for i >= 1;
+            relinearize(t, evk)                      (relin=False: t itself)
+        which is also what runs where the native call does not apply (several devices or ranks, logN outside 13..17, a checker
+        backend, relin=False).  One native call (lf_cc_dot) where every limb of both levels is on one device of this process.
+        All operands: ciphertexts of one level, coefficient domain, no special limbs; the same object may appear in any number
+        of pairs and on both sides of one."""
+        pairs = [tuple(p) for p in pairs]
+        if not pairs:
+            raise ValueError("cc_dot: at least one pair of ciphertexts")
+        for pair in pairs:
+            if len(pair) != 2:
+                raise ValueError("cc_dot: pairs of two ciphertexts")
+            for ct in pair:
+                if not is_struct(ct) or ct.origin != types.origins["ct"]:
+                    raise errors.NotMatchType(origin=getattr(ct, "origin", type(ct).__name__), to=types.origins["ct"])
+        l = pairs[0][0].level
+        for a, b in pairs:
+            for ct in (a, b):
+                if ct.level != l:
+                    raise errors.NotMatchDataStructState(origin=f"{ct.origin} at level {ct.level} beside level {l}")
+                if ct.ntt_state or ct.include_special:
+                    raise errors.NotMatchDataStructState(origin=ct.origin)
+        level = l + 1
+        if level >= self.num_levels:
+            raise errors.MaximumLevelError(level=l, level_max=self.num_levels)
+        d = self._native_level(level)
+        if relin and d is not None and self._native_level(l) == d and hasattr(self.backend, "cc_dot_native") \
+                and getattr(self.backend, "relin_fold", False) \
+                and all(t.is_contiguous() and t.dtype == torch.int64 for a, b in pairs for ct in (a, b) for t in (ct.data[0][0], ct.data[1][0])):
+            N, k = self.ctx.N, len(pairs)
+            sizes = getattr(self.backend, "ks_batch_sizes", ())
+            nct = next((n for n in sizes if n <= k), 1)     # pairs per launch of the tensor products: the plan's operand stacks
+            plan, _, first_part, row_off = self._op_plan(level, d, nct)
+            ins, row0s = (ctypes.c_void_p * (4 * k))(), (ctypes.c_void_p * (4 * k))()
+            i = 0
+            for a, b in pairs:
+                for ct in (a, b):
+                    for comp in range(2):
+                        ptr = ct.data[comp][0].data_ptr()
+                        row0s[i], ins[i] = ptr, ptr + N * 8      # the dropped limb is the first row; the survivors follow it
+                        i += 1
+            kpack = self._key_pack(evk)[self._loc(0, special=True).index(d)]
+            ws = self._ws("dot_ws", (self.backend.cc_dot_ws_words(plan),), d)
+            out = torch.empty((2, plan.ell, N), dtype=torch.int64, device=self.ntt.devices[d])
+            self.backend.cc_dot_native(plan, ins, row0s, kpack, first_part, row_off, out, ws)
+            return self._new(([out[0]], [out[1]]), types.origins["ct"], level=level)
+        t = self.cc_mult(pairs[0][0], pairs[0][1], evk, relin=False)
+        for a, b in pairs[1:]:
+            t = self.cc_add_triplet(t, self.cc_mult(a, b, evk, relin=False))
+        return self.relinearize(t, evk) if relin else t
+
     # =============================================================================================
     # hybrid key switching (eng.py:654-961)
     # =============================================================================================

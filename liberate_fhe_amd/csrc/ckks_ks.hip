@@ -40,18 +40,18 @@
     } while (0)
 
 // the same word into a row in planes format (u32 low[N] at byte 0, u16 high[N] at byte 4 N); rowb = the row's first word
-#define KS_ST_PL(rowb, N, idx, v)                                                                          \
-    do {                                                                                                   \
-        const i64 v_ = (i64)(v);                                                                           \
-        unsigned *lo_ = uniform_ptr(reinterpret_cast<unsigned *>(rowb) + (idx));                           \
-        unsigned short *hi_ = uniform_ptr(reinterpret_cast<unsigned short *>((rowb) + ((N) >> 1)) + (idx)); \
-        if (NT_KS_EXT) {                                                                                   \
-            __builtin_nontemporal_store((unsigned)v_, lo_ + lane);                                         \
-            __builtin_nontemporal_store((unsigned short)(v_ >> 32), hi_ + lane);                           \
-        } else {                                                                                           \
-            lo_[lane] = (unsigned)v_;                                                                      \
-            hi_[lane] = (unsigned short)(v_ >> 32);                                                        \
-        }                                                                                                  \
+#define KS_ST_PL(rowb, N, idx, v)                                                                                \
+    do {                                                                                                         \
+        const i64 v_ = (i64)(v);                                                                                 \
+        unsigned *lo_ = uniform_at(reinterpret_cast<unsigned *>(rowb) + (idx), lane);                            \
+        unsigned short *hi_ = uniform_at(reinterpret_cast<unsigned short *>((rowb) + ((N) >> 1)) + (idx), lane); \
+        if (NT_KS_EXT) {                                                                                         \
+            __builtin_nontemporal_store((unsigned)v_, lo_);                                                      \
+            __builtin_nontemporal_store((unsigned short)(v_ >> 32), hi_);                                        \
+        } else {                                                                                                 \
+            *lo_ = (unsigned)v_;                                                                                 \
+            *hi_ = (unsigned short)(v_ >> 32);                                                                   \
+        }                                                                                                        \
     } while (0)
 
 namespace {
@@ -324,7 +324,7 @@ __device__ __forceinline__ void ks_ext_cols_body(int b, const i64 *__restrict__ 
                 return;
             }
 #pragma unroll
-            for (int k = 0; k < R; ++k) KS_ST(uniform_row(dst, (i64)k << logC) + lane, dp_to_word(dp_reduce(x[k], c.d.q, c.d.qinv)));
+            for (int k = 0; k < R; ++k) KS_ST(uniform_at(dst + ((i64)k << logC), lane), dp_to_word(dp_reduce(x[k], c.d.q, c.d.qinv)));
             return;
         }
 #pragma unroll
@@ -352,7 +352,7 @@ __device__ __forceinline__ void ks_ext_cols_body(int b, const i64 *__restrict__ 
             return;
         }
 #pragma unroll
-        for (int k = 0; k < R; ++k) KS_ST(uniform_row(dst, (i64)k << logC) + lane, dp_to_word(dp_reduce(x[k], c.d.q, c.d.qinv)));
+        for (int k = 0; k < R; ++k) KS_ST(uniform_at(dst + ((i64)k << logC), lane), dp_to_word(dp_reduce(x[k], c.d.q, c.d.qinv)));
     } else {
         i64 w[R];
         if (wide && alpha > 1) {   // several 60-bit limbs in one digit (no preset has that): term by term

@@ -1106,16 +1106,39 @@ __global__ void __launch_bounds__(NTT_THREADS, NTT_PASS_WAVES) ntt_fwd_pass_mixe
 
 // row pointer of a column step as an opaque SGPR pair: keeps the compiler from folding the lane index into 2^K
 // per-lane 64-bit addresses (32 VGPRs held from the loads to the stores at K = 4)
-__device__ __forceinline__ i64 *uniform_row(i64 *base, i64 off) {
-    i64 *p = base + off;
-    asm("" : "+s"(p));
-    return p;
-}
-
+// The pointer goes through the asm as a GLOBAL (address space 1) pointer: an opaque generic pointer has no known address
+// space, and every access through it becomes a FLAT instruction — a VALU 64-bit add per access to build the per-lane
+// address, and a count on lgkmcnt as well as vmcnt, so that every LDS wait also waits for the loads in flight.  Known to be
+// global, the access is global_* with the SGPR pair as its base and the lane index as a 32-bit offset.  Every caller passes
+// device memory (a kernel argument plus a wave-uniform offset); LDS or private memory must not come through here.
 template <class T>
 __device__ __forceinline__ T *uniform_ptr(T *p) {
-    asm("" : "+s"(p));
-    return p;
+    typedef T __attribute__((address_space(1))) *GP;
+    GP g = (GP)p;
+    asm("" : "+s"(g));
+    return (T *)g;
+}
+
+// Element i of the wave-uniform row p, i the lane's index: the access global_* takes as (SGPR pair) + (32-bit VGPR byte offset).
+// The byte offset is formed in 32 bits — i * sizeof(T) < 2^32 is the caller's promise (i is a thread or tile-word index, at
+// most N / 2 words of a row) — because a 64-bit per-lane offset, which is what `uniform_ptr(p) + i` means wherever the
+// compiler cannot bound i (lf_tid() comes out of an asm), costs a 64-bit VALU add and a VGPR pair per access.
+template <class T>
+__device__ __forceinline__ T *uniform_at(T *p, unsigned i) {
+    typedef T __attribute__((address_space(1))) *GP;
+    typedef char __attribute__((address_space(1))) *GB;
+    GP g = (GP)p;
+    asm("" : "+s"(g));
+    return (T *)(GP)((GB)g + (unsigned)(i * (unsigned)sizeof(T)));
+}
+
+// The lane index as a value of its own from here on, tied to the (wave-uniform) row it will index.  The instruction selector
+// forms the SGPR-base access only where it sees the offset's zero extension in the access's own basic block: an extension the
+// optimiser shares with an earlier block, or hoists out of the tile loop, turns every access behind it back into a 64-bit VALU
+// add.  Taken once in front of a group of accesses; at most one v_mov.
+__device__ __forceinline__ unsigned lane_here(unsigned i, const void *row) {
+    asm("" : "+v"(i) : "s"(row));
+    return i;
 }
 
 // Streaming accesses (the `nt` bit of global loads / stores): words a pass reads once and writes once should not displace
@@ -1248,12 +1271,12 @@ __device__ __forceinline__ void fwd_cols_body(int b, i64 *__restrict__ a, const 
 #pragma unroll
             for (int k = 0; k < R; ++k) {
                 const i64 o = dp_to_word(dp_reduce(x[k], c.d.q, c.d.qinv));
-                __builtin_nontemporal_store((unsigned)o, uniform_ptr(lo + ((i64)k << logC)) + lane);
-                __builtin_nontemporal_store((unsigned short)((u64)o >> 32), uniform_ptr(hi + ((i64)k << logC)) + lane);
+                __builtin_nontemporal_store((unsigned)o, uniform_at(lo + ((i64)k << logC), lane));
+                __builtin_nontemporal_store((unsigned short)((u64)o >> 32), uniform_at(hi + ((i64)k << logC), lane));
             }
             return;
         }
-        COLS_ST_ALL(uniform_row(colu, (i64)k << logC) + lane, dp_to_word(dp_reduce(x[k], c.d.q, c.d.qinv)))
+        COLS_ST_ALL(uniform_at(colu + ((i64)k << logC), lane), dp_to_word(dp_reduce(x[k], c.d.q, c.d.qinv)))
         return;
     }
     i64 w[R];
@@ -1269,7 +1292,7 @@ __device__ __forceinline__ void fwd_cols_body(int b, i64 *__restrict__ a, const 
             w[k] = v < qq ? v : v - qq;
         }
     } else {
-        COLS_LD_ALL(w, uniform_row(colu, (i64)k << logC) + lane)
+        COLS_LD_ALL(w, uniform_at(colu + ((i64)k << logC), lane))
     }
     int odd = 0;
 #pragma unroll
@@ -1293,7 +1316,7 @@ __device__ __forceinline__ void fwd_cols_body(int b, i64 *__restrict__ a, const 
         if (g.relaxed) cols_fwd_stages<ArithDpR, K>(x, c);
         else cols_fwd_stages<ArithDp, K>(x, c);
         const double md = g.relaxed ? c.d.q : c.d.q2, mi = g.relaxed ? c.d.qinv : c.d.q2inv;
-        COLS_ST_ALL(uniform_row(colu, (i64)k << logC) + lane, dp_to_word(dp_reduce(x[k], md, mi)))
+        COLS_ST_ALL(uniform_at(colu + ((i64)k << logC), lane), dp_to_word(dp_reduce(x[k], md, mi)))
     } else {
         // integer class, or a lane of the fp64 class holding signed-lazy words
         if (enter) {
@@ -1306,12 +1329,12 @@ __device__ __forceinline__ void fwd_cols_body(int b, i64 *__restrict__ a, const 
         if (!DP && g.relaxed) {
             // residues only: Shoup products on lazy words (the fold / the entry left them in [0, 2q)), canonical out
             cols_fwd_stages<ArithShoup, K>(w, c);
-            COLS_ST_ALL(uniform_row(colu, (i64)k << logC) + lane, ArithShoup::canon(c, w[k]))
+            COLS_ST_ALL(uniform_at(colu + ((i64)k << logC), lane), ArithShoup::canon(c, w[k]))
             return;
         }
         if (odd || DP) cols_fwd_stages<ArithInt<true>, K>(w, c);
         else cols_fwd_stages<ArithInt<false>, K>(w, c);
-        COLS_ST_ALL(uniform_row(colu, (i64)k << logC) + lane, w[k])
+        COLS_ST_ALL(uniform_at(colu + ((i64)k << logC), lane), w[k])
     }
 }
 
@@ -1347,7 +1370,7 @@ __device__ __forceinline__ void fwd_cols_ws_body(int b, const i64 *__restrict__ 
     const unsigned lane = threadIdx.x;
     i64 w[R];
 #pragma unroll
-    for (int k = 0; k < R; ++k) w[k] = __builtin_nontemporal_load(uniform_ptr(colu + ((i64)k << logC)) + lane);
+    for (int k = 0; k < R; ++k) w[k] = __builtin_nontemporal_load(uniform_at(colu + ((i64)k << logC), lane));
     int odd = 0;
 #pragma unroll
     for (int k = 0; k < R; ++k) odd |= ((u64)w[k] >= (u64)c.m.q2);
@@ -1386,16 +1409,17 @@ __device__ __forceinline__ void fwd_cols_ws_body(int b, const i64 *__restrict__ 
         wflags[(ri << 6) + (((c0 >> 6) & 3u) << 4) + (c0 >> 8)] = wide ? 1 : 0;
     }
     if constexpr (!DP) {
+        const unsigned ls = lane_here(lane, orow);   // (the loads' 8-byte offset lives in another block)
 #pragma unroll
-        for (int k = 0; k < R; ++k) __builtin_nontemporal_store(w[k], uniform_ptr(orow + col0 + ((i64)k << logC)) + lane);
+        for (int k = 0; k < R; ++k) __builtin_nontemporal_store(w[k], uniform_at(orow + col0 + ((i64)k << logC), ls));
     } else {
         unsigned *lo = reinterpret_cast<unsigned *>(orow) + col0;
         unsigned short *mid = reinterpret_cast<unsigned short *>(orow + ((i64)1 << (g.logN - 1))) + col0;
 #pragma unroll
-        for (int k = 0; k < R; ++k) __builtin_nontemporal_store((unsigned)w[k], uniform_ptr(lo + ((i64)k << logC)) + lane);
+        for (int k = 0; k < R; ++k) __builtin_nontemporal_store((unsigned)w[k], uniform_at(lo + ((i64)k << logC), lane));
 #pragma unroll
         for (int k = 0; k < R; ++k)
-            __builtin_nontemporal_store((unsigned short)((u64)w[k] >> 32), uniform_ptr(mid + ((i64)k << logC)) + lane);
+            __builtin_nontemporal_store((unsigned short)((u64)w[k] >> 32), uniform_at(mid + ((i64)k << logC), lane));
         // (pairs of lanes trading halves through DPP so that each stores four bytes — half the store instructions of this plane —
         // measured neutral: 1.5518 against 1.5540 ms per step, tools/ab_ntt_ws.py with a variant build)
         if (wide) {
@@ -1657,8 +1681,8 @@ __device__ __forceinline__ void inv_cols_compute(int poly, int crow, int chunk, 
         const unsigned short *mid = reinterpret_cast<const unsigned short *>(rowb + ((i64)1 << (g.logN - 1))) + col0;
 #pragma unroll
         for (int k = 0; k < R; ++k) {
-            const unsigned l = __builtin_nontemporal_load(uniform_ptr(lo + ((i64)k << logC)) + lane);
-            const unsigned m = __builtin_nontemporal_load(uniform_ptr(mid + ((i64)k << logC)) + lane);
+            const unsigned l = __builtin_nontemporal_load(uniform_at(lo + ((i64)k << logC), lane));
+            const unsigned m = __builtin_nontemporal_load(uniform_at(mid + ((i64)k << logC), lane));
             w[k] = (i64)(((u64)m << 32) | (u64)l);
         }
         if (fany != 0) {
@@ -1674,13 +1698,13 @@ __device__ __forceinline__ void inv_cols_compute(int poly, int crow, int chunk, 
         const unsigned short *hi = reinterpret_cast<const unsigned short *>(rowb + ((i64)1 << (g.logN - 1))) + col0;
 #pragma unroll
         for (int k = 0; k < R; ++k) {
-            const unsigned l = __builtin_nontemporal_load(uniform_ptr(lo + ((i64)k << logC)) + lane);
-            const unsigned m = __builtin_nontemporal_load(uniform_ptr(hi + ((i64)k << logC)) + lane);
+            const unsigned l = __builtin_nontemporal_load(uniform_at(lo + ((i64)k << logC), lane));
+            const unsigned m = __builtin_nontemporal_load(uniform_at(hi + ((i64)k << logC), lane));
             w[k] = (i64)(((u64)m << 32) | (u64)l);
         }
     } else {
 #pragma unroll
-        for (int k = 0; k < R; ++k) w[k] = INV_LD(uniform_row(colu, (i64)k << logC) + lane);
+        for (int k = 0; k < R; ++k) w[k] = INV_LD(uniform_at(colu + ((i64)k << logC), lane));
     }
     int odd = 0;
     if (!WS || fany != 0) {   // (WS: the words of unflagged tiles are lazy words by construction)
@@ -1749,7 +1773,7 @@ __device__ __forceinline__ void inv_cols_body(int b, i64 *__restrict__ a, const 
     i64 *colu = a + ((i64)(poly * g.rows + crow) << g.logN) + chunk * NTT_COL_THREADS;
     const unsigned lane = threadIdx.x;
 #pragma unroll
-    for (int k = 0; k < R; ++k) INV_ST(uniform_row(colu, (i64)k << logC) + lane, out[k]);
+    for (int k = 0; k < R; ++k) INV_ST(uniform_at(colu + ((i64)k << logC), lane), out[k]);
 }
 
 // last pass of an exact inverse transform through a workspace (lf_intt_ws): reads the workspace, writes the tensor
@@ -1771,7 +1795,7 @@ __device__ __forceinline__ void inv_cols_ws_body(int b, const i64 *__restrict__ 
     i64 *colu = a + ((i64)(poly * g.rows + crow) << g.logN) + chunk * NTT_COL_THREADS;
     const unsigned lane = threadIdx.x;
 #pragma unroll
-    for (int k = 0; k < R; ++k) INV_ST(uniform_row(colu, (i64)k << logC) + lane, out[k]);
+    for (int k = 0; k < R; ++k) INV_ST(uniform_at(colu + ((i64)k << logC), lane), out[k]);
 }
 
 template <int K>

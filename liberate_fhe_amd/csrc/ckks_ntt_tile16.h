@@ -326,14 +326,14 @@ __device__ __forceinline__ void fwd_tile16(i64 *sm, i64 *__restrict__ row, int t
         const unsigned short *hi = reinterpret_cast<const unsigned short *>(row + ((i64)1 << (E - 1))) + base;
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            plo[e] = __builtin_nontemporal_load(uniform_ptr(lo + (e << 8)) + (unsigned)w);
-            phi[e] = __builtin_nontemporal_load(uniform_ptr(hi + (e << 8)) + (unsigned)w);
+            plo[e] = __builtin_nontemporal_load(uniform_at(lo + (e << 8), (unsigned)w));
+            phi[e] = __builtin_nontemporal_load(uniform_at(hi + (e << 8), (unsigned)w));
         }
     } else {
 #pragma unroll
         for (int e = 0; e < 16; ++e) {   // SGPR row pointers + lane index
-            if constexpr (NTL) raw[e] = __builtin_nontemporal_load(uniform_row(row + base, e << 8) + (unsigned)w);
-            else raw[e] = uniform_row(row + base, e << 8)[(unsigned)w];
+            if constexpr (NTL) raw[e] = __builtin_nontemporal_load(uniform_at(row + base + (e << 8), (unsigned)w));
+            else raw[e] = *uniform_at(row + base + (e << 8), (unsigned)w);
         }
     }
     if (CHECK) {
@@ -438,6 +438,7 @@ template <bool DP, bool SKIP0>
 __device__ __forceinline__ bool ws_load_tile(const i64 *__restrict__ srow, const unsigned char *__restrict__ wf, int base, int E,
                                              int w, i64 (&raw)[16]) {
     const int wave = __builtin_amdgcn_readfirstlane(w >> 6);
+    w = (int)lane_here((unsigned)w, srow);   // (the slow tile calls this a second time, from another block)
     const u64 *fp = reinterpret_cast<const u64 *>(wf + (wave << 4));
     const u64 fl = fp[0], fh = SKIP0 ? fp[0] : fp[1];
     if constexpr (DP) {
@@ -445,8 +446,8 @@ __device__ __forceinline__ bool ws_load_tile(const i64 *__restrict__ srow, const
         const unsigned short *mid = reinterpret_cast<const unsigned short *>(srow + ((i64)1 << (E - 1))) + base;
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            const unsigned l = __builtin_nontemporal_load(uniform_ptr(lo + (e << 8)) + (unsigned)w);
-            const unsigned m = __builtin_nontemporal_load(uniform_ptr(mid + (e << 8)) + (unsigned)w);
+            const unsigned l = __builtin_nontemporal_load(uniform_at(lo + (e << 8), (unsigned)w));
+            const unsigned m = __builtin_nontemporal_load(uniform_at(mid + (e << 8), (unsigned)w));
             raw[e] = (i64)(((u64)m << 32) | (u64)l);
         }
         if ((fl | fh) != 0) {
@@ -457,7 +458,7 @@ __device__ __forceinline__ bool ws_load_tile(const i64 *__restrict__ srow, const
         }
     } else {
 #pragma unroll
-        for (int e = 0; e < 16; ++e) raw[e] = __builtin_nontemporal_load(uniform_ptr(srow + base + (e << 8)) + (unsigned)w);
+        for (int e = 0; e < 16; ++e) raw[e] = __builtin_nontemporal_load(uniform_at(srow + base + (e << 8), (unsigned)w));
     }
     return (fl | fh) != 0;
 }
@@ -658,22 +659,22 @@ __device__ __forceinline__ void inv_tile16(i64 *sm, const i64 *src_row, i64 *dst
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
                 const i64 o = dp_to_word(dp_addmask(x[e], c.d.q));
-                uniform_ptr(olo + (e << 8))[(unsigned)w] = (unsigned)o;
-                uniform_ptr(ohi + (e << 8))[(unsigned)w] = (unsigned short)((u64)o >> 32);
+                *uniform_at(olo + (e << 8), (unsigned)w) = (unsigned)o;
+                *uniform_at(ohi + (e << 8), (unsigned)w) = (unsigned short)((u64)o >> 32);
             }
         } else if (ok) {   // exact: the lazy word in [0, 2q); relaxed: balanced residue -> canonical
 #pragma unroll
-            for (int e = 0; e < 16; ++e) INV_ST(uniform_row(out, e << 8) + (unsigned)w, dp_to_word(RLX ? dp_addmask(x[e], c.d.q) : x[e]));
+            for (int e = 0; e < 16; ++e) INV_ST(uniform_at(out + (e << 8), (unsigned)w), dp_to_word(RLX ? dp_addmask(x[e], c.d.q) : x[e]));
         }
     } else if (RLX) {
         ok = inv_tile16_steps<ArithShoup, false, true>(sm, sm, raw, w, base, logN, s, cc, false);
 #pragma unroll
-        for (int e = 0; e < 16; ++e) INV_ST(uniform_row(out, e << 8) + (unsigned)w, ArithShoup::canon(c, raw[e]));
+        for (int e = 0; e < 16; ++e) INV_ST(uniform_at(out + (e << 8), (unsigned)w), ArithShoup::canon(c, raw[e]));
     } else {
         ok = inv_tile16_steps<ArithInt<false>, false, RLX>(sm, sm, raw, w, base, logN, s, cc, true);
         if (ok) {
 #pragma unroll
-            for (int e = 0; e < 16; ++e) INV_ST(uniform_row(out, e << 8) + (unsigned)w, raw[e]);
+            for (int e = 0; e < 16; ++e) INV_ST(uniform_at(out + (e << 8), (unsigned)w), raw[e]);
         }
     }
     if (!ok) {
@@ -728,8 +729,8 @@ __device__ __forceinline__ void inv_tile16_ws(i64 *sm, const i64 *src_row, i64 *
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
                 const i64 v = dp_to_word(x[e]);
-                __builtin_nontemporal_store((unsigned)v, uniform_ptr(lo + (e << 8)) + (unsigned)w);
-                __builtin_nontemporal_store((unsigned short)((u64)v >> 32), uniform_ptr(mid + (e << 8)) + (unsigned)w);
+                __builtin_nontemporal_store((unsigned)v, uniform_at(lo + (e << 8), (unsigned)w));
+                __builtin_nontemporal_store((unsigned short)((u64)v >> 32), uniform_at(mid + (e << 8), (unsigned)w));
             }
             if (w == 0) tflags[tile] = 0;
         }
@@ -737,7 +738,7 @@ __device__ __forceinline__ void inv_tile16_ws(i64 *sm, const i64 *src_row, i64 *
         ok = inv_tile16_steps<ArithInt<false>, false, false>(sm, sm, raw, w, base, logN, s, cc, true);
         if (ok) {
 #pragma unroll
-            for (int e = 0; e < 16; ++e) INV_ST(uniform_ptr(ws_row + base + (e << 8)) + (unsigned)w, raw[e]);
+            for (int e = 0; e < 16; ++e) INV_ST(uniform_at(ws_row + base + (e << 8), (unsigned)w), raw[e]);
             if (w == 0) tflags[tile] = 0;
         }
     }
@@ -990,8 +991,11 @@ __global__ void __launch_bounds__(NTT16_THREADS, 4) ntt_pass16_fwd_seq(i64 *dst,
 // one.  The words stay UNASSEMBLED in their registers (an OR on arrival would put the wait right behind the loads): fp64 class
 // low / mid planes (16 + 16 registers), integer class raw words.  A flagged wave (third plane, rare) reloads the slow way.
 template <bool DP> struct TilePf;
+// (mid stays 16 bits wide: kept as `unsigned`, the zero extension of the loaded halfword is placed behind the merge of the
+// "next tile / no next tile" paths, that is right behind the loads, and the prefetch was waited for where it was issued)
 template <> struct TilePf<true> {
-    unsigned lo[16], mid[16];
+    unsigned lo[16];
+    unsigned short mid[16];
 };
 template <> struct TilePf<false> {
     i64 raw[16];
@@ -1001,6 +1005,7 @@ template <bool DP, bool SKIP0>
 __device__ __forceinline__ bool ws_prefetch_tile(const i64 *__restrict__ srow, const unsigned char *__restrict__ wf, int base, int E, int w,
                                                  TilePf<DP> &pf) {
     const int wave = __builtin_amdgcn_readfirstlane(w >> 6);
+    w = (int)lane_here((unsigned)w, srow);   // (called in and outside the tile loop)
     const u64 *fp = reinterpret_cast<const u64 *>(wf + (wave << 4));
     const u64 fl = fp[0], fh = SKIP0 ? fp[0] : fp[1];
     if constexpr (DP) {
@@ -1008,12 +1013,12 @@ __device__ __forceinline__ bool ws_prefetch_tile(const i64 *__restrict__ srow, c
         const unsigned short *mid = reinterpret_cast<const unsigned short *>(srow + ((i64)1 << (E - 1))) + base;
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            pf.lo[e] = __builtin_nontemporal_load(uniform_ptr(lo + (e << 8)) + (unsigned)w);
-            pf.mid[e] = __builtin_nontemporal_load(uniform_ptr(mid + (e << 8)) + (unsigned)w);
+            pf.lo[e] = __builtin_nontemporal_load(uniform_at(lo + (e << 8), (unsigned)w));
+            pf.mid[e] = __builtin_nontemporal_load(uniform_at(mid + (e << 8), (unsigned)w));
         }
     } else {
 #pragma unroll
-        for (int e = 0; e < 16; ++e) pf.raw[e] = __builtin_nontemporal_load(uniform_ptr(srow + base + (e << 8)) + (unsigned)w);
+        for (int e = 0; e < 16; ++e) pf.raw[e] = __builtin_nontemporal_load(uniform_at(srow + base + (e << 8), (unsigned)w));
     }
     return (fl | fh) != 0;
 }

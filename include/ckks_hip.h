@@ -53,6 +53,24 @@ int lf_abi_version(void);
 #define LF_LIMIT_LOGN 4
 int lf_limits(int which);
 
+/* Key-switch digits (`nparts`) where a limb row is of the fp64 class (prime below 2^41): a constant of the ABI, not a capacity
+ * lf_limits reports (its answers stay as they are).  The inner products of
+ * that class add one balanced product (|.| <= q / 2) per digit and reduce once, with a reduction that is exact for |x| < 64 q.
+ * The kernel that adds most besides (the giant step of lf_linear_transform_bsgs: a gathered word and an accumulator word, both
+ * below 2q) needs nparts / 2 + 4 < 64, so 119 digits is the most for which every such sum is proven in range.  Every entry that
+ * launches such a kernel - lf_ks_core(_batch), lf_ks_tail, lf_relin_core_batch, lf_relin_tail and every entry that takes an
+ * lf_ks_plan - returns LF_ERR_ARG before any launch when q_host holds a prime of that class and nparts is larger.  Parameter
+ * sets whose rows are all of the integer class keep the entries' own limit (254 where one is stated): they reduce after every
+ * addition. */
+#define LF_FP64_MAX_DIGITS 119
+
+/* Keyed baby steps of one lf_linear_transform_bsgs call: slot 0 is the ciphertext and slots 1 .. 63 the keys, one bit each of the
+ * 64-bit masks of the diagonal products.  lf_linear_transform_bsgs and lf_linear_transform_bsgs_ws_words refuse more. */
+#define LF_BSGS_MAX_BABY_KEYS 63
+
+/* Every entry that takes an lf_ks_plan also refuses a plan with more than lf_limits(LF_LIMIT_ROWS) rows (ell + K), as the step
+ * entries do for their `rows`. */
+
 /* Launch-shape thresholds (never results: every setting produces the same words).  Returns the previous value, -1 for an
  * unknown `which`; value < 0 only reads.  PROCESS-WIDE mutable state, read by every entry at launch time on whatever
  * thread calls it and not synchronised: set it once, before any other thread launches (the engine never touches it; only

@@ -1160,6 +1160,22 @@ bool digit_planes(int logN, const RowList &dp, const RowList &in) {
 }
 
 }  // namespace
+
+// LF_FP64_MAX_DIGITS (include/ckks_hip.h): every fp64-class inner product adds `nparts` balanced products (|.| <= q / 2 each)
+// and reduces once with dp_reduce, exact for |x| < 64 q.  What else joins the sum before that reduction, per kernel:
+//   ks_inner_hoist_kernel                  nothing                                    nparts / 2     < 64:  nparts <= 127
+//   ks_inner2(_presum)_kernel              the fold's balanced product with PR        nparts / 2 + 1/2 < 64: nparts <= 126
+//   ks_inner_baby_kernel, ks_inner_lt_     one word of P c0 below 2q                  nparts / 2 + 2 < 64:  nparts <= 123
+//     kernel (it reduces there with dp_reduce_bal, |x| < 2^52, and its running pair stays within (NR + 2) q)
+//   ks_inner_giant_kernel                  a word of S^g_0 and one of the accumulator, both below 2q
+//                                                                                     nparts / 2 + 4 < 64:  nparts <= 119
+// The tightest holds for all of them.  Integer-class rows reduce after every addition and have no such bound.
+bool lf_fp64_digits_ok(int nparts, int rows, const int64_t *q_host) {
+    if (nparts <= LF_FP64_MAX_DIGITS || !q_host) return true;
+    for (int r = 0; r < rows; ++r)
+        if ((uint64_t)q_host[r] < SMALL_PRIME_LIMIT) return false;
+    return true;
+}
 extern "C" int lf_stack_planes(int logN, int rows, const int64_t *q_host) {
     if (!g_digit_planes || !(g_more_planes & 2) || logN <= NTT_TILE_LOG_MAX || logN > KS_LOGN_MAX || !q_host || rows < 1) return 0;
     int small = 0, large = 0;
@@ -1374,6 +1390,7 @@ int lf_dot_relin(const int64_t *state, int nparts, int rows, int logN, const int
     if (nparts < 1 || nparts > 254 || rows < 1 || rows > MAX_LIST_ROWS || logN <= NTT_TILE_LOG_MAX || logN > KS_LOGN_MAX || !q_host ||
         !psi_dp || !ipsi_dp || !Ed || !T || !PR || ell < 0 || ell > rows)
         return LF_ERR_ARG;
+    if (!lf_fp64_digits_ok(nparts, rows, q_host)) return LF_ERR_ARG;
     if (int e = ks_forward(state, 0, 1, nparts, rows, logN, desc, E, Ed, tmp, psi_br, psi_dp, q_host, ql, qh, kl, kh, st,
                            (const unsigned char *)own, 0))
         return e;
@@ -1391,6 +1408,7 @@ int lf_ks_tail_hoisted(int nr, const unsigned *p, int nparts, int rows, int logN
                        int64_t scratch_words, const int64_t *ipsi_br, const double *ipsi_dp, const int64_t *Ninv, const int64_t *q_host,
                        const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st) {
     if (!ipsi_dp || (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES) || (nr != 1 && nr != 2 && nr != 4)) return LF_ERR_ARG;
+    if (rows < 1 || rows > MAX_LIST_ROWS || !lf_fp64_digits_ok(nparts, rows, q_host)) return LF_ERR_ARG;
     HoistKeys hk{};
     for (int i = 0; i < nr; ++i) {
         if (!ksk[i]) return LF_ERR_ARG;
@@ -1442,6 +1460,7 @@ int lf_ks_tail_lt(int nr, const int64_t *p_host, int nparts, int rows, int ell, 
                   const int64_t *kl, const int64_t *kh, hipStream_t st) {
     if (!ipsi_dp || (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES) || nr < 0 || (nr == 0 && !pt0) || !chat || ell < 0 || ell > rows)
         return LF_ERR_ARG;
+    if (rows < 1 || rows > MAX_LIST_ROWS || !lf_fp64_digits_ok(nparts, rows, q_host)) return LF_ERR_ARG;
     for (int i = 0; i < nr; ++i)
         if (!ksk[i] || !pt || (key_format == LF_KEY_PLANES && ((((uintptr_t)ksk[i] | (uintptr_t)(part_stride * 8) | (uintptr_t)(comp_stride * 8)) & 15))))
             return LF_ERR_ARG;
@@ -1500,6 +1519,7 @@ int lf_ks_baby_sums(int nr, const int64_t *p_host, int nparts, int rows, int ell
                     int64_t comp_stride, int64_t row_off, int key_format, const int64_t *chat0, const int64_t *ext, int64_t *u,
                     const int64_t *q_host, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st) {
     if (nr < 0 || !chat0 || !u || ell < 0 || ell > rows) return LF_ERR_ARG;
+    if (rows < 1 || rows > MAX_LIST_ROWS || !lf_fp64_digits_ok(nparts, rows, q_host)) return LF_ERR_ARG;
     for (int i = 0; i < nr; ++i)
         if (!key_args_ok(ksk[i], part_stride, comp_stride, key_format)) return LF_ERR_ARG;
     if (!nr) return 0;
@@ -1567,6 +1587,7 @@ int lf_ks_giant_sums(int64_t p, int nparts, int rows, int logN, const int64_t *k
                      int64_t row_off, int key_format, const int64_t *ext, const int64_t *s0, int64_t *acc, const int64_t *q_host,
                      const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st) {
     if (!key_args_ok(ksk, part_stride, comp_stride, key_format) || !s0 || !acc) return LF_ERR_ARG;
+    if (rows < 1 || rows > MAX_LIST_ROWS || !lf_fp64_digits_ok(nparts, rows, q_host)) return LF_ERR_ARG;
     RowList dp, in;
     classify_rows(rows, q_host, dp, in);
     const bool dplanes = digit_planes(logN, dp, in);
@@ -1630,6 +1651,7 @@ int lf_ks_core_batch(const int64_t *state, int64_t state_stride, int nct, int np
     if (nparts < 1 || rows < 1 || rows > MAX_LIST_ROWS || logN <= NTT_TILE_LOG_MAX || logN > KS_LOGN_MAX ||
         !q_host || !psi_dp || !ipsi_dp || !Ed || (nct != 1 && nct != 2 && nct != 4))
         return LF_ERR_ARG;
+    if (!lf_fp64_digits_ok(nparts, rows, q_host)) return LF_ERR_ARG;
     if (int e = lf_set_device(device)) return e;
     hipStream_t st = (hipStream_t)stream;
     if (int e = ks_forward(state, state_stride, nct, nparts, rows, logN, desc, E, Ed, tmp, psi_br, psi_dp, q_host, ql, qh, kl, kh, st))
@@ -1661,6 +1683,7 @@ int lf_ks_tail(int nparts, int rows, int logN, const int64_t *ksk, int64_t part_
     if (nparts < 1 || rows < 1 || rows > MAX_LIST_ROWS || logN <= NTT_TILE_LOG_MAX || logN > KS_LOGN_MAX ||
         !q_host || !ipsi_dp)
         return LF_ERR_ARG;
+    if (!lf_fp64_digits_ok(nparts, rows, q_host)) return LF_ERR_ARG;
     if (int e = lf_set_device(device)) return e;
     return ks_tail(1, nparts, rows, logN, ksk, part_stride, comp_stride, row_off, tmp, s, ipsi_br, ipsi_dp, Ninv, q_host, ql, qh, kl,
                    kh, (hipStream_t)stream, nullptr, key_format);
@@ -1678,6 +1701,7 @@ int lf_relin_core_batch(const int64_t *state, int64_t state_stride, int nct, int
     if (nparts < 1 || nparts > 254 || rows < 1 || rows > MAX_LIST_ROWS || logN <= NTT_TILE_LOG_MAX || logN > KS_LOGN_MAX ||
         !q_host || !psi_dp || !ipsi_dp || !Ed || (nct != 1 && nct != 2 && nct != 4) || !x || !PR || ell < 0 || ell > rows)
         return LF_ERR_ARG;
+    if (!lf_fp64_digits_ok(nparts, rows, q_host)) return LF_ERR_ARG;
     if (int e = lf_set_device(device)) return e;
     hipStream_t st = (hipStream_t)stream;
     if (int e = ks_forward(state, state_stride, nct, nparts, rows, logN, desc, E, Ed, tmp, psi_br, psi_dp, q_host, ql, qh, kl, kh, st,
@@ -1711,6 +1735,7 @@ int lf_relin_tail(int nparts, int rows, int logN, const int64_t *ksk, int64_t pa
     if (nparts < 1 || nparts > 254 || rows < 1 || rows > MAX_LIST_ROWS || logN <= NTT_TILE_LOG_MAX || logN > KS_LOGN_MAX ||
         !q_host || !ipsi_dp || !x || !PR || ell < 0 || ell > rows)
         return LF_ERR_ARG;
+    if (!lf_fp64_digits_ok(nparts, rows, q_host)) return LF_ERR_ARG;
     if (int e = lf_set_device(device)) return e;
     const int xpl = (key_format & LF_STACK_PLANES) ? 1 : 0;
     if (int e = lf_fmt_expect(x, ((size_t)4 * ell << logN) * 8, xpl ? LF_FMT_PLANES : LF_FMT_RAW)) return e;

@@ -11,6 +11,8 @@
 #include "ckks_common.h"
 
 extern int lf_g_intt_digits;   // ckks_ks.hip (lf_tune)
+// ckks_ks.hip: false when a row is of the fp64 class and nparts exceeds LF_FP64_MAX_DIGITS (reads q_host[0 .. rows))
+bool lf_fp64_digits_ok(int nparts, int rows, const int64_t *q_host);
 // ckks_ks.hip: the key-dependent half of lf_rotate_hoisted (gathered inner product of up to 4 keys + inverse NTT of their sums)
 int lf_ks_tail_hoisted(int nr, const unsigned *p, int nparts, int rows, int logN, const int64_t *const *ksk, int64_t part_stride,
                        int64_t comp_stride, int64_t row_off, int key_format, const int64_t *ext, int64_t *s, int64_t *scratch,
@@ -50,7 +52,9 @@ static int plan_ok(const lf_ks_plan *p) {
     return p && p->logN > NTT_TILE_LOG_MAX && p->logN <= KS_LOGN_MAX && p->ell >= 1 && p->K >= 1 && p->K <= KS_MAX_K &&
            p->nparts >= 1 && p->dig_nparts >= 0 && p->max_nct >= 1 && p->ql && p->qh && p->kl && p->kh && p->_2q && p->Rs && p->Ninv && p->q_host &&
            p->psi && p->ipsi && p->psi_dp && p->ipsi_dp && p->dig_desc && p->dig_tab && p->ext_desc && p->E && p->Ed && p->PiR &&
-           p->state && p->ext && p->sum && p->md_ws;
+           p->state && p->ext && p->sum && p->md_ws &&
+           // (every op behind a plan ends in an fp64-class inner product where a row is of that class: refused here, before any launch)
+           p->ell + p->K <= MAX_LIST_ROWS && lf_fp64_digits_ok(p->nparts, p->ell + p->K, p->q_host);
 }
 
 // cc_mult's operand stack x4 in planes format (include/ckks_hip.h LF_NTT_PLANES): decided per call from lf_tune's knob; the pieces
@@ -326,7 +330,7 @@ int lf_linear_transform(const lf_ks_plan *p, const int64_t *c0, const int64_t *c
 }
 
 /* ---- linear transform, baby-step / giant-step: y = sum_g rot(sum_b pt_{g,b} * rot(x, b), g) (include/ckks_hip.h) ---- */
-#define LF_BSGS_MAX_BABY_KEYS 63   // slots 0 .. 63 are the bits of lt_diag_products_kernel's masks
+// LF_BSGS_MAX_BABY_KEYS (include/ckks_hip.h): slots 0 .. 63 are the bits of lt_diag_products_kernel's masks
 #define LF_BSGS_S_PAIRS 4          // giant steps per launch of the diagonal products
 
 int64_t lf_linear_transform_bsgs_ws_words(const lf_ks_plan *p, int nb) {

@@ -92,6 +92,9 @@ class HipBackend:
     # capacities compiled into the fused kernels (include/ckks_hip.h: lf_limits)
     limits = {"digit_limbs": int(lib.lf_limits(0)), "special_primes": int(lib.lf_limits(1)), "rows": int(lib.lf_limits(2)),
               "batch": int(lib.lf_limits(3)), "logN": int(lib.lf_limits(4))}
+    # include/ckks_hip.h: LF_BSGS_MAX_BABY_KEYS (tests/test_linear_transform_bsgs_cpu.py holds this copy to the header and to what
+    # lf_linear_transform_bsgs_ws_words accepts)
+    bsgs_max_baby_keys = 63
 
     def warm_twiddles(self, table, c: "Consts"):
         """Build the fp64 twin of a twiddle table on the current stream (otherwise built by its first user)."""

@@ -2137,7 +2137,8 @@ class ckks_engine(EvaluatorOps):
         round_at = self.ctx.q[self.ntt.p.destination_arrays[level][owner][0]] // 2
 
         d = self._native_level(level)
-        if d is not None and hasattr(self.backend, "linear_transform_bsgs_native") and len(kb) < 63 and \
+        if d is not None and hasattr(self.backend, "linear_transform_bsgs_native") and \
+                len(kb) <= getattr(self.backend, "bsgs_max_baby_keys", 0) and \
                 steps == sorted(steps) and ct.data[0][0].is_contiguous() and ct.data[1][0].is_contiguous():
             plan, _, first_part, row_off = self._op_plan(level, d)
             i0 = self._loc(0, special=True).index(d)

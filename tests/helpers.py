@@ -427,6 +427,33 @@ def edge_key(engine, pattern, seed=0, origin="key switch key"):
     return out
 
 
+def edge_diagonals(engine, level, steps, pattern, seed=0, n1=None):
+    """utils.synth.diagonals (n1 given: utils.synth.diagonals_bsgs: steps taken mod num_slots, the baby-step / giant-step
+    tag) — same layout, same origin tags, _remember_diag_pack called the same way — with the lazy words of
+    edge_rows(.., lazy=True) over the ordinary and the special rows of `level`: "top" is 2q - 1 everywhere.  The row ids are
+    shifted by the diagonal's index in the pack ("mixed" then gives every diagonal another rotation of the four patterns,
+    "random" another stream); a word follows its prime's id, not the device that holds it."""
+    import torch
+    from liberate_fhe_amd.utils.synth import _data_struct
+    ds_type = _data_struct(engine)
+    q, N, p = engine.ctx.q, engine.ctx.N, engine.ntt.p
+    steps = sorted(int(s) if n1 is None else int(s) % engine.num_slots for s in steps)
+    packs = []
+    for d in _edge_ids(engine):
+        dest = p.destination_arrays_with_special[level][d]
+        pack = np.empty((len(steps), len(dest), N), dtype=np.int64)
+        for j in range(len(steps)):
+            pack[j] = edge_rows([q[i] for i in dest], N, pattern, seed * 8192 + steps[j], lazy=True, ids=[i + j for i in dest])
+        packs.append(torch.from_numpy(pack).to(engine.ntt.devices[d]))
+    tag = "plain diagonals:" if n1 is None else f"plain diagonals bsgs:{int(n1)};"
+    out = ds_type(data=[[pk[j] for pk in packs] for j in range(len(steps))], include_special=True, ntt_state=True,
+                  montgomery_state=True, origin=tag + ",".join(str(s) for s in steps), level=level,
+                  hash=engine.hash, version=engine.version)
+    if hasattr(engine, "_remember_diag_pack"):
+        engine._remember_diag_pack(out, packs, own=True)   # the rows are views of the packs
+    return out
+
+
 def pre_rescale_rows(q_rows, q_drop, target_rows, row0):
     """The words a_i = ((t_i - rho) q_drop + r) mod q_i whose rescale (a_i - r) q_drop^-1 + rho is t_i, with r = row0 the
     dropped limb's words and rho = [r > q_drop // 2]; Python integers."""

@@ -451,6 +451,88 @@ def test_c_entry_refuses_bad_arguments_before_any_launch():
     assert call(one) == LF_ERR_ARG
 
 
+def test_the_engines_baby_key_limit_is_the_headers_and_the_entrys():
+    """HipBackend.bsgs_max_baby_keys (what ckks_engine._linear_transform_bsgs hands to the native call) equals
+    LF_BSGS_MAX_BABY_KEYS of include/ckks_hip.h, and the library accepts exactly that many: lf_linear_transform_bsgs_ws_words
+    answers for nb = limit and refuses nb = limit + 1, and so does the entry itself (LF_ERR_ARG from its arguments)."""
+    import re
+    from liberate_fhe_amd._native import lib
+    from liberate_fhe_amd.fhe.backend import HipBackend
+    header = open(os.path.join(ROOT, "include", "ckks_hip.h")).read()
+    limit = int(re.search(r"#define LF_BSGS_MAX_BABY_KEYS (\d+)", header).group(1))
+    assert HipBackend.bsgs_max_baby_keys == limit == 63
+    assert "define LF_BSGS_MAX_BABY_KEYS" not in open(os.path.join(ROOT, "liberate_fhe_amd", "csrc", "ckks_ops.hip")).read()
+    plan = _fake_plan(13)
+    assert lib.lf_linear_transform_bsgs_ws_words(ctypes.byref(plan), limit) > 0
+    assert lib.lf_linear_transform_bsgs_ws_words(ctypes.byref(plan), limit + 1) == 0
+
+
+def test_c_entries_refuse_more_digits_than_the_fp64_bound_before_any_launch():
+    """LF_FP64_MAX_DIGITS (include/ckks_hip.h) = 119: the fp64-class inner products add one balanced product (|.| <= q / 2) per
+    digit and reduce once, exactly for |x| < 64 q; ks_inner_giant_kernel adds two words below 2q besides, so nparts / 2 + 4 < 64
+    is the tightest condition over the kernels and 119 the last digit count that meets it.  With a prime below 2^41 in q_host and
+    nparts = 120 every entry that ends in such a kernel returns LF_ERR_ARG from its arguments alone (fake pointers, never
+    dereferenced; a call that passed would launch, so acceptance is read from the *_ws_words functions, which launch nothing).
+    Rows of the integer class only keep the entries' own limit of 254."""
+    from liberate_fhe_amd._native import lib
+    import re
+    LF_ERR_ARG = 10001
+    header = open(os.path.join(ROOT, "include", "ckks_hip.h")).read()
+    BOUND = int(re.search(r"#define LF_FP64_MAX_DIGITS (\d+)", header).group(1))
+    assert BOUND == max(n for n in range(1, 255) if n / 2 + 4 < 64) == 119      # the header's constant IS the derived one
+    dummy = ctypes.c_void_p(64)
+    arr = (ctypes.c_void_p * 8)(*[64] * 8)
+    exps = (ctypes.c_int64 * 4)(3, 5, 7, 9)
+    big = np.array([(1 << 60) - 93, (1 << 60) - 173, (1 << 59) - 55], dtype=np.int64)      # integer class only
+
+    def plan_of(nparts, q):
+        plan = _fake_plan(13)
+        plan.nparts, plan.dig_nparts, plan.q_host = nparts, nparts, q.ctypes.data
+        return plan
+
+    def words(plan):
+        ref = ctypes.byref(plan)
+        return (lib.lf_linear_transform_bsgs_ws_words(ref, 3), lib.lf_cc_dot_ws_words(ref), lib.lf_rotate_hoisted_ws_words(ref))
+
+    assert all(w > 0 for w in words(plan_of(BOUND, _Q)))                    # 119 digits beside an fp64-class row: accepted
+    assert words(plan_of(BOUND + 1, _Q)) == (0, 0, 0)                       # 120: refused
+    assert all(w > 0 for w in words(plan_of(254, big)))                     # integer class only: as before
+    plan = plan_of(BOUND + 1, _Q)
+    ref, S = ctypes.byref(plan), 3 << 13
+    calls = {
+        "lf_linear_transform_bsgs": lambda: lib.lf_linear_transform_bsgs(ref, dummy, dummy, 1, exps, arr, 2, (ctypes.c_int64 * 2)(0, 5), arr,
+                                                                         0, 0, 0, 0, dummy, S, (ctypes.c_int64 * 2)(2, 1),
+                                                                         (ctypes.c_int64 * 3)(0, 1, 1), dummy, 0, dummy, 1 << 40, dummy, dummy, None),
+        "lf_linear_transform": lambda: lib.lf_linear_transform(ref, dummy, dummy, 2, exps, arr, 0, 0, 0, 0, dummy, S, dummy, dummy, 0, dummy,
+                                                               1 << 40, dummy, dummy, None),
+        "lf_rotate_hoisted": lambda: lib.lf_rotate_hoisted(ref, dummy, dummy, 2, exps, 1, arr, 0, 0, 0, 0, dummy, 1 << 40, arr, arr, None),
+        "lf_cc_dot": lambda: lib.lf_cc_dot(ref, 2, arr, arr, dummy, 0, 0, 0, 0, dummy, 1 << 40, dummy, dummy, None),
+        "lf_switch_key": lambda: lib.lf_switch_key(ref, dummy, dummy, 0, 0, dummy, 0, 0, 0, 0, dummy, dummy, None),
+        "lf_cc_mult_evk": lambda: lib.lf_cc_mult_evk(ref, arr, arr, dummy, 0, 0, 0, 0, dummy, dummy, None),
+        "lf_switch_key_batch": lambda: lib.lf_switch_key_batch(ref, 1, arr, arr, 0, 0, dummy, 0, 0, 0, 0, arr, arr, None),
+        "lf_cc_mult_evk_batch": lambda: lib.lf_cc_mult_evk_batch(ref, 1, arr, arr, dummy, 0, 0, 0, 0, arr, arr, None),
+        "lf_cc_mult_evk_post": lambda: lib.lf_cc_mult_evk_post(ref, dummy, 0, 0, 0, 0, dummy, dummy, 3, None),
+        "lf_switch_key_post": lambda: lib.lf_switch_key_post(ref, dummy, 0, 0, dummy, 0, 0, 0, 0, dummy, dummy, 3, None),
+    }
+    q = ctypes.c_void_p(_Q.ctypes.data)
+    n, rows, logN = BOUND + 1, 3, 13
+    calls.update({
+        "lf_ks_core_batch": lambda: lib.lf_ks_core_batch(dummy, 0, 1, n, rows, logN, dummy, dummy, dummy, dummy, 0, 0, 0, 0, dummy, dummy, dummy,
+                                                         dummy, dummy, dummy, dummy, q, dummy, dummy, dummy, dummy, 0, None),
+        "lf_ks_core": lambda: lib.lf_ks_core(dummy, n, rows, logN, dummy, dummy, dummy, dummy, 0, 0, 0, 0, dummy, dummy, dummy, dummy, dummy,
+                                             dummy, dummy, q, dummy, dummy, dummy, dummy, 0, None),
+        "lf_ks_tail": lambda: lib.lf_ks_tail(n, rows, logN, dummy, 0, 0, 0, 0, dummy, dummy, dummy, dummy, dummy, q, dummy, dummy, dummy, dummy,
+                                             0, None),
+        "lf_relin_core_batch": lambda: lib.lf_relin_core_batch(dummy, 0, 1, n, rows, logN, dummy, dummy, dummy, dummy, 0, 0, 0, 0, dummy, dummy,
+                                                               dummy, dummy, dummy, dummy, dummy, dummy, 0, dummy, 2, dummy, q, dummy, dummy,
+                                                               dummy, dummy, 0, None),
+        "lf_relin_tail": lambda: lib.lf_relin_tail(n, rows, logN, dummy, 0, 0, 0, 0, dummy, dummy, dummy, dummy, dummy, dummy, dummy, 2, dummy,
+                                                   q, dummy, dummy, dummy, dummy, 0, None),
+    })
+    for name, call in calls.items():
+        assert call() == LF_ERR_ARG, name
+
+
 def test_bsgs_kernels_use_no_scratch():
     """The three new launches exist under their own names (baby: 1, 2, 4 keys x raw / planes key x raw / planes digits; giant:
     raw / planes key x raw / planes digits; diagonal products: 1, 2, 4 giant steps per launch) with scratch 0, no spill, and an

@@ -625,6 +625,26 @@ int lf_cc_dot(const lf_ks_plan *plan, int np, const int64_t *const *in, const in
               int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format, int64_t *ws, int64_t ws_words, int64_t *out0,
               int64_t *out1, void *stream);
 
+/* Several weighted sums of the same ciphertexts under ONE rescale (the baby-step sums of a polynomial evaluation): for
+ * g < G, out_g = rescale(sum_{t < k} s_{g,t} ct_t) (+ a constant), level l -> l + 1, one launch per group of 4, 2 or 1 outputs
+ * (weighted_sums_kernel<4 | 2 | 1>: every input word is read once per group).
+ * in / row0: HOST arrays of 2 k device pointers, [term][component]: the first surviving row ([rows][N]) resp. the dropped row
+ * of ct_t.c0, ct_t.c1 at level l, lazy words in [0, 2q); the same polynomial may appear any number of times.  out: HOST array of
+ * 2 G device pointers, [output][component], [rows][N] each, canonical.  rows = limbs of level l + 1; ql .. kh hold rows + 1
+ * entries, those of level l: entry 0 is the dropped limb.  scales / round_at as lf_rescale_batch (rows entries).
+ * tab: DEVICE table [G][k][rows + 1] of s_{g,t} R^2 mod q_row (R = 2^62: the kernel sums x_t * tab in 128 bits and reduces
+ * twice); consts: NULL or DEVICE table [G][rows] of plain residues added to coefficient 0 of component 0 after the rescale.
+ * The result has exactly the words of ckks_engine's
+ *     acc = scale_rows(ct_0, s_{g,0});  acc = cc_add(acc, scale_rows(ct_t, s_{g,t})) for t >= 1;  rescale(acc);  add_scalar
+ * (scale_rows = mont_enter_scalar + reduce_2q: mult_int_scalar) for every prime below 2^60.
+ * LF_ERR_ARG before any device call for k < 1 or > LF_WSUM_MAX_TERMS, G < 1 or > LF_WSUM_MAX_OUTPUTS, rows < 0 or
+ * rows + 1 > lf_limits(LF_LIMIT_ROWS), logN outside 13 .. 17, a NULL among in / row0 / out, their entries, tab, scales, ql .. kh. */
+#define LF_WSUM_MAX_TERMS 16
+#define LF_WSUM_MAX_OUTPUTS 64
+int lf_weighted_sums(const int64_t *const *in, const int64_t *const *row0, int64_t *const *out, int k, int G, int rows, int logN,
+                     const int64_t *tab, const int64_t *consts, const int64_t *scales, int64_t round_at, const int64_t *ql,
+                     const int64_t *qh, const int64_t *kl, const int64_t *kh, int device, void *stream);
+
 /* The halves of an op around the digit exchange of a limb-sharded engine (one process per GPU; the reference gathers every
  * digit on every GPU through the host before it extends any, ckks_engine.py:778-829).  The plan describes THIS rank's rows
  * at the level (dig_nparts = the digits it owns, nparts = all digits, state = its own digit rows):

@@ -110,6 +110,7 @@ _SIGNATURES["lf_rotate_hoisted_ws_words"] = [_PL]
 _SIGNATURES["lf_rotate_hoisted"] = [_PL, _P, _P, _I, _P, _I, _P, _L, _L, _L, _I, _P, _L, _P, _P, _P]
 _SIGNATURES["lf_cc_dot_ws_words"] = [_PL]
 _SIGNATURES["lf_cc_dot"] = [_PL, _I, _P, _P, _P, _L, _L, _L, _I, _P, _L, _P, _P, _P]
+_SIGNATURES["lf_weighted_sums"] = [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _L, _P, _P, _P, _P, _I, _P]
 _SIGNATURES["lf_linear_transform_ws_words"] = [_PL]
 _SIGNATURES["lf_linear_transform"] = [_PL, _P, _P, _I, _P, _P, _L, _L, _L, _I, _P, _L, _P, _P, _L, _P, _L, _P, _P, _P]
 _SIGNATURES["lf_linear_transform_bsgs_ws_words"] = [_PL, _I]
@@ -157,5 +158,7 @@ LF_NTT_ONLY_COLS = 4
 LF_NTT_ONLY_TILED = 8
 LF_NTT_PLANES = 16
 LF_STACK_PLANES = 4
+LF_WSUM_MAX_TERMS = 16      # include/ckks_hip.h: terms per lf_weighted_sums call
+LF_WSUM_MAX_OUTPUTS = 64    # .. and outputs
 LF_ERR_ARG = 10001
 LF_ERR_STATE = 10002

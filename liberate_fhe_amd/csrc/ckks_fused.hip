@@ -54,6 +54,99 @@ __global__ void __launch_bounds__(256) rescale_kernel(PtrBatch pb, i64 N, const 
     *reinterpret_cast<longlong2 *>(out + (i64)r * N + j) = o;
 }
 
+// ---- weighted sums under one rescale (ckks_engine.weighted_sums; no counterpart in the reference) ----------------
+// out_g = rescale( sum_t s_{g,t} * ct_t ) [+ const_g on coefficient 0 of component 0], G outputs of the same k inputs per launch.
+// The composition that defines the words keeps a CANONICAL accumulator on every row (mont_enter_scalar + reduce_2q per term,
+// mont_add + reduce_2q per sum), so what the rescale reads is the canonical residue of sum_t s_t x_t on the thread's own row
+// and on the dropped row — a function of the residues alone.  It is formed here without a reduction per term:
+//     X = sum_t x_t * S_t  in 128 bits,  S_t = s_t R^2 mod q < q  (the table),  x_t a lazy word in [0, 2q);
+//     X < k * 2q * q <= 16 * 2^61 * 2^60 = 2^125 for q < 2^60 (the engine takes the composition for a larger prime);
+//     v = (X + ((X k) mod R) q) / R < 2^63 + q: an unsigned word, = X R^-1 (mod q);
+//     w = (v + ((v k) mod R) q) / R <= 2 + (q - 1) + 1 < 2q, = X R^-2 = sum_t s_t x_t (mod q); one conditional subtraction.
+// Then rescale_kernel's arithmetic word for word.  One block walks WSUM_ROWS rows of a column pair, so the dropped row's sums
+// (re-read by every block of a column: L2) are formed once per WSUM_ROWS rows; each input word is read once per launch.
+#define WSUM_ROWS 4
+struct WsumBatch {
+    const i64 *in[2 * LF_WSUM_MAX_TERMS];     // [term][component]: first surviving row
+    const i64 *row0[2 * LF_WSUM_MAX_TERMS];   // [term][component]: the dropped row
+    i64 *out[2 * 4];                          // [output][component]
+};
+
+static __device__ __forceinline__ i64 wsum_canon(u128 X, u64 q, u64 k) {
+    const u64 lo = (u64)X, hi = (u64)(X >> 64);
+    const u64 xl = lo & M62;
+    const u64 s = (xl * k) & M62;
+    const u64 v = ((hi << 2) | (lo >> 62)) + __umul64hi(s << 2, q) + (u64)(xl != 0);
+    const u64 vl = v & M62;
+    const u64 s2 = (vl * k) & M62;
+    const u64 w = (v >> 62) + __umul64hi(s2 << 2, q) + (u64)(vl != 0);
+    return (i64)(w < q ? w : w - q);
+}
+
+template <int G>
+__global__ void __launch_bounds__(256) weighted_sums_kernel(WsumBatch pb, int k, int rows, i64 N, const i64 *__restrict__ tab,
+                                                            const i64 *__restrict__ consts, const i64 *__restrict__ scales,
+                                                            i64 round_at, const i64 *__restrict__ ql, const i64 *__restrict__ qh,
+                                                            const i64 *__restrict__ kl, const i64 *__restrict__ kh) {
+    const int c = blockIdx.z;
+    const i64 j = ((i64)blockIdx.x * 256 + threadIdx.x) * 2;
+    if (j >= N) return;
+    const int L = rows + 1;   // tab [G][k][L], ql .. kh [L]: row 0 is the dropped limb
+    i64 z[G][2];
+    {
+        const RowMod m = load_mod(ql, qh, kl, kh, 0);
+        u128 a[G][2];
+#pragma unroll
+        for (int g = 0; g < G; ++g) a[g][0] = a[g][1] = 0;
+#pragma unroll 4
+        for (int t = 0; t < k; ++t) {
+            const longlong2 x = *reinterpret_cast<const longlong2 *>(pb.row0[2 * t + c] + j);
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                const u64 s = (u64)tab[(i64)(g * k + t) * L];
+                a[g][0] += (u128)(u64)x.x * s;
+                a[g][1] += (u128)(u64)x.y * s;
+            }
+        }
+#pragma unroll
+        for (int g = 0; g < G; ++g) z[g][0] = wsum_canon(a[g][0], m.q, m.k), z[g][1] = wsum_canon(a[g][1], m.q, m.k);
+    }
+    const int r0 = blockIdx.y * WSUM_ROWS;
+    const int r1 = r0 + WSUM_ROWS < rows ? r0 + WSUM_ROWS : rows;
+    for (int r = r0; r < r1; ++r) {
+        const RowMod m = load_mod(ql, qh, kl, kh, r + 1);
+        const i64 sc = scales[r];
+        const i64 off = (i64)r * N + j;
+        u128 a[G][2];
+#pragma unroll
+        for (int g = 0; g < G; ++g) a[g][0] = a[g][1] = 0;
+#pragma unroll 4
+        for (int t = 0; t < k; ++t) {
+            const longlong2 x = *reinterpret_cast<const longlong2 *>(pb.in[2 * t + c] + off);
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                const u64 s = (u64)tab[(i64)(g * k + t) * L + r + 1];
+                a[g][0] += (u128)(u64)x.x * s;
+                a[g][1] += (u128)(u64)x.y * s;
+            }
+        }
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            longlong2 o;
+            i64 v = mm62s(wsum_canon(a[g][0], m.q, m.k) - z[g][0], sc, m.q, m.k) + (i64)(z[g][0] > round_at);
+            v = v < (i64)m.q ? v : v - (i64)m.q;
+            if (consts && c == 0 && j == 0) {   // add_scalar: the const's residue on coefficient 0 of c0, one reduction
+                v += consts[g * rows + r];
+                v = v < (i64)m.q ? v : v - (i64)m.q;
+            }
+            o.x = v;
+            v = mm62s(wsum_canon(a[g][1], m.q, m.k) - z[g][1], sc, m.q, m.k) + (i64)(z[g][1] > round_at);
+            o.y = v < (i64)m.q ? v : v - (i64)m.q;
+            *reinterpret_cast<longlong2 *>(pb.out[2 * g + c] + off) = o;
+        }
+    }
+}
+
 // ---- tensor product (ckks_engine.py:1095-1101) ---------------------------------------------------
 __global__ void __launch_bounds__(256) tensor_kernel(const i64 *__restrict__ x0, const i64 *__restrict__ x1,
                                                      const i64 *__restrict__ y0, const i64 *__restrict__ y1,
@@ -536,6 +629,42 @@ int lf_rescale(const int64_t *in, const int64_t *row0, int64_t *out, int rows, i
                int64_t round_at, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, int device,
                void *stream) {
     return lf_rescale_batch(&in, &row0, &out, 1, rows, N, scales, round_at, ql, qh, kl, kh, device, stream);
+}
+
+int lf_weighted_sums(const int64_t *const *in, const int64_t *const *row0, int64_t *const *out, int k, int G, int rows, int logN,
+                     const int64_t *tab, const int64_t *consts, const int64_t *scales, int64_t round_at, const int64_t *ql,
+                     const int64_t *qh, const int64_t *kl, const int64_t *kh, int device, void *stream) {
+    if (k < 1 || k > LF_WSUM_MAX_TERMS || G < 1 || G > LF_WSUM_MAX_OUTPUTS || rows < 0 || rows + 1 > MAX_LIST_ROWS) return LF_ERR_ARG;
+    if (logN < 13 || logN > KS_LOGN_MAX) return LF_ERR_ARG;
+    if (!in || !row0 || !out || !tab || !scales || !ql || !qh || !kl || !kh) return LF_ERR_ARG;
+    for (int i = 0; i < 2 * k; ++i)
+        if (!in[i] || !row0[i]) return LF_ERR_ARG;
+    for (int i = 0; i < 2 * G; ++i)
+        if (!out[i]) return LF_ERR_ARG;
+    if (rows == 0) return 0;
+    if (int e = lf_set_device(device)) return e;
+    const i64 N = (i64)1 << logN;
+    WsumBatch pb;
+    for (int i = 0; i < 2 * k; ++i) pb.in[i] = (const i64 *)in[i], pb.row0[i] = (const i64 *)row0[i];
+    for (int i = 2 * k; i < 2 * LF_WSUM_MAX_TERMS; ++i) pb.in[i] = nullptr, pb.row0[i] = nullptr;
+    dim3 grid((unsigned)((N / 2 + 255) / 256), (unsigned)((rows + WSUM_ROWS - 1) / WSUM_ROWS), 2u);
+    const i64 L = rows + 1;
+    for (int g0 = 0; g0 < G;) {   // the inputs are read once per group of 4, 2 or 1 outputs
+        const int n = G - g0 >= 4 ? 4 : G - g0 >= 2 ? 2 : 1;
+        for (int i = 0; i < 8; ++i) pb.out[i] = i < 2 * n ? (i64 *)out[2 * g0 + i] : nullptr;
+        const i64 *t = (const i64 *)tab + (i64)g0 * k * L;
+        const i64 *cst = consts ? (const i64 *)consts + (i64)g0 * rows : nullptr;
+#define LF_WSUM_LAUNCH(GG)                                                                                                       \
+    hipLaunchKernelGGL((weighted_sums_kernel<GG>), grid, dim3(256), 0, (hipStream_t)stream, pb, k, rows, N, t, cst,              \
+                       (const i64 *)scales, (i64)round_at, (const i64 *)ql, (const i64 *)qh, (const i64 *)kl, (const i64 *)kh)
+        if (n == 4) LF_WSUM_LAUNCH(4);
+        else if (n == 2) LF_WSUM_LAUNCH(2);
+        else LF_WSUM_LAUNCH(1);
+#undef LF_WSUM_LAUNCH
+        if (hipError_t e = hipGetLastError()) return (int)e;
+        g0 += n;
+    }
+    return 0;
 }
 
 int lf_tensor(const int64_t *x0, const int64_t *x1, const int64_t *y0, const int64_t *y1, int64_t *d0, int64_t *d1,

@@ -129,19 +129,24 @@ struct FmtRange {
     uintptr_t lo, hi;
     int fmt;
     unsigned long long age;
-    unsigned epoch;   // lf_tune generation the range was written under
+    unsigned epoch;   // lf_tune generation (of this format's family) the range was written under
 };
 std::mutex g_fmt_mutex;
 FmtRange g_fmt[256];
 int g_fmt_n = 0;
 unsigned long long g_fmt_clock = 0;
-unsigned g_fmt_epoch = 0;
+// One generation per FAMILY of formats (fmt >> 1: RAW / PLANES, the digit and stack formats, set by LF_TUNE_DIGIT_PLANES and
+// LF_TUNE_MORE_PLANES; WS_SPLIT0 / 1, the workspace of lf_ntt_ws, set by LF_TUNE_WS_EXTRA_STAGE).  A knob ages only the notes of the
+// family it can change, and a reader weighs only notes of the family it reads: a flip of the workspace knob must not turn the
+// stale digit notes on memory the caller's allocator recycled (nobody unregisters a freed buffer) into refusals of hand-filled
+// digits, and a workspace note says nothing about digits written over it later.
+unsigned g_fmt_epoch[2] = {0, 0};
 }  // namespace
 
-// lf_tune changed a format knob: ranges noted before are now "written under another setting"
-void lf_fmt_epoch_bump() {
+// lf_tune changed a knob that sets the formats of fmt's family: its ranges noted before are now "written under another setting"
+void lf_fmt_epoch_bump(int fmt) {
     std::lock_guard<std::mutex> lock(g_fmt_mutex);
-    ++g_fmt_epoch;
+    ++g_fmt_epoch[(fmt >> 1) & 1];
 }
 
 void lf_fmt_note(const void *p, size_t bytes, int fmt) {
@@ -172,7 +177,7 @@ void lf_fmt_note(const void *p, size_t bytes, int fmt) {
             if (g_fmt[i].age < g_fmt[o].age) o = i;
         g_fmt[o] = g_fmt[--g_fmt_n];
     }
-    g_fmt[g_fmt_n++] = FmtRange{lo, hi, fmt, ++g_fmt_clock, g_fmt_epoch};
+    g_fmt[g_fmt_n++] = FmtRange{lo, hi, fmt, ++g_fmt_clock, g_fmt_epoch[(fmt >> 1) & 1]};
 }
 
 int lf_fmt_expect(const void *p, size_t bytes, int fmt) {
@@ -181,8 +186,12 @@ int lf_fmt_expect(const void *p, size_t bytes, int fmt) {
     std::lock_guard<std::mutex> lock(g_fmt_mutex);
     // a mismatching note made under the CURRENT knob setting is not this hazard: it is a stale note on memory the caller's
     // allocator has recycled (nobody unregisters a freed buffer), or a caller that passes explicit format flags and owns them
+    // (.. and a note of the other family is no statement about this one)
+    const int fam = (fmt >> 1) & 1;
     for (int i = 0; i < g_fmt_n; ++i)
-        if (g_fmt[i].hi > lo && g_fmt[i].lo < hi && g_fmt[i].fmt != fmt && g_fmt[i].epoch != g_fmt_epoch) return LF_ERR_STATE;
+        if (g_fmt[i].hi > lo && g_fmt[i].lo < hi && g_fmt[i].fmt != fmt && ((g_fmt[i].fmt >> 1) & 1) == fam &&
+            g_fmt[i].epoch != g_fmt_epoch[fam])
+            return LF_ERR_STATE;
     return 0;
 }
 

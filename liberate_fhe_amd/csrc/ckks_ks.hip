@@ -1625,7 +1625,7 @@ int lf_tune(int which, int value) {
     if (which == LF_TUNE_MORE_PLANES && value > 3) return old;
     if ((which == LF_TUNE_INTT_DIGITS || which == LF_TUNE_DIGIT_PLANES || which == LF_TUNE_WS_EXTRA_STAGE) && value > 1) return old;
     if (*knob != value && (which == LF_TUNE_DIGIT_PLANES || which == LF_TUNE_WS_EXTRA_STAGE || which == LF_TUNE_MORE_PLANES))
-        lf_fmt_epoch_bump();   // scratch written so far was written under another format setting
+        lf_fmt_epoch_bump(which == LF_TUNE_WS_EXTRA_STAGE ? LF_FMT_WS_SPLIT0 : LF_FMT_RAW);   // scratch of that family so far: another setting
     *knob = value;
     return old;
 }

@@ -413,6 +413,19 @@ class HipBackend:
         check(lib.lf_cc_dot(ctypes.byref(plan), len(ins) // 4, ins, row0s, base, ps, cs, row_off, self._kfmt(key), _p(ws),
                             0 if ws is None else ws.numel(), out.data_ptr(), out.data_ptr() + out.stride(0) * 8, st), "lf_cc_dot")
 
+    # include/ckks_hip.h: LF_WSUM_MAX_TERMS / LF_WSUM_MAX_OUTPUTS (tests/test_poly_eval_cpu.py holds these copies to the header)
+    wsum_max_terms = 16
+    wsum_max_outputs = 64
+
+    def weighted_sums_native(self, ins, row0s, outs, k, G, rows, logN, tab, consts, scales, round_at, c: Consts):
+        """G weighted sums of the same k ciphertexts under one rescale as ONE native call (lf_weighted_sums).  ins / row0s:
+        ctypes arrays of 2 k device pointers ([term][component]: first surviving row, dropped row); outs: the 2 G output
+        tensors [rows, N] ([output][component]); tab [G, k, rows + 1] and consts [G, rows] (or None) device tables; c: the
+        constants of the level the operands are at (rows + 1 entries, the dropped limb first)."""
+        dev, st = _ds(outs[0])
+        check(lib.lf_weighted_sums(ins, row0s, _parr(outs), k, G, rows, logN, _p(tab), _p(consts), _p(scales), round_at, *c.mont(),
+                                   dev, st), "lf_weighted_sums")
+
     @staticmethod
     def rotate_hoisted_ws_words(plan):
         return int(lib.lf_rotate_hoisted_ws_words(ctypes.byref(plan)))

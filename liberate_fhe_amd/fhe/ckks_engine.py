@@ -24,6 +24,7 @@ import ctypes
 import math
 import os
 import weakref
+from collections import OrderedDict
 from hashlib import sha256
 
 import numpy as np
@@ -36,6 +37,7 @@ from .backend import Consts
 from .context.ckks_context import ckks_context
 from .data_struct import data_struct
 from .evaluator import EvaluatorOps, is_struct
+from .polyeval import PolyOps
 from .presets import errors, types
 from .version import VERSION
 
@@ -73,7 +75,7 @@ class _OneShard:
         return ckks_engine._decrypt_rows_on(self, ct, sk, self.li, self.dev)
 
 
-class ckks_engine(EvaluatorOps):
+class ckks_engine(EvaluatorOps, PolyOps):
     @errors.log_error
     def __init__(self, devices: list[int] = None, verbose: bool = False, bias_guard: bool = True,
                  norm: str = "forward", backend=None, comm=None, balanced_limb_map: bool = False, **ctx_params):
@@ -133,6 +135,7 @@ class ckks_engine(EvaluatorOps):
         self.create_rescale_scales()
         self.galois_deltas = [2 ** i for i in range(self.ctx.logN - 1)]
         self._tables = {}
+        self._wsum_tables = OrderedDict()   # polyeval.py: device tables of weighted_sums' integers, least recently used of 64 dropped
         self._key_packs = {}
         self._workspace = {}
         self._md_ready = set()

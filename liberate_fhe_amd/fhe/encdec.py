@@ -165,6 +165,69 @@ def bsgs_split(steps, num_slots: int, n1=None) -> tuple:
     return n1, babies, giants
 
 
+def _tree_levels(b: int) -> int:
+    """Levels above the base at which the b-th power stands when powers are built by the tree rule of ckks_engine.poly_eval
+    (a power of two 2^j by j squarings; any other b as top power of two times the rest, one level above the former)."""
+    return (b - 1).bit_length()
+
+
+def poly_schedule(degree: int, n1: int) -> dict:
+    """The level schedule of ckks_engine.poly_eval for a polynomial of this degree split at n1 (a power of two >= 2), levels
+    counted from the operand's: G = ceil((degree + 1) / n1) baby polynomials; "baby": the deepest baby power (all are brought
+    there); "common": the level the baby polynomials (baby + 1) and the giant powers y^g are brought to before cc_dot; "depth":
+    levels consumed; "products": ciphertext products (tensor products, the pairs of the final cc_dot included)."""
+    try:
+        ok = int(degree) == degree and degree >= 1 and int(n1) == n1 and n1 >= 2 and (int(n1) & (int(n1) - 1)) == 0
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"poly_schedule: degree >= 1 and n1 a power of two >= 2 are required, got {degree!r}, {n1!r}")
+    degree, n1 = int(degree), int(n1)
+    G = -(-(degree + 1) // n1)
+    baby = _tree_levels(n1 - 1)
+    if G == 1:
+        return {"n1": n1, "G": 1, "baby": baby, "common": baby + 1, "depth": baby + 1, "products": n1 - 2}
+    common = max(n1.bit_length() - 1 + _tree_levels(G - 1), baby + 1)
+    return {"n1": n1, "G": G, "baby": baby, "common": common, "depth": common + 1,
+            "products": (n1 - 2) + 1 + (G - 2) + (G - 1)}
+
+
+def poly_split(degree: int) -> int:
+    """The baby-step count n1 (a power of two, 2 <= n1 <= the first power of two above `degree`) ckks_engine.poly_eval uses
+    unless told otherwise: the one with the fewest ciphertext products (n1 - 2 baby powers, y = x^n1, G - 2 further giant powers
+    and the G - 1 pairs of the closing cc_dot, G = ceil((degree + 1) / n1)); ties go to the smaller depth, then to the larger n1
+    (more of the work in the fused baby sums, fewer pairs under the closing relinearisation)."""
+    best = None
+    n = 2
+    while True:
+        s = poly_schedule(degree, n)
+        key = (s["products"], s["depth"], -n)
+        if best is None or key < best[0]:
+            best = (key, n)
+        if n > degree:
+            break
+        n *= 2
+    return best[1]
+
+
+def cheb_blocks(coeffs, n1: int) -> np.ndarray:
+    """The Chebyshev series p = sum_i coeffs[i] T_i as p = sum_g r_g(x) T_n1(x)^g with every r_g a Chebyshev series of degree
+    below n1: row g of the result ([G][n1], G = ceil(len(coeffs) / n1)) holds r_g, from repeated numpy chebdiv by T_n1."""
+    from numpy.polynomial import chebyshev as C
+    c = np.asarray(coeffs, dtype=np.float64)
+    G = -(-c.size // n1)
+    divisor = np.zeros(n1 + 1)
+    divisor[n1] = 1.0
+    out = np.zeros((G, n1))
+    for g in range(G):
+        if c.size > n1:
+            c, rem = C.chebdiv(c, divisor)
+        else:
+            c, rem = np.zeros(1), c
+        out[g, :rem.size] = rem
+    return out
+
+
 def ntt_galois_index(logN: int, p: int) -> np.ndarray:
     """pi_p as an int64 index array: NTT(a(X^p))[k] = NTT(a)[pi_p(k)] for the forward transform's order (index k holds the
     evaluation at psi^(2 brev(k) + 1)), pi_p(k) = brev(((2 brev(k) + 1) p mod 2N - 1) / 2).  A pure permutation (p odd):

@@ -282,16 +282,22 @@ class EvaluatorOps:
         scaled = int(scalar * self.scale * np.sqrt(self.deviations[ct.level + 1]) + 0.5)
         return self.rescale(self._scale_rows(ct, self._row_scalars(scaled, ct.level, True)))
 
-    def add_scalar(self, ct, scalar):
-        scaled = int(scalar * self.scale * self.deviations[ct.level] + 0.5)
+    def _add_scalar_int(self, scalar, level):
+        """The integer add_scalar adds to coefficient 0 of c0 at `level`."""
+        scaled = int(scalar * self.scale * self.deviations[level] + 0.5)
         if self.norm == "backward":
             scaled *= self.ctx.N
-        scaled *= self.int_scale
+        return scaled * self.int_scale
+
+    def _add_int_to_coefficient0(self, ct, value):
         out = self.clone(ct)
-        for t, s in zip(out.data[0], self._row_scalars(scaled, ct.level, False)):
+        for t, s in zip(out.data[0], self._row_scalars(value, ct.level, False)):
             t[:, 0] += s
         self.ntt.reduce_2q(out.data[0], ct.level)
         return out
+
+    def add_scalar(self, ct, scalar):
+        return self._add_int_to_coefficient0(ct, self._add_scalar_int(scalar, ct.level))
 
     def sub_scalar(self, ct, scalar):
         return self.add_scalar(ct, -scalar)

@@ -645,6 +645,38 @@ int lf_weighted_sums(const int64_t *const *in, const int64_t *const *row0, int64
                      const int64_t *tab, const int64_t *consts, const int64_t *scales, int64_t round_at, const int64_t *ql,
                      const int64_t *qh, const int64_t *kl, const int64_t *kh, int device, void *stream);
 
+/* Sum of plaintext-ciphertext products under ONE rescale, for plaintexts encoded once (ckks_engine.encode_plain): out decrypts to
+ * sum_i pt_i * ct_i (+ bias), level l -> l + 1.  Plan-free: no key, no digits.
+ * k >= 1 terms; in: HOST array of 2 k device pointers, [term][component]: ct_i.c0, ct_i.c1, each [rows][N] at level l (all its
+ * rows, the dropped limb first), lazy words in [0, 2q), 16-byte aligned; pt: HOST array of k device pointers, [rows][N] each: the
+ * plaintext mc_mult builds (NTT domain, Montgomery form, lazy words below 2q); the same polynomial may appear any number of times.
+ * bias: NULL or the plaintext mc_add builds at level l + 1, [rows - 1][N].  out0 / out1 [rows - 1][N], canonical.
+ * Tables of level l, `rows` entries each, the dropped limb first: psi_br / psi_dp, ipsi_br / ipsi_dp, q_host (HOST), Rs, Ninv,
+ * ql .. kh, and mont_one[r] = R mod q_r (DEVICE); zero_row: N zero words (DEVICE).  rescale_scales / round_at as lf_rescale_batch
+ * (rows - 1 entries).
+ * The result has exactly the words of ckks_engine's
+ *     S_c = mont_mult(pt_0, enter_ntt(ct_0.c));  S_c = mont_add(S_c, mont_mult(pt_i, enter_ntt(ct_i.c))) for i >= 1, c = 0, 1;
+ *     intt_exit_reduce(S_c);  rescale((S_0, S_1));  then mc_add's chain with `bias` on component 0
+ * (k = 1 without bias: mc_mult's words behind its encode).  Only the residues of S reach the result — intt_exit_reduce leaves
+ * canonical words — so S is kept in the relaxed representation of the other fused ops: plain canonical residues on fp64-class
+ * rows, Montgomery-form words below 2q on integer-class rows.
+ * Enqueued: per chunk of 4, 2 or 1 terms ONE lf_rescale_ntt of its 2 g polynomials into the workspace (RELAXED | PLAIN, PLANES
+ * where lf_stack_planes says so; the rescale step of that transform is handed the identity: zero_row as every dropped row,
+ * mont_one as the scales — it is the forward transform that reads its operands where they lie) and ONE launch of
+ * pc_dot_kernel<4 | 2 | 1> adding the chunk's products into S = [2][rows][N] (the first chunk writes); lf_intt (tail 2, relaxed,
+ * plain) of S; ONE lf_rescale_batch of the pair; with a bias one element-wise launch (pc_bias_kernel) on out0.
+ * (k = 1 takes the same launches: lf_intt_mul's product-on-load multiplies PLAIN residues on fp64-class rows, and the plaintext
+ * is in Montgomery form there.)
+ * ws: lf_pc_dot_ws_words(k, rows, logN) = (2 min(k, 4) + 2) rows N words (0 for shapes the entry refuses), 16-byte aligned, lent
+ * by the caller.  LF_ERR_ARG before any device call for k < 1, rows < 2 or > lf_limits(LF_LIMIT_ROWS), logN outside 13 .. 17, a
+ * NULL among the pointers (bias excepted), the 2 k entries of `in`, the k of `pt` or the tables, ws NULL, too small or misaligned. */
+int64_t lf_pc_dot_ws_words(int k, int rows, int logN);
+int lf_pc_dot(int k, const int64_t *const *in, const int64_t *const *pt, const int64_t *bias, int64_t *out0, int64_t *out1, int rows,
+              int logN, const int64_t *psi_br, const double *psi_dp, const int64_t *ipsi_br, const double *ipsi_dp,
+              const int64_t *q_host, const int64_t *Rs, const int64_t *Ninv, const int64_t *mont_one, const int64_t *zero_row,
+              const int64_t *rescale_scales, int64_t round_at, int64_t *ws, int64_t ws_words, const int64_t *ql, const int64_t *qh,
+              const int64_t *kl, const int64_t *kh, int device, void *stream);
+
 /* The halves of an op around the digit exchange of a limb-sharded engine (one process per GPU; the reference gathers every
  * digit on every GPU through the host before it extends any, ckks_engine.py:778-829).  The plan describes THIS rank's rows
  * at the level (dig_nparts = the digits it owns, nparts = all digits, state = its own digit rows):

@@ -111,6 +111,8 @@ _SIGNATURES["lf_rotate_hoisted"] = [_PL, _P, _P, _I, _P, _I, _P, _L, _L, _L, _I,
 _SIGNATURES["lf_cc_dot_ws_words"] = [_PL]
 _SIGNATURES["lf_cc_dot"] = [_PL, _I, _P, _P, _P, _L, _L, _L, _I, _P, _L, _P, _P, _P]
 _SIGNATURES["lf_weighted_sums"] = [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _L, _P, _P, _P, _P, _I, _P]
+_SIGNATURES["lf_pc_dot_ws_words"] = [_I, _I, _I]
+_SIGNATURES["lf_pc_dot"] = [_I, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _I, _P]
 _SIGNATURES["lf_linear_transform_ws_words"] = [_PL]
 _SIGNATURES["lf_linear_transform"] = [_PL, _P, _P, _I, _P, _P, _L, _L, _L, _I, _P, _L, _P, _P, _L, _P, _L, _P, _P, _P]
 _SIGNATURES["lf_linear_transform_bsgs_ws_words"] = [_PL, _I]

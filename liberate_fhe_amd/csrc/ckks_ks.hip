@@ -611,6 +611,110 @@ __global__ void __launch_bounds__(256) dot_tensor_kernel(const i64 *__restrict__
     if (t2 != nullptr) *reinterpret_cast<longlong2 *>(t2 + (i64)r * N + j0) = o[2];
 }
 
+// ---- pc_dot: the products of G ciphertexts with an encoded plaintext each, summed into ONE pair S = [2][rows][N] ------------
+// x = [G][2][rows][N]: c0, c1 per term as lf_rescale_ntt(RELAXED | PLAIN) leaves them (xpl: fp64-class rows as planes);
+// pt[g] = [rows][N]: the plaintext of term g as mc_mult builds it (NTT domain, Montgomery form on every row, lazy words below 2q).
+//     S0 += sum_g pt_g c0_g,   S1 += sum_g pt_g c1_g
+// grid = (N / 512, rows) as dot_tensor_kernel; a thread owns one 16-byte column pair: it reads the 2 G transformed words and the G
+// plaintext words of each of its two coefficients once, sums both components in registers and makes one read-modify-write of S
+// (first: the first chunk writes without reading).  Only the residues of S reach the result (its inverse transform reduces):
+//   fp64-class rows  the plaintext's Montgomery word m R goes through one REDC to the plain m (a word in [0, q]), so that c m is
+//                    the plain product the plain-domain inverse transform expects (ks_inner_lt_kernel treats a diagonal the same
+//                    way); balanced products (|.| <= q / 2): for G = 4 a coefficient's sum is 4 balanced terms plus the one
+//                    canonical word read back, |.| <= 4 q / 2 + q = 3 q < 2^43 for q < 2^41 — inside dp_reduce's |x| < 64 q and
+//                    the exact range of fp64; stored as the plain canonical residue, below q < 2^41: far under the 2^46 a
+//                    relaxed inverse transform takes on these rows;
+//   integer rows     REDC62 products of a canonical word and a lazy one (below 2q), a conditional subtraction after every
+//                    addition: Montgomery form below 2q throughout, what the relaxed inverse transform takes on these rows.
+struct PcTerms {
+    const i64 *pt[4];   // plaintext of term g, [rows][N]
+};
+
+template <int G>
+__global__ void __launch_bounds__(256) pc_dot_kernel(const i64 *__restrict__ x, PcTerms pa, i64 *__restrict__ S, int rows, i64 N, int xpl,
+                                                     int first, const i64 *__restrict__ ql, const i64 *__restrict__ qh,
+                                                     const i64 *__restrict__ kl, const i64 *__restrict__ kh) {
+    const int r = blockIdx.y;
+    const i64 j0 = (i64)blockIdx.x * 512 + threadIdx.x * 2;
+    if (j0 >= N) return;
+    const RowMod m = load_mod(ql, qh, kl, kh, r);
+    const i64 pstride = (i64)rows * N;
+    i64 *s = S + (i64)r * N + j0;
+    longlong2 o[2];
+    if (m.q < SMALL_PRIME_LIMIT) {
+        const RowDp d = make_dp(m);
+        double a[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const i64 *xs = x + (i64)g * 2 * pstride + (i64)r * N;
+            double c0[2], c1[2];
+            ld_pair_dp(xs, j0, N, xpl, c0[0], c0[1]);
+            ld_pair_dp(xs + pstride, j0, N, xpl, c1[0], c1[1]);
+            const longlong2 w = *reinterpret_cast<const longlong2 *>(pa.pt[g] + (i64)r * N + j0);
+            const double wp[2] = {dp_from_word(mm62u((u64)w.x, 1ull, m.q, m.k)), dp_from_word(mm62u((u64)w.y, 1ull, m.q, m.k))};
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                a[0][e] += dp_mulmod_bal(c0[e], wp[e], d);
+                a[1][e] += dp_mulmod_bal(c1[e], wp[e], d);
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            if (!first) {
+                const longlong2 v = *reinterpret_cast<const longlong2 *>(s + c * pstride);
+                a[c][0] += dp_from_word(v.x), a[c][1] += dp_from_word(v.y);
+            }
+            o[c].x = dp_to_word(dp_reduce(a[c][0], d.q, d.qinv));
+            o[c].y = dp_to_word(dp_reduce(a[c][1], d.q, d.qinv));
+        }
+    } else {
+        i64 a[2][2];
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const i64 *xs = x + (i64)g * 2 * pstride + (i64)r * N + j0;
+            const longlong2 C0 = *reinterpret_cast<const longlong2 *>(xs), C1 = *reinterpret_cast<const longlong2 *>(xs + pstride);
+            const longlong2 w = *reinterpret_cast<const longlong2 *>(pa.pt[g] + (i64)r * N + j0);
+            const u64 c0[2] = {(u64)C0.x, (u64)C0.y}, c1[2] = {(u64)C1.x, (u64)C1.y}, wm[2] = {(u64)w.x, (u64)w.y};
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const i64 d0 = mm62u(c0[e], wm[e], m.q, m.k), d1 = mm62u(c1[e], wm[e], m.q, m.k);
+                a[0][e] = g == 0 ? d0 : csub(a[0][e] + d0, m.q2);
+                a[1][e] = g == 0 ? d1 : csub(a[1][e] + d1, m.q2);
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            if (!first) {
+                const longlong2 v = *reinterpret_cast<const longlong2 *>(s + c * pstride);
+                a[c][0] = csub(a[c][0] + v.x, m.q2), a[c][1] = csub(a[c][1] + v.y, m.q2);
+            }
+            o[c].x = a[c][0], o[c].y = a[c][1];
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 2; ++c) *reinterpret_cast<longlong2 *>(s + c * pstride) = o[c];
+}
+
+// pc_dot's bias: mc_add's chain on component 0 of the rescaled sum, word for word —
+//     reduce_2q(mont_redc(mont_add(pt, mont_enter(c0))))
+// c0 [rows][N] canonical, in place; pt [rows][N] the "add" plaintext (Montgomery form, lazy words below 2q).
+__global__ void __launch_bounds__(256) pc_bias_kernel(i64 *__restrict__ c0, const i64 *__restrict__ pt, const i64 *__restrict__ Rs, i64 N,
+                                                      const i64 *__restrict__ ql, const i64 *__restrict__ qh,
+                                                      const i64 *__restrict__ kl, const i64 *__restrict__ kh) {
+    const int r = blockIdx.y;
+    const i64 j = ((i64)blockIdx.x * 256 + threadIdx.x) * 2;
+    if (j >= N) return;
+    const RowMod m = load_mod(ql, qh, kl, kh, r);
+    const i64 rs = Rs[r], off = (i64)r * N + j;
+    const longlong2 v = *reinterpret_cast<const longlong2 *>(c0 + off), w = *reinterpret_cast<const longlong2 *>(pt + off);
+    longlong2 o;
+    i64 t = redc62(csub(mm62s(v.x, rs, m.q, m.k) + w.x, m.q2), m.q, m.k);
+    o.x = t < (i64)m.q ? t : t - (i64)m.q;
+    t = redc62(csub(mm62s(v.y, rs, m.q, m.k) + w.y, m.q2), m.q, m.k);
+    o.y = t < (i64)m.q ? t : t - (i64)m.q;
+    *reinterpret_cast<longlong2 *>(c0 + off) = o;
+}
+
 // ---- K3 of hoisted rotations (lf_rotate_hoisted): ONE ciphertext's extended digits, NR keys with an exponent each ----------
 // X -> X^p permutes the NTT slots: NTT(a(X^p))[k] = NTT(a)[pi_p(k)], pi_p(k) = brev(((2 brev(k) + 1) p mod 2N - 1) / 2) (the forward
 // transform stores the evaluation at psi^(2 brev(k) + 1) at index k).  So the digits of c1, extended and transformed ONCE, serve every
@@ -1376,6 +1480,40 @@ int lf_dot_tensor(int g, const int64_t *x, int64_t *T, int64_t *t2, int ell, int
         break;
     switch (g) { LF_DOT_CASE(1) LF_DOT_CASE(2) LF_DOT_CASE(4) }
 #undef LF_DOT_CASE
+    return (int)hipGetLastError();
+}
+
+// The launches of lf_pc_dot that are its own (ckks_ops.hip checks the arguments).
+// lf_pc_dot_products: the products of g (1, 2 or 4) terms' transformed pairs x = [g][2][rows][N] (xpl: fp64-class rows as planes)
+// with their plaintexts pt[0 .. g), added into S = [2][rows][N] (first: written).
+int lf_pc_dot_products(int g, const int64_t *x, const int64_t *const *pt, int64_t *S, int rows, int logN, int xpl, int first,
+                       const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st) {
+    if ((g != 1 && g != 2 && g != 4) || !x || !pt || !S || rows < 1 || rows > 65535 || logN < 9) return LF_ERR_ARG;
+    const i64 N = (i64)1 << logN;
+    PcTerms pa{};
+    for (int i = 0; i < g; ++i) {
+        if (!pt[i]) return LF_ERR_ARG;
+        pa.pt[i] = (const i64 *)pt[i];
+    }
+    const dim3 grid((unsigned)(N / 512), (unsigned)rows);
+#define LF_PCDOT_CASE(GG)                                                                                                         \
+    case GG:                                                                                                                      \
+        hipLaunchKernelGGL((pc_dot_kernel<GG>), grid, dim3(256), 0, st, (const i64 *)x, pa, (i64 *)S, rows, N, xpl, first,         \
+                           (const i64 *)ql, (const i64 *)qh, (const i64 *)kl, (const i64 *)kh);                                   \
+        break;
+    switch (g) { LF_PCDOT_CASE(1) LF_PCDOT_CASE(2) LF_PCDOT_CASE(4) }
+#undef LF_PCDOT_CASE
+    return (int)hipGetLastError();
+}
+
+// lf_pc_bias: c0 [rows][N] (canonical) <- mc_add's chain with the "add" plaintext pt, in place; constants of those rows.
+int lf_pc_bias(int64_t *c0, const int64_t *pt, const int64_t *Rs, int rows, int logN, const int64_t *ql, const int64_t *qh,
+               const int64_t *kl, const int64_t *kh, hipStream_t st) {
+    if (!c0 || !pt || !Rs || rows < 1 || rows > 65535 || logN < 9) return LF_ERR_ARG;
+    const i64 N = (i64)1 << logN;
+    const dim3 grid((unsigned)(N / 512), (unsigned)rows);
+    hipLaunchKernelGGL(pc_bias_kernel, grid, dim3(256), 0, st, (i64 *)c0, (const i64 *)pt, (const i64 *)Rs, N, (const i64 *)ql,
+                       (const i64 *)qh, (const i64 *)kl, (const i64 *)kh);
     return (int)hipGetLastError();
 }
 

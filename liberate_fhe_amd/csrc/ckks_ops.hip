@@ -46,6 +46,12 @@ int lf_dot_relin(const int64_t *state, int nparts, int rows, int logN, const int
                  const int64_t *T, const int64_t *PR, int ell, const uint8_t *own, const int64_t *q_host, const int64_t *ql,
                  const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st);
 
+// ckks_ks.hip: the launches of lf_pc_dot that are its own
+int lf_pc_dot_products(int g, const int64_t *x, const int64_t *const *pt, int64_t *S, int rows, int logN, int xpl, int first,
+                       const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st);
+int lf_pc_bias(int64_t *c0, const int64_t *pt, const int64_t *Rs, int rows, int logN, const int64_t *ql, const int64_t *qh,
+               const int64_t *kl, const int64_t *kh, hipStream_t st);
+
 extern "C" {
 
 static int plan_ok(const lf_ks_plan *p) {
@@ -184,6 +190,60 @@ int lf_cc_dot(const lf_ks_plan *p, int np, const int64_t *const *in, const int64
     const int64_t *ss[2] = {p->sum, p->sum + (int64_t)rows * N};
     int64_t *outs[2] = {out0, out1};
     return moddown_any(p, ss, outs, nullptr, 2, 0, nullptr, stream);
+}
+
+/* ---- pc_dot: sum_i pt_i * ct_i (+ bias) for plaintexts encoded once, under ONE rescale (include/ckks_hip.h).  Plan-free, like
+ * lf_weighted_sums: no key, no digits.  The product with a plaintext is linear in the ciphertext, so the products are summed
+ * in the NTT domain and the inverse transform and the rescale run once, on the sum. ---- */
+int64_t lf_pc_dot_ws_words(int k, int rows, int logN) {
+    if (k < 1 || rows < 2 || rows > MAX_LIST_ROWS || logN < 13 || logN > KS_LOGN_MAX) return 0;
+    return ((int64_t)(2 * (k < 4 ? k : 4) + 2) * rows) << logN;   // the chunk's transformed pairs + S
+}
+
+int lf_pc_dot(int k, const int64_t *const *in, const int64_t *const *pt, const int64_t *bias, int64_t *out0, int64_t *out1, int rows,
+              int logN, const int64_t *psi_br, const double *psi_dp, const int64_t *ipsi_br, const double *ipsi_dp,
+              const int64_t *q_host, const int64_t *Rs, const int64_t *Ninv, const int64_t *mont_one, const int64_t *zero_row,
+              const int64_t *rescale_scales, int64_t round_at, int64_t *ws, int64_t ws_words, const int64_t *ql, const int64_t *qh,
+              const int64_t *kl, const int64_t *kh, int device, void *stream) {
+    const int64_t need = lf_pc_dot_ws_words(k, rows, logN);
+    if (!need || !in || !pt || !out0 || !out1 || !psi_br || !psi_dp || !ipsi_br || !ipsi_dp || !q_host || !Rs || !Ninv || !mont_one ||
+        !zero_row || !rescale_scales || !ql || !qh || !kl || !kh)
+        return LF_ERR_ARG;
+    if (!ws || ws_words < need || ((uintptr_t)ws & 15)) return LF_ERR_ARG;
+    for (int64_t i = 0; i < (int64_t)2 * k; ++i)
+        if (!in[i]) return LF_ERR_ARG;
+    for (int i = 0; i < k; ++i)
+        if (!pt[i]) return LF_ERR_ARG;
+    const int64_t N = (int64_t)1 << logN, poly = (int64_t)rows * N;
+    const int xpl = lf_stack_planes(logN, rows, q_host);
+    const int relaxed_plain = LF_NTT_RELAXED | LF_NTT_PLAIN | (xpl ? LF_NTT_PLANES : 0);
+    if (int e = lf_set_device(device)) return e;
+    int64_t *x = ws, *S = ws + (int64_t)2 * (k < 4 ? k : 4) * poly;
+    const int64_t *zeros[8];
+    for (int i = 0; i < 8; ++i) zeros[i] = zero_row;
+    for (int i0 = 0; i0 < k;) {
+        const int left = k - i0, g = left >= 4 ? 4 : left >= 2 ? 2 : 1;
+        // 1. c0, c1 of the chunk's ciphertexts, all rows of their level, through the forward transform that reads its operands
+        //    where they lie (the form lf_cc_dot fills its operand stack with: the only column pass that writes planes): its
+        //    rescale step is handed the identity — a dropped row of zeros, the scale R (REDC(w R) = w), a threshold out of reach
+        if (int e = lf_rescale_ntt(in + 2 * i0, zeros, 2 * g, x, rows, logN, mont_one, INT64_MAX, psi_br, psi_dp, q_host, Rs, relaxed_plain,
+                                   nullptr, ql, qh, kl, kh, device, stream))
+            return e;
+        // 2. their products with the plaintexts into the one pair S
+        if (int e = lf_pc_dot_products(g, x, pt + i0, S, rows, logN, xpl, i0 == 0, ql, qh, kl, kh, (hipStream_t)stream)) return e;
+        i0 += g;
+    }
+    // 3. S -> canonical coefficients (intt_exit_reduce's words)
+    if (int e = lf_intt(S, 2, rows, logN, ipsi_br, ipsi_dp, q_host, Ninv, 2, LF_NTT_RELAXED | LF_NTT_PLAIN, nullptr, ql, qh, kl, kh, device,
+                        stream))
+        return e;
+    // 4. one rescale of the pair (the dropped limb is the first row), 5. the bias on component 0
+    const int64_t *ins[2] = {S + N, S + poly + N}, *row0[2] = {S, S + poly};
+    int64_t *outs[2] = {out0, out1};
+    if (int e = lf_rescale_batch(ins, row0, outs, 2, rows - 1, N, rescale_scales, round_at, ql + 1, qh + 1, kl + 1, kh + 1, device, stream))
+        return e;
+    if (!bias) return 0;
+    return lf_pc_bias(out0, bias, Rs + 1, rows - 1, logN, ql + 1, qh + 1, kl + 1, kh + 1, (hipStream_t)stream);
 }
 
 int lf_switch_key(const lf_ks_plan *p, const int64_t *c0, const int64_t *c1, int64_t gal_pinv, int gal_canonical,

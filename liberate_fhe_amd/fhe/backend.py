@@ -427,6 +427,23 @@ class HipBackend:
                                    dev, st), "lf_weighted_sums")
 
     @staticmethod
+    def pc_dot_ws_words(k, rows, logN):
+        return int(lib.lf_pc_dot_ws_words(k, rows, logN))
+
+    def pc_dot_native(self, ins, pts, bias, outs, k, rows, logN, psi, ipsi, Rs, Ninv, mont_one, zero_row, scales, round_at, ws, c: Consts):
+        """sum of k plaintext-ciphertext products (+ bias) under one rescale as ONE native call (lf_pc_dot).  ins: ctypes array of
+        2 k device pointers ([term][component], [rows, N] each, the dropped limb first); pts: ctypes array of k device pointers
+        (encode_plain's "mult" tensors); bias: the "add" tensor [rows - 1, N] or None; outs: the two output tensors [rows - 1, N];
+        psi .. Ninv, c: tables and constants of the level the operands are at; mont_one [rows] = R mod q, zero_row [N] zeros;
+        ws: at least pc_dot_ws_words(k, rows, logN) words."""
+        dev, st = _ds(outs[0])
+        psi_dp = twiddles.dp_pointer(psi, c.ql, c.qh, c.kl, c.kh, dev, st)
+        ipsi_dp = twiddles.dp_pointer(ipsi, c.ql, c.qh, c.kl, c.kh, dev, st)
+        check(lib.lf_pc_dot(k, ins, pts, _p(bias), _p(outs[0]), _p(outs[1]), rows, logN, _p(psi), psi_dp, _p(ipsi), ipsi_dp, c.qptr(True),
+                            _p(Rs), _p(Ninv), _p(mont_one), _p(zero_row), _p(scales), round_at, _p(ws), ws.numel(), *c.mont(), dev, st),
+              "lf_pc_dot")
+
+    @staticmethod
     def rotate_hoisted_ws_words(plan):
         return int(lib.lf_rotate_hoisted_ws_words(ctypes.byref(plan)))
 

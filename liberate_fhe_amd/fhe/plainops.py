@@ -1,0 +1,173 @@
+"""Encoded plaintexts, mixed into `ckks_engine`: a message vector encoded ONCE (encode_plain) and then multiplied into, added to,
+or summed against ciphertexts any number of times (pc_mult, pc_add, pc_dot) — per-channel weights, masks, biases, convolution
+taps.  The reference only has mc_mult / mc_add, which encode on every call; like the engine's other options beyond it, the words
+of these ops are DEFINED as compositions of ops the engine already has (written out in the docstrings), and that composition is
+what runs wherever the native call (lf_pc_dot) does not apply.  DESIGN.md §4.2.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+import torch
+
+from .evaluator import is_struct
+from .presets import errors, types
+
+
+class PlainOps:
+    # =============================================================================================
+    # the encoded object
+    # =============================================================================================
+    def encode_plain(self, m, level: int, op: str = "mult"):
+        """The plaintext mc_mult (op="mult") resp. mc_add (op="add") builds from the message `m` for a ciphertext at `level`, as
+        a data_struct of its own (one [rows, N] tensor per local device) that save / load / cpu / cuda / clone treat like any other:
+          "mult"  enter_ntt(tile_unsigned(encode(m * sqrt(deviations[level + 1]), 0), level)): NTT domain, Montgomery form;
+          "add"   mont_enter_scale(tile_unsigned(encode(m, level), level)): coefficient domain, Montgomery form."""
+        if op not in ("mult", "add"):
+            raise ValueError(f"encode_plain: op must be 'mult' or 'add', got {op!r}")
+        if not 0 <= level < self.num_levels:
+            raise errors.MaximumLevelError(level=level, level_max=self.num_levels)
+        if op == "mult":
+            if level + 1 >= self.num_levels:
+                raise errors.MaximumLevelError(level=level, level_max=self.num_levels)
+            m = np.array(m) * np.sqrt(self.deviations[level + 1])
+            pt = self.ntt.tile_unsigned(self.encode(m, 0), level)
+            self.ntt.enter_ntt(pt, level)
+            return self._new(pt, types.origins["pt_mult"], level=level, ntt_state=True, montgomery_state=True)
+        pt = self.ntt.tile_unsigned(self.encode(m, level), level)
+        self.ntt.mont_enter_scale(pt, level)
+        return self._new(pt, types.origins["pt_add"], level=level, montgomery_state=True)
+
+    # =============================================================================================
+    # checks (all before any launch)
+    # =============================================================================================
+    @staticmethod
+    def _check_plain(pt, kind):
+        want = types.origins["pt_" + kind]
+        if not is_struct(pt) or pt.origin != want:
+            raise errors.NotMatchType(origin=getattr(pt, "origin", type(pt).__name__), to=want)
+        if pt.include_special or not pt.montgomery_state or pt.ntt_state != (kind == "mult"):
+            raise errors.NotMatchDataStructState(origin=pt.origin)
+
+    @staticmethod
+    def _check_plain_operand(ct):
+        if not is_struct(ct) or ct.origin != types.origins["ct"]:
+            raise errors.NotMatchType(origin=getattr(ct, "origin", type(ct).__name__), to=types.origins["ct"])
+        if ct.ntt_state or ct.include_special:
+            raise errors.NotMatchDataStructState(origin=ct.origin)
+
+    def _check_plain_pair(self, pt, ct, kind):
+        self._check_plain(pt, kind)
+        self._check_plain_operand(ct)
+        if pt.level != ct.level:
+            raise errors.NotMatchDataStructState(origin=f"{pt.origin} at level {pt.level} beside level {ct.level}")
+
+    # =============================================================================================
+    # the ops
+    # =============================================================================================
+    def pc_mult(self, pt, ct):
+        """mc_mult(m, ct) for pt = encode_plain(m, ct.level): mc_mult's body behind its encode, the same words whenever encode
+        returns the same polynomial."""
+        self._check_plain_pair(pt, ct, "mult")
+        l = ct.level
+        if l + 1 >= self.num_levels:
+            raise errors.MaximumLevelError(level=l, level_max=self.num_levels)
+        out = self.clone(ct)
+        self.ntt.enter_ntt(out.data[0], l)
+        self.ntt.enter_ntt(out.data[1], l)
+        d0 = self.ntt.mont_mult(pt.data, out.data[0], l)
+        d1 = self.ntt.mont_mult(pt.data, out.data[1], l)
+        self.ntt.intt_exit_reduce(d0, l)
+        self.ntt.intt_exit_reduce(d1, l)
+        return self.rescale(out._replace(data=[d0, d1]))
+
+    def pc_add(self, pt, ct):
+        """mc_add(m, ct) for pt = encode_plain(m, ct.level, "add"): mc_add's body behind its encode."""
+        self._check_plain_pair(pt, ct, "add")
+        l = ct.level
+        out = self.clone(ct)
+        self.ntt.mont_enter(out.data[0], l)
+        d0 = self.ntt.mont_add(pt.data, out.data[0], l)
+        self.ntt.mont_redc(d0, l)
+        self.ntt.reduce_2q(d0, l)
+        return out._replace(data=[d0, out.data[1]])
+
+    def pc_dot(self, pairs, bias=None):
+        """sum_i pt_i * ct_i (+ bias) over the pairs (pt_i, ct_i) as ONE ciphertext at level + 1, under one rescale.  Every pt_i an
+        encode_plain(.., level) of kind "mult", every ct_i a ciphertext of that level (coefficient domain, no special limbs; the
+        same object may repeat on either side), bias an encode_plain(.., level + 1, "add") or None.  The product with a plaintext
+        is linear in the ciphertext, so the inverse transforms and the rescale run once, on the sum: one rescale rounding instead
+        of len(pairs).  The result has exactly the words of
+            S_c = mont_mult(pt_0, enter_ntt(ct_0.c));  S_c = mont_add(S_c, mont_mult(pt_i, enter_ntt(ct_i.c)))  for i >= 1, c = 0, 1
+            intt_exit_reduce(S_c);  out = rescale((S_0, S_1));  out = pc_add(bias, out)  if bias is given
+        (one pair without bias: pc_mult), which is also what runs where the native call does not apply: several devices or ranks,
+        logN outside 13..17, a checker backend, operands that are not contiguous or not 16-byte aligned.  Otherwise ONE native call
+        (lf_pc_dot)."""
+        pairs = [tuple(p) for p in pairs]
+        if not pairs:
+            raise ValueError("pc_dot: at least one (plaintext, ciphertext) pair")
+        for pair in pairs:
+            if len(pair) != 2:
+                raise ValueError("pc_dot: pairs of an encoded plaintext and a ciphertext")
+            self._check_plain(pair[0], "mult")
+            self._check_plain_operand(pair[1])
+        l = pairs[0][1].level
+        for pt, ct in pairs:
+            for x in (pt, ct):
+                if x.level != l:
+                    raise errors.NotMatchDataStructState(origin=f"{x.origin} at level {x.level} beside level {l}")
+        if bias is not None:
+            self._check_plain(bias, "add")
+            if bias.level != l + 1:
+                raise errors.NotMatchDataStructState(origin=f"{bias.origin} at level {bias.level} beside level {l + 1}")
+        if l + 1 >= self.num_levels:
+            raise errors.MaximumLevelError(level=l, level_max=self.num_levels)
+        d = self._native_level(l + 1)
+        # (16-byte loads: a contiguous view at an odd word offset takes the composition, as do rows in another order than the
+        # dropped limb first and the survivors behind it)
+        if d is not None and self._native_level(l) == d and hasattr(self.backend, "pc_dot_native") and self.ctx.logN <= 17 \
+                and list(self.ntt.p.destination_arrays[l][d][1:]) == list(self.ntt.p.destination_arrays[l + 1][d]) \
+                and all(t.is_contiguous() and t.dtype == torch.int64 and t.data_ptr() % 16 == 0
+                        for pt, ct in pairs for t in (pt.data[0], ct.data[0][0], ct.data[1][0])) \
+                and (bias is None or (bias.data[0].is_contiguous() and bias.data[0].dtype == torch.int64 and bias.data[0].data_ptr() % 16 == 0)):
+            return self._pc_dot_native(pairs, bias, l, d)
+        S = None
+        for pt, ct in pairs:
+            x = self.clone(ct)
+            term = []
+            for comp in range(2):
+                self.ntt.enter_ntt(x.data[comp], l)
+                term.append(self.ntt.mont_mult(pt.data, x.data[comp], l))
+            S = term if S is None else [self.ntt.mont_add(S[comp], term[comp], l) for comp in range(2)]
+        for comp in range(2):
+            self.ntt.intt_exit_reduce(S[comp], l)
+        out = self.rescale(self._new(S, types.origins["ct"], level=l))
+        return out if bias is None else self.pc_add(bias, out)
+
+    def _pc_dot_native(self, pairs, bias, l, d):
+        N, k = self.ctx.N, len(pairs)
+        rows = len(self.ntt.p.destination_arrays[l][d])          # the dropped limb first
+        owner = self.ntt.p.rescaler_loc[l]
+        round_at = self.ctx.q[self.ntt.p.destination_arrays[l][owner][0]] // 2
+        ins, pts = (ctypes.c_void_p * (2 * k))(), (ctypes.c_void_p * k)()
+        for t, (pt, ct) in enumerate(pairs):
+            pts[t] = pt.data[0].data_ptr()
+            for comp in range(2):
+                ins[2 * t + comp] = ct.data[comp][0].data_ptr()
+        dev = self.ntt.devices[d]
+        # the identity the forward transform's rescale step is handed (include/ckks_hip.h: lf_pc_dot): R mod q per row, a row of zeros
+        key = ("pc_dot_identity", l, d)
+        ident = self._tables.get(key)
+        if ident is None:
+            zero = self._tables.get(("zero_row", d))
+            if zero is None:
+                zero = self._tables[("zero_row", d)] = torch.zeros(N, dtype=torch.int64, device=dev)
+            ident = self._tables[key] = (self._row_scalars(1, l, True)[self._loc(l).index(d)], zero)
+        ws = self._ws("pc_dot_ws", (self.backend.pc_dot_ws_words(min(k, 4), rows, self.ctx.logN),), d)   # (per device and level: the shape)
+        out = [torch.empty((rows - 1, N), dtype=torch.int64, device=dev) for _ in range(2)]
+        self.backend.pc_dot_native(ins, pts, None if bias is None else bias.data[0], out, k, rows, self.ctx.logN,
+                                   self._tw(d, l, False), self._tw(d, l, False, True), self._vec("Rs", d, l, False),
+                                   self._vec("Ninv", d, l, False), ident[0], ident[1], self.rescale_scales[l][d], round_at, ws,
+                                   self._consts(d, l, False))
+        return self._new(([out[0]], [out[1]]), types.origins["ct"], level=l + 1)

@@ -677,6 +677,37 @@ int lf_pc_dot(int k, const int64_t *const *in, const int64_t *const *pt, const i
               const int64_t *rescale_scales, int64_t round_at, int64_t *ws, int64_t ws_words, const int64_t *ql, const int64_t *qh,
               const int64_t *kl, const int64_t *kh, int device, void *stream);
 
+/* A plaintext matrix times a vector of ciphertexts under ONE rescale per output (a layer over feature-per-ciphertext packing):
+ * for o < k_out, out_o decrypts to sum_{i < k_in} pt_{o,i} * ct_i (+ bias_o), level l -> l + 1.  Plan-free, the tables of lf_pc_dot.
+ * in: HOST array of 2 k_in device pointers, [input][component], as lf_pc_dot's; pt: HOST array of k_out k_in device pointers,
+ * row-major ([output][input]), NULL for an absent term (a zero weight); bias: NULL, or a HOST array of k_out pointers, each NULL or
+ * the plaintext mc_add builds at level l + 1; out0 / out1: HOST arrays of k_out pointers, [rows - 1][N] each, canonical.  The same
+ * polynomial may appear any number of times among `in` and among `pt`.
+ * Output o has exactly the words of lf_pc_dot over the terms (pt_{o,i}, ct_i) with a non-NULL plaintext, in the order of i, with
+ * bias_o: only the residues of that entry's S reach its result, so the order and grouping of the additions are free.
+ * Enqueued: per chunk of at most LF_PC_MATMUL_CI of the inputs some output uses (an input whose column of pt is all NULL is not
+ * transformed) their forward transforms as lf_pc_dot runs them — lf_rescale_ntt with the identity rescale, RELAXED | PLAIN,
+ * PLANES where lf_stack_planes says so, 4, 2 or 1 ciphertexts per call — into consecutive slots of the workspace: every input is
+ * transformed ONCE per call of the entry, whatever k_out; per chunk and per group of 4, 2 or 1 outputs ONE launch of
+ * pc_matmul_kernel<4 | 2 | 1> (grid N / 512 x rows; a thread reads the two transformed pairs of an input once for its group's
+ * outputs and each plaintext pair once) adding the chunk's products into the group's pairs of S = [k_out][2][rows][N] (the first
+ * chunk writes); ONE lf_intt (tail 2, relaxed, plain) of the 2 k_out polynomials of S; lf_rescale_batch per 4 outputs; one
+ * pc_bias_kernel launch per output that has a bias.
+ * ws: lf_pc_matmul_ws_words(k_in, k_out, rows, logN) = (2 min(k_in, LF_PC_MATMUL_CI) + 2 k_out) rows N words (0 for shapes the
+ * entry refuses), 16-byte aligned, lent by the caller.  LF_ERR_ARG before any device call for k_in < 1, k_out < 1 or
+ * > LF_PC_MATMUL_MAX_OUTPUTS, rows < 2 or > lf_limits(LF_LIMIT_ROWS), logN outside 13 .. 17, a NULL among the tables, in, out0,
+ * out1 or their entries, an output whose k_in entries of pt are all NULL, ws NULL, too small or misaligned.  LF_ERR_STATE where
+ * the library's note of a chunk's slots says another format than the one this call's products read (a knob flipped by another
+ * thread between the two). */
+#define LF_PC_MATMUL_CI 16            /* inputs per chunk: fp64-class rows sum CI balanced products + one word, < 64 q up to 125 */
+#define LF_PC_MATMUL_MAX_OUTPUTS 64
+int64_t lf_pc_matmul_ws_words(int k_in, int k_out, int rows, int logN);
+int lf_pc_matmul(int k_in, int k_out, const int64_t *const *in, const int64_t *const *pt, const int64_t *const *bias,
+                 int64_t *const *out0, int64_t *const *out1, int rows, int logN, const int64_t *psi_br, const double *psi_dp,
+                 const int64_t *ipsi_br, const double *ipsi_dp, const int64_t *q_host, const int64_t *Rs, const int64_t *Ninv,
+                 const int64_t *mont_one, const int64_t *zero_row, const int64_t *rescale_scales, int64_t round_at, int64_t *ws,
+                 int64_t ws_words, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, int device, void *stream);
+
 /* The halves of an op around the digit exchange of a limb-sharded engine (one process per GPU; the reference gathers every
  * digit on every GPU through the host before it extends any, ckks_engine.py:778-829).  The plan describes THIS rank's rows
  * at the level (dig_nparts = the digits it owns, nparts = all digits, state = its own digit rows):

@@ -113,6 +113,8 @@ _SIGNATURES["lf_cc_dot"] = [_PL, _I, _P, _P, _P, _L, _L, _L, _I, _P, _L, _P, _P,
 _SIGNATURES["lf_weighted_sums"] = [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _L, _P, _P, _P, _P, _I, _P]
 _SIGNATURES["lf_pc_dot_ws_words"] = [_I, _I, _I]
 _SIGNATURES["lf_pc_dot"] = [_I, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _I, _P]
+_SIGNATURES["lf_pc_matmul_ws_words"] = [_I, _I, _I, _I]
+_SIGNATURES["lf_pc_matmul"] = [_I, _I, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _I, _P]
 _SIGNATURES["lf_linear_transform_ws_words"] = [_PL]
 _SIGNATURES["lf_linear_transform"] = [_PL, _P, _P, _I, _P, _P, _L, _L, _L, _I, _P, _L, _P, _P, _L, _P, _L, _P, _P, _P]
 _SIGNATURES["lf_linear_transform_bsgs_ws_words"] = [_PL, _I]
@@ -162,5 +164,7 @@ LF_NTT_PLANES = 16
 LF_STACK_PLANES = 4
 LF_WSUM_MAX_TERMS = 16      # include/ckks_hip.h: terms per lf_weighted_sums call
 LF_WSUM_MAX_OUTPUTS = 64    # .. and outputs
+LF_PC_MATMUL_CI = 16           # include/ckks_hip.h: inputs per chunk of lf_pc_matmul
+LF_PC_MATMUL_MAX_OUTPUTS = 64  # .. and outputs per call
 LF_ERR_ARG = 10001
 LF_ERR_STATE = 10002

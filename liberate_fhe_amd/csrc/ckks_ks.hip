@@ -715,6 +715,107 @@ __global__ void __launch_bounds__(256) pc_bias_kernel(i64 *__restrict__ c0, cons
     *reinterpret_cast<longlong2 *>(c0 + off) = o;
 }
 
+// ---- pc_matmul: GO outputs' sums over the SAME n transformed ciphertexts (a plaintext matrix times a vector of ciphertexts) ----
+// x = [n][2][rows][N]: the chunk's transformed pairs as pc_dot_kernel reads them; pt[i][g]: the plaintext of input i for output g
+// of the group, or nullptr for an absent term (kernel arguments: the test is uniform over the launch);
+// S = [GO][2][rows][N]: the group's pairs (first: written without being read, zeros where an output has no term in the chunk).
+//     S0_g += sum_i pt_{i,g} c0_i,   S1_g += sum_i pt_{i,g} c1_i
+// grid and thread as pc_dot_kernel; the loop over the inputs is a run-time one: a thread reads the two transformed pairs of an
+// input ONCE for its GO outputs (ordinary loads: the next group reads them again) and every plaintext pair once per call
+// (nontemporal).  The arithmetic is pc_dot_kernel's; only the residues of S reach the result, so the grouping of the additions
+// is free.  Bounds over a chunk of n <= LF_PC_MATMUL_CI inputs:
+//   fp64-class rows  n balanced products (|.| <= q / 2 each) plus the one canonical word read back:
+//                    |.| <= LF_PC_MATMUL_CI q / 2 + q <= 9 q < 2^45 for q < 2^41 — inside dp_reduce's |x| < 64 q (which holds up to
+//                    a chunk of 125) and the exact range of fp64; stored as the plain canonical residue;
+//   integer rows     a conditional subtraction after every addition: Montgomery form below 2q throughout.
+struct PcMatTerms {
+    const i64 *pt[LF_PC_MATMUL_CI][4];   // [input of the chunk][output of the group], [rows][N] each or nullptr
+};
+static_assert(LF_PC_MATMUL_CI >= 1 && LF_PC_MATMUL_CI / 2 + 1 < 64, "pc_matmul_kernel: a chunk's sum must stay inside dp_reduce's |x| < 64 q");
+
+template <int GO>
+__global__ void __launch_bounds__(256) pc_matmul_kernel(const i64 *__restrict__ x, PcMatTerms pa, i64 *__restrict__ S, int n, int rows, i64 N,
+                                                        int xpl, int first, const i64 *__restrict__ ql, const i64 *__restrict__ qh,
+                                                        const i64 *__restrict__ kl, const i64 *__restrict__ kh) {
+    const int r = blockIdx.y;
+    const i64 j0 = (i64)blockIdx.x * 512 + threadIdx.x * 2;
+    if (j0 >= N) return;
+    const RowMod m = load_mod(ql, qh, kl, kh, r);
+    const i64 pstride = (i64)rows * N, o0 = (i64)r * N + j0;
+    i64 *s = S + o0;
+    longlong2 o[GO][2];
+    if (m.q < SMALL_PRIME_LIMIT) {
+        const RowDp d = make_dp(m);
+        double a[GO][2][2];
+#pragma unroll
+        for (int g = 0; g < GO; ++g) a[g][0][0] = a[g][0][1] = a[g][1][0] = a[g][1][1] = 0.0;
+        for (int i = 0; i < n; ++i) {
+            const i64 *xs = x + (i64)i * 2 * pstride + (i64)r * N;
+            double c0[2], c1[2];
+            ld_pair_dp(xs, j0, N, xpl, c0[0], c0[1]);
+            ld_pair_dp(xs + pstride, j0, N, xpl, c1[0], c1[1]);
+#pragma unroll
+            for (int g = 0; g < GO; ++g) {
+                const i64 *p = pa.pt[i][g];
+                if (p == nullptr) continue;   // (uniform: a kernel argument)
+                const longlong2 w = ld_nt(p + o0);
+                const double wp[2] = {dp_from_word(mm62u((u64)w.x, 1ull, m.q, m.k)), dp_from_word(mm62u((u64)w.y, 1ull, m.q, m.k))};
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    a[g][0][e] += dp_mulmod_bal(c0[e], wp[e], d);
+                    a[g][1][e] += dp_mulmod_bal(c1[e], wp[e], d);
+                }
+            }
+        }
+#pragma unroll
+        for (int g = 0; g < GO; ++g)
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                if (!first) {
+                    const longlong2 v = *reinterpret_cast<const longlong2 *>(s + (2 * g + c) * pstride);
+                    a[g][c][0] += dp_from_word(v.x), a[g][c][1] += dp_from_word(v.y);
+                }
+                o[g][c].x = dp_to_word(dp_reduce(a[g][c][0], d.q, d.qinv));
+                o[g][c].y = dp_to_word(dp_reduce(a[g][c][1], d.q, d.qinv));
+            }
+    } else {
+        i64 a[GO][2][2];
+#pragma unroll
+        for (int g = 0; g < GO; ++g) a[g][0][0] = a[g][0][1] = a[g][1][0] = a[g][1][1] = 0;
+        for (int i = 0; i < n; ++i) {
+            const i64 *xs = x + (i64)i * 2 * pstride + o0;
+            const longlong2 C0 = *reinterpret_cast<const longlong2 *>(xs), C1 = *reinterpret_cast<const longlong2 *>(xs + pstride);
+            const u64 c0[2] = {(u64)C0.x, (u64)C0.y}, c1[2] = {(u64)C1.x, (u64)C1.y};
+#pragma unroll
+            for (int g = 0; g < GO; ++g) {
+                const i64 *p = pa.pt[i][g];
+                if (p == nullptr) continue;
+                const longlong2 w = ld_nt(p + o0);
+                const u64 wm[2] = {(u64)w.x, (u64)w.y};
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    a[g][0][e] = csub(a[g][0][e] + mm62u(c0[e], wm[e], m.q, m.k), m.q2);
+                    a[g][1][e] = csub(a[g][1][e] + mm62u(c1[e], wm[e], m.q, m.k), m.q2);
+                }
+            }
+        }
+#pragma unroll
+        for (int g = 0; g < GO; ++g)
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                if (!first) {
+                    const longlong2 v = *reinterpret_cast<const longlong2 *>(s + (2 * g + c) * pstride);
+                    a[g][c][0] = csub(a[g][c][0] + v.x, m.q2), a[g][c][1] = csub(a[g][c][1] + v.y, m.q2);
+                }
+                o[g][c].x = a[g][c][0], o[g][c].y = a[g][c][1];
+            }
+    }
+#pragma unroll
+    for (int g = 0; g < GO; ++g)
+#pragma unroll
+        for (int c = 0; c < 2; ++c) *reinterpret_cast<longlong2 *>(s + (2 * g + c) * pstride) = o[g][c];
+}
+
 // ---- K3 of hoisted rotations (lf_rotate_hoisted): ONE ciphertext's extended digits, NR keys with an exponent each ----------
 // X -> X^p permutes the NTT slots: NTT(a(X^p))[k] = NTT(a)[pi_p(k)], pi_p(k) = brev(((2 brev(k) + 1) p mod 2N - 1) / 2) (the forward
 // transform stores the evaluation at psi^(2 brev(k) + 1) at index k).  So the digits of c1, extended and transformed ONCE, serve every
@@ -1514,6 +1615,31 @@ int lf_pc_bias(int64_t *c0, const int64_t *pt, const int64_t *Rs, int rows, int 
     const dim3 grid((unsigned)(N / 512), (unsigned)rows);
     hipLaunchKernelGGL(pc_bias_kernel, grid, dim3(256), 0, st, (i64 *)c0, (const i64 *)pt, (const i64 *)Rs, N, (const i64 *)ql,
                        (const i64 *)qh, (const i64 *)kl, (const i64 *)kh);
+    return (int)hipGetLastError();
+}
+
+// The launch of lf_pc_matmul that is its own (ckks_ops.hip checks the arguments).
+// lf_pc_matmul_products: go (1, 2 or 4) outputs over the n <= LF_PC_MATMUL_CI transformed pairs x = [n][2][rows][N] (xpl: fp64-class
+// rows as planes — refused where the library's note of that range says another format); pt[i * pt_stride + g]: the plaintext of
+// input i for output g, or NULL; added into S = [go][2][rows][N] (first: written).
+int lf_pc_matmul_products(int go, int n, const int64_t *x, const int64_t *const *pt, int pt_stride, int64_t *S, int rows, int logN,
+                          int xpl, int first, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st) {
+    if ((go != 1 && go != 2 && go != 4) || n < 1 || n > LF_PC_MATMUL_CI || !x || !pt || pt_stride < go || !S || rows < 1 || rows > 65535 ||
+        logN < 9)
+        return LF_ERR_ARG;
+    const i64 N = (i64)1 << logN;
+    if (int e = lf_fmt_expect(x, ((size_t)2 * n * rows << logN) * 8, xpl ? LF_FMT_PLANES : LF_FMT_RAW)) return e;
+    PcMatTerms pa{};
+    for (int i = 0; i < n; ++i)
+        for (int g = 0; g < go; ++g) pa.pt[i][g] = (const i64 *)pt[(size_t)i * pt_stride + g];
+    const dim3 grid((unsigned)(N / 512), (unsigned)rows);
+#define LF_PCMM_CASE(GG)                                                                                                          \
+    case GG:                                                                                                                      \
+        hipLaunchKernelGGL((pc_matmul_kernel<GG>), grid, dim3(256), 0, st, (const i64 *)x, pa, (i64 *)S, n, rows, N, xpl, first,   \
+                           (const i64 *)ql, (const i64 *)qh, (const i64 *)kl, (const i64 *)kh);                                   \
+        break;
+    switch (go) { LF_PCMM_CASE(1) LF_PCMM_CASE(2) LF_PCMM_CASE(4) }
+#undef LF_PCMM_CASE
     return (int)hipGetLastError();
 }
 

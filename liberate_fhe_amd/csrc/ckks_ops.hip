@@ -10,6 +10,8 @@
 #include "../../include/ckks_hip.h"
 #include "ckks_common.h"
 
+#include <vector>
+
 extern int lf_g_intt_digits;   // ckks_ks.hip (lf_tune)
 // ckks_ks.hip: false when a row is of the fp64 class and nparts exceeds LF_FP64_MAX_DIGITS (reads q_host[0 .. rows))
 bool lf_fp64_digits_ok(int nparts, int rows, const int64_t *q_host);
@@ -51,6 +53,10 @@ int lf_pc_dot_products(int g, const int64_t *x, const int64_t *const *pt, int64_
                        const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st);
 int lf_pc_bias(int64_t *c0, const int64_t *pt, const int64_t *Rs, int rows, int logN, const int64_t *ql, const int64_t *qh,
                const int64_t *kl, const int64_t *kh, hipStream_t st);
+
+// ckks_ks.hip: the launch of lf_pc_matmul that is its own
+int lf_pc_matmul_products(int go, int n, const int64_t *x, const int64_t *const *pt, int pt_stride, int64_t *S, int rows, int logN,
+                          int xpl, int first, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st);
 
 extern "C" {
 
@@ -244,6 +250,99 @@ int lf_pc_dot(int k, const int64_t *const *in, const int64_t *const *pt, const i
         return e;
     if (!bias) return 0;
     return lf_pc_bias(out0, bias, Rs + 1, rows - 1, logN, ql + 1, qh + 1, kl + 1, kh + 1, (hipStream_t)stream);
+}
+
+/* ---- pc_matmul: k_out sums of plaintext-ciphertext products over the SAME k_in ciphertexts (include/ckks_hip.h): lf_pc_dot's
+ * launches with the forward transforms shared by all outputs and every transformed word read once per group of 4 outputs. ---- */
+int64_t lf_pc_matmul_ws_words(int k_in, int k_out, int rows, int logN) {
+    if (k_in < 1 || k_out < 1 || k_out > LF_PC_MATMUL_MAX_OUTPUTS || rows < 2 || rows > MAX_LIST_ROWS || logN < 13 || logN > KS_LOGN_MAX)
+        return 0;
+    const int64_t ci = k_in < LF_PC_MATMUL_CI ? k_in : LF_PC_MATMUL_CI;
+    return ((2 * ci + 2 * (int64_t)k_out) * rows) << logN;   // the chunk's transformed pairs + the k_out pairs of S
+}
+
+int lf_pc_matmul(int k_in, int k_out, const int64_t *const *in, const int64_t *const *pt, const int64_t *const *bias,
+                 int64_t *const *out0, int64_t *const *out1, int rows, int logN, const int64_t *psi_br, const double *psi_dp,
+                 const int64_t *ipsi_br, const double *ipsi_dp, const int64_t *q_host, const int64_t *Rs, const int64_t *Ninv,
+                 const int64_t *mont_one, const int64_t *zero_row, const int64_t *rescale_scales, int64_t round_at, int64_t *ws,
+                 int64_t ws_words, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, int device, void *stream) {
+    const int64_t need = lf_pc_matmul_ws_words(k_in, k_out, rows, logN);
+    if (!need || !in || !pt || !out0 || !out1 || !psi_br || !psi_dp || !ipsi_br || !ipsi_dp || !q_host || !Rs || !Ninv || !mont_one ||
+        !zero_row || !rescale_scales || !ql || !qh || !kl || !kh)
+        return LF_ERR_ARG;
+    if (!ws || ws_words < need || ((uintptr_t)ws & 15)) return LF_ERR_ARG;
+    for (int64_t i = 0; i < (int64_t)2 * k_in; ++i)
+        if (!in[i]) return LF_ERR_ARG;
+    // the inputs some output uses, in their order (a column of NULLs is not transformed); every output needs a term
+    std::vector<int> used;
+    for (int i = 0; i < k_in; ++i)
+        for (int o = 0; o < k_out; ++o)
+            if (pt[(int64_t)o * k_in + i]) {
+                used.push_back(i);
+                break;
+            }
+    for (int o = 0; o < k_out; ++o) {
+        if (!out0[o] || !out1[o]) return LF_ERR_ARG;
+        bool any = false;
+        for (int i = 0; i < k_in && !any; ++i) any = pt[(int64_t)o * k_in + i] != nullptr;
+        if (!any) return LF_ERR_ARG;
+    }
+    const int64_t N = (int64_t)1 << logN, poly = (int64_t)rows * N;
+    const int xpl = lf_stack_planes(logN, rows, q_host);
+    const int relaxed_plain = LF_NTT_RELAXED | LF_NTT_PLAIN | (xpl ? LF_NTT_PLANES : 0);
+    if (int e = lf_set_device(device)) return e;
+    int64_t *x = ws, *S = ws + 2 * (int64_t)(k_in < LF_PC_MATMUL_CI ? k_in : LF_PC_MATMUL_CI) * poly;
+    const int64_t *zeros[8];
+    for (int i = 0; i < 8; ++i) zeros[i] = zero_row;
+    const int na = (int)used.size();
+    for (int a0 = 0; a0 < na; a0 += LF_PC_MATMUL_CI) {
+        const int n = na - a0 < LF_PC_MATMUL_CI ? na - a0 : LF_PC_MATMUL_CI;
+        // 1. the chunk's forward transforms into consecutive slots, as lf_pc_dot runs them: 4, 2 or 1 ciphertexts per call
+        for (int t0 = 0; t0 < n;) {
+            const int left = n - t0, g = left >= 4 ? 4 : left >= 2 ? 2 : 1;
+            const int64_t *ins[8];
+            for (int t = 0; t < g; ++t) ins[2 * t] = in[2 * used[a0 + t0 + t]], ins[2 * t + 1] = in[2 * used[a0 + t0 + t] + 1];
+            if (int e = lf_rescale_ntt(ins, zeros, 2 * g, x + (int64_t)t0 * 2 * poly, rows, logN, mont_one, INT64_MAX, psi_br, psi_dp, q_host,
+                                       Rs, relaxed_plain, nullptr, ql, qh, kl, kh, device, stream))
+                return e;
+            t0 += g;
+        }
+        // 2. per group of 4, 2 or 1 outputs ONE launch over the chunk: the group's pairs of S
+        for (int o0 = 0; o0 < k_out;) {
+            const int left = k_out - o0, go = left >= 4 ? 4 : left >= 2 ? 2 : 1;
+            const int64_t *tab[LF_PC_MATMUL_CI * 4];
+            for (int i = 0; i < n; ++i)
+                for (int g = 0; g < go; ++g) tab[4 * i + g] = pt[(int64_t)(o0 + g) * k_in + used[a0 + i]];
+            if (int e = lf_pc_matmul_products(go, n, x, tab, 4, S + (int64_t)o0 * 2 * poly, rows, logN, xpl, a0 == 0, ql, qh, kl, kh,
+                                              (hipStream_t)stream))
+                return e;
+            o0 += go;
+        }
+    }
+    // 3. all 2 k_out polynomials of S -> canonical coefficients in one inverse transform
+    if (int e = lf_intt(S, 2 * k_out, rows, logN, ipsi_br, ipsi_dp, q_host, Ninv, 2, LF_NTT_RELAXED | LF_NTT_PLAIN, nullptr, ql, qh, kl, kh,
+                        device, stream))
+        return e;
+    // 4. the rescales, four outputs (8 polynomials) per launch; 5. the bias on component 0 of the outputs that have one
+    for (int o0 = 0; o0 < k_out; o0 += 4) {
+        const int go = k_out - o0 < 4 ? k_out - o0 : 4;
+        const int64_t *ins[8], *row0[8];
+        int64_t *outs[8];
+        for (int g = 0; g < go; ++g)
+            for (int c = 0; c < 2; ++c) {
+                row0[2 * g + c] = S + (2 * (int64_t)(o0 + g) + c) * poly;
+                ins[2 * g + c] = row0[2 * g + c] + N;
+                outs[2 * g + c] = c ? out1[o0 + g] : out0[o0 + g];
+            }
+        if (int e = lf_rescale_batch(ins, row0, outs, 2 * go, rows - 1, N, rescale_scales, round_at, ql + 1, qh + 1, kl + 1, kh + 1, device,
+                                     stream))
+            return e;
+    }
+    if (!bias) return 0;
+    for (int o = 0; o < k_out; ++o)
+        if (bias[o])
+            if (int e = lf_pc_bias(out0[o], bias[o], Rs + 1, rows - 1, logN, ql + 1, qh + 1, kl + 1, kh + 1, (hipStream_t)stream)) return e;
+    return 0;
 }
 
 int lf_switch_key(const lf_ks_plan *p, const int64_t *c0, const int64_t *c1, int64_t gal_pinv, int gal_canonical,

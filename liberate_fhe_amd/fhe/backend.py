@@ -443,6 +443,28 @@ class HipBackend:
                             _p(Rs), _p(Ninv), _p(mont_one), _p(zero_row), _p(scales), round_at, _p(ws), ws.numel(), *c.mont(), dev, st),
               "lf_pc_dot")
 
+    # include/ckks_hip.h: LF_PC_MATMUL_CI / LF_PC_MATMUL_MAX_OUTPUTS (tests/test_pc_matmul_cpu.py holds these copies to the header)
+    pc_matmul_chunk = 16
+    pc_matmul_max_outputs = 64
+
+    @staticmethod
+    def pc_matmul_ws_words(k_in, k_out, rows, logN):
+        return int(lib.lf_pc_matmul_ws_words(k_in, k_out, rows, logN))
+
+    def pc_matmul_native(self, ins, pts, biases, outs, k_in, k_out, rows, logN, psi, ipsi, Rs, Ninv, mont_one, zero_row, scales, round_at,
+                         ws, c: Consts):
+        """k_out sums of plaintext-ciphertext products over the same k_in ciphertexts (+ biases) as ONE native call (lf_pc_matmul).
+        ins: ctypes array of 2 k_in device pointers ([input][component]); pts: ctypes array of k_out k_in device pointers, row-major,
+        None for an absent term; biases: None or a ctypes array of k_out pointers (None: no bias); outs: k_out pairs of output
+        tensors [rows - 1, N]; the rest as pc_dot_native; ws: at least pc_matmul_ws_words(k_in, k_out, rows, logN) words."""
+        dev, st = _ds(outs[0][0])
+        psi_dp = twiddles.dp_pointer(psi, c.ql, c.qh, c.kl, c.kh, dev, st)
+        ipsi_dp = twiddles.dp_pointer(ipsi, c.ql, c.qh, c.kl, c.kh, dev, st)
+        out0, out1 = _parr([o[0] for o in outs]), _parr([o[1] for o in outs])
+        check(lib.lf_pc_matmul(k_in, k_out, ins, pts, biases, out0, out1, rows, logN, _p(psi), psi_dp, _p(ipsi), ipsi_dp, c.qptr(True),
+                               _p(Rs), _p(Ninv), _p(mont_one), _p(zero_row), _p(scales), round_at, _p(ws), ws.numel(), *c.mont(), dev, st),
+              "lf_pc_matmul")
+
     @staticmethod
     def rotate_hoisted_ws_words(plan):
         return int(lib.lf_rotate_hoisted_ws_words(ctypes.byref(plan)))

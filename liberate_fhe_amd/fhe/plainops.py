@@ -1,8 +1,8 @@
 """Encoded plaintexts, mixed into `ckks_engine`: a message vector encoded ONCE (encode_plain) and then multiplied into, added to,
-or summed against ciphertexts any number of times (pc_mult, pc_add, pc_dot) — per-channel weights, masks, biases, convolution
-taps.  The reference only has mc_mult / mc_add, which encode on every call; like the engine's other options beyond it, the words
+or summed against ciphertexts any number of times (pc_mult, pc_add, pc_dot, pc_matmul) — per-channel weights, masks, biases,
+convolution taps, layers.  The reference only has mc_mult / mc_add, which encode on every call; like the engine's other options beyond it, the words
 of these ops are DEFINED as compositions of ops the engine already has (written out in the docstrings), and that composition is
-what runs wherever the native call (lf_pc_dot) does not apply.  DESIGN.md §4.2.
+what runs wherever the native call (lf_pc_dot, lf_pc_matmul) does not apply.  DESIGN.md §4.2.
 """
 from __future__ import annotations
 
@@ -145,6 +145,96 @@ class PlainOps:
         out = self.rescale(self._new(S, types.origins["ct"], level=l))
         return out if bias is None else self.pc_add(bias, out)
 
+    def pc_matmul(self, W, cts, bias=None):
+        """A plaintext matrix times a vector of ciphertexts: the list of the k_out ciphertexts sum_i W[o][i] * cts[i] (+ bias[o]) at
+        level + 1, one rescale each.  W: k_out rows of k_in entries, each an encode_plain(.., level) of kind "mult" or None (a zero
+        weight, skipped; every row needs an entry); cts: k_in ciphertexts of that level (coefficient domain, no special limbs);
+        bias: None, or k_out entries, each None or an encode_plain(.., level + 1, "add").  Objects may repeat on either side; a
+        ciphertext whose whole column is None is legal and is not touched.  Output o has exactly the words of
+            pc_dot([(W[o][i], cts[i]) for i in range(k_in) if W[o][i] is not None], bias[o])
+        and that loop is what runs where the native call does not apply (pc_dot's conditions).  Otherwise ONE native call
+        (lf_pc_matmul) per 64 outputs: every ciphertext is transformed once, whatever k_out, and every transformed word is read
+        once per group of four outputs."""
+        W = [list(row) for row in W]
+        cts = list(cts)
+        k_out, k_in = len(W), len(cts)
+        if not W or not cts:
+            raise ValueError("pc_matmul: at least one row of plaintexts and one ciphertext")
+        for row in W:
+            if len(row) != k_in:
+                raise ValueError(f"pc_matmul: a row of {len(row)} plaintexts beside {k_in} ciphertexts")
+            if all(pt is None for pt in row):
+                raise ValueError("pc_matmul: a row without a plaintext")
+            for pt in row:
+                if pt is not None:
+                    self._check_plain(pt, "mult")
+        for ct in cts:
+            self._check_plain_operand(ct)
+        l = cts[0].level
+        for x in cts + [pt for row in W for pt in row if pt is not None]:
+            if x.level != l:
+                raise errors.NotMatchDataStructState(origin=f"{x.origin} at level {x.level} beside level {l}")
+        if bias is not None:
+            bias = list(bias)
+            if len(bias) != k_out:
+                raise ValueError(f"pc_matmul: {len(bias)} biases for {k_out} rows")
+            for b in bias:
+                if b is not None:
+                    self._check_plain(b, "add")
+                    if b.level != l + 1:
+                        raise errors.NotMatchDataStructState(origin=f"{b.origin} at level {b.level} beside level {l + 1}")
+        else:
+            bias = [None] * k_out
+        if l + 1 >= self.num_levels:
+            raise errors.MaximumLevelError(level=l, level_max=self.num_levels)
+        d = self._native_level(l + 1)
+        if d is not None and self._native_level(l) == d and hasattr(self.backend, "pc_matmul_native") and self.ctx.logN <= 17 \
+                and list(self.ntt.p.destination_arrays[l][d][1:]) == list(self.ntt.p.destination_arrays[l + 1][d]):
+            tensors = [t for ct in cts for t in (ct.data[0][0], ct.data[1][0])]
+            tensors += [x.data[0] for x in {id(x): x for x in [pt for row in W for pt in row] + bias if x is not None}.values()]
+            if all(t.is_contiguous() and t.dtype == torch.int64 and t.data_ptr() % 16 == 0 and t.is_cuda for t in tensors):
+                step = self.backend.pc_matmul_max_outputs
+                return [out for o0 in range(0, k_out, step) for out in self._pc_matmul_native(W[o0:o0 + step], cts, bias[o0:o0 + step], l, d)]
+        return [self.pc_dot([(pt, ct) for pt, ct in zip(row, cts) if pt is not None], b) for row, b in zip(W, bias)]
+
+    def _pc_matmul_native(self, W, cts, bias, l, d):
+        N, k_out, k_in = self.ctx.N, len(W), len(cts)
+        rows = len(self.ntt.p.destination_arrays[l][d])          # the dropped limb first
+        owner = self.ntt.p.rescaler_loc[l]
+        round_at = self.ctx.q[self.ntt.p.destination_arrays[l][owner][0]] // 2
+        ins, pts = (ctypes.c_void_p * (2 * k_in))(), (ctypes.c_void_p * (k_out * k_in))()
+        for i, ct in enumerate(cts):
+            for comp in range(2):
+                ins[2 * i + comp] = ct.data[comp][0].data_ptr()
+        for o, row in enumerate(W):
+            for i, pt in enumerate(row):
+                pts[o * k_in + i] = None if pt is None else pt.data[0].data_ptr()
+        biases = None
+        if any(b is not None for b in bias):
+            biases = (ctypes.c_void_p * k_out)()
+            for o, b in enumerate(bias):
+                biases[o] = None if b is None else b.data[0].data_ptr()
+        dev = self.ntt.devices[d]
+        ident = self._pc_identity(l, d)
+        chunk = min(k_in, self.backend.pc_matmul_chunk)
+        ws = self._ws("pc_matmul_ws", (self.backend.pc_matmul_ws_words(chunk, k_out, rows, self.ctx.logN),), d)   # (per device and level: the shape)
+        outs = [[torch.empty((rows - 1, N), dtype=torch.int64, device=dev) for _ in range(2)] for _ in range(k_out)]
+        self.backend.pc_matmul_native(ins, pts, biases, outs, k_in, k_out, rows, self.ctx.logN, self._tw(d, l, False),
+                                      self._tw(d, l, False, True), self._vec("Rs", d, l, False), self._vec("Ninv", d, l, False), ident[0],
+                                      ident[1], self.rescale_scales[l][d], round_at, ws, self._consts(d, l, False))
+        return [self._new(([o[0]], [o[1]]), types.origins["ct"], level=l + 1) for o in outs]
+
+    def _pc_identity(self, l, d):
+        """The identity the forward transform's rescale step is handed (include/ckks_hip.h: lf_pc_dot): R mod q per row, a row of zeros."""
+        key = ("pc_dot_identity", l, d)
+        ident = self._tables.get(key)
+        if ident is None:
+            zero = self._tables.get(("zero_row", d))
+            if zero is None:
+                zero = self._tables[("zero_row", d)] = torch.zeros(self.ctx.N, dtype=torch.int64, device=self.ntt.devices[d])
+            ident = self._tables[key] = (self._row_scalars(1, l, True)[self._loc(l).index(d)], zero)
+        return ident
+
     def _pc_dot_native(self, pairs, bias, l, d):
         N, k = self.ctx.N, len(pairs)
         rows = len(self.ntt.p.destination_arrays[l][d])          # the dropped limb first
@@ -156,14 +246,7 @@ class PlainOps:
             for comp in range(2):
                 ins[2 * t + comp] = ct.data[comp][0].data_ptr()
         dev = self.ntt.devices[d]
-        # the identity the forward transform's rescale step is handed (include/ckks_hip.h: lf_pc_dot): R mod q per row, a row of zeros
-        key = ("pc_dot_identity", l, d)
-        ident = self._tables.get(key)
-        if ident is None:
-            zero = self._tables.get(("zero_row", d))
-            if zero is None:
-                zero = self._tables[("zero_row", d)] = torch.zeros(N, dtype=torch.int64, device=dev)
-            ident = self._tables[key] = (self._row_scalars(1, l, True)[self._loc(l).index(d)], zero)
+        ident = self._pc_identity(l, d)
         ws = self._ws("pc_dot_ws", (self.backend.pc_dot_ws_words(min(k, 4), rows, self.ctx.logN),), d)   # (per device and level: the shape)
         out = [torch.empty((rows - 1, N), dtype=torch.int64, device=dev) for _ in range(2)]
         self.backend.pc_dot_native(ins, pts, None if bias is None else bias.data[0], out, k, rows, self.ctx.logN,

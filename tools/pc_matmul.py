@@ -1,0 +1,111 @@
+"""pc_matmul against the loop of pc_dot calls that defines it, on one GPU:
+    python tools/pc_matmul.py [--presets silver,gold] [--shapes 8x1,8x8,16x16,4x32] [--min-seconds 0.5] [--rounds 5] [--step-timeout 600]
+For every (preset, k_in x k_out) at level 0, a dense layer over three plaintexts and three ciphertexts:
+    matmul   pc_matmul(W, cts)                               one native call: every ciphertext transformed once
+    loop     [pc_dot(row of W against cts) for each row]     k_out native calls: every ciphertext transformed k_out times
+The two forms are timed alternately in ONE process per preset (a child of this one, under its own time limit; a preset that
+fails or runs out of time ends the run: nothing more is started on the GPU) with device events after a warm-up of each, every
+timing over at least --min-seconds of work, --rounds rounds; the median is kept and every form's own run-to-run spread
+((max - min) / median over its rounds) is reported beside it.  Prints one JSON line: microseconds per layer for each form, the
+spreads, and the ratio loop / matmul.
+    python tools/pc_matmul.py --trace gold:8x8 [--calls 10] [--form matmul|loop] [--out DIR]
+starts a FRESH child process that runs only that form at that point, under rocprofv3's kernel trace (--kernel-trace --stats,
+the program behind `--`), under the same time limit.
+Synthetic ciphertexts (utils/synth.py) and random messages: the kernels do not look at the values."""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+import warnings
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+warnings.filterwarnings("ignore")
+
+
+def child(args):
+    """One preset in this process: every shape, the forms alternated; or (--form given by --trace) one form alone."""
+    import numpy as np
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit("pc_matmul: no GPU")
+    import __graft_entry__ as g
+    g.build()
+    from liberate_fhe_amd.fhe import ckks_engine, presets
+    from liberate_fhe_amd.utils import synth
+    from tools.hoisted_rotations import timed
+    name = args.child
+    params = {k: v for k, v in presets.params[name].items() if k != "devices"}
+    eng = ckks_engine(devices=["cuda:0"], **params)
+    assert eng._native_level(0) is not None and eng._native_level(1) is not None
+    rng = np.random.default_rng(3)
+    pts = [eng.encode_plain(rng.uniform(-1, 1, eng.num_slots), 0) for _ in range(3)]
+    pool = [synth.ciphertext(eng, 50 + i, 0) for i in range(3)]
+    points = []
+    for shape in args.shapes.split(","):
+        k_in, k_out = (int(v) for v in shape.split("x"))
+        cts = [pool[i % 3] for i in range(k_in)]
+        W = [[pts[(o + 2 * i) % 3] for i in range(k_in)] for o in range(k_out)]
+        forms = {"matmul": lambda: eng.pc_matmul(W, cts),
+                 "loop": lambda: [eng.pc_dot(list(zip(row, cts))) for row in W]}
+        if args.traced:
+            for _ in range(args.calls):
+                forms[args.form]()
+            torch.cuda.synchronize()
+            continue
+        for fn in forms.values():
+            fn()
+        times = {f: [] for f in forms}
+        for _ in range(args.rounds):
+            for f, fn in forms.items():
+                times[f].append(timed(fn, args.min_seconds))
+        med = {f: statistics.median(t) for f, t in times.items()}
+        spread = {f: (max(t) - min(t)) / med[f] for f, t in times.items()}
+        point = {"preset": name, "k_in": k_in, "k_out": k_out, **{f: round(med[f], 1) for f in forms},
+                 **{f"spread_{f}": round(spread[f], 4) for f in forms}, "loop_over_matmul": round(med["loop"] / med["matmul"], 3)}
+        points.append(point)
+        print(json.dumps(point), file=sys.stderr, flush=True)
+    print(json.dumps(points))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--presets", default="silver,gold")
+    ap.add_argument("--shapes", default="8x1,8x8,16x16,4x32", help="k_in x k_out, comma-separated")
+    ap.add_argument("--min-seconds", type=float, default=0.5)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--step-timeout", type=int, default=600, help="seconds a child process (one preset, or the trace) may take")
+    ap.add_argument("--trace", default=None, help="preset:k_inxk_out — one form alone, --calls times, in a fresh child under rocprofv3")
+    ap.add_argument("--form", default="matmul", choices=("matmul", "loop"))
+    ap.add_argument("--calls", type=int, default=10)
+    ap.add_argument("--out", default=os.path.join(ROOT, "out", "pc_matmul_trace"))
+    ap.add_argument("--child", default=None, help=argparse.SUPPRESS)       # the preset this process measures
+    ap.add_argument("--traced", action="store_true", help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    if args.child:
+        return child(args)
+    me = [sys.executable, os.path.abspath(__file__), "--min-seconds", str(args.min_seconds), "--rounds", str(args.rounds)]
+    if args.trace:
+        name, shape = args.trace.split(":")
+        os.makedirs(args.out, exist_ok=True)
+        cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", args.out, "--"] + me + ["--child", name, "--shapes", shape, "--traced", "--form",
+                                                                                    args.form, "--calls", str(args.calls)]
+        r = subprocess.run(cmd, cwd=ROOT, timeout=args.step_timeout)
+        sys.exit(r.returncode)
+    result = {"unit": "us per layer of k_in x k_out plaintext-ciphertext products, level 0", "points": []}
+    for name in args.presets.split(","):
+        try:
+            r = subprocess.run(me + ["--child", name, "--shapes", args.shapes], cwd=ROOT, stdout=subprocess.PIPE, text=True,
+                               timeout=args.step_timeout)
+        except subprocess.TimeoutExpired:
+            sys.exit(f"pc_matmul: preset {name} ran out of its {args.step_timeout} s; nothing more is started")
+        if r.returncode != 0:
+            sys.exit(f"pc_matmul: preset {name} ended with status {r.returncode}; nothing more is started")
+        result["points"] += json.loads(r.stdout.strip().splitlines()[-1])
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()

@@ -600,6 +600,51 @@ int lf_linear_transform_bsgs(const lf_ks_plan *plan, const int64_t *c0, const in
                              int64_t pt_stride, const int64_t *gcount, const int64_t *bidx, const int64_t *rescale_scales,
                              int64_t round_at, int64_t *ws, int64_t ws_words, int64_t *out0, int64_t *out1, void *stream);
 
+/* A matrix of linear transforms times a vector of ciphertexts (a matrix larger than one ciphertext's slots, or a layer over
+ * several packed inputs): for o < k_out, out_o decrypts to
+ *     sum_{i < k_in} sum_{step in steps(o, i)} diag_{o,i,step} * rot(m_i, step),
+ * level l -> l + 1.  The rotations of input i do not depend on the output: they are formed once per input and shared by every
+ * output; the sums over the inputs stay in Q P and come down once per output.
+ * in: HOST array of 2 k_in device pointers, [input][component] (c0, c1 of ciphertext i at the plan's level, [ell][N]); the two
+ * pointers of an input NO block uses are not read (that input costs nothing).  Column i has ncol[i] in 0 .. LF_BSGS_MAX_BABY_KEYS
+ * keyed steps (HOST array of k_in entries): SLOT 0 of a column is the ciphertext itself (step 0, no key), slot 1 + j its j-th
+ * keyed step.  p_host / ksk: HOST arrays of sum_i ncol[i] odd exponents < 2N resp. key pointers, column after column, one key
+ * layout for all (part_stride .. key_format as lf_rotate_hoisted; the same key may appear in any number of columns).
+ * pt / pt_stride / bcount: HOST arrays of k_out k_in entries, row-major ([output][input]): the first diagonal of block (o, i) or
+ * NULL for a zero block (bcount 0), the words between its diagonals ([ell + K][N] words each, NTT domain, Montgomery form, as
+ * ckks_engine.encode_diagonals lays them out) and their number >= 1; bidx: HOST array holding, block after block in the same
+ * order, the column slot of every diagonal, strictly ascending inside a block.  The same pack may serve any number of blocks.
+ * out0 / out1: HOST arrays of k_out pointers, [ell - 1][N] each, canonical.
+ * Output o has exactly the words of: per input i that some block uses c0, c1 made canonical, E_i and c^_i as lf_linear_transform
+ * forms them; per keyed step of the column t^{i,step}_c = sum over the digits of E_i gathered by pi_step times the key part,
+ * t_0 += c^_{i,0} gathered on the ordinary rows (slot 0: t_c = c^_{i,c}, zero on the special rows);
+ * S^o_c = sum_i sum_step mont_mult(pt_{o,i,step}, t^{i,step}_c); intt_exit_reduce, mod-down (no addend), ckks_engine.rescale.
+ * Only residues of t and S reach the result, so the grouping of the additions is free and the kernels use the relaxed arithmetic
+ * of the other fused ops.  k_in = 1: output o has the words of lf_linear_transform over block (o, 0).  For k_in > 1 the words are
+ * the op's own — not those of adding separate transforms, which round once per block.
+ * Enqueued, input-major: per used input the canonical copies, enter_ntt and the product with plan->PR into slot 0 (as
+ * lf_linear_transform_bsgs), lf_ks_digits_galois and lf_ks_fwd once and per group of 4, 2 or 1 of the column's keys one launch of
+ * ks_inner_baby_kernel (ncol[i] > 0); per group of 4, 2 or 1 outputs with a block in the column ONE launch of
+ * lt_block_products_kernel<4 | 2 | 1> (lt_diag_products_kernel's streaming loop: every pair of the input read once per launch,
+ * each output with its own pack, stride and slot mask; the first contributing input of an output writes S^o, later ones add).
+ * After the last input, per group of up to 4 outputs: one lf_intt of its 2 g polynomials, one lf_ks_moddown_ws, one
+ * lf_rescale_batch.  ws: lf_lt_matmul_ws_words(plan, nb_max, k_out) words, nb_max the largest ncol[i] of a used input, 16-byte
+ * aligned, lent by the caller: (nb_max + 1 + k_out) pairs [2][ell + K][N] + 2 g [ell][N] + lf_ks_moddown_ws_words(2 g, ..),
+ * g = min(k_out, 4) — it does not grow with k_in; 0 for what the entry refuses.  An engine with more than
+ * LF_LT_MATMUL_MAX_OUTPUTS outputs splits them over calls (each call repeats the inputs' rotations).
+ * LF_ERR_ARG before any launch for everything lf_linear_transform refuses, k_in < 1 or > LF_LT_MATMUL_MAX_INPUTS, k_out < 1 or
+ * > LF_LT_MATMUL_MAX_OUTPUTS, an ncol[i] out of range, a NULL among the pointers that are read (in and keys of used inputs only),
+ * an output with no block, a NULL block with bcount != 0, a block with bcount < 1, a stride below (ell + K) N, a slot outside its
+ * column's 0 .. ncol[i] or slots not ascending, a planes key not 16-byte aligned, ws NULL, misaligned or too small. */
+#define LF_LT_MATMUL_MAX_INPUTS 64
+#define LF_LT_MATMUL_MAX_OUTPUTS 64
+int64_t lf_lt_matmul_ws_words(const lf_ks_plan *plan, int nb_max, int k_out);
+int lf_lt_matmul(const lf_ks_plan *plan, int k_in, int k_out, const int64_t *const *in, const int64_t *ncol, const int64_t *p_host,
+                 const int64_t *const *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format,
+                 const int64_t *const *pt, const int64_t *pt_stride, const int64_t *bcount, const int64_t *bidx,
+                 const int64_t *rescale_scales, int64_t round_at, int64_t *ws, int64_t ws_words, int64_t *const *out0,
+                 int64_t *const *out1, void *stream);
+
 /* Sum of ciphertext products under ONE relinearisation ("lazy relinearisation"): out decrypts to sum_i a_i * b_i, level l -> l + 1.
  * np >= 1 pairs; in / row0: HOST arrays of 4 np device pointers, four per pair in the order of lf_cc_mult_evk (first surviving
  * row resp. dropped row of a_i.c0, a_i.c1, b_i.c0, b_i.c1; the same polynomial may appear any number of times); the plan

@@ -1292,6 +1292,71 @@ __global__ void __launch_bounds__(256) lt_diag_products_kernel(DiagArgs da, int 
     }
 }
 
+// ---- a matrix of linear transforms (lf_lt_matmul): S^o_c (+)= sum over the diagonals of block (o, i) of pt * t^{i,step}_c -----------
+// lt_diag_products_kernel's streaming loop over the baby pairs of ONE input for NO outputs that have a block in its column: integer
+// arithmetic on every row, each pair read once per launch whatever NO, a slot no output of the launch uses not read.  Every output
+// brings its own pack (pointer and stride), its own slot mask, and a flag: its pair is written (the first input that contributes
+// to it) or read - added - written (words below 2q both ways: the sums stay lazy Montgomery words whose residues alone count).
+struct BlockArgs {
+    const i64 *u;                  // the input's pairs [slots][2][rows][N] (slot 0: P NTT(c0), P NTT(c1), zero on the special rows)
+    const i64 *pt[4];              // output i: the first diagonal of its block, ascending slots
+    unsigned long long slots[4];   // bit t: the block has a diagonal for slot t
+    i64 *out[4];                   // the output's pair S^o [2][rows][N]
+    i64 pt_stride[4];              // words between the diagonals of the block's pack
+    int fresh[4];                  // non-zero: S^o is written; zero: read, added to, written
+    int nslots;
+};
+
+template <int NO>
+__global__ void __launch_bounds__(256) lt_block_products_kernel(BlockArgs ba, int rows, int logN, const i64 *__restrict__ ql,
+                                                                const i64 *__restrict__ qh, const i64 *__restrict__ kl,
+                                                                const i64 *__restrict__ kh) {
+    const int r = blockIdx.y;
+    const i64 N = (i64)1 << logN;
+    const i64 j0 = (i64)blockIdx.x * 512 + threadIdx.x * 2;
+    if (j0 >= N) return;
+    const RowMod m = load_mod(ql, qh, kl, kh, r);
+    const i64 o0 = (i64)r * N + j0, pair = 2 * (i64)rows * N;
+    i64 S[NO][2][2];
+    const i64 *pt[NO];
+    unsigned long long any = 0;
+#pragma unroll
+    for (int i = 0; i < NO; ++i) {
+        S[i][0][0] = S[i][0][1] = S[i][1][0] = S[i][1][1] = 0;
+        pt[i] = ba.pt[i] + o0;
+        any |= ba.slots[i];
+    }
+    for (int t = 0; t < ba.nslots; ++t) {
+        if (!((any >> t) & 1ull)) continue;   // (wave-uniform: kernel arguments)
+        const i64 *ur = ba.u + (i64)t * pair + o0;
+        const longlong2 u0 = *reinterpret_cast<const longlong2 *>(ur);
+        const longlong2 u1 = *reinterpret_cast<const longlong2 *>(ur + (i64)rows * N);
+#pragma unroll
+        for (int i = 0; i < NO; ++i) {
+            if (!((ba.slots[i] >> t) & 1ull)) continue;
+            const longlong2 w = ld_nt(pt[i]);
+            pt[i] += ba.pt_stride[i];
+            S[i][0][0] = csub(S[i][0][0] + mm62u((u64)u0.x, (u64)w.x, m.q, m.k), m.q2);
+            S[i][0][1] = csub(S[i][0][1] + mm62u((u64)u0.y, (u64)w.y, m.q, m.k), m.q2);
+            S[i][1][0] = csub(S[i][1][0] + mm62u((u64)u1.x, (u64)w.x, m.q, m.k), m.q2);
+            S[i][1][1] = csub(S[i][1][1] + mm62u((u64)u1.y, (u64)w.y, m.q, m.k), m.q2);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < NO; ++i) {
+        i64 *s0 = ba.out[i] + o0, *s1 = s0 + (i64)rows * N;
+        longlong2 a, b;
+        a.x = S[i][0][0], a.y = S[i][0][1], b.x = S[i][1][0], b.y = S[i][1][1];
+        if (!ba.fresh[i]) {   // (wave-uniform)
+            const longlong2 x = *reinterpret_cast<const longlong2 *>(s0), y = *reinterpret_cast<const longlong2 *>(s1);
+            a.x = csub(a.x + x.x, m.q2), a.y = csub(a.y + x.y, m.q2);
+            b.x = csub(b.x + y.x, m.q2), b.y = csub(b.y + y.y, m.q2);
+        }
+        *reinterpret_cast<longlong2 *>(s0) = a;
+        *reinterpret_cast<longlong2 *>(s1) = b;
+    }
+}
+
 struct GiantArgs {
     HoistKeys hk;        // (one key)
     const i64 *s0;       // S^g_0: [rows][N], raw words below 2q
@@ -1843,6 +1908,33 @@ int lf_lt_diag_products(int ng, const int64_t *u, int nslots, const int64_t *con
         case 4: LF_DIAG_LAUNCH(4); break;
     }
 #undef LF_DIAG_LAUNCH
+    return (int)hipGetLastError();
+}
+
+// ---- the launch of lf_lt_matmul that is its own (ckks_ops.hip checks the arguments and owns the order) ----
+// block products of no (1, 2 or 4) outputs over one input's pairs u: out[i] (+)= sum over the set bits t of slots[i] of
+// pt[i][k-th diagonal] * u[t]; fresh[i] != 0 writes out[i], 0 adds to it
+int lf_lt_block_products(int no, const int64_t *u, int nslots, const int64_t *const *pt, const unsigned long long *slots,
+                         const int64_t *pt_stride, int64_t *const *out, const int *fresh, int rows, int logN, const int64_t *ql,
+                         const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st) {
+    if ((no != 1 && no != 2 && no != 4) || !u || nslots < 1 || nslots > 64 || rows < 1 || rows > 65535) return LF_ERR_ARG;
+    BlockArgs ba{};
+    ba.u = (const i64 *)u, ba.nslots = nslots;
+    for (int i = 0; i < no; ++i) {
+        if (!pt[i] || !out[i] || !slots[i] || (nslots < 64 && (slots[i] >> nslots))) return LF_ERR_ARG;
+        ba.pt[i] = (const i64 *)pt[i], ba.slots[i] = slots[i], ba.out[i] = (i64 *)out[i], ba.pt_stride[i] = (i64)pt_stride[i];
+        ba.fresh[i] = fresh[i];
+    }
+    const dim3 grid((unsigned)((((i64)1 << logN) + 511) / 512), (unsigned)rows);
+#define LF_BLOCK_LAUNCH(NO)                                                                                                 \
+    hipLaunchKernelGGL((lt_block_products_kernel<NO>), grid, dim3(256), 0, st, ba, rows, logN, (const i64 *)ql, (const i64 *)qh, \
+                       (const i64 *)kl, (const i64 *)kh)
+    switch (no) {
+        case 1: LF_BLOCK_LAUNCH(1); break;
+        case 2: LF_BLOCK_LAUNCH(2); break;
+        case 4: LF_BLOCK_LAUNCH(4); break;
+    }
+#undef LF_BLOCK_LAUNCH
     return (int)hipGetLastError();
 }
 

@@ -39,6 +39,11 @@ int lf_ks_giant_sums(int64_t p, int nparts, int rows, int logN, const int64_t *k
                      int64_t row_off, int key_format, const int64_t *ext, const int64_t *s0, int64_t *acc, const int64_t *q_host,
                      const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st);
 
+// ckks_ks.hip: the launch of lf_lt_matmul that is its own
+int lf_lt_block_products(int no, const int64_t *u, int nslots, const int64_t *const *pt, const unsigned long long *slots,
+                         const int64_t *pt_stride, int64_t *const *out, const int *fresh, int rows, int logN, const int64_t *ql,
+                         const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st);
+
 // ckks_ks.hip: the launches of lf_cc_dot that are its own
 int lf_dot_tensor(int g, const int64_t *x, int64_t *T, int64_t *t2, int ell, int logN, int xpl, int first, const int64_t *ql,
                   const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st);
@@ -607,6 +612,155 @@ int lf_linear_transform_bsgs(const lf_ks_plan *p, const int64_t *c0, const int64
     const int64_t *ins[2] = {md + N, md + poly + N}, *row0[2] = {md, md + poly};
     int64_t *outs[2] = {out0, out1};
     return lf_rescale_batch(ins, row0, outs, 2, ell - 1, N, rescale_scales, round_at, p->ql + 1, p->qh + 1, p->kl + 1, p->kh + 1, dev, stream);
+}
+
+/* ---- a matrix of linear transforms times a vector of ciphertexts: y_o = sum_i sum_step diag_{o,i,step} * rot(x_i, step)
+ * (include/ckks_hip.h).  Input-major: the rotated sums t^{i,step} of one input are formed once, for every output, in the slots
+ * of the BSGS path's baby pairs; the outputs' sums S^o stay in Q P over all inputs and come down once each. ---- */
+#define LF_LT_MATMUL_GROUP 4       // outputs per launch of the block products and per inverse NTT / mod-down / rescale
+
+int64_t lf_lt_matmul_ws_words(const lf_ks_plan *p, int nb_max, int k_out) {
+    if (!plan_ok(p) || nb_max < 0 || nb_max > LF_BSGS_MAX_BABY_KEYS || k_out < 1 || k_out > LF_LT_MATMUL_MAX_OUTPUTS) return 0;
+    const int64_t N = (int64_t)1 << p->logN, pair = 2 * (int64_t)(p->ell + p->K) * N, poly = (int64_t)p->ell * N;
+    const int g = k_out < LF_LT_MATMUL_GROUP ? k_out : LF_LT_MATMUL_GROUP;
+    // one input's pairs (slot 0: the ciphertext), the k_out pairs of S, the mod-down's results of one group of outputs and its
+    // workspace (the plan's own is primed for pairs)
+    return pair * (nb_max + 1 + k_out) + 2 * g * poly + lf_ks_moddown_ws_words(2 * g, p->ell, p->K, N);
+}
+
+int lf_lt_matmul(const lf_ks_plan *p, int k_in, int k_out, const int64_t *const *in, const int64_t *ncol, const int64_t *p_host,
+                 const int64_t *const *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format,
+                 const int64_t *const *pt, const int64_t *pt_stride, const int64_t *bcount, const int64_t *bidx,
+                 const int64_t *rescale_scales, int64_t round_at, int64_t *ws, int64_t ws_words, int64_t *const *out0,
+                 int64_t *const *out1, void *stream) {
+    if (!plan_ok(p) || !p->PR || p->ell < 2 || k_in < 1 || k_in > LF_LT_MATMUL_MAX_INPUTS || k_out < 1 || k_out > LF_LT_MATMUL_MAX_OUTPUTS ||
+        !in || !ncol || !pt || !pt_stride || !bcount || !bidx || !rescale_scales || !out0 || !out1 ||
+        (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES))
+        return LF_ERR_ARG;
+    const int ell = p->ell, rows = p->ell + p->K, logN = p->logN, dev = p->device;
+    const int64_t N = (int64_t)1 << logN, twoN = 2 * N, poly = (int64_t)ell * N, pair = 2 * (int64_t)rows * N;
+    // the columns: keyed steps per input, the inputs some output uses, their keys
+    std::vector<int64_t> koff(k_in + 1, 0);
+    std::vector<char> used(k_in, 0);
+    int nb_max = 0;
+    for (int i = 0; i < k_in; ++i) {
+        if (ncol[i] < 0 || ncol[i] > LF_BSGS_MAX_BABY_KEYS) return LF_ERR_ARG;
+        koff[i + 1] = koff[i] + ncol[i];
+        for (int o = 0; o < k_out && !used[i]; ++o) used[i] = pt[(int64_t)o * k_in + i] != nullptr;
+        if (!used[i]) continue;
+        if (!in[2 * i] || !in[2 * i + 1]) return LF_ERR_ARG;
+        if (ncol[i] && (!p_host || !ksk)) return LF_ERR_ARG;
+        for (int64_t k = koff[i]; k < koff[i + 1]; ++k) {
+            if (!ksk[k] || p_host[k] <= 0 || p_host[k] >= twoN || !(p_host[k] & 1)) return LF_ERR_ARG;
+            if (key_format == LF_KEY_PLANES && ((((uintptr_t)ksk[k] | (uintptr_t)(part_stride * 8) | (uintptr_t)(comp_stride * 8)) & 15)))
+                return LF_ERR_ARG;
+        }
+        if (ncol[i] > nb_max) nb_max = (int)ncol[i];
+    }
+    // the blocks: per output at least one; per block its slots inside the column's set, ascending
+    std::vector<unsigned long long> masks((size_t)k_out * k_in, 0);
+    int64_t first = 0;
+    for (int o = 0; o < k_out; ++o) {
+        if (!out0[o] || !out1[o]) return LF_ERR_ARG;
+        bool any = false;
+        for (int i = 0; i < k_in; ++i) {
+            const int64_t b = (int64_t)o * k_in + i;
+            if (!pt[b]) {
+                if (bcount[b] != 0) return LF_ERR_ARG;
+                continue;
+            }
+            any = true;
+            if (bcount[b] < 1 || bcount[b] > ncol[i] + 1 || pt_stride[b] < (int64_t)rows * N) return LF_ERR_ARG;
+            for (int64_t k = 0; k < bcount[b]; ++k) {
+                const int64_t slot = bidx[first + k];
+                if (slot < 0 || slot > ncol[i] || (k && slot <= bidx[first + k - 1])) return LF_ERR_ARG;
+                masks[b] |= 1ull << slot;
+            }
+            first += bcount[b];
+        }
+        if (!any) return LF_ERR_ARG;
+    }
+    const int64_t need = lf_lt_matmul_ws_words(p, nb_max, k_out);
+    if (!need || !ws || ws_words < need || ((uintptr_t)ws & 15)) return LF_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const int gmax = k_out < LF_LT_MATMUL_GROUP ? k_out : LF_LT_MATMUL_GROUP;
+    int64_t *u = ws, *S = u + (nb_max + 1) * pair, *md = S + k_out * pair, *mdws = md + 2 * gmax * poly;
+    const int64_t mdws_words = lf_ks_moddown_ws_words(2 * gmax, ell, p->K, N);
+    if (int e = lf_set_device(dev)) return e;
+    // slot 0 holds nothing on the special rows, for every input
+    for (int c = 0; c < 2; ++c)
+        if (hipError_t e = hipMemsetAsync(u + c * (int64_t)rows * N + poly, 0, (size_t)p->K * N * 8, st)) return (int)e;
+    std::vector<char> written(k_out, 0);
+    for (int i = 0; i < k_in; ++i) {
+        if (!used[i]) continue;
+        const int nb = (int)ncol[i];
+        // 1. slot 0 = P NTT(c0), P NTT(c1) on the ordinary rows (canonical copy, enter_ntt, times P R)
+        {
+            const int64_t *srcs[2] = {in[2 * i], in[2 * i + 1]};
+            int64_t *dsts[2] = {u, u + (int64_t)rows * N};
+            if (int e = lf_galois_batch(srcs, dsts, 2, ell, logN, 1, p->_2q, dev, stream)) return e;
+            for (int c = 0; c < 2; ++c) {
+                if (int e = lf_ntt(dsts[c], 1, ell, logN, p->psi, p->psi_dp, p->q_host, p->Rs, 0, p->_2q, p->ql, p->qh, p->kl, p->kh, dev, stream))
+                    return e;
+                if (int e = lf_mont_enter(dsts[c], p->PR, ell, N, p->ql, p->qh, p->kl, p->kh, dev, stream)) return e;
+            }
+        }
+        // 2. the digits of c1 extended and transformed once, per group of the column's keys one launch into the slots 1 .. nb
+        if (nb) {
+            if (int e = lf_ks_digits_galois(in[2 * i + 1], p->state, p->dig_nparts, p->dig_desc, p->dig_tab, N, 1, p->_2q, p->ql, p->qh,
+                                            p->kl, p->kh, dev, stream))
+                return e;
+            if (int e = lf_ks_fwd(p->state, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, p->ext, p->psi, p->psi_dp, p->q_host, p->ql, p->qh,
+                                  p->kl, p->kh, dev, stream))
+                return e;
+            if (int e = lf_ks_baby_sums(nb, p_host + koff[i], p->nparts, rows, ell, logN, ksk + koff[i], part_stride, comp_stride, row_off,
+                                        key_format, u, p->ext, u + pair, p->q_host, p->ql, p->qh, p->kl, p->kh, st))
+                return e;
+        }
+        // 3. the outputs that have a block in this column, 4, 2 or 1 per launch over the input's pairs
+        std::vector<int> os;
+        for (int o = 0; o < k_out; ++o)
+            if (pt[(int64_t)o * k_in + i]) os.push_back(o);
+        for (size_t a0 = 0; a0 < os.size();) {
+            const size_t left = os.size() - a0;
+            const int g = left >= 4 ? 4 : left >= 2 ? 2 : 1;
+            const int64_t *pts[4];
+            int64_t *outs[4], strides[4];
+            unsigned long long slots[4];
+            int fresh[4];
+            for (int t = 0; t < g; ++t) {
+                const int o = os[a0 + t];
+                const int64_t b = (int64_t)o * k_in + i;
+                pts[t] = pt[b], strides[t] = pt_stride[b], slots[t] = masks[b], outs[t] = S + o * pair, fresh[t] = !written[o];
+                written[o] = 1;
+            }
+            if (int e = lf_lt_block_products(g, u, nb + 1, pts, slots, strides, outs, fresh, rows, logN, p->ql, p->qh, p->kl, p->kh, st))
+                return e;
+            a0 += g;
+        }
+    }
+    // 4. per group of outputs one exact inverse NTT (intt_exit_reduce) of its 2 g polynomials, one mod-down, one rescale
+    for (int o0 = 0; o0 < k_out; o0 += LF_LT_MATMUL_GROUP) {
+        const int g = k_out - o0 < LF_LT_MATMUL_GROUP ? k_out - o0 : LF_LT_MATMUL_GROUP;
+        int64_t *Sg = S + o0 * pair;
+        if (int e = lf_intt(Sg, 2 * g, rows, logN, p->ipsi, p->ipsi_dp, p->q_host, p->Ninv, 2, 0, p->_2q, p->ql, p->qh, p->kl, p->kh, dev, stream))
+            return e;
+        const int64_t *ss[2 * LF_LT_MATMUL_GROUP], *ins[2 * LF_LT_MATMUL_GROUP], *row0[2 * LF_LT_MATMUL_GROUP];
+        int64_t *mds[2 * LF_LT_MATMUL_GROUP], *outs[2 * LF_LT_MATMUL_GROUP];
+        for (int t = 0; t < 2 * g; ++t) {
+            ss[t] = Sg + t * (int64_t)rows * N;
+            mds[t] = md + t * poly;
+            row0[t] = mds[t], ins[t] = mds[t] + N;
+            outs[t] = (t & 1) ? out1[o0 + t / 2] : out0[o0 + t / 2];
+        }
+        if (int e = lf_ks_moddown_ws(ss, mds, nullptr, 2 * g, ell, p->K, N, mdws, mdws_words, p->PiR, p->PiP, p->Rs, 0, nullptr, p->ql, p->qh,
+                                     p->kl, p->kh, dev, stream))
+            return e;
+        if (int e = lf_rescale_batch(ins, row0, outs, 2 * g, ell - 1, N, rescale_scales, round_at, p->ql + 1, p->qh + 1, p->kl + 1, p->kh + 1,
+                                     dev, stream))
+            return e;
+    }
+    return 0;
 }
 
 /* ---- batches under one key: nct = 1, 2 or 4 ciphertexts per launch set (plan->max_nct >= nct; scratch of ciphertext t at

@@ -540,6 +540,52 @@ class HipBackend:
                                            _p(scales), round_at, _p(ws), ws.numel(), out.data_ptr(),
                                            out.data_ptr() + out.stride(0) * 8, st), "lf_linear_transform_bsgs")
 
+    # include/ckks_hip.h: LF_LT_MATMUL_MAX_INPUTS / LF_LT_MATMUL_MAX_OUTPUTS (tests/test_lt_matmul_cpu.py holds these copies to the
+    # header); the keyed steps of a column are bounded by bsgs_max_baby_keys
+    lt_matmul_max_inputs = 64
+    lt_matmul_max_outputs = 64
+
+    @staticmethod
+    def lt_matmul_ws_words(plan, nb_max, k_out):
+        return int(lib.lf_lt_matmul_ws_words(ctypes.byref(plan), nb_max, k_out))
+
+    def lt_matmul_native(self, plan, ins, col_exps, col_keys, first_part, row_off, blocks, scales, round_at, outs, ws):
+        """A k_out x k_in matrix of diagonal sets times k_in ciphertexts as ONE native call (lf_lt_matmul).  ins: per input the
+        pair of tensors (c0, c1), or None for an input no block uses; col_exps / col_keys: per input the Galois exponents and the
+        packed keys of its keyed steps, ascending (slot 1 + j of the column; slot 0 is the ciphertext); blocks: k_out rows of
+        k_in entries, None or (pack [k, rows, N], slots): the block's encoded diagonals and the column slot of each, ascending;
+        outs: k_out tensors [2, ell - 1, N]; ws: at least lt_matmul_ws_words(plan, the longest used column, k_out) words."""
+        dev, st = _ds(outs[0])
+        k_in, k_out = len(ins), len(blocks)
+        keyed = [k for col in col_keys for k in col]
+        fmt = {self._kfmt(k) for k in keyed}
+        if len(fmt) > 1:
+            raise ValueError("lt_matmul_native: the keys of one call must share one format")
+        ps = cs = 0
+        kb = (ctypes.c_void_p * max(len(keyed), 1))()
+        for j, key in enumerate(keyed):
+            kb[j], ps, cs = self._key_args(key, first_part)
+        i64 = lambda v: (ctypes.c_int64 * max(len(v), 1))(*v)
+        inp = (ctypes.c_void_p * (2 * k_in))()
+        for i, pair in enumerate(ins):
+            if pair is not None:
+                inp[2 * i], inp[2 * i + 1] = pair[0].data_ptr(), pair[1].data_ptr()
+        pts = (ctypes.c_void_p * (k_out * k_in))()
+        strides, counts, slots = [], [], []
+        for o, row in enumerate(blocks):
+            for i, blk in enumerate(row):
+                if blk is None:
+                    strides.append(0), counts.append(0)
+                    continue
+                pack, sl = blk
+                pts[o * k_in + i] = pack.data_ptr()
+                strides.append(pack.stride(0)), counts.append(len(sl))
+                slots += list(sl)
+        check(lib.lf_lt_matmul(ctypes.byref(plan), k_in, k_out, inp, i64([len(c) for c in col_keys]), i64([e for c in col_exps for e in c]),
+                               kb, ps, cs, row_off, fmt.pop() if fmt else 0, pts, i64(strides), i64(counts), i64(slots), _p(scales),
+                               round_at, _p(ws), ws.numel(), _parr([o[0] for o in outs]), _parr([o[1] for o in outs]), st),
+              "lf_lt_matmul")
+
     def ks_gather(self, ext, dst, index, rows, logN, c: Consts):
         """dst[p][r][k] = ext[p][r][index[k]] for extended digits as ks_fwd leaves them: fp64-class rows of a mixed stack in the
         planes format (u32 low words at byte 0, u16 high halves at byte 4 N of the row: LF_TUNE_DIGIT_PLANES), other rows raw

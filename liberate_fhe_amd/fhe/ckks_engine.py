@@ -37,6 +37,7 @@ from .backend import Consts
 from .context.ckks_context import ckks_context
 from .data_struct import data_struct
 from .evaluator import EvaluatorOps, is_struct
+from .ltmatmul import LtMatmulOps
 from .plainops import PlainOps
 from .polyeval import PolyOps
 from .presets import errors, types
@@ -76,7 +77,7 @@ class _OneShard:
         return ckks_engine._decrypt_rows_on(self, ct, sk, self.li, self.dev)
 
 
-class ckks_engine(EvaluatorOps, PolyOps, PlainOps):
+class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps):
     @errors.log_error
     def __init__(self, devices: list[int] = None, verbose: bool = False, bias_guard: bool = True,
                  norm: str = "forward", backend=None, comm=None, balanced_limb_map: bool = False, **ctx_params):

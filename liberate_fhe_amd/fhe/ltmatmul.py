@@ -1,0 +1,270 @@
+"""lt_matmul, mixed into `ckks_engine`: a k_out x k_in matrix of diagonal sets times k_in ciphertexts — a matrix larger than one
+ciphertext's slots, or a layer applied to several packed inputs:
+
+    y_o = sum_i sum_{step in steps(W[o][i])} diag_{o,i,step} * rot(x_i, step)
+
+It is the union of pc_matmul (a matrix of plaintexts, no rotations) and linear_transform (one ciphertext under a sum of diagonals
+times rotations).  The key-switched rotations of x_i do not depend on the output: they are formed once per input and shared by
+all outputs; the sums over the inputs stay in Q P and every output is brought down once.  Like the engine's other options beyond
+the reference, the words are DEFINED as a composition of steps the engine already has (written out in lt_matmul's docstring), and
+that composition is what runs wherever the native call (lf_lt_matmul) does not apply.  DESIGN.md §4.2.
+"""
+from __future__ import annotations
+
+from collections.abc import Mapping
+
+import torch
+
+from . import encdec
+from .backend import HipBackend
+from .evaluator import is_struct
+from .presets import errors, types
+
+
+class LtMatmulOps:
+    # include/ckks_hip.h: LF_LT_MATMUL_MAX_INPUTS and LF_BSGS_MAX_BABY_KEYS (the keyed steps of one column), refused on every path
+    # (the outputs of one native call are the backend's lt_matmul_max_outputs: more are split over calls)
+    lt_matmul_max_inputs = HipBackend.lt_matmul_max_inputs
+    lt_matmul_max_column_keys = HipBackend.bsgs_max_baby_keys
+
+    def _lt_matmul_blocks(self, W):
+        """W as a list of rows, and per block its steps in the order of its data (None for a zero block); the checks that need
+        nothing but the matrix.  Nothing is encoded or allocated here."""
+        W = [list(row) for row in W]
+        if not W:
+            raise ValueError("lt_matmul: at least one row of blocks")
+        k_in = len(W[0])
+        steps = []
+        for row in W:
+            if len(row) != k_in:
+                raise ValueError(f"lt_matmul: a row of {len(row)} blocks beside one of {k_in}")
+            if all(b is None for b in row):
+                raise ValueError("lt_matmul: a row without a block")
+            srow = []
+            for b in row:
+                if b is None:
+                    srow.append(None)
+                elif is_struct(b):
+                    if b.origin.startswith(types.origins["diag_bsgs"]):
+                        raise NotImplementedError("lt_matmul: flat diagonals only (giant steps inside a block are out of scope)")
+                    if not b.origin.startswith(types.origins["diag"]):
+                        raise errors.NotMatchType(origin=b.origin, to=types.origins["diag"])
+                    srow.append(self.diagonal_steps(b))
+                elif isinstance(b, Mapping):
+                    s = sorted(int(k) % self.num_slots for k in b)
+                    if not s:
+                        raise ValueError("lt_matmul: a block without a diagonal")
+                    if len(set(s)) != len(s):
+                        raise ValueError(f"lt_matmul: a step given twice in one block (steps are taken mod {self.num_slots})")
+                    srow.append(s)
+                else:
+                    raise errors.NotMatchType(origin=getattr(b, "origin", type(b).__name__), to=types.origins["diag"])
+            steps.append(srow)
+        if k_in < 1:
+            raise ValueError("lt_matmul: at least one ciphertext")
+        if k_in > self.lt_matmul_max_inputs:
+            raise ValueError(f"lt_matmul: {k_in} inputs, at most {self.lt_matmul_max_inputs}")
+        for i in range(k_in):
+            keyed = {s for srow in steps if srow[i] is not None for s in srow[i] if s}
+            if len(keyed) > self.lt_matmul_max_column_keys:
+                raise ValueError(f"lt_matmul: column {i} needs {len(keyed)} keyed steps, at most {self.lt_matmul_max_column_keys}")
+        return W, steps
+
+    def lt_matmul_steps(self, W) -> list:
+        """The sorted non-zero steps lt_matmul(W, ..) needs a rotation key for (one key per step serves every input)."""
+        _, steps = self._lt_matmul_blocks(W)
+        return sorted({s for srow in steps for b in srow if b is not None for s in b if s})
+
+    def lt_matmul(self, W, cts, rotks) -> list:
+        """A matrix of linear transforms times a vector of ciphertexts: the list of the k_out ciphertexts
+            y_o = sum_i sum_{step in steps(W[o][i])} diag_{o,i,step} * rotate(cts[i], step)
+        at level + 1 (rotate_single's direction, as linear_transform).  W: k_out rows of k_in entries, each a flat
+        encode_diagonals object of the ciphertexts' level, a plain {step: vector} mapping (encoded here, as linear_transform
+        does) or None for a zero block; every row needs a block.  cts: k_in ciphertexts of one level (coefficient domain, no
+        special limbs); rotks: a list or mapping of rotation keys looked up by the step in their origin — one key per step serves
+        every input, step 0 needs none (lt_matmul_steps).  Rows, cts and rotks may be any iterables, objects may repeat anywhere;
+        an input no output uses is legal and costs nothing.
+        The words are those of: per input i that some block uses c0, c1 made canonical, E_i and c^_i as linear_transform forms
+        them; per step != 0 of U_i = the union of the column's steps t^{i,step}_c = sum over the parts of E_i gathered by pi_step
+        times the key part, t_0 += c^_{i,0} gathered on the ordinary rows (step 0: t_c = c^_{i,c}, zero on the special rows); per
+        output S^o_c = sum_i sum_step mont_mult(pt_{o,i,step}, t^{i,step}_c); intt_exit_reduce, mod-down without addend,
+        rescale.  Only residues of t and S reach the result, so the grouping of the additions is free.  With k_in = 1 output o has
+        word for word the words of linear_transform(cts[0], W[o][0], rotks); for k_in > 1 the words are the op's own — NOT those
+        of cc_add over separate transforms, which round once per block.
+        One native call (lf_lt_matmul) per 64 outputs where every limb of the level is on one device of this process — each call
+        repeats the rotations of its inputs, so more than 64 outputs pay them again; otherwise the same words through the
+        engine's steps, the rotated sums formed once per input and step and accumulated into every output that uses them."""
+        W, steps = self._lt_matmul_blocks(W)
+        cts = list(cts)
+        k_out, k_in = len(W), len(W[0])
+        if len(cts) != k_in:
+            raise ValueError(f"lt_matmul: rows of {k_in} blocks beside {len(cts)} ciphertexts")
+        for ct in cts:
+            if not is_struct(ct) or ct.origin != types.origins["ct"]:
+                raise errors.NotMatchType(origin=getattr(ct, "origin", type(ct).__name__), to=types.origins["ct"])
+        keys = list(rotks.values()) if isinstance(rotks, dict) else list(rotks)
+        by_step = {}
+        for k in keys:
+            if not is_struct(k) or types.origins["rotk"] not in k.origin:
+                raise errors.NotMatchType(origin=getattr(k, "origin", type(k).__name__), to=types.origins["rotk"])
+            by_step.setdefault(int(k.origin.split(":")[-1]) % self.num_slots, k)
+        for ct in cts:
+            if ct.ntt_state or ct.include_special:
+                raise NotImplementedError("lt_matmul: coefficient-domain ciphertexts without special limbs only")
+        level = cts[0].level
+        for ct in cts:
+            if ct.level != level:
+                raise errors.NotMatchDataStructState(origin=f"{ct.origin} at level {ct.level} beside level {level}")
+        for row in W:
+            for b in row:
+                if is_struct(b) and b.level != level:
+                    raise errors.NotMatchDataStructState(origin=f"{b.origin} at level {b.level}, ciphertexts at level {level}")
+        if level + 1 >= self.num_levels:
+            raise errors.MaximumLevelError(level=level, level_max=self.num_levels)
+        for s in sorted({s for srow in steps for b in srow if b is not None for s in b if s}):
+            if s not in by_step:
+                raise errors.NotMatchType(origin=f"no key for step {s}", to=types.origins["rotk"] + str(s))
+        # (every refusal is behind us: from here on things are encoded, allocated and launched)
+        encoded = {}
+        for row in W:
+            for i, b in enumerate(row):
+                if b is not None and not is_struct(b):
+                    if id(b) not in encoded:
+                        encoded[id(b)] = self.encode_diagonals(b, level)
+                    row[i] = encoded[id(b)]
+        steps = [[None if b is None else self.diagonal_steps(b) for b in row] for row in W]
+
+        d = self._native_level(level)
+        if d is not None and hasattr(self.backend, "lt_matmul_native") and \
+                all(s is None or s == sorted(s) for srow in steps for s in srow) and \
+                all(ct.data[c][0].is_contiguous() for i, ct in enumerate(cts) if any(s[i] is not None for s in steps) for c in range(2)):
+            step = self.backend.lt_matmul_max_outputs
+            return [out for o0 in range(0, k_out, step)
+                    for out in self._lt_matmul_native(W[o0:o0 + step], steps[o0:o0 + step], cts, by_step, level, d)]
+        return self._lt_matmul_steps(W, steps, cts, by_step, level)
+
+    def _lt_matmul_native(self, W, steps, cts, by_step, level, d):
+        N, k_in = self.ctx.N, len(cts)
+        plan, _, first_part, row_off = self._op_plan(level, d)
+        i0 = self._loc(0, special=True).index(d)
+        li = self.local_ids.index(d)
+        owner = self.ntt.p.rescaler_loc[level]
+        round_at = self.ctx.q[self.ntt.p.destination_arrays[level][owner][0]] // 2
+        ins, col_exps, col_keys, slot = [], [], [], []
+        for i in range(k_in):
+            col = [s for s in steps if s[i] is not None]
+            keyed = sorted({t for s in col for t in s[i] if t})
+            ins.append((cts[i].data[0][0], cts[i].data[1][0]) if col else None)
+            col_exps.append([encdec.galois_exponent(N, t) for t in keyed])
+            col_keys.append([self._key_pack(by_step[t])[i0] for t in keyed])
+            slot.append({0: 0, **{t: 1 + j for j, t in enumerate(keyed)}})
+        blocks = [[None if b is None else (self._diag_pack(b)[li], [slot[i][t] for t in s[i]]) for i, b in enumerate(row)]
+                  for row, s in zip(W, steps)]
+        nb_max = max(len(c) for c in col_keys)
+        ws = self._ws("lt_matmul_ws", (self.backend.lt_matmul_ws_words(plan, nb_max, len(W)),), d)
+        outs = [torch.empty((2, plan.ell - 1, N), dtype=torch.int64, device=self.ntt.devices[d]) for _ in W]
+        self.backend.lt_matmul_native(plan, ins, col_exps, col_keys, first_part, row_off, blocks, self.rescale_scales[level][d],
+                                      round_at, outs, ws)
+        return [self._new(([o[0]], [o[1]]), types.origins["ct"], level=level + 1) for o in outs]
+
+    def _lt_matmul_steps(self, W, steps, cts, by_step, level):
+        """The same words through the engine's steps (linear_transform's orchestrated loop): per used input the digits of c1 and
+        their exchange once, extension + forward NTT once per device, c^ per device on its own rows; per step of the column the
+        gather, the key's inner product and the products with the diagonal of EVERY output that has the step in this column; per
+        output ONE inverse NTT, mod-down and rescale."""
+        N, logN = self.ctx.N, self.ctx.logN
+        tabs = self._ks_tables(level)
+        loc, loc0 = self._loc(level), self._loc(0, special=True)
+        K, n = self.ntt.num_special_primes, self.ntt
+        nparts = len(tabs["order"])
+        fused = logN >= self.backend.fused_ks_min_logN
+        gather = getattr(self.backend, "ks_gather", None)
+        S = [[[None, None] for _ in loc] for _ in W]
+
+        def accumulate(di, li, i, step, t):
+            mont = [x[li:li + 1] for x in n.mont_prepack[-2][level][0]]
+            _2q = [n._2q_prepack[-2][level][0][li]]
+            for o, (row, srow) in enumerate(zip(W, steps)):
+                if srow[i] is None or step not in srow[i]:
+                    continue
+                ptj = row[i].data[srow[i].index(step)][li]
+                acc = S[o][di]
+                for comp in range(2):
+                    prod = n.ops.mont_mult([ptj], [t[comp]], *mont)[0]
+                    acc[comp] = prod if acc[comp] is None else n.ops.mont_add([acc[comp]], [prod], _2q)[0]
+
+        for i, ct in enumerate(cts):
+            U = sorted({t for srow in steps if srow[i] is not None for t in srow[i]})
+            if not U:
+                continue                                                  # an input no output uses
+            keyed = [t for t in U if t]
+            digits = self._ks_digits_exchanged(ct.data[1], level, galois=(1, True)) if keyed else {}
+            for di, d in enumerate(loc):
+                li = self.local_ids.index(d)
+                rows, ell = self._rows(d, level, True), self._rows(d, level, False)
+                cs, cso = self._consts(d, level, True), self._consts(d, level, False)
+                tw, itw, ninv = self._tw(d, level, True), self._tw(d, level, True, True), self._vec("Ninv", d, level, True)
+                _2q = [n._2q_prepack[-2][level][0][li]]
+                g2q = self._vec("_2q", d, level, False)
+                dev = self.ntt.devices[d]
+                # c^0, c^1 = P * enter_ntt(canonical c) on the ordinary rows
+                chat = torch.empty((2, ell, N), dtype=torch.int64, device=dev)
+                for comp in range(2):
+                    src = ct.data[comp][di] if ct.data[comp][di].is_contiguous() else ct.data[comp][di].contiguous()
+                    self.backend.galois(src, chat[comp], ell, logN, 1, g2q)
+                    self.backend.ntt(chat[comp], 1, ell, logN, self._tw(d, level, False), self._vec("Rs", d, level, False), cso)
+                    n.ops.mont_enter([chat[comp]], [self._PR(d, level)], *[x[li:li + 1] for x in n.mont_prepack[-1][level][0]])
+                if 0 in U:
+                    t = torch.zeros((2, rows, N), dtype=torch.int64, device=dev)
+                    t[:, :ell] = chat
+                    accumulate(di, li, i, 0, t)
+                if not keyed:
+                    continue
+                desc, E, Ed = tabs[("extend", d)]
+                ext = self._ws("ks_ext", (nparts, rows, N), d)
+                dig, ready = digits[d]
+                for handle, first, count in ready:
+                    if handle is not None:
+                        handle.wait()
+                    if fused:
+                        self.backend.ks_fwd(dig, first, count, rows, logN, desc, E, Ed, ext, tw, cs)
+                if not fused:
+                    self.backend.ks_extend(dig, ext, nparts, rows, desc, E, cs)
+                    self.backend.ntt(ext, nparts, rows, logN, tw, None, cs, relaxed=True)
+                src = self._ws("ks_ext_hoisted", (nparts, rows, N), d)   # (see rotate_hoisted: `ext` receives each key's gather)
+                src.copy_(ext)
+                s = self._ws("ks_sum", (2, rows, N), d)
+                Rs = self._vec("Rs", d, level, True)
+                for step in keyed:
+                    idx = self._galois_index(encdec.galois_exponent(N, step), d)
+                    if gather is not None:
+                        gather(src, ext, idx, rows, logN, cs)
+                    else:
+                        torch.index_select(src, 2, idx, out=ext)
+                    kp = self._key_pack(by_step[step])[loc0.index(d)]
+                    if fused:
+                        self.backend.ks_tail(nparts, rows, logN, kp, tabs["first_part"], self.ntt.starts[level][d], ext, s, itw, ninv, cs)
+                        self.backend.ntt(s, 2, rows, logN, tw, Rs, cs)     # back into the NTT domain, Montgomery form
+                    else:
+                        self.backend.ks_inner(ext, kp, tabs["first_part"], self.ntt.starts[level][d], s[0], s[1], nparts, rows, cs)
+                    t = s.clone()
+                    t[0, :ell] = n.ops.mont_add([t[0, :ell]], [chat[0].index_select(1, idx)], [_2q[0][:ell]])[0]
+                    accumulate(di, li, i, step, t)
+
+        outs = []
+        for o in range(len(W)):
+            c0o, c1o = [], []
+            for di, d in enumerate(loc):
+                rows, ell = self._rows(d, level, True), self._rows(d, level, False)
+                cs = self._consts(d, level, True)
+                s2 = torch.stack(S[o][di]).contiguous()
+                self.backend.intt(s2, 2, rows, logN, self._tw(d, level, True, True), self._vec("Ninv", d, level, True), 2, cs)
+                out = torch.empty((2, ell, N), dtype=torch.int64, device=self.ntt.devices[d])
+                ws, one = self._moddown_ws("ks_moddown", 2, ell, K, d, tabs, cs)
+                mkw = {"one_launch": True} if one else {}
+                self.backend.ks_moddown_ws([s2[0], s2[1]], [out[0], out[1]], [None, None], ell, K, ws, tabs[("pir", d)],
+                                           self._vec("Rs", d, level, True), cs, PiP=tabs[("pip", d)], **mkw)
+                c0o.append(out[0]); c1o.append(out[1])
+            S[o] = None
+            outs.append(self.rescale(self._new((c0o, c1o), types.origins["ct"], level=level)))
+        return outs

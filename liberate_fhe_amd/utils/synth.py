@@ -110,6 +110,11 @@ def diagonals_bsgs(engine, seed: int, level: int, steps, n1: int, ds_type=None):
     return out._replace(origin=f"plain diagonals bsgs:{int(n1)};" + out.origin.split(":", 1)[1])
 
 
+def diagonal_matrix(blocks, k_in: int, k_out: int):
+    """A dense W for ckks_engine.lt_matmul: k_out rows of k_in entries drawn in turn from the `diagonals` objects `blocks`."""
+    return [[blocks[(o + 2 * i) % len(blocks)] for i in range(k_in)] for o in range(k_out)]
+
+
 def _data_struct(engine):
     import importlib
     mod = importlib.import_module(type(engine).__module__.rsplit(".", 1)[0] + ".data_struct")

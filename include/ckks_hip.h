@@ -670,6 +670,25 @@ int lf_cc_dot(const lf_ks_plan *plan, int np, const int64_t *const *in, const in
               int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format, int64_t *ws, int64_t ws_words, int64_t *out0,
               int64_t *out1, void *stream);
 
+/* nd = 1, 2 or 4 independent dots under ONE key (nd <= plan->max_nct, the rule of lf_cc_mult_evk_batch): dot d has np_host[d] >= 1
+ * pairs (HOST array of nd entries); in / row0: HOST arrays of 4 sum_d np_host[d] device pointers, four per pair in lf_cc_dot's
+ * order, all pairs of dot 0, then those of dot 1, and so on; out0 / out1: HOST arrays of nd device pointers, [ell][N] each, canonical.
+ * Output d has exactly the words of lf_cc_dot on dot d's pairs.
+ * Enqueued: per dot lf_cc_dot's chunks — lf_rescale_ntt into plan->x4 and dot_tensor_kernel into that dot's triplet
+ * T_d = ws + d * 3 ell N, the last chunk of dot d leaving its copy of T2 at plan->d2 + d * ell N; ONE lf_intt (batch nd, tail 2,
+ * relaxed, plain) of the nd copies and ONE lf_ks_digits_batch into plan->state (stride ell N); ONE extension + forward NTT of all
+ * nd x nparts digits (own-limb pairs skipped) and ONE launch of ks_dotb_inner_kernel<nd> — the pre-summed fold of
+ * ks_inner2_presum_kernel for nd triplets, every key word read once for all of them — with the inverse NTT of the 2 nd sums in
+ * plan->sum; ONE mod-down of the 2 nd sums, no addend (in one launch where plan->md_consts = 2 nd).  nd = 1: lf_cc_dot's launches.
+ * The triplets live in `ws` of at least lf_cc_dot_batch_ws_words(plan, nd) = 3 nd ell N words, lent by the caller (0 for a plan
+ * or an nd the entry refuses).
+ * LF_ERR_ARG before any launch for everything lf_cc_dot refuses, nd not 1, 2 or 4 or above plan->max_nct, np_host NULL or an entry
+ * below 1, a NULL among the 4 sum np pointers of in or row0 or among the nd of out0 or out1, ws NULL or too small. */
+int64_t lf_cc_dot_batch_ws_words(const lf_ks_plan *plan, int nd);
+int lf_cc_dot_batch(const lf_ks_plan *plan, int nd, const int64_t *np_host, const int64_t *const *in, const int64_t *const *row0,
+                    const int64_t *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format, int64_t *ws,
+                    int64_t ws_words, int64_t *const *out0, int64_t *const *out1, void *stream);
+
 /* Several weighted sums of the same ciphertexts under ONE rescale (the baby-step sums of a polynomial evaluation): for
  * g < G, out_g = rescale(sum_{t < k} s_{g,t} ct_t) (+ a constant), level l -> l + 1, one launch per group of 4, 2 or 1 outputs
  * (weighted_sums_kernel<4 | 2 | 1>: every input word is read once per group).

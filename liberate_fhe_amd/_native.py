@@ -110,7 +110,9 @@ _SIGNATURES["lf_rotate_hoisted_ws_words"] = [_PL]
 _SIGNATURES["lf_rotate_hoisted"] = [_PL, _P, _P, _I, _P, _I, _P, _L, _L, _L, _I, _P, _L, _P, _P, _P]
 _SIGNATURES["lf_cc_dot_ws_words"] = [_PL]
 _SIGNATURES["lf_cc_dot"] = [_PL, _I, _P, _P, _P, _L, _L, _L, _I, _P, _L, _P, _P, _P]
-_SIGNATURES["lf_weighted_sums"] = [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _L, _P, _P, _P, _P, _I, _P]
+_SIGNATURES["lf_cc_dot_batch_ws_words"] = [_PL, _I]
+_SIGNATURES["lf_cc_dot_batch"] = [_PL, _I, _P, _P, _P, _P, _L, _L, _L, _I, _P, _L, _P, _P, _P]
+_SIGNATURES["lf_weighted_sums"] =[_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _L, _P, _P, _P, _P, _I, _P]
 _SIGNATURES["lf_pc_dot_ws_words"] = [_I, _I, _I]
 _SIGNATURES["lf_pc_dot"] = [_I, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _I, _P]
 _SIGNATURES["lf_pc_matmul_ws_words"] = [_I, _I, _I, _I]

@@ -482,7 +482,7 @@ __device__ __forceinline__ longlong2 ld_nt(const i64 *p) {
 // the number PR = P * R mod q as a double; integer rows hold Montgomery-form words and take REDC(d * PR).
 struct RelinFold {
     const i64 *x;       // [nct][4][ell][N] = x0, x1, y0, y1 per ciphertext pair, as lf_rescale_ntt(RELAXED | PLAIN) leaves them
-    i64 ct_stride;      // words between the stacks of consecutive pairs
+    i64 ct_stride;      // words between the stacks of consecutive pairs (the pre-summed forms: between the triplets [3][ell][N])
     const i64 *PR;      // [ell]  P * R mod q_r
     int ell;            // ordinary rows: the first `ell` of the `rows` limbs
     // own[r] = the digit limb r belongs to (nullptr: none skipped): that digit's extension to limb r IS the third tensor
@@ -522,6 +522,20 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) k
                                                         const i64 *__restrict__ ql, const i64 *__restrict__ qh,
                                                         const i64 *__restrict__ kl, const i64 *__restrict__ kh) {
     constexpr int NCT = 1;
+    constexpr bool FOLD = true, PRESUM = true;
+#include "ckks_ks_inner2.h"
+}
+
+// the pre-summed fold for NCT = 2 or 4 triplets under one key (cc_dot_batch): a key word is read once for all of them; triplet t at
+// fold.x + t * fold.ct_stride.  A name of its own, the same body.  amdgpu_waves_per_eu as ks_inner2_kernel<NCT, true, ..> (the
+// folded form of the same NCT, whose register needs this one shares): that choice is carried over, NOT measured for this kernel.
+template <int NCT, bool PLANES, bool DPL>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NCT == 4 ? 4 : 1))) ks_dotb_inner_kernel(const i64 *__restrict__ ext, const i64 *__restrict__ ksk,
+                                                        i64 part_stride, i64 comp_stride, i64 row_off, i64 *__restrict__ s,
+                                                        int nparts, int rows, i64 N, RelinFold fold, int spl,
+                                                        const i64 *__restrict__ ql, const i64 *__restrict__ qh,
+                                                        const i64 *__restrict__ kl, const i64 *__restrict__ kh) {
+    static_assert(NCT == 2 || NCT == 4, "one triplet: ks_inner2_presum_kernel");
     constexpr bool FOLD = true, PRESUM = true;
 #include "ckks_ks_inner2.h"
 }
@@ -1434,7 +1448,8 @@ bool digit_planes(int logN, const RowList &dp, const RowList &in) {
 // LF_FP64_MAX_DIGITS (include/ckks_hip.h): every fp64-class inner product adds `nparts` balanced products (|.| <= q / 2 each)
 // and reduces once with dp_reduce, exact for |x| < 64 q.  What else joins the sum before that reduction, per kernel:
 //   ks_inner_hoist_kernel                  nothing                                    nparts / 2     < 64:  nparts <= 127
-//   ks_inner2(_presum)_kernel              the fold's balanced product with PR        nparts / 2 + 1/2 < 64: nparts <= 126
+//   ks_inner2(_presum)_kernel, ks_dotb_    the fold's balanced product with PR        nparts / 2 + 1/2 < 64: nparts <= 126
+//     inner_kernel (the same body)
 //   ks_inner_baby_kernel, ks_inner_lt_     one word of P c0 below 2q                  nparts / 2 + 2 < 64:  nparts <= 123
 //     kernel (it reduces there with dp_reduce_bal, |x| < 2^52, and its running pair stays within (NR + 2) q)
 //   ks_inner_giant_kernel                  a word of S^g_0 and one of the accumulator, both below 2q
@@ -1569,7 +1584,7 @@ int ks_tail(int nct, int nparts, int rows, int logN, const int64_t *ksk, int64_t
             int64_t row_off, int64_t *tmp, int64_t *s, const int64_t *ipsi_br, const double *ipsi_dp,
             const int64_t *Ninv, const int64_t *q_host, const int64_t *ql, const int64_t *qh, const int64_t *kl,
             const int64_t *kh, hipStream_t st, const RelinFold *fold = nullptr, int key_format = LF_KEY_RAW, bool presum = false) {
-    if (!ipsi_dp || (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES) || (presum && (!fold || nct != 1))) return LF_ERR_ARG;
+    if (!ipsi_dp || (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES) || (presum && !fold)) return LF_ERR_ARG;
     if (key_format == LF_KEY_PLANES && ((((uintptr_t)ksk | (uintptr_t)(part_stride * 8) | (uintptr_t)(comp_stride * 8)) & 15)))
         return LF_ERR_ARG;
     const int tl = NTT_TILE_LOG_MAX, S1 = logN - tl;
@@ -1611,16 +1626,34 @@ int ks_tail(int nct, int nparts, int rows, int logN, const int64_t *ksk, int64_t
     hipLaunchKernelGGL((ks_inner2_presum_kernel<PL, DPLB>), grid, dim3(256), 0, st, (const i64 *)tmp, (const i64 *)ksk,  \
                        (i64)part_stride, (i64)comp_stride, (i64)row_off, (i64 *)s, nparts, rows, N, *fold, spl ? 1 : 0, (const i64 *)ql, \
                        (const i64 *)qh, (const i64 *)kl, (const i64 *)kh)
-        if (presum) {   // cc_dot: the fold reads a triplet already summed (one ciphertext)
+#define LF_DOTB_LAUNCH(NCT, PL, DPLB)                                                                                  \
+    hipLaunchKernelGGL((ks_dotb_inner_kernel<NCT, PL, DPLB>), grid, dim3(256), 0, st, (const i64 *)tmp, (const i64 *)ksk, \
+                       (i64)part_stride, (i64)comp_stride, (i64)row_off, (i64 *)s, nparts, rows, N, *fold, spl ? 1 : 0, (const i64 *)ql, \
+                       (const i64 *)qh, (const i64 *)kl, (const i64 *)kh)
+#define LF_DOTB_CASE(NCT)                                                                                              \
+    case NCT:                                                                                                          \
+        if (planes && dplanes) LF_DOTB_LAUNCH(NCT, true, true);                                                        \
+        else if (planes) LF_DOTB_LAUNCH(NCT, true, false);                                                             \
+        else if (dplanes) LF_DOTB_LAUNCH(NCT, false, true);                                                            \
+        else LF_DOTB_LAUNCH(NCT, false, false);                                                                        \
+        break;
+        if (presum && nct == 1) {   // cc_dot: the fold reads a triplet already summed (one ciphertext)
             if (planes && dplanes) LF_PRESUM_LAUNCH(true, true);
             else if (planes) LF_PRESUM_LAUNCH(true, false);
             else if (dplanes) LF_PRESUM_LAUNCH(false, true);
             else LF_PRESUM_LAUNCH(false, false);
+        } else if (presum) {   // cc_dot_batch: nct summed triplets, fold->ct_stride apart
+            switch (nct) {
+                LF_DOTB_CASE(2) LF_DOTB_CASE(4)
+                default: return LF_ERR_ARG;
+            }
         } else
         switch (nct) {
             LF_INNER_CASE(1) LF_INNER_CASE(2) LF_INNER_CASE(4)
         }
 #undef LF_PRESUM_LAUNCH
+#undef LF_DOTB_LAUNCH
+#undef LF_DOTB_CASE
 #undef LF_INNER_LAUNCH
 #undef LF_INNER_DPL
 #undef LF_INNER_CASE
@@ -1726,6 +1759,27 @@ int lf_dot_relin(const int64_t *state, int nparts, int rows, int logN, const int
     const RelinFold fold{(const i64 *)T, 0, (const i64 *)PR, ell, (const unsigned char *)own, 0};
     return ks_tail(1, nparts, rows, logN, ksk, part_stride, comp_stride, row_off, tmp, s, ipsi_br, ipsi_dp, Ninv, q_host, ql, qh, kl, kh,
                    st, &fold, key_format, true);
+}
+
+// lf_dot_relin_batch: lf_dot_relin for nct (2 or 4) summed triplets T + t * 3 ell N under one key: the digits of triplet t at
+// state + t * ell N, ONE extension + forward NTT of all of them, ONE launch of ks_dotb_inner_kernel<nct> (every key word read once
+// for the nct triplets), the inverse NTT of the 2 nct sums s [nct][2][rows][N].  Internal: ckks_ops.hip checks the arguments.
+int lf_dot_relin_batch(const int64_t *state, int nct, int nparts, int rows, int logN, const int64_t *desc, const int64_t *E,
+                       const double *Ed, const int64_t *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format,
+                       int64_t *tmp, int64_t *s, const int64_t *psi_br, const double *psi_dp, const int64_t *ipsi_br,
+                       const double *ipsi_dp, const int64_t *Ninv, const int64_t *T, const int64_t *PR, int ell, const uint8_t *own,
+                       const int64_t *q_host, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st) {
+    if ((nct != 2 && nct != 4) || nparts < 1 || nparts > 254 || rows < 1 || rows > MAX_LIST_ROWS || logN <= NTT_TILE_LOG_MAX ||
+        logN > KS_LOGN_MAX || !q_host || !psi_dp || !ipsi_dp || !Ed || !T || !PR || ell < 0 || ell > rows)
+        return LF_ERR_ARG;
+    if (!lf_fp64_digits_ok(nparts, rows, q_host)) return LF_ERR_ARG;
+    const int64_t poly = (int64_t)ell << logN;
+    if (int e = ks_forward(state, poly, nct, nparts, rows, logN, desc, E, Ed, tmp, psi_br, psi_dp, q_host, ql, qh, kl, kh, st,
+                           (const unsigned char *)own, 0))
+        return e;
+    const RelinFold fold{(const i64 *)T, (i64)(3 * poly), (const i64 *)PR, ell, (const unsigned char *)own, 0};
+    return ks_tail(nct, nparts, rows, logN, ksk, part_stride, comp_stride, row_off, tmp, s, ipsi_br, ipsi_dp, Ninv, q_host, ql, qh, kl,
+                   kh, st, &fold, key_format, true);
 }
 
 // The key-dependent half of nr (1, 2 or 4) hoisted rotations of ONE ciphertext (lf_rotate_hoisted, ckks_ops.hip): inner product of

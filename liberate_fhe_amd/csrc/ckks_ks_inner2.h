@@ -1,12 +1,14 @@
 // ckks_ks_inner2.h — the body of the key switch's inner-product kernel (ckks_ks.hip: K3), included once per kernel that shares it:
-// ks_inner2_kernel<NCT, FOLD, PLANES, DPL> (PRESUM = false) and ks_inner2_presum_kernel<PLANES, DPL> (NCT = 1, FOLD, PRESUM = true).
+// ks_inner2_kernel<NCT, FOLD, PLANES, DPL> (PRESUM = false), ks_inner2_presum_kernel<PLANES, DPL> (NCT = 1, FOLD, PRESUM = true) and
+// ks_dotb_inner_kernel<NCT, PLANES, DPL> (NCT = 2 or 4, FOLD, PRESUM = true).
 // Text inclusion, not a function: the existing instantiations keep the very code they had (a shared __device__ body moved a
 // register or two in a dozen of them; profiles/r06_kernel_resources.txt).  The including kernel provides the compile-time
 // constants NCT, FOLD, PLANES, DPL, PRESUM and the parameters ext, ksk, part_stride, comp_stride, row_off, s, nparts, rows, N,
 // fold, spl, ql, qh, kl, kh.
 // PRESUM (cc_dot): fold.x points at a triplet T = [3][ell][N] already summed over many pairs (dot_tensor_kernel: fp64-class rows
 // plain canonical residues, integer-class rows Montgomery-form words below 2q, raw words on every row), so the sums take
-// REDC(T0 * PR) and REDC(T1 * PR) and the own-limb digit words are T2's, read as they lie; ct_stride and xpl are unused.
+// REDC(T0 * PR) and REDC(T1 * PR) and the own-limb digit words are T2's, read as they lie; xpl is unused.  cc_dot_batch: the
+// triplet of ciphertext t lies at fold.x + t * fold.ct_stride (NCT = 1: t = 0, the stride is never read).
     // spl: the sums of fp64-class rows leave as planes (the inverse passes behind read them so: ks_tail)
     // each thread owns KI_V 16-byte column pairs 4 KiB apart: every block streams KI_V x 4 KiB contiguous runs
     // from 3 x nparts arrays, enough bytes in flight to keep HBM busy
@@ -35,7 +37,7 @@
 #pragma unroll
             for (int t = 0; t < NCT; ++t) {
                 if constexpr (PRESUM) {
-                    const longlong2 T2 = *reinterpret_cast<const longlong2 *>(fold.x + (2 * (i64)fold.ell + r) * N + j0);
+                    const longlong2 T2 = *reinterpret_cast<const longlong2 *>(fold.x + t * fold.ct_stride + (2 * (i64)fold.ell + r) * N + j0);
                     xo_x[t] = T2.x, xo_y[t] = T2.y;
                 } else {
                     const i64 *xs = fold.x + t * fold.ct_stride + (i64)r * N + (i64)fold.ell * N;
@@ -111,8 +113,8 @@
 #pragma unroll
             for (int t = 0; t < NCT; ++t) {
                 if constexpr (PRESUM) {   // plain canonical words: one product with PR each
-                    const longlong2 T0 = *reinterpret_cast<const longlong2 *>(fold.x + (i64)r * N + j0);
-                    const longlong2 T1 = *reinterpret_cast<const longlong2 *>(fold.x + pstride + (i64)r * N + j0);
+                    const longlong2 T0 = *reinterpret_cast<const longlong2 *>(fold.x + t * fold.ct_stride + (i64)r * N + j0);
+                    const longlong2 T1 = *reinterpret_cast<const longlong2 *>(fold.x + t * fold.ct_stride + pstride + (i64)r * N + j0);
                     acc[t][0][0] += dp_mulmod_bal(dp_from_word(T0.x), pr, d);
                     acc[t][0][1] += dp_mulmod_bal(dp_from_word(T0.y), pr, d);
                     acc[t][1][0] += dp_mulmod_bal(dp_from_word(T1.x), pr, d);
@@ -161,7 +163,7 @@
 #pragma unroll
             for (int t = 0; t < NCT; ++t) {
                 if constexpr (PRESUM) {
-                    const longlong2 T2 = *reinterpret_cast<const longlong2 *>(fold.x + (2 * (i64)fold.ell + r) * N + j0);
+                    const longlong2 T2 = *reinterpret_cast<const longlong2 *>(fold.x + t * fold.ct_stride + (2 * (i64)fold.ell + r) * N + j0);
                     xo_x[t] = T2.x, xo_y[t] = T2.y;
                 } else {
                     const i64 *xs = fold.x + t * fold.ct_stride + (i64)r * N + j0 + (i64)fold.ell * N;
@@ -195,8 +197,8 @@
 #pragma unroll
             for (int t = 0; t < NCT; ++t) {
                 if constexpr (PRESUM) {   // Montgomery-form words below 2q
-                    const longlong2 T0 = *reinterpret_cast<const longlong2 *>(fold.x + (i64)r * N + j0);
-                    const longlong2 T1 = *reinterpret_cast<const longlong2 *>(fold.x + pstride + (i64)r * N + j0);
+                    const longlong2 T0 = *reinterpret_cast<const longlong2 *>(fold.x + t * fold.ct_stride + (i64)r * N + j0);
+                    const longlong2 T1 = *reinterpret_cast<const longlong2 *>(fold.x + t * fold.ct_stride + pstride + (i64)r * N + j0);
                     acc[t][0][0] = csub(acc[t][0][0] + mm62u((u64)T0.x, pr, m.q, m.k), m.q2);
                     acc[t][0][1] = csub(acc[t][0][1] + mm62u((u64)T0.y, pr, m.q, m.k), m.q2);
                     acc[t][1][0] = csub(acc[t][1][0] + mm62u((u64)T1.x, pr, m.q, m.k), m.q2);

@@ -53,6 +53,12 @@ int lf_dot_relin(const int64_t *state, int nparts, int rows, int logN, const int
                  const int64_t *T, const int64_t *PR, int ell, const uint8_t *own, const int64_t *q_host, const int64_t *ql,
                  const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st);
 
+int lf_dot_relin_batch(const int64_t *state, int nct, int nparts, int rows, int logN, const int64_t *desc, const int64_t *E,
+                       const double *Ed, const int64_t *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format,
+                       int64_t *tmp, int64_t *s, const int64_t *psi_br, const double *psi_dp, const int64_t *ipsi_br,
+                       const double *ipsi_dp, const int64_t *Ninv, const int64_t *T, const int64_t *PR, int ell, const uint8_t *own,
+                       const int64_t *q_host, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st);
+
 // ckks_ks.hip: the launches of lf_pc_dot that are its own
 int lf_pc_dot_products(int g, const int64_t *x, const int64_t *const *pt, int64_t *S, int rows, int logN, int xpl, int first,
                        const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st);
@@ -152,24 +158,14 @@ int64_t lf_cc_dot_ws_words(const lf_ks_plan *p) {
     return ((int64_t)3 * p->ell) << p->logN;
 }
 
-int lf_cc_dot(const lf_ks_plan *p, int np, const int64_t *const *in, const int64_t *const *row0, const int64_t *ksk,
-              int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format, int64_t *ws, int64_t ws_words, int64_t *out0,
-              int64_t *out1, void *stream) {
-    if (!dot_ok(p) || np < 1 || !in || !row0 || !ksk || !out0 || !out1 || (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES))
-        return LF_ERR_ARG;
-    if (key_format == LF_KEY_PLANES && ((((uintptr_t)ksk | (uintptr_t)(part_stride * 8) | (uintptr_t)(comp_stride * 8)) & 15)))
-        return LF_ERR_ARG;
-    for (int64_t i = 0; i < (int64_t)4 * np; ++i)
-        if (!in[i] || !row0[i]) return LF_ERR_ARG;
-    const int64_t need = lf_cc_dot_ws_words(p);
-    if (need && (!ws || ws_words < need)) return LF_ERR_ARG;
-    const int ell = p->ell, rows = p->ell + p->K, logN = p->logN, dev = p->device;
-    const int64_t N = (int64_t)1 << logN, poly = (int64_t)ell * N;
+// steps 1 and 2 of lf_cc_dot for one dot: the tensor products of its np pairs summed into the triplet T; a copy of T2 into t2
+static int dot_triplet(const lf_ks_plan *p, int np, const int64_t *const *in, const int64_t *const *row0, int64_t *T, int64_t *t2,
+                       void *stream) {
+    const int ell = p->ell, logN = p->logN, dev = p->device;
+    const int64_t poly = (int64_t)ell << logN;
     const int xpl = stack_planes(p);
     const int relaxed_plain = LF_NTT_RELAXED | LF_NTT_PLAIN | (xpl ? LF_NTT_PLANES : 0);
     const int gmax = p->max_nct >= 4 ? 4 : p->max_nct >= 2 ? 2 : 1;
-    if (int e = lf_set_device(dev)) return e;
-    int64_t *T = ws;
     for (int i0 = 0; i0 < np;) {
         const int left = np - i0;
         const int g = left >= 4 && gmax >= 4 ? 4 : left >= 2 && gmax >= 2 ? 2 : 1;
@@ -182,11 +178,31 @@ int lf_cc_dot(const lf_ks_plan *p, int np, const int64_t *const *in, const int64
                 return e;
         }
         // 2. their tensor products into the one triplet; the last launch leaves a copy of T2 where its inverse transform runs
-        if (int e = lf_dot_tensor(g, p->x4, T, i0 + g == np ? p->d2 : nullptr, ell, logN, xpl, i0 == 0, p->ql, p->qh, p->kl, p->kh,
+        if (int e = lf_dot_tensor(g, p->x4, T, i0 + g == np ? t2 : nullptr, ell, logN, xpl, i0 == 0, p->ql, p->qh, p->kl, p->kh,
                                   (hipStream_t)stream))
             return e;
         i0 += g;
     }
+    return 0;
+}
+
+int lf_cc_dot(const lf_ks_plan *p, int np, const int64_t *const *in, const int64_t *const *row0, const int64_t *ksk,
+              int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format, int64_t *ws, int64_t ws_words, int64_t *out0,
+              int64_t *out1, void *stream) {
+    if (!dot_ok(p) || np < 1 || !in || !row0 || !ksk || !out0 || !out1 || (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES))
+        return LF_ERR_ARG;
+    if (key_format == LF_KEY_PLANES && ((((uintptr_t)ksk | (uintptr_t)(part_stride * 8) | (uintptr_t)(comp_stride * 8)) & 15)))
+        return LF_ERR_ARG;
+    for (int64_t i = 0; i < (int64_t)4 * np; ++i)
+        if (!in[i] || !row0[i]) return LF_ERR_ARG;
+    const int64_t need = lf_cc_dot_ws_words(p);
+    if (need && (!ws || ws_words < need)) return LF_ERR_ARG;
+    const int ell = p->ell, rows = p->ell + p->K, logN = p->logN, dev = p->device;
+    const int64_t N = (int64_t)1 << logN;
+    if (int e = lf_set_device(dev)) return e;
+    int64_t *T = ws;
+    // 1., 2. the pairs' tensor products into the one triplet
+    if (int e = dot_triplet(p, np, in, row0, T, p->d2, stream)) return e;
     // 3. T2 -> canonical coefficients (the words lf_intt_mul leaves for one pair), its digits
     if (int e = lf_intt(p->d2, 1, ell, logN, p->ipsi, p->ipsi_dp, p->q_host, p->Ninv, 2, LF_NTT_RELAXED | LF_NTT_PLAIN, p->_2q, p->ql, p->qh,
                         p->kl, p->kh, dev, stream))
@@ -201,6 +217,67 @@ int lf_cc_dot(const lf_ks_plan *p, int np, const int64_t *const *in, const int64
     const int64_t *ss[2] = {p->sum, p->sum + (int64_t)rows * N};
     int64_t *outs[2] = {out0, out1};
     return moddown_any(p, ss, outs, nullptr, 2, 0, nullptr, stream);
+}
+
+/* ---- cc_dot_batch: nd = 1, 2 or 4 independent dots under ONE key (include/ckks_hip.h): lf_cc_dot's launches with everything behind
+ * the tensor products covering all nd summed triplets, the key read once for them. ---- */
+int64_t lf_cc_dot_batch_ws_words(const lf_ks_plan *p, int nd) {
+    if (!dot_ok(p) || !batch_ok(p, nd)) return 0;
+    return ((int64_t)3 * nd * p->ell) << p->logN;
+}
+
+int lf_cc_dot_batch(const lf_ks_plan *p, int nd, const int64_t *np_host, const int64_t *const *in, const int64_t *const *row0,
+                    const int64_t *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format, int64_t *ws,
+                    int64_t ws_words, int64_t *const *out0, int64_t *const *out1, void *stream) {
+    if (!dot_ok(p) || !batch_ok(p, nd) || !np_host || !in || !row0 || !ksk || !out0 || !out1 ||
+        (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES))
+        return LF_ERR_ARG;
+    if (key_format == LF_KEY_PLANES && ((((uintptr_t)ksk | (uintptr_t)(part_stride * 8) | (uintptr_t)(comp_stride * 8)) & 15)))
+        return LF_ERR_ARG;
+    int64_t pairs = 0;
+    for (int d = 0; d < nd; ++d) {
+        if (np_host[d] < 1 || np_host[d] > INT32_MAX || !out0[d] || !out1[d]) return LF_ERR_ARG;
+        pairs += np_host[d];
+    }
+    for (int64_t i = 0; i < 4 * pairs; ++i)
+        if (!in[i] || !row0[i]) return LF_ERR_ARG;
+    const int64_t need = lf_cc_dot_batch_ws_words(p, nd);
+    if (!ws || ws_words < need) return LF_ERR_ARG;
+    if (nd == 1)
+        return lf_cc_dot(p, (int)np_host[0], in, row0, ksk, part_stride, comp_stride, row_off, key_format, ws, ws_words, out0[0], out1[0],
+                         stream);
+    const int ell = p->ell, rows = p->ell + p->K, logN = p->logN, dev = p->device;
+    const int64_t N = (int64_t)1 << logN, poly = (int64_t)ell * N;
+    if (int e = lf_set_device(dev)) return e;
+    // 1., 2. per dot: its pairs' tensor products into its triplet T_d; the copy of T2_d into slot d of plan->d2
+    int64_t first = 0;
+    for (int d = 0; d < nd; ++d) {
+        if (int e = dot_triplet(p, (int)np_host[d], in + 4 * first, row0 + 4 * first, ws + d * 3 * poly, p->d2 + d * poly, stream)) return e;
+        first += np_host[d];
+    }
+    // 3. the nd copies -> canonical coefficients in one inverse transform, their digits in one launch
+    if (int e = lf_intt(p->d2, nd, ell, logN, p->ipsi, p->ipsi_dp, p->q_host, p->Ninv, 2, LF_NTT_RELAXED | LF_NTT_PLAIN, p->_2q, p->ql, p->qh,
+                        p->kl, p->kh, dev, stream))
+        return e;
+    const int64_t *srcs[4];
+    int64_t *states[4];
+    for (int d = 0; d < nd; ++d) srcs[d] = p->d2 + d * poly, states[d] = p->state + d * poly;
+    if (int e = lf_ks_digits_batch(srcs, states, nd, p->dig_nparts, p->dig_desc, p->dig_tab, N, 0, nullptr, p->ql, p->qh, p->kl, p->kh, dev,
+                                   stream))
+        return e;
+    // 4. the key switch of the nd T2 with P T0, P T1 folded into their sums: every key word read once for all of them
+    if (int e = lf_dot_relin_batch(p->state, nd, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, ksk, part_stride, comp_stride, row_off,
+                                   key_format, p->ext, p->sum, p->psi, p->psi_dp, p->ipsi, p->ipsi_dp, p->Ninv, ws, p->PR, ell, p->own,
+                                   p->q_host, p->ql, p->qh, p->kl, p->kh, (hipStream_t)stream))
+        return e;
+    // 5. one mod-down of the 2 nd sums, no addend
+    const int64_t *ss[8];
+    int64_t *outs[8];
+    for (int d = 0; d < nd; ++d) {
+        ss[2 * d] = p->sum + (int64_t)(2 * d) * rows * N, ss[2 * d + 1] = p->sum + (int64_t)(2 * d + 1) * rows * N;
+        outs[2 * d] = out0[d], outs[2 * d + 1] = out1[d];
+    }
+    return moddown_any(p, ss, outs, nullptr, 2 * nd, 0, nullptr, stream);
 }
 
 /* ---- pc_dot: sum_i pt_i * ct_i (+ bias) for plaintexts encoded once, under ONE rescale (include/ckks_hip.h).  Plan-free, like

@@ -413,6 +413,22 @@ class HipBackend:
         check(lib.lf_cc_dot(ctypes.byref(plan), len(ins) // 4, ins, row0s, base, ps, cs, row_off, self._kfmt(key), _p(ws),
                             0 if ws is None else ws.numel(), out.data_ptr(), out.data_ptr() + out.stride(0) * 8, st), "lf_cc_dot")
 
+    @staticmethod
+    def cc_dot_batch_ws_words(plan, nd):
+        return int(lib.lf_cc_dot_batch_ws_words(ctypes.byref(plan), nd))
+
+    def cc_dot_batch_native(self, plan, np_list, ins, row0s, key, first_part, row_off, outs, ws):
+        """len(np_list) in (1, 2, 4) <= plan.max_nct dots under one key as ONE native call (lf_cc_dot_batch).  np_list: the pair
+        count of each dot; ins / row0s: ctypes arrays of 4 device pointers per pair, in cc_mult_evk's order, dot after dot;
+        outs: one [2, ell, N] tensor per dot; ws: at least cc_dot_batch_ws_words(plan, len(np_list)) words (the summed triplets)."""
+        dev, st = _ds(outs[0])
+        base, ps, cs = self._key_args(key, first_part)
+        nd = len(np_list)
+        nps = (ctypes.c_int64 * nd)(*np_list)
+        check(lib.lf_cc_dot_batch(ctypes.byref(plan), nd, nps, ins, row0s, base, ps, cs, row_off, self._kfmt(key), _p(ws),
+                                  0 if ws is None else ws.numel(), _parr([o[0] for o in outs]), _parr([o[1] for o in outs]), st),
+              "lf_cc_dot_batch")
+
     # include/ckks_hip.h: LF_WSUM_MAX_TERMS / LF_WSUM_MAX_OUTPUTS (tests/test_poly_eval_cpu.py holds these copies to the header)
     wsum_max_terms = 16
     wsum_max_outputs = 64

@@ -1328,18 +1328,8 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps):
             return torch.as_strided(t0, (len(ts),) + tuple(t0.shape), (t0.numel(),) + tuple(t0.stride()))
         return None
 
-    def cc_dot(self, pairs: list, evk: data_struct, relin=True) -> data_struct:
-        """sum of a_i * b_i over the ciphertext pairs (a_i, b_i) as ONE ciphertext at level + 1, under one relinearisation
-        ("lazy relinearisation"; the reference has no such entry).  Everything of a cc_mult but the tensor product is linear in
-        the triplet (d0, d1, d2), so the triplets are summed and the inverse transforms, the digits, the key switch and the
-        mod-down run once, on the sum: one key stream and one key-switch noise instead of len(pairs).  The result has exactly the
-        words of
-            t = cc_mult(a_0, b_0, evk, relin=False); t = cc_add_triplet(t, cc_mult(a_i, b_i, evk, relin=False)) for i >= 1;
-            relinearize(t, evk)                      (relin=False: t itself)
-        which is also what runs where the native call does not apply (several devices or ranks, logN outside 13..17, a checker
-        backend, relin=False).  One native call (lf_cc_dot) where every limb of both levels is on one device of this process.
-        All operands: ciphertexts of one level, coefficient domain, no special limbs; the same object may appear in any number
-        of pairs and on both sides of one."""
+    def _cc_dot_pairs(self, pairs):
+        """cc_dot's argument checks: (the pairs as a list of tuples, their level)."""
         pairs = [tuple(p) for p in pairs]
         if not pairs:
             raise ValueError("cc_dot: at least one pair of ciphertexts")
@@ -1356,25 +1346,53 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps):
                     raise errors.NotMatchDataStructState(origin=f"{ct.origin} at level {ct.level} beside level {l}")
                 if ct.ntt_state or ct.include_special:
                     raise errors.NotMatchDataStructState(origin=ct.origin)
-        level = l + 1
-        if level >= self.num_levels:
+        if l + 1 >= self.num_levels:
             raise errors.MaximumLevelError(level=l, level_max=self.num_levels)
+        return pairs, l
+
+    def _cc_dot_device(self, pairs, level):
+        """The device on which a relinearising cc_dot of `pairs` INTO `level` is one native call; None: the composition runs."""
         d = self._native_level(level)
-        if relin and d is not None and self._native_level(l) == d and hasattr(self.backend, "cc_dot_native") \
+        if d is not None and self._native_level(level - 1) == d and hasattr(self.backend, "cc_dot_native") \
                 and getattr(self.backend, "relin_fold", False) \
                 and all(t.is_contiguous() and t.dtype == torch.int64 for a, b in pairs for ct in (a, b) for t in (ct.data[0][0], ct.data[1][0])):
+            return d
+        return None
+
+    def _cc_dot_pointers(self, pairs):
+        """(in, row0) of lf_cc_dot: four device pointers per pair, in cc_mult_evk's order."""
+        N, k = self.ctx.N, len(pairs)
+        ins, row0s = (ctypes.c_void_p * (4 * k))(), (ctypes.c_void_p * (4 * k))()
+        i = 0
+        for a, b in pairs:
+            for ct in (a, b):
+                for comp in range(2):
+                    ptr = ct.data[comp][0].data_ptr()
+                    row0s[i], ins[i] = ptr, ptr + N * 8      # the dropped limb is the first row; the survivors follow it
+                    i += 1
+        return ins, row0s
+
+    def cc_dot(self, pairs: list, evk: data_struct, relin=True) -> data_struct:
+        """sum of a_i * b_i over the ciphertext pairs (a_i, b_i) as ONE ciphertext at level + 1, under one relinearisation
+        ("lazy relinearisation"; the reference has no such entry).  Everything of a cc_mult but the tensor product is linear in
+        the triplet (d0, d1, d2), so the triplets are summed and the inverse transforms, the digits, the key switch and the
+        mod-down run once, on the sum: one key stream and one key-switch noise instead of len(pairs).  The result has exactly the
+        words of
+            t = cc_mult(a_0, b_0, evk, relin=False); t = cc_add_triplet(t, cc_mult(a_i, b_i, evk, relin=False)) for i >= 1;
+            relinearize(t, evk)                      (relin=False: t itself)
+        which is also what runs where the native call does not apply (several devices or ranks, logN outside 13..17, a checker
+        backend, relin=False).  One native call (lf_cc_dot) where every limb of both levels is on one device of this process.
+        All operands: ciphertexts of one level, coefficient domain, no special limbs; the same object may appear in any number
+        of pairs and on both sides of one."""
+        pairs, l = self._cc_dot_pairs(pairs)
+        level = l + 1
+        d = self._cc_dot_device(pairs, level) if relin else None
+        if d is not None:
             N, k = self.ctx.N, len(pairs)
             sizes = getattr(self.backend, "ks_batch_sizes", ())
             nct = next((n for n in sizes if n <= k), 1)     # pairs per launch of the tensor products: the plan's operand stacks
             plan, _, first_part, row_off = self._op_plan(level, d, nct)
-            ins, row0s = (ctypes.c_void_p * (4 * k))(), (ctypes.c_void_p * (4 * k))()
-            i = 0
-            for a, b in pairs:
-                for ct in (a, b):
-                    for comp in range(2):
-                        ptr = ct.data[comp][0].data_ptr()
-                        row0s[i], ins[i] = ptr, ptr + N * 8      # the dropped limb is the first row; the survivors follow it
-                        i += 1
+            ins, row0s = self._cc_dot_pointers(pairs)
             kpack = self._key_pack(evk)[self._loc(0, special=True).index(d)]
             ws = self._ws("dot_ws", (self.backend.cc_dot_ws_words(plan),), d)
             out = torch.empty((2, plan.ell, N), dtype=torch.int64, device=self.ntt.devices[d])
@@ -1384,6 +1402,52 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps):
         for a, b in pairs[1:]:
             t = self.cc_add_triplet(t, self.cc_mult(a, b, evk, relin=False))
         return self.relinearize(t, evk) if relin else t
+
+    def cc_dot_batch(self, dots: list, evk: data_struct) -> list:
+        """cc_dot of several lists of ciphertext pairs under one evaluation key: returns [cc_dot(pairs, evk) for pairs in dots],
+        bit for bit (the recombinations of a polynomial evaluated on many ciphertexts: poly_eval_batch).  Argument checks per
+        dot are cc_dot's; dots may sit at different levels and are grouped by level.  On one GPU, groups of 4 and then 2 dots
+        of a level go through ONE native call each (lf_cc_dot_batch): the tensor products run per dot, as in cc_dot, and
+        everything behind them — the inverse transforms, the digits, their extension, the inner product with the key (read once
+        per group: ks_dotb_inner_kernel), the sums' inverse transforms and the mod-down — covers the group's summed triplets
+        at once.  A leftover single dot goes through cc_dot, and so does every dot for which cc_dot itself would not go native
+        (several devices or ranks, a checker backend, operands that are not contiguous, relin_fold off, logN outside 13..17)."""
+        dots = [self._cc_dot_pairs(pairs) for pairs in dots]
+        out = [None] * len(dots)
+        sizes = getattr(self.backend, "ks_batch_sizes", ())
+        groups = {}
+        for i, (pairs, l) in enumerate(dots):
+            d = self._cc_dot_device(pairs, l + 1) if sizes and hasattr(self.backend, "cc_dot_batch_native") else None
+            if d is not None:
+                groups.setdefault((l + 1, d), []).append(i)
+            else:
+                out[i] = self.cc_dot(pairs, evk)
+        for (level, d), idx in groups.items():
+            jobs, slots, pos = [], [], 0
+            while pos < len(idx):
+                n = next((k for k in sizes if k <= len(idx) - pos), 1)
+                sel = idx[pos:pos + n]
+                if n == 1:
+                    jobs.append(lambda sel=sel: [self.cc_dot(dots[sel[0]][0], evk)])
+                else:
+                    jobs.append(lambda sel=sel, level=level, d=d: self._cc_dot_group([dots[i][0] for i in sel], evk, level, d))
+                slots.append(sel)
+                pos += n
+            for sel, res in zip(slots, self._run_groups(jobs, d, lambda level=level: self._prepare_ks(evk, level))):
+                for i, r in zip(sel, res):
+                    out[i] = r
+        return out
+
+    def _cc_dot_group(self, dots, evk, level, d):
+        """len(dots) in (2, 4) dots INTO `level` on device d as ONE native call (lf_cc_dot_batch); one allocation per output."""
+        N, nd = self.ctx.N, len(dots)
+        plan, _, first_part, row_off = self._op_plan(level, d, nd)
+        ins, row0s = self._cc_dot_pointers([pair for pairs in dots for pair in pairs])
+        kpack = self._key_pack(evk)[self._loc(0, special=True).index(d)]
+        ws = self._ws("dot_batch_ws", (self.backend.cc_dot_batch_ws_words(plan, nd),), d)
+        outs = [torch.empty((2, plan.ell, N), dtype=torch.int64, device=self.ntt.devices[d]) for _ in range(nd)]
+        self.backend.cc_dot_batch_native(plan, [len(pairs) for pairs in dots], ins, row0s, kpack, first_part, row_off, outs, ws)
+        return [self._new(([o[0]], [o[1]]), types.origins["ct"], level=level) for o in outs]
 
     # =============================================================================================
     # hybrid key switching (eng.py:654-961)

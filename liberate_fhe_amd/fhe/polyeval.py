@@ -172,6 +172,27 @@ class PolyOps:
     def _at_level(self, ct, level):
         return ct if ct.level == level else self.level_up(ct, level)
 
+    def _power_tree_batch(self, trees: list, top: int, evk, cheb: bool):
+        """_power_tree on one dictionary per ciphertext, walked once: the squares of a step, and the products of one hi, of ALL
+        ciphertexts share one cc_mult_batch (whose results are cc_mult's, bit for bit)."""
+        hi = 1
+        while 2 * hi <= top:
+            sqs = self.cc_mult_batch([(t[hi], t[hi]) for t in trees], evk)
+            for t, sq in zip(trees, sqs):
+                t[2 * hi] = self.add_scalar(self.mult_int_scalar(sq, 2), -1) if cheb else sq
+            hi *= 2
+        hi = 2
+        while hi < top:
+            los = [b - hi for b in range(hi + 1, min(2 * hi, top + 1))]
+            if los:
+                prods = self.cc_mult_batch([self.auto_level(t[hi], t[lo]) for t in trees for lo in los], evk)
+                for i, t in enumerate(trees):
+                    for j, lo in enumerate(los):
+                        p = prods[i * len(los) + j]
+                        t[hi + lo] = self.auto_cc_sub(self.mult_int_scalar(p, 2), t[hi - lo]) if cheb else p
+            hi *= 2
+        return trees
+
     def poly_eval(self, ct, coeffs, evk, basis="power", interval=None, n1=None):
         """p(ct) for p = sum_i coeffs[i] x^i (basis="power") or sum_i coeffs[i] T_i((2x - a - b) / (b - a)) (basis="chebyshev",
         interval=(a, b), default (-1, 1)), degree d = len(coeffs) - 1 >= 1, by Paterson-Stockmeyer: with n1 a power of two
@@ -226,3 +247,66 @@ class PolyOps:
         Lc = base + sched["common"]
         r = self.cc_dot([(self._at_level(q[g], Lc), self._at_level(ys[g], Lc)) for g in range(1, G)], evk)
         return self.cc_add(r, self.level_up(q[0], Lc + 1))
+
+    def poly_eval_batch(self, cts: list, coeffs, evk, basis="power", interval=None, n1=None) -> list:
+        """The same polynomial on B ciphertexts of one level (an activation over a layer's outputs): returns
+        [poly_eval(ct, coeffs, evk, basis, interval, n1) for ct in cts], bit for bit.  poly_eval's schedule, walked once for all B
+        ciphertexts, so that the key is streamed once per group of up to 4 ciphertexts instead of once per ciphertext:
+          chebyshev, interval != (-1, 1):  the change of variable per ciphertext, as poly_eval makes it
+          babies: every square p_2h = square(p_h) of all B ciphertexts in ONE cc_mult_batch per step h, every product
+              p_hi * p_{b - hi} of one hi of all B ciphertexts in ONE cc_mult_batch; the Chebyshev corrections and the level_ups per
+              ciphertext
+          q_g: weighted_sums per ciphertext (the sets share nothing: a batched entry would only save launches)
+          giants: y = p_n1 from p_{n1 / 2} in ONE cc_mult_batch of B squares, y^g by the same batched tree
+          r = cc_dot_batch of B dots [(q_g, y^g) g >= 1], ONE call;  result = cc_add(r, level_up(q_0, L_c + 1)) per ciphertext;
+          G = 1: q_0, no dot.
+        cc_mult_batch and cc_dot_batch return the words of cc_mult and cc_dot, so each result has the words of poly_eval's
+        composition.  An empty list: ValueError; ciphertexts of different levels: NotMatchDataStructState; the other refusals are
+        poly_eval's, before any work."""
+        cts = list(cts)
+        if not cts:
+            raise ValueError("poly_eval_batch: at least one ciphertext")
+        for ct in cts:
+            if not is_struct(ct) or ct.origin != types.origins["ct"]:
+                raise errors.NotMatchType(origin=getattr(ct, "origin", type(ct).__name__), to=types.origins["ct"])
+        base = cts[0].level
+        for ct in cts:
+            if ct.level != base:
+                raise errors.NotMatchDataStructState(origin=f"{ct.origin} at level {ct.level} beside level {base}")
+            if ct.ntt_state or ct.include_special:
+                raise errors.NotMatchDataStructState(origin=ct.origin)
+        c = np.asarray(coeffs, dtype=np.float64)
+        if c.ndim != 1 or c.size < 2:
+            raise ValueError("poly_eval: coefficients of a polynomial of degree >= 1")
+        d = c.size - 1
+        depth = self.poly_depth(d, basis, interval, n1)
+        if base + depth >= self.num_levels:
+            raise errors.MaximumLevelError(level=base, level_max=self.num_levels)
+        cheb = basis == "chebyshev"
+        if not cheb and interval is not None:
+            raise ValueError("poly_eval: an interval belongs to basis='chebyshev'; the power basis has no change of variable")
+        n1 = encdec.poly_split(d) if n1 is None else int(n1)
+        sched = encdec.poly_schedule(d, n1)
+        G = sched["G"]
+        if cheb:
+            blocks = encdec.cheb_blocks(c, n1)
+            if interval is not None and tuple(interval) != (-1, 1):
+                a, b = (float(v) for v in interval)
+                cts = [self.add_scalar(self.mult_scalar(ct, 2.0 / (b - a)), -(a + b) / (b - a)) for ct in cts]
+        else:
+            padded = np.concatenate([c, np.zeros(G * n1 - c.size)])
+            blocks = padded.reshape(G, n1)
+        base = cts[0].level
+        trees = self._power_tree_batch([{1: ct} for ct in cts], n1 - 1, evk, cheb)
+        Lb = base + sched["baby"]
+        qs = [self.weighted_sums([self._at_level(t[b], Lb) for b in range(1, n1)], blocks[:, 1:], consts=blocks[:, 0]) for t in trees]
+        if G == 1:
+            return [q[0] for q in qs]
+        ys = self.cc_mult_batch([(t[n1 // 2], t[n1 // 2]) for t in trees], evk)
+        if cheb:
+            ys = [self.add_scalar(self.mult_int_scalar(y, 2), -1) for y in ys]
+        giants = self._power_tree_batch([{1: y} for y in ys], G - 1, evk, False)
+        Lc = base + sched["common"]
+        rs = self.cc_dot_batch([[(self._at_level(q[g], Lc), self._at_level(yt[g], Lc)) for g in range(1, G)]
+                                for q, yt in zip(qs, giants)], evk)
+        return [self.cc_add(r, self.level_up(q[0], Lc + 1)) for r, q in zip(rs, qs)]

@@ -568,6 +568,29 @@ int lf_linear_transform(const lf_ks_plan *plan, const int64_t *c0, const int64_t
                         const int64_t *pt, int64_t pt_stride, const int64_t *pt0, const int64_t *rescale_scales, int64_t round_at,
                         int64_t *ws, int64_t ws_words, int64_t *out0, int64_t *out1, void *stream);
 
+/* Rotation sum: out = moddown(sum_i (ks_i + P c0(X^p_i)) [+ P (c0, c1)]), the ciphertext that decrypts to sum_i rot(m, step_i)
+ * [+ m] at the SAME level as (c0, c1): lf_linear_transform without the diagonals and without the rescale.  nr >= 0 keys with odd
+ * exponents p_host[i] < 2N (HOST arrays as lf_rotate_hoisted; a key may repeat, p = 1 is legal, and so is the conjugation's
+ * p = 2N - 1 with its key); with_self != 0 adds the ciphertext itself, which needs no key (nr = 0 with with_self is legal).
+ * Addition commutes with the mod-down, so the key-switch sums of all rotations are added while still in the NTT domain over Q P
+ * and everything behind the inner product happens once.  The result has exactly the words of: c0, c1 made canonical; E = per
+ * digit pre_extend(c1), extend, exact forward NTT; c^ = P * enter_ntt(c) on the ordinary rows; per key t_c = sum over the digits
+ * of E gathered by pi_{p_i} times the key part (mont_mult, mont_add), t_0 += c^0 gathered by pi_{p_i} on the ordinary rows; self
+ * term: t_c = c^c, zero on the special rows; S_c = sum of the t_c; intt_exit_reduce, mod-down (no addend).  Only the residues of
+ * S_c reach the result, so the kernel is free in the order of its additions and uses the relaxed arithmetic of the other fused ops.
+ * Enqueued: a canonical copy of c0 (and of c1 with with_self), ONE forward NTT of it (enter_ntt) on the ell ordinary rows and the
+ * product with plan->PR; lf_ks_digits_galois (gal_pinv = 1) and lf_ks_fwd once (nr > 0); per group of 4, 2 or 1 keys one launch
+ * of ks_inner_rsum_kernel, all groups adding into the ONE pair plan->sum (nr = 0: one launch without keys); one inverse NTT of
+ * the pair (its planes pass through plan->ext, which is spent by then); one mod-down without addend straight into out0 / out1
+ * [ell][N], canonical.  No rescale.  P c^ lives in plan->x4 (free during this op) or, with plan->x4 = NULL, in `ws` of at least
+ * lf_rotate_sum_ws_words(plan) words (0: ws may be NULL).
+ * LF_ERR_ARG before any launch for everything lf_rotate_hoisted refuses (nr < 0 instead of nr < 1), nr = 0 without with_self,
+ * plan->PR = NULL and a workspace too small. */
+int64_t lf_rotate_sum_ws_words(const lf_ks_plan *plan);
+int lf_rotate_sum(const lf_ks_plan *plan, const int64_t *c0, const int64_t *c1, int nr, const int64_t *p_host,
+                  const int64_t *const *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format,
+                  int with_self, int64_t *ws, int64_t ws_words, int64_t *out0, int64_t *out1, void *stream);
+
 /* Linear transform by the diagonal method in its baby-step / giant-step form: out decrypts to
  *     sum_g rot( sum_b diag_{g+b}(rolled by -g) * rot(m, b), g )        b = step mod n1, g = step - b,
  * so that k diagonals need about n1 + k / n1 rotation keys (and key streams) instead of k.  nb >= 0 baby keys with odd

@@ -1112,6 +1112,153 @@ __global__ void __launch_bounds__(256) ks_inner_lt_kernel(const i64 *__restrict_
     }
 }
 
+// ---- K3 of a rotation sum (lf_rotate_sum): sum_i (key switch sums of rotation i + P c0(X^p_i)) [+ P (c0, c1)] in Q P ------------
+// ks_inner_lt_kernel without the diagonals: the same grid, pi computation and key / digit formats, and ONE accumulator pair per
+// thread for the whole group — the digits x key products of all NR keys go into the same acc[2][2]; on the ordinary rows c^0
+// gathered by each pi_{p_i} joins component 0.  The first group adds the self term P (c^0, c^1), ungathered, on the ordinary
+// rows when asked to (self); later groups add the pair the previous group left in `s`.  The pair leaves in the format the sums'
+// inverse pass reads (spl).  Only residues reach the result, so the additions come in the order that suits the loads.
+// fp64 class: the accumulator takes NR nparts balanced products (|.| <= q / 2 each), NR gathered words of c^0 and one word of
+// c^ (all below 2q) or of the previous pair (canonical, below q): NR nparts + NR + 2 terms, |acc| <= (NR nparts / 2 + 2 NR + 2) q.
+// With NR = 4 that passes dp_reduce's 64 q from nparts = 27 on, and LF_FP64_MAX_DIGITS allows 119: (238 + 10) q < 2^8 q < 2^49.
+// So the sum is first brought to a balanced residue by dp_reduce_bal (exact for |x| < 2^52; every partial sum is an integer
+// below 2^49, exact in fp64) and that residue, |.| <= q / 2, goes through dp_reduce: two more fp64 instructions per word, once.
+struct RsumArgs {
+    HoistKeys hk;
+    const i64 *chat;     // P NTT(c0), P NTT(c1): [2][ell][N], Montgomery form, words below 2q (c1 is read for the self term only)
+    int ell;             // ordinary rows (the first `ell` of the rows)
+    int first;           // first group: `s` is not read
+    int self;            // the first group adds P (c^0, c^1) on the ordinary rows
+};
+
+template <int NR, bool PLANES, bool DPL>
+__global__ void __launch_bounds__(256) ks_inner_rsum_kernel(const i64 *__restrict__ ext, RsumArgs ra, i64 part_stride, i64 comp_stride,
+                                                            i64 row_off, i64 *__restrict__ s, int nparts, int rows, int logN, int spl,
+                                                            const i64 *__restrict__ ql, const i64 *__restrict__ qh,
+                                                            const i64 *__restrict__ kl, const i64 *__restrict__ kh) {
+    constexpr int NA = NR ? NR : 1;
+    const int r = blockIdx.y;
+    const i64 N = (i64)1 << logN;
+    const i64 j0 = (i64)blockIdx.x * 512 + threadIdx.x * 2;
+    if (j0 >= N) return;
+    const RowMod m = load_mod(ql, qh, kl, kh, r);
+    const unsigned sh = 32u - (unsigned)logN, mask = (2u << logN) - 1u;
+    const unsigned bj = (2u * (__builtin_bitreverse32((unsigned)j0) >> sh) + 1u);
+    unsigned src[NA];
+    bool sw[NA];
+#pragma unroll
+    for (int i = 0; i < NR; ++i) {
+        const unsigned t = (bj * ra.hk.p[i]) & mask;
+        const unsigned mi = __builtin_bitreverse32((t - 1u) >> 1) >> sh;
+        src[i] = mi & ~1u;
+        sw[i] = (mi & 1u) != 0;
+    }
+    const i64 krow = (row_off + r) * N;
+    const bool ord = r < ra.ell;
+    const i64 *c0row = ra.chat + (i64)r * N, *c1row = c0row + (i64)ra.ell * N;   // (read on ordinary rows only)
+    i64 *srow0 = s + (i64)r * N, *srow1 = s + ((i64)rows + r) * N;
+    if (m.q < SMALL_PRIME_LIMIT) {
+        const RowDp d = make_dp(m);
+        double acc[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
+#pragma unroll KI_UNROLL
+        for (int p = 0; p < nparts; ++p) {
+            const i64 *er = ext + ((i64)p * rows + r) * N;
+#pragma unroll
+            for (int i = 0; i < NR; ++i) {
+                double xa, xb;
+                ld_pair_dp(er, (i64)src[i], N, DPL ? 1 : 0, xa, xb);
+                const double x0 = sw[i] ? xb : xa, x1 = sw[i] ? xa : xb;
+                const i64 *kr = ra.hk.ksk[i] + krow + (i64)p * part_stride;
+                double k0x, k0y, k1x, k1y;
+                if (PLANES) {   // 16 + 8 bytes for both components (see lf_key_planes)
+                    const lf_u4_t l = __builtin_nontemporal_load(reinterpret_cast<const lf_u4_t *>(reinterpret_cast<const unsigned *>(kr) + 2 * j0));
+                    const lf_u2_t h = __builtin_nontemporal_load(reinterpret_cast<const lf_u2_t *>(reinterpret_cast<const unsigned *>(kr + comp_stride) + j0));
+                    k0x = dp_from_planes(l.x, h.x & 0xffffu), k0y = dp_from_planes(l.y, h.x >> 16);
+                    k1x = dp_from_planes(l.z, h.y & 0xffffu), k1y = dp_from_planes(l.w, h.y >> 16);
+                } else {
+                    const longlong2 k0 = ld_nt(kr + j0);
+                    const longlong2 k1 = ld_nt(kr + j0 + comp_stride);
+                    k0x = dp_from_word(k0.x), k0y = dp_from_word(k0.y), k1x = dp_from_word(k1.x), k1y = dp_from_word(k1.y);
+                }
+                acc[0][0] += dp_mulmod_bal(x0, k0x, d);
+                acc[0][1] += dp_mulmod_bal(x1, k0y, d);
+                acc[1][0] += dp_mulmod_bal(x0, k1x, d);
+                acc[1][1] += dp_mulmod_bal(x1, k1y, d);
+            }
+        }
+        if (!ra.first) {   // the pair the previous group left (canonical words)
+            double a0, b0, a1, b1;
+            ld_pair_dp(srow0, j0, N, spl, a0, b0);
+            ld_pair_dp(srow1, j0, N, spl, a1, b1);
+            acc[0][0] += a0, acc[0][1] += b0, acc[1][0] += a1, acc[1][1] += b1;
+        } else if (ra.self && ord) {
+            double a0, b0, a1, b1;
+            ld_pair_dp(c0row, j0, N, 0, a0, b0);
+            ld_pair_dp(c1row, j0, N, 0, a1, b1);
+            acc[0][0] += a0, acc[0][1] += b0, acc[1][0] += a1, acc[1][1] += b1;
+        }
+        if (ord) {
+#pragma unroll
+            for (int i = 0; i < NR; ++i) {
+                double ca, cb;
+                ld_pair_dp(c0row, (i64)src[i], N, 0, ca, cb);
+                acc[0][0] += sw[i] ? cb : ca;
+                acc[0][1] += sw[i] ? ca : cb;
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            longlong2 o;
+            o.x = dp_to_word(dp_reduce(dp_reduce_bal(acc[c][0], d), d.q, d.qinv));
+            o.y = dp_to_word(dp_reduce(dp_reduce_bal(acc[c][1], d), d.q, d.qinv));
+            i64 *srow = c ? srow1 : srow0;
+            if (spl) {
+                const lf_u2_t l = {(unsigned)o.x, (unsigned)o.y};
+                *reinterpret_cast<lf_u2_t *>(reinterpret_cast<unsigned *>(srow) + j0) = l;
+                *reinterpret_cast<unsigned *>(reinterpret_cast<unsigned short *>(srow + (N >> 1)) + j0) =
+                    (unsigned)((u64)o.x >> 32) | ((unsigned)((u64)o.y >> 32) << 16);
+            } else {
+                *reinterpret_cast<longlong2 *>(srow + j0) = o;
+            }
+        }
+    } else {
+        i64 acc[2][2] = {{0, 0}, {0, 0}};   // lazy words below 2q throughout
+        for (int p = 0; p < nparts; ++p) {
+            const i64 *er = ext + ((i64)p * rows + r) * N;
+#pragma unroll
+            for (int i = 0; i < NR; ++i) {
+                const longlong2 v = *reinterpret_cast<const longlong2 *>(er + src[i]);
+                const u64 x0 = (u64)(sw[i] ? v.y : v.x), x1 = (u64)(sw[i] ? v.x : v.y);
+                const i64 *kr = ra.hk.ksk[i] + krow + (i64)p * part_stride + j0;
+                const longlong2 k0 = ld_nt(kr);
+                const longlong2 k1 = ld_nt(kr + comp_stride);
+                acc[0][0] = csub(acc[0][0] + mm62u(x0, (u64)k0.x, m.q, m.k), m.q2);
+                acc[0][1] = csub(acc[0][1] + mm62u(x1, (u64)k0.y, m.q, m.k), m.q2);
+                acc[1][0] = csub(acc[1][0] + mm62u(x0, (u64)k1.x, m.q, m.k), m.q2);
+                acc[1][1] = csub(acc[1][1] + mm62u(x1, (u64)k1.y, m.q, m.k), m.q2);
+            }
+        }
+        if (!ra.first || (ra.self && ord)) {   // the previous group's pair, or the self term (both below 2q)
+            const i64 *a = ra.first ? c0row : srow0, *b = ra.first ? c1row : srow1;
+            const longlong2 va = *reinterpret_cast<const longlong2 *>(a + j0), vb = *reinterpret_cast<const longlong2 *>(b + j0);
+            acc[0][0] = csub(acc[0][0] + va.x, m.q2), acc[0][1] = csub(acc[0][1] + va.y, m.q2);
+            acc[1][0] = csub(acc[1][0] + vb.x, m.q2), acc[1][1] = csub(acc[1][1] + vb.y, m.q2);
+        }
+        if (ord) {
+#pragma unroll
+            for (int i = 0; i < NR; ++i) {
+                const longlong2 v = *reinterpret_cast<const longlong2 *>(c0row + src[i]);
+                acc[0][0] = csub(acc[0][0] + (sw[i] ? v.y : v.x), m.q2);
+                acc[0][1] = csub(acc[0][1] + (sw[i] ? v.x : v.y), m.q2);
+            }
+        }
+        longlong2 o0, o1;
+        o0.x = acc[0][0], o0.y = acc[0][1], o1.x = acc[1][0], o1.y = acc[1][1];
+        *reinterpret_cast<longlong2 *>(srow0 + j0) = o0;
+        *reinterpret_cast<longlong2 *>(srow1 + j0) = o1;
+    }
+}
+
 // ---- baby-step / giant-step linear transform (lf_linear_transform_bsgs): y = sum_g rot(sum_b pt_{g,b} * rot(x, b), g) ------------
 // Three launches on the grid, the pi computation and the key / digit formats of the two kernels above, under names of their own:
 //   ks_inner_baby_kernel     per group of 4 / 2 / 1 baby keys the gathered sums over the digits, + P c0 gathered on the ordinary
@@ -1454,6 +1601,8 @@ bool digit_planes(int logN, const RowList &dp, const RowList &in) {
 //     kernel (it reduces there with dp_reduce_bal, |x| < 2^52, and its running pair stays within (NR + 2) q)
 //   ks_inner_giant_kernel                  a word of S^g_0 and one of the accumulator, both below 2q
 //                                                                                     nparts / 2 + 4 < 64:  nparts <= 119
+//   ks_inner_rsum_kernel                   NR nparts products, NR + 1 words below 2q: reduced first with dp_reduce_bal
+//                                          (|x| < 2^52), so no bound of its own below 119 (see the kernel)
 // The tightest holds for all of them.  Integer-class rows reduce after every addition and have no such bound.
 bool lf_fp64_digits_ok(int nparts, int rows, const int64_t *q_host) {
     if (nparts <= LF_FP64_MAX_DIGITS || !q_host) return true;
@@ -1886,6 +2035,64 @@ int lf_ks_tail_lt(int nr, const int64_t *p_host, int nparts, int rows, int ell, 
     }
 #undef LF_LT_LAUNCH
 #undef LF_LT_CASE
+    return ks_inv_sums(2, rows, logN, spl, cols_last, mixed, in, dp, (i64 *)scratch, (i64 *)s, ipsi_br, ipsi_dp, Ninv, ql, qh, kl, kh, st);
+}
+
+// The key-dependent part of lf_rotate_sum (ckks_ops.hip): per group of up to 4 keys ONE launch of ks_inner_rsum_kernel over the
+// shared extended digits `ext` (nr = 0: the self term alone, one launch without keys), all of them adding into the one pair of
+// sums s [2][rows][N]; then the inverse transform of that pair.  `scratch` as in lf_ks_tail_lt.  chat = P NTT(c0), P NTT(c1) on
+// the `ell` ordinary rows (c1 only with `with_self`).  Internal: ckks_ops.hip checks the arguments (nr >= 0, odd exponents below
+// 2N, with_self when nr == 0).
+int lf_ks_tail_rsum(int nr, const int64_t *p_host, int nparts, int rows, int ell, int logN, const int64_t *const *ksk, int64_t part_stride,
+                    int64_t comp_stride, int64_t row_off, int key_format, int with_self, const int64_t *chat, const int64_t *ext,
+                    int64_t *s, int64_t *scratch, int64_t scratch_words, const int64_t *ipsi_br, const double *ipsi_dp,
+                    const int64_t *Ninv, const int64_t *q_host, const int64_t *ql, const int64_t *qh, const int64_t *kl,
+                    const int64_t *kh, hipStream_t st) {
+    if (!ipsi_dp || (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES) || nr < 0 || (nr == 0 && !with_self) || !chat || ell < 0 ||
+        ell > rows || (nr && (!ksk || !p_host)))
+        return LF_ERR_ARG;
+    if (rows < 1 || rows > MAX_LIST_ROWS || !lf_fp64_digits_ok(nparts, rows, q_host)) return LF_ERR_ARG;
+    for (int i = 0; i < nr; ++i)
+        if (!ksk[i] || (key_format == LF_KEY_PLANES && ((((uintptr_t)ksk[i] | (uintptr_t)(part_stride * 8) | (uintptr_t)(comp_stride * 8)) & 15))))
+            return LF_ERR_ARG;
+    const int tl = NTT_TILE_LOG_MAX, S1 = logN - tl;
+    RowList dp, in;
+    classify_rows(rows, q_host, dp, in);
+    const bool mixed = dp.n && in.n;
+    const bool dplanes = digit_planes(logN, dp, in);
+    const bool cols_last = S1 <= 4 || (S1 == 5 && mixed && g_ks_ext_cols_max > 4);
+    if (nr)   // the digits must be in the format the groups read (see ks_tail)
+        if (int e = lf_fmt_expect(ext, ((size_t)nparts * rows << logN) * 8, dplanes ? LF_FMT_PLANES : LF_FMT_RAW)) return e;
+    const bool spl = dplanes && (g_more_planes & 1) && cols_last && scratch && scratch_words >= ((int64_t)2 * rows << logN);
+    const dim3 grid((unsigned)((((i64)1 << logN) + 511) / 512), (unsigned)rows);
+    const bool planes = key_format == LF_KEY_PLANES;
+#define LF_RSUM_LAUNCH(NR, PL, DPLB)                                                                                        \
+    hipLaunchKernelGGL((ks_inner_rsum_kernel<NR, PL, DPLB>), grid, dim3(256), 0, st, (const i64 *)ext, ra, (i64)part_stride, \
+                       (i64)comp_stride, (i64)row_off, (i64 *)s, nparts, rows, logN, spl ? 1 : 0, (const i64 *)ql, (const i64 *)qh, \
+                       (const i64 *)kl, (const i64 *)kh)
+#define LF_RSUM_CASE(NR)                                                                                                   \
+    case NR:                                                                                                               \
+        if (planes && dplanes) LF_RSUM_LAUNCH(NR, true, true);                                                            \
+        else if (planes) LF_RSUM_LAUNCH(NR, true, false);                                                                 \
+        else if (dplanes) LF_RSUM_LAUNCH(NR, false, true);                                                                \
+        else LF_RSUM_LAUNCH(NR, false, false);                                                                            \
+        break;
+    for (int i0 = 0; i0 < nr || i0 == 0;) {
+        const int left = nr - i0, g = left >= 4 ? 4 : left >= 2 ? 2 : left;
+        RsumArgs ra{};
+        for (int t = 0; t < g; ++t) {
+            ra.hk.ksk[t] = (const i64 *)ksk[i0 + t];
+            ra.hk.p[t] = (unsigned)p_host[i0 + t];
+        }
+        ra.chat = (const i64 *)chat, ra.ell = ell, ra.first = i0 == 0, ra.self = with_self ? 1 : 0;
+        switch (g) {
+            LF_RSUM_CASE(1) LF_RSUM_CASE(2) LF_RSUM_CASE(4)
+            case 0: LF_RSUM_LAUNCH(0, false, false); break;
+        }
+        i0 += g ? g : 1;
+    }
+#undef LF_RSUM_LAUNCH
+#undef LF_RSUM_CASE
     return ks_inv_sums(2, rows, logN, spl, cols_last, mixed, in, dp, (i64 *)scratch, (i64 *)s, ipsi_br, ipsi_dp, Ninv, ql, qh, kl, kh, st);
 }
 

@@ -29,6 +29,11 @@ int lf_ks_tail_lt(int nr, const int64_t *p_host, int nparts, int rows, int ell, 
                   const int64_t *kl, const int64_t *kh, hipStream_t st);
 
 // ckks_ks.hip: the launches of lf_linear_transform_bsgs
+int lf_ks_tail_rsum(int nr, const int64_t *p_host, int nparts, int rows, int ell, int logN, const int64_t *const *ksk, int64_t part_stride,
+                    int64_t comp_stride, int64_t row_off, int key_format, int with_self, const int64_t *chat, const int64_t *ext,
+                    int64_t *s, int64_t *scratch, int64_t scratch_words, const int64_t *ipsi_br, const double *ipsi_dp,
+                    const int64_t *Ninv, const int64_t *q_host, const int64_t *ql, const int64_t *qh, const int64_t *kl,
+                    const int64_t *kh, hipStream_t st);
 int lf_ks_baby_sums(int nr, const int64_t *p_host, int nparts, int rows, int ell, int logN, const int64_t *const *ksk, int64_t part_stride,
                     int64_t comp_stride, int64_t row_off, int key_format, const int64_t *chat0, const int64_t *ext, int64_t *u,
                     const int64_t *q_host, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st);
@@ -568,6 +573,63 @@ int lf_linear_transform(const lf_ks_plan *p, const int64_t *c0, const int64_t *c
     const int64_t *ins[2] = {md + N, md + poly + N}, *row0[2] = {md, md + poly};
     int64_t *outs[2] = {out0, out1};
     return lf_rescale_batch(ins, row0, outs, 2, ell - 1, N, rescale_scales, round_at, p->ql + 1, p->qh + 1, p->kl + 1, p->kh + 1, dev, stream);
+}
+
+/* ---- rotation sum: sum_i rot(ct, step_i) [+ ct], summed in the NTT domain over Q P, ONE inverse NTT and mod-down for the
+ * whole sum, no rescale: the result is at the ciphertext's own level (include/ckks_hip.h) ---- */
+// P NTT(c0), P NTT(c1): the plan's operand stack x4 (free during this op), else `ws`
+int64_t lf_rotate_sum_ws_words(const lf_ks_plan *p) {
+    if (!plan_ok(p) || p->x4) return 0;
+    return ((int64_t)2 * p->ell) << p->logN;
+}
+
+int lf_rotate_sum(const lf_ks_plan *p, const int64_t *c0, const int64_t *c1, int nr, const int64_t *p_host,
+                  const int64_t *const *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format,
+                  int with_self, int64_t *ws, int64_t ws_words, int64_t *out0, int64_t *out1, void *stream) {
+    if (!plan_ok(p) || !p->PR || nr < 0 || (nr == 0 && !with_self) || !c0 || !c1 || !out0 || !out1 ||
+        (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES))
+        return LF_ERR_ARG;
+    const int ell = p->ell, rows = p->ell + p->K, logN = p->logN, dev = p->device;
+    const int64_t N = (int64_t)1 << logN, twoN = 2 * N, poly = (int64_t)ell * N;
+    if (nr && (!p_host || !ksk)) return LF_ERR_ARG;
+    for (int i = 0; i < nr; ++i) {
+        if (!ksk[i] || p_host[i] <= 0 || p_host[i] >= twoN || !(p_host[i] & 1)) return LF_ERR_ARG;
+        if (key_format == LF_KEY_PLANES && ((((uintptr_t)ksk[i] | (uintptr_t)(part_stride * 8) | (uintptr_t)(comp_stride * 8)) & 15)))
+            return LF_ERR_ARG;
+    }
+    const int64_t need = lf_rotate_sum_ws_words(p);
+    if (need && (!ws || ws_words < need)) return LF_ERR_ARG;
+    int64_t *chat = need ? ws : p->x4;
+    // 1. P NTT(c0) (and P NTT(c1) for the self term) on the ordinary rows, as lf_linear_transform forms them
+    const int nc = with_self ? 2 : 1;
+    {
+        const int64_t *srcs[2] = {c0, c1};
+        int64_t *dsts[2] = {chat, chat + poly};
+        if (int e = lf_galois_batch(srcs, dsts, nc, ell, logN, 1, p->_2q, dev, stream)) return e;
+        if (int e = lf_ntt(chat, nc, ell, logN, p->psi, p->psi_dp, p->q_host, p->Rs, 0, p->_2q, p->ql, p->qh, p->kl, p->kh, dev, stream))
+            return e;
+        for (int c = 0; c < nc; ++c)
+            if (int e = lf_mont_enter(chat + c * poly, p->PR, ell, N, p->ql, p->qh, p->kl, p->kh, dev, stream)) return e;
+    }
+    // 2. digits of c1 (canonical, no permutation), their extension + forward NTT: once, as lf_rotate_hoisted
+    if (nr) {
+        if (int e = lf_ks_digits_galois(c1, p->state, p->dig_nparts, p->dig_desc, p->dig_tab, N, 1, p->_2q, p->ql, p->qh, p->kl, p->kh, dev,
+                                        stream))
+            return e;
+        if (int e = lf_ks_fwd(p->state, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, p->ext, p->psi, p->psi_dp, p->q_host, p->ql, p->qh,
+                              p->kl, p->kh, dev, stream))
+            return e;
+    }
+    // 3. the groups' launches into the one pair of sums, its inverse NTT (planes through the spent digits, two slots or more)
+    const int64_t spare = p->nparts >= 2 ? ((int64_t)p->nparts * rows) << logN : 0;
+    if (int e = lf_ks_tail_rsum(nr, p_host, p->nparts, rows, ell, logN, ksk, part_stride, comp_stride, row_off, key_format, with_self, chat,
+                                p->ext, p->sum, spare ? p->ext : nullptr, spare, p->ipsi, p->ipsi_dp, p->Ninv, p->q_host, p->ql, p->qh,
+                                p->kl, p->kh, (hipStream_t)stream))
+        return e;
+    // 4. one mod-down, straight into the caller's [ell][N] pair: no rescale, the level stays
+    const int64_t *ss[2] = {p->sum, p->sum + (int64_t)rows * N};
+    int64_t *outs[2] = {out0, out1};
+    return moddown_any(p, ss, outs, nullptr, 2, 0, nullptr, stream);
 }
 
 /* ---- linear transform, baby-step / giant-step: y = sum_g rot(sum_b pt_{g,b} * rot(x, b), g) (include/ckks_hip.h) ---- */

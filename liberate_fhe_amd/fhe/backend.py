@@ -527,6 +527,27 @@ class HipBackend:
               "lf_linear_transform")
 
     @staticmethod
+    def rotate_sum_ws_words(plan):
+        return int(lib.lf_rotate_sum_ws_words(ctypes.byref(plan)))
+
+    def rotate_sum_native(self, plan, c0, c1, exponents, keys, first_part, row_off, with_self, out, ws=None):
+        """sum_i rot_i(c0, c1) (+ (c0, c1) with with_self) and ONE mod-down as ONE native call (lf_rotate_sum): no rescale, the
+        level stays.  keys: packed key tensors of one format and shape, exponents their Galois exponents; out [2, ell, N]."""
+        dev, st = _ds(out)
+        n = len(keys)
+        bases = (ctypes.c_void_p * max(n, 1))()
+        ps = cs = 0
+        for i, key in enumerate(keys):
+            bases[i], ps, cs = self._key_args(key, first_part)
+        fmt = {self._kfmt(k) for k in keys}
+        if len(fmt) > 1:
+            raise ValueError("rotate_sum_native: the keys of one call must share one format")
+        exps = (ctypes.c_int64 * max(n, 1))(*exponents)
+        check(lib.lf_rotate_sum(ctypes.byref(plan), _p(c0), _p(c1), n, exps, bases, ps, cs, row_off, fmt.pop() if fmt else 0,
+                                1 if with_self else 0, _p(ws), 0 if ws is None else ws.numel(), out.data_ptr(),
+                                out.data_ptr() + out.stride(0) * 8, st), "lf_rotate_sum")
+
+    @staticmethod
     def linear_transform_bsgs_ws_words(plan, nb):
         return int(lib.lf_linear_transform_bsgs_ws_words(ctypes.byref(plan), nb))
 

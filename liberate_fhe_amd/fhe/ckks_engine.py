@@ -41,6 +41,7 @@ from .ltmatmul import LtMatmulOps
 from .plainops import PlainOps
 from .polyeval import PolyOps
 from .presets import errors, types
+from .slotsum import SlotSumOps
 from .version import VERSION
 
 
@@ -77,7 +78,7 @@ class _OneShard:
         return ckks_engine._decrypt_rows_on(self, ct, sk, self.li, self.dev)
 
 
-class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps):
+class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps):
     @errors.log_error
     def __init__(self, devices: list[int] = None, verbose: bool = False, bias_guard: bool = True,
                  norm: str = "forward", backend=None, comm=None, balanced_limb_map: bool = False, **ctx_params):

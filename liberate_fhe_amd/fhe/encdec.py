@@ -165,6 +165,46 @@ def bsgs_split(steps, num_slots: int, n1=None) -> tuple:
     return n1, babies, giants
 
 
+# The radix inner_sum uses unless told otherwise: the fastest of {2, 4, 8} at gold, level 0, for n = 64 on one MI355X
+# (tools/inner_sum.py; the figures are in DESIGN.md §4.2)
+INNER_SUM_RADIX = 4
+# the most one stage may be: what lf_linear_transform_bsgs allows one hoisted set (LF_BSGS_MAX_BABY_KEYS keys + the ciphertext)
+INNER_SUM_MAX_STAGE = 64
+
+
+def inner_sum_plan(n: int, stride: int, num_slots: int, radix: int = INNER_SUM_RADIX) -> list:
+    """The mixed-radix stages of sum_{j < n} rot(x, j * stride): [(r_t, (steps ..)), ..] with n = r_1 r_2 .. r_m.  Stage t adds
+    the r_t copies of its input rotated by j * stride * r_1 .. r_{t-1} (mod num_slots), j = 0 .. r_t - 1; its `steps` are those
+    of j >= 1, the ones that need a rotation key.  Every j < n is sum_t j_t r_1 .. r_{t-1} with j_t < r_t exactly once, so the
+    chain of the stages is the whole sum.  Factors <= radix are taken greedily, largest first; a prime factor above radix is a
+    stage of its own.  n = 1: no stage.  ValueError for n < 1, radix < 2, a stage above INNER_SUM_MAX_STAGE, or
+    n * |stride| > num_slots (the sum would wrap onto itself)."""
+    try:
+        ok = int(n) == n and int(stride) == stride and int(radix) == radix and not isinstance(n, bool)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"inner_sum_plan: integers are required, got n={n!r}, stride={stride!r}, radix={radix!r}")
+    n, stride, radix = int(n), int(stride), int(radix)
+    if n < 1:
+        raise ValueError(f"inner_sum_plan: n >= 1 is required, got {n}")
+    if radix < 2:
+        raise ValueError(f"inner_sum_plan: radix >= 2 is required, got {radix}")
+    if n * abs(stride) > num_slots:
+        raise ValueError(f"inner_sum_plan: n * |stride| = {n * abs(stride)} exceeds the {num_slots} slots")
+    stages, rest, unit = [], n, stride
+    while rest > 1:
+        r = next((f for f in range(min(radix, rest), 1, -1) if rest % f == 0), None)
+        if r is None:                                   # no factor <= radix: the smallest factor left is a prime above it
+            r = next(f for f in range(radix + 1, rest + 1) if rest % f == 0)
+        if r > INNER_SUM_MAX_STAGE:
+            raise ValueError(f"inner_sum_plan: n = {n} has the prime factor {r}, above the {INNER_SUM_MAX_STAGE} of one stage")
+        stages.append((r, tuple((j * unit) % num_slots for j in range(1, r))))
+        rest //= r
+        unit *= r
+    return stages
+
+
 def _tree_levels(b: int) -> int:
     """Levels above the base at which the b-th power stands when powers are built by the tree rule of ckks_engine.poly_eval
     (a power of two 2^j by j squarings; any other b as top power of two times the rest, one level above the former)."""

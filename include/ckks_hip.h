@@ -668,6 +668,56 @@ int lf_lt_matmul(const lf_ks_plan *plan, int k_in, int k_out, const int64_t *con
                  const int64_t *rescale_scales, int64_t round_at, int64_t *ws, int64_t ws_words, int64_t *const *out0,
                  int64_t *const *out1, void *stream);
 
+/* A matrix of baby-step / giant-step transforms times a vector of ciphertexts: lf_lt_matmul for blocks of hundreds of diagonals,
+ * from the keys of the baby and the giant steps alone.  For o < k_out, out_o decrypts to
+ *     sum_{i < k_in} sum_{step in steps(o, i)} diag_{o,i,step} * rot(m_i, step),   step = g + b, b = step mod n1,
+ * level l -> l + 1, with the diagonals encoded as ckks_engine.encode_diagonals(.., bsgs=n1) does (rolled by -g).  The baby
+ * rotations of input i do not depend on the output and are formed once per input; the giant rotation is linear, so the inner sums
+ * of ALL inputs of one output are added in Q P before the giant key switch: an output pays one key switch per giant step, not one
+ * per giant step and input; and the outputs that share a giant step share the stream of its key.
+ * in / ncol / bp_host / bksk: the columns and their baby keys, exactly as in / ncol / p_host / ksk of lf_lt_matmul (SLOT 0 of a
+ * column is the ciphertext itself, slot 1 + j its j-th keyed baby step).  ng / gp_host / gksk: the giant steps as in
+ * lf_linear_transform_bsgs: gp_host[j] = 0 marks giant step 0, which comes first, at most once, and has no key.  One key layout
+ * for all (part_stride .. key_format as lf_rotate_hoisted); the same key may serve as a baby and as a giant step.
+ * pt / pt_stride / gcount: HOST arrays of k_out k_in ng entries, [output][input][giant]: the first diagonal of block (o, i) in
+ * giant step j or NULL (gcount 0), the words between its diagonals, their number >= 1; bidx: HOST array holding, in the same
+ * order, the column slot of every diagonal, strictly ascending inside one (o, i, j).
+ * Output o has exactly the words of: per input i that some block uses c0, c1 made canonical, E_i and c^_i as lf_linear_transform
+ * forms them; per keyed baby step b of the column u^{i,b}_c = sum over the digits of E_i gathered by pi_b times key b's part,
+ * u^{i,b}_0 += c^_{i,0} gathered on the ordinary rows (b = 0: u^{i,0}_c = c^_{i,c}, zero on the special rows); per output o and
+ * giant step g of its row S^{o,g}_c = sum_i sum_{b : g + b in steps(o, i)} mont_mult(pt_{o,i,g+b}, u^{i,b}_c), summed over the
+ * inputs BEFORE anything comes down; g = 0: S^{o,0} joins the accumulator A^o; g != 0: w = mod-down (no addend) of
+ * intt_exit_reduce(S^{o,g}_1), made canonical, E^{o,g} its digits extended and transformed, v_c = sum over the digits of E^{o,g}
+ * gathered by pi_g times key g's part, v_0 += S^{o,g}_0 gathered on ALL ell + K rows, A^o += v; then intt_exit_reduce(A^o),
+ * mod-down (no addend), ckks_engine.rescale.  Only residues of u, S, v and A reach the result, so the grouping of the additions
+ * is free.  k_in = 1: output o has the words of lf_linear_transform_bsgs over block (o, 0); giant step 0 alone: those of
+ * lf_lt_matmul over the same packs; output o depends on row o only.
+ * Enqueued: (1) input-major, steps 1 - 3 of lf_lt_matmul with the pairs (o, j) that have a diagonal in the place of the outputs:
+ * per used input slot 0, lf_ks_digits_galois, lf_ks_fwd and ks_inner_baby_kernel per group of its keys, then
+ * lt_block_products_kernel<4 | 2 | 1> per group of targets; the target of (o, giant step 0) is the accumulator A^o itself, an
+ * output without giant step 0 has A^o zeroed by one hipMemsetAsync.  (2) giant-step-major: per keyed giant step the outputs that
+ * have it in groups of n = 4, 2 or 1 (n <= plan->max_nct): per polynomial one lf_intt of S_1, ONE lf_ks_moddown_ws for the n
+ * polynomials, ONE lf_ks_digits_batch into plan->state, ONE extension + forward NTT of all n nparts digits into plan->ext, ONE
+ * launch of ks_inner_giantb_kernel<n> (every key word read once for the group; n = 1: ks_inner_giant_kernel).  (3) per group of
+ * up to 4 outputs one lf_intt of its 2 g accumulator polynomials, one lf_ks_moddown_ws, one lf_rescale_batch.
+ * ws: lf_lt_matmul_bsgs_ws_words(plan, nb_max, k_out, keyed_sums) words, 16-byte aligned, lent by the caller — nb_max the largest
+ * ncol[i] of a used input, keyed_sums the pairs (o, j) with gp_host[j] != 0 that have a diagonal:
+ *     (nb_max + 1 + k_out + keyed_sums) pairs [2][ell + K][N] + gw [ell][N] + 2 g4 [ell][N]
+ *         + max(lf_ks_moddown_ws_words(gw, ..), lf_ks_moddown_ws_words(2 g4, ..)),   g4 = min(k_out, 4), gw = min(4, plan->max_nct);
+ * 0 for what the entry refuses.  An engine with more outputs, giant steps or keyed sums than one call takes splits the outputs
+ * over calls (each call repeats the inputs' baby steps).
+ * LF_ERR_ARG before any launch for everything lf_lt_matmul and lf_linear_transform_bsgs refuse, ng < 1 or
+ * > LF_LT_MATMUL_BSGS_MAX_GIANTS, more than LF_LT_MATMUL_BSGS_MAX_SUMS keyed sums, an (o, i, j) with a NULL pack and a count or
+ * the other way round, an output with no diagonal at all, a keyed giant step no output uses. */
+#define LF_LT_MATMUL_BSGS_MAX_GIANTS 64
+#define LF_LT_MATMUL_BSGS_MAX_SUMS 256
+int64_t lf_lt_matmul_bsgs_ws_words(const lf_ks_plan *plan, int nb_max, int k_out, int keyed_sums);
+int lf_lt_matmul_bsgs(const lf_ks_plan *plan, int k_in, int k_out, const int64_t *const *in, const int64_t *ncol, const int64_t *bp_host,
+                      const int64_t *const *bksk, int ng, const int64_t *gp_host, const int64_t *const *gksk, int64_t part_stride,
+                      int64_t comp_stride, int64_t row_off, int key_format, const int64_t *const *pt, const int64_t *pt_stride,
+                      const int64_t *gcount, const int64_t *bidx, const int64_t *rescale_scales, int64_t round_at, int64_t *ws,
+                      int64_t ws_words, int64_t *const *out0, int64_t *const *out1, void *stream);
+
 /* Sum of ciphertext products under ONE relinearisation ("lazy relinearisation"): out decrypts to sum_i a_i * b_i, level l -> l + 1.
  * np >= 1 pairs; in / row0: HOST arrays of 4 np device pointers, four per pair in the order of lf_cc_mult_evk (first surviving
  * row resp. dropped row of a_i.c0, a_i.c1, b_i.c0, b_i.c1; the same polynomial may appear any number of times); the plan

@@ -125,6 +125,8 @@ _SIGNATURES["lf_linear_transform_bsgs_ws_words"] = [_PL, _I]
 _SIGNATURES["lf_linear_transform_bsgs"] = [_PL, _P, _P, _I, _P, _P, _I, _P, _P, _L, _L, _L, _I, _P, _L, _P, _P, _P, _L, _P, _L, _P, _P, _P]
 _SIGNATURES["lf_lt_matmul_ws_words"] = [_PL, _I, _I]
 _SIGNATURES["lf_lt_matmul"] = [_PL, _I, _I, _P, _P, _P, _P, _L, _L, _L, _I, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _P]
+_SIGNATURES["lf_lt_matmul_bsgs_ws_words"] = [_PL, _I, _I, _I]
+_SIGNATURES["lf_lt_matmul_bsgs"] = [_PL, _I, _I, _P, _P, _P, _P, _I, _P, _P, _L, _L, _L, _I, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _P]
 
 # the 30-bit / int32 word mode of the ntt_cuda surface (csrc/ckks_w30.hip)
 _SIGNATURES.update({
@@ -174,5 +176,7 @@ LF_PC_MATMUL_CI = 16           # include/ckks_hip.h: inputs per chunk of lf_pc_m
 LF_PC_MATMUL_MAX_OUTPUTS = 64  # .. and outputs per call
 LF_LT_MATMUL_MAX_INPUTS = 64   # include/ckks_hip.h: inputs per lf_lt_matmul call
 LF_LT_MATMUL_MAX_OUTPUTS = 64  # .. and outputs per call
+LF_LT_MATMUL_BSGS_MAX_GIANTS = 64   # include/ckks_hip.h: giant steps per lf_lt_matmul_bsgs call
+LF_LT_MATMUL_BSGS_MAX_SUMS = 256    # .. and keyed inner sums (pairs of an output and a keyed giant step)
 LF_ERR_ARG = 10001
 LF_ERR_STATE = 10002

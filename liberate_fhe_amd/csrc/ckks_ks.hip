@@ -1572,6 +1572,117 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PLANES
     }
 }
 
+// ---- a matrix of baby-step / giant-step transforms (lf_lt_matmul_bsgs): the giant step of NCT outputs under ONE key -------------
+// ks_inner_giant_kernel for the NCT (2 or 4) outputs that share a giant step: its grid and its key / digit formats, one key and
+// hence ONE pi for the whole group (src / sw once per thread).  Per part the key's four words are loaded once and multiplied into
+// NCT x 4 accumulators; then per output the gathered word of its S^g_0 on all rows and the read - add - write of its accumulator
+// pair, exactly as the single kernel does: dp_reduce once on the fp64-class rows (|sums| < (digits / 2 + 4) q: lf_fp64_digits_ok),
+// lazy words below 2q on the integer rows.  The key stream of the giant step crosses HBM once for the group.
+struct GiantBatchArgs {
+    const i64 *ksk;      // the key, at its first part
+    unsigned p;          // its exponent (odd, < 2N)
+    i64 ext_stride;      // words between the outputs' stacks of extended digits ([nparts][rows][N] each)
+    const i64 *s0[4];    // output t: S^g_0 [rows][N], raw words below 2q
+    i64 *acc[4];         // .. its accumulator pair [2][rows][N]: read, added to, written
+};
+
+template <int NCT, bool PLANES, bool DPL>   // (four outputs already have four digit pairs in flight per key word: their digit loop is not unrolled)
+__global__ void __launch_bounds__(256) ks_inner_giantb_kernel(const i64 *__restrict__ ext, GiantBatchArgs ga, i64 part_stride, i64 comp_stride,
+                                                              i64 row_off, int nparts, int rows, int logN,
+                                                              const i64 *__restrict__ ql, const i64 *__restrict__ qh,
+                                                              const i64 *__restrict__ kl, const i64 *__restrict__ kh) {
+    const int r = blockIdx.y;
+    const i64 N = (i64)1 << logN;
+    const i64 j0 = (i64)blockIdx.x * 512 + threadIdx.x * 2;
+    if (j0 >= N) return;
+    const RowMod m = load_mod(ql, qh, kl, kh, r);
+    const unsigned sh = 32u - (unsigned)logN, mask = (2u << logN) - 1u;
+    const unsigned bj = (2u * (__builtin_bitreverse32((unsigned)j0) >> sh) + 1u);
+    const unsigned t0 = (bj * ga.p) & mask;
+    const unsigned mi = __builtin_bitreverse32((t0 - 1u) >> 1) >> sh;
+    const i64 src = (i64)(mi & ~1u);
+    const bool sw = (mi & 1u) != 0;
+    const i64 *krow = ga.ksk + (row_off + r) * N;
+    const i64 a0 = (i64)r * N + j0, a1 = ((i64)rows + r) * N + j0;
+    if (m.q < SMALL_PRIME_LIMIT) {
+        const RowDp d = make_dp(m);
+        constexpr int DIGITS_IN_FLIGHT = NCT == 4 ? 1 : KI_UNROLL;
+        double acc[NCT][2][2];
+#pragma unroll
+        for (int t = 0; t < NCT; ++t) acc[t][0][0] = acc[t][0][1] = acc[t][1][0] = acc[t][1][1] = 0.0;
+#pragma unroll DIGITS_IN_FLIGHT
+        for (int p = 0; p < nparts; ++p) {
+            const i64 *kr = krow + (i64)p * part_stride;
+            double k0x, k0y, k1x, k1y;
+            if (PLANES) {   // 16 + 8 bytes for both components (see lf_key_planes)
+                const lf_u4_t l = __builtin_nontemporal_load(reinterpret_cast<const lf_u4_t *>(reinterpret_cast<const unsigned *>(kr) + 2 * j0));
+                const lf_u2_t h = __builtin_nontemporal_load(reinterpret_cast<const lf_u2_t *>(reinterpret_cast<const unsigned *>(kr + comp_stride) + j0));
+                k0x = dp_from_planes(l.x, h.x & 0xffffu), k0y = dp_from_planes(l.y, h.x >> 16);
+                k1x = dp_from_planes(l.z, h.y & 0xffffu), k1y = dp_from_planes(l.w, h.y >> 16);
+            } else {
+                const longlong2 k0 = ld_nt(kr + j0);
+                const longlong2 k1 = ld_nt(kr + j0 + comp_stride);
+                k0x = dp_from_word(k0.x), k0y = dp_from_word(k0.y), k1x = dp_from_word(k1.x), k1y = dp_from_word(k1.y);
+            }
+            const i64 *er = ext + ((i64)p * rows + r) * N;
+#pragma unroll
+            for (int t = 0; t < NCT; ++t) {
+                double xa, xb;
+                ld_pair_dp(er + (i64)t * ga.ext_stride, src, N, DPL ? 1 : 0, xa, xb);
+                const double x0 = sw ? xb : xa, x1 = sw ? xa : xb;
+                acc[t][0][0] += dp_mulmod_bal(x0, k0x, d);
+                acc[t][0][1] += dp_mulmod_bal(x1, k0y, d);
+                acc[t][1][0] += dp_mulmod_bal(x0, k1x, d);
+                acc[t][1][1] += dp_mulmod_bal(x1, k1y, d);
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < NCT; ++t) {
+            double ca, cb, x0, y0, x1, y1;
+            ld_pair_dp(ga.s0[t] + (i64)r * N, src, N, 0, ca, cb);
+            ld_pair_dp(ga.acc[t] + a0, 0, N, 0, x0, y0);
+            ld_pair_dp(ga.acc[t] + a1, 0, N, 0, x1, y1);
+            longlong2 a, b;   // |sums| < (digits / 2 + 4) q, inside dp_reduce's 64 q
+            a.x = dp_to_word(dp_reduce(acc[t][0][0] + (sw ? cb : ca) + x0, d.q, d.qinv));
+            a.y = dp_to_word(dp_reduce(acc[t][0][1] + (sw ? ca : cb) + y0, d.q, d.qinv));
+            b.x = dp_to_word(dp_reduce(acc[t][1][0] + x1, d.q, d.qinv));
+            b.y = dp_to_word(dp_reduce(acc[t][1][1] + y1, d.q, d.qinv));
+            *reinterpret_cast<longlong2 *>(ga.acc[t] + a0) = a;
+            *reinterpret_cast<longlong2 *>(ga.acc[t] + a1) = b;
+        }
+    } else {
+        i64 acc[NCT][2][2];
+#pragma unroll
+        for (int t = 0; t < NCT; ++t) acc[t][0][0] = acc[t][0][1] = acc[t][1][0] = acc[t][1][1] = 0;
+        for (int p = 0; p < nparts; ++p) {
+            const i64 *kr = krow + (i64)p * part_stride + j0;
+            const longlong2 k0 = ld_nt(kr);
+            const longlong2 k1 = ld_nt(kr + comp_stride);
+            const i64 *er = ext + ((i64)p * rows + r) * N + src;
+#pragma unroll
+            for (int t = 0; t < NCT; ++t) {
+                const longlong2 v = *reinterpret_cast<const longlong2 *>(er + (i64)t * ga.ext_stride);
+                const u64 x0 = (u64)(sw ? v.y : v.x), x1 = (u64)(sw ? v.x : v.y);
+                acc[t][0][0] = csub(acc[t][0][0] + mm62u(x0, (u64)k0.x, m.q, m.k), m.q2);
+                acc[t][0][1] = csub(acc[t][0][1] + mm62u(x1, (u64)k0.y, m.q, m.k), m.q2);
+                acc[t][1][0] = csub(acc[t][1][0] + mm62u(x0, (u64)k1.x, m.q, m.k), m.q2);
+                acc[t][1][1] = csub(acc[t][1][1] + mm62u(x1, (u64)k1.y, m.q, m.k), m.q2);
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < NCT; ++t) {
+            const longlong2 v = *reinterpret_cast<const longlong2 *>(ga.s0[t] + (i64)r * N + src);
+            longlong2 a = *reinterpret_cast<const longlong2 *>(ga.acc[t] + a0), b = *reinterpret_cast<const longlong2 *>(ga.acc[t] + a1);
+            a.x = csub(a.x + csub(acc[t][0][0] + (sw ? v.y : v.x), m.q2), m.q2);
+            a.y = csub(a.y + csub(acc[t][0][1] + (sw ? v.x : v.y), m.q2), m.q2);
+            b.x = csub(b.x + acc[t][1][0], m.q2);
+            b.y = csub(b.y + acc[t][1][1], m.q2);
+            *reinterpret_cast<longlong2 *>(ga.acc[t] + a0) = a;
+            *reinterpret_cast<longlong2 *>(ga.acc[t] + a1) = b;
+        }
+    }
+}
+
 // largest number of leading stages (logN - 12) whose extension + strided pass runs as the column kernel (lf_tune).
 // With the digit loop as a runtime loop (R loads in flight, 100 VGPRs at R = 16) the column form also wins at logN 16:
 // gold cc_mult 2 104-2 130 -> 2 168-2 183 ops/s, rotate 2 653-2 695 -> 2 733-2 763, 64 rotations under one key
@@ -2222,6 +2333,60 @@ int lf_ks_giant_sums(int64_t p, int nparts, int rows, int logN, const int64_t *k
     else if (dplanes) LF_GIANT_LAUNCH(false, true);
     else LF_GIANT_LAUNCH(false, false);
 #undef LF_GIANT_LAUNCH
+    return (int)hipGetLastError();
+}
+
+// ---- the launches of lf_lt_matmul_bsgs that are its own (ckks_ops.hip checks the arguments and owns the order) ----
+// extension + forward NTT of the digits of nct polynomials (state + t * state_stride) into tmp [nct][nparts][rows][N]
+int lf_ks_fwd_batch(const int64_t *state, int64_t state_stride, int nct, int nparts, int rows, int logN, const int64_t *desc,
+                    const int64_t *E, const double *Ed, int64_t *tmp, const int64_t *psi_br, const double *psi_dp, const int64_t *q_host,
+                    const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st) {
+    if ((nct != 2 && nct != 4) || nparts < 1 || rows < 1 || rows > MAX_LIST_ROWS || logN <= NTT_TILE_LOG_MAX || logN > KS_LOGN_MAX ||
+        !q_host || !psi_dp || !Ed || !state || !tmp)
+        return LF_ERR_ARG;
+    return ks_forward(state, state_stride, nct, nparts, rows, logN, desc, E, Ed, tmp, psi_br, psi_dp, q_host, ql, qh, kl, kh, st);
+}
+
+// giant step of nct (2 or 4) outputs under one key: acc[t] += (sum over the parts of output t's digits ext + t * nparts rows N
+// gathered by pi_p times the key part, + s0[t] gathered on all rows on component 0); every key word is read once for the group
+int lf_ks_giant_sums_batch(int nct, int64_t p, int nparts, int rows, int logN, const int64_t *ksk, int64_t part_stride, int64_t comp_stride,
+                           int64_t row_off, int key_format, const int64_t *ext, const int64_t *const *s0, int64_t *const *acc,
+                           const int64_t *q_host, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh,
+                           hipStream_t st) {
+    if ((nct != 2 && nct != 4) || !key_args_ok(ksk, part_stride, comp_stride, key_format) || !ext || !s0 || !acc || nparts < 1 ||
+        logN <= NTT_TILE_LOG_MAX || logN > KS_LOGN_MAX || p <= 0 || p >= ((int64_t)2 << logN) || !(p & 1))
+        return LF_ERR_ARG;
+    if (rows < 1 || rows > MAX_LIST_ROWS || !lf_fp64_digits_ok(nparts, rows, q_host)) return LF_ERR_ARG;
+    RowList dp, in;
+    classify_rows(rows, q_host, dp, in);
+    const bool dplanes = digit_planes(logN, dp, in);
+    if (int e = lf_fmt_expect(ext, ((size_t)nct * nparts * rows << logN) * 8, dplanes ? LF_FMT_PLANES : LF_FMT_RAW)) return e;
+    GiantBatchArgs ga{};
+    ga.ksk = (const i64 *)ksk, ga.p = (unsigned)p, ga.ext_stride = ((i64)nparts * rows) << logN;
+    for (int t = 0; t < nct; ++t) {
+        if (!s0[t] || !acc[t]) return LF_ERR_ARG;
+        for (int k = 0; k < t; ++k)
+            if (acc[k] == acc[t]) return LF_ERR_ARG;   // (two outputs of one launch never share an accumulator)
+        ga.s0[t] = (const i64 *)s0[t], ga.acc[t] = (i64 *)acc[t];
+    }
+    const dim3 grid((unsigned)((((i64)1 << logN) + 511) / 512), (unsigned)rows);
+    const bool planes = key_format == LF_KEY_PLANES;
+#define LF_GIANTB_LAUNCH(NCT, PL, DPLB)                                                                                         \
+    hipLaunchKernelGGL((ks_inner_giantb_kernel<NCT, PL, DPLB>), grid, dim3(256), 0, st, (const i64 *)ext, ga, (i64)part_stride, \
+                       (i64)comp_stride, (i64)row_off, nparts, rows, logN, (const i64 *)ql, (const i64 *)qh, (const i64 *)kl,   \
+                       (const i64 *)kh)
+#define LF_GIANTB_CASE(NCT)                                                                                                   \
+    if (planes && dplanes) LF_GIANTB_LAUNCH(NCT, true, true);                                                                 \
+    else if (planes) LF_GIANTB_LAUNCH(NCT, true, false);                                                                      \
+    else if (dplanes) LF_GIANTB_LAUNCH(NCT, false, true);                                                                     \
+    else LF_GIANTB_LAUNCH(NCT, false, false)
+    if (nct == 2) {
+        LF_GIANTB_CASE(2);
+    } else {
+        LF_GIANTB_CASE(4);
+    }
+#undef LF_GIANTB_LAUNCH
+#undef LF_GIANTB_CASE
     return (int)hipGetLastError();
 }
 

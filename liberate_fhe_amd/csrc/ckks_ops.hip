@@ -49,6 +49,15 @@ int lf_lt_block_products(int no, const int64_t *u, int nslots, const int64_t *co
                          const int64_t *pt_stride, int64_t *const *out, const int *fresh, int rows, int logN, const int64_t *ql,
                          const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st);
 
+// ckks_ks.hip: the launches of lf_lt_matmul_bsgs that are its own
+int lf_ks_fwd_batch(const int64_t *state, int64_t state_stride, int nct, int nparts, int rows, int logN, const int64_t *desc,
+                    const int64_t *E, const double *Ed, int64_t *tmp, const int64_t *psi_br, const double *psi_dp, const int64_t *q_host,
+                    const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st);
+int lf_ks_giant_sums_batch(int nct, int64_t p, int nparts, int rows, int logN, const int64_t *ksk, int64_t part_stride, int64_t comp_stride,
+                           int64_t row_off, int key_format, const int64_t *ext, const int64_t *const *s0, int64_t *const *acc,
+                           const int64_t *q_host, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh,
+                           hipStream_t st);
+
 // ckks_ks.hip: the launches of lf_cc_dot that are its own
 int lf_dot_tensor(int g, const int64_t *x, int64_t *T, int64_t *t2, int ell, int logN, int xpl, int first, const int64_t *ql,
                   const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st);
@@ -888,6 +897,227 @@ int lf_lt_matmul(const lf_ks_plan *p, int k_in, int k_out, const int64_t *const 
         int64_t *mds[2 * LF_LT_MATMUL_GROUP], *outs[2 * LF_LT_MATMUL_GROUP];
         for (int t = 0; t < 2 * g; ++t) {
             ss[t] = Sg + t * (int64_t)rows * N;
+            mds[t] = md + t * poly;
+            row0[t] = mds[t], ins[t] = mds[t] + N;
+            outs[t] = (t & 1) ? out1[o0 + t / 2] : out0[o0 + t / 2];
+        }
+        if (int e = lf_ks_moddown_ws(ss, mds, nullptr, 2 * g, ell, p->K, N, mdws, mdws_words, p->PiR, p->PiP, p->Rs, 0, nullptr, p->ql, p->qh,
+                                     p->kl, p->kh, dev, stream))
+            return e;
+        if (int e = lf_rescale_batch(ins, row0, outs, 2 * g, ell - 1, N, rescale_scales, round_at, p->ql + 1, p->qh + 1, p->kl + 1, p->kh + 1,
+                                     dev, stream))
+            return e;
+    }
+    return 0;
+}
+
+/* ---- a matrix of baby-step / giant-step transforms: y_o = sum_g rot(sum_i sum_b pt_{o,i,g+b} * rot(x_i, b), g)
+ * (include/ckks_hip.h).  Input-major as lf_lt_matmul, with the pairs (output, giant step) in the place of the outputs: the inner
+ * sums S^{o,g} stay in Q P over ALL inputs, so an output pays one key switch per giant step, and the outputs that share a giant
+ * step share the stream of its key. ---- */
+// polynomials the giant phase brings down at once: groups of 4, 2 or 1 outputs within the batch the plan is sized for
+static int bsgs_giant_group(const lf_ks_plan *p) { return p->max_nct < 4 ? p->max_nct : 4; }
+
+int64_t lf_lt_matmul_bsgs_ws_words(const lf_ks_plan *p, int nb_max, int k_out, int keyed_sums) {
+    if (!plan_ok(p) || nb_max < 0 || nb_max > LF_BSGS_MAX_BABY_KEYS || k_out < 1 || k_out > LF_LT_MATMUL_MAX_OUTPUTS || keyed_sums < 0 ||
+        keyed_sums > LF_LT_MATMUL_BSGS_MAX_SUMS)
+        return 0;
+    const int64_t N = (int64_t)1 << p->logN, pair = 2 * (int64_t)(p->ell + p->K) * N, poly = (int64_t)p->ell * N;
+    const int g4 = k_out < LF_LT_MATMUL_GROUP ? k_out : LF_LT_MATMUL_GROUP, gw = bsgs_giant_group(p);
+    const int64_t md_w = lf_ks_moddown_ws_words(gw, p->ell, p->K, N), md_t = lf_ks_moddown_ws_words(2 * g4, p->ell, p->K, N);
+    // one input's pairs (slot 0: the ciphertext), the k_out accumulators, the keyed inner sums, w of one giant group, the mod-down's
+    // results of one group of outputs, and the workspace of either mod-down (the plan's own is primed for pairs)
+    return pair * (nb_max + 1 + k_out + keyed_sums) + gw * poly + 2 * g4 * poly + (md_w > md_t ? md_w : md_t);
+}
+
+int lf_lt_matmul_bsgs(const lf_ks_plan *p, int k_in, int k_out, const int64_t *const *in, const int64_t *ncol, const int64_t *bp_host,
+                      const int64_t *const *bksk, int ng, const int64_t *gp_host, const int64_t *const *gksk, int64_t part_stride,
+                      int64_t comp_stride, int64_t row_off, int key_format, const int64_t *const *pt, const int64_t *pt_stride,
+                      const int64_t *gcount, const int64_t *bidx, const int64_t *rescale_scales, int64_t round_at, int64_t *ws,
+                      int64_t ws_words, int64_t *const *out0, int64_t *const *out1, void *stream) {
+    if (!plan_ok(p) || !p->PR || p->ell < 2 || k_in < 1 || k_in > LF_LT_MATMUL_MAX_INPUTS || k_out < 1 || k_out > LF_LT_MATMUL_MAX_OUTPUTS ||
+        ng < 1 || ng > LF_LT_MATMUL_BSGS_MAX_GIANTS || !in || !ncol || !gp_host || !gksk || !pt || !pt_stride || !gcount || !bidx ||
+        !rescale_scales || !out0 || !out1 || (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES))
+        return LF_ERR_ARG;
+    const int ell = p->ell, rows = p->ell + p->K, logN = p->logN, dev = p->device;
+    const int64_t N = (int64_t)1 << logN, twoN = 2 * N, poly = (int64_t)ell * N, pair = 2 * (int64_t)rows * N;
+    auto key_ok = [&](const int64_t *k, int64_t e) {
+        if (!k || e <= 0 || e >= twoN || !(e & 1)) return false;
+        return key_format != LF_KEY_PLANES || !((((uintptr_t)k | (uintptr_t)(part_stride * 8) | (uintptr_t)(comp_stride * 8)) & 15));
+    };
+    auto block = [&](int o, int i, int j) { return ((int64_t)o * k_in + i) * ng + j; };
+    for (int j = 0; j < ng; ++j)
+        if (gp_host[j] == 0 ? j != 0 : !key_ok(gksk[j], gp_host[j])) return LF_ERR_ARG;   // (giant step 0: first, so at most once)
+    // the columns: keyed baby steps per input, the inputs some output uses, their keys
+    std::vector<int64_t> koff(k_in + 1, 0);
+    std::vector<char> used(k_in, 0);
+    int nb_max = 0;
+    for (int i = 0; i < k_in; ++i) {
+        if (ncol[i] < 0 || ncol[i] > LF_BSGS_MAX_BABY_KEYS) return LF_ERR_ARG;
+        koff[i + 1] = koff[i] + ncol[i];
+        for (int o = 0; o < k_out && !used[i]; ++o)
+            for (int j = 0; j < ng && !used[i]; ++j) used[i] = pt[block(o, i, j)] != nullptr;
+        if (!used[i]) continue;
+        if (!in[2 * i] || !in[2 * i + 1]) return LF_ERR_ARG;
+        if (ncol[i] && (!bp_host || !bksk)) return LF_ERR_ARG;
+        for (int64_t k = koff[i]; k < koff[i + 1]; ++k)
+            if (!key_ok(bksk[k], bp_host[k])) return LF_ERR_ARG;
+        if (ncol[i] > nb_max) nb_max = (int)ncol[i];
+    }
+    // the diagonals: per (output, input, giant step) its slots inside the column's set, ascending; per (output, giant step) the
+    // target of its inner sum: the accumulator A^o itself for giant step 0, else the next pair of S (giant step after giant step)
+    std::vector<unsigned long long> masks((size_t)k_out * k_in * ng, 0);
+    std::vector<char> has((size_t)k_out * ng, 0);
+    int64_t first = 0;
+    for (int o = 0; o < k_out; ++o) {
+        if (!out0[o] || !out1[o]) return LF_ERR_ARG;
+        bool any = false;
+        for (int i = 0; i < k_in; ++i)
+            for (int j = 0; j < ng; ++j) {
+                const int64_t b = block(o, i, j);
+                if (!pt[b]) {
+                    if (gcount[b] != 0) return LF_ERR_ARG;
+                    continue;
+                }
+                any = true, has[(size_t)o * ng + j] = 1;
+                if (gcount[b] < 1 || gcount[b] > ncol[i] + 1 || pt_stride[b] < (int64_t)rows * N) return LF_ERR_ARG;
+                for (int64_t k = 0; k < gcount[b]; ++k) {
+                    const int64_t slot = bidx[first + k];
+                    if (slot < 0 || slot > ncol[i] || (k && slot <= bidx[first + k - 1])) return LF_ERR_ARG;
+                    masks[b] |= 1ull << slot;
+                }
+                first += gcount[b];
+            }
+        if (!any) return LF_ERR_ARG;
+    }
+    std::vector<int> sidx((size_t)k_out * ng, -1);
+    int keyed_sums = 0;
+    for (int j = 0; j < ng; ++j) {
+        if (gp_host[j] == 0) continue;
+        bool any = false;
+        for (int o = 0; o < k_out; ++o)
+            if (has[(size_t)o * ng + j]) sidx[(size_t)o * ng + j] = keyed_sums++, any = true;
+        if (!any) return LF_ERR_ARG;   // a keyed giant step no output uses
+    }
+    if (keyed_sums > LF_LT_MATMUL_BSGS_MAX_SUMS) return LF_ERR_ARG;
+    const int64_t need = lf_lt_matmul_bsgs_ws_words(p, nb_max, k_out, keyed_sums);
+    if (!need || !ws || ws_words < need || ((uintptr_t)ws & 15)) return LF_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const int g4 = k_out < LF_LT_MATMUL_GROUP ? k_out : LF_LT_MATMUL_GROUP, gw = bsgs_giant_group(p);
+    int64_t *u = ws, *A = u + (nb_max + 1) * pair, *S = A + k_out * pair, *w = S + keyed_sums * pair, *md = w + gw * poly,
+            *mdws = md + 2 * g4 * poly;
+    const int64_t md_w = lf_ks_moddown_ws_words(gw, ell, p->K, N), md_t = lf_ks_moddown_ws_words(2 * g4, ell, p->K, N);
+    const int64_t mdws_words = md_w > md_t ? md_w : md_t;
+    auto target = [&](int o, int j) { return gp_host[j] == 0 ? A + o * pair : S + sidx[(size_t)o * ng + j] * pair; };
+    if (int e = lf_set_device(dev)) return e;
+    // slot 0 holds nothing on the special rows, for every input; an output without giant step 0 starts from a zero accumulator
+    for (int c = 0; c < 2; ++c)
+        if (hipError_t e = hipMemsetAsync(u + c * (int64_t)rows * N + poly, 0, (size_t)p->K * N * 8, st)) return (int)e;
+    for (int o = 0; o < k_out; ++o)
+        if (!(gp_host[0] == 0 && has[(size_t)o * ng]))
+            if (hipError_t e = hipMemsetAsync(A + o * pair, 0, (size_t)pair * 8, st)) return (int)e;
+    // 1. input-major (steps 1 - 3 of lf_lt_matmul, the pairs (o, j) in the place of the outputs)
+    std::vector<char> written((size_t)k_out * ng, 0);
+    for (int i = 0; i < k_in; ++i) {
+        if (!used[i]) continue;
+        const int nb = (int)ncol[i];
+        {
+            const int64_t *srcs[2] = {in[2 * i], in[2 * i + 1]};
+            int64_t *dsts[2] = {u, u + (int64_t)rows * N};
+            if (int e = lf_galois_batch(srcs, dsts, 2, ell, logN, 1, p->_2q, dev, stream)) return e;
+            for (int c = 0; c < 2; ++c) {
+                if (int e = lf_ntt(dsts[c], 1, ell, logN, p->psi, p->psi_dp, p->q_host, p->Rs, 0, p->_2q, p->ql, p->qh, p->kl, p->kh, dev, stream))
+                    return e;
+                if (int e = lf_mont_enter(dsts[c], p->PR, ell, N, p->ql, p->qh, p->kl, p->kh, dev, stream)) return e;
+            }
+        }
+        if (nb) {
+            if (int e = lf_ks_digits_galois(in[2 * i + 1], p->state, p->dig_nparts, p->dig_desc, p->dig_tab, N, 1, p->_2q, p->ql, p->qh,
+                                            p->kl, p->kh, dev, stream))
+                return e;
+            if (int e = lf_ks_fwd(p->state, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, p->ext, p->psi, p->psi_dp, p->q_host, p->ql, p->qh,
+                                  p->kl, p->kh, dev, stream))
+                return e;
+            if (int e = lf_ks_baby_sums(nb, bp_host + koff[i], p->nparts, rows, ell, logN, bksk + koff[i], part_stride, comp_stride, row_off,
+                                        key_format, u, p->ext, u + pair, p->q_host, p->ql, p->qh, p->kl, p->kh, st))
+                return e;
+        }
+        std::vector<int> ts;   // the targets o * ng + j with a diagonal in this column
+        for (int o = 0; o < k_out; ++o)
+            for (int j = 0; j < ng; ++j)
+                if (pt[block(o, i, j)]) ts.push_back(o * ng + j);
+        for (size_t a0 = 0; a0 < ts.size();) {
+            const size_t left = ts.size() - a0;
+            const int g = left >= 4 ? 4 : left >= 2 ? 2 : 1;
+            const int64_t *pts[4];
+            int64_t *outs[4], strides[4];
+            unsigned long long slots[4];
+            int fresh[4];
+            for (int t = 0; t < g; ++t) {
+                const int o = ts[a0 + t] / ng, j = ts[a0 + t] % ng;
+                const int64_t b = block(o, i, j);
+                pts[t] = pt[b], strides[t] = pt_stride[b], slots[t] = masks[b], outs[t] = target(o, j), fresh[t] = !written[ts[a0 + t]];
+                written[ts[a0 + t]] = 1;
+            }
+            if (int e = lf_lt_block_products(g, u, nb + 1, pts, slots, strides, outs, fresh, rows, logN, p->ql, p->qh, p->kl, p->kh, st))
+                return e;
+            a0 += g;
+        }
+    }
+    // 2. giant-step-major: the outputs that have the giant step, 4, 2 or 1 per key stream
+    for (int j = 0; j < ng; ++j) {
+        if (gp_host[j] == 0) continue;
+        std::vector<int> os;
+        for (int o = 0; o < k_out; ++o)
+            if (has[(size_t)o * ng + j]) os.push_back(o);
+        for (size_t a0 = 0; a0 < os.size();) {
+            const size_t left = os.size() - a0;
+            const int n = (left >= 4 && gw >= 4) ? 4 : (left >= 2 && gw >= 2) ? 2 : 1;
+            const int64_t *ss[4], *s0s[4], *srcs[4];
+            int64_t *ws1[4], *accs[4], *states[4];
+            for (int t = 0; t < n; ++t) {
+                int64_t *S0 = target(os[a0 + t], j), *S1 = S0 + (int64_t)rows * N;
+                // S^{o,g}_1 down to Q: inverse NTT (the pair layout stays), then the group's mod-down, digits, extension and transform
+                if (int e = lf_intt(S1, 1, rows, logN, p->ipsi, p->ipsi_dp, p->q_host, p->Ninv, 2, 0, p->_2q, p->ql, p->qh, p->kl, p->kh, dev,
+                                    stream))
+                    return e;
+                ss[t] = S1, s0s[t] = S0, ws1[t] = w + t * poly, srcs[t] = ws1[t], states[t] = p->state + t * poly, accs[t] = A + os[a0 + t] * pair;
+            }
+            if (int e = lf_ks_moddown_ws(ss, ws1, nullptr, n, ell, p->K, N, mdws, mdws_words, p->PiR, p->PiP, p->Rs, 0, nullptr, p->ql, p->qh,
+                                         p->kl, p->kh, dev, stream))
+                return e;
+            if (int e = lf_ks_digits_batch(srcs, states, n, p->dig_nparts, p->dig_desc, p->dig_tab, N, 1, p->_2q, p->ql, p->qh, p->kl, p->kh,
+                                           dev, stream))
+                return e;
+            if (n == 1) {
+                if (int e = lf_ks_fwd(p->state, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, p->ext, p->psi, p->psi_dp, p->q_host, p->ql,
+                                      p->qh, p->kl, p->kh, dev, stream))
+                    return e;
+                if (int e = lf_ks_giant_sums(gp_host[j], p->nparts, rows, logN, gksk[j], part_stride, comp_stride, row_off, key_format, p->ext,
+                                             s0s[0], accs[0], p->q_host, p->ql, p->qh, p->kl, p->kh, st))
+                    return e;
+            } else {
+                if (int e = lf_ks_fwd_batch(p->state, poly, n, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, p->ext, p->psi, p->psi_dp,
+                                            p->q_host, p->ql, p->qh, p->kl, p->kh, st))
+                    return e;
+                if (int e = lf_ks_giant_sums_batch(n, gp_host[j], p->nparts, rows, logN, gksk[j], part_stride, comp_stride, row_off, key_format,
+                                                   p->ext, s0s, accs, p->q_host, p->ql, p->qh, p->kl, p->kh, st))
+                    return e;
+            }
+            a0 += n;
+        }
+    }
+    // 3. the tail (step 4 of lf_lt_matmul): per group of outputs one exact inverse NTT of its 2 g accumulator polynomials, one
+    // mod-down, one rescale
+    for (int o0 = 0; o0 < k_out; o0 += LF_LT_MATMUL_GROUP) {
+        const int g = k_out - o0 < LF_LT_MATMUL_GROUP ? k_out - o0 : LF_LT_MATMUL_GROUP;
+        int64_t *Ag = A + o0 * pair;
+        if (int e = lf_intt(Ag, 2 * g, rows, logN, p->ipsi, p->ipsi_dp, p->q_host, p->Ninv, 2, 0, p->_2q, p->ql, p->qh, p->kl, p->kh, dev, stream))
+            return e;
+        const int64_t *ss[2 * LF_LT_MATMUL_GROUP], *ins[2 * LF_LT_MATMUL_GROUP], *row0[2 * LF_LT_MATMUL_GROUP];
+        int64_t *mds[2 * LF_LT_MATMUL_GROUP], *outs[2 * LF_LT_MATMUL_GROUP];
+        for (int t = 0; t < 2 * g; ++t) {
+            ss[t] = Ag + t * (int64_t)rows * N;
             mds[t] = md + t * poly;
             row0[t] = mds[t], ins[t] = mds[t] + N;
             outs[t] = (t & 1) ? out1[o0 + t / 2] : out0[o0 + t / 2];

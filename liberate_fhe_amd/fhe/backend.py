@@ -11,7 +11,7 @@ import ctypes
 
 import torch
 
-from .._native import lib, check, KsPlan, LF_KEY_PLANES
+from .._native import lib, check, KsPlan, LF_KEY_PLANES, LF_LT_MATMUL_BSGS_MAX_GIANTS, LF_LT_MATMUL_BSGS_MAX_SUMS
 from ..ntt import ntt_cuda, twiddles
 
 
@@ -622,6 +622,61 @@ class HipBackend:
                                kb, ps, cs, row_off, fmt.pop() if fmt else 0, pts, i64(strides), i64(counts), i64(slots), _p(scales),
                                round_at, _p(ws), ws.numel(), _parr([o[0] for o in outs]), _parr([o[1] for o in outs]), st),
               "lf_lt_matmul")
+
+    # include/ckks_hip.h: LF_LT_MATMUL_BSGS_MAX_GIANTS / LF_LT_MATMUL_BSGS_MAX_SUMS through _native.py's copies
+    # (tests/test_lt_matmul_bsgs_cpu.py holds them to the header): the giant steps and the keyed inner sums of one lf_lt_matmul_bsgs call
+    lt_matmul_bsgs_max_giants = LF_LT_MATMUL_BSGS_MAX_GIANTS
+    lt_matmul_bsgs_max_sums = LF_LT_MATMUL_BSGS_MAX_SUMS
+
+    @staticmethod
+    def lt_matmul_bsgs_ws_words(plan, nb_max, k_out, keyed_sums):
+        return int(lib.lf_lt_matmul_bsgs_ws_words(ctypes.byref(plan), nb_max, k_out, keyed_sums))
+
+    def lt_matmul_bsgs_native(self, plan, ins, col_exps, col_keys, giant_exps, giant_keys, first_part, row_off, blocks, scales,
+                              round_at, outs, ws):
+        """A k_out x k_in matrix of baby-step / giant-step diagonal sets times k_in ciphertexts as ONE native call
+        (lf_lt_matmul_bsgs).  ins / col_exps / col_keys: as lt_matmul_native, for the keyed BABY steps of each column; giant_exps /
+        giant_keys: per giant step its exponent and packed key (0 and None for the giant step 0, which comes first); blocks: k_out
+        rows of k_in entries, None or (pack [k, rows, N], per giant step None or (first, slots)): the block's encoded diagonals
+        in (giant, baby) order, per giant step the index of its first diagonal in the pack and the column slot of each,
+        ascending; outs: k_out tensors [2, ell - 1, N]; ws: at least lt_matmul_bsgs_ws_words(..) words."""
+        dev, st = _ds(outs[0])
+        k_in, k_out, ng = len(ins), len(blocks), len(giant_keys)
+        babies = [k for col in col_keys for k in col]
+        fmt = {self._kfmt(k) for k in babies + [k for k in giant_keys if k is not None]}
+        if len(fmt) > 1:
+            raise ValueError("lt_matmul_bsgs_native: the keys of one call must share one format")
+        ps = cs = 0
+        kb, gb = (ctypes.c_void_p * max(len(babies), 1))(), (ctypes.c_void_p * max(ng, 1))()
+        for j, key in enumerate(babies):
+            kb[j], ps, cs = self._key_args(key, first_part)
+        for j, key in enumerate(giant_keys):
+            if key is not None:
+                gb[j], ps, cs = self._key_args(key, first_part)
+        i64 = lambda v: (ctypes.c_int64 * max(len(v), 1))(*v)
+        inp = (ctypes.c_void_p * (2 * k_in))()
+        for i, pair in enumerate(ins):
+            if pair is not None:
+                inp[2 * i], inp[2 * i + 1] = pair[0].data_ptr(), pair[1].data_ptr()
+        pts = (ctypes.c_void_p * (k_out * k_in * ng))()
+        strides, counts, slots = [0] * (k_out * k_in * ng), [0] * (k_out * k_in * ng), []
+        for o, row in enumerate(blocks):
+            for i, blk in enumerate(row):
+                if blk is None:
+                    continue
+                pack, per_giant = blk
+                for j, part in enumerate(per_giant):
+                    if part is None:
+                        continue
+                    first, sl = part
+                    e = (o * k_in + i) * ng + j
+                    pts[e] = pack.data_ptr() + first * pack.stride(0) * 8
+                    strides[e], counts[e] = pack.stride(0), len(sl)
+                    slots += list(sl)
+        check(lib.lf_lt_matmul_bsgs(ctypes.byref(plan), k_in, k_out, inp, i64([len(c) for c in col_keys]),
+                                    i64([e for c in col_exps for e in c]), kb, ng, i64(giant_exps), gb, ps, cs, row_off,
+                                    fmt.pop() if fmt else 0, pts, i64(strides), i64(counts), i64(slots), _p(scales), round_at, _p(ws),
+                                    ws.numel(), _parr([o[0] for o in outs]), _parr([o[1] for o in outs]), st), "lf_lt_matmul_bsgs")
 
     def ks_gather(self, ext, dst, index, rows, logN, c: Consts):
         """dst[p][r][k] = ext[p][r][index[k]] for extended digits as ks_fwd leaves them: fp64-class rows of a mixed stack in the

@@ -2225,45 +2225,10 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps):
 
         # orchestrated: the same words through the engine's steps (see linear_transform's own orchestration for the pieces)
         tabs = self._ks_tables(level)
-        loc, loc0 = self._loc(level), self._loc(0, special=True)
+        loc = self._loc(level)
         K, n = self.ntt.num_special_primes, self.ntt
-        nparts = len(tabs["order"])
-        fused = logN >= self.backend.fused_ks_min_logN
-        gather = getattr(self.backend, "ks_gather", None)
-
-        def forward(d, digits):
-            """extension + forward NTT of the exchanged digits on device d, kept aside in the buffer the keys gather from"""
-            rows, cs, tw = self._rows(d, level, True), self._consts(d, level, True), self._tw(d, level, True)
-            desc, E, Ed = tabs[("extend", d)]
-            ext = self._ws("ks_ext", (nparts, rows, N), d)
-            dig, ready = digits[d]
-            for handle, first, count in ready:
-                if handle is not None:
-                    handle.wait()
-                if fused:
-                    self.backend.ks_fwd(dig, first, count, rows, logN, desc, E, Ed, ext, tw, cs)
-            if not fused:
-                self.backend.ks_extend(dig, ext, nparts, rows, desc, E, cs)
-                self.backend.ntt(ext, nparts, rows, logN, tw, None, cs, relaxed=True)
-            self._ws("ks_ext_hoisted", (nparts, rows, N), d).copy_(ext)
-
-        def inner(d, idx, key):
-            """sum over the parts of (the digits gathered by idx) times the key part: [2, rows, N], NTT domain, Montgomery form"""
-            rows, cs = self._rows(d, level, True), self._consts(d, level, True)
-            ext, src = self._ws("ks_ext", (nparts, rows, N), d), self._ws("ks_ext_hoisted", (nparts, rows, N), d)
-            s = self._ws("ks_sum", (2, rows, N), d)
-            if gather is not None:
-                gather(src, ext, idx, rows, logN, cs)
-            else:
-                torch.index_select(src, 2, idx, out=ext)
-            kp = self._key_pack(key)[loc0.index(d)]
-            if fused:
-                self.backend.ks_tail(nparts, rows, logN, kp, tabs["first_part"], self.ntt.starts[level][d], ext, s,
-                                     self._tw(d, level, True, True), self._vec("Ninv", d, level, True), cs)
-                self.backend.ntt(s, 2, rows, logN, self._tw(d, level, True), self._vec("Rs", d, level, True), cs)
-            else:
-                self.backend.ks_inner(ext, kp, tabs["first_part"], self.ntt.starts[level][d], s[0], s[1], nparts, rows, cs)
-            return s.clone()
+        forward = lambda d, digits: self._lt_forward(level, d, digits)
+        inner = lambda d, idx, key: self._lt_inner(level, d, idx, key)
 
         # baby steps: u^b per device, kept for every giant step
         digits = self._ks_digits_exchanged(ct.data[1], level, galois=(1, True)) if kb else {}
@@ -2346,6 +2311,50 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps):
                                        self._vec("Rs", d, level, True), cs, PiP=tabs[("pip", d)], **mkw)
             c0o.append(out[0]); c1o.append(out[1])
         return self.rescale(self._new((c0o, c1o), types.origins["ct"], level=level))
+
+    def _lt_forward(self, level, d, digits):
+        """extension + forward NTT of the exchanged digits on device d, kept aside in the buffer the keys gather from (the shared
+        half of the orchestrated baby-step / giant-step forms: _linear_transform_bsgs, _lt_matmul_bsgs_steps)"""
+        N, logN = self.ctx.N, self.ctx.logN
+        tabs = self._ks_tables(level)
+        nparts = len(tabs["order"])
+        fused = logN >= self.backend.fused_ks_min_logN
+        rows, cs, tw = self._rows(d, level, True), self._consts(d, level, True), self._tw(d, level, True)
+        desc, E, Ed = tabs[("extend", d)]
+        ext = self._ws("ks_ext", (nparts, rows, N), d)
+        dig, ready = digits[d]
+        for handle, first, count in ready:
+            if handle is not None:
+                handle.wait()
+            if fused:
+                self.backend.ks_fwd(dig, first, count, rows, logN, desc, E, Ed, ext, tw, cs)
+        if not fused:
+            self.backend.ks_extend(dig, ext, nparts, rows, desc, E, cs)
+            self.backend.ntt(ext, nparts, rows, logN, tw, None, cs, relaxed=True)
+        self._ws("ks_ext_hoisted", (nparts, rows, N), d).copy_(ext)
+
+    def _lt_inner(self, level, d, idx, key):
+        """sum over the parts of (the digits _lt_forward left, gathered by idx) times the key part: a fresh [2, rows, N], NTT
+        domain, Montgomery form"""
+        N, logN = self.ctx.N, self.ctx.logN
+        tabs = self._ks_tables(level)
+        nparts = len(tabs["order"])
+        rows, cs = self._rows(d, level, True), self._consts(d, level, True)
+        ext, src = self._ws("ks_ext", (nparts, rows, N), d), self._ws("ks_ext_hoisted", (nparts, rows, N), d)
+        s = self._ws("ks_sum", (2, rows, N), d)
+        gather = getattr(self.backend, "ks_gather", None)
+        if gather is not None:
+            gather(src, ext, idx, rows, logN, cs)
+        else:
+            torch.index_select(src, 2, idx, out=ext)
+        kp = self._key_pack(key)[self._loc(0, special=True).index(d)]
+        if logN >= self.backend.fused_ks_min_logN:
+            self.backend.ks_tail(nparts, rows, logN, kp, tabs["first_part"], self.ntt.starts[level][d], ext, s,
+                                 self._tw(d, level, True, True), self._vec("Ninv", d, level, True), cs)
+            self.backend.ntt(s, 2, rows, logN, self._tw(d, level, True), self._vec("Rs", d, level, True), cs)
+        else:
+            self.backend.ks_inner(ext, kp, tabs["first_part"], self.ntt.starts[level][d], s[0], s[1], nparts, rows, cs)
+        return s.clone()
 
     def _prepare_ks(self, key, level):
         """Build, on the CURRENT stream, every lazily built piece of shared state a key switch at `level` under

@@ -8,6 +8,10 @@ times rotations).  The key-switched rotations of x_i do not depend on the output
 all outputs; the sums over the inputs stay in Q P and every output is brought down once.  Like the engine's other options beyond
 the reference, the words are DEFINED as a composition of steps the engine already has (written out in lt_matmul's docstring), and
 that composition is what runs wherever the native call (lf_lt_matmul) does not apply.  DESIGN.md §4.2.
+
+lt_matmul_bsgs is the same matrix over baby-step / giant-step blocks (encode_diagonals(.., bsgs=n1)): the baby rotations are formed
+once per input, the inner sums of all inputs of one output are added in Q P before the giant key switch, and the outputs that share
+a giant step share the stream of its key (lf_lt_matmul_bsgs).
 """
 from __future__ import annotations
 
@@ -70,6 +74,37 @@ class LtMatmulOps:
                 raise ValueError(f"lt_matmul: column {i} needs {len(keyed)} keyed steps, at most {self.lt_matmul_max_column_keys}")
         return W, steps
 
+    def _lt_matmul_operands(self, name, W, cts, rotks):
+        """(cts as a list, {step: key}, level): the checks of lt_matmul and lt_matmul_bsgs on the ciphertexts, the keys and the
+        levels, in their order; nothing is encoded or allocated here."""
+        cts = list(cts)
+        k_in = len(W[0])
+        if len(cts) != k_in:
+            raise ValueError(f"{name}: rows of {k_in} blocks beside {len(cts)} ciphertexts")
+        for ct in cts:
+            if not is_struct(ct) or ct.origin != types.origins["ct"]:
+                raise errors.NotMatchType(origin=getattr(ct, "origin", type(ct).__name__), to=types.origins["ct"])
+        keys = list(rotks.values()) if isinstance(rotks, dict) else list(rotks)
+        by_step = {}
+        for k in keys:
+            if not is_struct(k) or types.origins["rotk"] not in k.origin:
+                raise errors.NotMatchType(origin=getattr(k, "origin", type(k).__name__), to=types.origins["rotk"])
+            by_step.setdefault(int(k.origin.split(":")[-1]) % self.num_slots, k)
+        for ct in cts:
+            if ct.ntt_state or ct.include_special:
+                raise NotImplementedError(f"{name}: coefficient-domain ciphertexts without special limbs only")
+        level = cts[0].level
+        for ct in cts:
+            if ct.level != level:
+                raise errors.NotMatchDataStructState(origin=f"{ct.origin} at level {ct.level} beside level {level}")
+        for row in W:
+            for b in row:
+                if is_struct(b) and b.level != level:
+                    raise errors.NotMatchDataStructState(origin=f"{b.origin} at level {b.level}, ciphertexts at level {level}")
+        if level + 1 >= self.num_levels:
+            raise errors.MaximumLevelError(level=level, level_max=self.num_levels)
+        return cts, by_step, level
+
     def lt_matmul_steps(self, W) -> list:
         """The sorted non-zero steps lt_matmul(W, ..) needs a rotation key for (one key per step serves every input)."""
         _, steps = self._lt_matmul_blocks(W)
@@ -95,32 +130,8 @@ class LtMatmulOps:
         repeats the rotations of its inputs, so more than 64 outputs pay them again; otherwise the same words through the
         engine's steps, the rotated sums formed once per input and step and accumulated into every output that uses them."""
         W, steps = self._lt_matmul_blocks(W)
-        cts = list(cts)
         k_out, k_in = len(W), len(W[0])
-        if len(cts) != k_in:
-            raise ValueError(f"lt_matmul: rows of {k_in} blocks beside {len(cts)} ciphertexts")
-        for ct in cts:
-            if not is_struct(ct) or ct.origin != types.origins["ct"]:
-                raise errors.NotMatchType(origin=getattr(ct, "origin", type(ct).__name__), to=types.origins["ct"])
-        keys = list(rotks.values()) if isinstance(rotks, dict) else list(rotks)
-        by_step = {}
-        for k in keys:
-            if not is_struct(k) or types.origins["rotk"] not in k.origin:
-                raise errors.NotMatchType(origin=getattr(k, "origin", type(k).__name__), to=types.origins["rotk"])
-            by_step.setdefault(int(k.origin.split(":")[-1]) % self.num_slots, k)
-        for ct in cts:
-            if ct.ntt_state or ct.include_special:
-                raise NotImplementedError("lt_matmul: coefficient-domain ciphertexts without special limbs only")
-        level = cts[0].level
-        for ct in cts:
-            if ct.level != level:
-                raise errors.NotMatchDataStructState(origin=f"{ct.origin} at level {ct.level} beside level {level}")
-        for row in W:
-            for b in row:
-                if is_struct(b) and b.level != level:
-                    raise errors.NotMatchDataStructState(origin=f"{b.origin} at level {b.level}, ciphertexts at level {level}")
-        if level + 1 >= self.num_levels:
-            raise errors.MaximumLevelError(level=level, level_max=self.num_levels)
+        cts, by_step, level = self._lt_matmul_operands("lt_matmul", W, cts, rotks)
         for s in sorted({s for srow in steps for b in srow if b is not None for s in b if s}):
             if s not in by_step:
                 raise errors.NotMatchType(origin=f"no key for step {s}", to=types.origins["rotk"] + str(s))
@@ -266,5 +277,287 @@ class LtMatmulOps:
                                            self._vec("Rs", d, level, True), cs, PiP=tabs[("pip", d)], **mkw)
                 c0o.append(out[0]); c1o.append(out[1])
             S[o] = None
+            outs.append(self.rescale(self._new((c0o, c1o), types.origins["ct"], level=level)))
+        return outs
+
+    # =============================================================================================
+    # lt_matmul_bsgs: a matrix of baby-step / giant-step transforms (lf_lt_matmul_bsgs)
+    # =============================================================================================
+    # the largest group of outputs whose giant step under one key goes through ONE mod-down, digit launch, forward pass and key
+    # stream (4, 2 or 1: the batch the plan of the native call is asked for; 1 takes the single kernel everywhere: same words)
+    lt_matmul_bsgs_group = 4
+
+    def _lt_matmul_bsgs_blocks(self, W, n1):
+        """(W as a list of rows, per block its steps in the order of its data or None, n1): the checks that need nothing but the
+        matrix and n1.  Nothing is encoded or allocated here."""
+        W = [list(row) for row in W]
+        if n1 is not None:
+            n1 = encdec.bsgs_split([0], self.num_slots, n1)[0]            # (ValueError for anything but an integer >= 1)
+        if not W:
+            raise ValueError("lt_matmul_bsgs: at least one row of blocks")
+        k_in = len(W[0])
+        steps, tagged = [], set()
+        for row in W:
+            if len(row) != k_in:
+                raise ValueError(f"lt_matmul_bsgs: a row of {len(row)} blocks beside one of {k_in}")
+            if all(b is None for b in row):
+                raise ValueError("lt_matmul_bsgs: a row without a block")
+            srow = []
+            for b in row:
+                if b is None:
+                    srow.append(None)
+                elif is_struct(b):
+                    if not b.origin.startswith(types.origins["diag_bsgs"]):
+                        raise errors.NotMatchType(origin=b.origin, to=types.origins["diag_bsgs"])
+                    tagged.add(int(b.origin.split(":", 1)[1].split(";")[0]))
+                    srow.append(self.diagonal_steps(b))
+                elif isinstance(b, Mapping):
+                    s = sorted(int(k) % self.num_slots for k in b)
+                    if not s:
+                        raise ValueError("lt_matmul_bsgs: a block without a diagonal")
+                    if len(set(s)) != len(s):
+                        raise ValueError(f"lt_matmul_bsgs: a step given twice in one block (steps are taken mod {self.num_slots})")
+                    srow.append(s)
+                else:
+                    raise errors.NotMatchType(origin=getattr(b, "origin", type(b).__name__), to=types.origins["diag_bsgs"])
+            steps.append(srow)
+        if k_in < 1:
+            raise ValueError("lt_matmul_bsgs: at least one ciphertext")
+        if len(tagged) > 1:
+            raise ValueError(f"lt_matmul_bsgs: blocks encoded for different n1 ({sorted(tagged)})")
+        if tagged and n1 is not None and n1 not in tagged:
+            raise ValueError(f"lt_matmul_bsgs: n1 = {n1} beside blocks encoded for n1 = {min(tagged)}")
+        if not tagged and n1 is None:
+            raise ValueError("lt_matmul_bsgs: n1 is required when every block is a plain mapping")
+        n1 = min(tagged) if tagged else n1
+        if k_in > self.lt_matmul_max_inputs:
+            raise ValueError(f"lt_matmul_bsgs: {k_in} inputs, at most {self.lt_matmul_max_inputs}")
+        for i in range(k_in):
+            keyed = {s % n1 for srow in steps if srow[i] is not None for s in srow[i] if s % n1}
+            if len(keyed) > self.lt_matmul_max_column_keys:
+                raise ValueError(f"lt_matmul_bsgs: column {i} needs {len(keyed)} keyed baby steps, at most {self.lt_matmul_max_column_keys}")
+        return W, steps, n1
+
+    def lt_matmul_bsgs_steps(self, W, n1=None) -> tuple:
+        """(n1, baby steps, giant steps) of lt_matmul_bsgs(W, .., n1): both sorted, 0 included where present, each the union over
+        all blocks in the sense of bsgs_steps.  A rotation key is needed for every non-zero entry of either list (one key per
+        step serves every input and every output, as a baby and as a giant step)."""
+        _, steps, n1 = self._lt_matmul_bsgs_blocks(W, n1)
+        flat = [s for srow in steps for b in srow if b is not None for s in b]
+        return n1, sorted({s % n1 for s in flat}), sorted({s - s % n1 for s in flat})
+
+    def lt_matmul_bsgs(self, W, cts, rotks, n1=None) -> list:
+        """A matrix of baby-step / giant-step linear transforms times a vector of ciphertexts: the list of the k_out ciphertexts
+            y_o = sum_i sum_{step in steps(W[o][i])} diag_{o,i,step} * rotate(cts[i], step)
+        at level + 1 — lt_matmul for blocks of hundreds of diagonals, from the keys of the non-zero baby steps b = step mod n1 and
+        giant steps g = step - b alone (lt_matmul_bsgs_steps).  W: k_out rows of k_in entries, each an encode_diagonals(..,
+        bsgs=n1) object of the ciphertexts' level, a plain {step: vector} mapping (encoded here with bsgs=n1, each distinct
+        mapping object once) or None for a zero block; every row needs a block.  All blocks share one n1: that of the tagged
+        objects, with which the argument must agree if it is given; it is required when every block is a mapping.  cts and rotks
+        as in lt_matmul: one key per step serves every input and every output, and the same key may serve as a baby and as a
+        giant step; an input no output uses is legal and is not read.
+        The words are those of: per input i that some block uses c0, c1 made canonical, E_i and c^_i as linear_transform forms
+        them; per keyed baby step b of B_i = the union of the column's baby steps u^{i,b}_c = sum over the parts of E_i gathered
+        by pi_b times key b's part, u^{i,b}_0 += c^_{i,0} gathered on the ordinary rows (b = 0: u^{i,0}_c = c^_{i,c}, zero on the
+        special rows); per output o and giant step g of G_o = the union of the row's giant steps
+            S^{o,g}_c = sum_i sum_{b : g + b in steps(W[o][i])} mont_mult(pt_{o,i,g+b}, u^{i,b}_c),
+        summed over the inputs BEFORE anything comes down; g = 0: S^{o,0} joins the accumulator A^o; g != 0: w = mod-down without
+        addend of intt_exit_reduce(S^{o,g}_1), made canonical, E^{o,g} its digits extended and transformed, v_c = sum over the
+        parts of E^{o,g} gathered by pi_g times key g's part, v_0 += S^{o,g}_0 gathered on all ell + K rows, A^o += v; then
+        intt_exit_reduce(A^o), mod-down without addend, rescale.  Only residues of u, S, v and A reach the result, so the grouping
+        of the additions is free.  Hence: with k_in = 1 output o has word for word the words of linear_transform(cts[0], W[o][0],
+        rotks) in its baby-step / giant-step form; when every step is below n1 (the only giant step is 0) those of lt_matmul on
+        the same packs tagged flat; and output o depends on row o only.  For k_in > 1 with keyed giant steps the words are the
+        op's own — NOT those of cc_add over separate transforms.
+        One native call (lf_lt_matmul_bsgs) per 64 outputs, 64 giant steps and 256 keyed inner sums where every limb of the level
+        is on one device of this process (more outputs or keyed sums are split over calls, each of which repeats the baby steps);
+        otherwise the same words through the engine's steps (_lt_matmul_bsgs_steps) — which is also where a matrix goes that has
+        a single row beyond the caps of one call, more than 64 giant steps in one row: it is not run natively."""
+        W, steps, n1 = self._lt_matmul_bsgs_blocks(W, n1)
+        cts, by_step, level = self._lt_matmul_operands("lt_matmul_bsgs", W, cts, rotks)
+        flat = [s for srow in steps for b in srow if b is not None for s in b]
+        for s in sorted({s % n1 for s in flat} | {s - s % n1 for s in flat}):
+            if s and s not in by_step:
+                raise errors.NotMatchType(origin=f"no key for step {s}", to=types.origins["rotk"] + str(s))
+        # (every refusal is behind us: from here on things are encoded, allocated and launched)
+        encoded = {}
+        for row in W:
+            for i, b in enumerate(row):
+                if b is not None and not is_struct(b):
+                    if id(b) not in encoded:
+                        encoded[id(b)] = self.encode_diagonals(b, level, bsgs=n1)
+                    row[i] = encoded[id(b)]
+        steps = [[None if b is None else self.diagonal_steps(b) for b in row] for row in W]
+
+        d = self._native_level(level)
+        if d is not None and hasattr(self.backend, "lt_matmul_bsgs_native") and \
+                all(s is None or s == sorted(s) for srow in steps for s in srow) and \
+                all(ct.data[c][0].is_contiguous() for i, ct in enumerate(cts) if any(s[i] is not None for s in steps) for c in range(2)):
+            calls = self._lt_matmul_bsgs_calls(steps, n1)
+            if calls is not None:
+                return [out for o0, o1 in calls
+                        for out in self._lt_matmul_bsgs_native(W[o0:o1], steps[o0:o1], n1, cts, by_step, level, d)]
+        return self._lt_matmul_bsgs_steps(W, steps, n1, cts, by_step, level)
+
+    def _lt_matmul_bsgs_calls(self, steps, n1):
+        """The outputs as consecutive ranges (first, past the last), each within what one native call takes (outputs, giant steps,
+        keyed inner sums); None where a single row is beyond it (lt_matmul_bsgs then takes the orchestrated steps for the whole
+        matrix)."""
+        be = self.backend
+        calls, o0, giants, sums = [], 0, set(), 0
+        for o, srow in enumerate(steps):
+            g = {s - s % n1 for b in srow if b is not None for s in b}
+            keyed = len(g - {0})
+            if len(g) > be.lt_matmul_bsgs_max_giants or keyed > be.lt_matmul_bsgs_max_sums:
+                return None
+            if o > o0 and (o - o0 == be.lt_matmul_max_outputs or len(giants | g) > be.lt_matmul_bsgs_max_giants or
+                           sums + keyed > be.lt_matmul_bsgs_max_sums):
+                calls.append((o0, o))
+                o0, giants, sums = o, set(), 0
+            giants |= g
+            sums += keyed
+        calls.append((o0, len(steps)))
+        return calls
+
+    def _lt_matmul_bsgs_native(self, W, steps, n1, cts, by_step, level, d):
+        N, k_in = self.ctx.N, len(cts)
+        giants = sorted({s - s % n1 for srow in steps for b in srow if b is not None for s in b})   # (0 sorts first)
+        rows_of = {g: sum(any(b is not None and any(s - s % n1 == g for s in b) for b in srow) for srow in steps) for g in giants}
+        shared = any(g and rows_of[g] >= 2 for g in giants)
+        if self.lt_matmul_bsgs_group not in (1, 2, 4):
+            raise ValueError("lt_matmul_bsgs_group: 1, 2 or 4")
+        plan, _, first_part, row_off = self._op_plan(level, d, self.lt_matmul_bsgs_group if shared else 1)
+        i0 = self._loc(0, special=True).index(d)
+        li = self.local_ids.index(d)
+        owner = self.ntt.p.rescaler_loc[level]
+        round_at = self.ctx.q[self.ntt.p.destination_arrays[level][owner][0]] // 2
+        ins, col_exps, col_keys, slot = [], [], [], []
+        for i in range(k_in):
+            col = [s for s in steps if s[i] is not None]
+            keyed = sorted({t % n1 for s in col for t in s[i] if t % n1})
+            ins.append((cts[i].data[0][0], cts[i].data[1][0]) if col else None)
+            col_exps.append([encdec.galois_exponent(N, t) for t in keyed])
+            col_keys.append([self._key_pack(by_step[t])[i0] for t in keyed])
+            slot.append({0: 0, **{t: 1 + j for j, t in enumerate(keyed)}})
+
+        def per_giant(i, s):
+            """per giant step None, or (the index of its first diagonal in the block's pack, the column slots of its diagonals)"""
+            out = []
+            for g in giants:
+                at = [k for k, t in enumerate(s) if t - t % n1 == g]      # (ascending steps: one slice of the pack)
+                out.append((at[0], [slot[i][s[k] % n1] for k in at]) if at else None)
+            return out
+
+        blocks = [[None if b is None else (self._diag_pack(b)[li], per_giant(i, s[i])) for i, b in enumerate(row)]
+                  for row, s in zip(W, steps)]
+        nb_max = max(len(c) for c in col_keys)
+        keyed_sums = sum(rows_of[g] for g in giants if g)
+        ws = self._ws("lt_matmul_bsgs_ws", (self.backend.lt_matmul_bsgs_ws_words(plan, nb_max, len(W), keyed_sums),), d)
+        outs = [torch.empty((2, plan.ell - 1, N), dtype=torch.int64, device=self.ntt.devices[d]) for _ in W]
+        self.backend.lt_matmul_bsgs_native(plan, ins, col_exps, col_keys, [encdec.galois_exponent(N, g) if g else 0 for g in giants],
+                                           [self._key_pack(by_step[g])[i0] if g else None for g in giants], first_part, row_off,
+                                           blocks, self.rescale_scales[level][d], round_at, outs, ws)
+        return [self._new(([o[0]], [o[1]]), types.origins["ct"], level=level + 1) for o in outs]
+
+    def _lt_matmul_bsgs_steps(self, W, steps, n1, cts, by_step, level):
+        """The same words through the engine's steps — the pieces of _linear_transform_bsgs (_lt_forward, _lt_inner, the
+        one-polynomial mod-down, _ks_digits_exchanged per keyed (o, g)) in the order of _lt_matmul_steps: per used input the
+        digits of c1 and their exchange once, per baby step of the column the gather, the key's inner product and the products
+        with the diagonals of EVERY (output, giant step) that has it in this column; per keyed (o, g) S_1 down to Q, its digits,
+        the giant key's inner product and S_0 gathered on all rows into A^o; per output ONE inverse NTT, mod-down and rescale."""
+        N, logN = self.ctx.N, self.ctx.logN
+        tabs = self._ks_tables(level)
+        loc = self._loc(level)
+        K, n = self.ntt.num_special_primes, self.ntt
+        S = {}                                                            # (o, g) -> per device [S_0, S_1]
+
+        def accumulate(di, li, i, b, t):
+            mont = [x[li:li + 1] for x in n.mont_prepack[-2][level][0]]
+            _2q = [n._2q_prepack[-2][level][0][li]]
+            for o, (row, srow) in enumerate(zip(W, steps)):
+                if srow[i] is None:
+                    continue
+                for k, step in enumerate(srow[i]):
+                    if step % n1 != b:
+                        continue
+                    acc = S.setdefault((o, step - b), [[None, None] for _ in loc])[di]
+                    for comp in range(2):
+                        prod = n.ops.mont_mult([row[i].data[k][li]], [t[comp]], *mont)[0]
+                        acc[comp] = prod if acc[comp] is None else n.ops.mont_add([acc[comp]], [prod], _2q)[0]
+
+        for i, ct in enumerate(cts):
+            B = sorted({t % n1 for srow in steps if srow[i] is not None for t in srow[i]})
+            if not B:
+                continue                                                  # an input no output uses
+            keyed = [b for b in B if b]
+            digits = self._ks_digits_exchanged(ct.data[1], level, galois=(1, True)) if keyed else {}
+            for di, d in enumerate(loc):
+                li = self.local_ids.index(d)
+                rows, ell = self._rows(d, level, True), self._rows(d, level, False)
+                cso, g2q = self._consts(d, level, False), self._vec("_2q", d, level, False)
+                dev = self.ntt.devices[d]
+                # c^0, c^1 = P * enter_ntt(canonical c) on the ordinary rows
+                chat = torch.empty((2, ell, N), dtype=torch.int64, device=dev)
+                for comp in range(2):
+                    src = ct.data[comp][di] if ct.data[comp][di].is_contiguous() else ct.data[comp][di].contiguous()
+                    self.backend.galois(src, chat[comp], ell, logN, 1, g2q)
+                    self.backend.ntt(chat[comp], 1, ell, logN, self._tw(d, level, False), self._vec("Rs", d, level, False), cso)
+                    n.ops.mont_enter([chat[comp]], [self._PR(d, level)], *[x[li:li + 1] for x in n.mont_prepack[-1][level][0]])
+                if 0 in B:
+                    t = torch.zeros((2, rows, N), dtype=torch.int64, device=dev)
+                    t[:, :ell] = chat
+                    accumulate(di, li, i, 0, t)
+                if not keyed:
+                    continue
+                self._lt_forward(level, d, digits)
+                _2q = n._2q_prepack[-2][level][0][li]
+                for b in keyed:
+                    idx = self._galois_index(encdec.galois_exponent(N, b), d)
+                    t = self._lt_inner(level, d, idx, by_step[b])
+                    t[0, :ell] = n.ops.mont_add([t[0, :ell]], [chat[0].index_select(1, idx)], [_2q[:ell]])[0]
+                    accumulate(di, li, i, b, t)
+
+        outs = []
+        for o in range(len(W)):
+            A = [[None, None] for _ in loc]
+            for g in sorted(g for (oo, g) in S if oo == o):
+                Sg = S.pop((o, g))
+                if g:
+                    w = []
+                    for di, d in enumerate(loc):
+                        rows, ell = self._rows(d, level, True), self._rows(d, level, False)
+                        cs = self._consts(d, level, True)
+                        s1 = Sg[di][1].contiguous()
+                        self.backend.intt(s1, 1, rows, logN, self._tw(d, level, True, True), self._vec("Ninv", d, level, True), 2, cs)
+                        wd = torch.empty((ell, N), dtype=torch.int64, device=self.ntt.devices[d])
+                        ws, one = self._moddown_ws("ks_moddown_one_poly", 1, ell, K, d, tabs, cs)
+                        mkw = {"one_launch": True} if one else {}
+                        self.backend.ks_moddown_ws([s1], [wd], [None], ell, K, ws, tabs[("pir", d)], self._vec("Rs", d, level, True), cs,
+                                                   PiP=tabs[("pip", d)], **mkw)
+                        w.append(wd)
+                    digits = self._ks_digits_exchanged(w, level, galois=(1, True))
+                    for di, d in enumerate(loc):
+                        li = self.local_ids.index(d)
+                        self._lt_forward(level, d, digits)
+                        idx = self._galois_index(encdec.galois_exponent(N, g), d)
+                        v = self._lt_inner(level, d, idx, by_step[g])
+                        v0 = n.ops.mont_add([v[0]], [Sg[di][0].index_select(1, idx)], [n._2q_prepack[-2][level][0][li]])[0]
+                        Sg[di] = [v0, v[1]]
+                for di, d in enumerate(loc):
+                    _2q = [n._2q_prepack[-2][level][0][self.local_ids.index(d)]]
+                    for comp in range(2):
+                        A[di][comp] = Sg[di][comp] if A[di][comp] is None else n.ops.mont_add([A[di][comp]], [Sg[di][comp]], _2q)[0]
+            c0o, c1o = [], []
+            for di, d in enumerate(loc):
+                rows, ell = self._rows(d, level, True), self._rows(d, level, False)
+                cs = self._consts(d, level, True)
+                s2 = torch.stack(A[di]).contiguous()
+                self.backend.intt(s2, 2, rows, logN, self._tw(d, level, True, True), self._vec("Ninv", d, level, True), 2, cs)
+                out = torch.empty((2, ell, N), dtype=torch.int64, device=self.ntt.devices[d])
+                ws, one = self._moddown_ws("ks_moddown", 2, ell, K, d, tabs, cs)
+                mkw = {"one_launch": True} if one else {}
+                self.backend.ks_moddown_ws([s2[0], s2[1]], [out[0], out[1]], [None, None], ell, K, ws, tabs[("pir", d)],
+                                           self._vec("Rs", d, level, True), cs, PiP=tabs[("pip", d)], **mkw)
+                c0o.append(out[0]); c1o.append(out[1])
             outs.append(self.rescale(self._new((c0o, c1o), types.origins["ct"], level=level)))
         return outs

@@ -115,6 +115,12 @@ def diagonal_matrix(blocks, k_in: int, k_out: int):
     return [[blocks[(o + 2 * i) % len(blocks)] for i in range(k_in)] for o in range(k_out)]
 
 
+def diagonal_matrix_bsgs(engine, seed: int, level: int, steps, n1: int, k_in: int, k_out: int, distinct: int = 3):
+    """A dense W for ckks_engine.lt_matmul_bsgs: k_out rows of k_in entries drawn in turn (as diagonal_matrix draws them) from
+    `distinct` diagonals_bsgs objects over `steps` under one n1, seeded seed, seed + 1, .."""
+    return diagonal_matrix([diagonals_bsgs(engine, seed + j, level, steps, n1) for j in range(distinct)], k_in, k_out)
+
+
 def _data_struct(engine):
     import importlib
     mod = importlib.import_module(type(engine).__module__.rsplit(".", 1)[0] + ".data_struct")

@@ -762,6 +762,36 @@ int lf_cc_dot_batch(const lf_ks_plan *plan, int nd, const int64_t *np_host, cons
                     const int64_t *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format, int64_t *ws,
                     int64_t ws_words, int64_t *const *out0, int64_t *const *out1, void *stream);
 
+/* A matrix of ciphertexts times a matrix of ciphertexts under ONE key: C[i][j] = sum_t A[i][t] * B[t][j], slot-wise, level l -> l + 1;
+ * A is m x k, B is k x n (attention scores, a bilinear layer, many small matrix products packed slot-wise).
+ * The nu DISTINCT operand ciphertexts: in / row0 are HOST arrays of 2 nu device pointers, [operand][component], in lf_cc_dot's
+ * convention (first surviving row resp. dropped row of c0, c1 at level l).  ia[i * k + t] / ib[t * n + j]: HOST tables of the
+ * operand in 0 .. nu - 1 that is A[i][t] resp. B[t][j], or -1 for a zero entry; an operand may appear anywhere in both, any number
+ * of times.  Key as for lf_cc_dot; out0 / out1: HOST arrays of m n device pointers, [i * n + j], [ell][N] each, canonical.
+ * Output (i, j) has exactly the words of lf_cc_dot on the pairs (A[i][t], B[t][j]) over the t where neither is a zero entry.
+ * Enqueued: (1) every distinct operand rescaled and forward-transformed ONCE — lf_rescale_ntt (RELAXED | PLAIN, PLANES where
+ * lf_stack_planes says so), 4 operands (8 polynomials) per call — into a resident store [nu][2][ell][N] at the head of `ws`
+ * (lf_cc_dot_batch transforms both operands of every pair of every dot: 2 m k n ciphertexts where m k + k n are distinct).
+ * (2) C is cut into tiles of R x C outputs, R C = 4, 2 or 1 and at most plan->max_nct: 2 x 2 where both dimensions allow it (and
+ * max_nct >= 4), strips of 1 x 4 / 4 x 1, 1 x 2 / 2 x 1 and 1 x 1 along a vector, an odd last column or row; per tile ONE launch
+ * of matmul_tensor_kernel<R, C>, which loads the R + C operands of an inner index once, sums the R C triplets over the whole inner
+ * dimension in registers and writes each once: T_d at ws + (2 nu + 3 d) ell N, its copy of T2 at plan->d2 + d ell N.  (3) per tile
+ * steps 3 to 5 of lf_cc_dot_batch for nd = R C (nd = 1: of lf_cc_dot): lf_intt of the copies, their digits, the pre-summed fold
+ * under the key, one mod-down.
+ * ws: lf_cc_matmul_ws_words(plan, nu) = (2 nu + 3 g) ell N words, g = min(4, plan->max_nct), 16-byte aligned, lent by the caller
+ * (0 for a plan or an nu the entry refuses).  An engine with more distinct operands than one call takes splits C by row blocks of
+ * A over several calls; the inner dimension is never split.
+ * LF_ERR_ARG before any launch for everything lf_cc_dot refuses, m, k or n below 1, k above LF_CC_MATMUL_MAX_INNER, nu outside
+ * 1 .. LF_CC_MATMUL_MAX_OPERANDS, ia or ib NULL or an entry outside -1 .. nu - 1, an operand that no entry uses, a NULL among the
+ * 2 nu pointers of in or row0, an output with no term, a NULL among the m n pointers of out0 or out1, ws NULL, not 16-byte
+ * aligned or too small. */
+#define LF_CC_MATMUL_MAX_INNER 64
+#define LF_CC_MATMUL_MAX_OPERANDS 256
+int64_t lf_cc_matmul_ws_words(const lf_ks_plan *plan, int nu);
+int lf_cc_matmul(const lf_ks_plan *plan, int m, int k, int n, int nu, const int64_t *const *in, const int64_t *const *row0,
+                 const int64_t *ia, const int64_t *ib, const int64_t *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off,
+                 int key_format, int64_t *ws, int64_t ws_words, int64_t *const *out0, int64_t *const *out1, void *stream);
+
 /* Several weighted sums of the same ciphertexts under ONE rescale (the baby-step sums of a polynomial evaluation): for
  * g < G, out_g = rescale(sum_{t < k} s_{g,t} ct_t) (+ a constant), level l -> l + 1, one launch per group of 4, 2 or 1 outputs
  * (weighted_sums_kernel<4 | 2 | 1>: every input word is read once per group).

@@ -112,6 +112,8 @@ _SIGNATURES["lf_cc_dot_ws_words"] = [_PL]
 _SIGNATURES["lf_cc_dot"] = [_PL, _I, _P, _P, _P, _L, _L, _L, _I, _P, _L, _P, _P, _P]
 _SIGNATURES["lf_cc_dot_batch_ws_words"] = [_PL, _I]
 _SIGNATURES["lf_cc_dot_batch"] = [_PL, _I, _P, _P, _P, _P, _L, _L, _L, _I, _P, _L, _P, _P, _P]
+_SIGNATURES["lf_cc_matmul_ws_words"] = [_PL, _I]
+_SIGNATURES["lf_cc_matmul"] = [_PL, _I, _I, _I, _I, _P, _P, _P, _P, _P, _L, _L, _L, _I, _P, _L, _P, _P, _P]
 _SIGNATURES["lf_weighted_sums"] =[_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _L, _P, _P, _P, _P, _I, _P]
 _SIGNATURES["lf_pc_dot_ws_words"] = [_I, _I, _I]
 _SIGNATURES["lf_pc_dot"] = [_I, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _I, _P]
@@ -178,5 +180,7 @@ LF_LT_MATMUL_MAX_INPUTS = 64   # include/ckks_hip.h: inputs per lf_lt_matmul cal
 LF_LT_MATMUL_MAX_OUTPUTS = 64  # .. and outputs per call
 LF_LT_MATMUL_BSGS_MAX_GIANTS = 64   # include/ckks_hip.h: giant steps per lf_lt_matmul_bsgs call
 LF_LT_MATMUL_BSGS_MAX_SUMS = 256    # .. and keyed inner sums (pairs of an output and a keyed giant step)
+LF_CC_MATMUL_MAX_INNER = 64         # include/ckks_hip.h: inner dimension of an lf_cc_matmul call
+LF_CC_MATMUL_MAX_OPERANDS = 256     # .. and distinct operands per call
 LF_ERR_ARG = 10001
 LF_ERR_STATE = 10002

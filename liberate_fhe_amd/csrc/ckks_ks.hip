@@ -830,6 +830,159 @@ __global__ void __launch_bounds__(256) pc_matmul_kernel(const i64 *__restrict__ 
         for (int c = 0; c < 2; ++c) *reinterpret_cast<longlong2 *>(s + (2 * g + c) * pstride) = o[g][c];
 }
 
+// ---- cc_matmul: the summed triplets of an R x C tile of C = A B, every operand of the tile read once per inner index ----------
+// x = [nu][2][ell][N]: the resident store of the DISTINCT operands, c0, c1 of each as lf_rescale_ntt(RELAXED | PLAIN) leaves them
+// (xpl: fp64-class rows as planes).  ix.a[t][i] / ix.b[t][j]: the operand that is A[i0 + i][t] resp. B[t][j0 + j], or -1 for a zero
+// entry (kernel arguments: every test on them is uniform over the launch).  Output d = i C + j of the tile:
+//     T0_d = sum_t x0 y0,   T1_d = sum_t (x0 y1 + x1 y0),   T2_d = sum_t x1 y1      (x = A[i0 + i][t], y = B[t][j0 + j])
+// written ONCE to T + d * 3 ell N (no read-modify-write: the whole inner dimension is summed in registers), T2_d a second time to
+// t2 + d * ell N, where its inverse transform runs in place.  grid and thread as dot_tensor_kernel; the loop over t is a run-time
+// one: a thread loads the R + C operand pairs of an inner index once and forms the R C products of that index from registers —
+// dot_tensor_kernel reads four operand polynomials per product.  The arithmetic is dot_tensor_kernel's, and only the residues of T
+// reach the result, so the words are those of lf_cc_dot on each output's pairs:
+//   fp64-class rows  balanced products (|.| <= q / 2): one inner index adds at most q / 2 to |T0|, |T2| and q to |T1|.  dp_reduce
+//                    takes |x| < 64 q, so at most 63 indices could be summed between two reductions; the accumulators are reduced
+//                    in registers (to [0, q)) after every LF_MATMUL_REDUCE_EVERY = 32 indices: |.| < q + 32 q = 33 q < 2^47 for
+//                    q < 2^41 — inside dp_reduce's range and the exact range 2^53 of fp64 for any inner dimension; stored as the
+//                    plain canonical residue, which does not depend on where the reductions fell;
+//   integer rows     REDC62 products of words below 2q are below 2q (q < 2^60); a conditional subtraction after every addition
+//                    makes every sum an addition mod 2q of words below 2q — associative and commutative, so the words do not
+//                    depend on the grouping (dot_tensor_kernel's chunks of 4) and the zero the accumulators start from changes
+//                    none: Montgomery form below 2q throughout.
+#define LF_MATMUL_REDUCE_EVERY 32
+static_assert(LF_MATMUL_REDUCE_EVERY + 1 < 64, "matmul_tensor_kernel: a run of inner indices must stay inside dp_reduce's |x| < 64 q");
+static_assert(LF_CC_MATMUL_MAX_OPERANDS <= 32767, "MatmulIdx keeps operand indices in 16 bits");
+struct MatmulIdx {
+    short a[LF_CC_MATMUL_MAX_INNER][4];   // [inner index][row of the tile]
+    short b[LF_CC_MATMUL_MAX_INNER][4];   // [inner index][column of the tile]
+};
+
+template <int R, int C>
+__global__ void __launch_bounds__(256) matmul_tensor_kernel(const i64 *__restrict__ x, MatmulIdx ix, int k, i64 *__restrict__ T,
+                                                            i64 *__restrict__ t2, int ell, i64 N, int xpl, const i64 *__restrict__ ql,
+                                                            const i64 *__restrict__ qh, const i64 *__restrict__ kl,
+                                                            const i64 *__restrict__ kh) {
+    static_assert(R * C == 1 || R * C == 2 || R * C == 4, "a tile has 1, 2 or 4 outputs");
+    constexpr int D = R * C;
+    const int r = blockIdx.y;
+    const i64 j0 = (i64)blockIdx.x * 512 + threadIdx.x * 2;
+    if (j0 >= N) return;
+    const RowMod m = load_mod(ql, qh, kl, kh, r);
+    const i64 pstride = (i64)ell * N, o0 = (i64)r * N + j0;
+    longlong2 o[D][3];
+    if (m.q < SMALL_PRIME_LIMIT) {
+        const RowDp d = make_dp(m);
+        double acc[D][3][2];
+#pragma unroll
+        for (int i = 0; i < D; ++i)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) acc[i][c][0] = acc[i][c][1] = 0.0;
+        for (int tb = 0; tb < k; tb += LF_MATMUL_REDUCE_EVERY) {
+            const int te = tb + LF_MATMUL_REDUCE_EVERY < k ? tb + LF_MATMUL_REDUCE_EVERY : k;
+            if (tb) {   // (uniform) the run before this one left |.| <= 33 q: back to [0, q)
+#pragma unroll
+                for (int i = 0; i < D; ++i)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c)
+#pragma unroll
+                        for (int e = 0; e < 2; ++e) acc[i][c][e] = dp_reduce(acc[i][c][e], d.q, d.qinv);
+            }
+            for (int t = tb; t < te; ++t) {
+                double a0[R][2], a1[R][2], b0[C][2], b1[C][2];
+#pragma unroll
+                for (int i = 0; i < R; ++i) {
+                    a0[i][0] = a0[i][1] = a1[i][0] = a1[i][1] = 0.0;
+                    const int u = ix.a[t][i];
+                    if (u < 0) continue;
+                    const i64 *p = x + (i64)u * 2 * pstride + (i64)r * N;
+                    ld_pair_dp(p, j0, N, xpl, a0[i][0], a0[i][1]);
+                    ld_pair_dp(p + pstride, j0, N, xpl, a1[i][0], a1[i][1]);
+                }
+#pragma unroll
+                for (int j = 0; j < C; ++j) {
+                    b0[j][0] = b0[j][1] = b1[j][0] = b1[j][1] = 0.0;
+                    const int u = ix.b[t][j];
+                    if (u < 0) continue;
+                    const i64 *p = x + (i64)u * 2 * pstride + (i64)r * N;
+                    ld_pair_dp(p, j0, N, xpl, b0[j][0], b0[j][1]);
+                    ld_pair_dp(p + pstride, j0, N, xpl, b1[j][0], b1[j][1]);
+                }
+#pragma unroll
+                for (int i = 0; i < R; ++i)
+#pragma unroll
+                    for (int j = 0; j < C; ++j) {
+                        if (ix.a[t][i] < 0 || ix.b[t][j] < 0) continue;   // a zero entry: no product
+#pragma unroll
+                        for (int e = 0; e < 2; ++e) {
+                            acc[i * C + j][0][e] += dp_mulmod_bal(a0[i][e], b0[j][e], d);
+                            acc[i * C + j][1][e] += dp_mulmod_bal(a0[i][e], b1[j][e], d) + dp_mulmod_bal(a1[i][e], b0[j][e], d);
+                            acc[i * C + j][2][e] += dp_mulmod_bal(a1[i][e], b1[j][e], d);
+                        }
+                    }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < D; ++i)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                o[i][c].x = dp_to_word(dp_reduce(acc[i][c][0], d.q, d.qinv));
+                o[i][c].y = dp_to_word(dp_reduce(acc[i][c][1], d.q, d.qinv));
+            }
+    } else {
+        i64 acc[D][3][2];
+#pragma unroll
+        for (int i = 0; i < D; ++i)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) acc[i][c][0] = acc[i][c][1] = 0;
+        for (int t = 0; t < k; ++t) {
+            u64 a0[R][2], a1[R][2], b0[C][2], b1[C][2];
+#pragma unroll
+            for (int i = 0; i < R; ++i) {
+                a0[i][0] = a0[i][1] = a1[i][0] = a1[i][1] = 0;
+                const int u = ix.a[t][i];
+                if (u < 0) continue;
+                const i64 *p = x + (i64)u * 2 * pstride + o0;
+                const longlong2 v0 = *reinterpret_cast<const longlong2 *>(p), v1 = *reinterpret_cast<const longlong2 *>(p + pstride);
+                a0[i][0] = (u64)v0.x, a0[i][1] = (u64)v0.y, a1[i][0] = (u64)v1.x, a1[i][1] = (u64)v1.y;
+            }
+#pragma unroll
+            for (int j = 0; j < C; ++j) {
+                b0[j][0] = b0[j][1] = b1[j][0] = b1[j][1] = 0;
+                const int u = ix.b[t][j];
+                if (u < 0) continue;
+                const i64 *p = x + (i64)u * 2 * pstride + o0;
+                const longlong2 v0 = *reinterpret_cast<const longlong2 *>(p), v1 = *reinterpret_cast<const longlong2 *>(p + pstride);
+                b0[j][0] = (u64)v0.x, b0[j][1] = (u64)v0.y, b1[j][0] = (u64)v1.x, b1[j][1] = (u64)v1.y;
+            }
+#pragma unroll
+            for (int i = 0; i < R; ++i)
+#pragma unroll
+                for (int j = 0; j < C; ++j) {
+                    if (ix.a[t][i] < 0 || ix.b[t][j] < 0) continue;
+#pragma unroll
+                    for (int e = 0; e < 2; ++e) {
+                        const i64 d0 = mm62u(a0[i][e], b0[j][e], m.q, m.k);
+                        const i64 d1 = csub(mm62u(a0[i][e], b1[j][e], m.q, m.k) + mm62u(a1[i][e], b0[j][e], m.q, m.k), m.q2);
+                        const i64 d2 = mm62u(a1[i][e], b1[j][e], m.q, m.k);
+                        acc[i * C + j][0][e] = csub(acc[i * C + j][0][e] + d0, m.q2);
+                        acc[i * C + j][1][e] = csub(acc[i * C + j][1][e] + d1, m.q2);
+                        acc[i * C + j][2][e] = csub(acc[i * C + j][2][e] + d2, m.q2);
+                    }
+                }
+        }
+#pragma unroll
+        for (int i = 0; i < D; ++i)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) o[i][c].x = acc[i][c][0], o[i][c].y = acc[i][c][1];
+    }
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) *reinterpret_cast<longlong2 *>(T + (i64)(3 * i + c) * pstride + o0) = o[i][c];
+        *reinterpret_cast<longlong2 *>(t2 + (i64)i * pstride + o0) = o[i][2];
+    }
+}
+
 // ---- K3 of hoisted rotations (lf_rotate_hoisted): ONE ciphertext's extended digits, NR keys with an exponent each ----------
 // X -> X^p permutes the NTT slots: NTT(a(X^p))[k] = NTT(a)[pi_p(k)], pi_p(k) = brev(((2 brev(k) + 1) p mod 2N - 1) / 2) (the forward
 // transform stores the evaluation at psi^(2 brev(k) + 1) at index k).  So the digits of c1, extended and transformed ONCE, serve every
@@ -1998,6 +2151,48 @@ int lf_pc_matmul_products(int go, int n, const int64_t *x, const int64_t *const 
         break;
     switch (go) { LF_PCMM_CASE(1) LF_PCMM_CASE(2) LF_PCMM_CASE(4) }
 #undef LF_PCMM_CASE
+    return (int)hipGetLastError();
+}
+
+// The launch of lf_cc_matmul that is its own (ckks_ops.hip checks the arguments).
+// lf_matmul_tensor: the summed triplets of an R x C tile (R C = 1, 2 or 4) over the inner dimension k <= LF_CC_MATMUL_MAX_INNER from the
+// store x = [nu][2][ell][N] of transformed operands (xpl: fp64-class rows as planes — refused where the library's note of that range
+// says another format); ta[t * R + i] / tb[t * C + j]: the operand of row i / column j of the tile at inner index t, in 0 .. nu - 1,
+// or -1; written to T = [R C][3][ell][N], the T2 copies to t2 = [R C][ell][N].
+int lf_matmul_tensor(int R, int C, int k, int nu, const int64_t *x, const int *ta, const int *tb, int64_t *T, int64_t *t2, int ell,
+                     int logN, int xpl, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st) {
+    if (R < 1 || C < 1 || R > 4 || C > 4 || (R * C != 1 && R * C != 2 && R * C != 4) || (R > 1 && C > 1 && R != C) || k < 1 ||
+        k > LF_CC_MATMUL_MAX_INNER || nu < 1 || nu > LF_CC_MATMUL_MAX_OPERANDS || !x || !ta || !tb || !T || !t2 || ell < 1 || ell > 65535 ||
+        logN < 9)
+        return LF_ERR_ARG;
+    const i64 N = (i64)1 << logN;
+    if (int e = lf_fmt_expect(x, ((size_t)2 * nu * ell << logN) * 8, xpl ? LF_FMT_PLANES : LF_FMT_RAW)) return e;
+    MatmulIdx ix{};
+    for (int t = 0; t < k; ++t) {
+        for (int i = 0; i < 4; ++i) ix.a[t][i] = ix.b[t][i] = -1;
+        for (int i = 0; i < R; ++i) {
+            if (ta[t * R + i] < -1 || ta[t * R + i] >= nu) return LF_ERR_ARG;
+            ix.a[t][i] = (short)ta[t * R + i];
+        }
+        for (int j = 0; j < C; ++j) {
+            if (tb[t * C + j] < -1 || tb[t * C + j] >= nu) return LF_ERR_ARG;
+            ix.b[t][j] = (short)tb[t * C + j];
+        }
+    }
+    const dim3 grid((unsigned)(N / 512), (unsigned)ell);
+#define LF_MM_LAUNCH(RR, CC)                                                                                                      \
+    hipLaunchKernelGGL((matmul_tensor_kernel<RR, CC>), grid, dim3(256), 0, st, (const i64 *)x, ix, k, (i64 *)T, (i64 *)t2, ell, N, xpl, \
+                       (const i64 *)ql, (const i64 *)qh, (const i64 *)kl, (const i64 *)kh)
+    switch (R * 8 + C) {
+        case 1 * 8 + 1: LF_MM_LAUNCH(1, 1); break;
+        case 1 * 8 + 2: LF_MM_LAUNCH(1, 2); break;
+        case 2 * 8 + 1: LF_MM_LAUNCH(2, 1); break;
+        case 1 * 8 + 4: LF_MM_LAUNCH(1, 4); break;
+        case 4 * 8 + 1: LF_MM_LAUNCH(4, 1); break;
+        case 2 * 8 + 2: LF_MM_LAUNCH(2, 2); break;
+        default: return LF_ERR_ARG;
+    }
+#undef LF_MM_LAUNCH
     return (int)hipGetLastError();
 }
 

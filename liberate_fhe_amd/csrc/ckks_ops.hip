@@ -83,6 +83,10 @@ int lf_pc_bias(int64_t *c0, const int64_t *pt, const int64_t *Rs, int rows, int 
 int lf_pc_matmul_products(int go, int n, const int64_t *x, const int64_t *const *pt, int pt_stride, int64_t *S, int rows, int logN,
                           int xpl, int first, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st);
 
+// ckks_ks.hip: the launch of lf_cc_matmul that is its own
+int lf_matmul_tensor(int R, int C, int k, int nu, const int64_t *x, const int *ta, const int *tb, int64_t *T, int64_t *t2, int ell,
+                     int logN, int xpl, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st);
+
 extern "C" {
 
 static int plan_ok(const lf_ks_plan *p) {
@@ -292,6 +296,144 @@ int lf_cc_dot_batch(const lf_ks_plan *p, int nd, const int64_t *np_host, const i
         outs[2 * d] = out0[d], outs[2 * d + 1] = out1[d];
     }
     return moddown_any(p, ss, outs, nullptr, 2 * nd, 0, nullptr, stream);
+}
+
+/* ---- cc_matmul: C = A B over ciphertexts under ONE key (include/ckks_hip.h): every distinct operand transformed once into a
+ * resident store, the triplets of a tile of outputs summed over the whole inner dimension in one launch, and lf_cc_dot_batch's
+ * steps behind the tensor products per tile. ---- */
+static int matmul_group(const lf_ks_plan *p) { return p->max_nct >= 4 ? 4 : p->max_nct >= 2 ? 2 : 1; }
+
+int64_t lf_cc_matmul_ws_words(const lf_ks_plan *p, int nu) {
+    if (!dot_ok(p) || nu < 1 || nu > LF_CC_MATMUL_MAX_OPERANDS) return 0;
+    return ((int64_t)(2 * nu + 3 * matmul_group(p)) * p->ell) << p->logN;
+}
+
+struct MatmulTile {
+    int i0, j0, R, C;
+};
+
+// a strip of `len` outputs from (i0, j0), along a row (1 x g tiles) or down a column (g x 1): g = 4, 2, 1, at most gmax
+static void matmul_strip(std::vector<MatmulTile> &tiles, int i0, int j0, int len, bool along_row, int gmax) {
+    for (int s = 0; s < len;) {
+        const int left = len - s, g = left >= 4 && gmax >= 4 ? 4 : left >= 2 && gmax >= 2 ? 2 : 1;
+        tiles.push_back(along_row ? MatmulTile{i0, j0 + s, 1, g} : MatmulTile{i0 + s, j0, g, 1});
+        s += g;
+    }
+}
+
+// the tiling of an m x n matrix of outputs (encdec.cc_matmul_tiles is the same rule): 2 x 2 where both dimensions allow it and a
+// tile may hold 4 outputs; strips along a vector, an odd last column and an odd last row
+static void matmul_tiles(std::vector<MatmulTile> &tiles, int m, int n, int gmax) {
+    if (n == 1 && m > 1) {
+        matmul_strip(tiles, 0, 0, m, false, gmax);
+    } else if (m == 1 || gmax < 4) {
+        for (int i = 0; i < m; ++i) matmul_strip(tiles, i, 0, n, true, gmax);
+    } else {
+        const int m2 = m & ~1, n2 = n & ~1;
+        for (int i = 0; i < m2; i += 2)
+            for (int j = 0; j < n2; j += 2) tiles.push_back(MatmulTile{i, j, 2, 2});
+        if (n & 1) matmul_strip(tiles, 0, n - 1, m, false, gmax);
+        if (m & 1) matmul_strip(tiles, m - 1, 0, n2, true, gmax);
+    }
+}
+
+// steps 3 to 5 of lf_cc_dot (nd = 1) resp. lf_cc_dot_batch (nd = 2, 4) on nd summed triplets at T, their T2 copies in plan->d2
+static int dot_tail(const lf_ks_plan *p, int nd, const int64_t *T, const int64_t *ksk, int64_t part_stride, int64_t comp_stride,
+                    int64_t row_off, int key_format, int64_t *const *out0, int64_t *const *out1, void *stream) {
+    const int ell = p->ell, rows = p->ell + p->K, logN = p->logN, dev = p->device;
+    const int64_t N = (int64_t)1 << logN, poly = (int64_t)ell * N;
+    if (int e = lf_intt(p->d2, nd, ell, logN, p->ipsi, p->ipsi_dp, p->q_host, p->Ninv, 2, LF_NTT_RELAXED | LF_NTT_PLAIN, p->_2q, p->ql, p->qh,
+                        p->kl, p->kh, dev, stream))
+        return e;
+    if (nd == 1) {
+        if (int e = lf_ks_digits(p->d2, p->state, p->dig_nparts, p->dig_desc, p->dig_tab, N, p->ql, p->qh, p->kl, p->kh, dev, stream)) return e;
+        if (int e = lf_dot_relin(p->state, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, ksk, part_stride, comp_stride, row_off,
+                                 key_format, p->ext, p->sum, p->psi, p->psi_dp, p->ipsi, p->ipsi_dp, p->Ninv, T, p->PR, ell, p->own,
+                                 p->q_host, p->ql, p->qh, p->kl, p->kh, (hipStream_t)stream))
+            return e;
+    } else {
+        const int64_t *srcs[4];
+        int64_t *states[4];
+        for (int d = 0; d < nd; ++d) srcs[d] = p->d2 + d * poly, states[d] = p->state + d * poly;
+        if (int e = lf_ks_digits_batch(srcs, states, nd, p->dig_nparts, p->dig_desc, p->dig_tab, N, 0, nullptr, p->ql, p->qh, p->kl, p->kh,
+                                       dev, stream))
+            return e;
+        if (int e = lf_dot_relin_batch(p->state, nd, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, ksk, part_stride, comp_stride,
+                                       row_off, key_format, p->ext, p->sum, p->psi, p->psi_dp, p->ipsi, p->ipsi_dp, p->Ninv, T, p->PR, ell,
+                                       p->own, p->q_host, p->ql, p->qh, p->kl, p->kh, (hipStream_t)stream))
+            return e;
+    }
+    const int64_t *ss[8];
+    int64_t *outs[8];
+    for (int d = 0; d < nd; ++d) {
+        ss[2 * d] = p->sum + (int64_t)(2 * d) * rows * N, ss[2 * d + 1] = p->sum + (int64_t)(2 * d + 1) * rows * N;
+        outs[2 * d] = out0[d], outs[2 * d + 1] = out1[d];
+    }
+    return moddown_any(p, ss, outs, nullptr, 2 * nd, 0, nullptr, stream);
+}
+
+int lf_cc_matmul(const lf_ks_plan *p, int m, int k, int n, int nu, const int64_t *const *in, const int64_t *const *row0,
+                 const int64_t *ia, const int64_t *ib, const int64_t *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off,
+                 int key_format, int64_t *ws, int64_t ws_words, int64_t *const *out0, int64_t *const *out1, void *stream) {
+    if (!dot_ok(p) || m < 1 || k < 1 || n < 1 || k > LF_CC_MATMUL_MAX_INNER || nu < 1 || nu > LF_CC_MATMUL_MAX_OPERANDS || !in || !row0 ||
+        !ia || !ib || !ksk || !out0 || !out1 || (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES))
+        return LF_ERR_ARG;
+    if ((int64_t)m * k > INT32_MAX || (int64_t)k * n > INT32_MAX || (int64_t)m * n > INT32_MAX) return LF_ERR_ARG;
+    if (key_format == LF_KEY_PLANES && ((((uintptr_t)ksk | (uintptr_t)(part_stride * 8) | (uintptr_t)(comp_stride * 8)) & 15)))
+        return LF_ERR_ARG;
+    std::vector<char> used((size_t)nu, 0);
+    for (int64_t i = 0; i < (int64_t)m * k; ++i) {
+        if (ia[i] < -1 || ia[i] >= nu) return LF_ERR_ARG;
+        if (ia[i] >= 0) used[(size_t)ia[i]] = 1;
+    }
+    for (int64_t i = 0; i < (int64_t)k * n; ++i) {
+        if (ib[i] < -1 || ib[i] >= nu) return LF_ERR_ARG;
+        if (ib[i] >= 0) used[(size_t)ib[i]] = 1;
+    }
+    for (int u = 0; u < nu; ++u)   // every operand of the store is transformed: one that nothing uses is a mistake of the caller's
+        if (!used[(size_t)u] || !in[2 * u] || !in[2 * u + 1] || !row0[2 * u] || !row0[2 * u + 1]) return LF_ERR_ARG;
+    for (int i = 0; i < m; ++i)
+        for (int j = 0; j < n; ++j) {
+            bool term = false;
+            for (int t = 0; t < k && !term; ++t) term = ia[(int64_t)i * k + t] >= 0 && ib[(int64_t)t * n + j] >= 0;
+            if (!term || !out0[(int64_t)i * n + j] || !out1[(int64_t)i * n + j]) return LF_ERR_ARG;
+        }
+    const int64_t need = lf_cc_matmul_ws_words(p, nu);
+    if (!ws || ws_words < need || ((uintptr_t)ws & 15)) return LF_ERR_ARG;
+    const int ell = p->ell, logN = p->logN, dev = p->device;
+    const int64_t poly = (int64_t)ell << logN;
+    const int xpl = stack_planes(p);
+    const int relaxed_plain = LF_NTT_RELAXED | LF_NTT_PLAIN | (xpl ? LF_NTT_PLANES : 0);
+    if (int e = lf_set_device(dev)) return e;
+    // 1. the store: c0, c1 of every distinct operand, rescale inside the forward transform, 4 operands (8 polynomials) per call
+    int64_t *store = ws, *T = ws + (int64_t)2 * nu * poly;
+    for (int u0 = 0; u0 < nu; u0 += 4) {
+        const int g = nu - u0 < 4 ? nu - u0 : 4;
+        if (int e = lf_rescale_ntt(in + 2 * u0, row0 + 2 * u0, 2 * g, store + (int64_t)2 * u0 * poly, ell, logN, p->rescale_scales, p->round_at,
+                                   p->psi, p->psi_dp, p->q_host, p->Rs, relaxed_plain, p->_2q, p->ql, p->qh, p->kl, p->kh, dev, stream))
+            return e;
+    }
+    // 2., 3. per tile: its summed triplets in one launch, then everything behind the tensor products as lf_cc_dot_batch runs it
+    int ta[LF_CC_MATMUL_MAX_INNER * 4], tb[LF_CC_MATMUL_MAX_INNER * 4];
+    std::vector<MatmulTile> tiles;
+    matmul_tiles(tiles, m, n, matmul_group(p));
+    for (const MatmulTile &tl : tiles) {
+        for (int t = 0; t < k; ++t) {
+            for (int i = 0; i < tl.R; ++i) ta[t * tl.R + i] = (int)ia[(int64_t)(tl.i0 + i) * k + t];
+            for (int j = 0; j < tl.C; ++j) tb[t * tl.C + j] = (int)ib[(int64_t)t * n + tl.j0 + j];
+        }
+        if (int e = lf_matmul_tensor(tl.R, tl.C, k, nu, store, ta, tb, T, p->d2, ell, logN, xpl, p->ql, p->qh, p->kl, p->kh,
+                                     (hipStream_t)stream))
+            return e;
+        int64_t *o0[4], *o1[4];
+        for (int i = 0; i < tl.R; ++i)
+            for (int j = 0; j < tl.C; ++j) {
+                const int64_t at = (int64_t)(tl.i0 + i) * n + tl.j0 + j;
+                o0[i * tl.C + j] = out0[at], o1[i * tl.C + j] = out1[at];
+            }
+        if (int e = dot_tail(p, tl.R * tl.C, T, ksk, part_stride, comp_stride, row_off, key_format, o0, o1, stream)) return e;
+    }
+    return 0;
 }
 
 /* ---- pc_dot: sum_i pt_i * ct_i (+ bias) for plaintexts encoded once, under ONE rescale (include/ckks_hip.h).  Plan-free, like

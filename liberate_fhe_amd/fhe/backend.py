@@ -429,6 +429,22 @@ class HipBackend:
                                   0 if ws is None else ws.numel(), _parr([o[0] for o in outs]), _parr([o[1] for o in outs]), st),
               "lf_cc_dot_batch")
 
+    @staticmethod
+    def cc_matmul_ws_words(plan, nu):
+        return int(lib.lf_cc_matmul_ws_words(ctypes.byref(plan), nu))
+
+    def cc_matmul_native(self, plan, m, k, n, ins, row0s, ia, ib, key, first_part, row_off, outs, ws):
+        """An m x k matrix of ciphertexts times a k x n one under one key as ONE native call (lf_cc_matmul).  ins / row0s: ctypes
+        arrays of 2 device pointers per DISTINCT operand ([operand][component]: first surviving row, dropped row); ia (m k entries,
+        [i][t]) / ib (k n entries, [t][j]): the operand of every entry, -1 for a zero one; outs: m n tensors [2, ell, N], [i][j];
+        ws: at least cc_matmul_ws_words(plan, len(ins) // 2) words (the transformed operands and a tile's summed triplets)."""
+        dev, st = _ds(outs[0])
+        base, ps, cs = self._key_args(key, first_part)
+        check(lib.lf_cc_matmul(ctypes.byref(plan), m, k, n, len(ins) // 2, ins, row0s, (ctypes.c_int64 * len(ia))(*ia),
+                               (ctypes.c_int64 * len(ib))(*ib), base, ps, cs, row_off, self._kfmt(key), _p(ws),
+                               0 if ws is None else ws.numel(), _parr([o[0] for o in outs]), _parr([o[1] for o in outs]), st),
+              "lf_cc_matmul")
+
     # include/ckks_hip.h: LF_WSUM_MAX_TERMS / LF_WSUM_MAX_OUTPUTS (tests/test_poly_eval_cpu.py holds these copies to the header)
     wsum_max_terms = 16
     wsum_max_outputs = 64

@@ -34,6 +34,7 @@ from ..csprng import Csprng
 from ..ntt import ntt_context
 from . import encdec
 from .backend import Consts
+from .ccmatmul import CcMatmulOps
 from .context.ckks_context import ckks_context
 from .data_struct import data_struct
 from .evaluator import EvaluatorOps, is_struct
@@ -78,7 +79,7 @@ class _OneShard:
         return ckks_engine._decrypt_rows_on(self, ct, sk, self.li, self.dev)
 
 
-class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps):
+class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMatmulOps):
     @errors.log_error
     def __init__(self, devices: list[int] = None, verbose: bool = False, bias_guard: bool = True,
                  norm: str = "forward", backend=None, comm=None, balanced_limb_map: bool = False, **ctx_params):

@@ -205,6 +205,94 @@ def inner_sum_plan(n: int, stride: int, num_slots: int, radix: int = INNER_SUM_R
     return stages
 
 
+# include/ckks_hip.h: LF_CC_MATMUL_MAX_INNER / LF_CC_MATMUL_MAX_OPERANDS (tests/test_cc_matmul_cpu.py holds these copies to the header)
+CC_MATMUL_MAX_INNER = 64
+CC_MATMUL_MAX_OPERANDS = 256
+
+
+def cc_matmul_tiles(m: int, n: int, gmax: int = 4) -> list:
+    """The tiles (i0, j0, R, C) lf_cc_matmul cuts an m x n matrix of outputs into (the native entry applies the same rule): every
+    output in exactly one tile, R C in {4, 2, 1} and at most gmax (the plan's max_nct).  2 x 2 where both dimensions allow it and
+    a tile may hold 4 outputs; strips of 1 x 4 / 4 x 1, then 1 x 2 / 2 x 1, then 1 x 1 along a vector, down an odd last column
+    and along an odd last row."""
+    if m < 1 or n < 1 or gmax < 1:
+        raise ValueError(f"cc_matmul_tiles: m, n, gmax >= 1 are required, got {m}, {n}, {gmax}")
+
+    def strip(i0, j0, length, along_row):
+        s = 0
+        while s < length:
+            left = length - s
+            g = 4 if left >= 4 and gmax >= 4 else 2 if left >= 2 and gmax >= 2 else 1
+            tiles.append((i0, j0 + s, 1, g) if along_row else (i0 + s, j0, g, 1))
+            s += g
+
+    tiles = []
+    if n == 1 and m > 1:
+        strip(0, 0, m, False)
+    elif m == 1 or gmax < 4:
+        for i in range(m):
+            strip(i, 0, n, True)
+    else:
+        m2, n2 = m & ~1, n & ~1
+        tiles += [(i, j, 2, 2) for i in range(0, m2, 2) for j in range(0, n2, 2)]
+        if n & 1:
+            strip(0, n - 1, m, False)
+        if m & 1:
+            strip(m - 1, 0, n2, True)
+    return tiles
+
+
+def cc_matmul_plan(A, B, max_operands: int = CC_MATMUL_MAX_OPERANDS, max_inner: int = CC_MATMUL_MAX_INNER):
+    """The shape and the native calls of C = A B for matrices of ciphertext OBJECTS (rows of entries; None: a zero entry):
+    (m, k, n, calls).  calls: None where no native call can take the product (k above max_inner, or B with one row of A holding
+    more than max_operands distinct operands); else row blocks of A, each a dict
+        rows (i0, i1)      the rows of A, and of C, the call covers
+        operands           its DISTINCT operands, by object identity, in order of first use (A's rows, then B)
+        ia, ib             flat index tables into `operands`, [i - i0][t] resp. [t][j], -1 for None
+    with at most max_operands operands per call: rows are taken greedily, the inner dimension is never split.  Pure: no engine,
+    no device.  ValueError for an empty matrix, ragged rows, mismatched inner dimensions and an output with no term."""
+    A, B = [list(r) for r in A], [list(r) for r in B]
+    if not A or not B or not A[0] or not B[0]:
+        raise ValueError("cc_matmul: empty matrix")
+    m, k, n = len(A), len(A[0]), len(B[0])
+    if any(len(r) != k for r in A) or any(len(r) != n for r in B):
+        raise ValueError("cc_matmul: ragged rows")
+    if len(B) != k:
+        raise ValueError(f"cc_matmul: A has {k} columns, B has {len(B)} rows")
+    for i in range(m):
+        for j in range(n):
+            if not any(A[i][t] is not None and B[t][j] is not None for t in range(k)):
+                raise ValueError(f"cc_matmul: output ({i}, {j}) has no term")
+    if k > max_inner:
+        return m, k, n, None
+    b_ids = {id(x) for row in B for x in row if x is not None}
+    calls, i0 = [], 0
+    while i0 < m:
+        seen, i1 = set(b_ids), i0
+        while i1 < m:
+            more = seen | {id(x) for x in A[i1] if x is not None}
+            if len(more) > max_operands:
+                break
+            seen, i1 = more, i1 + 1
+        if i1 == i0:
+            return m, k, n, None
+        index, operands = {}, []
+
+        def at(x):
+            if x is None:
+                return -1
+            if id(x) not in index:
+                index[id(x)] = len(operands)
+                operands.append(x)
+            return index[id(x)]
+
+        ia = [at(A[i][t]) for i in range(i0, i1) for t in range(k)]
+        ib = [at(B[t][j]) for t in range(k) for j in range(n)]
+        calls.append({"rows": (i0, i1), "operands": operands, "ia": ia, "ib": ib})
+        i0 = i1
+    return m, k, n, calls
+
+
 def _tree_levels(b: int) -> int:
     """Levels above the base at which the b-th power stands when powers are built by the tree rule of ckks_engine.poly_eval
     (a power of two 2^j by j squarings; any other b as top power of two times the rest, one level above the former)."""

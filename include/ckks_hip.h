@@ -568,6 +568,29 @@ int lf_linear_transform(const lf_ks_plan *plan, const int64_t *c0, const int64_t
                         const int64_t *pt, int64_t pt_stride, const int64_t *pt0, const int64_t *rescale_scales, int64_t round_at,
                         int64_t *ws, int64_t ws_words, int64_t *out0, int64_t *out1, void *stream);
 
+/* lf_linear_transform for nct ciphertexts under the SAME diagonals and keys.  c0 / c1 / out0 / out1: HOST arrays of nct device
+ * pointers (a ciphertext may appear several times); everything else means what it means in lf_linear_transform.  Output t has
+ * exactly the words of lf_linear_transform on ciphertext t.  The ciphertexts are taken in groups of min(4, plan->max_nct), then 2,
+ * then 1; a group of one IS lf_linear_transform.  Enqueued per group of g = 4 or 2: canonical copies of the g c0 (c1 with pt0),
+ * ONE forward NTT of them (enter_ntt) on the ell ordinary rows and the products with plan->PR; lf_ks_digits_batch (gal_pinv = 1)
+ * into plan->state + t ell N and ONE extension + forward NTT of all g nparts digits into plan->ext (nr > 0); per chunk of
+ * 8 keys (csrc/ckks_ks.hip: LF_LTB_KEYS) one launch of ks_inner_ltb_kernel, which loops over the chunk's keys itself, loads every key and diagonal word once for the g ciphertexts and keeps their g running pairs in
+ * registers, all launches adding into the g pairs plan->sum (nr = 0: one launch without keys); ONE inverse NTT of the 2 g
+ * polynomials (their planes pass through plan->ext, which is spent by then); ONE mod-down and ONE lf_rescale_batch of the 2 g
+ * polynomials into out0[t] / out1[t] [ell - 1][N].  The g (P c^0, P c^1) and the mod-down's [2 g][ell][N] result live in the
+ * group's slots of plan->x4 ([max_nct][4][ell][N], free during this op) or, with plan->x4 = NULL, in `ws` of at least
+ * lf_linear_transform_batch_ws_words(plan, nct) words (0: ws may be NULL; it grows with the largest group, not with nct; 0 also
+ * for a plan or an nct the op refuses), 16-byte aligned.
+ * LF_ERR_ARG before any launch for everything lf_linear_transform refuses, nct < 1 or > LF_LT_BATCH_MAX_CTS, a NULL among the
+ * pointer arrays or their entries, and a workspace that is NULL where words are needed, misaligned or too small. */
+#define LF_LT_BATCH_MAX_CTS 64
+int64_t lf_linear_transform_batch_ws_words(const lf_ks_plan *plan, int nct);
+int lf_linear_transform_batch(const lf_ks_plan *plan, int nct, const int64_t *const *c0, const int64_t *const *c1,
+                              int nr, const int64_t *p_host, const int64_t *const *ksk, int64_t part_stride,
+                              int64_t comp_stride, int64_t row_off, int key_format, const int64_t *pt, int64_t pt_stride,
+                              const int64_t *pt0, const int64_t *rescale_scales, int64_t round_at, int64_t *ws,
+                              int64_t ws_words, int64_t *const *out0, int64_t *const *out1, void *stream);
+
 /* Rotation sum: out = moddown(sum_i (ks_i + P c0(X^p_i)) [+ P (c0, c1)]), the ciphertext that decrypts to sum_i rot(m, step_i)
  * [+ m] at the SAME level as (c0, c1): lf_linear_transform without the diagonals and without the rescale.  nr >= 0 keys with odd
  * exponents p_host[i] < 2N (HOST arrays as lf_rotate_hoisted; a key may repeat, p = 1 is legal, and so is the conjugation's

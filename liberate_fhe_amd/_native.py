@@ -121,6 +121,8 @@ _SIGNATURES["lf_pc_matmul_ws_words"] = [_I, _I, _I, _I]
 _SIGNATURES["lf_pc_matmul"] = [_I, _I, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _I, _P]
 _SIGNATURES["lf_linear_transform_ws_words"] = [_PL]
 _SIGNATURES["lf_linear_transform"] = [_PL, _P, _P, _I, _P, _P, _L, _L, _L, _I, _P, _L, _P, _P, _L, _P, _L, _P, _P, _P]
+_SIGNATURES["lf_linear_transform_batch_ws_words"] = [_PL, _I]
+_SIGNATURES["lf_linear_transform_batch"] = [_PL, _I, _P, _P, _I, _P, _P, _L, _L, _L, _I, _P, _L, _P, _P, _L, _P, _L, _P, _P, _P]
 _SIGNATURES["lf_rotate_sum_ws_words"] = [_PL]
 _SIGNATURES["lf_rotate_sum"] = [_PL, _P, _P, _I, _P, _P, _L, _L, _L, _I, _I, _P, _L, _P, _P, _P]
 _SIGNATURES["lf_linear_transform_bsgs_ws_words"] = [_PL, _I]
@@ -180,6 +182,7 @@ LF_LT_MATMUL_MAX_INPUTS = 64   # include/ckks_hip.h: inputs per lf_lt_matmul cal
 LF_LT_MATMUL_MAX_OUTPUTS = 64  # .. and outputs per call
 LF_LT_MATMUL_BSGS_MAX_GIANTS = 64   # include/ckks_hip.h: giant steps per lf_lt_matmul_bsgs call
 LF_LT_MATMUL_BSGS_MAX_SUMS = 256    # .. and keyed inner sums (pairs of an output and a keyed giant step)
+LF_LT_BATCH_MAX_CTS = 64            # include/ckks_hip.h: ciphertexts per lf_linear_transform_batch call
 LF_CC_MATMUL_MAX_INNER = 64         # include/ckks_hip.h: inner dimension of an lf_cc_matmul call
 LF_CC_MATMUL_MAX_OPERANDS = 256     # .. and distinct operands per call
 LF_ERR_ARG = 10001

@@ -1265,6 +1265,244 @@ __global__ void __launch_bounds__(256) ks_inner_lt_kernel(const i64 *__restrict_
     }
 }
 
+// ---- K3 of a batched linear transform (lf_linear_transform_batch): ks_inner_lt_kernel for NCT ciphertexts under the SAME keys ---
+// and diagonals.  The grid, the pi computation and the key / digit formats are ks_inner_lt_kernel's.  The kernel loops over the
+// keys of its launch itself (la.nk <= LF_LTB_KEYS; keys, exponents and diagonals travel in the argument struct): per key and part
+// the key's four words are loaded once and multiplied into NCT x 4 accumulators (ciphertext t's digits at ext + t * ext_stride,
+// gathered by the key's pi); then the diagonal's two words are loaded once, REDCed once on the fp64-class rows, and multiplied
+// into the NCT running pairs S, which stay in registers across the key loop and cross HBM once per launch: the first launch
+// starts them from the step-0 term pt0 * P (c^0_t, c^1_t) (ordinary rows, no key; zero without pt0), later launches from the
+// pair the previous launch left at s + t * sum_stride.  The pairs leave in the format the sums' inverse pass reads (spl).
+// NK = keys whose digit loops run together.  pi differs from key to key, and the 512 words a block gathers are one contiguous
+// segment of the row, ANOTHER one per key: two keys never share a digit word in registers, only in cache, which the key loop
+// already arranges (every block of a row re-reads that row's digits once per key).  NK = 2 doubles the accumulators for
+// nothing the cache does not give: NK = 1 is what runs.
+// fp64 class: per key and ciphertext the sums are ks_inner_lt_kernel's (nparts balanced products + one word below 2q, reduced
+// with dp_reduce_bal); a running pair takes per launch one start term — the step-0 balanced product, |.| <= q / 2, or the
+// canonical word below q of the previous launch — and la.nk balanced products: |S| <= (LF_LTB_KEYS / 2 + 1) q = 5 q, inside
+// dp_reduce's 64 q without a reduction inside the loop (it would be needed from 126 keys a launch on).
+#define LF_LTB_KEYS 8   // keys per launch (backend.lt_batch_keys_per_launch): the pairs' trip is 2 x 2 rows N words per 8 keys' streams
+static_assert(LF_LTB_KEYS / 2 + 1 < 64, "running pairs of ks_inner_ltb_kernel: (keys / 2 + 1) q must stay inside dp_reduce's 64 q");
+struct LtbArgs {
+    const i64 *ksk[LF_LTB_KEYS];   // key i, at its first part
+    const i64 *pt[LF_LTB_KEYS];    // its encoded diagonal, [rows][N]
+    unsigned p[LF_LTB_KEYS];       // its exponent (odd, < 2N)
+    const i64 *pt0;                // step-0 diagonal or nullptr (read by the first launch only)
+    const i64 *chat;               // ciphertext t at chat + t * chat_stride: P NTT(c0), P NTT(c1), [2][ell][N], words below 2q
+    i64 chat_stride, ext_stride, sum_stride;   // words between the ciphertexts' c^, extended digits and running pairs
+    int nk;                        // keys of this launch (0: the step-0 term alone)
+    int ell;                       // ordinary rows (the first `ell` of the rows)
+    int first;                     // first launch: `s` is not read
+};
+
+template <int NCT, int NK, bool PLANES, bool DPL>
+__global__ void __launch_bounds__(256) ks_inner_ltb_kernel(const i64 *__restrict__ ext, LtbArgs la, i64 part_stride, i64 comp_stride,
+                                                           i64 row_off, i64 *__restrict__ s, int nparts, int rows, int logN, int spl,
+                                                           const i64 *__restrict__ ql, const i64 *__restrict__ qh,
+                                                           const i64 *__restrict__ kl, const i64 *__restrict__ kh) {
+    static_assert((NCT == 2 || NCT == 4) && (NK == 1 || NK == 2), "ks_inner_ltb_kernel: 2 or 4 ciphertexts, 1 or 2 keys together");
+    const int r = blockIdx.y;
+    const i64 N = (i64)1 << logN;
+    const i64 j0 = (i64)blockIdx.x * 512 + threadIdx.x * 2;
+    if (j0 >= N) return;
+    const RowMod m = load_mod(ql, qh, kl, kh, r);
+    const unsigned sh = 32u - (unsigned)logN, mask = (2u << logN) - 1u;
+    const unsigned bj = (2u * (__builtin_bitreverse32((unsigned)j0) >> sh) + 1u);
+    const i64 krow = (row_off + r) * N;
+    const bool ord = r < la.ell;
+    const i64 *c0row = la.chat + (i64)r * N, *c1row = c0row + (i64)la.ell * N;   // (read on ordinary rows only)
+    i64 *srow0 = s + (i64)r * N, *srow1 = s + ((i64)rows + r) * N;
+    constexpr int DIGITS_IN_FLIGHT = NCT * NK >= 4 ? 1 : KI_UNROLL;   // (NCT x NK digit pairs are in flight per key word already)
+    if (m.q < SMALL_PRIME_LIMIT) {
+        const RowDp d = make_dp(m);
+        double S[NCT][2][2];
+        if (!la.first) {   // the pairs the previous launch left (canonical words)
+#pragma unroll
+            for (int t = 0; t < NCT; ++t) {
+                ld_pair_dp(srow0 + t * la.sum_stride, j0, N, spl, S[t][0][0], S[t][0][1]);
+                ld_pair_dp(srow1 + t * la.sum_stride, j0, N, spl, S[t][1][0], S[t][1][1]);
+            }
+        } else if (la.pt0 != nullptr && ord) {
+            const longlong2 w = ld_nt(la.pt0 + (i64)r * N + j0);
+            const double wa = dp_from_word(mm62u((u64)w.x, 1ull, m.q, m.k)), wb = dp_from_word(mm62u((u64)w.y, 1ull, m.q, m.k));
+#pragma unroll
+            for (int t = 0; t < NCT; ++t) {
+                double a0, b0, a1, b1;
+                ld_pair_dp(c0row + t * la.chat_stride, j0, N, 0, a0, b0);
+                ld_pair_dp(c1row + t * la.chat_stride, j0, N, 0, a1, b1);
+                S[t][0][0] = dp_mulmod_bal(a0, wa, d), S[t][0][1] = dp_mulmod_bal(b0, wb, d);
+                S[t][1][0] = dp_mulmod_bal(a1, wa, d), S[t][1][1] = dp_mulmod_bal(b1, wb, d);
+            }
+        } else {
+#pragma unroll
+            for (int t = 0; t < NCT; ++t) S[t][0][0] = S[t][0][1] = S[t][1][0] = S[t][1][1] = 0.0;
+        }
+        for (int k0 = 0; k0 < la.nk; k0 += NK) {
+            i64 src[NK];
+            bool sw[NK];
+            double acc[NK][NCT][2][2];
+#pragma unroll
+            for (int i = 0; i < NK; ++i) {
+                const int ki = k0 + i < la.nk ? k0 + i : k0;   // (an odd count: the last pair's second key repeats the first and is dropped)
+                const unsigned t = (bj * la.p[ki]) & mask;
+                const unsigned mi = __builtin_bitreverse32((t - 1u) >> 1) >> sh;
+                src[i] = (i64)(mi & ~1u);
+                sw[i] = (mi & 1u) != 0;
+#pragma unroll
+                for (int t2 = 0; t2 < NCT; ++t2) acc[i][t2][0][0] = acc[i][t2][0][1] = acc[i][t2][1][0] = acc[i][t2][1][1] = 0.0;
+            }
+#pragma unroll DIGITS_IN_FLIGHT
+            for (int p = 0; p < nparts; ++p) {
+                const i64 *er = ext + ((i64)p * rows + r) * N;
+#pragma unroll
+                for (int i = 0; i < NK; ++i) {
+                    if (NK > 1 && k0 + i >= la.nk) break;
+                    const i64 *kr = la.ksk[k0 + i] + krow + (i64)p * part_stride;
+                    double k0x, k0y, k1x, k1y;
+                    if (PLANES) {   // 16 + 8 bytes for both components (see lf_key_planes)
+                        const lf_u4_t l = __builtin_nontemporal_load(reinterpret_cast<const lf_u4_t *>(reinterpret_cast<const unsigned *>(kr) + 2 * j0));
+                        const lf_u2_t h = __builtin_nontemporal_load(reinterpret_cast<const lf_u2_t *>(reinterpret_cast<const unsigned *>(kr + comp_stride) + j0));
+                        k0x = dp_from_planes(l.x, h.x & 0xffffu), k0y = dp_from_planes(l.y, h.x >> 16);
+                        k1x = dp_from_planes(l.z, h.y & 0xffffu), k1y = dp_from_planes(l.w, h.y >> 16);
+                    } else {
+                        const longlong2 w0 = ld_nt(kr + j0);
+                        const longlong2 w1 = ld_nt(kr + j0 + comp_stride);
+                        k0x = dp_from_word(w0.x), k0y = dp_from_word(w0.y), k1x = dp_from_word(w1.x), k1y = dp_from_word(w1.y);
+                    }
+#pragma unroll
+                    for (int t = 0; t < NCT; ++t) {
+                        double xa, xb;
+                        ld_pair_dp(er + t * la.ext_stride, src[i], N, DPL ? 1 : 0, xa, xb);
+                        const double x0 = sw[i] ? xb : xa, x1 = sw[i] ? xa : xb;
+                        acc[i][t][0][0] += dp_mulmod_bal(x0, k0x, d);
+                        acc[i][t][0][1] += dp_mulmod_bal(x1, k0y, d);
+                        acc[i][t][1][0] += dp_mulmod_bal(x0, k1x, d);
+                        acc[i][t][1][1] += dp_mulmod_bal(x1, k1y, d);
+                    }
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < NK; ++i) {
+                if (NK > 1 && k0 + i >= la.nk) break;
+                const longlong2 w = ld_nt(la.pt[k0 + i] + (i64)r * N + j0);
+                const double wa = dp_from_word(mm62u((u64)w.x, 1ull, m.q, m.k)), wb = dp_from_word(mm62u((u64)w.y, 1ull, m.q, m.k));
+#pragma unroll
+                for (int t = 0; t < NCT; ++t) {
+                    if (ord) {
+                        double ca, cb;
+                        ld_pair_dp(c0row + t * la.chat_stride, src[i], N, 0, ca, cb);
+                        acc[i][t][0][0] += sw[i] ? cb : ca;
+                        acc[i][t][0][1] += sw[i] ? ca : cb;
+                    }
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) {
+                        S[t][c][0] += dp_mulmod_bal(dp_reduce_bal(acc[i][t][c][0], d), wa, d);
+                        S[t][c][1] += dp_mulmod_bal(dp_reduce_bal(acc[i][t][c][1], d), wb, d);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < NCT; ++t)
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                longlong2 o;   // |S| <= (LF_LTB_KEYS / 2 + 1) q, inside dp_reduce's 64 q
+                o.x = dp_to_word(dp_reduce(S[t][c][0], d.q, d.qinv));
+                o.y = dp_to_word(dp_reduce(S[t][c][1], d.q, d.qinv));
+                i64 *srow = (c ? srow1 : srow0) + t * la.sum_stride;
+                if (spl) {
+                    const lf_u2_t l = {(unsigned)o.x, (unsigned)o.y};
+                    *reinterpret_cast<lf_u2_t *>(reinterpret_cast<unsigned *>(srow) + j0) = l;
+                    *reinterpret_cast<unsigned *>(reinterpret_cast<unsigned short *>(srow + (N >> 1)) + j0) =
+                        (unsigned)((u64)o.x >> 32) | ((unsigned)((u64)o.y >> 32) << 16);
+                } else {
+                    *reinterpret_cast<longlong2 *>(srow + j0) = o;
+                }
+            }
+    } else {
+        i64 S[NCT][2][2];   // lazy words below 2q throughout
+        if (!la.first) {
+#pragma unroll
+            for (int t = 0; t < NCT; ++t) {
+                const longlong2 a = *reinterpret_cast<const longlong2 *>(srow0 + t * la.sum_stride + j0);
+                const longlong2 b = *reinterpret_cast<const longlong2 *>(srow1 + t * la.sum_stride + j0);
+                S[t][0][0] = a.x, S[t][0][1] = a.y, S[t][1][0] = b.x, S[t][1][1] = b.y;
+            }
+        } else if (la.pt0 != nullptr && ord) {
+            const longlong2 w = ld_nt(la.pt0 + (i64)r * N + j0);
+#pragma unroll
+            for (int t = 0; t < NCT; ++t) {
+                const longlong2 a = *reinterpret_cast<const longlong2 *>(c0row + t * la.chat_stride + j0);
+                const longlong2 b = *reinterpret_cast<const longlong2 *>(c1row + t * la.chat_stride + j0);
+                S[t][0][0] = mm62u((u64)a.x, (u64)w.x, m.q, m.k), S[t][0][1] = mm62u((u64)a.y, (u64)w.y, m.q, m.k);
+                S[t][1][0] = mm62u((u64)b.x, (u64)w.x, m.q, m.k), S[t][1][1] = mm62u((u64)b.y, (u64)w.y, m.q, m.k);
+            }
+        } else {
+#pragma unroll
+            for (int t = 0; t < NCT; ++t) S[t][0][0] = S[t][0][1] = S[t][1][0] = S[t][1][1] = 0;
+        }
+        for (int k0 = 0; k0 < la.nk; k0 += NK) {
+            i64 src[NK];
+            bool sw[NK];
+            i64 acc[NK][NCT][2][2];
+#pragma unroll
+            for (int i = 0; i < NK; ++i) {
+                const int ki = k0 + i < la.nk ? k0 + i : k0;
+                const unsigned t = (bj * la.p[ki]) & mask;
+                const unsigned mi = __builtin_bitreverse32((t - 1u) >> 1) >> sh;
+                src[i] = (i64)(mi & ~1u);
+                sw[i] = (mi & 1u) != 0;
+#pragma unroll
+                for (int t2 = 0; t2 < NCT; ++t2) acc[i][t2][0][0] = acc[i][t2][0][1] = acc[i][t2][1][0] = acc[i][t2][1][1] = 0;
+            }
+            for (int p = 0; p < nparts; ++p) {
+                const i64 *er = ext + ((i64)p * rows + r) * N;
+#pragma unroll
+                for (int i = 0; i < NK; ++i) {
+                    if (NK > 1 && k0 + i >= la.nk) break;
+                    const i64 *kr = la.ksk[k0 + i] + krow + (i64)p * part_stride + j0;
+                    const longlong2 w0 = ld_nt(kr);
+                    const longlong2 w1 = ld_nt(kr + comp_stride);
+#pragma unroll
+                    for (int t = 0; t < NCT; ++t) {
+                        const longlong2 v = *reinterpret_cast<const longlong2 *>(er + t * la.ext_stride + src[i]);
+                        const u64 x0 = (u64)(sw[i] ? v.y : v.x), x1 = (u64)(sw[i] ? v.x : v.y);
+                        acc[i][t][0][0] = csub(acc[i][t][0][0] + mm62u(x0, (u64)w0.x, m.q, m.k), m.q2);
+                        acc[i][t][0][1] = csub(acc[i][t][0][1] + mm62u(x1, (u64)w0.y, m.q, m.k), m.q2);
+                        acc[i][t][1][0] = csub(acc[i][t][1][0] + mm62u(x0, (u64)w1.x, m.q, m.k), m.q2);
+                        acc[i][t][1][1] = csub(acc[i][t][1][1] + mm62u(x1, (u64)w1.y, m.q, m.k), m.q2);
+                    }
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < NK; ++i) {
+                if (NK > 1 && k0 + i >= la.nk) break;
+                const longlong2 w = ld_nt(la.pt[k0 + i] + (i64)r * N + j0);
+#pragma unroll
+                for (int t = 0; t < NCT; ++t) {
+                    if (ord) {
+                        const longlong2 v = *reinterpret_cast<const longlong2 *>(c0row + t * la.chat_stride + src[i]);
+                        acc[i][t][0][0] = csub(acc[i][t][0][0] + (sw[i] ? v.y : v.x), m.q2);
+                        acc[i][t][0][1] = csub(acc[i][t][0][1] + (sw[i] ? v.x : v.y), m.q2);
+                    }
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) {
+                        S[t][c][0] = csub(S[t][c][0] + mm62u((u64)acc[i][t][c][0], (u64)w.x, m.q, m.k), m.q2);
+                        S[t][c][1] = csub(S[t][c][1] + mm62u((u64)acc[i][t][c][1], (u64)w.y, m.q, m.k), m.q2);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < NCT; ++t) {
+            longlong2 o0, o1;
+            o0.x = S[t][0][0], o0.y = S[t][0][1], o1.x = S[t][1][0], o1.y = S[t][1][1];
+            *reinterpret_cast<longlong2 *>(srow0 + t * la.sum_stride + j0) = o0;
+            *reinterpret_cast<longlong2 *>(srow1 + t * la.sum_stride + j0) = o1;
+        }
+    }
+}
+
 // ---- K3 of a rotation sum (lf_rotate_sum): sum_i (key switch sums of rotation i + P c0(X^p_i)) [+ P (c0, c1)] in Q P ------------
 // ks_inner_lt_kernel without the diagonals: the same grid, pi computation and key / digit formats, and ONE accumulator pair per
 // thread for the whole group — the digits x key products of all NR keys go into the same acc[2][2]; on the ordinary rows c^0
@@ -1863,6 +2101,10 @@ bool digit_planes(int logN, const RowList &dp, const RowList &in) {
 //     inner_kernel (the same body)
 //   ks_inner_baby_kernel, ks_inner_lt_     one word of P c0 below 2q                  nparts / 2 + 2 < 64:  nparts <= 123
 //     kernel (it reduces there with dp_reduce_bal, |x| < 2^52, and its running pair stays within (NR + 2) q)
+//   ks_inner_ltb_kernel                    per key and ciphertext as ks_inner_lt_kernel               nparts <= 123
+//     (its NCT running pairs stay in registers over the LF_LTB_KEYS keys of a launch: one start term — a balanced product or a
+//     canonical word below q — and LF_LTB_KEYS balanced products, |S| <= (LF_LTB_KEYS / 2 + 1) q = 5 q < 64 q, reduced once
+//     with dp_reduce when the launch ends; a launch of 126 keys or more would have to reduce inside its loop: static_assert there)
 //   ks_inner_giant_kernel                  a word of S^g_0 and one of the accumulator, both below 2q
 //                                                                                     nparts / 2 + 4 < 64:  nparts <= 119
 //   ks_inner_rsum_kernel                   NR nparts products, NR + 1 words below 2q: reduced first with dp_reduce_bal
@@ -2342,6 +2584,68 @@ int lf_ks_tail_lt(int nr, const int64_t *p_host, int nparts, int rows, int ell, 
 #undef LF_LT_LAUNCH
 #undef LF_LT_CASE
     return ks_inv_sums(2, rows, logN, spl, cols_last, mixed, in, dp, (i64 *)scratch, (i64 *)s, ipsi_br, ipsi_dp, Ninv, ql, qh, kl, kh, st);
+}
+
+// The key-dependent part of lf_linear_transform_batch (ckks_ops.hip) for nct (2 or 4) ciphertexts: per LF_LTB_KEYS keys ONE launch
+// of ks_inner_ltb_kernel over the ciphertexts' extended digits ext [nct][nparts][rows][N] (nr = 0: the step-0 term alone, one
+// launch without keys), all of them adding into the nct pairs of sums s [nct][2][rows][N]; then ONE inverse transform of the
+// 2 nct polynomials.  `scratch` (>= 2 nct rows N words, or NULL: the sums stay raw words, same outputs) as in lf_ks_tail_lt.
+// Ciphertext t's c^ = P NTT(c0), P NTT(c1) on the `ell` ordinary rows at chat + t * chat_stride.  Internal: ckks_ops.hip checks
+// the arguments (nr >= 0, odd exponents below 2N, pt0 != NULL when nr == 0).
+int lf_ks_tail_ltb(int nct, int nr, const int64_t *p_host, int nparts, int rows, int ell, int logN, const int64_t *const *ksk,
+                   int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format, const int64_t *pt, int64_t pt_stride,
+                   const int64_t *pt0, const int64_t *chat, int64_t chat_stride, const int64_t *ext, int64_t *s, int64_t *scratch,
+                   int64_t scratch_words, const int64_t *ipsi_br, const double *ipsi_dp, const int64_t *Ninv, const int64_t *q_host,
+                   const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st) {
+    if ((nct != 2 && nct != 4) || !ipsi_dp || (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES) || nr < 0 || (nr == 0 && !pt0) ||
+        !chat || !ext || !s || ell < 0 || ell > rows || nparts < 1 || logN <= NTT_TILE_LOG_MAX || logN > KS_LOGN_MAX ||
+        (nr && (!ksk || !p_host || !pt)))
+        return LF_ERR_ARG;
+    if (rows < 1 || rows > MAX_LIST_ROWS || !lf_fp64_digits_ok(nparts, rows, q_host)) return LF_ERR_ARG;
+    for (int i = 0; i < nr; ++i)
+        if (!ksk[i] || (key_format == LF_KEY_PLANES && ((((uintptr_t)ksk[i] | (uintptr_t)(part_stride * 8) | (uintptr_t)(comp_stride * 8)) & 15))))
+            return LF_ERR_ARG;
+    const int tl = NTT_TILE_LOG_MAX, S1 = logN - tl;
+    RowList dp, in;
+    classify_rows(rows, q_host, dp, in);
+    const bool mixed = dp.n && in.n;
+    const bool dplanes = digit_planes(logN, dp, in);
+    const bool cols_last = S1 <= 4 || (S1 == 5 && mixed && g_ks_ext_cols_max > 4);
+    if (nr)   // the digits must be in the format the launches read (see ks_tail)
+        if (int e = lf_fmt_expect(ext, ((size_t)nct * nparts * rows << logN) * 8, dplanes ? LF_FMT_PLANES : LF_FMT_RAW)) return e;
+    const bool spl = dplanes && (g_more_planes & 1) && cols_last && scratch && scratch_words >= ((int64_t)2 * nct * rows << logN);
+    const dim3 grid((unsigned)((((i64)1 << logN) + 511) / 512), (unsigned)rows);
+    const bool planes = key_format == LF_KEY_PLANES;
+#define LF_LTB_LAUNCH(NCT, PL, DPLB)                                                                                          \
+    hipLaunchKernelGGL((ks_inner_ltb_kernel<NCT, 1, PL, DPLB>), grid, dim3(256), 0, st, (const i64 *)ext, la, (i64)part_stride, \
+                       (i64)comp_stride, (i64)row_off, (i64 *)s, nparts, rows, logN, spl ? 1 : 0, (const i64 *)ql, (const i64 *)qh, \
+                       (const i64 *)kl, (const i64 *)kh)
+#define LF_LTB_CASE(NCT)                                                                                                      \
+    if (planes && dplanes) LF_LTB_LAUNCH(NCT, true, true);                                                                    \
+    else if (planes) LF_LTB_LAUNCH(NCT, true, false);                                                                         \
+    else if (dplanes) LF_LTB_LAUNCH(NCT, false, true);                                                                        \
+    else LF_LTB_LAUNCH(NCT, false, false)
+    for (int i0 = 0; i0 < nr || i0 == 0; i0 += LF_LTB_KEYS) {
+        const int g = nr - i0 < LF_LTB_KEYS ? nr - i0 : LF_LTB_KEYS;
+        LtbArgs la{};
+        for (int t = 0; t < g; ++t) {
+            la.ksk[t] = (const i64 *)ksk[i0 + t];
+            la.p[t] = (unsigned)p_host[i0 + t];
+            la.pt[t] = (const i64 *)pt + (i64)(i0 + t) * pt_stride;
+        }
+        la.pt0 = (const i64 *)pt0, la.chat = (const i64 *)chat, la.chat_stride = (i64)chat_stride;
+        la.ext_stride = ((i64)nparts * rows) << logN, la.sum_stride = ((i64)2 * rows) << logN;
+        la.nk = g, la.ell = ell, la.first = i0 == 0;
+        if (nct == 2) {
+            LF_LTB_CASE(2);
+        } else {
+            LF_LTB_CASE(4);
+        }
+    }
+#undef LF_LTB_LAUNCH
+#undef LF_LTB_CASE
+    return ks_inv_sums(2 * nct, rows, logN, spl, cols_last, mixed, in, dp, (i64 *)scratch, (i64 *)s, ipsi_br, ipsi_dp, Ninv, ql, qh, kl,
+                       kh, st);
 }
 
 // The key-dependent part of lf_rotate_sum (ckks_ops.hip): per group of up to 4 keys ONE launch of ks_inner_rsum_kernel over the

@@ -28,6 +28,14 @@ int lf_ks_tail_lt(int nr, const int64_t *p_host, int nparts, int rows, int ell, 
                   const double *ipsi_dp, const int64_t *Ninv, const int64_t *q_host, const int64_t *ql, const int64_t *qh,
                   const int64_t *kl, const int64_t *kh, hipStream_t st);
 
+// ckks_ks.hip: the key-dependent part of lf_linear_transform_batch for a group of 2 or 4 ciphertexts (the launches into the
+// group's pairs of sums + their one inverse NTT)
+int lf_ks_tail_ltb(int nct, int nr, const int64_t *p_host, int nparts, int rows, int ell, int logN, const int64_t *const *ksk,
+                   int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format, const int64_t *pt, int64_t pt_stride,
+                   const int64_t *pt0, const int64_t *chat, int64_t chat_stride, const int64_t *ext, int64_t *s, int64_t *scratch,
+                   int64_t scratch_words, const int64_t *ipsi_br, const double *ipsi_dp, const int64_t *Ninv, const int64_t *q_host,
+                   const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st);
+
 // ckks_ks.hip: the launches of lf_linear_transform_bsgs
 int lf_ks_tail_rsum(int nr, const int64_t *p_host, int nparts, int rows, int ell, int logN, const int64_t *const *ksk, int64_t part_stride,
                     int64_t comp_stride, int64_t row_off, int key_format, int with_self, const int64_t *chat, const int64_t *ext,
@@ -724,6 +732,99 @@ int lf_linear_transform(const lf_ks_plan *p, const int64_t *c0, const int64_t *c
     const int64_t *ins[2] = {md + N, md + poly + N}, *row0[2] = {md, md + poly};
     int64_t *outs[2] = {out0, out1};
     return lf_rescale_batch(ins, row0, outs, 2, ell - 1, N, rescale_scales, round_at, p->ql + 1, p->qh + 1, p->kl + 1, p->kh + 1, dev, stream);
+}
+
+/* ---- linear transform of many ciphertexts under the same diagonals and keys (include/ckks_hip.h): groups of 4, 2 or 1; a group
+ * of g shares every launch, and its inner product reads each key and diagonal word once for the g ciphertexts ---- */
+static int lt_batch_group(const lf_ks_plan *p, int left) {
+    return left >= 4 && p->max_nct >= 4 ? 4 : left >= 2 && p->max_nct >= 2 ? 2 : 1;
+}
+
+// per ciphertext of the largest group P NTT(c0), P NTT(c1) and the mod-down's [2][ell][N] result: the plan's operand stacks x4
+// (free during this op), else `ws`
+int64_t lf_linear_transform_batch_ws_words(const lf_ks_plan *p, int nct) {
+    if (!plan_ok(p) || nct < 1 || nct > LF_LT_BATCH_MAX_CTS || p->x4) return 0;
+    return ((int64_t)4 * lt_batch_group(p, nct) * p->ell) << p->logN;
+}
+
+int lf_linear_transform_batch(const lf_ks_plan *p, int nct, const int64_t *const *c0, const int64_t *const *c1, int nr,
+                              const int64_t *p_host, const int64_t *const *ksk, int64_t part_stride, int64_t comp_stride,
+                              int64_t row_off, int key_format, const int64_t *pt, int64_t pt_stride, const int64_t *pt0,
+                              const int64_t *rescale_scales, int64_t round_at, int64_t *ws, int64_t ws_words, int64_t *const *out0,
+                              int64_t *const *out1, void *stream) {
+    if (!plan_ok(p) || !p->PR || p->ell < 2 || nct < 1 || nct > LF_LT_BATCH_MAX_CTS || nr < 0 || (nr == 0 && !pt0) || !c0 || !c1 ||
+        !rescale_scales || !out0 || !out1 || (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES))
+        return LF_ERR_ARG;
+    const int ell = p->ell, rows = p->ell + p->K, logN = p->logN, dev = p->device;
+    const int64_t N = (int64_t)1 << logN, twoN = 2 * N, poly = (int64_t)ell * N;
+    if (nr && (!p_host || !ksk || !pt || pt_stride < (int64_t)rows * N)) return LF_ERR_ARG;
+    for (int i = 0; i < nr; ++i) {
+        if (!ksk[i] || p_host[i] <= 0 || p_host[i] >= twoN || !(p_host[i] & 1)) return LF_ERR_ARG;
+        if (key_format == LF_KEY_PLANES && ((((uintptr_t)ksk[i] | (uintptr_t)(part_stride * 8) | (uintptr_t)(comp_stride * 8)) & 15)))
+            return LF_ERR_ARG;
+    }
+    for (int t = 0; t < nct; ++t)
+        if (!c0[t] || !c1[t] || !out0[t] || !out1[t]) return LF_ERR_ARG;
+    const int64_t need = lf_linear_transform_batch_ws_words(p, nct);
+    if (need && (!ws || ws_words < need || ((uintptr_t)ws & 15))) return LF_ERR_ARG;
+    int64_t *base = need ? ws : p->x4;
+    const int nc = pt0 ? 2 : 1;
+    for (int t0 = 0; t0 < nct;) {
+        const int g = lt_batch_group(p, nct - t0);
+        if (g == 1) {   // a straggler: the flat op, whose scratch is the first slot of this one's
+            if (int e = lf_linear_transform(p, c0[t0], c1[t0], nr, p_host, ksk, part_stride, comp_stride, row_off, key_format, pt, pt_stride, pt0,
+                                            rescale_scales, round_at, ws, ws_words, out0[t0], out1[t0], stream))
+                return e;
+            t0 += 1;
+            continue;
+        }
+        // 1. c^_t = P NTT(c0_t) (and P NTT(c1_t) for the step-0 term) on the ordinary rows, as lf_linear_transform forms them:
+        //    chat [g][nc][ell][N], one canonical copy and one forward transform for the group
+        int64_t *chat = base, *md = base + 2 * g * poly;
+        {
+            const int64_t *srcs[8];
+            int64_t *dsts[8];
+            for (int t = 0; t < g; ++t)
+                for (int c = 0; c < nc; ++c) srcs[t * nc + c] = c ? c1[t0 + t] : c0[t0 + t], dsts[t * nc + c] = chat + (t * nc + c) * poly;
+            if (int e = lf_galois_batch(srcs, dsts, g * nc, ell, logN, 1, p->_2q, dev, stream)) return e;
+            if (int e = lf_ntt(chat, g * nc, ell, logN, p->psi, p->psi_dp, p->q_host, p->Rs, 0, p->_2q, p->ql, p->qh, p->kl, p->kh, dev, stream))
+                return e;
+            for (int i = 0; i < g * nc; ++i)
+                if (int e = lf_mont_enter(chat + i * poly, p->PR, ell, N, p->ql, p->qh, p->kl, p->kh, dev, stream)) return e;
+        }
+        // 2. the digits of the g c1 (canonical, no permutation), ONE extension + forward NTT of all of them
+        if (nr) {
+            const int64_t *srcs[4];
+            int64_t *states[4];
+            for (int t = 0; t < g; ++t) srcs[t] = c1[t0 + t], states[t] = p->state + t * poly;
+            if (int e = lf_ks_digits_batch(srcs, states, g, p->dig_nparts, p->dig_desc, p->dig_tab, N, 1, p->_2q, p->ql, p->qh, p->kl, p->kh, dev,
+                                           stream))
+                return e;
+            if (int e = lf_ks_fwd_batch(p->state, poly, g, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, p->ext, p->psi, p->psi_dp, p->q_host,
+                                        p->ql, p->qh, p->kl, p->kh, (hipStream_t)stream))
+                return e;
+        }
+        // 3. the launches into the g pairs of sums, ONE inverse NTT of the 2 g polynomials (planes through the spent digits)
+        const int64_t spare = p->nparts >= 2 ? ((int64_t)g * p->nparts * rows) << logN : 0;
+        if (int e = lf_ks_tail_ltb(g, nr, p_host, p->nparts, rows, ell, logN, ksk, part_stride, comp_stride, row_off, key_format, pt, pt_stride, pt0,
+                                   chat, nc * poly, p->ext, p->sum, spare ? p->ext : nullptr, spare, p->ipsi, p->ipsi_dp, p->Ninv, p->q_host,
+                                   p->ql, p->qh, p->kl, p->kh, (hipStream_t)stream))
+            return e;
+        // 4. one mod-down and one rescale of the 2 g polynomials into the callers' [ell - 1][N] pairs
+        const int64_t *ss[8], *ins[8], *row0[8];
+        int64_t *mds[8], *outs[8];
+        for (int t = 0; t < 2 * g; ++t) {
+            ss[t] = p->sum + t * (int64_t)rows * N;
+            mds[t] = md + t * poly, row0[t] = mds[t], ins[t] = mds[t] + N;
+            outs[t] = (t & 1) ? out1[t0 + t / 2] : out0[t0 + t / 2];
+        }
+        if (int e = moddown_any(p, ss, mds, nullptr, 2 * g, 0, nullptr, stream)) return e;
+        if (int e = lf_rescale_batch(ins, row0, outs, 2 * g, ell - 1, N, rescale_scales, round_at, p->ql + 1, p->qh + 1, p->kl + 1, p->kh + 1,
+                                     dev, stream))
+            return e;
+        t0 += g;
+    }
+    return 0;
 }
 
 /* ---- rotation sum: sum_i rot(ct, step_i) [+ ct], summed in the NTT domain over Q P, ONE inverse NTT and mod-down for the

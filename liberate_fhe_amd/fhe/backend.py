@@ -11,7 +11,7 @@ import ctypes
 
 import torch
 
-from .._native import lib, check, KsPlan, LF_KEY_PLANES, LF_LT_MATMUL_BSGS_MAX_GIANTS, LF_LT_MATMUL_BSGS_MAX_SUMS
+from .._native import lib, check, KsPlan, LF_KEY_PLANES, LF_LT_MATMUL_BSGS_MAX_GIANTS, LF_LT_MATMUL_BSGS_MAX_SUMS, LF_LT_BATCH_MAX_CTS
 from ..ntt import ntt_cuda, twiddles
 
 
@@ -541,6 +541,36 @@ class HipBackend:
                                       _p(pt), 0 if pt is None else pt.stride(0), _p(pt0), _p(scales), round_at, _p(ws),
                                       0 if ws is None else ws.numel(), out.data_ptr(), out.data_ptr() + out.stride(0) * 8, st),
               "lf_linear_transform")
+
+    # csrc/ckks_ks.hip: LF_LTB_KEYS, the keys one launch of ks_inner_ltb_kernel loops over (tests/test_linear_transform_batch_cpu.py
+    # holds this copy to the source); include/ckks_hip.h: LF_LT_BATCH_MAX_CTS through _native.py's copy
+    lt_batch_keys_per_launch = 8
+    lt_batch_max_cts = LF_LT_BATCH_MAX_CTS
+
+    @staticmethod
+    def linear_transform_batch_ws_words(plan, nct):
+        return int(lib.lf_linear_transform_batch_ws_words(ctypes.byref(plan), nct))
+
+    def linear_transform_batch_native(self, plan, c0s, c1s, exponents, keys, first_part, row_off, pt, pt0, scales, round_at, outs, ws=None):
+        """linear_transform_native for len(c0s) <= lt_batch_max_cts ciphertexts under the same diagonals and keys as ONE native call
+        (lf_linear_transform_batch): groups of 4, 2 or 1 ciphertexts (plan.max_nct permitting) share every launch, and the inner
+        product reads each key and diagonal word once per group.  c0s / c1s: the components, one tensor each per ciphertext;
+        outs: one [2, ell - 1, N] tensor per ciphertext; ws: >= linear_transform_batch_ws_words(plan, len(c0s)) words (None
+        when that is 0); the rest as linear_transform_native."""
+        dev, st = _ds(outs[0])
+        n = len(keys)
+        bases = (ctypes.c_void_p * max(n, 1))()
+        ps = cs = 0
+        for i, key in enumerate(keys):
+            bases[i], ps, cs = self._key_args(key, first_part)
+        fmt = {self._kfmt(k) for k in keys}
+        if len(fmt) > 1:
+            raise ValueError("linear_transform_batch_native: the keys of one call must share one format")
+        exps = (ctypes.c_int64 * max(n, 1))(*exponents)
+        check(lib.lf_linear_transform_batch(ctypes.byref(plan), len(c0s), _parr(c0s), _parr(c1s), n, exps, bases, ps, cs, row_off,
+                                            fmt.pop() if fmt else 0, _p(pt), 0 if pt is None else pt.stride(0), _p(pt0), _p(scales),
+                                            round_at, _p(ws), 0 if ws is None else ws.numel(), _parr([o[0] for o in outs]),
+                                            _parr([o[1] for o in outs]), st), "lf_linear_transform_batch")
 
     @staticmethod
     def rotate_sum_ws_words(plan):

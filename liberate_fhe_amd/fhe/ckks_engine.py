@@ -2112,7 +2112,8 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMa
         nparts = len(tabs["order"])
         fused = logN >= self.backend.fused_ks_min_logN
         gather = getattr(self.backend, "ks_gather", None)
-        digits = self._ks_digits_exchanged(ct.data[1], level, galois=(1, True)) if sel else {}
+        c1 = [t if t.is_contiguous() else t.contiguous() for t in ct.data[1]]   # (the digit kernels take a raw pointer and a row pitch of N)
+        digits = self._ks_digits_exchanged(c1, level, galois=(1, True)) if sel else {}
         c0o, c1o = [], []
         for i, d in enumerate(loc):
             li = self.local_ids.index(d)
@@ -2181,6 +2182,107 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMa
                                        self._vec("Rs", d, level, True), cs, PiP=tabs[("pip", d)], **mkw)
             c0o.append(out[0]); c1o.append(out[1])
         return self.rescale(self._new((c0o, c1o), types.origins["ct"], level=level))
+
+    # group sizes of linear_transform_batch's native path, largest first (a subset of backend.ks_batch_sizes that starts at its
+    # largest: lf_linear_transform_batch itself takes 4, then 2); a size that does not beat the loop is left out here and its
+    # ciphertexts take linear_transform one by one — the words are the same (DESIGN.md §4.2 has the numbers)
+    lt_batch_sizes = (4, 2)
+
+    def linear_transform_batch(self, cts: list, diags, rotks) -> list:
+        """linear_transform of many ciphertexts under the SAME diagonals and keys: returns exactly
+        [linear_transform(ct, diags, rotks) for ct in cts], word for word and in order (the words are linear_transform's own; a
+        ciphertext may appear several times; an empty list gives []).  diags: an encode_diagonals object or a {step: vector}
+        mapping, which is encoded ONCE, at cts[0].level; rotks: as linear_transform takes them.  What linear_transform refuses is
+        refused here for the whole list before anything is encoded, allocated or launched: a wrong origin, an NTT-domain or
+        special-limb ciphertext, no level left, a missing key (named by its step), diagonals at another level than a ciphertext
+        (NotMatchDataStructState, naming its index).
+        Where linear_transform's native call applies (every limb of the level on one device of this process, a backend with
+        lf_linear_transform_batch, contiguous operands) groups of 4 and 2 ciphertexts (lt_batch_sizes, over the plan of groups
+        of 4) go through ONE native call: a group shares every launch, and its inner product — nearly all of the op — reads
+        each key and each encoded diagonal once per group instead of once per ciphertext, looping over the keys inside the
+        kernel (ks_inner_ltb_kernel) with the group's running sums in registers.  Ciphertexts that do not qualify, the one
+        left over by the groups, and every ciphertext on a backend without the entry take linear_transform one by one.
+        Baby-step / giant-step diagonals (encode_diagonals(.., bsgs=n1)) are accepted and run as the loop of linear_transform:
+        a batched baby-step / giant-step form is not built."""
+        cts = list(cts)
+        if not cts:
+            return []
+        for ct in cts:
+            if not is_struct(ct) or ct.origin != types.origins["ct"]:
+                raise errors.NotMatchType(origin=getattr(ct, "origin", type(ct).__name__), to=types.origins["ct"])
+        keys = list(rotks.values()) if isinstance(rotks, dict) else list(rotks)
+        by_step = {}
+        for k in keys:
+            if not is_struct(k) or types.origins["rotk"] not in k.origin:
+                raise errors.NotMatchType(origin=getattr(k, "origin", type(k).__name__), to=types.origins["rotk"])
+            by_step.setdefault(int(k.origin.split(":")[-1]) % self.num_slots, k)
+        for ct in cts:
+            if ct.ntt_state or ct.include_special:
+                raise NotImplementedError("linear_transform_batch: coefficient-domain ciphertexts without special limbs only")
+        for ct in cts:
+            if ct.level + 1 >= self.num_levels:
+                raise errors.MaximumLevelError(level=ct.level, level_max=self.num_levels)
+        level, N = cts[0].level, self.ctx.N
+        if is_struct(diags):
+            bsgs = diags.origin.startswith(types.origins["diag_bsgs"])
+            if not bsgs and not diags.origin.startswith(types.origins["diag"]):
+                raise errors.NotMatchType(origin=diags.origin, to=types.origins["diag"])
+            dlevel, dname = diags.level, diags.origin
+            need = [s for part in self.bsgs_steps(diags)[1:] for s in part] if bsgs else self.diagonal_steps(diags)
+        else:
+            bsgs, dlevel, dname = False, level, types.origins["diag"] + "(a mapping, encoded at the level of ciphertext 0)"
+            need = sorted({int(delta) % self.num_slots for delta in dict(diags)})
+        for i, ct in enumerate(cts):
+            if ct.level != dlevel:
+                raise errors.NotMatchDataStructState(origin=f"{dname} at level {dlevel}, ciphertext {i} at level {ct.level}")
+        for s in need:
+            if s and s not in by_step:
+                raise errors.NotMatchType(origin=f"no key for step {s}", to=types.origins["rotk"] + str(s))
+        if not is_struct(diags):
+            diags = self.encode_diagonals(diags, level)
+        d = self._native_level(level)
+        if bsgs or d is None or not hasattr(self.backend, "linear_transform_batch_native"):
+            return [self.linear_transform(ct, diags, by_step) for ct in cts]
+        out = [None] * len(cts)
+        ready = [i for i, ct in enumerate(cts) if ct.data[0][0].is_contiguous() and ct.data[1][0].is_contiguous()]
+        sizes = [k for k in self.lt_batch_sizes if k in getattr(self.backend, "ks_batch_sizes", ())]
+        native, pos = [], 0
+        while True:
+            n = next((k for k in sizes if k <= len(ready) - pos), 0)
+            if not n:
+                break
+            native += ready[pos:pos + n]
+            pos += n
+        if native:
+            steps = self.diagonal_steps(diags)
+            j0 = steps.index(0) if 0 in steps else None
+            sel = [j for j, s in enumerate(steps) if s]
+            rkeys = [by_step[steps[j]] for j in sel]
+            exps = [encdec.galois_exponent(N, steps[j]) for j in sel]
+            owner = self.ntt.p.rescaler_loc[level]
+            round_at = self.ctx.q[self.ntt.p.destination_arrays[level][owner][0]] // 2
+            plan, _, first_part, row_off = self._op_plan(level, d, nct=4)
+            i0 = self._loc(0, special=True).index(d)
+            pack = self._diag_pack(diags)[self.local_ids.index(d)]
+            pt = None
+            if sel:   # (as linear_transform: the keyed diagonals are one slice of the pack, or a copy)
+                pt = pack[sel[0]:sel[-1] + 1] if sel[-1] - sel[0] + 1 == len(sel) else pack[sel].contiguous()
+            kpacks = [self._key_pack(k)[i0] for k in rkeys]
+            cap = self.backend.lt_batch_max_cts - self.backend.lt_batch_max_cts % max(sizes)
+            for a in range(0, len(native), cap):
+                idx = native[a:a + cap]
+                words = self.backend.linear_transform_batch_ws_words(plan, len(idx))
+                ws = self._ws("lt_batch_ws", (words,), d) if words else None
+                outs = [torch.empty((2, plan.ell - 1, N), dtype=torch.int64, device=self.ntt.devices[d]) for _ in idx]
+                self.backend.linear_transform_batch_native(plan, [cts[i].data[0][0] for i in idx], [cts[i].data[1][0] for i in idx],
+                                                           exps, kpacks, first_part, row_off, pt, None if j0 is None else pack[j0],
+                                                           self.rescale_scales[level][d], round_at, outs, ws)
+                for i, o in zip(idx, outs):
+                    out[i] = self._new(([o[0]], [o[1]]), types.origins["ct"], level=level + 1)
+        for i, ct in enumerate(cts):
+            if out[i] is None:
+                out[i] = self.linear_transform(ct, diags, by_step)
+        return out
 
     def _linear_transform_bsgs(self, ct, diags, by_step):
         """linear_transform on encode_diagonals(.., bsgs=n1) diagonals: y = sum_g rot(sum_b pt_{g,b} * rot(x, b), g), so that k

@@ -646,6 +646,33 @@ int lf_linear_transform_bsgs(const lf_ks_plan *plan, const int64_t *c0, const in
                              int64_t pt_stride, const int64_t *gcount, const int64_t *bidx, const int64_t *rescale_scales,
                              int64_t round_at, int64_t *ws, int64_t ws_words, int64_t *out0, int64_t *out1, void *stream);
 
+/* lf_linear_transform_bsgs for nct ciphertexts under the SAME diagonals and keys.  c0 / c1 / out0 / out1: HOST arrays of nct
+ * device pointers (a ciphertext may appear several times); everything else means what it means in lf_linear_transform_bsgs.
+ * Output t has exactly the words of lf_linear_transform_bsgs on ciphertext t.  The ciphertexts are taken in groups of
+ * min(4, plan->max_nct), then 2, then 1, as lf_linear_transform_batch takes them; a group of one IS lf_linear_transform_bsgs.
+ * Enqueued per group of g = 4 or 2: canonical copies of the 2 g polynomials, ONE forward NTT of them (enter_ntt) on the ell
+ * ordinary rows, the products with plan->PR, each copied into slot 0 of its member, zero on the special rows; with nb > 0
+ * lf_ks_digits_batch (gal_pinv = 1) into plan->state + t ell N, ONE extension + forward NTT of all g nparts digits into
+ * plan->ext, and per baby key ONE launch of ks_inner_babyb_kernel<g> into the g slots of that key (the key crosses HBM once for
+ * the group); per group of 4, 2 or 1 giant steps one launch of lt_diag_products_kernel PER MEMBER (the diagonals are read once
+ * per member), then per keyed giant step of that group the inverse NTT of each member's S^g_1, ONE lf_ks_moddown_ws of the g
+ * polynomials, ONE lf_ks_digits_batch, ONE extension + forward NTT and ONE launch of ks_inner_giantb_kernel<g> adding into the
+ * g accumulators (the steps lf_lt_matmul_bsgs takes for outputs that share a giant step); ONE inverse NTT of the g accumulator
+ * pairs, ONE mod-down of the 2 g polynomials, ONE lf_rescale_batch into out0[t] / out1[t] [ell - 1][N].
+ * `ws`, lent by the caller and 16-byte aligned, holds at least lf_linear_transform_bsgs_batch_ws_words(plan, nb, nct) words:
+ * per member of the largest group its nb + 1 baby pairs, four S pairs and the accumulator, then the g polynomials w, the
+ * mod-down's [2 g][ell][N] result and the larger of the two mod-down workspaces.  It grows with the largest group, not with nct;
+ * for nct = 1 it is lf_linear_transform_bsgs_ws_words(plan, nb); it is 0 for a plan, an nb or an nct the entry refuses.
+ * LF_ERR_ARG before any launch for everything lf_linear_transform_bsgs refuses, nct < 1 or > LF_LT_BATCH_MAX_CTS, a NULL among
+ * the pointer arrays or their entries, and a workspace that is NULL, misaligned or too small. */
+int64_t lf_linear_transform_bsgs_batch_ws_words(const lf_ks_plan *plan, int nb, int nct);
+int lf_linear_transform_bsgs_batch(const lf_ks_plan *plan, int nct, const int64_t *const *c0, const int64_t *const *c1, int nb,
+                                   const int64_t *bp_host, const int64_t *const *bksk, int ng, const int64_t *gp_host,
+                                   const int64_t *const *gksk, int64_t part_stride, int64_t comp_stride, int64_t row_off,
+                                   int key_format, const int64_t *pt, int64_t pt_stride, const int64_t *gcount,
+                                   const int64_t *bidx, const int64_t *rescale_scales, int64_t round_at, int64_t *ws,
+                                   int64_t ws_words, int64_t *const *out0, int64_t *const *out1, void *stream);
+
 /* A matrix of linear transforms times a vector of ciphertexts (a matrix larger than one ciphertext's slots, or a layer over
  * several packed inputs): for o < k_out, out_o decrypts to
  *     sum_{i < k_in} sum_{step in steps(o, i)} diag_{o,i,step} * rot(m_i, step),

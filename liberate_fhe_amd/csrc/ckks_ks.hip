@@ -2074,6 +2074,123 @@ __global__ void __launch_bounds__(256) ks_inner_giantb_kernel(const i64 *__restr
     }
 }
 
+// ---- baby-step / giant-step transform of many ciphertexts (lf_linear_transform_bsgs_batch): the baby step of NCT ciphertexts
+// under ONE key -------------
+// ks_inner_baby_kernel<1, ..> for the NCT (2 or 4) ciphertexts of a group: the grid, the pi computation (one key, hence ONE pi:
+// src / sw once per thread) and the key / digit formats of ks_inner_giantb_kernel.  Per part the key's four words are loaded once
+// and multiplied into NCT x 4 accumulators; then per ciphertext the gathered word of its own P NTT(c0) on the ordinary rows, and
+// its pair u^{t,b} written in the format lt_diag_products_kernel reads, exactly as the single kernel writes it: dp_reduce once per
+// word to a canonical word on the fp64-class rows (the sums are per ciphertext: |sums| < (digits / 2 + 2) q, lf_fp64_digits_ok),
+// lazy words below 2q on the integer rows.  No read - add - write: the baby key's stream crosses HBM once for the group.
+static_assert(LF_FP64_MAX_DIGITS / 2 + 2 < 64, "ks_inner_babyb_kernel: digits / 2 + 2 (the word of P c0) must stay inside dp_reduce's 64 q");
+struct BabyBatchArgs {
+    const i64 *ksk;        // the key, at its first part
+    unsigned p;            // its exponent (odd, < 2N)
+    int ell;               // ordinary rows (the first `ell` of the rows)
+    i64 ext_stride;        // words between the ciphertexts' stacks of extended digits ([nparts][rows][N] each)
+    const i64 *chat0[4];   // ciphertext t: P NTT(c0) [ell][N], Montgomery form, words below 2q
+    i64 *u[4];             // .. its pair under this key [2][rows][N]: written
+};
+
+template <int NCT, bool PLANES, bool DPL>   // (the digit loop as in ks_inner_giantb_kernel: not unrolled for four ciphertexts)
+__global__ void __launch_bounds__(256) ks_inner_babyb_kernel(const i64 *__restrict__ ext, BabyBatchArgs ba, i64 part_stride, i64 comp_stride,
+                                                             i64 row_off, int nparts, int rows, int logN,
+                                                             const i64 *__restrict__ ql, const i64 *__restrict__ qh,
+                                                             const i64 *__restrict__ kl, const i64 *__restrict__ kh) {
+    const int r = blockIdx.y;
+    const i64 N = (i64)1 << logN;
+    const i64 j0 = (i64)blockIdx.x * 512 + threadIdx.x * 2;
+    if (j0 >= N) return;
+    const RowMod m = load_mod(ql, qh, kl, kh, r);
+    const unsigned sh = 32u - (unsigned)logN, mask = (2u << logN) - 1u;
+    const unsigned bj = (2u * (__builtin_bitreverse32((unsigned)j0) >> sh) + 1u);
+    const unsigned t0 = (bj * ba.p) & mask;
+    const unsigned mi = __builtin_bitreverse32((t0 - 1u) >> 1) >> sh;
+    const i64 src = (i64)(mi & ~1u);
+    const bool sw = (mi & 1u) != 0;
+    const i64 *krow = ba.ksk + (row_off + r) * N;
+    const bool ord = r < ba.ell;   // (wave-uniform; P NTT(c0) is read on ordinary rows only)
+    const i64 o0 = (i64)r * N + j0, o1 = ((i64)rows + r) * N + j0;
+    if (m.q < SMALL_PRIME_LIMIT) {
+        const RowDp d = make_dp(m);
+        constexpr int DIGITS_IN_FLIGHT = NCT == 4 ? 1 : KI_UNROLL;
+        double acc[NCT][2][2];
+#pragma unroll
+        for (int t = 0; t < NCT; ++t) acc[t][0][0] = acc[t][0][1] = acc[t][1][0] = acc[t][1][1] = 0.0;
+#pragma unroll DIGITS_IN_FLIGHT
+        for (int p = 0; p < nparts; ++p) {
+            const i64 *kr = krow + (i64)p * part_stride;
+            double k0x, k0y, k1x, k1y;
+            if (PLANES) {   // 16 + 8 bytes for both components (see lf_key_planes)
+                const lf_u4_t l = __builtin_nontemporal_load(reinterpret_cast<const lf_u4_t *>(reinterpret_cast<const unsigned *>(kr) + 2 * j0));
+                const lf_u2_t h = __builtin_nontemporal_load(reinterpret_cast<const lf_u2_t *>(reinterpret_cast<const unsigned *>(kr + comp_stride) + j0));
+                k0x = dp_from_planes(l.x, h.x & 0xffffu), k0y = dp_from_planes(l.y, h.x >> 16);
+                k1x = dp_from_planes(l.z, h.y & 0xffffu), k1y = dp_from_planes(l.w, h.y >> 16);
+            } else {
+                const longlong2 k0 = ld_nt(kr + j0);
+                const longlong2 k1 = ld_nt(kr + j0 + comp_stride);
+                k0x = dp_from_word(k0.x), k0y = dp_from_word(k0.y), k1x = dp_from_word(k1.x), k1y = dp_from_word(k1.y);
+            }
+            const i64 *er = ext + ((i64)p * rows + r) * N;
+#pragma unroll
+            for (int t = 0; t < NCT; ++t) {
+                double xa, xb;
+                ld_pair_dp(er + (i64)t * ba.ext_stride, src, N, DPL ? 1 : 0, xa, xb);
+                const double x0 = sw ? xb : xa, x1 = sw ? xa : xb;
+                acc[t][0][0] += dp_mulmod_bal(x0, k0x, d);
+                acc[t][0][1] += dp_mulmod_bal(x1, k0y, d);
+                acc[t][1][0] += dp_mulmod_bal(x0, k1x, d);
+                acc[t][1][1] += dp_mulmod_bal(x1, k1y, d);
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < NCT; ++t) {
+            if (ord) {
+                double ca, cb;
+                ld_pair_dp(ba.chat0[t] + (i64)r * N, src, N, 0, ca, cb);
+                acc[t][0][0] += sw ? cb : ca;
+                acc[t][0][1] += sw ? ca : cb;
+            }
+            longlong2 a, b;   // |sums| < (digits / 2 + 2) q, inside dp_reduce's 64 q
+            a.x = dp_to_word(dp_reduce(acc[t][0][0], d.q, d.qinv)), a.y = dp_to_word(dp_reduce(acc[t][0][1], d.q, d.qinv));
+            b.x = dp_to_word(dp_reduce(acc[t][1][0], d.q, d.qinv)), b.y = dp_to_word(dp_reduce(acc[t][1][1], d.q, d.qinv));
+            *reinterpret_cast<longlong2 *>(ba.u[t] + o0) = a;
+            *reinterpret_cast<longlong2 *>(ba.u[t] + o1) = b;
+        }
+    } else {
+        i64 acc[NCT][2][2];
+#pragma unroll
+        for (int t = 0; t < NCT; ++t) acc[t][0][0] = acc[t][0][1] = acc[t][1][0] = acc[t][1][1] = 0;
+        for (int p = 0; p < nparts; ++p) {
+            const i64 *kr = krow + (i64)p * part_stride + j0;
+            const longlong2 k0 = ld_nt(kr);
+            const longlong2 k1 = ld_nt(kr + comp_stride);
+            const i64 *er = ext + ((i64)p * rows + r) * N + src;
+#pragma unroll
+            for (int t = 0; t < NCT; ++t) {
+                const longlong2 v = *reinterpret_cast<const longlong2 *>(er + (i64)t * ba.ext_stride);
+                const u64 x0 = (u64)(sw ? v.y : v.x), x1 = (u64)(sw ? v.x : v.y);
+                acc[t][0][0] = csub(acc[t][0][0] + mm62u(x0, (u64)k0.x, m.q, m.k), m.q2);
+                acc[t][0][1] = csub(acc[t][0][1] + mm62u(x1, (u64)k0.y, m.q, m.k), m.q2);
+                acc[t][1][0] = csub(acc[t][1][0] + mm62u(x0, (u64)k1.x, m.q, m.k), m.q2);
+                acc[t][1][1] = csub(acc[t][1][1] + mm62u(x1, (u64)k1.y, m.q, m.k), m.q2);
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < NCT; ++t) {
+            if (ord) {
+                const longlong2 v = *reinterpret_cast<const longlong2 *>(ba.chat0[t] + (i64)r * N + src);
+                acc[t][0][0] = csub(acc[t][0][0] + (sw ? v.y : v.x), m.q2);
+                acc[t][0][1] = csub(acc[t][0][1] + (sw ? v.x : v.y), m.q2);
+            }
+            longlong2 a, b;
+            a.x = acc[t][0][0], a.y = acc[t][0][1], b.x = acc[t][1][0], b.y = acc[t][1][1];
+            *reinterpret_cast<longlong2 *>(ba.u[t] + o0) = a;
+            *reinterpret_cast<longlong2 *>(ba.u[t] + o1) = b;
+        }
+    }
+}
+
 // largest number of leading stages (logN - 12) whose extension + strided pass runs as the column kernel (lf_tune).
 // With the digit loop as a runtime loop (R loads in flight, 100 VGPRs at R = 16) the column form also wins at logN 16:
 // gold cc_mult 2 104-2 130 -> 2 168-2 183 ops/s, rotate 2 653-2 695 -> 2 733-2 763, 64 rotations under one key
@@ -2101,6 +2218,8 @@ bool digit_planes(int logN, const RowList &dp, const RowList &in) {
 //     inner_kernel (the same body)
 //   ks_inner_baby_kernel, ks_inner_lt_     one word of P c0 below 2q                  nparts / 2 + 2 < 64:  nparts <= 123
 //     kernel (it reduces there with dp_reduce_bal, |x| < 2^52, and its running pair stays within (NR + 2) q)
+//   ks_inner_babyb_kernel                  per ciphertext as ks_inner_baby_kernel: one word of P c0 below 2q (the NCT sums of a
+//                                          launch are separate accumulators)          nparts / 2 + 2 < 64:  nparts <= 123
 //   ks_inner_ltb_kernel                    per key and ciphertext as ks_inner_lt_kernel               nparts <= 123
 //     (its NCT running pairs stay in registers over the LF_LTB_KEYS keys of a launch: one start term — a balanced product or a
 //     canonical word below q — and LF_LTB_KEYS balanced products, |S| <= (LF_LTB_KEYS / 2 + 1) q = 5 q < 64 q, reduced once
@@ -2886,6 +3005,51 @@ int lf_ks_giant_sums_batch(int nct, int64_t p, int nparts, int rows, int logN, c
     }
 #undef LF_GIANTB_LAUNCH
 #undef LF_GIANTB_CASE
+    return (int)hipGetLastError();
+}
+
+// ---- the launch of lf_linear_transform_bsgs_batch that is its own (ckks_ops.hip checks the arguments and owns the order) ----
+// baby step of nct (2 or 4) ciphertexts under one key: u[t] = the sum over the parts of ciphertext t's digits ext + t * nparts rows N
+// gathered by pi_p times the key part, + chat0[t] gathered on the ordinary rows on component 0; every key word is read once for
+// the group
+int lf_ks_baby_sums_batch(int nct, int64_t p, int nparts, int rows, int ell, int logN, const int64_t *ksk, int64_t part_stride,
+                          int64_t comp_stride, int64_t row_off, int key_format, const int64_t *ext, const int64_t *const *chat0,
+                          int64_t *const *u, const int64_t *q_host, const int64_t *ql, const int64_t *qh, const int64_t *kl,
+                          const int64_t *kh, hipStream_t st) {
+    if ((nct != 2 && nct != 4) || !key_args_ok(ksk, part_stride, comp_stride, key_format) || !ext || !chat0 || !u || nparts < 1 ||
+        logN <= NTT_TILE_LOG_MAX || logN > KS_LOGN_MAX || p <= 0 || p >= ((int64_t)2 << logN) || !(p & 1) || ell < 0 || ell > rows)
+        return LF_ERR_ARG;
+    if (rows < 1 || rows > MAX_LIST_ROWS || !lf_fp64_digits_ok(nparts, rows, q_host)) return LF_ERR_ARG;
+    RowList dp, in;
+    classify_rows(rows, q_host, dp, in);
+    const bool dplanes = digit_planes(logN, dp, in);
+    if (int e = lf_fmt_expect(ext, ((size_t)nct * nparts * rows << logN) * 8, dplanes ? LF_FMT_PLANES : LF_FMT_RAW)) return e;
+    BabyBatchArgs ba{};
+    ba.ksk = (const i64 *)ksk, ba.p = (unsigned)p, ba.ell = ell, ba.ext_stride = ((i64)nparts * rows) << logN;
+    for (int t = 0; t < nct; ++t) {
+        if (!chat0[t] || !u[t]) return LF_ERR_ARG;
+        for (int k = 0; k < t; ++k)
+            if (u[k] == u[t]) return LF_ERR_ARG;   // (two ciphertexts of one launch never share a pair)
+        ba.chat0[t] = (const i64 *)chat0[t], ba.u[t] = (i64 *)u[t];
+    }
+    const dim3 grid((unsigned)((((i64)1 << logN) + 511) / 512), (unsigned)rows);
+    const bool planes = key_format == LF_KEY_PLANES;
+#define LF_BABYB_LAUNCH(NCT, PL, DPLB)                                                                                         \
+    hipLaunchKernelGGL((ks_inner_babyb_kernel<NCT, PL, DPLB>), grid, dim3(256), 0, st, (const i64 *)ext, ba, (i64)part_stride, \
+                       (i64)comp_stride, (i64)row_off, nparts, rows, logN, (const i64 *)ql, (const i64 *)qh, (const i64 *)kl,  \
+                       (const i64 *)kh)
+#define LF_BABYB_CASE(NCT)                                                                                                   \
+    if (planes && dplanes) LF_BABYB_LAUNCH(NCT, true, true);                                                                 \
+    else if (planes) LF_BABYB_LAUNCH(NCT, true, false);                                                                      \
+    else if (dplanes) LF_BABYB_LAUNCH(NCT, false, true);                                                                     \
+    else LF_BABYB_LAUNCH(NCT, false, false)
+    if (nct == 2) {
+        LF_BABYB_CASE(2);
+    } else {
+        LF_BABYB_CASE(4);
+    }
+#undef LF_BABYB_LAUNCH
+#undef LF_BABYB_CASE
     return (int)hipGetLastError();
 }
 

@@ -66,6 +66,12 @@ int lf_ks_giant_sums_batch(int nct, int64_t p, int nparts, int rows, int logN, c
                            const int64_t *q_host, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh,
                            hipStream_t st);
 
+// ckks_ks.hip: the launch of lf_linear_transform_bsgs_batch that is its own
+int lf_ks_baby_sums_batch(int nct, int64_t p, int nparts, int rows, int ell, int logN, const int64_t *ksk, int64_t part_stride,
+                          int64_t comp_stride, int64_t row_off, int key_format, const int64_t *ext, const int64_t *const *chat0,
+                          int64_t *const *u, const int64_t *q_host, const int64_t *ql, const int64_t *qh, const int64_t *kl,
+                          const int64_t *kh, hipStream_t st);
+
 // ckks_ks.hip: the launches of lf_cc_dot that are its own
 int lf_dot_tensor(int g, const int64_t *x, int64_t *T, int64_t *t2, int ell, int logN, int xpl, int first, const int64_t *ql,
                   const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st);
@@ -896,18 +902,16 @@ int64_t lf_linear_transform_bsgs_ws_words(const lf_ks_plan *p, int nb) {
     return pair * (nb + 1 + LF_BSGS_S_PAIRS + 1) + poly + 2 * poly + lf_ks_moddown_ws_words(1, p->ell, p->K, N);
 }
 
-int lf_linear_transform_bsgs(const lf_ks_plan *p, const int64_t *c0, const int64_t *c1, int nb, const int64_t *bp_host,
-                             const int64_t *const *bksk, int ng, const int64_t *gp_host, const int64_t *const *gksk,
-                             int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format, const int64_t *pt,
-                             int64_t pt_stride, const int64_t *gcount, const int64_t *bidx, const int64_t *rescale_scales,
-                             int64_t round_at, int64_t *ws, int64_t ws_words, int64_t *out0, int64_t *out1, void *stream) {
-    if (!plan_ok(p) || !p->PR || p->ell < 2 || nb < 0 || nb > LF_BSGS_MAX_BABY_KEYS || ng < 1 || !c0 || !c1 || !rescale_scales || !out0 ||
-        !out1 || !pt || !gp_host || !gksk || !gcount || !bidx || (nb && (!bp_host || !bksk)) ||
-        (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES))
+// what lf_linear_transform_bsgs refuses in its keys, giant steps and diagonals (everything but the ciphertext, the outputs and the
+// workspace): 0 or LF_ERR_ARG, nothing launched
+static int bsgs_args_ok(const lf_ks_plan *p, int nb, const int64_t *bp_host, const int64_t *const *bksk, int ng, const int64_t *gp_host,
+                        const int64_t *const *gksk, int64_t part_stride, int64_t comp_stride, int key_format, const int64_t *pt,
+                        int64_t pt_stride, const int64_t *gcount, const int64_t *bidx, const int64_t *rescale_scales) {
+    if (!plan_ok(p) || !p->PR || p->ell < 2 || nb < 0 || nb > LF_BSGS_MAX_BABY_KEYS || ng < 1 || !rescale_scales || !pt || !gp_host ||
+        !gksk || !gcount || !bidx || (nb && (!bp_host || !bksk)) || (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES))
         return LF_ERR_ARG;
-    const int ell = p->ell, rows = p->ell + p->K, logN = p->logN, dev = p->device;
-    const int64_t N = (int64_t)1 << logN, twoN = 2 * N, poly = (int64_t)ell * N, pair = 2 * (int64_t)rows * N;
-    if (pt_stride < (int64_t)rows * N) return LF_ERR_ARG;
+    const int64_t N = (int64_t)1 << p->logN, twoN = 2 * N;
+    if (pt_stride < (int64_t)(p->ell + p->K) * N) return LF_ERR_ARG;
     auto key_ok = [&](const int64_t *k, int64_t e) {
         if (!k || e <= 0 || e >= twoN || !(e & 1)) return false;
         return key_format != LF_KEY_PLANES || !((((uintptr_t)k | (uintptr_t)(part_stride * 8) | (uintptr_t)(comp_stride * 8)) & 15));
@@ -924,6 +928,20 @@ int lf_linear_transform_bsgs(const lf_ks_plan *p, const int64_t *c0, const int64
         }
         ndiag += gcount[i];
     }
+    return 0;
+}
+
+int lf_linear_transform_bsgs(const lf_ks_plan *p, const int64_t *c0, const int64_t *c1, int nb, const int64_t *bp_host,
+                             const int64_t *const *bksk, int ng, const int64_t *gp_host, const int64_t *const *gksk,
+                             int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format, const int64_t *pt,
+                             int64_t pt_stride, const int64_t *gcount, const int64_t *bidx, const int64_t *rescale_scales,
+                             int64_t round_at, int64_t *ws, int64_t ws_words, int64_t *out0, int64_t *out1, void *stream) {
+    if (!c0 || !c1 || !out0 || !out1) return LF_ERR_ARG;
+    if (int e = bsgs_args_ok(p, nb, bp_host, bksk, ng, gp_host, gksk, part_stride, comp_stride, key_format, pt, pt_stride, gcount, bidx,
+                             rescale_scales))
+        return e;
+    const int ell = p->ell, rows = p->ell + p->K, logN = p->logN, dev = p->device;
+    const int64_t N = (int64_t)1 << logN, poly = (int64_t)ell * N, pair = 2 * (int64_t)rows * N;
     const int64_t need = lf_linear_transform_bsgs_ws_words(p, nb);
     if (!ws || ws_words < need) return LF_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
@@ -1161,6 +1179,43 @@ int lf_lt_matmul(const lf_ks_plan *p, int k_in, int k_out, const int64_t *const 
 // polynomials the giant phase brings down at once: groups of 4, 2 or 1 outputs within the batch the plan is sized for
 static int bsgs_giant_group(const lf_ks_plan *p) { return p->max_nct < 4 ? p->max_nct : 4; }
 
+// the giant step of n (4, 2 or 1) pairs S^g under ONE key, added into their accumulators: per pair the inverse NTT of S^g_1 (the pair
+// layout stays), then for the group ONE mod-down into w, ONE digit launch, ONE extension + forward pass and ONE launch of the key
+// switch, with each pair's S^g_0 gathered on all rows.  w: n [ell][N] polynomials; mdws: the workspace of a mod-down of n
+static int bsgs_giant_step(const lf_ks_plan *p, int n, int64_t *const *S, int64_t *const *accs, int64_t gp, const int64_t *gksk,
+                           int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format, int64_t *w, int64_t *mdws,
+                           int64_t mdws_words, void *stream) {
+    const int ell = p->ell, rows = p->ell + p->K, logN = p->logN, dev = p->device;
+    const int64_t N = (int64_t)1 << logN, poly = (int64_t)ell * N;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t *ss[4], *s0s[4], *srcs[4];
+    int64_t *ws1[4], *states[4];
+    for (int t = 0; t < n; ++t) {
+        int64_t *S0 = S[t], *S1 = S0 + (int64_t)rows * N;
+        if (int e = lf_intt(S1, 1, rows, logN, p->ipsi, p->ipsi_dp, p->q_host, p->Ninv, 2, 0, p->_2q, p->ql, p->qh, p->kl, p->kh, dev, stream))
+            return e;
+        ss[t] = S1, s0s[t] = S0, ws1[t] = w + t * poly, srcs[t] = ws1[t], states[t] = p->state + t * poly;
+    }
+    if (int e = lf_ks_moddown_ws(ss, ws1, nullptr, n, ell, p->K, N, mdws, mdws_words, p->PiR, p->PiP, p->Rs, 0, nullptr, p->ql, p->qh, p->kl,
+                                 p->kh, dev, stream))
+        return e;
+    if (int e = lf_ks_digits_batch(srcs, states, n, p->dig_nparts, p->dig_desc, p->dig_tab, N, 1, p->_2q, p->ql, p->qh, p->kl, p->kh, dev,
+                                   stream))
+        return e;
+    if (n == 1) {
+        if (int e = lf_ks_fwd(p->state, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, p->ext, p->psi, p->psi_dp, p->q_host, p->ql, p->qh,
+                              p->kl, p->kh, dev, stream))
+            return e;
+        return lf_ks_giant_sums(gp, p->nparts, rows, logN, gksk, part_stride, comp_stride, row_off, key_format, p->ext, s0s[0], accs[0],
+                                p->q_host, p->ql, p->qh, p->kl, p->kh, st);
+    }
+    if (int e = lf_ks_fwd_batch(p->state, poly, n, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, p->ext, p->psi, p->psi_dp, p->q_host,
+                                p->ql, p->qh, p->kl, p->kh, st))
+        return e;
+    return lf_ks_giant_sums_batch(n, gp, p->nparts, rows, logN, gksk, part_stride, comp_stride, row_off, key_format, p->ext, s0s, accs,
+                                  p->q_host, p->ql, p->qh, p->kl, p->kh, st);
+}
+
 int64_t lf_lt_matmul_bsgs_ws_words(const lf_ks_plan *p, int nb_max, int k_out, int keyed_sums) {
     if (!plan_ok(p) || nb_max < 0 || nb_max > LF_BSGS_MAX_BABY_KEYS || k_out < 1 || k_out > LF_LT_MATMUL_MAX_OUTPUTS || keyed_sums < 0 ||
         keyed_sums > LF_LT_MATMUL_BSGS_MAX_SUMS)
@@ -1316,37 +1371,11 @@ int lf_lt_matmul_bsgs(const lf_ks_plan *p, int k_in, int k_out, const int64_t *c
         for (size_t a0 = 0; a0 < os.size();) {
             const size_t left = os.size() - a0;
             const int n = (left >= 4 && gw >= 4) ? 4 : (left >= 2 && gw >= 2) ? 2 : 1;
-            const int64_t *ss[4], *s0s[4], *srcs[4];
-            int64_t *ws1[4], *accs[4], *states[4];
-            for (int t = 0; t < n; ++t) {
-                int64_t *S0 = target(os[a0 + t], j), *S1 = S0 + (int64_t)rows * N;
-                // S^{o,g}_1 down to Q: inverse NTT (the pair layout stays), then the group's mod-down, digits, extension and transform
-                if (int e = lf_intt(S1, 1, rows, logN, p->ipsi, p->ipsi_dp, p->q_host, p->Ninv, 2, 0, p->_2q, p->ql, p->qh, p->kl, p->kh, dev,
-                                    stream))
-                    return e;
-                ss[t] = S1, s0s[t] = S0, ws1[t] = w + t * poly, srcs[t] = ws1[t], states[t] = p->state + t * poly, accs[t] = A + os[a0 + t] * pair;
-            }
-            if (int e = lf_ks_moddown_ws(ss, ws1, nullptr, n, ell, p->K, N, mdws, mdws_words, p->PiR, p->PiP, p->Rs, 0, nullptr, p->ql, p->qh,
-                                         p->kl, p->kh, dev, stream))
+            int64_t *Ss[4], *accs[4];
+            for (int t = 0; t < n; ++t) Ss[t] = target(os[a0 + t], j), accs[t] = A + os[a0 + t] * pair;
+            if (int e = bsgs_giant_step(p, n, Ss, accs, gp_host[j], gksk[j], part_stride, comp_stride, row_off, key_format, w, mdws, mdws_words,
+                                        stream))
                 return e;
-            if (int e = lf_ks_digits_batch(srcs, states, n, p->dig_nparts, p->dig_desc, p->dig_tab, N, 1, p->_2q, p->ql, p->qh, p->kl, p->kh,
-                                           dev, stream))
-                return e;
-            if (n == 1) {
-                if (int e = lf_ks_fwd(p->state, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, p->ext, p->psi, p->psi_dp, p->q_host, p->ql,
-                                      p->qh, p->kl, p->kh, dev, stream))
-                    return e;
-                if (int e = lf_ks_giant_sums(gp_host[j], p->nparts, rows, logN, gksk[j], part_stride, comp_stride, row_off, key_format, p->ext,
-                                             s0s[0], accs[0], p->q_host, p->ql, p->qh, p->kl, p->kh, st))
-                    return e;
-            } else {
-                if (int e = lf_ks_fwd_batch(p->state, poly, n, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, p->ext, p->psi, p->psi_dp,
-                                            p->q_host, p->ql, p->qh, p->kl, p->kh, st))
-                    return e;
-                if (int e = lf_ks_giant_sums_batch(n, gp_host[j], p->nparts, rows, logN, gksk[j], part_stride, comp_stride, row_off, key_format,
-                                                   p->ext, s0s, accs, p->q_host, p->ql, p->qh, p->kl, p->kh, st))
-                    return e;
-            }
             a0 += n;
         }
     }
@@ -1371,6 +1400,143 @@ int lf_lt_matmul_bsgs(const lf_ks_plan *p, int k_in, int k_out, const int64_t *c
         if (int e = lf_rescale_batch(ins, row0, outs, 2 * g, ell - 1, N, rescale_scales, round_at, p->ql + 1, p->qh + 1, p->kl + 1, p->kh + 1,
                                      dev, stream))
             return e;
+    }
+    return 0;
+}
+
+/* ---- baby-step / giant-step linear transform of many ciphertexts under the same diagonals and keys (include/ckks_hip.h): groups
+ * of 4, 2 or 1 as lf_linear_transform_batch; a group of g shares every launch but the diagonal products, and each baby and giant
+ * key crosses HBM once for the g ciphertexts ---- */
+int64_t lf_linear_transform_bsgs_batch_ws_words(const lf_ks_plan *p, int nb, int nct) {
+    if (!plan_ok(p) || nb < 0 || nb > LF_BSGS_MAX_BABY_KEYS || nct < 1 || nct > LF_LT_BATCH_MAX_CTS) return 0;
+    const int g = lt_batch_group(p, nct);
+    if (g == 1) return lf_linear_transform_bsgs_ws_words(p, nb);
+    const int64_t N = (int64_t)1 << p->logN, pair = 2 * (int64_t)(p->ell + p->K) * N, poly = (int64_t)p->ell * N;
+    const int64_t md_w = lf_ks_moddown_ws_words(g, p->ell, p->K, N), md_t = lf_ks_moddown_ws_words(2 * g, p->ell, p->K, N);
+    // per member its baby pairs (slot 0: the ciphertext), the S pairs of one launch and the accumulator A; the g polynomials w, the
+    // final mod-down's 2 g results, and the workspace of either mod-down (the plan's own is primed for pairs)
+    return g * pair * (nb + 1 + LF_BSGS_S_PAIRS + 1) + g * poly + 2 * g * poly + (md_w > md_t ? md_w : md_t);
+}
+
+int lf_linear_transform_bsgs_batch(const lf_ks_plan *p, int nct, const int64_t *const *c0, const int64_t *const *c1, int nb,
+                                   const int64_t *bp_host, const int64_t *const *bksk, int ng, const int64_t *gp_host,
+                                   const int64_t *const *gksk, int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format,
+                                   const int64_t *pt, int64_t pt_stride, const int64_t *gcount, const int64_t *bidx,
+                                   const int64_t *rescale_scales, int64_t round_at, int64_t *ws, int64_t ws_words, int64_t *const *out0,
+                                   int64_t *const *out1, void *stream) {
+    if (nct < 1 || nct > LF_LT_BATCH_MAX_CTS || !c0 || !c1 || !out0 || !out1) return LF_ERR_ARG;
+    if (int e = bsgs_args_ok(p, nb, bp_host, bksk, ng, gp_host, gksk, part_stride, comp_stride, key_format, pt, pt_stride, gcount, bidx,
+                             rescale_scales))
+        return e;
+    for (int t = 0; t < nct; ++t)
+        if (!c0[t] || !c1[t] || !out0[t] || !out1[t]) return LF_ERR_ARG;
+    const int64_t need = lf_linear_transform_bsgs_batch_ws_words(p, nb, nct);
+    if (!need || !ws || ws_words < need || ((uintptr_t)ws & 15)) return LF_ERR_ARG;
+    const int ell = p->ell, rows = p->ell + p->K, logN = p->logN, dev = p->device;
+    const int64_t N = (int64_t)1 << logN, poly = (int64_t)ell * N, half = (int64_t)rows * N, pair = 2 * half;
+    hipStream_t st = (hipStream_t)stream;
+    if (int e = lf_set_device(dev)) return e;
+    for (int t0 = 0; t0 < nct;) {
+        const int g = lt_batch_group(p, nct - t0);
+        if (g == 1) {   // a straggler: the single op, whose workspace is the head of this one's
+            if (int e = lf_linear_transform_bsgs(p, c0[t0], c1[t0], nb, bp_host, bksk, ng, gp_host, gksk, part_stride, comp_stride, row_off,
+                                                 key_format, pt, pt_stride, gcount, bidx, rescale_scales, round_at, ws, ws_words, out0[t0],
+                                                 out1[t0], stream))
+                return e;
+            t0 += 1;
+            continue;
+        }
+        // member t: its pairs u_t [nb + 1], S_t [LF_BSGS_S_PAIRS]; then the g accumulators (one run of 2 g polynomials), w, md, mdws
+        const int64_t member = (nb + 1 + LF_BSGS_S_PAIRS) * pair;
+        int64_t *A = ws + g * member, *w = A + g * pair, *md = w + g * poly, *mdws = md + 2 * g * poly;
+        const int64_t md_w = lf_ks_moddown_ws_words(g, ell, p->K, N), md_t = lf_ks_moddown_ws_words(2 * g, ell, p->K, N);
+        const int64_t mdws_words = md_w > md_t ? md_w : md_t;
+        auto U = [&](int t) { return ws + t * member; };
+        auto S = [&](int t) { return ws + t * member + (nb + 1) * pair; };
+        // 1. slot 0 of every member = P NTT(c0), P NTT(c1) on the ordinary rows, zero on the special rows: canonical copies and ONE
+        //    forward NTT of the 2 g polynomials in `md` (free until the tail), times P R, then into the slots
+        {
+            const int64_t *srcs[8];
+            int64_t *dsts[8];
+            for (int t = 0; t < g; ++t) srcs[2 * t] = c0[t0 + t], srcs[2 * t + 1] = c1[t0 + t];
+            for (int i = 0; i < 2 * g; ++i) dsts[i] = md + i * poly;
+            if (int e = lf_galois_batch(srcs, dsts, 2 * g, ell, logN, 1, p->_2q, dev, stream)) return e;
+            if (int e = lf_ntt(md, 2 * g, ell, logN, p->psi, p->psi_dp, p->q_host, p->Rs, 0, p->_2q, p->ql, p->qh, p->kl, p->kh, dev, stream))
+                return e;
+            for (int i = 0; i < 2 * g; ++i) {
+                int64_t *slot = U(i / 2) + (i & 1) * half;
+                if (int e = lf_mont_enter(dsts[i], p->PR, ell, N, p->ql, p->qh, p->kl, p->kh, dev, stream)) return e;
+                if (hipError_t e = hipMemcpyAsync(slot, dsts[i], (size_t)poly * 8, hipMemcpyDeviceToDevice, st)) return (int)e;
+                if (hipError_t e = hipMemsetAsync(slot + poly, 0, (size_t)p->K * N * 8, st)) return (int)e;
+            }
+        }
+        // 2. baby steps: the digits of the g c1 (canonical, no permutation), ONE extension + forward NTT of all of them, per baby key
+        //    ONE launch into the g slots of that key
+        if (nb) {
+            const int64_t *srcs[4], *chat0[4];
+            int64_t *states[4], *us[4];
+            for (int t = 0; t < g; ++t) srcs[t] = c1[t0 + t], states[t] = p->state + t * poly, chat0[t] = U(t);
+            if (int e = lf_ks_digits_batch(srcs, states, g, p->dig_nparts, p->dig_desc, p->dig_tab, N, 1, p->_2q, p->ql, p->qh, p->kl, p->kh, dev,
+                                           stream))
+                return e;
+            if (int e = lf_ks_fwd_batch(p->state, poly, g, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, p->ext, p->psi, p->psi_dp, p->q_host,
+                                        p->ql, p->qh, p->kl, p->kh, st))
+                return e;
+            for (int b = 0; b < nb; ++b) {
+                for (int t = 0; t < g; ++t) us[t] = U(t) + (b + 1) * pair;
+                if (int e = lf_ks_baby_sums_batch(g, bp_host[b], p->nparts, rows, ell, logN, bksk[b], part_stride, comp_stride, row_off, key_format,
+                                                  p->ext, chat0, us, p->q_host, p->ql, p->qh, p->kl, p->kh, st))
+                    return e;
+            }
+        }
+        // 3. giant steps, LF_BSGS_S_PAIRS per launch of each member's diagonal products; giant step 0 writes the accumulators
+        if (gp_host[0] != 0)
+            if (hipError_t e = hipMemsetAsync(A, 0, (size_t)g * pair * 8, st)) return (int)e;
+        int64_t first = 0;   // first diagonal of the giant step in the pack
+        for (int i0 = 0; i0 < ng;) {
+            const int left = ng - i0, gc = left >= 4 ? 4 : left >= 2 ? 2 : 1;
+            const int64_t *pts[4];
+            unsigned long long slots[4];
+            for (int i = 0; i < gc; ++i) {
+                pts[i] = pt + first * pt_stride;
+                slots[i] = 0;
+                for (int64_t k = 0; k < gcount[i0 + i]; ++k) slots[i] |= 1ull << bidx[first + k];
+                first += gcount[i0 + i];
+            }
+            for (int t = 0; t < g; ++t) {
+                int64_t *outs[4];
+                for (int i = 0; i < gc; ++i) outs[i] = gp_host[i0 + i] == 0 ? A + t * pair : S(t) + i * pair;
+                if (int e = lf_lt_diag_products(gc, U(t), nb + 1, pts, slots, pt_stride, outs, rows, logN, p->ql, p->qh, p->kl, p->kh, st))
+                    return e;
+            }
+            for (int i = 0; i < gc; ++i) {
+                if (gp_host[i0 + i] == 0) continue;
+                int64_t *Ss[4], *accs[4];
+                for (int t = 0; t < g; ++t) Ss[t] = S(t) + i * pair, accs[t] = A + t * pair;
+                if (int e = bsgs_giant_step(p, g, Ss, accs, gp_host[i0 + i], gksk[i0 + i], part_stride, comp_stride, row_off, key_format, w, mdws,
+                                            mdws_words, stream))
+                    return e;
+            }
+            i0 += gc;
+        }
+        // 4. the tail: ONE exact inverse NTT of the g accumulator pairs, ONE mod-down of the 2 g polynomials, ONE rescale into the
+        //    callers' [ell - 1][N] pairs
+        if (int e = lf_intt(A, 2 * g, rows, logN, p->ipsi, p->ipsi_dp, p->q_host, p->Ninv, 2, 0, p->_2q, p->ql, p->qh, p->kl, p->kh, dev, stream))
+            return e;
+        const int64_t *ss[8], *ins[8], *row0[8];
+        int64_t *mds[8], *outs[8];
+        for (int t = 0; t < 2 * g; ++t) {
+            ss[t] = A + t * half;
+            mds[t] = md + t * poly, row0[t] = mds[t], ins[t] = mds[t] + N;
+            outs[t] = (t & 1) ? out1[t0 + t / 2] : out0[t0 + t / 2];
+        }
+        if (int e = lf_ks_moddown_ws(ss, mds, nullptr, 2 * g, ell, p->K, N, mdws, mdws_words, p->PiR, p->PiP, p->Rs, 0, nullptr, p->ql, p->qh,
+                                     p->kl, p->kh, dev, stream))
+            return e;
+        if (int e = lf_rescale_batch(ins, row0, outs, 2 * g, ell - 1, N, rescale_scales, round_at, p->ql + 1, p->qh + 1, p->kl + 1, p->kh + 1,
+                                     dev, stream))
+            return e;
+        t0 += g;
     }
     return 0;
 }

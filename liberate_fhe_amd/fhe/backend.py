@@ -623,6 +623,38 @@ class HipBackend:
                                            _p(scales), round_at, _p(ws), ws.numel(), out.data_ptr(),
                                            out.data_ptr() + out.stride(0) * 8, st), "lf_linear_transform_bsgs")
 
+    @staticmethod
+    def linear_transform_bsgs_batch_ws_words(plan, nb, nct):
+        return int(lib.lf_linear_transform_bsgs_batch_ws_words(ctypes.byref(plan), nb, nct))
+
+    def linear_transform_bsgs_batch_native(self, plan, c0s, c1s, baby_exps, baby_keys, giant_exps, giant_keys, first_part, row_off,
+                                           pack, counts, slots, scales, round_at, outs, ws):
+        """linear_transform_bsgs_native for len(c0s) <= lt_batch_max_cts ciphertexts under the same diagonals and keys as ONE native
+        call (lf_linear_transform_bsgs_batch): groups of 4, 2 or 1 ciphertexts (plan.max_nct permitting) share every launch but the
+        diagonal products, and every baby and giant key is read once per group.  c0s / c1s: the components, one tensor each per
+        ciphertext; outs: one [2, ell - 1, N] tensor per ciphertext; ws: at least
+        linear_transform_bsgs_batch_ws_words(plan, len(baby_keys), len(c0s)) words, 16-byte aligned; the rest as
+        linear_transform_bsgs_native."""
+        dev, st = _ds(outs[0])
+        nb, ng = len(baby_keys), len(giant_keys)
+        keyed = list(baby_keys) + [k for k in giant_keys if k is not None]
+        fmt = {self._kfmt(k) for k in keyed}
+        if len(fmt) > 1:
+            raise ValueError("linear_transform_bsgs_batch_native: the keys of one call must share one format")
+        ps = cs = 0
+        bb, gb = (ctypes.c_void_p * max(nb, 1))(), (ctypes.c_void_p * max(ng, 1))()
+        for i, key in enumerate(baby_keys):
+            bb[i], ps, cs = self._key_args(key, first_part)
+        for i, key in enumerate(giant_keys):
+            if key is not None:
+                gb[i], ps, cs = self._key_args(key, first_part)
+        i64 = lambda v: (ctypes.c_int64 * max(len(v), 1))(*v)
+        check(lib.lf_linear_transform_bsgs_batch(ctypes.byref(plan), len(c0s), _parr(c0s), _parr(c1s), nb, i64(baby_exps), bb, ng,
+                                                 i64(giant_exps), gb, ps, cs, row_off, fmt.pop() if fmt else 0, _p(pack),
+                                                 pack.stride(0), i64(counts), i64(slots), _p(scales), round_at, _p(ws), ws.numel(),
+                                                 _parr([o[0] for o in outs]), _parr([o[1] for o in outs]), st),
+              "lf_linear_transform_bsgs_batch")
+
     # include/ckks_hip.h: LF_LT_MATMUL_MAX_INPUTS / LF_LT_MATMUL_MAX_OUTPUTS (tests/test_lt_matmul_cpu.py holds these copies to the
     # header); the keyed steps of a column are bounded by bsgs_max_baby_keys
     lt_matmul_max_inputs = 64

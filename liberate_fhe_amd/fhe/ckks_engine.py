@@ -2187,6 +2187,9 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMa
     # largest: lf_linear_transform_batch itself takes 4, then 2); a size that does not beat the loop is left out here and its
     # ciphertexts take linear_transform one by one — the words are the same (DESIGN.md §4.2 has the numbers)
     lt_batch_sizes = (4, 2)
+    # the same for baby-step / giant-step diagonals (lf_linear_transform_bsgs_batch): both sizes beat the loop at every measured
+    # point
+    lt_bsgs_batch_sizes = (4, 2)
 
     def linear_transform_batch(self, cts: list, diags, rotks) -> list:
         """linear_transform of many ciphertexts under the SAME diagonals and keys: returns exactly
@@ -2202,8 +2205,12 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMa
         each key and each encoded diagonal once per group instead of once per ciphertext, looping over the keys inside the
         kernel (ks_inner_ltb_kernel) with the group's running sums in registers.  Ciphertexts that do not qualify, the one
         left over by the groups, and every ciphertext on a backend without the entry take linear_transform one by one.
-        Baby-step / giant-step diagonals (encode_diagonals(.., bsgs=n1)) are accepted and run as the loop of linear_transform:
-        a batched baby-step / giant-step form is not built."""
+        Baby-step / giant-step diagonals (encode_diagonals(.., bsgs=n1)) give [linear_transform(ct, ..)] of that form in the same
+        way: where its native call applies (a native level, at most bsgs_max_baby_keys keyed baby steps, the pack in ascending
+        steps, a backend with lf_linear_transform_bsgs_batch, contiguous operands) groups of lt_bsgs_batch_sizes ciphertexts go
+        through ONE native call.  A group shares every launch but the diagonal products: each baby key (ks_inner_babyb_kernel)
+        and each giant key is read once per group, and the tails of every giant step (inverse NTT, mod-down, digits, forward
+        pass) run once per group.  Everything else takes linear_transform one by one and keeps its place in the result."""
         cts = list(cts)
         if not cts:
             return []
@@ -2241,11 +2248,17 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMa
         if not is_struct(diags):
             diags = self.encode_diagonals(diags, level)
         d = self._native_level(level)
-        if bsgs or d is None or not hasattr(self.backend, "linear_transform_batch_native"):
+        entry = "linear_transform_bsgs_batch_native" if bsgs else "linear_transform_batch_native"
+        if d is None or not hasattr(self.backend, entry):
             return [self.linear_transform(ct, diags, by_step) for ct in cts]
+        if bsgs:
+            steps, _, _, kb, _ = self._bsgs_layout(diags)
+            if not self._bsgs_native_ok(steps, kb):
+                return [self.linear_transform(ct, diags, by_step) for ct in cts]
         out = [None] * len(cts)
         ready = [i for i, ct in enumerate(cts) if ct.data[0][0].is_contiguous() and ct.data[1][0].is_contiguous()]
-        sizes = [k for k in self.lt_batch_sizes if k in getattr(self.backend, "ks_batch_sizes", ())]
+        sizes = [k for k in (self.lt_bsgs_batch_sizes if bsgs else self.lt_batch_sizes)
+                 if k in getattr(self.backend, "ks_batch_sizes", ())]
         native, pos = [], 0
         while True:
             n = next((k for k in sizes if k <= len(ready) - pos), 0)
@@ -2253,6 +2266,19 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMa
                 break
             native += ready[pos:pos + n]
             pos += n
+        if native and bsgs:
+            plan, _, first_part, row_off = self._op_plan(level, d, nct=4)
+            args = self._bsgs_native_args(level, d, diags, by_step, first_part, row_off)
+            cap = self.backend.lt_batch_max_cts - self.backend.lt_batch_max_cts % max(sizes)
+            for a in range(0, len(native), cap):
+                idx = native[a:a + cap]
+                ws = self._ws("lt_bsgs_batch_ws", (self.backend.linear_transform_bsgs_batch_ws_words(plan, len(kb), len(idx)),), d)
+                outs = [torch.empty((2, plan.ell - 1, N), dtype=torch.int64, device=self.ntt.devices[d]) for _ in idx]
+                self.backend.linear_transform_bsgs_batch_native(plan, [cts[i].data[0][0] for i in idx],
+                                                                [cts[i].data[1][0] for i in idx], *args, outs, ws)
+                for i, o in zip(idx, outs):
+                    out[i] = self._new(([o[0]], [o[1]]), types.origins["ct"], level=level + 1)
+            native = []
         if native:
             steps = self.diagonal_steps(diags)
             j0 = steps.index(0) if 0 in steps else None
@@ -2284,6 +2310,40 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMa
                 out[i] = self.linear_transform(ct, diags, by_step)
         return out
 
+    def _bsgs_layout(self, diags):
+        """(steps of the pack, baby steps, giant steps, keyed baby steps, giant step -> [(row of the pack, baby step)]) of
+        encode_diagonals(.., bsgs=n1) diagonals: what _linear_transform_bsgs and linear_transform_batch derive their calls from"""
+        n1, babies, giants = self.bsgs_steps(diags)
+        steps = self.diagonal_steps(diags)
+        kb = [b for b in babies if b]                                    # keyed baby steps: slot 1 + index (slot 0: the ciphertext)
+        groups = {g: [] for g in giants}                                 # giant step -> [(row of the pack, baby step)], ascending b
+        for j, s in enumerate(steps):
+            groups[s - s % n1].append((j, s % n1))
+        return steps, babies, giants, kb, groups
+
+    def _bsgs_native_ok(self, steps, kb):
+        """what the native baby-step / giant-step entries need of the diagonals: the baby keys within the masks of the diagonal
+        products, the pack in (giant, baby) order"""
+        return len(kb) <= getattr(self.backend, "bsgs_max_baby_keys", 0) and steps == sorted(steps)
+
+    def _bsgs_native_args(self, level, d, diags, by_step, first_part, row_off):
+        """the arguments of backend.linear_transform_bsgs_native between the ciphertext and the output (the batched call takes the
+        same): baby exponents and keys, giant exponents and keys, first_part, row_off, the pack, the diagonals per giant step,
+        the baby slot of every diagonal, the rescale constants"""
+        N = self.ctx.N
+        _, _, giants, kb, groups = self._bsgs_layout(diags)
+        slot = {b: 1 + i for i, b in enumerate(kb)}
+        slot[0] = 0
+        owner = self.ntt.p.rescaler_loc[level]
+        round_at = self.ctx.q[self.ntt.p.destination_arrays[level][owner][0]] // 2
+        i0 = self._loc(0, special=True).index(d)
+        pack = self._diag_pack(diags)[self.local_ids.index(d)]
+        return ([encdec.galois_exponent(N, b) for b in kb], [self._key_pack(by_step[b])[i0] for b in kb],
+                [encdec.galois_exponent(N, g) if g else 0 for g in giants],
+                [self._key_pack(by_step[g])[i0] if g else None for g in giants], first_part, row_off, pack,
+                [len(groups[g]) for g in giants], [slot[b] for g in giants for _, b in groups[g]],
+                self.rescale_scales[level][d], round_at)
+
     def _linear_transform_bsgs(self, ct, diags, by_step):
         """linear_transform on encode_diagonals(.., bsgs=n1) diagonals: y = sum_g rot(sum_b pt_{g,b} * rot(x, b), g), so that k
         diagonals need about n1 + k / n1 keys instead of k.  The words are those of: c0, c1 made canonical, E and c^ as in the flat
@@ -2295,35 +2355,19 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMa
         canonical words, so only residues of u, S, v and A reach the result.  One native call (lf_linear_transform_bsgs) where
         every limb of the level is on one device of this process; otherwise the same words through the engine's steps."""
         level, N, logN = ct.level, self.ctx.N, self.ctx.logN
-        n1, babies, giants = self.bsgs_steps(diags)
-        steps = self.diagonal_steps(diags)
+        steps, babies, giants, kb, groups = self._bsgs_layout(diags)
         for s in babies + giants:
             if s and s not in by_step:
                 raise errors.NotMatchType(origin=f"no key for step {s}", to=types.origins["rotk"] + str(s))
-        kb = [b for b in babies if b]                                    # keyed baby steps: slot 1 + index (slot 0: the ciphertext)
-        slot = {b: 1 + i for i, b in enumerate(kb)}
-        slot[0] = 0
-        groups = {g: [] for g in giants}                                 # giant step -> [(row of the pack, baby step)], ascending b
-        for j, s in enumerate(steps):
-            groups[s - s % n1].append((j, s % n1))
-        owner = self.ntt.p.rescaler_loc[level]
-        round_at = self.ctx.q[self.ntt.p.destination_arrays[level][owner][0]] // 2
 
         d = self._native_level(level)
         if d is not None and hasattr(self.backend, "linear_transform_bsgs_native") and \
-                len(kb) <= getattr(self.backend, "bsgs_max_baby_keys", 0) and \
-                steps == sorted(steps) and ct.data[0][0].is_contiguous() and ct.data[1][0].is_contiguous():
+                self._bsgs_native_ok(steps, kb) and ct.data[0][0].is_contiguous() and ct.data[1][0].is_contiguous():
             plan, _, first_part, row_off = self._op_plan(level, d)
-            i0 = self._loc(0, special=True).index(d)
-            pack = self._diag_pack(diags)[self.local_ids.index(d)]
             ws = self._ws("lt_bsgs_ws", (self.backend.linear_transform_bsgs_ws_words(plan, len(kb)),), d)
             out = torch.empty((2, plan.ell - 1, N), dtype=torch.int64, device=self.ntt.devices[d])
-            self.backend.linear_transform_bsgs_native(
-                plan, ct.data[0][0], ct.data[1][0], [encdec.galois_exponent(N, b) for b in kb],
-                [self._key_pack(by_step[b])[i0] for b in kb], [encdec.galois_exponent(N, g) if g else 0 for g in giants],
-                [self._key_pack(by_step[g])[i0] if g else None for g in giants], first_part, row_off, pack,
-                [len(groups[g]) for g in giants], [slot[b] for g in giants for _, b in groups[g]],
-                self.rescale_scales[level][d], round_at, out, ws)
+            self.backend.linear_transform_bsgs_native(plan, ct.data[0][0], ct.data[1][0],
+                                                      *self._bsgs_native_args(level, d, diags, by_step, first_part, row_off), out, ws)
             return self._new(([out[0]], [out[1]]), types.origins["ct"], level=level + 1)
 
         # orchestrated: the same words through the engine's steps (see linear_transform's own orchestration for the pieces)
@@ -2334,7 +2378,8 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMa
         inner = lambda d, idx, key: self._lt_inner(level, d, idx, key)
 
         # baby steps: u^b per device, kept for every giant step
-        digits = self._ks_digits_exchanged(ct.data[1], level, galois=(1, True)) if kb else {}
+        c1 = [t if t.is_contiguous() else t.contiguous() for t in ct.data[1]]   # (the digit kernels take a raw pointer and a row pitch of N)
+        digits = self._ks_digits_exchanged(c1, level, galois=(1, True)) if kb else {}
         u = []
         for i, d in enumerate(loc):
             li = self.local_ids.index(d)

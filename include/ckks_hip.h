@@ -614,6 +614,28 @@ int lf_rotate_sum(const lf_ks_plan *plan, const int64_t *c0, const int64_t *c1, 
                   const int64_t *const *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format,
                   int with_self, int64_t *ws, int64_t ws_words, int64_t *out0, int64_t *out1, void *stream);
 
+/* lf_rotate_sum for nct ciphertexts under the SAME keys.  c0 / c1 / out0 / out1: HOST arrays of nct device pointers (a ciphertext
+ * may appear several times); everything else means what it means in lf_rotate_sum.  Output t has exactly the words of
+ * lf_rotate_sum on ciphertext t.  The ciphertexts are taken in groups of min(4, plan->max_nct), then 2, then 1, as
+ * lf_linear_transform_batch takes them; a group of one IS lf_rotate_sum, with the first slot of this call's scratch as its own.
+ * Enqueued per group of g = 4 or 2: canonical copies of the g c0 (c1 with with_self), ONE forward NTT of them (enter_ntt) on the
+ * ell ordinary rows and the products with plan->PR; lf_ks_digits_batch (gal_pinv = 1) into plan->state + t ell N and ONE
+ * extension + forward NTT of all g nparts digits into plan->ext (nr > 0); per chunk of 8 keys (csrc/ckks_ks.hip: LF_RSB_KEYS) one
+ * launch of ks_inner_rsumb_kernel, which loops over the chunk's keys itself, loads every key word once for the g ciphertexts and
+ * keeps ONE accumulator pair per ciphertext for all keys of the launch, all launches adding into the g pairs plan->sum (nr = 0:
+ * one launch without keys); ONE inverse NTT of the 2 g polynomials (their planes pass through plan->ext, which is spent by
+ * then); ONE mod-down without addend of the 2 g polynomials straight into out0[t] / out1[t] [ell][N], canonical.  No rescale.
+ * The g (P c^0, P c^1) live in the group's slots of plan->x4 ([max_nct][4][ell][N], free during this op) or, with
+ * plan->x4 = NULL, in `ws` of at least lf_rotate_sum_batch_ws_words(plan, nct) words (2 g ell N for the largest group; 0: ws may
+ * be NULL; it grows with the largest group, not with nct; 0 also for a plan or an nct the op refuses), 16-byte aligned.
+ * LF_ERR_ARG before any launch for everything lf_rotate_sum refuses, nct < 1 or > LF_LT_BATCH_MAX_CTS, a NULL among the pointer
+ * arrays or their entries, and a workspace that is NULL where words are needed, misaligned or too small. */
+int64_t lf_rotate_sum_batch_ws_words(const lf_ks_plan *plan, int nct);
+int lf_rotate_sum_batch(const lf_ks_plan *plan, int nct, const int64_t *const *c0, const int64_t *const *c1,
+                        int nr, const int64_t *p_host, const int64_t *const *ksk, int64_t part_stride,
+                        int64_t comp_stride, int64_t row_off, int key_format, int with_self, int64_t *ws,
+                        int64_t ws_words, int64_t *const *out0, int64_t *const *out1, void *stream);
+
 /* Linear transform by the diagonal method in its baby-step / giant-step form: out decrypts to
  *     sum_g rot( sum_b diag_{g+b}(rolled by -g) * rot(m, b), g )        b = step mod n1, g = step - b,
  * so that k diagonals need about n1 + k / n1 rotation keys (and key streams) instead of k.  nb >= 0 baby keys with odd

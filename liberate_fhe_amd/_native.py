@@ -125,6 +125,8 @@ _SIGNATURES["lf_linear_transform_batch_ws_words"] = [_PL, _I]
 _SIGNATURES["lf_linear_transform_batch"] = [_PL, _I, _P, _P, _I, _P, _P, _L, _L, _L, _I, _P, _L, _P, _P, _L, _P, _L, _P, _P, _P]
 _SIGNATURES["lf_rotate_sum_ws_words"] = [_PL]
 _SIGNATURES["lf_rotate_sum"] = [_PL, _P, _P, _I, _P, _P, _L, _L, _L, _I, _I, _P, _L, _P, _P, _P]
+_SIGNATURES["lf_rotate_sum_batch_ws_words"] = [_PL, _I]
+_SIGNATURES["lf_rotate_sum_batch"] = [_PL, _I, _P, _P, _I, _P, _P, _L, _L, _L, _I, _I, _P, _L, _P, _P, _P]
 _SIGNATURES["lf_linear_transform_bsgs_ws_words"] = [_PL, _I]
 _SIGNATURES["lf_linear_transform_bsgs"] = [_PL, _P, _P, _I, _P, _P, _I, _P, _P, _L, _L, _L, _I, _P, _L, _P, _P, _P, _L, _P, _L, _P, _P, _P]
 _SIGNATURES["lf_linear_transform_bsgs_batch_ws_words"] = [_PL, _I, _I]

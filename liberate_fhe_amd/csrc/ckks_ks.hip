@@ -1650,6 +1650,185 @@ __global__ void __launch_bounds__(256) ks_inner_rsum_kernel(const i64 *__restric
     }
 }
 
+// ---- K3 of a batched rotation sum (lf_rotate_sum_batch): ks_inner_rsum_kernel for NCT ciphertexts under the SAME keys -----------
+// The grid, the pi computation and the key / digit formats are ks_inner_rsum_kernel's.  The kernel loops over the keys of its
+// launch itself (ra.nk <= LF_RSB_KEYS; keys and exponents travel in the argument struct, as in LtbArgs): per key and part the
+// key's four words are loaded once and multiplied into the NCT accumulator pairs acc[NCT][2][2] (ciphertext t's digits at
+// ext + t * ext_stride, gathered by that key's pi); on the ordinary rows c^0 of ciphertext t gathered by pi joins component 0.
+// ONE accumulator set per ciphertext serves ALL keys of the launch — ks_inner_rsum_kernel's single pair, times NCT — so there is
+// no running pair beside the accumulators (half the live doubles of ks_inner_ltb_kernel).  The first launch starts the pairs from
+// the self term P (c^0_t, c^1_t), ungathered, on the ordinary rows when asked to (self), else from zero; later launches start
+// from the pair the previous launch left at s + t * sum_stride.  The pairs leave in the format the sums' inverse pass reads (spl).
+// Only residues reach the result, so the additions come in the order that suits the loads.
+// fp64 class: an accumulator takes nk nparts balanced products (|.| <= q / 2 each), nk gathered words of c^0 and one start word
+// (all below 2q): |acc| <= (nk nparts / 2 + 2 nk + 2) q.  With nk = LF_RSB_KEYS = 8 and nparts = LF_FP64_MAX_DIGITS = 119 that is
+// 494 q < 2^9 q < 2^50 for q < 2^41: every partial sum is an integer below 2^52, exact in fp64, and the ONE dp_reduce_bal (exact
+// for |x| < 2^52) brings it to a balanced residue for dp_reduce, as in ks_inner_rsum_kernel.
+#define LF_RSB_KEYS 8   // keys per launch (backend.rsum_batch_keys_per_launch): the pairs' trip is 2 x 2 rows N words per 8 keys' streams
+static_assert(((unsigned long long)(LF_RSB_KEYS * LF_FP64_MAX_DIGITS / 2 + 2 * LF_RSB_KEYS + 2) << 41) < (1ull << 52),
+              "accumulators of ks_inner_rsumb_kernel: (keys nparts / 2 + 2 keys + 2) q must stay below dp_reduce_bal's 2^52");
+struct RsbArgs {
+    const i64 *ksk[LF_RSB_KEYS];   // key i, at its first part
+    unsigned p[LF_RSB_KEYS];       // its exponent (odd, < 2N)
+    const i64 *chat;               // ciphertext t at chat + t * chat_stride: P NTT(c0), P NTT(c1), [2][ell][N], words below 2q
+    i64 chat_stride, ext_stride, sum_stride;   // words between the ciphertexts' c^, extended digits and pairs of sums
+    int nk;                        // keys of this launch (0: the self term alone)
+    int ell;                       // ordinary rows (the first `ell` of the rows)
+    int first;                     // first launch: `s` is not read
+    int self;                      // the first launch starts from P (c^0_t, c^1_t) on the ordinary rows
+};
+
+template <int NCT, bool PLANES, bool DPL>
+__global__ void __launch_bounds__(256) ks_inner_rsumb_kernel(const i64 *__restrict__ ext, RsbArgs ra, i64 part_stride, i64 comp_stride,
+                                                             i64 row_off, i64 *__restrict__ s, int nparts, int rows, int logN, int spl,
+                                                             const i64 *__restrict__ ql, const i64 *__restrict__ qh,
+                                                             const i64 *__restrict__ kl, const i64 *__restrict__ kh) {
+    static_assert(NCT == 2 || NCT == 4, "ks_inner_rsumb_kernel: 2 or 4 ciphertexts");
+    const int r = blockIdx.y;
+    const i64 N = (i64)1 << logN;
+    const i64 j0 = (i64)blockIdx.x * 512 + threadIdx.x * 2;
+    if (j0 >= N) return;
+    const RowMod m = load_mod(ql, qh, kl, kh, r);
+    const unsigned sh = 32u - (unsigned)logN, mask = (2u << logN) - 1u;
+    const unsigned bj = (2u * (__builtin_bitreverse32((unsigned)j0) >> sh) + 1u);
+    const i64 krow = (row_off + r) * N;
+    const bool ord = r < ra.ell;
+    const i64 *c0row = ra.chat + (i64)r * N, *c1row = c0row + (i64)ra.ell * N;   // (read on ordinary rows only)
+    i64 *srow0 = s + (i64)r * N, *srow1 = s + ((i64)rows + r) * N;
+    constexpr int DIGITS_IN_FLIGHT = NCT >= 4 ? 1 : KI_UNROLL;   // (NCT digit pairs are in flight per key word already)
+    if (m.q < SMALL_PRIME_LIMIT) {
+        const RowDp d = make_dp(m);
+        double acc[NCT][2][2];
+        if (!ra.first) {   // the pairs the previous launch left (canonical words)
+#pragma unroll
+            for (int t = 0; t < NCT; ++t) {
+                ld_pair_dp(srow0 + t * ra.sum_stride, j0, N, spl, acc[t][0][0], acc[t][0][1]);
+                ld_pair_dp(srow1 + t * ra.sum_stride, j0, N, spl, acc[t][1][0], acc[t][1][1]);
+            }
+        } else if (ra.self && ord) {
+#pragma unroll
+            for (int t = 0; t < NCT; ++t) {
+                ld_pair_dp(c0row + t * ra.chat_stride, j0, N, 0, acc[t][0][0], acc[t][0][1]);
+                ld_pair_dp(c1row + t * ra.chat_stride, j0, N, 0, acc[t][1][0], acc[t][1][1]);
+            }
+        } else {
+#pragma unroll
+            for (int t = 0; t < NCT; ++t) acc[t][0][0] = acc[t][0][1] = acc[t][1][0] = acc[t][1][1] = 0.0;
+        }
+        for (int k = 0; k < ra.nk; ++k) {
+            const unsigned tk = (bj * ra.p[k]) & mask;
+            const unsigned mi = __builtin_bitreverse32((tk - 1u) >> 1) >> sh;
+            const i64 src = (i64)(mi & ~1u);
+            const bool sw = (mi & 1u) != 0;
+            const i64 *kbase = ra.ksk[k] + krow;
+#pragma unroll DIGITS_IN_FLIGHT
+            for (int p = 0; p < nparts; ++p) {
+                const i64 *er = ext + ((i64)p * rows + r) * N;
+                const i64 *kr = kbase + (i64)p * part_stride;
+                double k0x, k0y, k1x, k1y;
+                if (PLANES) {   // 16 + 8 bytes for both components (see lf_key_planes)
+                    const lf_u4_t l = __builtin_nontemporal_load(reinterpret_cast<const lf_u4_t *>(reinterpret_cast<const unsigned *>(kr) + 2 * j0));
+                    const lf_u2_t h = __builtin_nontemporal_load(reinterpret_cast<const lf_u2_t *>(reinterpret_cast<const unsigned *>(kr + comp_stride) + j0));
+                    k0x = dp_from_planes(l.x, h.x & 0xffffu), k0y = dp_from_planes(l.y, h.x >> 16);
+                    k1x = dp_from_planes(l.z, h.y & 0xffffu), k1y = dp_from_planes(l.w, h.y >> 16);
+                } else {
+                    const longlong2 w0 = ld_nt(kr + j0);
+                    const longlong2 w1 = ld_nt(kr + j0 + comp_stride);
+                    k0x = dp_from_word(w0.x), k0y = dp_from_word(w0.y), k1x = dp_from_word(w1.x), k1y = dp_from_word(w1.y);
+                }
+#pragma unroll
+                for (int t = 0; t < NCT; ++t) {
+                    double xa, xb;
+                    ld_pair_dp(er + t * ra.ext_stride, src, N, DPL ? 1 : 0, xa, xb);
+                    const double x0 = sw ? xb : xa, x1 = sw ? xa : xb;
+                    acc[t][0][0] += dp_mulmod_bal(x0, k0x, d);
+                    acc[t][0][1] += dp_mulmod_bal(x1, k0y, d);
+                    acc[t][1][0] += dp_mulmod_bal(x0, k1x, d);
+                    acc[t][1][1] += dp_mulmod_bal(x1, k1y, d);
+                }
+            }
+            if (ord) {
+#pragma unroll
+                for (int t = 0; t < NCT; ++t) {
+                    double ca, cb;
+                    ld_pair_dp(c0row + t * ra.chat_stride, src, N, 0, ca, cb);
+                    acc[t][0][0] += sw ? cb : ca;
+                    acc[t][0][1] += sw ? ca : cb;
+                }
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < NCT; ++t)
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                longlong2 o;   // |acc| <= (LF_RSB_KEYS nparts / 2 + 2 LF_RSB_KEYS + 2) q < 2^52: dp_reduce_bal first
+                o.x = dp_to_word(dp_reduce(dp_reduce_bal(acc[t][c][0], d), d.q, d.qinv));
+                o.y = dp_to_word(dp_reduce(dp_reduce_bal(acc[t][c][1], d), d.q, d.qinv));
+                i64 *srow = (c ? srow1 : srow0) + t * ra.sum_stride;
+                if (spl) {
+                    const lf_u2_t l = {(unsigned)o.x, (unsigned)o.y};
+                    *reinterpret_cast<lf_u2_t *>(reinterpret_cast<unsigned *>(srow) + j0) = l;
+                    *reinterpret_cast<unsigned *>(reinterpret_cast<unsigned short *>(srow + (N >> 1)) + j0) =
+                        (unsigned)((u64)o.x >> 32) | ((unsigned)((u64)o.y >> 32) << 16);
+                } else {
+                    *reinterpret_cast<longlong2 *>(srow + j0) = o;
+                }
+            }
+    } else {
+        i64 acc[NCT][2][2];   // lazy words below 2q throughout
+        if (!ra.first || (ra.self && ord)) {   // the previous launch's pairs, or the self term (both below 2q)
+            const i64 *a = ra.first ? c0row : srow0, *b = ra.first ? c1row : srow1;
+            const i64 stride = ra.first ? ra.chat_stride : ra.sum_stride;
+#pragma unroll
+            for (int t = 0; t < NCT; ++t) {
+                const longlong2 va = *reinterpret_cast<const longlong2 *>(a + t * stride + j0);
+                const longlong2 vb = *reinterpret_cast<const longlong2 *>(b + t * stride + j0);
+                acc[t][0][0] = va.x, acc[t][0][1] = va.y, acc[t][1][0] = vb.x, acc[t][1][1] = vb.y;
+            }
+        } else {
+#pragma unroll
+            for (int t = 0; t < NCT; ++t) acc[t][0][0] = acc[t][0][1] = acc[t][1][0] = acc[t][1][1] = 0;
+        }
+        for (int k = 0; k < ra.nk; ++k) {
+            const unsigned tk = (bj * ra.p[k]) & mask;
+            const unsigned mi = __builtin_bitreverse32((tk - 1u) >> 1) >> sh;
+            const i64 src = (i64)(mi & ~1u);
+            const bool sw = (mi & 1u) != 0;
+            const i64 *kbase = ra.ksk[k] + krow + j0;
+            for (int p = 0; p < nparts; ++p) {
+                const i64 *er = ext + ((i64)p * rows + r) * N;
+                const i64 *kr = kbase + (i64)p * part_stride;
+                const longlong2 w0 = ld_nt(kr);
+                const longlong2 w1 = ld_nt(kr + comp_stride);
+#pragma unroll
+                for (int t = 0; t < NCT; ++t) {
+                    const longlong2 v = *reinterpret_cast<const longlong2 *>(er + t * ra.ext_stride + src);
+                    const u64 x0 = (u64)(sw ? v.y : v.x), x1 = (u64)(sw ? v.x : v.y);
+                    acc[t][0][0] = csub(acc[t][0][0] + mm62u(x0, (u64)w0.x, m.q, m.k), m.q2);
+                    acc[t][0][1] = csub(acc[t][0][1] + mm62u(x1, (u64)w0.y, m.q, m.k), m.q2);
+                    acc[t][1][0] = csub(acc[t][1][0] + mm62u(x0, (u64)w1.x, m.q, m.k), m.q2);
+                    acc[t][1][1] = csub(acc[t][1][1] + mm62u(x1, (u64)w1.y, m.q, m.k), m.q2);
+                }
+            }
+            if (ord) {
+#pragma unroll
+                for (int t = 0; t < NCT; ++t) {
+                    const longlong2 v = *reinterpret_cast<const longlong2 *>(c0row + t * ra.chat_stride + src);
+                    acc[t][0][0] = csub(acc[t][0][0] + (sw ? v.y : v.x), m.q2);
+                    acc[t][0][1] = csub(acc[t][0][1] + (sw ? v.x : v.y), m.q2);
+                }
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < NCT; ++t) {
+            longlong2 o0, o1;
+            o0.x = acc[t][0][0], o0.y = acc[t][0][1], o1.x = acc[t][1][0], o1.y = acc[t][1][1];
+            *reinterpret_cast<longlong2 *>(srow0 + t * ra.sum_stride + j0) = o0;
+            *reinterpret_cast<longlong2 *>(srow1 + t * ra.sum_stride + j0) = o1;
+        }
+    }
+}
+
 // ---- baby-step / giant-step linear transform (lf_linear_transform_bsgs): y = sum_g rot(sum_b pt_{g,b} * rot(x, b), g) ------------
 // Three launches on the grid, the pi computation and the key / digit formats of the two kernels above, under names of their own:
 //   ks_inner_baby_kernel     per group of 4 / 2 / 1 baby keys the gathered sums over the digits, + P c0 gathered on the ordinary
@@ -2228,6 +2407,9 @@ bool digit_planes(int logN, const RowList &dp, const RowList &in) {
 //                                                                                     nparts / 2 + 4 < 64:  nparts <= 119
 //   ks_inner_rsum_kernel                   NR nparts products, NR + 1 words below 2q: reduced first with dp_reduce_bal
 //                                          (|x| < 2^52), so no bound of its own below 119 (see the kernel)
+//   ks_inner_rsumb_kernel                  per ciphertext nk nparts products, nk + 1 words below 2q over the nk <= LF_RSB_KEYS keys
+//                                          of a launch: (8 x 119 / 2 + 18) q = 494 q < 2^52, reduced once with dp_reduce_bal
+//                                          (static_assert there), so no bound of its own below 119
 // The tightest holds for all of them.  Integer-class rows reduce after every addition and have no such bound.
 bool lf_fp64_digits_ok(int nparts, int rows, const int64_t *q_host) {
     if (nparts <= LF_FP64_MAX_DIGITS || !q_host) return true;
@@ -2823,6 +3005,67 @@ int lf_ks_tail_rsum(int nr, const int64_t *p_host, int nparts, int rows, int ell
 #undef LF_RSUM_LAUNCH
 #undef LF_RSUM_CASE
     return ks_inv_sums(2, rows, logN, spl, cols_last, mixed, in, dp, (i64 *)scratch, (i64 *)s, ipsi_br, ipsi_dp, Ninv, ql, qh, kl, kh, st);
+}
+
+// The key-dependent part of lf_rotate_sum_batch (ckks_ops.hip) for nct (2 or 4) ciphertexts: per LF_RSB_KEYS keys ONE launch of
+// ks_inner_rsumb_kernel over the ciphertexts' extended digits ext [nct][nparts][rows][N] (nr = 0: the self term alone, one launch
+// without keys), all of them adding into the nct pairs of sums s [nct][2][rows][N]; then ONE inverse transform of the 2 nct
+// polynomials.  `scratch` (>= 2 nct rows N words, or NULL: the sums stay raw words, same outputs) as in lf_ks_tail_lt.
+// Ciphertext t's c^ = P NTT(c0), P NTT(c1) on the `ell` ordinary rows at chat + t * chat_stride (c1 only with `with_self`).
+// Internal: ckks_ops.hip checks the arguments (nr >= 0, odd exponents below 2N, with_self when nr == 0).
+int lf_ks_tail_rsumb(int nct, int nr, const int64_t *p_host, int nparts, int rows, int ell, int logN, const int64_t *const *ksk,
+                     int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format, int with_self, const int64_t *chat,
+                     int64_t chat_stride, const int64_t *ext, int64_t *s, int64_t *scratch, int64_t scratch_words,
+                     const int64_t *ipsi_br, const double *ipsi_dp, const int64_t *Ninv, const int64_t *q_host, const int64_t *ql,
+                     const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st) {
+    if ((nct != 2 && nct != 4) || !ipsi_dp || (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES) || nr < 0 ||
+        (nr == 0 && !with_self) || !chat || !ext || !s || ell < 0 || ell > rows || nparts < 1 || logN <= NTT_TILE_LOG_MAX ||
+        logN > KS_LOGN_MAX || (nr && (!ksk || !p_host)))
+        return LF_ERR_ARG;
+    if (rows < 1 || rows > MAX_LIST_ROWS || !lf_fp64_digits_ok(nparts, rows, q_host)) return LF_ERR_ARG;
+    for (int i = 0; i < nr; ++i)
+        if (!ksk[i] || (key_format == LF_KEY_PLANES && ((((uintptr_t)ksk[i] | (uintptr_t)(part_stride * 8) | (uintptr_t)(comp_stride * 8)) & 15))))
+            return LF_ERR_ARG;
+    const int tl = NTT_TILE_LOG_MAX, S1 = logN - tl;
+    RowList dp, in;
+    classify_rows(rows, q_host, dp, in);
+    const bool mixed = dp.n && in.n;
+    const bool dplanes = digit_planes(logN, dp, in);
+    const bool cols_last = S1 <= 4 || (S1 == 5 && mixed && g_ks_ext_cols_max > 4);
+    if (nr)   // the digits must be in the format the launches read (see ks_tail)
+        if (int e = lf_fmt_expect(ext, ((size_t)nct * nparts * rows << logN) * 8, dplanes ? LF_FMT_PLANES : LF_FMT_RAW)) return e;
+    const bool spl = dplanes && (g_more_planes & 1) && cols_last && scratch && scratch_words >= ((int64_t)2 * nct * rows << logN);
+    const dim3 grid((unsigned)((((i64)1 << logN) + 511) / 512), (unsigned)rows);
+    const bool planes = key_format == LF_KEY_PLANES;
+#define LF_RSB_LAUNCH(NCT, PL, DPLB)                                                                                         \
+    hipLaunchKernelGGL((ks_inner_rsumb_kernel<NCT, PL, DPLB>), grid, dim3(256), 0, st, (const i64 *)ext, ra, (i64)part_stride, \
+                       (i64)comp_stride, (i64)row_off, (i64 *)s, nparts, rows, logN, spl ? 1 : 0, (const i64 *)ql, (const i64 *)qh, \
+                       (const i64 *)kl, (const i64 *)kh)
+#define LF_RSB_CASE(NCT)                                                                                                     \
+    if (planes && dplanes) LF_RSB_LAUNCH(NCT, true, true);                                                                   \
+    else if (planes) LF_RSB_LAUNCH(NCT, true, false);                                                                        \
+    else if (dplanes) LF_RSB_LAUNCH(NCT, false, true);                                                                       \
+    else LF_RSB_LAUNCH(NCT, false, false)
+    for (int i0 = 0; i0 < nr || i0 == 0; i0 += LF_RSB_KEYS) {
+        const int g = nr - i0 < LF_RSB_KEYS ? nr - i0 : LF_RSB_KEYS;
+        RsbArgs ra{};
+        for (int t = 0; t < g; ++t) {
+            ra.ksk[t] = (const i64 *)ksk[i0 + t];
+            ra.p[t] = (unsigned)p_host[i0 + t];
+        }
+        ra.chat = (const i64 *)chat, ra.chat_stride = (i64)chat_stride;
+        ra.ext_stride = ((i64)nparts * rows) << logN, ra.sum_stride = ((i64)2 * rows) << logN;
+        ra.nk = g, ra.ell = ell, ra.first = i0 == 0, ra.self = with_self ? 1 : 0;
+        if (nct == 2) {
+            LF_RSB_CASE(2);
+        } else {
+            LF_RSB_CASE(4);
+        }
+    }
+#undef LF_RSB_LAUNCH
+#undef LF_RSB_CASE
+    return ks_inv_sums(2 * nct, rows, logN, spl, cols_last, mixed, in, dp, (i64 *)scratch, (i64 *)s, ipsi_br, ipsi_dp, Ninv, ql, qh, kl,
+                       kh, st);
 }
 
 // ---- the launches of lf_linear_transform_bsgs (ckks_ops.hip checks the arguments and owns the order) ----

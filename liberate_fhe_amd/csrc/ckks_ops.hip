@@ -45,6 +45,13 @@ int lf_ks_tail_rsum(int nr, const int64_t *p_host, int nparts, int rows, int ell
 int lf_ks_baby_sums(int nr, const int64_t *p_host, int nparts, int rows, int ell, int logN, const int64_t *const *ksk, int64_t part_stride,
                     int64_t comp_stride, int64_t row_off, int key_format, const int64_t *chat0, const int64_t *ext, int64_t *u,
                     const int64_t *q_host, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st);
+// ckks_ks.hip: the key-dependent part of lf_rotate_sum_batch for a group of 2 or 4 ciphertexts (the launches into the group's
+// pairs of sums + their one inverse NTT)
+int lf_ks_tail_rsumb(int nct, int nr, const int64_t *p_host, int nparts, int rows, int ell, int logN, const int64_t *const *ksk,
+                     int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format, int with_self, const int64_t *chat,
+                     int64_t chat_stride, const int64_t *ext, int64_t *s, int64_t *scratch, int64_t scratch_words,
+                     const int64_t *ipsi_br, const double *ipsi_dp, const int64_t *Ninv, const int64_t *q_host, const int64_t *ql,
+                     const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st);
 int lf_lt_diag_products(int ng, const int64_t *u, int nslots, const int64_t *const *pt, const unsigned long long *slots, int64_t pt_stride,
                         int64_t *const *out, int rows, int logN, const int64_t *ql, const int64_t *qh, const int64_t *kl,
                         const int64_t *kh, hipStream_t st);
@@ -888,6 +895,88 @@ int lf_rotate_sum(const lf_ks_plan *p, const int64_t *c0, const int64_t *c1, int
     const int64_t *ss[2] = {p->sum, p->sum + (int64_t)rows * N};
     int64_t *outs[2] = {out0, out1};
     return moddown_any(p, ss, outs, nullptr, 2, 0, nullptr, stream);
+}
+
+/* ---- rotation sum of many ciphertexts under the same keys (include/ckks_hip.h): groups of 4, 2 or 1 as lt_batch_group takes
+ * them; a group of g shares every launch, and its inner product reads each key word once for the g ciphertexts ---- */
+// per ciphertext of the largest group P NTT(c0), P NTT(c1): the plan's operand stacks x4 (free during this op), else `ws`
+int64_t lf_rotate_sum_batch_ws_words(const lf_ks_plan *p, int nct) {
+    if (!plan_ok(p) || nct < 1 || nct > LF_LT_BATCH_MAX_CTS || p->x4) return 0;
+    return ((int64_t)2 * lt_batch_group(p, nct) * p->ell) << p->logN;
+}
+
+int lf_rotate_sum_batch(const lf_ks_plan *p, int nct, const int64_t *const *c0, const int64_t *const *c1, int nr,
+                        const int64_t *p_host, const int64_t *const *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off,
+                        int key_format, int with_self, int64_t *ws, int64_t ws_words, int64_t *const *out0, int64_t *const *out1,
+                        void *stream) {
+    if (!plan_ok(p) || !p->PR || nct < 1 || nct > LF_LT_BATCH_MAX_CTS || nr < 0 || (nr == 0 && !with_self) || !c0 || !c1 || !out0 ||
+        !out1 || (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES))
+        return LF_ERR_ARG;
+    const int ell = p->ell, rows = p->ell + p->K, logN = p->logN, dev = p->device;
+    const int64_t N = (int64_t)1 << logN, twoN = 2 * N, poly = (int64_t)ell * N;
+    if (nr && (!p_host || !ksk)) return LF_ERR_ARG;
+    for (int i = 0; i < nr; ++i) {
+        if (!ksk[i] || p_host[i] <= 0 || p_host[i] >= twoN || !(p_host[i] & 1)) return LF_ERR_ARG;
+        if (key_format == LF_KEY_PLANES && ((((uintptr_t)ksk[i] | (uintptr_t)(part_stride * 8) | (uintptr_t)(comp_stride * 8)) & 15)))
+            return LF_ERR_ARG;
+    }
+    for (int t = 0; t < nct; ++t)
+        if (!c0[t] || !c1[t] || !out0[t] || !out1[t]) return LF_ERR_ARG;
+    const int64_t need = lf_rotate_sum_batch_ws_words(p, nct);
+    if (need && (!ws || ws_words < need || ((uintptr_t)ws & 15))) return LF_ERR_ARG;
+    int64_t *chat = need ? ws : p->x4;
+    const int nc = with_self ? 2 : 1;
+    for (int t0 = 0; t0 < nct;) {
+        const int g = lt_batch_group(p, nct - t0);
+        if (g == 1) {   // a straggler: the op itself, whose scratch is the first slot of this one's
+            if (int e = lf_rotate_sum(p, c0[t0], c1[t0], nr, p_host, ksk, part_stride, comp_stride, row_off, key_format, with_self, ws, ws_words,
+                                      out0[t0], out1[t0], stream))
+                return e;
+            t0 += 1;
+            continue;
+        }
+        // 1. c^_t = P NTT(c0_t) (and P NTT(c1_t) for the self term) on the ordinary rows, as lf_rotate_sum forms them:
+        //    chat [g][nc][ell][N], one canonical copy and one forward transform for the group
+        {
+            const int64_t *srcs[8];
+            int64_t *dsts[8];
+            for (int t = 0; t < g; ++t)
+                for (int c = 0; c < nc; ++c) srcs[t * nc + c] = c ? c1[t0 + t] : c0[t0 + t], dsts[t * nc + c] = chat + (t * nc + c) * poly;
+            if (int e = lf_galois_batch(srcs, dsts, g * nc, ell, logN, 1, p->_2q, dev, stream)) return e;
+            if (int e = lf_ntt(chat, g * nc, ell, logN, p->psi, p->psi_dp, p->q_host, p->Rs, 0, p->_2q, p->ql, p->qh, p->kl, p->kh, dev, stream))
+                return e;
+            for (int i = 0; i < g * nc; ++i)
+                if (int e = lf_mont_enter(chat + i * poly, p->PR, ell, N, p->ql, p->qh, p->kl, p->kh, dev, stream)) return e;
+        }
+        // 2. the digits of the g c1 (canonical, no permutation), ONE extension + forward NTT of all of them
+        if (nr) {
+            const int64_t *srcs[4];
+            int64_t *states[4];
+            for (int t = 0; t < g; ++t) srcs[t] = c1[t0 + t], states[t] = p->state + t * poly;
+            if (int e = lf_ks_digits_batch(srcs, states, g, p->dig_nparts, p->dig_desc, p->dig_tab, N, 1, p->_2q, p->ql, p->qh, p->kl, p->kh, dev,
+                                           stream))
+                return e;
+            if (int e = lf_ks_fwd_batch(p->state, poly, g, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, p->ext, p->psi, p->psi_dp, p->q_host,
+                                        p->ql, p->qh, p->kl, p->kh, (hipStream_t)stream))
+                return e;
+        }
+        // 3. the launches into the g pairs of sums, ONE inverse NTT of the 2 g polynomials (planes through the spent digits)
+        const int64_t spare = p->nparts >= 2 ? ((int64_t)g * p->nparts * rows) << logN : 0;
+        if (int e = lf_ks_tail_rsumb(g, nr, p_host, p->nparts, rows, ell, logN, ksk, part_stride, comp_stride, row_off, key_format, with_self,
+                                     chat, nc * poly, p->ext, p->sum, spare ? p->ext : nullptr, spare, p->ipsi, p->ipsi_dp, p->Ninv,
+                                     p->q_host, p->ql, p->qh, p->kl, p->kh, (hipStream_t)stream))
+            return e;
+        // 4. one mod-down of the 2 g polynomials, straight into the callers' [ell][N] pairs: no rescale, the level stays
+        const int64_t *ss[8];
+        int64_t *outs[8];
+        for (int t = 0; t < 2 * g; ++t) {
+            ss[t] = p->sum + t * (int64_t)rows * N;
+            outs[t] = (t & 1) ? out1[t0 + t / 2] : out0[t0 + t / 2];
+        }
+        if (int e = moddown_any(p, ss, outs, nullptr, 2 * g, 0, nullptr, stream)) return e;
+        t0 += g;
+    }
+    return 0;
 }
 
 /* ---- linear transform, baby-step / giant-step: y = sum_g rot(sum_b pt_{g,b} * rot(x, b), g) (include/ckks_hip.h) ---- */

@@ -593,6 +593,34 @@ class HipBackend:
                                 1 if with_self else 0, _p(ws), 0 if ws is None else ws.numel(), out.data_ptr(),
                                 out.data_ptr() + out.stride(0) * 8, st), "lf_rotate_sum")
 
+    # csrc/ckks_ks.hip: LF_RSB_KEYS, the keys one launch of ks_inner_rsumb_kernel loops over (tests/test_rotate_sum_batch_cpu.py
+    # holds this copy to the source)
+    rsum_batch_keys_per_launch = 8
+
+    @staticmethod
+    def rotate_sum_batch_ws_words(plan, nct):
+        return int(lib.lf_rotate_sum_batch_ws_words(ctypes.byref(plan), nct))
+
+    def rotate_sum_batch_native(self, plan, c0s, c1s, exponents, keys, first_part, row_off, with_self, outs, ws=None):
+        """rotate_sum_native for len(c0s) <= lt_batch_max_cts ciphertexts under the same keys as ONE native call
+        (lf_rotate_sum_batch): groups of 4, 2 or 1 ciphertexts (plan.max_nct permitting) share every launch, and the inner product
+        reads each key word once per group.  c0s / c1s: the components, one tensor each per ciphertext; outs: one [2, ell, N]
+        tensor per ciphertext; ws: >= rotate_sum_batch_ws_words(plan, len(c0s)) words (None when that is 0); the rest as
+        rotate_sum_native."""
+        dev, st = _ds(outs[0])
+        n = len(keys)
+        bases = (ctypes.c_void_p * max(n, 1))()
+        ps = cs = 0
+        for i, key in enumerate(keys):
+            bases[i], ps, cs = self._key_args(key, first_part)
+        fmt = {self._kfmt(k) for k in keys}
+        if len(fmt) > 1:
+            raise ValueError("rotate_sum_batch_native: the keys of one call must share one format")
+        exps = (ctypes.c_int64 * max(n, 1))(*exponents)
+        check(lib.lf_rotate_sum_batch(ctypes.byref(plan), len(c0s), _parr(c0s), _parr(c1s), n, exps, bases, ps, cs, row_off,
+                                      fmt.pop() if fmt else 0, 1 if with_self else 0, _p(ws), 0 if ws is None else ws.numel(),
+                                      _parr([o[0] for o in outs]), _parr([o[1] for o in outs]), st), "lf_rotate_sum_batch")
+
     @staticmethod
     def linear_transform_bsgs_ws_words(plan, nb):
         return int(lib.lf_linear_transform_bsgs_ws_words(ctypes.byref(plan), nb))

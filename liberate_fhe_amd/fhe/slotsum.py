@@ -11,7 +11,9 @@ half): per rotation only the gathered inner product with its key remains.  It is
 without the rescale: the level stays.  inner_sum chains such sums over the mixed-radix stages of n (encdec.inner_sum_plan).
 Like the engine's other options beyond the reference, the words are DEFINED as a composition of steps the engine already has
 (written out in rotate_sum's docstring), and that composition is what runs wherever the native call (lf_rotate_sum) does not
-apply.  DESIGN.md §4.2.
+apply.  rotate_sum_batch / inner_sum_batch are the same sums over a list of ciphertexts under ONE key set, with exactly the
+loop's words: groups of ciphertexts share every launch of one native call (lf_rotate_sum_batch), which reads each key word once
+per group.  DESIGN.md §4.2.
 """
 from __future__ import annotations
 
@@ -77,7 +79,8 @@ class SlotSumOps:
         nparts = len(tabs["order"])
         fused = logN >= self.backend.fused_ks_min_logN
         gather = getattr(self.backend, "ks_gather", None)
-        digits = self._ks_digits_exchanged(ct.data[1], level, galois=(1, True)) if keys else {}
+        c1 = [t if t.is_contiguous() else t.contiguous() for t in ct.data[1]]   # (the digit kernels take a raw pointer and a row pitch of N)
+        digits = self._ks_digits_exchanged(c1, level, galois=(1, True)) if keys else {}
         c0o, c1o = [], []
         for i, d in enumerate(loc):
             li = self.local_ids.index(d)
@@ -138,6 +141,110 @@ class SlotSumOps:
                                        self._vec("Rs", d, level, True), cs, PiP=tabs[("pip", d)], **mkw)
             c0o.append(out[0]); c1o.append(out[1])
         return self._new((c0o, c1o), types.origins["ct"], level=level, montgomery_state=ct.montgomery_state)
+
+    # group sizes of rotate_sum_batch's native path, largest first (a subset of backend.ks_batch_sizes that starts at its
+    # largest: lf_rotate_sum_batch itself takes 4, then 2), as lt_batch_sizes: a size that does not beat the loop is left out
+    # here and its ciphertexts take rotate_sum one by one — the words are the same (DESIGN.md §4.2 has the numbers)
+    rsum_batch_sizes = (4, 2)
+
+    def rotate_sum_batch(self, cts: list, keys: list, include_self: bool = True) -> list:
+        """rotate_sum of many ciphertexts under the SAME keys: returns exactly [rotate_sum(ct, keys, include_self) for ct in cts],
+        word for word and in order (the words are rotate_sum's own; a ciphertext may appear several times; an empty list gives
+        []).  keys: as rotate_sum takes them.  What rotate_sum refuses is refused here for the whole list before anything is
+        allocated or launched: a wrong origin, a wrong key type, no key and no self term, an NTT-domain or special-limb
+        ciphertext.  Ciphertexts of different levels are legal: they are bucketed by level and every output keeps its place.
+        Where rotate_sum's native call applies (every limb of the level on one device of this process, a backend with
+        lf_rotate_sum_batch, contiguous operands) groups of rsum_batch_sizes ciphertexts of one level go through ONE native
+        call of at most backend.lt_batch_max_cts ciphertexts: a group shares every launch, and its inner product — nearly all
+        of the op — reads each key word once per group instead of once per ciphertext, looping over the keys inside the
+        kernel (ks_inner_rsumb_kernel) with one accumulator pair per ciphertext.  Ciphertexts that do not qualify, the one left
+        over by the groups, and every ciphertext on a backend without the entry take rotate_sum one by one."""
+        cts = list(cts)
+        if not cts:
+            return []
+        for ct in cts:
+            if not is_struct(ct) or ct.origin != types.origins["ct"]:
+                raise errors.NotMatchType(origin=getattr(ct, "origin", type(ct).__name__), to=types.origins["ct"])
+        keys = list(keys)
+        N = self.ctx.N
+        exps = []
+        for k in keys:
+            origin = k.origin if is_struct(k) else type(k).__name__
+            if types.origins["rotk"] in origin:
+                exps.append(encdec.galois_exponent(N, int(origin.split(":")[-1])))
+            elif origin == types.origins["conjk"]:
+                exps.append(encdec.conjugation_exponent(N))
+            else:
+                raise errors.NotMatchType(origin=origin, to=types.origins["rotk"])
+        if not keys and not include_self:
+            raise ValueError("rotate_sum_batch: no key and no self term: nothing to sum")
+        for ct in cts:
+            if ct.ntt_state or ct.include_special:
+                raise NotImplementedError("rotate_sum_batch: coefficient-domain ciphertexts without special limbs only")
+        out = [None] * len(cts)
+        sizes = [k for k in self.rsum_batch_sizes if k in getattr(self.backend, "ks_batch_sizes", ())]
+        by_level = {}
+        for i, ct in enumerate(cts):
+            by_level.setdefault(ct.level, []).append(i)
+        for level, members in by_level.items():
+            d = self._native_level(level)
+            if d is None or not sizes or not hasattr(self.backend, "rotate_sum_batch_native"):
+                continue
+            ready = [i for i in members if cts[i].data[0][0].is_contiguous() and cts[i].data[1][0].is_contiguous()]
+            native, pos = [], 0
+            while True:
+                n = next((k for k in sizes if k <= len(ready) - pos), 0)
+                if not n:
+                    break
+                native += ready[pos:pos + n]
+                pos += n
+            if not native:
+                continue
+            plan, _, first_part, row_off = self._op_plan(level, d, nct=4)
+            i0 = self._loc(0, special=True).index(d)
+            kpacks = [self._key_pack(k)[i0] for k in keys]
+            cap = self.backend.lt_batch_max_cts - self.backend.lt_batch_max_cts % max(sizes)
+            for a in range(0, len(native), cap):
+                idx = native[a:a + cap]
+                words = self.backend.rotate_sum_batch_ws_words(plan, len(idx))
+                ws = self._ws("rsum_batch_ws", (words,), d) if words else None
+                outs = [torch.empty((2, plan.ell, N), dtype=torch.int64, device=self.ntt.devices[d]) for _ in idx]
+                self.backend.rotate_sum_batch_native(plan, [cts[i].data[0][0] for i in idx], [cts[i].data[1][0] for i in idx], exps,
+                                                     kpacks, first_part, row_off, include_self, outs, ws)
+                for i, o in zip(idx, outs):
+                    out[i] = self._new(([o[0]], [o[1]]), types.origins["ct"], level=level, montgomery_state=cts[i].montgomery_state)
+        for i, ct in enumerate(cts):
+            if out[i] is None:
+                out[i] = self.rotate_sum(ct, keys, include_self)
+        return out
+
+    def inner_sum_batch(self, cts: list, n: int, rotks, stride: int = 1, radix: int = encdec.INNER_SUM_RADIX) -> list:
+        """inner_sum of many ciphertexts under the SAME keys: returns exactly [inner_sum(ct, n, rotks, stride, radix) for ct in
+        cts], word for word and in order.  It validates like inner_sum, for the whole list before anything runs, and then chains
+        one rotate_sum_batch(.., include_self=True) per stage of encdec.inner_sum_plan, so every stage reads its keys once per
+        group of ciphertexts (inner_sum_steps lists the steps a key is needed for).  An empty list gives []."""
+        cts = list(cts)
+        if not cts:
+            return []
+        for ct in cts:
+            if not is_struct(ct) or ct.origin != types.origins["ct"]:
+                raise errors.NotMatchType(origin=getattr(ct, "origin", type(ct).__name__), to=types.origins["ct"])
+        plan = encdec.inner_sum_plan(n, stride, self.num_slots, radix)
+        by_step = {}
+        for k in (list(rotks.values()) if isinstance(rotks, dict) else list(rotks)):
+            if not is_struct(k) or types.origins["rotk"] not in k.origin:
+                raise errors.NotMatchType(origin=getattr(k, "origin", type(k).__name__), to=types.origins["rotk"])
+            by_step.setdefault(int(k.origin.split(":")[-1]) % self.num_slots, k)
+        for _, steps in plan:
+            for s in steps:
+                if s not in by_step:
+                    raise errors.NotMatchType(origin=f"no key for step {s}", to=types.origins["rotk"] + str(s))
+        for ct in cts:
+            if ct.ntt_state or ct.include_special:
+                raise NotImplementedError("inner_sum_batch: coefficient-domain ciphertexts without special limbs only")
+        for _, steps in plan:
+            cts = self.rotate_sum_batch(cts, [by_step[s] for s in steps], include_self=True)
+        return cts
 
     def inner_sum_steps(self, n: int, stride: int = 1, radix: int = encdec.INNER_SUM_RADIX) -> list:
         """The sorted distinct steps inner_sum(ct, n, .., stride, radix) needs a rotation key for."""

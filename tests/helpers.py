@@ -454,6 +454,91 @@ def edge_diagonals(engine, level, steps, pattern, seed=0, n1=None):
     return out
 
 
+# ---- operands that take the fp64-class inner sums to the bound their range arguments name (tests/test_worst_case_sums_*.py) ----
+def constant_ciphertext(engine, level, seed=0):
+    """A ciphertext of CONSTANT polynomials: coefficient 0 is a non-zero word on every row, every other coefficient is 0.  Its
+    transforms are one constant per row, and a Galois rotation leaves it unchanged, so extended_constants() serve every key.
+    Component 1 holds the small word 1 + (seed + prime id) % 4: with digits of one limb the plain extended digit IS that word
+    on every row, which keeps the fp64 quotient of (digit word x key word) / q away from the rounding seam at the products
+    +-(q - 1) / 2 that extreme_key() asks for.  Component 0 holds (q - 1) (P R)^-1: P c0 in Montgomery form, the word the
+    kernels gather and add, is then q - 1 mod q — the top of its range."""
+    import torch
+    q, N, p = engine.ctx.q, engine.ctx.N, engine.ntt.p
+    dest = p.destination_arrays[level]
+    K = engine.ntt.num_special_primes
+    P = 1
+    for i in p.destination_arrays_with_special[level][0][-K:]:
+        P *= int(q[i])
+    data = []
+    for comp in range(2):
+        rows = []
+        for d in _edge_ids(engine):
+            if d < len(dest):
+                w = np.zeros((len(dest[d]), N), dtype=np.int64)
+                for r, i in enumerate(dest[d]):
+                    m = int(q[i])
+                    w[r, 0] = (m - 1) * pow(P * R, -1, m) % m if comp == 0 else 1 + (seed + i) % 4
+                rows.append(torch.from_numpy(w).to(engine.ntt.devices[d]))
+        data.append(rows)
+    return _edge_ct(engine, data, level)
+
+
+def extended_constants(engine, ct):
+    """[parts][rows] Python integers: the extended digits of a constant_ciphertext in the NTT domain — pre_extend -> extend -> ntt
+    of component 1, as tests/test_inner_sum_cpu.composition forms them — which are one constant along the index per (part, row):
+    Montgomery-form words below 2q.  One device, a checker engine (the steps run on the CPU)."""
+    import torch
+    d, level = 0, ct.level
+    ell = engine._rows(d, level, False)
+    c1 = torch.empty_like(ct.data[1][0])
+    engine.backend.galois(ct.data[1][0].contiguous(), c1, ell, engine.ctx.logN, 1, engine._vec("_2q", d, level, False))
+    out = []
+    for part_id in range(len(engine.ntt.p.p[level][d])):
+        ext = engine.extend(engine.pre_extend([c1], d, level, part_id), d, level, part_id, d)
+        engine.ntt.ntt([ext], level, d, -2)
+        assert bool((ext == ext[:, :1]).all()), ("extended digits of a constant polynomial vary along the index", part_id)
+        out.append([int(v) for v in ext[:, 0]])
+    return out
+
+
+def extreme_key(engine, ext_constants, origin="key switch key", flip=False):
+    """A key-switch key (edge_key's layout, _remember_pack called the same way) under which EVERY product of the inner sums of
+    the ciphertext that ext_constants came from (extended_constants at level 0) sits at the end of the balanced range: the word
+    at (part p, component c, row r) is t R e[p, r]^-1 mod q_r, so that mont_mult(e, word) — and the fp64 kernels' plain product
+    (e R^-1) x word — has the residue t = +-(q_r - 1) / 2: + where the Thue-Morse parity of the coefficient index is 0 in
+    component 0, the opposite sign in component 1, all four swapped by `flip`.  Two values per (part, component, row),
+    broadcast along the index; odd rows hold the lazy representative word + q.  One device.  The rows and parts of a later level
+    are a sub-block of level 0's, and a rotation leaves a constant polynomial unchanged: the one pack serves every level and
+    every step (key._replace(origin=..) shares it, 138 MB at 32 digits, instead of copying it)."""
+    import torch
+    from liberate_fhe_amd.utils.synth import _data_struct
+    ds_type = _data_struct(engine)
+    q, N, p = engine.ctx.q, engine.ctx.N, engine.ntt.p
+    nparts = p.num_partitions + 1
+    assert len(_edge_ids(engine)) == 1 and len(ext_constants) == len(engine.parts_alloc[0][0])
+    dest = p.destination_arrays_with_special[0][0]
+    tm = torch.from_numpy(thue_morse(N)).bool()
+    vals = np.zeros((nparts, 2, len(dest), 2), dtype=np.int64)             # [.., 0]: parity 0, [.., 1]: parity 1
+    for part_id, gid in enumerate(engine.parts_alloc[0][0]):
+        for r, i in enumerate(dest):
+            m = int(q[i])
+            for comp in range(2):
+                for par in range(2):
+                    sign = -1 if (comp + par + int(flip)) % 2 else 1
+                    t = sign * ((m - 1) // 2)
+                    vals[gid, comp, r, par] = t * R * pow(int(ext_constants[part_id][r]), -1, m) % m + (m if r % 2 else 0)
+    v = torch.from_numpy(vals)
+    pack = torch.where(tm.view(1, 1, 1, N), v[..., 1:2], v[..., 0:1]).contiguous().to(engine.ntt.devices[0])
+    parts = [ds_type(data=([pack[gid, 0]], [pack[gid, 1]]), include_special=True, ntt_state=True, montgomery_state=True,
+                     origin=f"key switch key part index {gid}", level=0, hash=engine.hash, version=engine.version)
+             for gid in range(nparts)]
+    out = ds_type(data=parts, include_special=True, ntt_state=True, montgomery_state=True, origin=origin,
+                  level=0, hash=engine.hash, version=engine.version)
+    if hasattr(engine, "_remember_pack"):
+        engine._remember_pack(out, [pack], own=True)
+    return out
+
+
 def pre_rescale_rows(q_rows, q_drop, target_rows, row0):
     """The words a_i = ((t_i - rho) q_drop + r) mod q_i whose rescale (a_i - r) q_drop^-1 + rho is t_i, with r = row0 the
     dropped limb's words and rho = [r > q_drop // 2]; Python integers."""
@@ -524,6 +609,8 @@ def edge_param_sets():
     sets["sb45_K4"] = dict(base, scale_bits=45, num_scales=6, num_special_primes=4)
     sets["sb45_K8"] = dict(base, scale_bits=45, num_scales=9, num_special_primes=8)     # 9 scales: a digit of 8 wide limbs
     sets["sb20"] = dict(base, scale_bits=20, num_scales=8, num_special_primes=2)
+    # the deep set: 32 digits of one limb at level 0, 33 rows of which 31 are fp64-class (tests/test_worst_case_sums_*.py)
+    sets["sb40_K1_d32"] = dict(base, scale_bits=40, num_scales=31, num_special_primes=1)
     return sets
 
 

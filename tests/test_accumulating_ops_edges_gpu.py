@@ -88,15 +88,17 @@ def engines(cfg):
     return _ENGINES[cfg]
 
 
-def keys_of(cfg, eng, pattern):
-    """step -> rotation key of edge words for every step of key_steps; the keys of ONE configuration are kept (both engines',
-    both patterns'), those of the previous one are dropped."""
+def keys_of(cfg, eng, pattern, steps=None):
+    """step -> rotation key of edge words for every step of key_steps (or of `steps`: the files that share this cache, e.g.
+    tests/test_matrix_ops_edges_gpu.py; a step has the same words under either); the keys of ONE configuration are kept (both
+    engines', both patterns'), those of the previous one are dropped."""
     if _KEYS.get("cfg") != cfg:
         _KEYS.clear()
         _KEYS["cfg"] = cfg
-    key = (id(eng), pattern)
+    key = (id(eng), pattern) if steps is None else (id(eng), pattern, tuple(sorted(steps)))
     if key not in _KEYS:
-        _KEYS[key] = {s: edge_key(eng, pattern, 100 + s, origin=f"rotation key:{s}") for s in key_steps(eng.num_slots)}
+        wanted = key_steps(eng.num_slots) if steps is None else key[2]
+        _KEYS[key] = {s: edge_key(eng, pattern, 100 + s, origin=f"rotation key:{s}") for s in wanted}
     return _KEYS[key]
 
 

@@ -108,7 +108,13 @@ def test_pre_rescale_round_trip_and_the_negative_word(name):
             assert (out < qv).all() and (out >= -slack).all()
             assert not (neg & ~(src - row0[None, :] < 0)).any() and (out[neg] == (target - qv)[neg]).all()
             if SETS[name]["scale_bits"] == 40:       # the 40-bit sets: only -1, only at target q_i - 1 under a firing rounder
-                assert (out[neg] == -1).all() and not (neg & ~((target == qv - 1) & rho)).any()
+                # (.. or, without the rounder, on a limb so far below the dropped prime that x = (q_i - q_drop) scale / R, the
+                # a_i - r of the target q_i - 1, is itself below -1: only the deep set's 31 scale primes spread that far)
+                scale = [int(s) for s in eng.rescale_scales[level][0]]
+                assert len(scale) == T.ell
+                below = np.array([(q - q_drop) * s < -(1 << 62) for q, s in zip(T.q_ord, scale)])[:, None]
+                assert not below.any() or name == "sb40_K1_d32"
+                assert (out[neg] == -1).all() and not (neg & ~((target == qv - 1) & (rho | below))).any()
             assert (out[~neg] == target[~neg]).all()
             seen_negative |= bool(neg.any())
     assert seen_negative == (SETS[name]["scale_bits"] >= 40)

@@ -96,6 +96,11 @@ int lf_limits(int which);
  *                             the tiled inverse pass to the column pass as planes (through `tmp`, two digits or more); bit 1
  *                             (default 1) lf_stack_planes() answers 1: the op entries keep cc_mult's operand stack as planes. */
 #define LF_TUNE_MORE_PLANES 5
+/*   LF_TUNE_PC_MATMUL_TILE    how lf_pc_matmul_batch covers 4 tokens of a chunk: 0 (default) two launches of pc_matmulb_kernel<GO, 2>
+ *                             (2 tokens each, the plaintext words read twice); 1: ONE launch of <GO, 4>; 2: as 1, with 4 outputs
+ *                             as two launches of <2, 4> (the transformed words read twice).  1 and 2 measured slower on MI355X
+ *                             (DESIGN.md section 4.2); kept for tools/pc_matmul_batch.py --ab. */
+#define LF_TUNE_PC_MATMUL_TILE 6
 int lf_tune(int which, int value);
 
 /* Measurement entry (not one of the reference's ops; the engine never calls it): ONE wave, launched on `stream`, takes
@@ -946,6 +951,34 @@ int lf_pc_matmul(int k_in, int k_out, const int64_t *const *in, const int64_t *c
                  const int64_t *ipsi_br, const double *ipsi_dp, const int64_t *q_host, const int64_t *Rs, const int64_t *Ninv,
                  const int64_t *mont_one, const int64_t *zero_row, const int64_t *rescale_scales, int64_t round_at, int64_t *ws,
                  int64_t ws_words, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, int device, void *stream);
+
+/* lf_pc_matmul over nt token vectors that share the matrix (a dense layer over the tokens of a sequence or the samples of a
+ * batch): for t < nt, o < k_out, out_{t,o} decrypts to sum_i pt_{o,i} * ct_{t,i} (+ bias_o).  nt: 1 .. LF_PC_MATMUL_BATCH_MAX_TOKENS;
+ * in: HOST array of nt 2 k_in device pointers, [token][input][component]; out0 / out1: HOST arrays of nt k_out pointers,
+ * [token][output]; pt, bias and the tables: lf_pc_matmul's, shared by all tokens.  The same polynomial may appear any number of
+ * times among `in` (in one token or several) and among `pt`.
+ * Output (t, o) has exactly the words of lf_pc_matmul on token t: only the residues of that entry's S reach its result, so the
+ * order and grouping of the additions — and which other tokens share a launch — are free.
+ * Enqueued, for the inputs some output uses, in chunks of at most LF_PC_MATMUL_CI: per token the chunk's forward transforms as
+ * lf_pc_matmul runs them, into x = [nt][n][2][rows][N] (a token's slots 2 min(k_in, LF_PC_MATMUL_CI) polynomials apart): every
+ * (token, input) is transformed once per call; per chunk and per group of 4, 2 or 1 outputs ONE launch of pc_matmulb_kernel<GO, 2>
+ * per tile of 2 tokens (a thread reads the two transformed pairs of each of its tokens once and each plaintext pair ONCE for both)
+ * and lf_pc_matmul's own pc_matmul_kernel<GO> for an odd token left (3 tokens: 2 + 1; 4: 2 + 2 — one launch of <GO, 4> measured
+ * slower, LF_TUNE_PC_MATMUL_TILE), into S = [nt][k_out][2][rows][N] (the first chunk writes); lf_intt (tail
+ * 2, relaxed, plain) of the 2 k_out nt polynomials of S in ONE call up to 128 polynomials (the largest batch lf_pc_matmul hands
+ * it), per token beyond; lf_rescale_batch per 4 outputs and pc_bias_kernel per output with a bias, per token.  nt = 1 enqueues
+ * exactly what lf_pc_matmul does.
+ * ws: lf_pc_matmul_batch_ws_words(nt, k_in, k_out, rows, logN) = nt lf_pc_matmul_ws_words(k_in, k_out, rows, logN) words (0 for
+ * shapes the entry refuses), 16-byte aligned.  LF_ERR_ARG before any device call for nt < 1 or > the maximum, everything
+ * lf_pc_matmul refuses, a NULL among the nt 2 k_in inputs or the nt k_out outputs of either array.  LF_ERR_STATE as lf_pc_matmul. */
+#define LF_PC_MATMUL_BATCH_MAX_TOKENS 4
+int64_t lf_pc_matmul_batch_ws_words(int nt, int k_in, int k_out, int rows, int logN);
+int lf_pc_matmul_batch(int nt, int k_in, int k_out, const int64_t *const *in, const int64_t *const *pt, const int64_t *const *bias,
+                       int64_t *const *out0, int64_t *const *out1, int rows, int logN, const int64_t *psi_br, const double *psi_dp,
+                       const int64_t *ipsi_br, const double *ipsi_dp, const int64_t *q_host, const int64_t *Rs, const int64_t *Ninv,
+                       const int64_t *mont_one, const int64_t *zero_row, const int64_t *rescale_scales, int64_t round_at, int64_t *ws,
+                       int64_t ws_words, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, int device,
+                       void *stream);
 
 /* The halves of an op around the digit exchange of a limb-sharded engine (one process per GPU; the reference gathers every
  * digit on every GPU through the host before it extends any, ckks_engine.py:778-829).  The plan describes THIS rank's rows

@@ -119,6 +119,8 @@ _SIGNATURES["lf_pc_dot_ws_words"] = [_I, _I, _I]
 _SIGNATURES["lf_pc_dot"] = [_I, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _I, _P]
 _SIGNATURES["lf_pc_matmul_ws_words"] = [_I, _I, _I, _I]
 _SIGNATURES["lf_pc_matmul"] = [_I, _I, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _I, _P]
+_SIGNATURES["lf_pc_matmul_batch_ws_words"] = [_I, _I, _I, _I, _I]
+_SIGNATURES["lf_pc_matmul_batch"] = [_I] + _SIGNATURES["lf_pc_matmul"]
 _SIGNATURES["lf_linear_transform_ws_words"] = [_PL]
 _SIGNATURES["lf_linear_transform"] = [_PL, _P, _P, _I, _P, _P, _L, _L, _L, _I, _P, _L, _P, _P, _L, _P, _L, _P, _P, _P]
 _SIGNATURES["lf_linear_transform_batch_ws_words"] = [_PL, _I]
@@ -182,6 +184,7 @@ LF_WSUM_MAX_TERMS = 16      # include/ckks_hip.h: terms per lf_weighted_sums cal
 LF_WSUM_MAX_OUTPUTS = 64    # .. and outputs
 LF_PC_MATMUL_CI = 16           # include/ckks_hip.h: inputs per chunk of lf_pc_matmul
 LF_PC_MATMUL_MAX_OUTPUTS = 64  # .. and outputs per call
+LF_PC_MATMUL_BATCH_MAX_TOKENS = 4   # include/ckks_hip.h: token vectors per lf_pc_matmul_batch call
 LF_LT_MATMUL_MAX_INPUTS = 64   # include/ckks_hip.h: inputs per lf_lt_matmul call
 LF_LT_MATMUL_MAX_OUTPUTS = 64  # .. and outputs per call
 LF_LT_MATMUL_BSGS_MAX_GIANTS = 64   # include/ckks_hip.h: giant steps per lf_lt_matmul_bsgs call

@@ -830,6 +830,118 @@ __global__ void __launch_bounds__(256) pc_matmul_kernel(const i64 *__restrict__ 
         for (int c = 0; c < 2; ++c) *reinterpret_cast<longlong2 *>(s + (2 * g + c) * pstride) = o[g][c];
 }
 
+// ---- pc_matmul_batch: pc_matmul_kernel over GT token vectors that share the plaintexts (lf_pc_matmul_batch) -----------------
+// x: token t's chunk [n][2][rows][N] at x + t * xtok; S: token t's group [GO][2][rows][N] at S + t * stok; pa: the SAME table for
+// every token.  grid and thread as pc_matmul_kernel.  Per input of the run-time loop a thread loads the two transformed pairs of
+// each of its GT tokens once and, per non-NULL output of its group, the plaintext pair ONCE (nontemporal) — on fp64-class rows it
+// is converted to the plain word once, not once per token — and forms the GO GT 2 2 products from registers: the plaintext
+// stream, the larger one of pc_matmul_kernel, is divided by GT.  Arithmetic and bounds are pc_matmul_kernel's per (token, output)
+// accumulator (fp64 rows: at most LF_PC_MATMUL_CI balanced products plus the word read back, <= 9 q; integer rows: a conditional
+// subtraction after every addition), so output (t, g) has the words pc_matmul_kernel<GO> gives on token t.
+template <int GO, int GT>
+__global__ void __launch_bounds__(256) pc_matmulb_kernel(const i64 *__restrict__ x, i64 xtok, PcMatTerms pa, i64 *__restrict__ S, i64 stok,
+                                                         int n, int rows, i64 N, int xpl, int first, const i64 *__restrict__ ql,
+                                                         const i64 *__restrict__ qh, const i64 *__restrict__ kl,
+                                                         const i64 *__restrict__ kh) {
+    const int r = blockIdx.y;
+    const i64 j0 = (i64)blockIdx.x * 512 + threadIdx.x * 2;
+    if (j0 >= N) return;
+    const RowMod m = load_mod(ql, qh, kl, kh, r);
+    const i64 pstride = (i64)rows * N, o0 = (i64)r * N + j0;
+    i64 *s = S + o0;
+    if (m.q < SMALL_PRIME_LIMIT) {
+        const RowDp d = make_dp(m);
+        double a[GT][GO][2][2];
+#pragma unroll
+        for (int t = 0; t < GT; ++t)
+#pragma unroll
+            for (int g = 0; g < GO; ++g) a[t][g][0][0] = a[t][g][0][1] = a[t][g][1][0] = a[t][g][1][1] = 0.0;
+        for (int i = 0; i < n; ++i) {
+            double c0[GT][2], c1[GT][2];
+#pragma unroll
+            for (int t = 0; t < GT; ++t) {
+                const i64 *xs = x + t * xtok + (i64)i * 2 * pstride + (i64)r * N;
+                ld_pair_dp(xs, j0, N, xpl, c0[t][0], c0[t][1]);
+                ld_pair_dp(xs + pstride, j0, N, xpl, c1[t][0], c1[t][1]);
+            }
+#pragma unroll
+            for (int g = 0; g < GO; ++g) {
+                const i64 *p = pa.pt[i][g];
+                if (p == nullptr) continue;   // (uniform: a kernel argument)
+                const longlong2 w = ld_nt(p + o0);
+                const double wp[2] = {dp_from_word(mm62u((u64)w.x, 1ull, m.q, m.k)), dp_from_word(mm62u((u64)w.y, 1ull, m.q, m.k))};
+#pragma unroll
+                for (int t = 0; t < GT; ++t)
+#pragma unroll
+                    for (int e = 0; e < 2; ++e) {
+                        a[t][g][0][e] += dp_mulmod_bal(c0[t][e], wp[e], d);
+                        a[t][g][1][e] += dp_mulmod_bal(c1[t][e], wp[e], d);
+                    }
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < GT; ++t)
+#pragma unroll
+            for (int g = 0; g < GO; ++g)
+#pragma unroll
+                for (int c = 0; c < 2; ++c) {
+                    i64 *at = s + t * stok + (2 * g + c) * pstride;
+                    if (!first) {
+                        const longlong2 v = *reinterpret_cast<const longlong2 *>(at);
+                        a[t][g][c][0] += dp_from_word(v.x), a[t][g][c][1] += dp_from_word(v.y);
+                    }
+                    longlong2 o;
+                    o.x = dp_to_word(dp_reduce(a[t][g][c][0], d.q, d.qinv));
+                    o.y = dp_to_word(dp_reduce(a[t][g][c][1], d.q, d.qinv));
+                    *reinterpret_cast<longlong2 *>(at) = o;
+                }
+    } else {
+        i64 a[GT][GO][2][2];
+#pragma unroll
+        for (int t = 0; t < GT; ++t)
+#pragma unroll
+            for (int g = 0; g < GO; ++g) a[t][g][0][0] = a[t][g][0][1] = a[t][g][1][0] = a[t][g][1][1] = 0;
+        for (int i = 0; i < n; ++i) {
+            u64 c0[GT][2], c1[GT][2];
+#pragma unroll
+            for (int t = 0; t < GT; ++t) {
+                const i64 *xs = x + t * xtok + (i64)i * 2 * pstride + o0;
+                const longlong2 C0 = *reinterpret_cast<const longlong2 *>(xs), C1 = *reinterpret_cast<const longlong2 *>(xs + pstride);
+                c0[t][0] = (u64)C0.x, c0[t][1] = (u64)C0.y, c1[t][0] = (u64)C1.x, c1[t][1] = (u64)C1.y;
+            }
+#pragma unroll
+            for (int g = 0; g < GO; ++g) {
+                const i64 *p = pa.pt[i][g];
+                if (p == nullptr) continue;
+                const longlong2 w = ld_nt(p + o0);
+                const u64 wm[2] = {(u64)w.x, (u64)w.y};
+#pragma unroll
+                for (int t = 0; t < GT; ++t)
+#pragma unroll
+                    for (int e = 0; e < 2; ++e) {
+                        a[t][g][0][e] = csub(a[t][g][0][e] + mm62u(c0[t][e], wm[e], m.q, m.k), m.q2);
+                        a[t][g][1][e] = csub(a[t][g][1][e] + mm62u(c1[t][e], wm[e], m.q, m.k), m.q2);
+                    }
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < GT; ++t)
+#pragma unroll
+            for (int g = 0; g < GO; ++g)
+#pragma unroll
+                for (int c = 0; c < 2; ++c) {
+                    i64 *at = s + t * stok + (2 * g + c) * pstride;
+                    if (!first) {
+                        const longlong2 v = *reinterpret_cast<const longlong2 *>(at);
+                        a[t][g][c][0] = csub(a[t][g][c][0] + v.x, m.q2), a[t][g][c][1] = csub(a[t][g][c][1] + v.y, m.q2);
+                    }
+                    longlong2 o;
+                    o.x = a[t][g][c][0], o.y = a[t][g][c][1];
+                    *reinterpret_cast<longlong2 *>(at) = o;
+                }
+    }
+}
+
 // ---- cc_matmul: the summed triplets of an R x C tile of C = A B, every operand of the tile read once per inner index ----------
 // x = [nu][2][ell][N]: the resident store of the DISTINCT operands, c0, c1 of each as lf_rescale_ntt(RELAXED | PLAIN) leaves them
 // (xpl: fp64-class rows as planes).  ix.a[t][i] / ix.b[t][j]: the operand that is A[i0 + i][t] resp. B[t][j0 + j], or -1 for a zero
@@ -2697,6 +2809,51 @@ int lf_pc_matmul_products(int go, int n, const int64_t *x, const int64_t *const 
     return (int)hipGetLastError();
 }
 
+// The launch of lf_pc_matmul_batch that is its own (ckks_ops.hip checks the arguments).
+// lf_pc_matmul_batch_tile: the tile of tokens (2 or 1; 4 under LF_TUNE_PC_MATMUL_TILE) one launch takes for `left` tokens still to
+// go; 1 is lf_pc_matmul_products itself.  Every (go, gt) with gt > 1 this can return is instantiated below
+// (tests/test_pc_matmul_batch_cpu.py holds each of them to scratch 0 and no spill).  Measured on MI355X: a tile
+// of 4 tokens — 246 VGPRs at 4 outputs, 2 waves per SIMD — is slower than two tiles of 2, so the default never takes it.
+static int g_pc_matmul_tile = 0;   // LF_TUNE_PC_MATMUL_TILE
+int lf_pc_matmul_batch_tile(int go, int left) {
+    (void)go;
+    if (left >= 4 && g_pc_matmul_tile != 0) return 4;
+    return left >= 2 ? 2 : 1;
+}
+// .. and the outputs (4, 2 or 1) a launch takes for `left` outputs still to go over nt tokens
+int lf_pc_matmul_batch_outputs(int left, int nt) {
+    if (left >= 4 && nt >= 4 && g_pc_matmul_tile == 2) return 2;
+    return left >= 4 ? 4 : left >= 2 ? 2 : 1;
+}
+
+// lf_pc_matmulb_products: lf_pc_matmul_products over gt (2 or 4) tokens in one launch: token t's transformed pairs at x + t * xtok,
+// its group's pairs of S at S + t * stok (strides in words, multiples of 2: 16-byte accesses); pt shared by the tokens.
+int lf_pc_matmulb_products(int go, int gt, int n, const int64_t *x, int64_t xtok, const int64_t *const *pt, int pt_stride, int64_t *S,
+                           int64_t stok, int rows, int logN, int xpl, int first, const int64_t *ql, const int64_t *qh, const int64_t *kl,
+                           const int64_t *kh, hipStream_t st) {
+    if ((go != 1 && go != 2 && go != 4) || (gt != 2 && gt != 4) || n < 1 || n > LF_PC_MATMUL_CI || !x || !pt || pt_stride < go || !S ||
+        rows < 1 || rows > 65535 || logN < 9 || xtok < ((int64_t)2 * n * rows << logN) || stok < ((int64_t)2 * go * rows << logN) ||
+        (xtok & 1) || (stok & 1))
+        return LF_ERR_ARG;
+    const i64 N = (i64)1 << logN;
+    for (int t = 0; t < gt; ++t)
+        if (int e = lf_fmt_expect(x + t * xtok, ((size_t)2 * n * rows << logN) * 8, xpl ? LF_FMT_PLANES : LF_FMT_RAW)) return e;
+    PcMatTerms pa{};
+    for (int i = 0; i < n; ++i)
+        for (int g = 0; g < go; ++g) pa.pt[i][g] = (const i64 *)pt[(size_t)i * pt_stride + g];
+    const dim3 grid((unsigned)(N / 512), (unsigned)rows);
+#define LF_PCMMB_CASE(GG, TT)                                                                                                     \
+    case GG * 8 + TT:                                                                                                             \
+        hipLaunchKernelGGL((pc_matmulb_kernel<GG, TT>), grid, dim3(256), 0, st, (const i64 *)x, (i64)xtok, pa, (i64 *)S, (i64)stok, n, \
+                           rows, N, xpl, first, (const i64 *)ql, (const i64 *)qh, (const i64 *)kl, (const i64 *)kh);              \
+        break;
+    switch (go * 8 + gt) {
+        LF_PCMMB_CASE(1, 2) LF_PCMMB_CASE(2, 2) LF_PCMMB_CASE(4, 2) LF_PCMMB_CASE(1, 4) LF_PCMMB_CASE(2, 4) LF_PCMMB_CASE(4, 4)
+    }
+#undef LF_PCMMB_CASE
+    return (int)hipGetLastError();
+}
+
 // The launch of lf_cc_matmul that is its own (ckks_ops.hip checks the arguments).
 // lf_matmul_tensor: the summed triplets of an R x C tile (R C = 1, 2 or 4) over the inner dimension k <= LF_CC_MATMUL_MAX_INNER from the
 // store x = [nu][2][ell][N] of transformed operands (xpl: fp64-class rows as planes — refused where the library's note of that range
@@ -3305,12 +3462,13 @@ extern "C" {
 int lf_tune(int which, int value) {
     int *knob = which == LF_TUNE_KS_EXT_COLS_MAX ? &g_ks_ext_cols_max : which == LF_TUNE_INTT_DIGITS ? &lf_g_intt_digits
                 : which == LF_TUNE_DIGIT_PLANES ? &g_digit_planes : which == LF_TUNE_WS_EXTRA_STAGE ? &lf_g_ws_extra_stage
-                : which == LF_TUNE_MORE_PLANES ? &g_more_planes : nullptr;
+                : which == LF_TUNE_MORE_PLANES ? &g_more_planes : which == LF_TUNE_PC_MATMUL_TILE ? &g_pc_matmul_tile : nullptr;
     if (!knob) return -1;
     const int old = *knob;
     if (value < 0) return old;
     if (which == LF_TUNE_KS_EXT_COLS_MAX && value > 5) return old;
     if (which == LF_TUNE_MORE_PLANES && value > 3) return old;
+    if (which == LF_TUNE_PC_MATMUL_TILE && value > 2) return old;
     if ((which == LF_TUNE_INTT_DIGITS || which == LF_TUNE_DIGIT_PLANES || which == LF_TUNE_WS_EXTRA_STAGE) && value > 1) return old;
     if (*knob != value && (which == LF_TUNE_DIGIT_PLANES || which == LF_TUNE_WS_EXTRA_STAGE || which == LF_TUNE_MORE_PLANES))
         lf_fmt_epoch_bump(which == LF_TUNE_WS_EXTRA_STAGE ? LF_FMT_WS_SPLIT0 : LF_FMT_RAW);   // scratch of that family so far: another setting

@@ -104,6 +104,13 @@ int lf_pc_bias(int64_t *c0, const int64_t *pt, const int64_t *Rs, int rows, int 
 int lf_pc_matmul_products(int go, int n, const int64_t *x, const int64_t *const *pt, int pt_stride, int64_t *S, int rows, int logN,
                           int xpl, int first, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st);
 
+// ckks_ks.hip: the launch of lf_pc_matmul_batch that is its own, and the tile of tokens it takes
+int lf_pc_matmul_batch_tile(int go, int left);
+int lf_pc_matmul_batch_outputs(int left, int nt);
+int lf_pc_matmulb_products(int go, int gt, int n, const int64_t *x, int64_t xtok, const int64_t *const *pt, int pt_stride, int64_t *S,
+                           int64_t stok, int rows, int logN, int xpl, int first, const int64_t *ql, const int64_t *qh, const int64_t *kl,
+                           const int64_t *kh, hipStream_t st);
+
 // ckks_ks.hip: the launch of lf_cc_matmul that is its own
 int lf_matmul_tensor(int R, int C, int k, int nu, const int64_t *x, const int *ta, const int *tb, int64_t *T, int64_t *t2, int ell,
                      int logN, int xpl, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st);
@@ -520,17 +527,25 @@ int64_t lf_pc_matmul_ws_words(int k_in, int k_out, int rows, int logN) {
     return ((2 * ci + 2 * (int64_t)k_out) * rows) << logN;   // the chunk's transformed pairs + the k_out pairs of S
 }
 
-int lf_pc_matmul(int k_in, int k_out, const int64_t *const *in, const int64_t *const *pt, const int64_t *const *bias,
-                 int64_t *const *out0, int64_t *const *out1, int rows, int logN, const int64_t *psi_br, const double *psi_dp,
-                 const int64_t *ipsi_br, const double *ipsi_dp, const int64_t *q_host, const int64_t *Rs, const int64_t *Ninv,
-                 const int64_t *mont_one, const int64_t *zero_row, const int64_t *rescale_scales, int64_t round_at, int64_t *ws,
-                 int64_t ws_words, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, int device, void *stream) {
-    const int64_t need = lf_pc_matmul_ws_words(k_in, k_out, rows, logN);
+int64_t lf_pc_matmul_batch_ws_words(int nt, int k_in, int k_out, int rows, int logN) {
+    if (nt < 1 || nt > LF_PC_MATMUL_BATCH_MAX_TOKENS) return 0;
+    return nt * lf_pc_matmul_ws_words(k_in, k_out, rows, logN);
+}
+
+// lf_pc_matmul (nt = 1) and lf_pc_matmul_batch: `in` [token][input][component], out0 / out1 [token][output]; `need`: the words
+// of the workspace the entry asks for (0: a refused shape).  x = [nt][ci][2][rows][N] with ci = min(k_in, LF_PC_MATMUL_CI) slots
+// per token, S = [nt][k_out][2][rows][N] behind it.
+static int pc_matmul_tokens(int nt, int64_t need, int k_in, int k_out, const int64_t *const *in, const int64_t *const *pt,
+                            const int64_t *const *bias, int64_t *const *out0, int64_t *const *out1, int rows, int logN,
+                            const int64_t *psi_br, const double *psi_dp, const int64_t *ipsi_br, const double *ipsi_dp,
+                            const int64_t *q_host, const int64_t *Rs, const int64_t *Ninv, const int64_t *mont_one,
+                            const int64_t *zero_row, const int64_t *rescale_scales, int64_t round_at, int64_t *ws, int64_t ws_words,
+                            const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, int device, void *stream) {
     if (!need || !in || !pt || !out0 || !out1 || !psi_br || !psi_dp || !ipsi_br || !ipsi_dp || !q_host || !Rs || !Ninv || !mont_one ||
         !zero_row || !rescale_scales || !ql || !qh || !kl || !kh)
         return LF_ERR_ARG;
     if (!ws || ws_words < need || ((uintptr_t)ws & 15)) return LF_ERR_ARG;
-    for (int64_t i = 0; i < (int64_t)2 * k_in; ++i)
+    for (int64_t i = 0; i < (int64_t)nt * 2 * k_in; ++i)
         if (!in[i]) return LF_ERR_ARG;
     // the inputs some output uses, in their order (a column of NULLs is not transformed); every output needs a term
     std::vector<int> used;
@@ -541,7 +556,8 @@ int lf_pc_matmul(int k_in, int k_out, const int64_t *const *in, const int64_t *c
                 break;
             }
     for (int o = 0; o < k_out; ++o) {
-        if (!out0[o] || !out1[o]) return LF_ERR_ARG;
+        for (int t = 0; t < nt; ++t)
+            if (!out0[(int64_t)t * k_out + o] || !out1[(int64_t)t * k_out + o]) return LF_ERR_ARG;
         bool any = false;
         for (int i = 0; i < k_in && !any; ++i) any = pt[(int64_t)o * k_in + i] != nullptr;
         if (!any) return LF_ERR_ARG;
@@ -550,58 +566,101 @@ int lf_pc_matmul(int k_in, int k_out, const int64_t *const *in, const int64_t *c
     const int xpl = lf_stack_planes(logN, rows, q_host);
     const int relaxed_plain = LF_NTT_RELAXED | LF_NTT_PLAIN | (xpl ? LF_NTT_PLANES : 0);
     if (int e = lf_set_device(device)) return e;
-    int64_t *x = ws, *S = ws + 2 * (int64_t)(k_in < LF_PC_MATMUL_CI ? k_in : LF_PC_MATMUL_CI) * poly;
+    const int64_t xtok = 2 * (int64_t)(k_in < LF_PC_MATMUL_CI ? k_in : LF_PC_MATMUL_CI) * poly, stok = 2 * (int64_t)k_out * poly;
+    int64_t *x = ws, *S = ws + nt * xtok;
     const int64_t *zeros[8];
     for (int i = 0; i < 8; ++i) zeros[i] = zero_row;
     const int na = (int)used.size();
     for (int a0 = 0; a0 < na; a0 += LF_PC_MATMUL_CI) {
         const int n = na - a0 < LF_PC_MATMUL_CI ? na - a0 : LF_PC_MATMUL_CI;
         // 1. the chunk's forward transforms into consecutive slots, as lf_pc_dot runs them: 4, 2 or 1 ciphertexts per call
-        for (int t0 = 0; t0 < n;) {
-            const int left = n - t0, g = left >= 4 ? 4 : left >= 2 ? 2 : 1;
-            const int64_t *ins[8];
-            for (int t = 0; t < g; ++t) ins[2 * t] = in[2 * used[a0 + t0 + t]], ins[2 * t + 1] = in[2 * used[a0 + t0 + t] + 1];
-            if (int e = lf_rescale_ntt(ins, zeros, 2 * g, x + (int64_t)t0 * 2 * poly, rows, logN, mont_one, INT64_MAX, psi_br, psi_dp, q_host,
-                                       Rs, relaxed_plain, nullptr, ql, qh, kl, kh, device, stream))
-                return e;
-            t0 += g;
+        for (int tk = 0; tk < nt; ++tk) {
+            const int64_t *const *tin = in + (int64_t)tk * 2 * k_in;
+            for (int t0 = 0; t0 < n;) {
+                const int left = n - t0, g = left >= 4 ? 4 : left >= 2 ? 2 : 1;
+                const int64_t *ins[8];
+                for (int t = 0; t < g; ++t) ins[2 * t] = tin[2 * used[a0 + t0 + t]], ins[2 * t + 1] = tin[2 * used[a0 + t0 + t] + 1];
+                if (int e = lf_rescale_ntt(ins, zeros, 2 * g, x + tk * xtok + (int64_t)t0 * 2 * poly, rows, logN, mont_one, INT64_MAX, psi_br,
+                                           psi_dp, q_host, Rs, relaxed_plain, nullptr, ql, qh, kl, kh, device, stream))
+                    return e;
+                t0 += g;
+            }
         }
-        // 2. per group of 4, 2 or 1 outputs ONE launch over the chunk: the group's pairs of S
+        // 2. per group of 4, 2 or 1 outputs ONE launch over the chunk per tile of 2 tokens (an odd token left: lf_pc_matmul's own
+        //    launch): the group's pairs of S
         for (int o0 = 0; o0 < k_out;) {
-            const int left = k_out - o0, go = left >= 4 ? 4 : left >= 2 ? 2 : 1;
+            const int go = lf_pc_matmul_batch_outputs(k_out - o0, nt);   // (one token: 4, 2 or 1 of the outputs left, as ever)
             const int64_t *tab[LF_PC_MATMUL_CI * 4];
             for (int i = 0; i < n; ++i)
                 for (int g = 0; g < go; ++g) tab[4 * i + g] = pt[(int64_t)(o0 + g) * k_in + used[a0 + i]];
-            if (int e = lf_pc_matmul_products(go, n, x, tab, 4, S + (int64_t)o0 * 2 * poly, rows, logN, xpl, a0 == 0, ql, qh, kl, kh,
-                                              (hipStream_t)stream))
-                return e;
+            for (int tk = 0; tk < nt;) {
+                const int gt = lf_pc_matmul_batch_tile(go, nt - tk);
+                int64_t *Sg = S + tk * stok + (int64_t)o0 * 2 * poly;
+                const int e = gt == 1 ? lf_pc_matmul_products(go, n, x + tk * xtok, tab, 4, Sg, rows, logN, xpl, a0 == 0, ql, qh, kl, kh,
+                                                              (hipStream_t)stream)
+                                      : lf_pc_matmulb_products(go, gt, n, x + tk * xtok, xtok, tab, 4, Sg, stok, rows, logN, xpl, a0 == 0,
+                                                               ql, qh, kl, kh, (hipStream_t)stream);
+                if (e) return e;
+                tk += gt;
+            }
             o0 += go;
         }
     }
-    // 3. all 2 k_out polynomials of S -> canonical coefficients in one inverse transform
-    if (int e = lf_intt(S, 2 * k_out, rows, logN, ipsi_br, ipsi_dp, q_host, Ninv, 2, LF_NTT_RELAXED | LF_NTT_PLAIN, nullptr, ql, qh, kl, kh,
-                        device, stream))
-        return e;
-    // 4. the rescales, four outputs (8 polynomials) per launch; 5. the bias on component 0 of the outputs that have one
-    for (int o0 = 0; o0 < k_out; o0 += 4) {
-        const int go = k_out - o0 < 4 ? k_out - o0 : 4;
-        const int64_t *ins[8], *row0[8];
-        int64_t *outs[8];
-        for (int g = 0; g < go; ++g)
-            for (int c = 0; c < 2; ++c) {
-                row0[2 * g + c] = S + (2 * (int64_t)(o0 + g) + c) * poly;
-                ins[2 * g + c] = row0[2 * g + c] + N;
-                outs[2 * g + c] = c ? out1[o0 + g] : out0[o0 + g];
-            }
-        if (int e = lf_rescale_batch(ins, row0, outs, 2 * go, rows - 1, N, rescale_scales, round_at, ql + 1, qh + 1, kl + 1, kh + 1, device,
-                                     stream))
+    // 3. the polynomials of S -> canonical coefficients: one inverse transform up to 128 polynomials (what lf_pc_matmul hands it
+    //    at 64 outputs), one per token beyond
+    const int per = 2 * k_out * nt <= 2 * LF_PC_MATMUL_MAX_OUTPUTS ? nt : 1;
+    for (int tk = 0; tk < nt; tk += per)
+        if (int e = lf_intt(S + tk * stok, 2 * k_out * per, rows, logN, ipsi_br, ipsi_dp, q_host, Ninv, 2, LF_NTT_RELAXED | LF_NTT_PLAIN,
+                            nullptr, ql, qh, kl, kh, device, stream))
             return e;
+    // 4. the rescales, four outputs (8 polynomials) per launch; 5. the bias on component 0 of the outputs that have one
+    for (int tk = 0; tk < nt; ++tk) {
+        int64_t *St = S + tk * stok;
+        int64_t *const *o0s = out0 + (int64_t)tk * k_out, *const *o1s = out1 + (int64_t)tk * k_out;
+        for (int o0 = 0; o0 < k_out; o0 += 4) {
+            const int go = k_out - o0 < 4 ? k_out - o0 : 4;
+            const int64_t *ins[8], *row0[8];
+            int64_t *outs[8];
+            for (int g = 0; g < go; ++g)
+                for (int c = 0; c < 2; ++c) {
+                    row0[2 * g + c] = St + (2 * (int64_t)(o0 + g) + c) * poly;
+                    ins[2 * g + c] = row0[2 * g + c] + N;
+                    outs[2 * g + c] = c ? o1s[o0 + g] : o0s[o0 + g];
+                }
+            if (int e = lf_rescale_batch(ins, row0, outs, 2 * go, rows - 1, N, rescale_scales, round_at, ql + 1, qh + 1, kl + 1, kh + 1,
+                                         device, stream))
+                return e;
+        }
+        if (!bias) continue;
+        for (int o = 0; o < k_out; ++o)
+            if (bias[o])
+                if (int e = lf_pc_bias(o0s[o], bias[o], Rs + 1, rows - 1, logN, ql + 1, qh + 1, kl + 1, kh + 1, (hipStream_t)stream)) return e;
     }
-    if (!bias) return 0;
-    for (int o = 0; o < k_out; ++o)
-        if (bias[o])
-            if (int e = lf_pc_bias(out0[o], bias[o], Rs + 1, rows - 1, logN, ql + 1, qh + 1, kl + 1, kh + 1, (hipStream_t)stream)) return e;
     return 0;
+}
+
+int lf_pc_matmul(int k_in, int k_out, const int64_t *const *in, const int64_t *const *pt, const int64_t *const *bias,
+                 int64_t *const *out0, int64_t *const *out1, int rows, int logN, const int64_t *psi_br, const double *psi_dp,
+                 const int64_t *ipsi_br, const double *ipsi_dp, const int64_t *q_host, const int64_t *Rs, const int64_t *Ninv,
+                 const int64_t *mont_one, const int64_t *zero_row, const int64_t *rescale_scales, int64_t round_at, int64_t *ws,
+                 int64_t ws_words, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, int device, void *stream) {
+    return pc_matmul_tokens(1, lf_pc_matmul_ws_words(k_in, k_out, rows, logN), k_in, k_out, in, pt, bias, out0, out1, rows, logN, psi_br,
+                            psi_dp, ipsi_br, ipsi_dp, q_host, Rs, Ninv, mont_one, zero_row, rescale_scales, round_at, ws, ws_words, ql, qh,
+                            kl, kh, device, stream);
+}
+
+/* ---- pc_matmul_batch: lf_pc_matmul over nt token vectors that share the matrix (include/ckks_hip.h): every plaintext word is
+ * read once per tile of 2 tokens instead of once per token. ---- */
+int lf_pc_matmul_batch(int nt, int k_in, int k_out, const int64_t *const *in, const int64_t *const *pt, const int64_t *const *bias,
+                       int64_t *const *out0, int64_t *const *out1, int rows, int logN, const int64_t *psi_br, const double *psi_dp,
+                       const int64_t *ipsi_br, const double *ipsi_dp, const int64_t *q_host, const int64_t *Rs, const int64_t *Ninv,
+                       const int64_t *mont_one, const int64_t *zero_row, const int64_t *rescale_scales, int64_t round_at, int64_t *ws,
+                       int64_t ws_words, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, int device,
+                       void *stream) {
+    if (nt < 1 || nt > LF_PC_MATMUL_BATCH_MAX_TOKENS) return LF_ERR_ARG;
+    return pc_matmul_tokens(nt, lf_pc_matmul_batch_ws_words(nt, k_in, k_out, rows, logN), k_in, k_out, in, pt, bias, out0, out1, rows,
+                            logN, psi_br, psi_dp, ipsi_br, ipsi_dp, q_host, Rs, Ninv, mont_one, zero_row, rescale_scales, round_at, ws,
+                            ws_words, ql, qh, kl, kh, device, stream);
 }
 
 int lf_switch_key(const lf_ks_plan *p, const int64_t *c0, const int64_t *c1, int64_t gal_pinv, int gal_canonical,

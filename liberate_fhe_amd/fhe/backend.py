@@ -497,6 +497,28 @@ class HipBackend:
                                _p(Rs), _p(Ninv), _p(mont_one), _p(zero_row), _p(scales), round_at, _p(ws), ws.numel(), *c.mont(), dev, st),
               "lf_pc_matmul")
 
+    # include/ckks_hip.h: LF_PC_MATMUL_BATCH_MAX_TOKENS (tests/test_pc_matmul_batch_cpu.py holds this copy to the header); the
+    # group sizes lf_pc_matmul_batch has a tile of tokens for, largest first
+    pc_matmul_batch_max_tokens = 4
+    pc_matmul_batch_sizes = (4, 2)
+
+    @staticmethod
+    def pc_matmul_batch_ws_words(nt, k_in, k_out, rows, logN):
+        return int(lib.lf_pc_matmul_batch_ws_words(nt, k_in, k_out, rows, logN))
+
+    def pc_matmul_batch_native(self, ins, pts, biases, outs, nt, k_in, k_out, rows, logN, psi, ipsi, Rs, Ninv, mont_one, zero_row, scales,
+                               round_at, ws, c: Consts):
+        """pc_matmul_native over nt token vectors that share the matrix as ONE native call (lf_pc_matmul_batch).  ins: ctypes array
+        of nt 2 k_in device pointers ([token][input][component]); pts, biases: as pc_matmul_native, shared by the tokens; outs: nt
+        lists of k_out pairs of output tensors [rows - 1, N]; ws: at least pc_matmul_batch_ws_words(nt, k_in, k_out, rows, logN) words."""
+        dev, st = _ds(outs[0][0][0])
+        psi_dp = twiddles.dp_pointer(psi, c.ql, c.qh, c.kl, c.kh, dev, st)
+        ipsi_dp = twiddles.dp_pointer(ipsi, c.ql, c.qh, c.kl, c.kh, dev, st)
+        out0, out1 = _parr([o[0] for tok in outs for o in tok]), _parr([o[1] for tok in outs for o in tok])
+        check(lib.lf_pc_matmul_batch(nt, k_in, k_out, ins, pts, biases, out0, out1, rows, logN, _p(psi), psi_dp, _p(ipsi), ipsi_dp,
+                                     c.qptr(True), _p(Rs), _p(Ninv), _p(mont_one), _p(zero_row), _p(scales), round_at, _p(ws), ws.numel(),
+                                     *c.mont(), dev, st), "lf_pc_matmul_batch")
+
     @staticmethod
     def rotate_hoisted_ws_words(plan):
         return int(lib.lf_rotate_hoisted_ws_words(ctypes.byref(plan)))

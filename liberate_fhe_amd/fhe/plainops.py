@@ -1,8 +1,8 @@
 """Encoded plaintexts, mixed into `ckks_engine`: a message vector encoded ONCE (encode_plain) and then multiplied into, added to,
-or summed against ciphertexts any number of times (pc_mult, pc_add, pc_dot, pc_matmul) — per-channel weights, masks, biases,
+or summed against ciphertexts any number of times (pc_mult, pc_add, pc_dot, pc_matmul, pc_matmul_batch) — per-channel weights, masks, biases,
 convolution taps, layers.  The reference only has mc_mult / mc_add, which encode on every call; like the engine's other options beyond it, the words
 of these ops are DEFINED as compositions of ops the engine already has (written out in the docstrings), and that composition is
-what runs wherever the native call (lf_pc_dot, lf_pc_matmul) does not apply.  DESIGN.md §4.2.
+what runs wherever the native call (lf_pc_dot, lf_pc_matmul, lf_pc_matmul_batch) does not apply.  DESIGN.md §4.2.
 """
 from __future__ import annotations
 
@@ -145,18 +145,8 @@ class PlainOps:
         out = self.rescale(self._new(S, types.origins["ct"], level=l))
         return out if bias is None else self.pc_add(bias, out)
 
-    def pc_matmul(self, W, cts, bias=None):
-        """A plaintext matrix times a vector of ciphertexts: the list of the k_out ciphertexts sum_i W[o][i] * cts[i] (+ bias[o]) at
-        level + 1, one rescale each.  W: k_out rows of k_in entries, each an encode_plain(.., level) of kind "mult" or None (a zero
-        weight, skipped; every row needs an entry); cts: k_in ciphertexts of that level (coefficient domain, no special limbs);
-        bias: None, or k_out entries, each None or an encode_plain(.., level + 1, "add").  Objects may repeat on either side; a
-        ciphertext whose whole column is None is legal and is not touched.  Output o has exactly the words of
-            pc_dot([(W[o][i], cts[i]) for i in range(k_in) if W[o][i] is not None], bias[o])
-        and that loop is what runs where the native call does not apply (pc_dot's conditions).  Otherwise ONE native call
-        (lf_pc_matmul) per 64 outputs: every ciphertext is transformed once, whatever k_out, and every transformed word is read
-        once per group of four outputs."""
-        W = [list(row) for row in W]
-        cts = list(cts)
+    def _pc_matmul_checked(self, W, cts, bias):
+        """pc_matmul's checks on materialised lists, in its order: (bias as a list of k_out entries, the level)."""
         k_out, k_in = len(W), len(cts)
         if not W or not cts:
             raise ValueError("pc_matmul: at least one row of plaintexts and one ciphertext")
@@ -175,7 +165,6 @@ class PlainOps:
             if x.level != l:
                 raise errors.NotMatchDataStructState(origin=f"{x.origin} at level {x.level} beside level {l}")
         if bias is not None:
-            bias = list(bias)
             if len(bias) != k_out:
                 raise ValueError(f"pc_matmul: {len(bias)} biases for {k_out} rows")
             for b in bias:
@@ -187,6 +176,22 @@ class PlainOps:
             bias = [None] * k_out
         if l + 1 >= self.num_levels:
             raise errors.MaximumLevelError(level=l, level_max=self.num_levels)
+        return bias, l
+
+    def pc_matmul(self, W, cts, bias=None):
+        """A plaintext matrix times a vector of ciphertexts: the list of the k_out ciphertexts sum_i W[o][i] * cts[i] (+ bias[o]) at
+        level + 1, one rescale each.  W: k_out rows of k_in entries, each an encode_plain(.., level) of kind "mult" or None (a zero
+        weight, skipped; every row needs an entry); cts: k_in ciphertexts of that level (coefficient domain, no special limbs);
+        bias: None, or k_out entries, each None or an encode_plain(.., level + 1, "add").  Objects may repeat on either side; a
+        ciphertext whose whole column is None is legal and is not touched.  Output o has exactly the words of
+            pc_dot([(W[o][i], cts[i]) for i in range(k_in) if W[o][i] is not None], bias[o])
+        and that loop is what runs where the native call does not apply (pc_dot's conditions).  Otherwise ONE native call
+        (lf_pc_matmul) per 64 outputs: every ciphertext is transformed once, whatever k_out, and every transformed word is read
+        once per group of four outputs."""
+        W = [list(row) for row in W]
+        cts = list(cts)
+        k_out = len(W)
+        bias, l = self._pc_matmul_checked(W, cts, None if bias is None else list(bias))
         d = self._native_level(l + 1)
         if d is not None and self._native_level(l) == d and hasattr(self.backend, "pc_matmul_native") and self.ctx.logN <= 17 \
                 and list(self.ntt.p.destination_arrays[l][d][1:]) == list(self.ntt.p.destination_arrays[l + 1][d]):
@@ -223,6 +228,89 @@ class PlainOps:
                                       self._tw(d, l, False, True), self._vec("Rs", d, l, False), self._vec("Ninv", d, l, False), ident[0],
                                       ident[1], self.rescale_scales[l][d], round_at, ws, self._consts(d, l, False))
         return [self._new(([o[0]], [o[1]]), types.origins["ct"], level=l + 1) for o in outs]
+
+    # group sizes of pc_matmul_batch's native path, largest first (filtered by backend.pc_matmul_batch_sizes), as rsum_batch_sizes: a
+    # size that does not beat the loop is left out here and its tokens take pc_matmul one by one — the words are the same.
+    # Groups of 4 are left out: on MI355X they lose to groups of 2 everywhere and to the loop at silver (DESIGN.md §4.2 has the
+    # numbers); the backend still takes them (tools/pc_matmul_batch.py --ab measures them).
+    pc_matmul_batch_sizes = (2,)
+
+    @staticmethod
+    def _pc_operand_ok(t):
+        return t.is_contiguous() and t.dtype == torch.int64 and t.data_ptr() % 16 == 0 and t.is_cuda
+
+    def pc_matmul_batch(self, W, X, bias=None):
+        """pc_matmul of many token vectors under the SAME matrix (a dense layer over the tokens of a sequence or the samples of a
+        batch): returns exactly [pc_matmul(W, cts, bias) for cts in X], word for word and in order — B lists of k_out ciphertexts
+        at level + 1; an empty X gives [].  W, bias: as pc_matmul takes them; X: B token vectors of k_in ciphertexts each (the same
+        object may appear in any number of tokens and positions).  What pc_matmul refuses for any token is refused for the whole
+        call before anything is allocated or launched, with the error the loop would have raised first.  Where pc_matmul's native
+        call applies to a token and the backend has lf_pc_matmul_batch, the tokens that qualify go, in order, in groups of
+        pc_matmul_batch_sizes (pairs) through ONE native call per group and per 64 outputs: a group shares every product launch,
+        which reads each plaintext word — the larger stream of pc_matmul's products — once per group instead of once per token.  A token
+        that does not qualify (a component that is not contiguous, not 16-byte aligned or on the host), the one the groups leave
+        over, and every token on a backend without the entry take pc_matmul and keep their place."""
+        X = [list(cts) for cts in X]
+        if not X:
+            return []
+        W = [list(row) for row in W]
+        bias = None if bias is None else list(bias)
+        k_out = len(W)
+        levels = [self._pc_matmul_checked(W, cts, bias)[1] for cts in X]
+        l = levels[0]                                   # (every token is at W's level, so all levels are equal)
+        bias = [None] * k_out if bias is None else bias
+        out = [None] * len(X)
+        ready = []
+        sizes = [k for k in self.pc_matmul_batch_sizes if k in getattr(self.backend, "pc_matmul_batch_sizes", ())]
+        d = self._native_level(l + 1)
+        if sizes and d is not None and self._native_level(l) == d and hasattr(self.backend, "pc_matmul_batch_native") \
+                and 13 <= self.ctx.logN <= 17 \
+                and list(self.ntt.p.destination_arrays[l][d][1:]) == list(self.ntt.p.destination_arrays[l + 1][d]) \
+                and all(self._pc_operand_ok(x.data[0])
+                        for x in {id(x): x for x in [pt for row in W for pt in row] + bias if x is not None}.values()):
+            ready = [t for t, cts in enumerate(X) if all(self._pc_operand_ok(c) for ct in cts for c in (ct.data[0][0], ct.data[1][0]))]
+        step = getattr(self.backend, "pc_matmul_max_outputs", k_out)
+        while ready:
+            g = next((k for k in sizes if k <= len(ready)), None)
+            if g is None:
+                break
+            group, ready = ready[:g], ready[g:]
+            parts = [self._pc_matmul_batch_native(W[o0:o0 + step], [X[t] for t in group], bias[o0:o0 + step], l, d)
+                     for o0 in range(0, k_out, step)]
+            for j, t in enumerate(group):
+                out[t] = [o for part in parts for o in part[j]]
+        for t, cts in enumerate(X):
+            if out[t] is None:
+                out[t] = self.pc_matmul(W, cts, bias)
+        return out
+
+    def _pc_matmul_batch_native(self, W, toks, bias, l, d):
+        N, k_out, k_in, nt = self.ctx.N, len(W), len(toks[0]), len(toks)
+        rows = len(self.ntt.p.destination_arrays[l][d])          # the dropped limb first
+        owner = self.ntt.p.rescaler_loc[l]
+        round_at = self.ctx.q[self.ntt.p.destination_arrays[l][owner][0]] // 2
+        ins, pts = (ctypes.c_void_p * (nt * 2 * k_in))(), (ctypes.c_void_p * (k_out * k_in))()
+        for t, cts in enumerate(toks):
+            for i, ct in enumerate(cts):
+                for comp in range(2):
+                    ins[(t * k_in + i) * 2 + comp] = ct.data[comp][0].data_ptr()
+        for o, row in enumerate(W):
+            for i, pt in enumerate(row):
+                pts[o * k_in + i] = None if pt is None else pt.data[0].data_ptr()
+        biases = None
+        if any(b is not None for b in bias):
+            biases = (ctypes.c_void_p * k_out)()
+            for o, b in enumerate(bias):
+                biases[o] = None if b is None else b.data[0].data_ptr()
+        dev = self.ntt.devices[d]
+        ident = self._pc_identity(l, d)
+        chunk = min(k_in, self.backend.pc_matmul_chunk)
+        ws = self._ws("pc_matmul_batch_ws", (self.backend.pc_matmul_batch_ws_words(nt, chunk, k_out, rows, self.ctx.logN),), d)
+        outs = [[[torch.empty((rows - 1, N), dtype=torch.int64, device=dev) for _ in range(2)] for _ in range(k_out)] for _ in range(nt)]
+        self.backend.pc_matmul_batch_native(ins, pts, biases, outs, nt, k_in, k_out, rows, self.ctx.logN, self._tw(d, l, False),
+                                            self._tw(d, l, False, True), self._vec("Rs", d, l, False), self._vec("Ninv", d, l, False),
+                                            ident[0], ident[1], self.rescale_scales[l][d], round_at, ws, self._consts(d, l, False))
+        return [[self._new(([o[0]], [o[1]]), types.origins["ct"], level=l + 1) for o in tok] for tok in outs]
 
     def _pc_identity(self, l, d):
         """The identity the forward transform's rescale step is handed (include/ckks_hip.h: lf_pc_dot): R mod q per row, a row of zeros."""

@@ -398,6 +398,57 @@ def edge_ciphertext(engine, level, pattern, seed=0):
     return _edge_ct(engine, data, level)
 
 
+PLAINTEXT_EDGE_PATTERNS = ENGINE_EDGE_PATTERNS + ("q|0",)
+
+
+def _edge_pt(engine, data, level, kind):
+    from liberate_fhe_amd.fhe.presets import types
+    from liberate_fhe_amd.utils.synth import _data_struct
+    if kind not in ("mult", "add"):
+        raise ValueError(kind)
+    assert 0 <= level < engine.num_levels - (kind == "mult"), (level, kind)   # (a "mult" plaintext needs a level to rescale into)
+    return _data_struct(engine)(data=list(data), include_special=False, ntt_state=kind == "mult", montgomery_state=True,
+                                origin=types.origins["pt_" + kind], level=level, hash=engine.hash, version=engine.version)
+
+
+def edge_plaintext(engine, level, pattern, seed=0, kind="mult"):
+    """engine.encode_plain(.., level, kind) — same origin, flags, hash and version, one [rows, N] tensor per local device alive at
+    `level` — with the lazy words of edge_rows(.., lazy=True): "top" is 2q - 1 everywhere, "half" the seam of the balanced
+    representation, "mixed" another of the four patterns on every row, "random" uniform below 2q.  One more pattern, "q|0": the
+    lazy zero q and 0 by the Thue-Morse parity of the index — the REDC of the Montgomery word q is exactly q, the closed end of
+    the interval [0, q] the fp64-class rows of the pc kernels reduce a plaintext word into.  kind="add": the bias of `level`
+    (for a pc_dot of level-l operands: level = l + 1).  A word follows its prime's id, not the device that holds it."""
+    import torch
+    q, N = engine.ctx.q, engine.ctx.N
+    dest = engine.ntt.p.destination_arrays[level]
+    tm = thue_morse(N)
+    data = []
+    for d in _edge_ids(engine):
+        if d < len(dest):
+            if pattern == "q|0":
+                w = np.where(tm[None, :] == 1, 0, np.array([int(q[i]) for i in dest[d]], dtype=np.int64).reshape(-1, 1))
+            else:
+                w = edge_rows([q[i] for i in dest[d]], N, pattern, seed, lazy=True, ids=dest[d])
+            data.append(torch.from_numpy(w).to(engine.ntt.devices[d]))
+    return _edge_pt(engine, data, level, kind)
+
+
+def identity_plaintext(engine, level):
+    """The "mult" plaintext whose every word of row i is R mod q_i — the Montgomery form of 1 in every coefficient of the NTT
+    domain: the product with it leaves a ciphertext's words, so pc_dot([(identity, x)]) has exactly the words of rescale(x) and
+    whatever x holds in its dropped limb (pre_rescale_ciphertext: the five values of rounder_row0) reaches the rounder of the
+    pc entries."""
+    import torch
+    q, N = engine.ctx.q, engine.ctx.N
+    dest = engine.ntt.p.destination_arrays[level]
+    data = []
+    for d in _edge_ids(engine):
+        if d < len(dest):
+            w = np.repeat(np.array([R % int(q[i]) for i in dest[d]], dtype=np.int64)[:, None], N, axis=1)
+            data.append(torch.from_numpy(np.ascontiguousarray(w)).to(engine.ntt.devices[d]))
+    return _edge_pt(engine, data, level, "mult")
+
+
 def edge_key(engine, pattern, seed=0, origin="key switch key"):
     """utils.synth.key_switch_key (same layout, _remember_pack called the same way) with the lazy words of
     edge_rows(.., lazy=True): "top" is 2q - 1 everywhere."""

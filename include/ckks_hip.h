@@ -745,6 +745,37 @@ int lf_lt_matmul(const lf_ks_plan *plan, int k_in, int k_out, const int64_t *con
                  const int64_t *rescale_scales, int64_t round_at, int64_t *ws, int64_t ws_words, int64_t *const *out0,
                  int64_t *const *out1, void *stream);
 
+/* lf_lt_matmul over nt token vectors that share the matrix and the keys (a layer over the tokens of a sequence or the samples of
+ * a batch): for t < nt, o < k_out, out_{t,o} decrypts to sum_i sum_step diag_{o,i,step} * rot(m_{t,i}, step).  ONE call is one
+ * group of nt in {1, 2, 4} tokens, nt <= plan->max_nct.  in: HOST array of nt 2 k_in device pointers, [token][input][component]
+ * (the pointers of an input no block uses are not read, for any token); out0 / out1: HOST arrays of nt k_out pointers,
+ * [token][output]; everything else is lf_lt_matmul's, shared by all tokens.  The same polynomial may appear any number of times
+ * among `in`, in one token or several.
+ * Output (t, o) has exactly the words of lf_lt_matmul on token t: per (token, output) the products and the order of their
+ * additions are those of the single kernels, and the transforms act on each polynomial by itself.  nt = 1 IS lf_lt_matmul (the
+ * same launches).
+ * Enqueued for nt = 2 | 4, input-major as lf_lt_matmul; per input some block uses: the canonical copies of the 2 nt polynomials,
+ * ONE forward NTT of them on the ell ordinary rows and the products with plan->PR, into slot 0 of every token (zero on the special
+ * rows); where the column has keys ONE lf_ks_digits_batch of the nt c1 into plan->state, ONE extension + forward NTT of the
+ * nt nparts digits into plan->ext, and per key of the column ONE launch of ks_inner_babyb_kernel<nt> into slot 1 + j of every
+ * token (lf_linear_transform_bsgs_batch's baby step: the key crosses HBM once for the group); per group of 4, 2 or 1 outputs
+ * with a block in the column ONE launch of lt_block_productsb_kernel<4 | 2 | 1, 2> per tile of 2 tokens
+ * (lt_block_products_kernel's loop: a thread reads the pairs of its two tokens and each diagonal word ONCE for both).  After the
+ * last input the nt k_out sums S^{t,o}, token-major, in groups of up to 4: one lf_intt of the group's 2 g polynomials, one
+ * lf_ks_moddown_ws, one lf_rescale_batch.
+ * ws: lf_lt_matmul_batch_ws_words(plan, nb_max, k_out, nt) words, 16-byte aligned, lent by the caller: nt (nb_max + 1 + k_out)
+ * pairs [2][ell + K][N] + 2 g [ell][N] + lf_ks_moddown_ws_words(2 g, ..), g = min(nt k_out, 4) — it does not grow with k_in; for
+ * nt = 1 it is lf_lt_matmul_ws_words(plan, nb_max, k_out); 0 for what the entry refuses.
+ * LF_ERR_ARG before any launch for everything lf_lt_matmul refuses, nt not in {1, 2, 4} or above plan->max_nct, a NULL among the
+ * entries of in (used inputs) / out0 / out1 of any token, ws NULL, misaligned or too small. */
+#define LF_LT_MATMUL_BATCH_MAX_TOKENS 4
+int64_t lf_lt_matmul_batch_ws_words(const lf_ks_plan *plan, int nb_max, int k_out, int nt);
+int lf_lt_matmul_batch(const lf_ks_plan *plan, int nt, int k_in, int k_out, const int64_t *const *in, const int64_t *ncol,
+                       const int64_t *p_host, const int64_t *const *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off,
+                       int key_format, const int64_t *const *pt, const int64_t *pt_stride, const int64_t *bcount, const int64_t *bidx,
+                       const int64_t *rescale_scales, int64_t round_at, int64_t *ws, int64_t ws_words, int64_t *const *out0,
+                       int64_t *const *out1, void *stream);
+
 /* A matrix of baby-step / giant-step transforms times a vector of ciphertexts: lf_lt_matmul for blocks of hundreds of diagonals,
  * from the keys of the baby and the giant steps alone.  For o < k_out, out_o decrypts to
  *     sum_{i < k_in} sum_{step in steps(o, i)} diag_{o,i,step} * rot(m_i, step),   step = g + b, b = step mod n1,

@@ -135,6 +135,8 @@ _SIGNATURES["lf_linear_transform_bsgs_batch_ws_words"] = [_PL, _I, _I]
 _SIGNATURES["lf_linear_transform_bsgs_batch"] = [_PL, _I, _P, _P, _I, _P, _P, _I, _P, _P, _L, _L, _L, _I, _P, _L, _P, _P, _P, _L, _P, _L, _P, _P, _P]
 _SIGNATURES["lf_lt_matmul_ws_words"] = [_PL, _I, _I]
 _SIGNATURES["lf_lt_matmul"] = [_PL, _I, _I, _P, _P, _P, _P, _L, _L, _L, _I, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _P]
+_SIGNATURES["lf_lt_matmul_batch_ws_words"] = [_PL, _I, _I, _I]
+_SIGNATURES["lf_lt_matmul_batch"] = [_PL, _I, _I, _I, _P, _P, _P, _P, _L, _L, _L, _I, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _P]
 _SIGNATURES["lf_lt_matmul_bsgs_ws_words"] = [_PL, _I, _I, _I]
 _SIGNATURES["lf_lt_matmul_bsgs"] = [_PL, _I, _I, _P, _P, _P, _P, _I, _P, _P, _L, _L, _L, _I, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _P]
 
@@ -187,6 +189,7 @@ LF_PC_MATMUL_MAX_OUTPUTS = 64  # .. and outputs per call
 LF_PC_MATMUL_BATCH_MAX_TOKENS = 4   # include/ckks_hip.h: token vectors per lf_pc_matmul_batch call
 LF_LT_MATMUL_MAX_INPUTS = 64   # include/ckks_hip.h: inputs per lf_lt_matmul call
 LF_LT_MATMUL_MAX_OUTPUTS = 64  # .. and outputs per call
+LF_LT_MATMUL_BATCH_MAX_TOKENS = 4   # include/ckks_hip.h: token vectors per lf_lt_matmul_batch call
 LF_LT_MATMUL_BSGS_MAX_GIANTS = 64   # include/ckks_hip.h: giant steps per lf_lt_matmul_bsgs call
 LF_LT_MATMUL_BSGS_MAX_SUMS = 256    # .. and keyed inner sums (pairs of an output and a keyed giant step)
 LF_LT_BATCH_MAX_CTS = 64            # include/ckks_hip.h: ciphertexts per lf_linear_transform_batch call

@@ -2148,6 +2148,7 @@ struct BlockArgs {
     i64 pt_stride[4];              // words between the diagonals of the block's pack
     int fresh[4];                  // non-zero: S^o is written; zero: read, added to, written
     int nslots;
+    i64 u_tstride, out_tstride;    // lt_block_productsb_kernel: the words from one token's `u` resp. `out[i]` to the next token's
 };
 
 template <int NO>
@@ -2197,6 +2198,77 @@ __global__ void __launch_bounds__(256) lt_block_products_kernel(BlockArgs ba, in
         }
         *reinterpret_cast<longlong2 *>(s0) = a;
         *reinterpret_cast<longlong2 *>(s1) = b;
+    }
+}
+
+// ---- lf_lt_matmul over NT tokens (lf_lt_matmul_batch): lt_block_products_kernel<NO> for NT tokens that share the blocks --------
+// The same grid, the same loop over the slots of ONE input: per slot the NT pairs of the tokens (token k's pairs lie u_tstride
+// words behind token k - 1's), then per output the diagonal word ONCE (ld_nt, 16 bytes per thread) multiplied into the NT
+// accumulator sets; token k's sums go to out[i] + k * out_tstride, `fresh` per output as in the single kernel (the outputs of all
+// tokens of a call have seen the same inputs).  Per (token, output) the products, their order and the conditional subtractions are
+// those of lt_block_products_kernel<NO> on that token, so the words written are its words.
+// Range: a pair word is below 2q (slot 0: mont_enter's; slots 1 ..: the baby sums' csub / dp_to_word), a diagonal word below 2q, q < 2^60,
+// so the product a b < 4 q^2 < 2^122 is inside REDC62 and mm62u returns a b / 2^62 + q + 1 < 2q; S < 2q before every addition,
+// S + product < 4q < 2^62, csub brings it below 2q again; the read - add - write of fresh = 0 adds two words below 2q likewise.  Nothing depends on
+// the number of terms: every accumulator is reduced after each one.
+template <int NO, int NT>
+__global__ void __launch_bounds__(256) lt_block_productsb_kernel(BlockArgs ba, int rows, int logN, const i64 *__restrict__ ql,
+                                                                 const i64 *__restrict__ qh, const i64 *__restrict__ kl,
+                                                                 const i64 *__restrict__ kh) {
+    const int r = blockIdx.y;
+    const i64 N = (i64)1 << logN;
+    const i64 j0 = (i64)blockIdx.x * 512 + threadIdx.x * 2;
+    if (j0 >= N) return;
+    const RowMod m = load_mod(ql, qh, kl, kh, r);
+    const i64 o0 = (i64)r * N + j0, pair = 2 * (i64)rows * N;
+    i64 S[NT][NO][2][2];
+    const i64 *pt[NO];
+    unsigned long long any = 0;
+#pragma unroll
+    for (int i = 0; i < NO; ++i) {
+#pragma unroll
+        for (int k = 0; k < NT; ++k) S[k][i][0][0] = S[k][i][0][1] = S[k][i][1][0] = S[k][i][1][1] = 0;
+        pt[i] = ba.pt[i] + o0;
+        any |= ba.slots[i];
+    }
+    for (int t = 0; t < ba.nslots; ++t) {
+        if (!((any >> t) & 1ull)) continue;   // (wave-uniform: kernel arguments)
+        longlong2 u0[NT], u1[NT];
+#pragma unroll
+        for (int k = 0; k < NT; ++k) {
+            const i64 *ur = ba.u + (i64)k * ba.u_tstride + (i64)t * pair + o0;
+            u0[k] = *reinterpret_cast<const longlong2 *>(ur);
+            u1[k] = *reinterpret_cast<const longlong2 *>(ur + (i64)rows * N);
+        }
+#pragma unroll
+        for (int i = 0; i < NO; ++i) {
+            if (!((ba.slots[i] >> t) & 1ull)) continue;
+            const longlong2 w = ld_nt(pt[i]);
+            pt[i] += ba.pt_stride[i];
+#pragma unroll
+            for (int k = 0; k < NT; ++k) {
+                S[k][i][0][0] = csub(S[k][i][0][0] + mm62u((u64)u0[k].x, (u64)w.x, m.q, m.k), m.q2);
+                S[k][i][0][1] = csub(S[k][i][0][1] + mm62u((u64)u0[k].y, (u64)w.y, m.q, m.k), m.q2);
+                S[k][i][1][0] = csub(S[k][i][1][0] + mm62u((u64)u1[k].x, (u64)w.x, m.q, m.k), m.q2);
+                S[k][i][1][1] = csub(S[k][i][1][1] + mm62u((u64)u1[k].y, (u64)w.y, m.q, m.k), m.q2);
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < NO; ++i) {
+#pragma unroll
+        for (int k = 0; k < NT; ++k) {
+            i64 *s0 = ba.out[i] + (i64)k * ba.out_tstride + o0, *s1 = s0 + (i64)rows * N;
+            longlong2 a, b;
+            a.x = S[k][i][0][0], a.y = S[k][i][0][1], b.x = S[k][i][1][0], b.y = S[k][i][1][1];
+            if (!ba.fresh[i]) {   // (wave-uniform)
+                const longlong2 x = *reinterpret_cast<const longlong2 *>(s0), y = *reinterpret_cast<const longlong2 *>(s1);
+                a.x = csub(a.x + x.x, m.q2), a.y = csub(a.y + x.y, m.q2);
+                b.x = csub(b.x + y.x, m.q2), b.y = csub(b.y + y.y, m.q2);
+            }
+            *reinterpret_cast<longlong2 *>(s0) = a;
+            *reinterpret_cast<longlong2 *>(s1) = b;
+        }
     }
 }
 
@@ -3325,6 +3397,40 @@ int lf_lt_block_products(int no, const int64_t *u, int nslots, const int64_t *co
         case 4: LF_BLOCK_LAUNCH(4); break;
     }
 #undef LF_BLOCK_LAUNCH
+    return (int)hipGetLastError();
+}
+
+// ---- the launch of lf_lt_matmul_batch that is its own ----
+// lf_lt_block_products for nt (2 or 4) tokens that share the blocks: token k reads u + k * u_tstride and writes (or adds to)
+// out[i] + k * out_tstride.  One launch of lt_block_productsb_kernel<no, 2> per tile of 2 tokens: a diagonal word is read once per tile
+int lf_lt_block_productsb(int nt, int no, const int64_t *u, int64_t u_tstride, int nslots, const int64_t *const *pt,
+                          const unsigned long long *slots, const int64_t *pt_stride, int64_t *const *out, int64_t out_tstride,
+                          const int *fresh, int rows, int logN, const int64_t *ql, const int64_t *qh, const int64_t *kl,
+                          const int64_t *kh, hipStream_t st) {
+    if ((nt != 2 && nt != 4) || (no != 1 && no != 2 && no != 4) || !u || nslots < 1 || nslots > 64 || rows < 1 || rows > 65535)
+        return LF_ERR_ARG;
+    const int64_t pair = (2 * (int64_t)rows) << logN;
+    if (u_tstride < nslots * pair || out_tstride < pair) return LF_ERR_ARG;   // (the tokens' pairs and sums do not overlap)
+    BlockArgs ba{};
+    ba.nslots = nslots, ba.u_tstride = (i64)u_tstride, ba.out_tstride = (i64)out_tstride;
+    for (int i = 0; i < no; ++i) {
+        if (!pt[i] || !out[i] || !slots[i] || (nslots < 64 && (slots[i] >> nslots))) return LF_ERR_ARG;
+        ba.pt[i] = (const i64 *)pt[i], ba.slots[i] = slots[i], ba.pt_stride[i] = (i64)pt_stride[i], ba.fresh[i] = fresh[i];
+    }
+    const dim3 grid((unsigned)((((i64)1 << logN) + 511) / 512), (unsigned)rows);
+#define LF_BLOCKB_LAUNCH(NO)                                                                                                    \
+    hipLaunchKernelGGL((lt_block_productsb_kernel<NO, 2>), grid, dim3(256), 0, st, ba, rows, logN, (const i64 *)ql, (const i64 *)qh, \
+                       (const i64 *)kl, (const i64 *)kh)
+    for (int t0 = 0; t0 < nt; t0 += 2) {
+        ba.u = (const i64 *)u + t0 * u_tstride;
+        for (int i = 0; i < no; ++i) ba.out[i] = (i64 *)out[i] + t0 * out_tstride;
+        switch (no) {
+            case 1: LF_BLOCKB_LAUNCH(1); break;
+            case 2: LF_BLOCKB_LAUNCH(2); break;
+            case 4: LF_BLOCKB_LAUNCH(4); break;
+        }
+    }
+#undef LF_BLOCKB_LAUNCH
     return (int)hipGetLastError();
 }
 

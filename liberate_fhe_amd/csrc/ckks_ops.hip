@@ -64,6 +64,12 @@ int lf_lt_block_products(int no, const int64_t *u, int nslots, const int64_t *co
                          const int64_t *pt_stride, int64_t *const *out, const int *fresh, int rows, int logN, const int64_t *ql,
                          const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st);
 
+// ckks_ks.hip: the launch of lf_lt_matmul_batch that is its own
+int lf_lt_block_productsb(int nt, int no, const int64_t *u, int64_t u_tstride, int nslots, const int64_t *const *pt,
+                          const unsigned long long *slots, const int64_t *pt_stride, int64_t *const *out, int64_t out_tstride,
+                          const int *fresh, int rows, int logN, const int64_t *ql, const int64_t *qh, const int64_t *kl,
+                          const int64_t *kh, hipStream_t st);
+
 // ckks_ks.hip: the launches of lf_lt_matmul_bsgs that are its own
 int lf_ks_fwd_batch(const int64_t *state, int64_t state_stride, int nct, int nparts, int rows, int logN, const int64_t *desc,
                     const int64_t *E, const double *Ed, int64_t *tmp, const int64_t *psi_br, const double *psi_dp, const int64_t *q_host,
@@ -1185,27 +1191,31 @@ int64_t lf_lt_matmul_ws_words(const lf_ks_plan *p, int nb_max, int k_out) {
     return pair * (nb_max + 1 + k_out) + 2 * g * poly + lf_ks_moddown_ws_words(2 * g, p->ell, p->K, N);
 }
 
-int lf_lt_matmul(const lf_ks_plan *p, int k_in, int k_out, const int64_t *const *in, const int64_t *ncol, const int64_t *p_host,
-                 const int64_t *const *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format,
-                 const int64_t *const *pt, const int64_t *pt_stride, const int64_t *bcount, const int64_t *bidx,
-                 const int64_t *rescale_scales, int64_t round_at, int64_t *ws, int64_t ws_words, int64_t *const *out0,
-                 int64_t *const *out1, void *stream) {
+// the checks of lf_lt_matmul on everything but the ciphertexts', the outputs' and the workspace's pointers (nin: the pointers of
+// `in` per input, 2, times the tokens; those of a used input are checked for every token), and what the launches need of them:
+// the first key of every column, the inputs some output uses, the blocks' slot masks, the longest used column
+static int lt_matmul_args(const lf_ks_plan *p, int nt, int k_in, int k_out, const int64_t *const *in, const int64_t *ncol,
+                          const int64_t *p_host, const int64_t *const *ksk, int64_t part_stride, int64_t comp_stride, int key_format,
+                          const int64_t *const *pt, const int64_t *pt_stride, const int64_t *bcount, const int64_t *bidx,
+                          const int64_t *rescale_scales, int64_t *const *out0, int64_t *const *out1, std::vector<int64_t> &koff,
+                          std::vector<char> &used, std::vector<unsigned long long> &masks, int &nb_max) {
     if (!plan_ok(p) || !p->PR || p->ell < 2 || k_in < 1 || k_in > LF_LT_MATMUL_MAX_INPUTS || k_out < 1 || k_out > LF_LT_MATMUL_MAX_OUTPUTS ||
         !in || !ncol || !pt || !pt_stride || !bcount || !bidx || !rescale_scales || !out0 || !out1 ||
         (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES))
         return LF_ERR_ARG;
-    const int ell = p->ell, rows = p->ell + p->K, logN = p->logN, dev = p->device;
-    const int64_t N = (int64_t)1 << logN, twoN = 2 * N, poly = (int64_t)ell * N, pair = 2 * (int64_t)rows * N;
+    const int rows = p->ell + p->K;
+    const int64_t N = (int64_t)1 << p->logN, twoN = 2 * N;
     // the columns: keyed steps per input, the inputs some output uses, their keys
-    std::vector<int64_t> koff(k_in + 1, 0);
-    std::vector<char> used(k_in, 0);
-    int nb_max = 0;
+    koff.assign(k_in + 1, 0);
+    used.assign(k_in, 0);
+    nb_max = 0;
     for (int i = 0; i < k_in; ++i) {
         if (ncol[i] < 0 || ncol[i] > LF_BSGS_MAX_BABY_KEYS) return LF_ERR_ARG;
         koff[i + 1] = koff[i] + ncol[i];
         for (int o = 0; o < k_out && !used[i]; ++o) used[i] = pt[(int64_t)o * k_in + i] != nullptr;
         if (!used[i]) continue;
-        if (!in[2 * i] || !in[2 * i + 1]) return LF_ERR_ARG;
+        for (int t = 0; t < nt; ++t)
+            if (!in[2 * ((int64_t)t * k_in + i)] || !in[2 * ((int64_t)t * k_in + i) + 1]) return LF_ERR_ARG;
         if (ncol[i] && (!p_host || !ksk)) return LF_ERR_ARG;
         for (int64_t k = koff[i]; k < koff[i + 1]; ++k) {
             if (!ksk[k] || p_host[k] <= 0 || p_host[k] >= twoN || !(p_host[k] & 1)) return LF_ERR_ARG;
@@ -1215,10 +1225,11 @@ int lf_lt_matmul(const lf_ks_plan *p, int k_in, int k_out, const int64_t *const 
         if (ncol[i] > nb_max) nb_max = (int)ncol[i];
     }
     // the blocks: per output at least one; per block its slots inside the column's set, ascending
-    std::vector<unsigned long long> masks((size_t)k_out * k_in, 0);
+    masks.assign((size_t)k_out * k_in, 0);
     int64_t first = 0;
     for (int o = 0; o < k_out; ++o) {
-        if (!out0[o] || !out1[o]) return LF_ERR_ARG;
+        for (int t = 0; t < nt; ++t)
+            if (!out0[(int64_t)t * k_out + o] || !out1[(int64_t)t * k_out + o]) return LF_ERR_ARG;
         bool any = false;
         for (int i = 0; i < k_in; ++i) {
             const int64_t b = (int64_t)o * k_in + i;
@@ -1237,6 +1248,23 @@ int lf_lt_matmul(const lf_ks_plan *p, int k_in, int k_out, const int64_t *const 
         }
         if (!any) return LF_ERR_ARG;
     }
+    return 0;
+}
+
+int lf_lt_matmul(const lf_ks_plan *p, int k_in, int k_out, const int64_t *const *in, const int64_t *ncol, const int64_t *p_host,
+                 const int64_t *const *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format,
+                 const int64_t *const *pt, const int64_t *pt_stride, const int64_t *bcount, const int64_t *bidx,
+                 const int64_t *rescale_scales, int64_t round_at, int64_t *ws, int64_t ws_words, int64_t *const *out0,
+                 int64_t *const *out1, void *stream) {
+    std::vector<int64_t> koff;
+    std::vector<char> used;
+    std::vector<unsigned long long> masks;
+    int nb_max = 0;
+    if (int e = lt_matmul_args(p, 1, k_in, k_out, in, ncol, p_host, ksk, part_stride, comp_stride, key_format, pt, pt_stride, bcount, bidx,
+                               rescale_scales, out0, out1, koff, used, masks, nb_max))
+        return e;
+    const int ell = p->ell, rows = p->ell + p->K, logN = p->logN, dev = p->device;
+    const int64_t N = (int64_t)1 << logN, poly = (int64_t)ell * N, pair = 2 * (int64_t)rows * N;
     const int64_t need = lf_lt_matmul_ws_words(p, nb_max, k_out);
     if (!need || !ws || ws_words < need || ((uintptr_t)ws & 15)) return LF_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
@@ -1309,6 +1337,139 @@ int lf_lt_matmul(const lf_ks_plan *p, int k_in, int k_out, const int64_t *const 
             mds[t] = md + t * poly;
             row0[t] = mds[t], ins[t] = mds[t] + N;
             outs[t] = (t & 1) ? out1[o0 + t / 2] : out0[o0 + t / 2];
+        }
+        if (int e = lf_ks_moddown_ws(ss, mds, nullptr, 2 * g, ell, p->K, N, mdws, mdws_words, p->PiR, p->PiP, p->Rs, 0, nullptr, p->ql, p->qh,
+                                     p->kl, p->kh, dev, stream))
+            return e;
+        if (int e = lf_rescale_batch(ins, row0, outs, 2 * g, ell - 1, N, rescale_scales, round_at, p->ql + 1, p->qh + 1, p->kl + 1, p->kh + 1,
+                                     dev, stream))
+            return e;
+    }
+    return 0;
+}
+
+/* ---- lf_lt_matmul over nt token vectors under one matrix and one key set (include/ckks_hip.h): a group of nt = 2 or 4 tokens
+ * shares every launch; the baby sums read each key word and the block products each diagonal word once for the tokens of a
+ * launch.  nt = 1 is lf_lt_matmul. ---- */
+int64_t lf_lt_matmul_batch_ws_words(const lf_ks_plan *p, int nb_max, int k_out, int nt) {
+    if (!batch_ok(p, nt) || nt > LF_LT_MATMUL_BATCH_MAX_TOKENS || nb_max < 0 || nb_max > LF_BSGS_MAX_BABY_KEYS || k_out < 1 ||
+        k_out > LF_LT_MATMUL_MAX_OUTPUTS)
+        return 0;
+    const int64_t N = (int64_t)1 << p->logN, pair = 2 * (int64_t)(p->ell + p->K) * N, poly = (int64_t)p->ell * N;
+    const int g = nt * k_out < LF_LT_MATMUL_GROUP ? nt * k_out : LF_LT_MATMUL_GROUP;
+    // per token one input's pairs and the k_out pairs of S; the mod-down's results of one group of sums and its workspace
+    return pair * nt * (nb_max + 1 + k_out) + 2 * g * poly + lf_ks_moddown_ws_words(2 * g, p->ell, p->K, N);
+}
+
+int lf_lt_matmul_batch(const lf_ks_plan *p, int nt, int k_in, int k_out, const int64_t *const *in, const int64_t *ncol,
+                       const int64_t *p_host, const int64_t *const *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off,
+                       int key_format, const int64_t *const *pt, const int64_t *pt_stride, const int64_t *bcount, const int64_t *bidx,
+                       const int64_t *rescale_scales, int64_t round_at, int64_t *ws, int64_t ws_words, int64_t *const *out0,
+                       int64_t *const *out1, void *stream) {
+    if (!batch_ok(p, nt) || nt > LF_LT_MATMUL_BATCH_MAX_TOKENS) return LF_ERR_ARG;
+    if (nt == 1)
+        return lf_lt_matmul(p, k_in, k_out, in, ncol, p_host, ksk, part_stride, comp_stride, row_off, key_format, pt, pt_stride, bcount, bidx,
+                            rescale_scales, round_at, ws, ws_words, out0, out1, stream);
+    std::vector<int64_t> koff;
+    std::vector<char> used;
+    std::vector<unsigned long long> masks;
+    int nb_max = 0;
+    if (int e = lt_matmul_args(p, nt, k_in, k_out, in, ncol, p_host, ksk, part_stride, comp_stride, key_format, pt, pt_stride, bcount, bidx,
+                               rescale_scales, out0, out1, koff, used, masks, nb_max))
+        return e;
+    const int ell = p->ell, rows = p->ell + p->K, logN = p->logN, dev = p->device;
+    const int64_t N = (int64_t)1 << logN, poly = (int64_t)ell * N, half = (int64_t)rows * N, pair = 2 * half;
+    const int64_t need = lf_lt_matmul_batch_ws_words(p, nb_max, k_out, nt);
+    if (!need || !ws || ws_words < need || ((uintptr_t)ws & 15)) return LF_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    // token t: its input's pairs U(t) [nb_max + 1]; then the sums S [nt][k_out] (one run: a group of the tail may span two tokens), the
+    // mod-down's results of one group and its workspace
+    const int ns = nt * k_out, gmax = ns < LF_LT_MATMUL_GROUP ? ns : LF_LT_MATMUL_GROUP;
+    const int64_t member = (nb_max + 1) * pair;
+    int64_t *S = ws + nt * member, *md = S + ns * pair, *mdws = md + 2 * gmax * poly;
+    const int64_t mdws_words = lf_ks_moddown_ws_words(2 * gmax, ell, p->K, N);
+    auto U = [&](int t) { return ws + t * member; };
+    if (int e = lf_set_device(dev)) return e;
+    // slot 0 holds nothing on the special rows, for every input and token
+    for (int t = 0; t < nt; ++t)
+        for (int c = 0; c < 2; ++c)
+            if (hipError_t e = hipMemsetAsync(U(t) + c * half + poly, 0, (size_t)p->K * N * 8, st)) return (int)e;
+    std::vector<char> written(k_out, 0);
+    for (int i = 0; i < k_in; ++i) {
+        if (!used[i]) continue;
+        const int nb = (int)ncol[i];
+        // 1. slot 0 of every member = P NTT(c0), P NTT(c1) on the ordinary rows: canonical copies and ONE forward NTT of the 2 nt
+        //    polynomials in `md` (free until the tail; nt <= gmax), times P R, then into the slots
+        {
+            const int64_t *srcs[2 * LF_LT_MATMUL_BATCH_MAX_TOKENS];
+            int64_t *dsts[2 * LF_LT_MATMUL_BATCH_MAX_TOKENS];
+            for (int t = 0; t < nt; ++t)
+                for (int c = 0; c < 2; ++c) srcs[2 * t + c] = in[2 * ((int64_t)t * k_in + i) + c], dsts[2 * t + c] = md + (2 * t + c) * poly;
+            if (int e = lf_galois_batch(srcs, dsts, 2 * nt, ell, logN, 1, p->_2q, dev, stream)) return e;
+            if (int e = lf_ntt(md, 2 * nt, ell, logN, p->psi, p->psi_dp, p->q_host, p->Rs, 0, p->_2q, p->ql, p->qh, p->kl, p->kh, dev, stream))
+                return e;
+            for (int k = 0; k < 2 * nt; ++k) {
+                if (int e = lf_mont_enter(dsts[k], p->PR, ell, N, p->ql, p->qh, p->kl, p->kh, dev, stream)) return e;
+                if (hipError_t e = hipMemcpyAsync(U(k / 2) + (k & 1) * half, dsts[k], (size_t)poly * 8, hipMemcpyDeviceToDevice, st))
+                    return (int)e;
+            }
+        }
+        // 2. the digits of the nt c1 (canonical, no permutation), ONE extension + forward NTT of all of them, per key of the column
+        //    ONE launch into slot 1 + j of every member: the key crosses HBM once for the group
+        if (nb) {
+            const int64_t *srcs[LF_LT_MATMUL_BATCH_MAX_TOKENS], *chat0[LF_LT_MATMUL_BATCH_MAX_TOKENS];
+            int64_t *states[LF_LT_MATMUL_BATCH_MAX_TOKENS], *us[LF_LT_MATMUL_BATCH_MAX_TOKENS];
+            for (int t = 0; t < nt; ++t) srcs[t] = in[2 * ((int64_t)t * k_in + i) + 1], states[t] = p->state + t * poly, chat0[t] = U(t);
+            if (int e = lf_ks_digits_batch(srcs, states, nt, p->dig_nparts, p->dig_desc, p->dig_tab, N, 1, p->_2q, p->ql, p->qh, p->kl, p->kh, dev,
+                                           stream))
+                return e;
+            if (int e = lf_ks_fwd_batch(p->state, poly, nt, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, p->ext, p->psi, p->psi_dp, p->q_host,
+                                        p->ql, p->qh, p->kl, p->kh, st))
+                return e;
+            for (int j = 0; j < nb; ++j) {
+                for (int t = 0; t < nt; ++t) us[t] = U(t) + (j + 1) * pair;
+                if (int e = lf_ks_baby_sums_batch(nt, p_host[koff[i] + j], p->nparts, rows, ell, logN, ksk[koff[i] + j], part_stride, comp_stride,
+                                                  row_off, key_format, p->ext, chat0, us, p->q_host, p->ql, p->qh, p->kl, p->kh, st))
+                    return e;
+            }
+        }
+        // 3. the outputs that have a block in this column, 4, 2 or 1 per launch over the pairs of a tile of tokens
+        std::vector<int> os;
+        for (int o = 0; o < k_out; ++o)
+            if (pt[(int64_t)o * k_in + i]) os.push_back(o);
+        for (size_t a0 = 0; a0 < os.size();) {
+            const size_t left = os.size() - a0;
+            const int g = left >= 4 ? 4 : left >= 2 ? 2 : 1;
+            const int64_t *pts[4];
+            int64_t *outs[4], strides[4];
+            unsigned long long slots[4];
+            int fresh[4];
+            for (int t = 0; t < g; ++t) {
+                const int o = os[a0 + t];
+                const int64_t b = (int64_t)o * k_in + i;
+                pts[t] = pt[b], strides[t] = pt_stride[b], slots[t] = masks[b], outs[t] = S + o * pair, fresh[t] = !written[o];
+                written[o] = 1;
+            }
+            if (int e = lf_lt_block_productsb(nt, g, U(0), member, nb + 1, pts, slots, strides, outs, k_out * pair, fresh, rows, logN, p->ql,
+                                              p->qh, p->kl, p->kh, st))
+                return e;
+            a0 += g;
+        }
+    }
+    // 4. the nt k_out sums in groups of up to 4: one exact inverse NTT (intt_exit_reduce) of the group's 2 g polynomials, one
+    //    mod-down, one rescale into the callers' [ell - 1][N] pairs
+    for (int s0 = 0; s0 < ns; s0 += LF_LT_MATMUL_GROUP) {
+        const int g = ns - s0 < LF_LT_MATMUL_GROUP ? ns - s0 : LF_LT_MATMUL_GROUP;
+        int64_t *Sg = S + s0 * pair;
+        if (int e = lf_intt(Sg, 2 * g, rows, logN, p->ipsi, p->ipsi_dp, p->q_host, p->Ninv, 2, 0, p->_2q, p->ql, p->qh, p->kl, p->kh, dev, stream))
+            return e;
+        const int64_t *ss[2 * LF_LT_MATMUL_GROUP], *ins[2 * LF_LT_MATMUL_GROUP], *row0[2 * LF_LT_MATMUL_GROUP];
+        int64_t *mds[2 * LF_LT_MATMUL_GROUP], *outs[2 * LF_LT_MATMUL_GROUP];
+        for (int t = 0; t < 2 * g; ++t) {
+            ss[t] = Sg + t * half;
+            mds[t] = md + t * poly;
+            row0[t] = mds[t], ins[t] = mds[t] + N;
+            outs[t] = (t & 1) ? out1[s0 + t / 2] : out0[s0 + t / 2];
         }
         if (int e = lf_ks_moddown_ws(ss, mds, nullptr, 2 * g, ell, p->K, N, mdws, mdws_words, p->PiR, p->PiP, p->Rs, 0, nullptr, p->ql, p->qh,
                                      p->kl, p->kh, dev, stream))

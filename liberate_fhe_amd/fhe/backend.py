@@ -11,7 +11,8 @@ import ctypes
 
 import torch
 
-from .._native import lib, check, KsPlan, LF_KEY_PLANES, LF_LT_MATMUL_BSGS_MAX_GIANTS, LF_LT_MATMUL_BSGS_MAX_SUMS, LF_LT_BATCH_MAX_CTS
+from .._native import lib, check, KsPlan, LF_KEY_PLANES, LF_LT_MATMUL_BSGS_MAX_GIANTS, LF_LT_MATMUL_BSGS_MAX_SUMS, LF_LT_BATCH_MAX_CTS, \
+    LF_LT_MATMUL_BATCH_MAX_TOKENS
 from ..ntt import ntt_cuda, twiddles
 
 
@@ -722,20 +723,29 @@ class HipBackend:
         outs: k_out tensors [2, ell - 1, N]; ws: at least lt_matmul_ws_words(plan, the longest used column, k_out) words."""
         dev, st = _ds(outs[0])
         k_in, k_out = len(ins), len(blocks)
-        keyed = [k for col in col_keys for k in col]
-        fmt = {self._kfmt(k) for k in keyed}
-        if len(fmt) > 1:
-            raise ValueError("lt_matmul_native: the keys of one call must share one format")
-        ps = cs = 0
-        kb = (ctypes.c_void_p * max(len(keyed), 1))()
-        for j, key in enumerate(keyed):
-            kb[j], ps, cs = self._key_args(key, first_part)
+        kb, ps, cs, fmt, pts, strides, counts, slots = self._lt_matmul_marshal("lt_matmul_native", col_keys, first_part, blocks, k_in)
         i64 = lambda v: (ctypes.c_int64 * max(len(v), 1))(*v)
         inp = (ctypes.c_void_p * (2 * k_in))()
         for i, pair in enumerate(ins):
             if pair is not None:
                 inp[2 * i], inp[2 * i + 1] = pair[0].data_ptr(), pair[1].data_ptr()
-        pts = (ctypes.c_void_p * (k_out * k_in))()
+        check(lib.lf_lt_matmul(ctypes.byref(plan), k_in, k_out, inp, i64([len(c) for c in col_keys]), i64([e for c in col_exps for e in c]),
+                               kb, ps, cs, row_off, fmt, pts, i64(strides), i64(counts), i64(slots), _p(scales),
+                               round_at, _p(ws), ws.numel(), _parr([o[0] for o in outs]), _parr([o[1] for o in outs]), st),
+              "lf_lt_matmul")
+
+    def _lt_matmul_marshal(self, name, col_keys, first_part, blocks, k_in):
+        """(key pointers, part stride, component stride, key format, pack pointers, strides, counts, slots): the keys and the
+        blocks of lt_matmul_native / lt_matmul_batch_native as the C ABI takes them."""
+        keyed = [k for col in col_keys for k in col]
+        fmt = {self._kfmt(k) for k in keyed}
+        if len(fmt) > 1:
+            raise ValueError(f"{name}: the keys of one call must share one format")
+        ps = cs = 0
+        kb = (ctypes.c_void_p * max(len(keyed), 1))()
+        for j, key in enumerate(keyed):
+            kb[j], ps, cs = self._key_args(key, first_part)
+        pts = (ctypes.c_void_p * (len(blocks) * k_in))()
         strides, counts, slots = [], [], []
         for o, row in enumerate(blocks):
             for i, blk in enumerate(row):
@@ -746,10 +756,36 @@ class HipBackend:
                 pts[o * k_in + i] = pack.data_ptr()
                 strides.append(pack.stride(0)), counts.append(len(sl))
                 slots += list(sl)
-        check(lib.lf_lt_matmul(ctypes.byref(plan), k_in, k_out, inp, i64([len(c) for c in col_keys]), i64([e for c in col_exps for e in c]),
-                               kb, ps, cs, row_off, fmt.pop() if fmt else 0, pts, i64(strides), i64(counts), i64(slots), _p(scales),
-                               round_at, _p(ws), ws.numel(), _parr([o[0] for o in outs]), _parr([o[1] for o in outs]), st),
-              "lf_lt_matmul")
+        return kb, ps, cs, (fmt.pop() if fmt else 0), pts, strides, counts, slots
+
+    # include/ckks_hip.h: LF_LT_MATMUL_BATCH_MAX_TOKENS through _native.py's copy (tests/test_lt_matmul_batch_cpu.py holds both to
+    # the header); the group sizes lf_lt_matmul_batch takes beside 1
+    lt_matmul_batch_max_tokens = LF_LT_MATMUL_BATCH_MAX_TOKENS
+    lt_matmul_batch_sizes = (4, 2)
+
+    @staticmethod
+    def lt_matmul_batch_ws_words(plan, nb_max, k_out, nt):
+        return int(lib.lf_lt_matmul_batch_ws_words(ctypes.byref(plan), nb_max, k_out, nt))
+
+    def lt_matmul_batch_native(self, plan, toks, col_exps, col_keys, first_part, row_off, blocks, scales, round_at, outs, ws):
+        """lt_matmul_native for a group of nt = 1, 2 or 4 token vectors under one matrix and one key set as ONE native call
+        (lf_lt_matmul_batch; the plan sized for nt).  toks: per token what lt_matmul_native takes as `ins` (an input no block uses
+        may be None); outs: per token k_out tensors [2, ell - 1, N]; ws: at least lt_matmul_batch_ws_words(plan, the longest used
+        column, k_out, nt) words; everything else as lt_matmul_native."""
+        dev, st = _ds(outs[0][0])
+        nt, k_in, k_out = len(toks), len(toks[0]), len(blocks)
+        kb, ps, cs, fmt, pts, strides, counts, slots = self._lt_matmul_marshal("lt_matmul_batch_native", col_keys, first_part, blocks, k_in)
+        i64 = lambda v: (ctypes.c_int64 * max(len(v), 1))(*v)
+        inp = (ctypes.c_void_p * (nt * 2 * k_in))()
+        for t, ins in enumerate(toks):
+            for i, pair in enumerate(ins):
+                if pair is not None:
+                    inp[2 * (t * k_in + i)], inp[2 * (t * k_in + i) + 1] = pair[0].data_ptr(), pair[1].data_ptr()
+        check(lib.lf_lt_matmul_batch(ctypes.byref(plan), nt, k_in, k_out, inp, i64([len(c) for c in col_keys]),
+                                     i64([e for c in col_exps for e in c]), kb, ps, cs, row_off, fmt, pts, i64(strides), i64(counts),
+                                     i64(slots), _p(scales), round_at, _p(ws), ws.numel(), _parr([o[0] for tok in outs for o in tok]),
+                                     _parr([o[1] for tok in outs for o in tok]), st),
+              "lf_lt_matmul_batch")
 
     # include/ckks_hip.h: LF_LT_MATMUL_BSGS_MAX_GIANTS / LF_LT_MATMUL_BSGS_MAX_SUMS through _native.py's copies
     # (tests/test_lt_matmul_bsgs_cpu.py holds them to the header): the giant steps and the keyed inner sums of one lf_lt_matmul_bsgs call

@@ -9,6 +9,9 @@ all outputs; the sums over the inputs stay in Q P and every output is brought do
 the reference, the words are DEFINED as a composition of steps the engine already has (written out in lt_matmul's docstring), and
 that composition is what runs wherever the native call (lf_lt_matmul) does not apply.  DESIGN.md §4.2.
 
+lt_matmul_batch is lt_matmul over many token vectors under one matrix and one key set: the loop's words, the tokens in groups
+of 4 and 2 through one native call (lf_lt_matmul_batch) that reads every key once per group and every diagonal once per pair.
+
 lt_matmul_bsgs is the same matrix over baby-step / giant-step blocks (encode_diagonals(.., bsgs=n1)): the baby rotations are formed
 once per input, the inner sums of all inputs of one output are added in Q P before the giant key switch, and the outputs that share
 a giant step share the stream of its key (lf_lt_matmul_bsgs).
@@ -154,29 +157,116 @@ class LtMatmulOps:
                     for out in self._lt_matmul_native(W[o0:o0 + step], steps[o0:o0 + step], cts, by_step, level, d)]
         return self._lt_matmul_steps(W, steps, cts, by_step, level)
 
-    def _lt_matmul_native(self, W, steps, cts, by_step, level, d):
-        N, k_in = self.ctx.N, len(cts)
-        plan, _, first_part, row_off = self._op_plan(level, d)
+    def _lt_matmul_native_args(self, W, steps, by_step, level, d):
+        """What a native call takes of the matrix and the keys alone: (per input whether some block uses it, col_exps, col_keys,
+        blocks, the longest column's keyed steps, round_at), as HipBackend.lt_matmul_native names them."""
+        N, k_in = self.ctx.N, len(W[0])
         i0 = self._loc(0, special=True).index(d)
         li = self.local_ids.index(d)
         owner = self.ntt.p.rescaler_loc[level]
         round_at = self.ctx.q[self.ntt.p.destination_arrays[level][owner][0]] // 2
-        ins, col_exps, col_keys, slot = [], [], [], []
+        used, col_exps, col_keys, slot = [], [], [], []
         for i in range(k_in):
             col = [s for s in steps if s[i] is not None]
             keyed = sorted({t for s in col for t in s[i] if t})
-            ins.append((cts[i].data[0][0], cts[i].data[1][0]) if col else None)
+            used.append(bool(col))
             col_exps.append([encdec.galois_exponent(N, t) for t in keyed])
             col_keys.append([self._key_pack(by_step[t])[i0] for t in keyed])
             slot.append({0: 0, **{t: 1 + j for j, t in enumerate(keyed)}})
         blocks = [[None if b is None else (self._diag_pack(b)[li], [slot[i][t] for t in s[i]]) for i, b in enumerate(row)]
                   for row, s in zip(W, steps)]
-        nb_max = max(len(c) for c in col_keys)
+        return used, col_exps, col_keys, blocks, max(len(c) for c in col_keys), round_at
+
+    def _lt_matmul_native(self, W, steps, cts, by_step, level, d):
+        N = self.ctx.N
+        plan, _, first_part, row_off = self._op_plan(level, d)
+        used, col_exps, col_keys, blocks, nb_max, round_at = self._lt_matmul_native_args(W, steps, by_step, level, d)
+        ins = [(ct.data[0][0], ct.data[1][0]) if u else None for ct, u in zip(cts, used)]
         ws = self._ws("lt_matmul_ws", (self.backend.lt_matmul_ws_words(plan, nb_max, len(W)),), d)
         outs = [torch.empty((2, plan.ell - 1, N), dtype=torch.int64, device=self.ntt.devices[d]) for _ in W]
         self.backend.lt_matmul_native(plan, ins, col_exps, col_keys, first_part, row_off, blocks, self.rescale_scales[level][d],
                                       round_at, outs, ws)
         return [self._new(([o[0]], [o[1]]), types.origins["ct"], level=level + 1) for o in outs]
+
+    # group sizes of lt_matmul_batch's native path, largest first (filtered by backend.lt_matmul_batch_sizes), as
+    # pc_matmul_batch_sizes: a size that does not beat the loop of lt_matmul is left out here and its tokens take lt_matmul one by
+    # one — the words are the same (DESIGN.md §4.2 has the numbers; tools/lt_matmul_batch.py --ab measures every size)
+    lt_matmul_batch_sizes = (4, 2)
+
+    def lt_matmul_batch(self, W, X, rotks) -> list:
+        """lt_matmul of many token vectors under the SAME matrix and keys (a layer over the tokens of a sequence or the samples of
+        a batch): returns exactly [lt_matmul(W, cts, rotks) for cts in X], word for word and in order — B lists of k_out
+        ciphertexts at level + 1; an empty X gives [].  W, rotks: as lt_matmul takes them (lt_matmul_steps(W) names the keys); X:
+        B token vectors of k_in ciphertexts each (the same object may appear in any number of tokens and positions).  What
+        lt_matmul refuses for any token is refused for the whole call before anything is encoded, allocated or launched, with the
+        error the loop would have raised first.  A mapping block is encoded once per level of the tokens, not once per token:
+        encode draws its rounding at random, so a loop would multiply every token by other words; here the tokens of a level
+        share ONE encoding of each mapping object, and the words are those of the loop over these encoded objects.
+        Where lt_matmul's own native call applies (every limb of the level on one device of this process, ascending steps,
+        contiguous operands) and the backend has lf_lt_matmul_batch, the tokens of one level that qualify go, in order, in groups
+        of lt_matmul_batch_sizes through ONE native call per group and per 64 outputs: a group shares every launch, the baby sums
+        read each rotation key and the block products each diagonal once for the tokens of a launch instead of once per token.
+        A token that does not qualify, the one the groups leave over, and every token on a backend without the entry or on a
+        sharded or multi-device engine take lt_matmul and keep their place."""
+        X = [list(cts) for cts in X]
+        if not X:
+            return []
+        W, steps = self._lt_matmul_blocks(W)
+        if not isinstance(rotks, dict):
+            rotks = list(rotks)
+        need = sorted({s for srow in steps for b in srow if b is not None for s in b if s})
+        levels = []
+        for t, cts in enumerate(X):                  # the loop's order: token 0's operands, the keys, then the other tokens' operands
+            X[t], by_step, level = self._lt_matmul_operands("lt_matmul", W, cts, rotks)
+            levels.append(level)
+            if t == 0:
+                for s in need:
+                    if s not in by_step:
+                        raise errors.NotMatchType(origin=f"no key for step {s}", to=types.origins["rotk"] + str(s))
+        # (every refusal is behind us: from here on things are encoded, allocated and launched)
+        out = [None] * len(X)
+        sizes = [k for k in self.lt_matmul_batch_sizes if k in getattr(self.backend, "lt_matmul_batch_sizes", ())]
+        for level in sorted(set(levels)):
+            encoded, Wl = {}, [list(row) for row in W]
+            for row in Wl:
+                for i, b in enumerate(row):
+                    if b is not None and not is_struct(b):
+                        if id(b) not in encoded:
+                            encoded[id(b)] = self.encode_diagonals(b, level)
+                        row[i] = encoded[id(b)]
+            toks = [t for t, l in enumerate(levels) if l == level]
+            lsteps = [[None if b is None else self.diagonal_steps(b) for b in row] for row in Wl]
+            d = self._native_level(level)
+            ready = []
+            if sizes and d is not None and hasattr(self.backend, "lt_matmul_native") and hasattr(self.backend, "lt_matmul_batch_native") \
+                    and all(s is None or s == sorted(s) for srow in lsteps for s in srow):
+                used = [i for i in range(len(W[0])) if any(s[i] is not None for s in lsteps)]
+                ready = [t for t in toks if all(X[t][i].data[c][0].is_contiguous() for i in used for c in range(2))]
+            step = getattr(self.backend, "lt_matmul_max_outputs", len(W))
+            while ready:
+                g = next((k for k in sizes if k <= len(ready)), None)
+                if g is None:
+                    break
+                group, ready = ready[:g], ready[g:]
+                parts = [self._lt_matmul_batch_native(Wl[o0:o0 + step], lsteps[o0:o0 + step], [X[t] for t in group], by_step, level, d)
+                         for o0 in range(0, len(W), step)]
+                for j, t in enumerate(group):
+                    out[t] = [o for part in parts for o in part[j]]
+            for t in toks:
+                if out[t] is None:
+                    out[t] = self.lt_matmul(Wl, X[t], rotks)
+        return out
+
+    def _lt_matmul_batch_native(self, W, steps, toks, by_step, level, d):
+        N = self.ctx.N
+        plan, _, first_part, row_off = self._op_plan(level, d, nct=4)
+        used, col_exps, col_keys, blocks, nb_max, round_at = self._lt_matmul_native_args(W, steps, by_step, level, d)
+        ins = [[(ct.data[0][0], ct.data[1][0]) if u else None for ct, u in zip(cts, used)] for cts in toks]
+        ws = self._ws("lt_matmul_batch_ws", (self.backend.lt_matmul_batch_ws_words(plan, nb_max, len(W), len(toks)),), d)
+        outs = [[torch.empty((2, plan.ell - 1, N), dtype=torch.int64, device=self.ntt.devices[d]) for _ in W] for _ in toks]
+        self.backend.lt_matmul_batch_native(plan, ins, col_exps, col_keys, first_part, row_off, blocks, self.rescale_scales[level][d],
+                                            round_at, outs, ws)
+        return [[self._new(([o[0]], [o[1]]), types.origins["ct"], level=level + 1) for o in tok] for tok in outs]
 
     def _lt_matmul_steps(self, W, steps, cts, by_step, level):
         """The same words through the engine's steps (linear_transform's orchestrated loop): per used input the digits of c1 and
@@ -209,7 +299,8 @@ class LtMatmulOps:
             if not U:
                 continue                                                  # an input no output uses
             keyed = [t for t in U if t]
-            digits = self._ks_digits_exchanged(ct.data[1], level, galois=(1, True)) if keyed else {}
+            c1 = [t if t.is_contiguous() else t.contiguous() for t in ct.data[1]]   # (the digit launch takes a raw pointer)
+            digits = self._ks_digits_exchanged(c1, level, galois=(1, True)) if keyed else {}
             for di, d in enumerate(loc):
                 li = self.local_ids.index(d)
                 rows, ell = self._rows(d, level, True), self._rows(d, level, False)

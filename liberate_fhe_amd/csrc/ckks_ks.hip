@@ -29,6 +29,9 @@
 #include "../../include/ckks_hip.h"
 #include "ckks_ntt_core.h"
 #include "ckks_ntt_tile16.h"
+#include "ckks_launch.h"
+
+#include <type_traits>
 
 #define KS_WORDS ((1 << NTT_TILE_LOG_MAX) / NTT_THREADS)   // tile words owned by one thread (8)
 
@@ -2618,13 +2621,14 @@ void classify_rows(int rows, const int64_t *q_host, RowList &dp, RowList &in) {
 
 // K2 + P2 of `nparts` digits (descriptors desc[0 .. nparts), extended digits into tmp[nct][nparts][rows][N])
 int ks_forward(const int64_t *state, int64_t state_stride, int nct, int nparts, int rows, int logN, const int64_t *desc,
-               const int64_t *E, const double *Ed, int64_t *tmp, const int64_t *psi_br, const double *psi_dp,
-               const int64_t *q_host, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh,
-               hipStream_t st, const unsigned char *own = nullptr, int p0 = 0) {
+               const int64_t *E, const double *Ed, int64_t *tmp, const LfFwdTab &ft, const LfMod &m, hipStream_t st,
+               const unsigned char *own = nullptr, int p0 = 0) {
+    const int64_t *psi_br = ft.psi_br, *ql = m.ql, *qh = m.qh, *kl = m.kl, *kh = m.kh;
+    const double *psi_dp = ft.psi_dp;
     if (!psi_dp) return LF_ERR_ARG;   // the relaxed arithmetic of both classes lives in the auxiliary table
     const int tl = NTT_TILE_LOG_MAX, S1 = logN - tl;
     RowList dp, in;
-    classify_rows(rows, q_host, dp, in);
+    classify_rows(rows, m.q_host, dp, in);
     const bool dplanes = digit_planes(logN, dp, in);
     lf_fmt_note(tmp, ((size_t)nct * nparts * rows << logN) * 8, dplanes ? LF_FMT_PLANES : LF_FMT_RAW);
     const KsGeom kg{logN, tl, S1, rows, nparts, (i64)1 << logN, nct, (i64)state_stride, own, p0, dplanes ? 1 : 0};
@@ -2667,11 +2671,82 @@ int ks_forward(const int64_t *state, int64_t state_stride, int nct, int nparts, 
     return (int)hipGetLastError();
 }
 
-// K4: inverse transform of inv_polys sums [inv_polys][rows][N] -> canonical coefficients (relaxed, tail 2), in place on s;
-// spl: the sums' fp64-class rows arrive as planes and the tiled pass carries them through tmp (room for inv_polys polynomials)
-int ks_inv_sums(int inv_polys, int rows, int logN, bool spl, bool cols_last, bool mixed, const RowList &in, const RowList &dp,
-                i64 *tmp, i64 *s, const int64_t *ipsi_br, const double *ipsi_dp, const int64_t *Ninv, const int64_t *ql,
-                const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st) {
+// How the sums of ONE key switch travel, decided here and nowhere else: every launcher of an inner-product kernel takes its grid,
+// its DPL template flag and the `spl` argument from this, holds the digits to `digit_fmt`, and hands it to ks_inv_sums.  The
+// launchers whose sums stay in the NTT domain (baby and giant steps) ask for no pairs and use dplanes, digit_fmt and the grid alone.
+struct KsSums {
+    int logN, rows, pairs;   // pairs of sums [pairs][2][rows][N] the inverse transform takes
+    RowList dp, in;          // the rows of the fp64 class / of the integer class
+    bool mixed;              // both classes present: one launch per step covers both
+    bool dplanes;            // the digits' fp64-class rows are in planes format (digit_planes())
+    bool cols_last;          // the last inverse pass runs as the column kernel
+    bool spl;                // the sums' fp64-class rows travel as planes too
+    dim3 grid;               // of the inner-product kernels: 512 coefficients per block x rows
+    int digit_fmt;           // what lf_fmt_expect is asked about the digits
+    // the digits of `cts` ciphertexts must be in the format this half is about to read (lf_tune flipped between lf_ks_fwd and
+    // here: LF_ERR_STATE)
+    int expect_digits(const int64_t *ext, int cts, int nparts) const {
+        return lf_fmt_expect(ext, ((size_t)cts * nparts * rows << logN) * 8, digit_fmt);
+    }
+};
+KsSums ks_sums(int logN, int rows, const int64_t *q_host, int pairs, const int64_t *scratch, int64_t scratch_words) {
+    KsSums k{};
+    k.logN = logN, k.rows = rows, k.pairs = pairs;
+    classify_rows(rows, q_host, k.dp, k.in);
+    const int S1 = logN - NTT_TILE_LOG_MAX;
+    k.mixed = k.dp.n && k.in.n;
+    k.dplanes = digit_planes(logN, k.dp, k.in);
+    k.cols_last = S1 <= 4 || (S1 == 5 && k.mixed && g_ks_ext_cols_max > 4);   // column form of the last inverse pass
+    // The SUMS travel the same way as the digits: the inner product writes fp64-class rows as planes into s, the tiled inverse
+    // pass carries them s -> scratch (a pass that changes the format cannot run in place; ks_tail hands the digits' own buffer,
+    // spent by then), the column pass reads the planes and leaves canonical words in s.  6 instead of 8 bytes per word on three
+    // of the sums' four trips; needs room for the 2 x pairs polynomials in scratch and the column form of the last pass, else
+    // the sums stay raw words: same outputs.
+    k.spl = k.dplanes && (g_more_planes & 1) && k.cols_last && pairs && scratch && scratch_words >= ((int64_t)2 * pairs * rows << logN);
+    const i64 N = (i64)1 << logN;
+    k.grid = dim3((unsigned)((N + 512 * KI_COLS - 1) / (512 * KI_COLS)), (unsigned)rows);
+    k.digit_fmt = k.dplanes ? LF_FMT_PLANES : LF_FMT_RAW;
+    return k;
+}
+
+// the two formats of a launch as compile-time constants: f(PLANES, DPL) with the key in planes format / the digits' fp64-class rows
+// in planes format; LF_CT(X) is the constant an argument X carries
+#define LF_CT(X) std::remove_reference_t<decltype(X)>::value
+template <class F>
+void with_formats(bool planes, bool dplanes, F &&f) {
+    if (planes && dplanes) f(std::true_type{}, std::true_type{});
+    else if (planes) f(std::true_type{}, std::false_type{});
+    else if (dplanes) f(std::false_type{}, std::true_type{});
+    else f(std::false_type{}, std::false_type{});
+}
+// .. and a group size out of Gs (keys, ciphertexts or outputs of one launch): f(G); false, nothing called, for any other size
+template <int... Gs, class F>
+bool with_count(int g, F &&f) {
+    return ((g == Gs ? (f(std::integral_constant<int, Gs>{}), true) : false) || ...);
+}
+// the keys of one launch of the lt, rsum and baby kernels: 4 while 4 are left, then 2, then 1 (tests/test_accumulating_ops_edges_cpu.py
+// mirrors it)
+int key_group(int left) { return left >= 4 ? 4 : left >= 2 ? 2 : left > 0 ? 1 : 0; }
+// keys i0 .. i0 + g - 1 of the list and their exponents, as the kernels take them
+HoistKeys hoist_keys(const LfKeys &key, const int64_t *p_host, int i0, int g) {
+    HoistKeys hk{};
+    for (int t = 0; t < g; ++t) {
+        hk.ksk[t] = (const i64 *)key.ksk[i0 + t];
+        hk.p[t] = (unsigned)p_host[i0 + t];
+    }
+    return hk;
+}
+// the four per-row constant arrays as a kernel takes them
+#define LF_MOD_ARGS(m) (const i64 *)(m).ql, (const i64 *)(m).qh, (const i64 *)(m).kl, (const i64 *)(m).kh
+
+// K4: inverse transform of the 2 x ks.pairs sums [2 pairs][rows][N] -> canonical coefficients (relaxed, tail 2), in place on s;
+// ks.spl: the sums' fp64-class rows arrive as planes and the tiled pass carries them through tmp (room for all of them)
+int ks_inv_sums(const KsSums &ks, i64 *tmp, i64 *s, const LfInvTab &it, const LfMod &m, hipStream_t st) {
+    const int inv_polys = 2 * ks.pairs, rows = ks.rows, logN = ks.logN;
+    const bool spl = ks.spl, cols_last = ks.cols_last, mixed = ks.mixed;
+    const RowList &in = ks.in, &dp = ks.dp;
+    const int64_t *ipsi_br = it.ipsi_br, *Ninv = it.Ninv, *ql = m.ql, *qh = m.qh, *kl = m.kl, *kh = m.kh;
+    const double *ipsi_dp = it.ipsi_dp;
     const int tl = NTT_TILE_LOG_MAX, S1 = logN - tl;
     const unsigned per_row2 = (unsigned)inv_polys << (logN - tl);
     for (int pass = 0; pass < 2; ++pass) {
@@ -2720,86 +2795,37 @@ int ks_inv_sums(int inv_polys, int rows, int logN, bool spl, bool cols_last, boo
 }
 
 // K3 + K4: inner product of the nparts extended digits with the key, inverse transform to canonical coefficients
-int ks_tail(int nct, int nparts, int rows, int logN, const int64_t *ksk, int64_t part_stride, int64_t comp_stride,
-            int64_t row_off, int64_t *tmp, int64_t *s, const int64_t *ipsi_br, const double *ipsi_dp,
-            const int64_t *Ninv, const int64_t *q_host, const int64_t *ql, const int64_t *qh, const int64_t *kl,
-            const int64_t *kh, hipStream_t st, const RelinFold *fold = nullptr, int key_format = LF_KEY_RAW, bool presum = false) {
-    if (!ipsi_dp || (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES) || (presum && !fold)) return LF_ERR_ARG;
-    if (key_format == LF_KEY_PLANES && ((((uintptr_t)ksk | (uintptr_t)(part_stride * 8) | (uintptr_t)(comp_stride * 8)) & 15)))
-        return LF_ERR_ARG;
-    const int tl = NTT_TILE_LOG_MAX, S1 = logN - tl;
-    RowList dp, in;
-    classify_rows(rows, q_host, dp, in);
-    const bool mixed = dp.n && in.n;
-    const bool dplanes = digit_planes(logN, dp, in);
-    const bool cols_last = S1 <= 4 || (S1 == 5 && mixed && g_ks_ext_cols_max > 4);   // column form of the last inverse pass
-    // the digits in tmp must be in the format this half is about to read (lf_tune flipped between lf_ks_fwd and here: LF_ERR_STATE)
-    if (int e = lf_fmt_expect(tmp, ((size_t)nct * nparts * rows << logN) * 8, dplanes ? LF_FMT_PLANES : LF_FMT_RAW)) return e;
-    // The SUMS travel the same way: the inner product writes fp64-class rows as planes into s, the tiled inverse pass carries
-    // them s -> tmp (the digits are spent by then: tmp is scratch, and a pass that changes the format cannot run in place),
-    // the column pass reads the planes and leaves canonical words in s.  6 instead of 8 bytes per word on three of the
-    // sums' four trips; needs room for 2 nct polynomials in tmp (two digits or more) and the column form of the last pass.
-    const bool spl = dplanes && (g_more_planes & 1) && cols_last && nparts >= 2;
+int ks_tail(int nct, int nparts, int rows, int logN, const LfKeys &key, int64_t *tmp, int64_t *s, const LfInvTab &it, const LfMod &m,
+            hipStream_t st, const RelinFold *fold = nullptr, bool presum = false) {
+    if (!it.ipsi_dp || key.n != 1 || !lf_keys_ok(key) || (presum && !fold)) return LF_ERR_ARG;
+    // the sums' planes pass through tmp: the digits are spent by then, and two digits or more leave room for 2 nct polynomials
+    const KsSums ks = ks_sums(logN, rows, m.q_host, nct, tmp, ((int64_t)nct * nparts * rows) << logN);
+    if (int e = ks.expect_digits(tmp, nct, nparts)) return e;
     // K3: inner product with the key, summed over the digits
-    {
-        const i64 N = (i64)1 << logN;
-        dim3 grid((unsigned)((N + 512 * KI_COLS - 1) / (512 * KI_COLS)), (unsigned)rows);
-        const RelinFold nofold{nullptr, 0, nullptr, 0, nullptr, 0};
-#define LF_INNER_LAUNCH(NCT, FOLDB, PL, DPLB, FOLDV)                                                                   \
-    hipLaunchKernelGGL((ks_inner2_kernel<NCT, FOLDB, PL, DPLB>), grid, dim3(256), 0, st, (const i64 *)tmp, (const i64 *)ksk, \
-                       (i64)part_stride, (i64)comp_stride, (i64)row_off, (i64 *)s, nparts, rows, N, FOLDV, spl ? 1 : 0, (const i64 *)ql, \
-                       (const i64 *)qh, (const i64 *)kl, (const i64 *)kh)
-#define LF_INNER_DPL(NCT, FOLDB, PL, FOLDV)                                                                            \
-    do {                                                                                                               \
-        if (dplanes) LF_INNER_LAUNCH(NCT, FOLDB, PL, true, FOLDV);                                                     \
-        else LF_INNER_LAUNCH(NCT, FOLDB, PL, false, FOLDV);                                                            \
-    } while (0)
-#define LF_INNER_CASE(NCT)                                                                                             \
-    case NCT:                                                                                                          \
-        if (fold && planes) LF_INNER_DPL(NCT, true, true, *fold);                                                      \
-        else if (fold) LF_INNER_DPL(NCT, true, false, *fold);                                                          \
-        else if (planes) LF_INNER_DPL(NCT, false, true, nofold);                                                       \
-        else LF_INNER_DPL(NCT, false, false, nofold);                                                                  \
-        break;
-        const bool planes = key_format == LF_KEY_PLANES;
-#define LF_PRESUM_LAUNCH(PL, DPLB)                                                                                     \
-    hipLaunchKernelGGL((ks_inner2_presum_kernel<PL, DPLB>), grid, dim3(256), 0, st, (const i64 *)tmp, (const i64 *)ksk,  \
-                       (i64)part_stride, (i64)comp_stride, (i64)row_off, (i64 *)s, nparts, rows, N, *fold, spl ? 1 : 0, (const i64 *)ql, \
-                       (const i64 *)qh, (const i64 *)kl, (const i64 *)kh)
-#define LF_DOTB_LAUNCH(NCT, PL, DPLB)                                                                                  \
-    hipLaunchKernelGGL((ks_dotb_inner_kernel<NCT, PL, DPLB>), grid, dim3(256), 0, st, (const i64 *)tmp, (const i64 *)ksk, \
-                       (i64)part_stride, (i64)comp_stride, (i64)row_off, (i64 *)s, nparts, rows, N, *fold, spl ? 1 : 0, (const i64 *)ql, \
-                       (const i64 *)qh, (const i64 *)kl, (const i64 *)kh)
-#define LF_DOTB_CASE(NCT)                                                                                              \
-    case NCT:                                                                                                          \
-        if (planes && dplanes) LF_DOTB_LAUNCH(NCT, true, true);                                                        \
-        else if (planes) LF_DOTB_LAUNCH(NCT, true, false);                                                             \
-        else if (dplanes) LF_DOTB_LAUNCH(NCT, false, true);                                                            \
-        else LF_DOTB_LAUNCH(NCT, false, false);                                                                        \
-        break;
-        if (presum && nct == 1) {   // cc_dot: the fold reads a triplet already summed (one ciphertext)
-            if (planes && dplanes) LF_PRESUM_LAUNCH(true, true);
-            else if (planes) LF_PRESUM_LAUNCH(true, false);
-            else if (dplanes) LF_PRESUM_LAUNCH(false, true);
-            else LF_PRESUM_LAUNCH(false, false);
-        } else if (presum) {   // cc_dot_batch: nct summed triplets, fold->ct_stride apart
-            switch (nct) {
-                LF_DOTB_CASE(2) LF_DOTB_CASE(4)
-                default: return LF_ERR_ARG;
-            }
-        } else
-        switch (nct) {
-            LF_INNER_CASE(1) LF_INNER_CASE(2) LF_INNER_CASE(4)
-        }
-#undef LF_PRESUM_LAUNCH
-#undef LF_DOTB_LAUNCH
-#undef LF_DOTB_CASE
-#undef LF_INNER_LAUNCH
-#undef LF_INNER_DPL
-#undef LF_INNER_CASE
-    }
+    const i64 N = (i64)1 << logN;
+    const RelinFold nofold{nullptr, 0, nullptr, 0, nullptr, 0};
+    const bool planes = key.key_format == LF_KEY_PLANES;
+    auto launch = [&](auto kernel, const RelinFold &f) {
+        hipLaunchKernelGGL(kernel, ks.grid, dim3(256), 0, st, (const i64 *)tmp, (const i64 *)key.ksk[0], (i64)key.part_stride,
+                           (i64)key.comp_stride, (i64)key.row_off, (i64 *)s, nparts, rows, N, f, ks.spl ? 1 : 0, LF_MOD_ARGS(m));
+    };
+    if (presum && nct == 1) {   // cc_dot: the fold reads a triplet already summed (one ciphertext)
+        with_formats(planes, ks.dplanes, [&](auto PL, auto DPL) { launch(ks_inner2_presum_kernel<LF_CT(PL), LF_CT(DPL)>, *fold); });
+    } else if (presum) {   // cc_dot_batch: nct summed triplets, fold->ct_stride apart
+        if (!with_count<2, 4>(nct, [&](auto NCT) {
+                with_formats(planes, ks.dplanes,
+                             [&](auto PL, auto DPL) { launch(ks_dotb_inner_kernel<LF_CT(NCT), LF_CT(PL), LF_CT(DPL)>, *fold); });
+            }))
+            return LF_ERR_ARG;
+    } else
+        with_count<1, 2, 4>(nct, [&](auto NCT) {
+            with_formats(planes, ks.dplanes, [&](auto PL, auto DPL) {
+                if (fold) launch(ks_inner2_kernel<LF_CT(NCT), true, LF_CT(PL), LF_CT(DPL)>, *fold);
+                else launch(ks_inner2_kernel<LF_CT(NCT), false, LF_CT(PL), LF_CT(DPL)>, nofold);
+            });
+        });
     // K4: inverse transform -> canonical coefficients (relaxed, tail 2), in place on s
-    return ks_inv_sums(2 * nct, rows, logN, spl, cols_last, mixed, in, dp, (i64 *)tmp, (i64 *)s, ipsi_br, ipsi_dp, Ninv, ql, qh, kl, kh, st);
+    return ks_inv_sums(ks, (i64 *)tmp, (i64 *)s, it, m, st);
 }
 
 }  // namespace
@@ -2807,15 +2833,14 @@ int ks_tail(int nct, int nparts, int rows, int logN, const int64_t *ksk, int64_t
 // The launches of lf_cc_dot that are its own (ckks_ops.hip checks the arguments).
 // lf_dot_tensor: the tensor products of g (1, 2 or 4) pairs' operand stacks x = [g][4][ell][N] (pair stride 4 ell N; xpl: fp64-class
 // rows as planes) added into T = [3][ell][N] (first: written); t2 (may be NULL): a second copy of the new T2.
-int lf_dot_tensor(int g, const int64_t *x, int64_t *T, int64_t *t2, int ell, int logN, int xpl, int first, const int64_t *ql,
-                  const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st) {
+int lf_dot_tensor(int g, const int64_t *x, int64_t *T, int64_t *t2, int ell, int logN, int xpl, int first, const LfMod &m, hipStream_t st) {
     if ((g != 1 && g != 2 && g != 4) || !x || !T || ell < 1 || ell > 65535 || logN < 9) return LF_ERR_ARG;
     const i64 N = (i64)1 << logN;
     const dim3 grid((unsigned)(N / 512), (unsigned)ell);
 #define LF_DOT_CASE(GG)                                                                                                 \
     case GG:                                                                                                            \
         hipLaunchKernelGGL((dot_tensor_kernel<GG>), grid, dim3(256), 0, st, (const i64 *)x, (i64)4 * ell * N, (i64 *)T, (i64 *)t2, ell, N, \
-                           xpl, first, (const i64 *)ql, (const i64 *)qh, (const i64 *)kl, (const i64 *)kh);            \
+                           xpl, first, LF_MOD_ARGS(m));                                                                \
         break;
     switch (g) { LF_DOT_CASE(1) LF_DOT_CASE(2) LF_DOT_CASE(4) }
 #undef LF_DOT_CASE
@@ -2826,7 +2851,7 @@ int lf_dot_tensor(int g, const int64_t *x, int64_t *T, int64_t *t2, int ell, int
 // lf_pc_dot_products: the products of g (1, 2 or 4) terms' transformed pairs x = [g][2][rows][N] (xpl: fp64-class rows as planes)
 // with their plaintexts pt[0 .. g), added into S = [2][rows][N] (first: written).
 int lf_pc_dot_products(int g, const int64_t *x, const int64_t *const *pt, int64_t *S, int rows, int logN, int xpl, int first,
-                       const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st) {
+                       const LfMod &m, hipStream_t st) {
     if ((g != 1 && g != 2 && g != 4) || !x || !pt || !S || rows < 1 || rows > 65535 || logN < 9) return LF_ERR_ARG;
     const i64 N = (i64)1 << logN;
     PcTerms pa{};
@@ -2838,7 +2863,7 @@ int lf_pc_dot_products(int g, const int64_t *x, const int64_t *const *pt, int64_
 #define LF_PCDOT_CASE(GG)                                                                                                         \
     case GG:                                                                                                                      \
         hipLaunchKernelGGL((pc_dot_kernel<GG>), grid, dim3(256), 0, st, (const i64 *)x, pa, (i64 *)S, rows, N, xpl, first,         \
-                           (const i64 *)ql, (const i64 *)qh, (const i64 *)kl, (const i64 *)kh);                                   \
+                           LF_MOD_ARGS(m));                                                                                       \
         break;
     switch (g) { LF_PCDOT_CASE(1) LF_PCDOT_CASE(2) LF_PCDOT_CASE(4) }
 #undef LF_PCDOT_CASE
@@ -2846,13 +2871,11 @@ int lf_pc_dot_products(int g, const int64_t *x, const int64_t *const *pt, int64_
 }
 
 // lf_pc_bias: c0 [rows][N] (canonical) <- mc_add's chain with the "add" plaintext pt, in place; constants of those rows.
-int lf_pc_bias(int64_t *c0, const int64_t *pt, const int64_t *Rs, int rows, int logN, const int64_t *ql, const int64_t *qh,
-               const int64_t *kl, const int64_t *kh, hipStream_t st) {
+int lf_pc_bias(int64_t *c0, const int64_t *pt, const int64_t *Rs, int rows, int logN, const LfMod &m, hipStream_t st) {
     if (!c0 || !pt || !Rs || rows < 1 || rows > 65535 || logN < 9) return LF_ERR_ARG;
     const i64 N = (i64)1 << logN;
     const dim3 grid((unsigned)(N / 512), (unsigned)rows);
-    hipLaunchKernelGGL(pc_bias_kernel, grid, dim3(256), 0, st, (i64 *)c0, (const i64 *)pt, (const i64 *)Rs, N, (const i64 *)ql,
-                       (const i64 *)qh, (const i64 *)kl, (const i64 *)kh);
+    hipLaunchKernelGGL(pc_bias_kernel, grid, dim3(256), 0, st, (i64 *)c0, (const i64 *)pt, (const i64 *)Rs, N, LF_MOD_ARGS(m));
     return (int)hipGetLastError();
 }
 
@@ -2861,7 +2884,7 @@ int lf_pc_bias(int64_t *c0, const int64_t *pt, const int64_t *Rs, int rows, int 
 // rows as planes — refused where the library's note of that range says another format); pt[i * pt_stride + g]: the plaintext of
 // input i for output g, or NULL; added into S = [go][2][rows][N] (first: written).
 int lf_pc_matmul_products(int go, int n, const int64_t *x, const int64_t *const *pt, int pt_stride, int64_t *S, int rows, int logN,
-                          int xpl, int first, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st) {
+                          int xpl, int first, const LfMod &m, hipStream_t st) {
     if ((go != 1 && go != 2 && go != 4) || n < 1 || n > LF_PC_MATMUL_CI || !x || !pt || pt_stride < go || !S || rows < 1 || rows > 65535 ||
         logN < 9)
         return LF_ERR_ARG;
@@ -2874,7 +2897,7 @@ int lf_pc_matmul_products(int go, int n, const int64_t *x, const int64_t *const 
 #define LF_PCMM_CASE(GG)                                                                                                          \
     case GG:                                                                                                                      \
         hipLaunchKernelGGL((pc_matmul_kernel<GG>), grid, dim3(256), 0, st, (const i64 *)x, pa, (i64 *)S, n, rows, N, xpl, first,   \
-                           (const i64 *)ql, (const i64 *)qh, (const i64 *)kl, (const i64 *)kh);                                   \
+                           LF_MOD_ARGS(m));                                                                                       \
         break;
     switch (go) { LF_PCMM_CASE(1) LF_PCMM_CASE(2) LF_PCMM_CASE(4) }
 #undef LF_PCMM_CASE
@@ -2901,8 +2924,7 @@ int lf_pc_matmul_batch_outputs(int left, int nt) {
 // lf_pc_matmulb_products: lf_pc_matmul_products over gt (2 or 4) tokens in one launch: token t's transformed pairs at x + t * xtok,
 // its group's pairs of S at S + t * stok (strides in words, multiples of 2: 16-byte accesses); pt shared by the tokens.
 int lf_pc_matmulb_products(int go, int gt, int n, const int64_t *x, int64_t xtok, const int64_t *const *pt, int pt_stride, int64_t *S,
-                           int64_t stok, int rows, int logN, int xpl, int first, const int64_t *ql, const int64_t *qh, const int64_t *kl,
-                           const int64_t *kh, hipStream_t st) {
+                           int64_t stok, int rows, int logN, int xpl, int first, const LfMod &m, hipStream_t st) {
     if ((go != 1 && go != 2 && go != 4) || (gt != 2 && gt != 4) || n < 1 || n > LF_PC_MATMUL_CI || !x || !pt || pt_stride < go || !S ||
         rows < 1 || rows > 65535 || logN < 9 || xtok < ((int64_t)2 * n * rows << logN) || stok < ((int64_t)2 * go * rows << logN) ||
         (xtok & 1) || (stok & 1))
@@ -2917,7 +2939,7 @@ int lf_pc_matmulb_products(int go, int gt, int n, const int64_t *x, int64_t xtok
 #define LF_PCMMB_CASE(GG, TT)                                                                                                     \
     case GG * 8 + TT:                                                                                                             \
         hipLaunchKernelGGL((pc_matmulb_kernel<GG, TT>), grid, dim3(256), 0, st, (const i64 *)x, (i64)xtok, pa, (i64 *)S, (i64)stok, n, \
-                           rows, N, xpl, first, (const i64 *)ql, (const i64 *)qh, (const i64 *)kl, (const i64 *)kh);              \
+                           rows, N, xpl, first, LF_MOD_ARGS(m));                                                                  \
         break;
     switch (go * 8 + gt) {
         LF_PCMMB_CASE(1, 2) LF_PCMMB_CASE(2, 2) LF_PCMMB_CASE(4, 2) LF_PCMMB_CASE(1, 4) LF_PCMMB_CASE(2, 4) LF_PCMMB_CASE(4, 4)
@@ -2932,7 +2954,7 @@ int lf_pc_matmulb_products(int go, int gt, int n, const int64_t *x, int64_t xtok
 // says another format); ta[t * R + i] / tb[t * C + j]: the operand of row i / column j of the tile at inner index t, in 0 .. nu - 1,
 // or -1; written to T = [R C][3][ell][N], the T2 copies to t2 = [R C][ell][N].
 int lf_matmul_tensor(int R, int C, int k, int nu, const int64_t *x, const int *ta, const int *tb, int64_t *T, int64_t *t2, int ell,
-                     int logN, int xpl, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st) {
+                     int logN, int xpl, const LfMod &m, hipStream_t st) {
     if (R < 1 || C < 1 || R > 4 || C > 4 || (R * C != 1 && R * C != 2 && R * C != 4) || (R > 1 && C > 1 && R != C) || k < 1 ||
         k > LF_CC_MATMUL_MAX_INNER || nu < 1 || nu > LF_CC_MATMUL_MAX_OPERANDS || !x || !ta || !tb || !T || !t2 || ell < 1 || ell > 65535 ||
         logN < 9)
@@ -2954,7 +2976,7 @@ int lf_matmul_tensor(int R, int C, int k, int nu, const int64_t *x, const int *t
     const dim3 grid((unsigned)(N / 512), (unsigned)ell);
 #define LF_MM_LAUNCH(RR, CC)                                                                                                      \
     hipLaunchKernelGGL((matmul_tensor_kernel<RR, CC>), grid, dim3(256), 0, st, (const i64 *)x, ix, k, (i64 *)T, (i64 *)t2, ell, N, xpl, \
-                       (const i64 *)ql, (const i64 *)qh, (const i64 *)kl, (const i64 *)kh)
+                       LF_MOD_ARGS(m))
     switch (R * 8 + C) {
         case 1 * 8 + 1: LF_MM_LAUNCH(1, 1); break;
         case 1 * 8 + 2: LF_MM_LAUNCH(1, 2); break;
@@ -2968,391 +2990,225 @@ int lf_matmul_tensor(int R, int C, int k, int nu, const int64_t *x, const int *t
     return (int)hipGetLastError();
 }
 
-// lf_dot_relin: lf_relin_core_batch (one ciphertext) whose fold reads the summed triplet T instead of an operand stack: the
-// digits in `state` are those of T2's inverse transform; the (digit, own limb) pairs are not extended, the inner product takes
-// T2's words for them; the sums receive P T0 and P T1 on the ordinary rows.
-int lf_dot_relin(const int64_t *state, int nparts, int rows, int logN, const int64_t *desc, const int64_t *E, const double *Ed,
-                 const int64_t *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format, int64_t *tmp, int64_t *s,
-                 const int64_t *psi_br, const double *psi_dp, const int64_t *ipsi_br, const double *ipsi_dp, const int64_t *Ninv,
-                 const int64_t *T, const int64_t *PR, int ell, const uint8_t *own, const int64_t *q_host, const int64_t *ql,
-                 const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st) {
-    if (nparts < 1 || nparts > 254 || rows < 1 || rows > MAX_LIST_ROWS || logN <= NTT_TILE_LOG_MAX || logN > KS_LOGN_MAX || !q_host ||
-        !psi_dp || !ipsi_dp || !Ed || !T || !PR || ell < 0 || ell > rows)
+// lf_dot_relin: lf_relin_core_batch whose fold reads nct (1, 2 or 4) summed triplets T + t * 3 ell N instead of operand stacks: the
+// digits of triplet t at state + t * ell N are those of its T2's inverse transform; the (digit, own limb) pairs are not extended,
+// the inner product takes T2's words for them; the sums s [nct][2][rows][N] receive P T0 and P T1 on the ordinary rows.  ONE
+// extension + forward NTT of all digits, ONE launch of the inner product (every key word read once for the nct triplets), ONE
+// inverse NTT of the 2 nct sums.  Internal: ckks_ops.hip checks the arguments.
+int lf_dot_relin(const int64_t *state, int nct, int nparts, int rows, int logN, const int64_t *desc, const int64_t *E, const double *Ed,
+                 const LfKeys &key, int64_t *tmp, int64_t *s, const LfFwdTab &ft, const LfInvTab &it, const int64_t *T, const int64_t *PR,
+                 int ell, const uint8_t *own, const LfMod &m, hipStream_t st) {
+    if ((nct != 1 && nct != 2 && nct != 4) || nparts < 1 || nparts > 254 || rows < 1 || rows > MAX_LIST_ROWS || logN <= NTT_TILE_LOG_MAX ||
+        logN > KS_LOGN_MAX || !m.q_host || !ft.psi_dp || !it.ipsi_dp || !Ed || !T || !PR || ell < 0 || ell > rows)
         return LF_ERR_ARG;
-    if (!lf_fp64_digits_ok(nparts, rows, q_host)) return LF_ERR_ARG;
-    if (int e = ks_forward(state, 0, 1, nparts, rows, logN, desc, E, Ed, tmp, psi_br, psi_dp, q_host, ql, qh, kl, kh, st,
-                           (const unsigned char *)own, 0))
-        return e;
-    const RelinFold fold{(const i64 *)T, 0, (const i64 *)PR, ell, (const unsigned char *)own, 0};
-    return ks_tail(1, nparts, rows, logN, ksk, part_stride, comp_stride, row_off, tmp, s, ipsi_br, ipsi_dp, Ninv, q_host, ql, qh, kl, kh,
-                   st, &fold, key_format, true);
-}
-
-// lf_dot_relin_batch: lf_dot_relin for nct (2 or 4) summed triplets T + t * 3 ell N under one key: the digits of triplet t at
-// state + t * ell N, ONE extension + forward NTT of all of them, ONE launch of ks_dotb_inner_kernel<nct> (every key word read once
-// for the nct triplets), the inverse NTT of the 2 nct sums s [nct][2][rows][N].  Internal: ckks_ops.hip checks the arguments.
-int lf_dot_relin_batch(const int64_t *state, int nct, int nparts, int rows, int logN, const int64_t *desc, const int64_t *E,
-                       const double *Ed, const int64_t *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format,
-                       int64_t *tmp, int64_t *s, const int64_t *psi_br, const double *psi_dp, const int64_t *ipsi_br,
-                       const double *ipsi_dp, const int64_t *Ninv, const int64_t *T, const int64_t *PR, int ell, const uint8_t *own,
-                       const int64_t *q_host, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st) {
-    if ((nct != 2 && nct != 4) || nparts < 1 || nparts > 254 || rows < 1 || rows > MAX_LIST_ROWS || logN <= NTT_TILE_LOG_MAX ||
-        logN > KS_LOGN_MAX || !q_host || !psi_dp || !ipsi_dp || !Ed || !T || !PR || ell < 0 || ell > rows)
-        return LF_ERR_ARG;
-    if (!lf_fp64_digits_ok(nparts, rows, q_host)) return LF_ERR_ARG;
-    const int64_t poly = (int64_t)ell << logN;
-    if (int e = ks_forward(state, poly, nct, nparts, rows, logN, desc, E, Ed, tmp, psi_br, psi_dp, q_host, ql, qh, kl, kh, st,
-                           (const unsigned char *)own, 0))
-        return e;
+    if (!lf_fp64_digits_ok(nparts, rows, m.q_host)) return LF_ERR_ARG;
+    const int64_t poly = nct > 1 ? (int64_t)ell << logN : 0;   // (one triplet: no stride)
+    if (int e = ks_forward(state, poly, nct, nparts, rows, logN, desc, E, Ed, tmp, ft, m, st, (const unsigned char *)own, 0)) return e;
     const RelinFold fold{(const i64 *)T, (i64)(3 * poly), (const i64 *)PR, ell, (const unsigned char *)own, 0};
-    return ks_tail(nct, nparts, rows, logN, ksk, part_stride, comp_stride, row_off, tmp, s, ipsi_br, ipsi_dp, Ninv, q_host, ql, qh, kl,
-                   kh, st, &fold, key_format, true);
+    return ks_tail(nct, nparts, rows, logN, key, tmp, s, it, m, st, &fold, true);
 }
 
-// The key-dependent half of nr (1, 2 or 4) hoisted rotations of ONE ciphertext (lf_rotate_hoisted, ckks_ops.hip): inner product of
+namespace {
+// what the launchers of the gathered inner products refuse alike: the tables, the keys, the rows, the digits' count for fp64 rows
+bool gathered_args_ok(const LfKeys &key, const int64_t *p_host, int nparts, int rows, const LfInvTab *it, const LfMod &m) {
+    if ((it && !it->ipsi_dp) || !lf_keys_ok(key) || (key.n && !p_host)) return false;
+    return rows >= 1 && rows <= MAX_LIST_ROWS && lf_fp64_digits_ok(nparts, rows, m.q_host);
+}
+}  // namespace
+
+// The key-dependent half of key.n (1, 2 or 4) hoisted rotations of ONE ciphertext (lf_rotate_hoisted, ckks_ops.hip): inner product of
 // the extended digits `ext` [nparts][rows][N] (lf_ks_fwd) gathered by pi_{p_i} with key i, then the inverse transform of the
-// 2 nr sums s [nr][2][rows][N].  `ext` is only read, so it serves every group; the sums' planes pass through `scratch`
-// (scratch_words >= 2 nr rows N, else the sums stay raw words: same outputs).  Internal: ckks_ops.hip checks the arguments.
-int lf_ks_tail_hoisted(int nr, const unsigned *p, int nparts, int rows, int logN, const int64_t *const *ksk, int64_t part_stride,
-                       int64_t comp_stride, int64_t row_off, int key_format, const int64_t *ext, int64_t *s, int64_t *scratch,
-                       int64_t scratch_words, const int64_t *ipsi_br, const double *ipsi_dp, const int64_t *Ninv, const int64_t *q_host,
-                       const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st) {
-    if (!ipsi_dp || (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES) || (nr != 1 && nr != 2 && nr != 4)) return LF_ERR_ARG;
-    if (rows < 1 || rows > MAX_LIST_ROWS || !lf_fp64_digits_ok(nparts, rows, q_host)) return LF_ERR_ARG;
-    HoistKeys hk{};
-    for (int i = 0; i < nr; ++i) {
-        if (!ksk[i]) return LF_ERR_ARG;
-        if (key_format == LF_KEY_PLANES && ((((uintptr_t)ksk[i] | (uintptr_t)(part_stride * 8) | (uintptr_t)(comp_stride * 8)) & 15)))
-            return LF_ERR_ARG;
-        hk.ksk[i] = (const i64 *)ksk[i];
-        hk.p[i] = (unsigned)p[i];
-    }
-    const int tl = NTT_TILE_LOG_MAX, S1 = logN - tl;
-    RowList dp, in;
-    classify_rows(rows, q_host, dp, in);
-    const bool mixed = dp.n && in.n;
-    const bool dplanes = digit_planes(logN, dp, in);
-    const bool cols_last = S1 <= 4 || (S1 == 5 && mixed && g_ks_ext_cols_max > 4);
-    // the digits must be in the format this half reads (see ks_tail)
-    if (int e = lf_fmt_expect(ext, ((size_t)nparts * rows << logN) * 8, dplanes ? LF_FMT_PLANES : LF_FMT_RAW)) return e;
-    const bool spl = dplanes && (g_more_planes & 1) && cols_last && scratch && scratch_words >= ((int64_t)2 * nr * rows << logN);
-    const i64 N = (i64)1 << logN;
-    const dim3 grid((unsigned)((N + 511) / 512), (unsigned)rows);
-#define LF_HOIST_LAUNCH(NR, PL, DPLB)                                                                                       \
-    hipLaunchKernelGGL((ks_inner_hoist_kernel<NR, PL, DPLB>), grid, dim3(256), 0, st, (const i64 *)ext, hk, (i64)part_stride, \
-                       (i64)comp_stride, (i64)row_off, (i64 *)s, nparts, rows, logN, spl ? 1 : 0, (const i64 *)ql, (const i64 *)qh, \
-                       (const i64 *)kl, (const i64 *)kh)
-#define LF_HOIST_CASE(NR)                                                                                                  \
-    case NR:                                                                                                               \
-        if (planes && dplanes) LF_HOIST_LAUNCH(NR, true, true);                                                           \
-        else if (planes) LF_HOIST_LAUNCH(NR, true, false);                                                                \
-        else if (dplanes) LF_HOIST_LAUNCH(NR, false, true);                                                               \
-        else LF_HOIST_LAUNCH(NR, false, false);                                                                           \
-        break;
-    const bool planes = key_format == LF_KEY_PLANES;
-    switch (nr) { LF_HOIST_CASE(1) LF_HOIST_CASE(2) LF_HOIST_CASE(4) }
-#undef LF_HOIST_LAUNCH
-#undef LF_HOIST_CASE
-    return ks_inv_sums(2 * nr, rows, logN, spl, cols_last, mixed, in, dp, (i64 *)scratch, (i64 *)s, ipsi_br, ipsi_dp, Ninv, ql, qh, kl,
-                       kh, st);
+// 2 n sums s [n][2][rows][N].  `ext` is only read, so it serves every group; the sums' planes pass through `scratch`
+// (scratch_words >= 2 n rows N, else the sums stay raw words: same outputs).  Internal: ckks_ops.hip checks the arguments.
+int lf_ks_tail_hoisted(const int64_t *p_host, int nparts, int rows, int logN, const LfKeys &key, const int64_t *ext, int64_t *s,
+                       int64_t *scratch, int64_t scratch_words, const LfInvTab &it, const LfMod &m, hipStream_t st) {
+    const int nr = key.n;
+    if ((nr != 1 && nr != 2 && nr != 4) || !gathered_args_ok(key, p_host, nparts, rows, &it, m)) return LF_ERR_ARG;
+    const KsSums ks = ks_sums(logN, rows, m.q_host, nr, scratch, scratch_words);
+    if (int e = ks.expect_digits(ext, 1, nparts)) return e;
+    const HoistKeys hk = hoist_keys(key, p_host, 0, nr);
+    with_count<1, 2, 4>(nr, [&](auto NR) {
+        with_formats(key.key_format == LF_KEY_PLANES, ks.dplanes, [&](auto PL, auto DPL) {
+            hipLaunchKernelGGL((ks_inner_hoist_kernel<LF_CT(NR), LF_CT(PL), LF_CT(DPL)>), ks.grid, dim3(256), 0, st, (const i64 *)ext, hk,
+                               (i64)key.part_stride, (i64)key.comp_stride, (i64)key.row_off, (i64 *)s, nparts, rows, logN, ks.spl ? 1 : 0,
+                               LF_MOD_ARGS(m));
+        });
+    });
+    return ks_inv_sums(ks, (i64 *)scratch, (i64 *)s, it, m, st);
 }
 
-// The key-dependent part of lf_linear_transform (ckks_ops.hip): per group of up to 4 keys ONE launch of ks_inner_lt_kernel over
-// the shared extended digits `ext` (nr = 0: the step-0 term alone, one launch without keys), all of them adding into the one
-// pair of sums s [2][rows][N]; then the inverse transform of that pair.  `scratch` (>= 2 rows N words, or NULL: the sums stay
-// raw words, same outputs) carries the sums' planes through the tiled inverse pass; it may be `ext` itself, which is spent
-// once the last group has read it.  chat = P NTT(c0), P NTT(c1) on the `ell` ordinary rows.  Internal: ckks_ops.hip checks the
-// arguments (nr >= 0, odd exponents below 2N, pt0 != NULL when nr == 0).
-int lf_ks_tail_lt(int nr, const int64_t *p_host, int nparts, int rows, int ell, int logN, const int64_t *const *ksk, int64_t part_stride,
-                  int64_t comp_stride, int64_t row_off, int key_format, const int64_t *pt, int64_t pt_stride, const int64_t *pt0,
-                  const int64_t *chat, const int64_t *ext, int64_t *s, int64_t *scratch, int64_t scratch_words, const int64_t *ipsi_br,
-                  const double *ipsi_dp, const int64_t *Ninv, const int64_t *q_host, const int64_t *ql, const int64_t *qh,
-                  const int64_t *kl, const int64_t *kh, hipStream_t st) {
-    if (!ipsi_dp || (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES) || nr < 0 || (nr == 0 && !pt0) || !chat || ell < 0 || ell > rows)
+// The key-dependent part of lf_linear_transform (ckks_ops.hip): per group of up to 4 keys (key_group) ONE launch of
+// ks_inner_lt_kernel over the shared extended digits `ext` (no keys: the step-0 term alone, one launch without keys), all of them
+// adding into the one pair of sums s [2][rows][N]; then the inverse transform of that pair.  `scratch` (>= 2 rows N words, or
+// NULL: the sums stay raw words, same outputs) carries the sums' planes through the tiled inverse pass; it may be `ext` itself,
+// which is spent once the last group has read it.  chat = P NTT(c0), P NTT(c1) on the `ell` ordinary rows.  Internal:
+// ckks_ops.hip checks the arguments (odd exponents below 2N, pt0 != NULL without keys).
+int lf_ks_tail_lt(const int64_t *p_host, int nparts, int rows, int ell, int logN, const LfKeys &key, const int64_t *pt, int64_t pt_stride,
+                  const int64_t *pt0, const int64_t *chat, const int64_t *ext, int64_t *s, int64_t *scratch, int64_t scratch_words,
+                  const LfInvTab &it, const LfMod &m, hipStream_t st) {
+    const int nr = key.n;
+    if (!gathered_args_ok(key, p_host, nparts, rows, &it, m) || (nr == 0 && !pt0) || (nr && !pt) || !chat || ell < 0 || ell > rows)
         return LF_ERR_ARG;
-    if (rows < 1 || rows > MAX_LIST_ROWS || !lf_fp64_digits_ok(nparts, rows, q_host)) return LF_ERR_ARG;
-    for (int i = 0; i < nr; ++i)
-        if (!ksk[i] || !pt || (key_format == LF_KEY_PLANES && ((((uintptr_t)ksk[i] | (uintptr_t)(part_stride * 8) | (uintptr_t)(comp_stride * 8)) & 15))))
-            return LF_ERR_ARG;
-    const int tl = NTT_TILE_LOG_MAX, S1 = logN - tl;
-    RowList dp, in;
-    classify_rows(rows, q_host, dp, in);
-    const bool mixed = dp.n && in.n;
-    const bool dplanes = digit_planes(logN, dp, in);
-    const bool cols_last = S1 <= 4 || (S1 == 5 && mixed && g_ks_ext_cols_max > 4);
-    if (nr)   // the digits must be in the format the groups read (see ks_tail)
-        if (int e = lf_fmt_expect(ext, ((size_t)nparts * rows << logN) * 8, dplanes ? LF_FMT_PLANES : LF_FMT_RAW)) return e;
-    const bool spl = dplanes && (g_more_planes & 1) && cols_last && scratch && scratch_words >= ((int64_t)2 * rows << logN);
-    const dim3 grid((unsigned)((((i64)1 << logN) + 511) / 512), (unsigned)rows);
-    const bool planes = key_format == LF_KEY_PLANES;
-#define LF_LT_LAUNCH(NR, PL, DPLB)                                                                                         \
-    hipLaunchKernelGGL((ks_inner_lt_kernel<NR, PL, DPLB>), grid, dim3(256), 0, st, (const i64 *)ext, la, (i64)part_stride,  \
-                       (i64)comp_stride, (i64)row_off, (i64 *)s, nparts, rows, logN, spl ? 1 : 0, (const i64 *)ql, (const i64 *)qh, \
-                       (const i64 *)kl, (const i64 *)kh)
-#define LF_LT_CASE(NR)                                                                                                     \
-    case NR:                                                                                                               \
-        if (planes && dplanes) LF_LT_LAUNCH(NR, true, true);                                                              \
-        else if (planes) LF_LT_LAUNCH(NR, true, false);                                                                   \
-        else if (dplanes) LF_LT_LAUNCH(NR, false, true);                                                                  \
-        else LF_LT_LAUNCH(NR, false, false);                                                                              \
-        break;
+    const KsSums ks = ks_sums(logN, rows, m.q_host, 1, scratch, scratch_words);
+    if (nr)   // (without keys nothing reads the digits)
+        if (int e = ks.expect_digits(ext, 1, nparts)) return e;
     for (int i0 = 0; i0 < nr || i0 == 0;) {
-        const int left = nr - i0, g = left >= 4 ? 4 : left >= 2 ? 2 : left;
+        const int g = key_group(nr - i0);
         LtArgs la{};
-        for (int t = 0; t < g; ++t) {
-            la.hk.ksk[t] = (const i64 *)ksk[i0 + t];
-            la.hk.p[t] = (unsigned)p_host[i0 + t];
-            la.pt[t] = (const i64 *)pt + (i64)(i0 + t) * pt_stride;
-        }
+        la.hk = hoist_keys(key, p_host, i0, g);
+        for (int t = 0; t < g; ++t) la.pt[t] = (const i64 *)pt + (i64)(i0 + t) * pt_stride;
         la.pt0 = (const i64 *)pt0, la.chat = (const i64 *)chat, la.ell = ell, la.first = i0 == 0;
-        switch (g) {
-            LF_LT_CASE(1) LF_LT_CASE(2) LF_LT_CASE(4)
-            case 0: LF_LT_LAUNCH(0, false, false); break;
-        }
+        auto launch = [&](auto NR, auto PL, auto DPL) {
+            hipLaunchKernelGGL((ks_inner_lt_kernel<LF_CT(NR), LF_CT(PL), LF_CT(DPL)>), ks.grid, dim3(256), 0, st, (const i64 *)ext, la,
+                               (i64)key.part_stride, (i64)key.comp_stride, (i64)key.row_off, (i64 *)s, nparts, rows, logN, ks.spl ? 1 : 0,
+                               LF_MOD_ARGS(m));
+        };
+        if (!g) launch(std::integral_constant<int, 0>{}, std::false_type{}, std::false_type{});   // (no key: no format to tell apart)
+        with_count<1, 2, 4>(g, [&](auto NR) {
+            with_formats(key.key_format == LF_KEY_PLANES, ks.dplanes, [&](auto PL, auto DPL) { launch(NR, PL, DPL); });
+        });
         i0 += g ? g : 1;
     }
-#undef LF_LT_LAUNCH
-#undef LF_LT_CASE
-    return ks_inv_sums(2, rows, logN, spl, cols_last, mixed, in, dp, (i64 *)scratch, (i64 *)s, ipsi_br, ipsi_dp, Ninv, ql, qh, kl, kh, st);
+    return ks_inv_sums(ks, (i64 *)scratch, (i64 *)s, it, m, st);
 }
 
 // The key-dependent part of lf_linear_transform_batch (ckks_ops.hip) for nct (2 or 4) ciphertexts: per LF_LTB_KEYS keys ONE launch
-// of ks_inner_ltb_kernel over the ciphertexts' extended digits ext [nct][nparts][rows][N] (nr = 0: the step-0 term alone, one
+// of ks_inner_ltb_kernel over the ciphertexts' extended digits ext [nct][nparts][rows][N] (no keys: the step-0 term alone, one
 // launch without keys), all of them adding into the nct pairs of sums s [nct][2][rows][N]; then ONE inverse transform of the
 // 2 nct polynomials.  `scratch` (>= 2 nct rows N words, or NULL: the sums stay raw words, same outputs) as in lf_ks_tail_lt.
 // Ciphertext t's c^ = P NTT(c0), P NTT(c1) on the `ell` ordinary rows at chat + t * chat_stride.  Internal: ckks_ops.hip checks
-// the arguments (nr >= 0, odd exponents below 2N, pt0 != NULL when nr == 0).
-int lf_ks_tail_ltb(int nct, int nr, const int64_t *p_host, int nparts, int rows, int ell, int logN, const int64_t *const *ksk,
-                   int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format, const int64_t *pt, int64_t pt_stride,
-                   const int64_t *pt0, const int64_t *chat, int64_t chat_stride, const int64_t *ext, int64_t *s, int64_t *scratch,
-                   int64_t scratch_words, const int64_t *ipsi_br, const double *ipsi_dp, const int64_t *Ninv, const int64_t *q_host,
-                   const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st) {
-    if ((nct != 2 && nct != 4) || !ipsi_dp || (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES) || nr < 0 || (nr == 0 && !pt0) ||
-        !chat || !ext || !s || ell < 0 || ell > rows || nparts < 1 || logN <= NTT_TILE_LOG_MAX || logN > KS_LOGN_MAX ||
-        (nr && (!ksk || !p_host || !pt)))
+// the arguments (odd exponents below 2N, pt0 != NULL without keys).
+int lf_ks_tail_ltb(int nct, const int64_t *p_host, int nparts, int rows, int ell, int logN, const LfKeys &key, const int64_t *pt,
+                   int64_t pt_stride, const int64_t *pt0, const int64_t *chat, int64_t chat_stride, const int64_t *ext, int64_t *s,
+                   int64_t *scratch, int64_t scratch_words, const LfInvTab &it, const LfMod &m, hipStream_t st) {
+    const int nr = key.n;
+    if ((nct != 2 && nct != 4) || !gathered_args_ok(key, p_host, nparts, rows, &it, m) || (nr == 0 && !pt0) || (nr && !pt) || !chat ||
+        !ext || !s || ell < 0 || ell > rows || nparts < 1 || logN <= NTT_TILE_LOG_MAX || logN > KS_LOGN_MAX)
         return LF_ERR_ARG;
-    if (rows < 1 || rows > MAX_LIST_ROWS || !lf_fp64_digits_ok(nparts, rows, q_host)) return LF_ERR_ARG;
-    for (int i = 0; i < nr; ++i)
-        if (!ksk[i] || (key_format == LF_KEY_PLANES && ((((uintptr_t)ksk[i] | (uintptr_t)(part_stride * 8) | (uintptr_t)(comp_stride * 8)) & 15))))
-            return LF_ERR_ARG;
-    const int tl = NTT_TILE_LOG_MAX, S1 = logN - tl;
-    RowList dp, in;
-    classify_rows(rows, q_host, dp, in);
-    const bool mixed = dp.n && in.n;
-    const bool dplanes = digit_planes(logN, dp, in);
-    const bool cols_last = S1 <= 4 || (S1 == 5 && mixed && g_ks_ext_cols_max > 4);
-    if (nr)   // the digits must be in the format the launches read (see ks_tail)
-        if (int e = lf_fmt_expect(ext, ((size_t)nct * nparts * rows << logN) * 8, dplanes ? LF_FMT_PLANES : LF_FMT_RAW)) return e;
-    const bool spl = dplanes && (g_more_planes & 1) && cols_last && scratch && scratch_words >= ((int64_t)2 * nct * rows << logN);
-    const dim3 grid((unsigned)((((i64)1 << logN) + 511) / 512), (unsigned)rows);
-    const bool planes = key_format == LF_KEY_PLANES;
-#define LF_LTB_LAUNCH(NCT, PL, DPLB)                                                                                          \
-    hipLaunchKernelGGL((ks_inner_ltb_kernel<NCT, 1, PL, DPLB>), grid, dim3(256), 0, st, (const i64 *)ext, la, (i64)part_stride, \
-                       (i64)comp_stride, (i64)row_off, (i64 *)s, nparts, rows, logN, spl ? 1 : 0, (const i64 *)ql, (const i64 *)qh, \
-                       (const i64 *)kl, (const i64 *)kh)
-#define LF_LTB_CASE(NCT)                                                                                                      \
-    if (planes && dplanes) LF_LTB_LAUNCH(NCT, true, true);                                                                    \
-    else if (planes) LF_LTB_LAUNCH(NCT, true, false);                                                                         \
-    else if (dplanes) LF_LTB_LAUNCH(NCT, false, true);                                                                        \
-    else LF_LTB_LAUNCH(NCT, false, false)
+    const KsSums ks = ks_sums(logN, rows, m.q_host, nct, scratch, scratch_words);
+    if (nr)
+        if (int e = ks.expect_digits(ext, nct, nparts)) return e;
     for (int i0 = 0; i0 < nr || i0 == 0; i0 += LF_LTB_KEYS) {
         const int g = nr - i0 < LF_LTB_KEYS ? nr - i0 : LF_LTB_KEYS;
         LtbArgs la{};
         for (int t = 0; t < g; ++t) {
-            la.ksk[t] = (const i64 *)ksk[i0 + t];
+            la.ksk[t] = (const i64 *)key.ksk[i0 + t];
             la.p[t] = (unsigned)p_host[i0 + t];
             la.pt[t] = (const i64 *)pt + (i64)(i0 + t) * pt_stride;
         }
         la.pt0 = (const i64 *)pt0, la.chat = (const i64 *)chat, la.chat_stride = (i64)chat_stride;
         la.ext_stride = ((i64)nparts * rows) << logN, la.sum_stride = ((i64)2 * rows) << logN;
         la.nk = g, la.ell = ell, la.first = i0 == 0;
-        if (nct == 2) {
-            LF_LTB_CASE(2);
-        } else {
-            LF_LTB_CASE(4);
-        }
+        with_count<2, 4>(nct, [&](auto NCT) {
+            with_formats(key.key_format == LF_KEY_PLANES, ks.dplanes, [&](auto PL, auto DPL) {
+                hipLaunchKernelGGL((ks_inner_ltb_kernel<LF_CT(NCT), 1, LF_CT(PL), LF_CT(DPL)>), ks.grid, dim3(256), 0, st, (const i64 *)ext,
+                                   la, (i64)key.part_stride, (i64)key.comp_stride, (i64)key.row_off, (i64 *)s, nparts, rows, logN,
+                                   ks.spl ? 1 : 0, LF_MOD_ARGS(m));
+            });
+        });
     }
-#undef LF_LTB_LAUNCH
-#undef LF_LTB_CASE
-    return ks_inv_sums(2 * nct, rows, logN, spl, cols_last, mixed, in, dp, (i64 *)scratch, (i64 *)s, ipsi_br, ipsi_dp, Ninv, ql, qh, kl,
-                       kh, st);
+    return ks_inv_sums(ks, (i64 *)scratch, (i64 *)s, it, m, st);
 }
 
-// The key-dependent part of lf_rotate_sum (ckks_ops.hip): per group of up to 4 keys ONE launch of ks_inner_rsum_kernel over the
-// shared extended digits `ext` (nr = 0: the self term alone, one launch without keys), all of them adding into the one pair of
-// sums s [2][rows][N]; then the inverse transform of that pair.  `scratch` as in lf_ks_tail_lt.  chat = P NTT(c0), P NTT(c1) on
-// the `ell` ordinary rows (c1 only with `with_self`).  Internal: ckks_ops.hip checks the arguments (nr >= 0, odd exponents below
-// 2N, with_self when nr == 0).
-int lf_ks_tail_rsum(int nr, const int64_t *p_host, int nparts, int rows, int ell, int logN, const int64_t *const *ksk, int64_t part_stride,
-                    int64_t comp_stride, int64_t row_off, int key_format, int with_self, const int64_t *chat, const int64_t *ext,
-                    int64_t *s, int64_t *scratch, int64_t scratch_words, const int64_t *ipsi_br, const double *ipsi_dp,
-                    const int64_t *Ninv, const int64_t *q_host, const int64_t *ql, const int64_t *qh, const int64_t *kl,
-                    const int64_t *kh, hipStream_t st) {
-    if (!ipsi_dp || (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES) || nr < 0 || (nr == 0 && !with_self) || !chat || ell < 0 ||
-        ell > rows || (nr && (!ksk || !p_host)))
-        return LF_ERR_ARG;
-    if (rows < 1 || rows > MAX_LIST_ROWS || !lf_fp64_digits_ok(nparts, rows, q_host)) return LF_ERR_ARG;
-    for (int i = 0; i < nr; ++i)
-        if (!ksk[i] || (key_format == LF_KEY_PLANES && ((((uintptr_t)ksk[i] | (uintptr_t)(part_stride * 8) | (uintptr_t)(comp_stride * 8)) & 15))))
-            return LF_ERR_ARG;
-    const int tl = NTT_TILE_LOG_MAX, S1 = logN - tl;
-    RowList dp, in;
-    classify_rows(rows, q_host, dp, in);
-    const bool mixed = dp.n && in.n;
-    const bool dplanes = digit_planes(logN, dp, in);
-    const bool cols_last = S1 <= 4 || (S1 == 5 && mixed && g_ks_ext_cols_max > 4);
-    if (nr)   // the digits must be in the format the groups read (see ks_tail)
-        if (int e = lf_fmt_expect(ext, ((size_t)nparts * rows << logN) * 8, dplanes ? LF_FMT_PLANES : LF_FMT_RAW)) return e;
-    const bool spl = dplanes && (g_more_planes & 1) && cols_last && scratch && scratch_words >= ((int64_t)2 * rows << logN);
-    const dim3 grid((unsigned)((((i64)1 << logN) + 511) / 512), (unsigned)rows);
-    const bool planes = key_format == LF_KEY_PLANES;
-#define LF_RSUM_LAUNCH(NR, PL, DPLB)                                                                                        \
-    hipLaunchKernelGGL((ks_inner_rsum_kernel<NR, PL, DPLB>), grid, dim3(256), 0, st, (const i64 *)ext, ra, (i64)part_stride, \
-                       (i64)comp_stride, (i64)row_off, (i64 *)s, nparts, rows, logN, spl ? 1 : 0, (const i64 *)ql, (const i64 *)qh, \
-                       (const i64 *)kl, (const i64 *)kh)
-#define LF_RSUM_CASE(NR)                                                                                                   \
-    case NR:                                                                                                               \
-        if (planes && dplanes) LF_RSUM_LAUNCH(NR, true, true);                                                            \
-        else if (planes) LF_RSUM_LAUNCH(NR, true, false);                                                                 \
-        else if (dplanes) LF_RSUM_LAUNCH(NR, false, true);                                                                \
-        else LF_RSUM_LAUNCH(NR, false, false);                                                                            \
-        break;
+// The key-dependent part of lf_rotate_sum (ckks_ops.hip): per group of up to 4 keys (key_group) ONE launch of ks_inner_rsum_kernel
+// over the shared extended digits `ext` (no keys: the self term alone, one launch without keys), all of them adding into the one
+// pair of sums s [2][rows][N]; then the inverse transform of that pair.  `scratch` as in lf_ks_tail_lt.  chat = P NTT(c0),
+// P NTT(c1) on the `ell` ordinary rows (c1 only with `with_self`).  Internal: ckks_ops.hip checks the arguments (odd exponents
+// below 2N, with_self without keys).
+int lf_ks_tail_rsum(const int64_t *p_host, int nparts, int rows, int ell, int logN, const LfKeys &key, int with_self, const int64_t *chat,
+                    const int64_t *ext, int64_t *s, int64_t *scratch, int64_t scratch_words, const LfInvTab &it, const LfMod &m,
+                    hipStream_t st) {
+    const int nr = key.n;
+    if (!gathered_args_ok(key, p_host, nparts, rows, &it, m) || (nr == 0 && !with_self) || !chat || ell < 0 || ell > rows) return LF_ERR_ARG;
+    const KsSums ks = ks_sums(logN, rows, m.q_host, 1, scratch, scratch_words);
+    if (nr)
+        if (int e = ks.expect_digits(ext, 1, nparts)) return e;
     for (int i0 = 0; i0 < nr || i0 == 0;) {
-        const int left = nr - i0, g = left >= 4 ? 4 : left >= 2 ? 2 : left;
+        const int g = key_group(nr - i0);
         RsumArgs ra{};
-        for (int t = 0; t < g; ++t) {
-            ra.hk.ksk[t] = (const i64 *)ksk[i0 + t];
-            ra.hk.p[t] = (unsigned)p_host[i0 + t];
-        }
+        ra.hk = hoist_keys(key, p_host, i0, g);
         ra.chat = (const i64 *)chat, ra.ell = ell, ra.first = i0 == 0, ra.self = with_self ? 1 : 0;
-        switch (g) {
-            LF_RSUM_CASE(1) LF_RSUM_CASE(2) LF_RSUM_CASE(4)
-            case 0: LF_RSUM_LAUNCH(0, false, false); break;
-        }
+        auto launch = [&](auto NR, auto PL, auto DPL) {
+            hipLaunchKernelGGL((ks_inner_rsum_kernel<LF_CT(NR), LF_CT(PL), LF_CT(DPL)>), ks.grid, dim3(256), 0, st, (const i64 *)ext, ra,
+                               (i64)key.part_stride, (i64)key.comp_stride, (i64)key.row_off, (i64 *)s, nparts, rows, logN, ks.spl ? 1 : 0,
+                               LF_MOD_ARGS(m));
+        };
+        if (!g) launch(std::integral_constant<int, 0>{}, std::false_type{}, std::false_type{});
+        with_count<1, 2, 4>(g, [&](auto NR) {
+            with_formats(key.key_format == LF_KEY_PLANES, ks.dplanes, [&](auto PL, auto DPL) { launch(NR, PL, DPL); });
+        });
         i0 += g ? g : 1;
     }
-#undef LF_RSUM_LAUNCH
-#undef LF_RSUM_CASE
-    return ks_inv_sums(2, rows, logN, spl, cols_last, mixed, in, dp, (i64 *)scratch, (i64 *)s, ipsi_br, ipsi_dp, Ninv, ql, qh, kl, kh, st);
+    return ks_inv_sums(ks, (i64 *)scratch, (i64 *)s, it, m, st);
 }
 
 // The key-dependent part of lf_rotate_sum_batch (ckks_ops.hip) for nct (2 or 4) ciphertexts: per LF_RSB_KEYS keys ONE launch of
-// ks_inner_rsumb_kernel over the ciphertexts' extended digits ext [nct][nparts][rows][N] (nr = 0: the self term alone, one launch
+// ks_inner_rsumb_kernel over the ciphertexts' extended digits ext [nct][nparts][rows][N] (no keys: the self term alone, one launch
 // without keys), all of them adding into the nct pairs of sums s [nct][2][rows][N]; then ONE inverse transform of the 2 nct
 // polynomials.  `scratch` (>= 2 nct rows N words, or NULL: the sums stay raw words, same outputs) as in lf_ks_tail_lt.
 // Ciphertext t's c^ = P NTT(c0), P NTT(c1) on the `ell` ordinary rows at chat + t * chat_stride (c1 only with `with_self`).
-// Internal: ckks_ops.hip checks the arguments (nr >= 0, odd exponents below 2N, with_self when nr == 0).
-int lf_ks_tail_rsumb(int nct, int nr, const int64_t *p_host, int nparts, int rows, int ell, int logN, const int64_t *const *ksk,
-                     int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format, int with_self, const int64_t *chat,
-                     int64_t chat_stride, const int64_t *ext, int64_t *s, int64_t *scratch, int64_t scratch_words,
-                     const int64_t *ipsi_br, const double *ipsi_dp, const int64_t *Ninv, const int64_t *q_host, const int64_t *ql,
-                     const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st) {
-    if ((nct != 2 && nct != 4) || !ipsi_dp || (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES) || nr < 0 ||
-        (nr == 0 && !with_self) || !chat || !ext || !s || ell < 0 || ell > rows || nparts < 1 || logN <= NTT_TILE_LOG_MAX ||
-        logN > KS_LOGN_MAX || (nr && (!ksk || !p_host)))
+// Internal: ckks_ops.hip checks the arguments (odd exponents below 2N, with_self without keys).
+int lf_ks_tail_rsumb(int nct, const int64_t *p_host, int nparts, int rows, int ell, int logN, const LfKeys &key, int with_self,
+                     const int64_t *chat, int64_t chat_stride, const int64_t *ext, int64_t *s, int64_t *scratch, int64_t scratch_words,
+                     const LfInvTab &it, const LfMod &m, hipStream_t st) {
+    const int nr = key.n;
+    if ((nct != 2 && nct != 4) || !gathered_args_ok(key, p_host, nparts, rows, &it, m) || (nr == 0 && !with_self) || !chat || !ext || !s ||
+        ell < 0 || ell > rows || nparts < 1 || logN <= NTT_TILE_LOG_MAX || logN > KS_LOGN_MAX)
         return LF_ERR_ARG;
-    if (rows < 1 || rows > MAX_LIST_ROWS || !lf_fp64_digits_ok(nparts, rows, q_host)) return LF_ERR_ARG;
-    for (int i = 0; i < nr; ++i)
-        if (!ksk[i] || (key_format == LF_KEY_PLANES && ((((uintptr_t)ksk[i] | (uintptr_t)(part_stride * 8) | (uintptr_t)(comp_stride * 8)) & 15))))
-            return LF_ERR_ARG;
-    const int tl = NTT_TILE_LOG_MAX, S1 = logN - tl;
-    RowList dp, in;
-    classify_rows(rows, q_host, dp, in);
-    const bool mixed = dp.n && in.n;
-    const bool dplanes = digit_planes(logN, dp, in);
-    const bool cols_last = S1 <= 4 || (S1 == 5 && mixed && g_ks_ext_cols_max > 4);
-    if (nr)   // the digits must be in the format the launches read (see ks_tail)
-        if (int e = lf_fmt_expect(ext, ((size_t)nct * nparts * rows << logN) * 8, dplanes ? LF_FMT_PLANES : LF_FMT_RAW)) return e;
-    const bool spl = dplanes && (g_more_planes & 1) && cols_last && scratch && scratch_words >= ((int64_t)2 * nct * rows << logN);
-    const dim3 grid((unsigned)((((i64)1 << logN) + 511) / 512), (unsigned)rows);
-    const bool planes = key_format == LF_KEY_PLANES;
-#define LF_RSB_LAUNCH(NCT, PL, DPLB)                                                                                         \
-    hipLaunchKernelGGL((ks_inner_rsumb_kernel<NCT, PL, DPLB>), grid, dim3(256), 0, st, (const i64 *)ext, ra, (i64)part_stride, \
-                       (i64)comp_stride, (i64)row_off, (i64 *)s, nparts, rows, logN, spl ? 1 : 0, (const i64 *)ql, (const i64 *)qh, \
-                       (const i64 *)kl, (const i64 *)kh)
-#define LF_RSB_CASE(NCT)                                                                                                     \
-    if (planes && dplanes) LF_RSB_LAUNCH(NCT, true, true);                                                                   \
-    else if (planes) LF_RSB_LAUNCH(NCT, true, false);                                                                        \
-    else if (dplanes) LF_RSB_LAUNCH(NCT, false, true);                                                                       \
-    else LF_RSB_LAUNCH(NCT, false, false)
+    const KsSums ks = ks_sums(logN, rows, m.q_host, nct, scratch, scratch_words);
+    if (nr)
+        if (int e = ks.expect_digits(ext, nct, nparts)) return e;
     for (int i0 = 0; i0 < nr || i0 == 0; i0 += LF_RSB_KEYS) {
         const int g = nr - i0 < LF_RSB_KEYS ? nr - i0 : LF_RSB_KEYS;
         RsbArgs ra{};
         for (int t = 0; t < g; ++t) {
-            ra.ksk[t] = (const i64 *)ksk[i0 + t];
+            ra.ksk[t] = (const i64 *)key.ksk[i0 + t];
             ra.p[t] = (unsigned)p_host[i0 + t];
         }
         ra.chat = (const i64 *)chat, ra.chat_stride = (i64)chat_stride;
         ra.ext_stride = ((i64)nparts * rows) << logN, ra.sum_stride = ((i64)2 * rows) << logN;
         ra.nk = g, ra.ell = ell, ra.first = i0 == 0, ra.self = with_self ? 1 : 0;
-        if (nct == 2) {
-            LF_RSB_CASE(2);
-        } else {
-            LF_RSB_CASE(4);
-        }
+        with_count<2, 4>(nct, [&](auto NCT) {
+            with_formats(key.key_format == LF_KEY_PLANES, ks.dplanes, [&](auto PL, auto DPL) {
+                hipLaunchKernelGGL((ks_inner_rsumb_kernel<LF_CT(NCT), LF_CT(PL), LF_CT(DPL)>), ks.grid, dim3(256), 0, st, (const i64 *)ext,
+                                   ra, (i64)key.part_stride, (i64)key.comp_stride, (i64)key.row_off, (i64 *)s, nparts, rows, logN,
+                                   ks.spl ? 1 : 0, LF_MOD_ARGS(m));
+            });
+        });
     }
-#undef LF_RSB_LAUNCH
-#undef LF_RSB_CASE
-    return ks_inv_sums(2 * nct, rows, logN, spl, cols_last, mixed, in, dp, (i64 *)scratch, (i64 *)s, ipsi_br, ipsi_dp, Ninv, ql, qh, kl,
-                       kh, st);
+    return ks_inv_sums(ks, (i64 *)scratch, (i64 *)s, it, m, st);
 }
 
 // ---- the launches of lf_linear_transform_bsgs (ckks_ops.hip checks the arguments and owns the order) ----
-namespace {
-bool key_args_ok(const int64_t *ksk, int64_t part_stride, int64_t comp_stride, int key_format) {
-    if (!ksk || (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES)) return false;
-    return key_format != LF_KEY_PLANES || !((((uintptr_t)ksk | (uintptr_t)(part_stride * 8) | (uintptr_t)(comp_stride * 8)) & 15));
-}
-}  // namespace
-
 // baby steps: key i's gathered sums over the shared digits `ext`, + chat0 gathered on the ordinary rows, into u + i * 2 rows N
-int lf_ks_baby_sums(int nr, const int64_t *p_host, int nparts, int rows, int ell, int logN, const int64_t *const *ksk, int64_t part_stride,
-                    int64_t comp_stride, int64_t row_off, int key_format, const int64_t *chat0, const int64_t *ext, int64_t *u,
-                    const int64_t *q_host, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st) {
-    if (nr < 0 || !chat0 || !u || ell < 0 || ell > rows) return LF_ERR_ARG;
-    if (rows < 1 || rows > MAX_LIST_ROWS || !lf_fp64_digits_ok(nparts, rows, q_host)) return LF_ERR_ARG;
-    for (int i = 0; i < nr; ++i)
-        if (!key_args_ok(ksk[i], part_stride, comp_stride, key_format)) return LF_ERR_ARG;
+int lf_ks_baby_sums(const int64_t *p_host, int nparts, int rows, int ell, int logN, const LfKeys &key, const int64_t *chat0,
+                    const int64_t *ext, int64_t *u, const LfMod &m, hipStream_t st) {
+    const int nr = key.n;
+    if (!gathered_args_ok(key, p_host, nparts, rows, nullptr, m) || !chat0 || !u || ell < 0 || ell > rows) return LF_ERR_ARG;
     if (!nr) return 0;
-    RowList dp, in;
-    classify_rows(rows, q_host, dp, in);
-    const bool dplanes = digit_planes(logN, dp, in);
-    if (int e = lf_fmt_expect(ext, ((size_t)nparts * rows << logN) * 8, dplanes ? LF_FMT_PLANES : LF_FMT_RAW)) return e;
-    const dim3 grid((unsigned)((((i64)1 << logN) + 511) / 512), (unsigned)rows);
-    const bool planes = key_format == LF_KEY_PLANES;
+    const KsSums ks = ks_sums(logN, rows, m.q_host, 0, nullptr, 0);
+    if (int e = ks.expect_digits(ext, 1, nparts)) return e;
     const i64 pair = (i64)2 * rows << logN;
-#define LF_BABY_LAUNCH(NR, PL, DPLB)                                                                                        \
-    hipLaunchKernelGGL((ks_inner_baby_kernel<NR, PL, DPLB>), grid, dim3(256), 0, st, (const i64 *)ext, ba, (i64)part_stride, \
-                       (i64)comp_stride, (i64)row_off, nparts, rows, logN, (const i64 *)ql, (const i64 *)qh, (const i64 *)kl, \
-                       (const i64 *)kh)
-#define LF_BABY_CASE(NR)                                                                                                   \
-    case NR:                                                                                                               \
-        if (planes && dplanes) LF_BABY_LAUNCH(NR, true, true);                                                            \
-        else if (planes) LF_BABY_LAUNCH(NR, true, false);                                                                 \
-        else if (dplanes) LF_BABY_LAUNCH(NR, false, true);                                                                \
-        else LF_BABY_LAUNCH(NR, false, false);                                                                            \
-        break;
     for (int i0 = 0; i0 < nr;) {
-        const int left = nr - i0, g = left >= 4 ? 4 : left >= 2 ? 2 : 1;
+        const int g = key_group(nr - i0);
         BabyArgs ba{};
-        for (int t = 0; t < g; ++t) {
-            ba.hk.ksk[t] = (const i64 *)ksk[i0 + t];
-            ba.hk.p[t] = (unsigned)p_host[i0 + t];
-            ba.u[t] = (i64 *)u + (i64)(i0 + t) * pair;
-        }
+        ba.hk = hoist_keys(key, p_host, i0, g);
+        for (int t = 0; t < g; ++t) ba.u[t] = (i64 *)u + (i64)(i0 + t) * pair;
         ba.chat0 = (const i64 *)chat0, ba.ell = ell;
-        switch (g) { LF_BABY_CASE(1) LF_BABY_CASE(2) LF_BABY_CASE(4) }
+        with_count<1, 2, 4>(g, [&](auto NR) {
+            with_formats(key.key_format == LF_KEY_PLANES, ks.dplanes, [&](auto PL, auto DPL) {
+                hipLaunchKernelGGL((ks_inner_baby_kernel<LF_CT(NR), LF_CT(PL), LF_CT(DPL)>), ks.grid, dim3(256), 0, st, (const i64 *)ext, ba,
+                                   (i64)key.part_stride, (i64)key.comp_stride, (i64)key.row_off, nparts, rows, logN, LF_MOD_ARGS(m));
+            });
+        });
         i0 += g;
     }
-#undef LF_BABY_LAUNCH
-#undef LF_BABY_CASE
     return (int)hipGetLastError();
 }
 
 // diagonal products of ng (1, 2 or 4) giant steps: out[i] = sum over the set bits t of slots[i] of pt[i][k-th diagonal] * u[t]
 int lf_lt_diag_products(int ng, const int64_t *u, int nslots, const int64_t *const *pt, const unsigned long long *slots, int64_t pt_stride,
-                        int64_t *const *out, int rows, int logN, const int64_t *ql, const int64_t *qh, const int64_t *kl,
-                        const int64_t *kh, hipStream_t st) {
+                        int64_t *const *out, int rows, int logN, const LfMod &m, hipStream_t st) {
     if ((ng != 1 && ng != 2 && ng != 4) || !u || nslots < 1 || nslots > 64) return LF_ERR_ARG;
     DiagArgs da{};
     da.u = (const i64 *)u, da.pt_stride = (i64)pt_stride, da.nslots = nslots;
@@ -3362,8 +3218,7 @@ int lf_lt_diag_products(int ng, const int64_t *u, int nslots, const int64_t *con
     }
     const dim3 grid((unsigned)((((i64)1 << logN) + 511) / 512), (unsigned)rows);
 #define LF_DIAG_LAUNCH(NG)                                                                                                 \
-    hipLaunchKernelGGL((lt_diag_products_kernel<NG>), grid, dim3(256), 0, st, da, rows, logN, (const i64 *)ql, (const i64 *)qh, \
-                       (const i64 *)kl, (const i64 *)kh)
+    hipLaunchKernelGGL((lt_diag_products_kernel<NG>), grid, dim3(256), 0, st, da, rows, logN, LF_MOD_ARGS(m))
     switch (ng) {
         case 1: LF_DIAG_LAUNCH(1); break;
         case 2: LF_DIAG_LAUNCH(2); break;
@@ -3377,8 +3232,8 @@ int lf_lt_diag_products(int ng, const int64_t *u, int nslots, const int64_t *con
 // block products of no (1, 2 or 4) outputs over one input's pairs u: out[i] (+)= sum over the set bits t of slots[i] of
 // pt[i][k-th diagonal] * u[t]; fresh[i] != 0 writes out[i], 0 adds to it
 int lf_lt_block_products(int no, const int64_t *u, int nslots, const int64_t *const *pt, const unsigned long long *slots,
-                         const int64_t *pt_stride, int64_t *const *out, const int *fresh, int rows, int logN, const int64_t *ql,
-                         const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st) {
+                         const int64_t *pt_stride, int64_t *const *out, const int *fresh, int rows, int logN, const LfMod &m,
+                         hipStream_t st) {
     if ((no != 1 && no != 2 && no != 4) || !u || nslots < 1 || nslots > 64 || rows < 1 || rows > 65535) return LF_ERR_ARG;
     BlockArgs ba{};
     ba.u = (const i64 *)u, ba.nslots = nslots;
@@ -3389,8 +3244,7 @@ int lf_lt_block_products(int no, const int64_t *u, int nslots, const int64_t *co
     }
     const dim3 grid((unsigned)((((i64)1 << logN) + 511) / 512), (unsigned)rows);
 #define LF_BLOCK_LAUNCH(NO)                                                                                                 \
-    hipLaunchKernelGGL((lt_block_products_kernel<NO>), grid, dim3(256), 0, st, ba, rows, logN, (const i64 *)ql, (const i64 *)qh, \
-                       (const i64 *)kl, (const i64 *)kh)
+    hipLaunchKernelGGL((lt_block_products_kernel<NO>), grid, dim3(256), 0, st, ba, rows, logN, LF_MOD_ARGS(m))
     switch (no) {
         case 1: LF_BLOCK_LAUNCH(1); break;
         case 2: LF_BLOCK_LAUNCH(2); break;
@@ -3405,8 +3259,7 @@ int lf_lt_block_products(int no, const int64_t *u, int nslots, const int64_t *co
 // out[i] + k * out_tstride.  One launch of lt_block_productsb_kernel<no, 2> per tile of 2 tokens: a diagonal word is read once per tile
 int lf_lt_block_productsb(int nt, int no, const int64_t *u, int64_t u_tstride, int nslots, const int64_t *const *pt,
                           const unsigned long long *slots, const int64_t *pt_stride, int64_t *const *out, int64_t out_tstride,
-                          const int *fresh, int rows, int logN, const int64_t *ql, const int64_t *qh, const int64_t *kl,
-                          const int64_t *kh, hipStream_t st) {
+                          const int *fresh, int rows, int logN, const LfMod &m, hipStream_t st) {
     if ((nt != 2 && nt != 4) || (no != 1 && no != 2 && no != 4) || !u || nslots < 1 || nslots > 64 || rows < 1 || rows > 65535)
         return LF_ERR_ARG;
     const int64_t pair = (2 * (int64_t)rows) << logN;
@@ -3419,8 +3272,7 @@ int lf_lt_block_productsb(int nt, int no, const int64_t *u, int64_t u_tstride, i
     }
     const dim3 grid((unsigned)((((i64)1 << logN) + 511) / 512), (unsigned)rows);
 #define LF_BLOCKB_LAUNCH(NO)                                                                                                    \
-    hipLaunchKernelGGL((lt_block_productsb_kernel<NO, 2>), grid, dim3(256), 0, st, ba, rows, logN, (const i64 *)ql, (const i64 *)qh, \
-                       (const i64 *)kl, (const i64 *)kh)
+    hipLaunchKernelGGL((lt_block_productsb_kernel<NO, 2>), grid, dim3(256), 0, st, ba, rows, logN, LF_MOD_ARGS(m))
     for (int t0 = 0; t0 < nt; t0 += 2) {
         ba.u = (const i64 *)u + t0 * u_tstride;
         for (int i = 0; i < no; ++i) ba.out[i] = (i64 *)out[i] + t0 * out_tstride;
@@ -3435,82 +3287,62 @@ int lf_lt_block_productsb(int nt, int no, const int64_t *u, int64_t u_tstride, i
 }
 
 // giant step: acc += (sum over the parts of `ext` gathered by pi_p times the key part, + s0 gathered on all rows on component 0)
-int lf_ks_giant_sums(int64_t p, int nparts, int rows, int logN, const int64_t *ksk, int64_t part_stride, int64_t comp_stride,
-                     int64_t row_off, int key_format, const int64_t *ext, const int64_t *s0, int64_t *acc, const int64_t *q_host,
-                     const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st) {
-    if (!key_args_ok(ksk, part_stride, comp_stride, key_format) || !s0 || !acc) return LF_ERR_ARG;
-    if (rows < 1 || rows > MAX_LIST_ROWS || !lf_fp64_digits_ok(nparts, rows, q_host)) return LF_ERR_ARG;
-    RowList dp, in;
-    classify_rows(rows, q_host, dp, in);
-    const bool dplanes = digit_planes(logN, dp, in);
-    if (int e = lf_fmt_expect(ext, ((size_t)nparts * rows << logN) * 8, dplanes ? LF_FMT_PLANES : LF_FMT_RAW)) return e;
+int lf_ks_giant_sums(int64_t p, int nparts, int rows, int logN, const LfKeys &key, const int64_t *ext, const int64_t *s0, int64_t *acc,
+                     const LfMod &m, hipStream_t st) {
+    if (key.n != 1 || !gathered_args_ok(key, &p, nparts, rows, nullptr, m) || !s0 || !acc) return LF_ERR_ARG;
+    const KsSums ks = ks_sums(logN, rows, m.q_host, 0, nullptr, 0);
+    if (int e = ks.expect_digits(ext, 1, nparts)) return e;
     GiantArgs ga{};
-    ga.hk.ksk[0] = (const i64 *)ksk, ga.hk.p[0] = (unsigned)p, ga.s0 = (const i64 *)s0, ga.acc = (i64 *)acc;
-    const dim3 grid((unsigned)((((i64)1 << logN) + 511) / 512), (unsigned)rows);
-    const bool planes = key_format == LF_KEY_PLANES;
-#define LF_GIANT_LAUNCH(PL, DPLB)                                                                                          \
-    hipLaunchKernelGGL((ks_inner_giant_kernel<PL, DPLB>), grid, dim3(256), 0, st, (const i64 *)ext, ga, (i64)part_stride,   \
-                       (i64)comp_stride, (i64)row_off, nparts, rows, logN, (const i64 *)ql, (const i64 *)qh, (const i64 *)kl, \
-                       (const i64 *)kh)
-    if (planes && dplanes) LF_GIANT_LAUNCH(true, true);
-    else if (planes) LF_GIANT_LAUNCH(true, false);
-    else if (dplanes) LF_GIANT_LAUNCH(false, true);
-    else LF_GIANT_LAUNCH(false, false);
-#undef LF_GIANT_LAUNCH
+    ga.hk = hoist_keys(key, &p, 0, 1), ga.s0 = (const i64 *)s0, ga.acc = (i64 *)acc;
+    with_formats(key.key_format == LF_KEY_PLANES, ks.dplanes, [&](auto PL, auto DPL) {
+        hipLaunchKernelGGL((ks_inner_giant_kernel<LF_CT(PL), LF_CT(DPL)>), ks.grid, dim3(256), 0, st, (const i64 *)ext, ga,
+                           (i64)key.part_stride, (i64)key.comp_stride, (i64)key.row_off, nparts, rows, logN, LF_MOD_ARGS(m));
+    });
     return (int)hipGetLastError();
 }
 
 // ---- the launches of lf_lt_matmul_bsgs that are its own (ckks_ops.hip checks the arguments and owns the order) ----
 // extension + forward NTT of the digits of nct polynomials (state + t * state_stride) into tmp [nct][nparts][rows][N]
 int lf_ks_fwd_batch(const int64_t *state, int64_t state_stride, int nct, int nparts, int rows, int logN, const int64_t *desc,
-                    const int64_t *E, const double *Ed, int64_t *tmp, const int64_t *psi_br, const double *psi_dp, const int64_t *q_host,
-                    const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st) {
+                    const int64_t *E, const double *Ed, int64_t *tmp, const LfFwdTab &ft, const LfMod &m, hipStream_t st) {
     if ((nct != 2 && nct != 4) || nparts < 1 || rows < 1 || rows > MAX_LIST_ROWS || logN <= NTT_TILE_LOG_MAX || logN > KS_LOGN_MAX ||
-        !q_host || !psi_dp || !Ed || !state || !tmp)
+        !m.q_host || !ft.psi_dp || !Ed || !state || !tmp)
         return LF_ERR_ARG;
-    return ks_forward(state, state_stride, nct, nparts, rows, logN, desc, E, Ed, tmp, psi_br, psi_dp, q_host, ql, qh, kl, kh, st);
+    return ks_forward(state, state_stride, nct, nparts, rows, logN, desc, E, Ed, tmp, ft, m, st);
 }
+
+namespace {
+// what the two launchers of nct (2 or 4) ciphertexts under ONE key refuse alike; dst: the nct pairs they write or add to
+bool one_key_batch_ok(int nct, int64_t p, int nparts, int rows, int logN, const LfKeys &key, const int64_t *ext,
+                      const int64_t *const *src, int64_t *const *dst, const LfMod &m) {
+    if ((nct != 2 && nct != 4) || key.n != 1 || !gathered_args_ok(key, &p, nparts, rows, nullptr, m) || !ext || !src || !dst || nparts < 1 ||
+        logN <= NTT_TILE_LOG_MAX || logN > KS_LOGN_MAX || !lf_exponents_ok(&p, 1, logN))
+        return false;
+    for (int t = 0; t < nct; ++t) {
+        if (!src[t] || !dst[t]) return false;
+        for (int k = 0; k < t; ++k)
+            if (dst[k] == dst[t]) return false;   // (two ciphertexts of one launch never share a pair or an accumulator)
+    }
+    return true;
+}
+}  // namespace
 
 // giant step of nct (2 or 4) outputs under one key: acc[t] += (sum over the parts of output t's digits ext + t * nparts rows N
 // gathered by pi_p times the key part, + s0[t] gathered on all rows on component 0); every key word is read once for the group
-int lf_ks_giant_sums_batch(int nct, int64_t p, int nparts, int rows, int logN, const int64_t *ksk, int64_t part_stride, int64_t comp_stride,
-                           int64_t row_off, int key_format, const int64_t *ext, const int64_t *const *s0, int64_t *const *acc,
-                           const int64_t *q_host, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh,
-                           hipStream_t st) {
-    if ((nct != 2 && nct != 4) || !key_args_ok(ksk, part_stride, comp_stride, key_format) || !ext || !s0 || !acc || nparts < 1 ||
-        logN <= NTT_TILE_LOG_MAX || logN > KS_LOGN_MAX || p <= 0 || p >= ((int64_t)2 << logN) || !(p & 1))
-        return LF_ERR_ARG;
-    if (rows < 1 || rows > MAX_LIST_ROWS || !lf_fp64_digits_ok(nparts, rows, q_host)) return LF_ERR_ARG;
-    RowList dp, in;
-    classify_rows(rows, q_host, dp, in);
-    const bool dplanes = digit_planes(logN, dp, in);
-    if (int e = lf_fmt_expect(ext, ((size_t)nct * nparts * rows << logN) * 8, dplanes ? LF_FMT_PLANES : LF_FMT_RAW)) return e;
+int lf_ks_giant_sums_batch(int nct, int64_t p, int nparts, int rows, int logN, const LfKeys &key, const int64_t *ext,
+                           const int64_t *const *s0, int64_t *const *acc, const LfMod &m, hipStream_t st) {
+    if (!one_key_batch_ok(nct, p, nparts, rows, logN, key, ext, s0, acc, m)) return LF_ERR_ARG;
+    const KsSums ks = ks_sums(logN, rows, m.q_host, 0, nullptr, 0);
+    if (int e = ks.expect_digits(ext, nct, nparts)) return e;
     GiantBatchArgs ga{};
-    ga.ksk = (const i64 *)ksk, ga.p = (unsigned)p, ga.ext_stride = ((i64)nparts * rows) << logN;
-    for (int t = 0; t < nct; ++t) {
-        if (!s0[t] || !acc[t]) return LF_ERR_ARG;
-        for (int k = 0; k < t; ++k)
-            if (acc[k] == acc[t]) return LF_ERR_ARG;   // (two outputs of one launch never share an accumulator)
-        ga.s0[t] = (const i64 *)s0[t], ga.acc[t] = (i64 *)acc[t];
-    }
-    const dim3 grid((unsigned)((((i64)1 << logN) + 511) / 512), (unsigned)rows);
-    const bool planes = key_format == LF_KEY_PLANES;
-#define LF_GIANTB_LAUNCH(NCT, PL, DPLB)                                                                                         \
-    hipLaunchKernelGGL((ks_inner_giantb_kernel<NCT, PL, DPLB>), grid, dim3(256), 0, st, (const i64 *)ext, ga, (i64)part_stride, \
-                       (i64)comp_stride, (i64)row_off, nparts, rows, logN, (const i64 *)ql, (const i64 *)qh, (const i64 *)kl,   \
-                       (const i64 *)kh)
-#define LF_GIANTB_CASE(NCT)                                                                                                   \
-    if (planes && dplanes) LF_GIANTB_LAUNCH(NCT, true, true);                                                                 \
-    else if (planes) LF_GIANTB_LAUNCH(NCT, true, false);                                                                      \
-    else if (dplanes) LF_GIANTB_LAUNCH(NCT, false, true);                                                                     \
-    else LF_GIANTB_LAUNCH(NCT, false, false)
-    if (nct == 2) {
-        LF_GIANTB_CASE(2);
-    } else {
-        LF_GIANTB_CASE(4);
-    }
-#undef LF_GIANTB_LAUNCH
-#undef LF_GIANTB_CASE
+    ga.ksk = (const i64 *)key.ksk[0], ga.p = (unsigned)p, ga.ext_stride = ((i64)nparts * rows) << logN;
+    for (int t = 0; t < nct; ++t) ga.s0[t] = (const i64 *)s0[t], ga.acc[t] = (i64 *)acc[t];
+    with_count<2, 4>(nct, [&](auto NCT) {
+        with_formats(key.key_format == LF_KEY_PLANES, ks.dplanes, [&](auto PL, auto DPL) {
+            hipLaunchKernelGGL((ks_inner_giantb_kernel<LF_CT(NCT), LF_CT(PL), LF_CT(DPL)>), ks.grid, dim3(256), 0, st, (const i64 *)ext, ga,
+                               (i64)key.part_stride, (i64)key.comp_stride, (i64)key.row_off, nparts, rows, logN, LF_MOD_ARGS(m));
+        });
+    });
     return (int)hipGetLastError();
 }
 
@@ -3518,50 +3350,25 @@ int lf_ks_giant_sums_batch(int nct, int64_t p, int nparts, int rows, int logN, c
 // baby step of nct (2 or 4) ciphertexts under one key: u[t] = the sum over the parts of ciphertext t's digits ext + t * nparts rows N
 // gathered by pi_p times the key part, + chat0[t] gathered on the ordinary rows on component 0; every key word is read once for
 // the group
-int lf_ks_baby_sums_batch(int nct, int64_t p, int nparts, int rows, int ell, int logN, const int64_t *ksk, int64_t part_stride,
-                          int64_t comp_stride, int64_t row_off, int key_format, const int64_t *ext, const int64_t *const *chat0,
-                          int64_t *const *u, const int64_t *q_host, const int64_t *ql, const int64_t *qh, const int64_t *kl,
-                          const int64_t *kh, hipStream_t st) {
-    if ((nct != 2 && nct != 4) || !key_args_ok(ksk, part_stride, comp_stride, key_format) || !ext || !chat0 || !u || nparts < 1 ||
-        logN <= NTT_TILE_LOG_MAX || logN > KS_LOGN_MAX || p <= 0 || p >= ((int64_t)2 << logN) || !(p & 1) || ell < 0 || ell > rows)
-        return LF_ERR_ARG;
-    if (rows < 1 || rows > MAX_LIST_ROWS || !lf_fp64_digits_ok(nparts, rows, q_host)) return LF_ERR_ARG;
-    RowList dp, in;
-    classify_rows(rows, q_host, dp, in);
-    const bool dplanes = digit_planes(logN, dp, in);
-    if (int e = lf_fmt_expect(ext, ((size_t)nct * nparts * rows << logN) * 8, dplanes ? LF_FMT_PLANES : LF_FMT_RAW)) return e;
+int lf_ks_baby_sums_batch(int nct, int64_t p, int nparts, int rows, int ell, int logN, const LfKeys &key, const int64_t *ext,
+                          const int64_t *const *chat0, int64_t *const *u, const LfMod &m, hipStream_t st) {
+    if (!one_key_batch_ok(nct, p, nparts, rows, logN, key, ext, chat0, u, m) || ell < 0 || ell > rows) return LF_ERR_ARG;
+    const KsSums ks = ks_sums(logN, rows, m.q_host, 0, nullptr, 0);
+    if (int e = ks.expect_digits(ext, nct, nparts)) return e;
     BabyBatchArgs ba{};
-    ba.ksk = (const i64 *)ksk, ba.p = (unsigned)p, ba.ell = ell, ba.ext_stride = ((i64)nparts * rows) << logN;
-    for (int t = 0; t < nct; ++t) {
-        if (!chat0[t] || !u[t]) return LF_ERR_ARG;
-        for (int k = 0; k < t; ++k)
-            if (u[k] == u[t]) return LF_ERR_ARG;   // (two ciphertexts of one launch never share a pair)
-        ba.chat0[t] = (const i64 *)chat0[t], ba.u[t] = (i64 *)u[t];
-    }
-    const dim3 grid((unsigned)((((i64)1 << logN) + 511) / 512), (unsigned)rows);
-    const bool planes = key_format == LF_KEY_PLANES;
-#define LF_BABYB_LAUNCH(NCT, PL, DPLB)                                                                                         \
-    hipLaunchKernelGGL((ks_inner_babyb_kernel<NCT, PL, DPLB>), grid, dim3(256), 0, st, (const i64 *)ext, ba, (i64)part_stride, \
-                       (i64)comp_stride, (i64)row_off, nparts, rows, logN, (const i64 *)ql, (const i64 *)qh, (const i64 *)kl,  \
-                       (const i64 *)kh)
-#define LF_BABYB_CASE(NCT)                                                                                                   \
-    if (planes && dplanes) LF_BABYB_LAUNCH(NCT, true, true);                                                                 \
-    else if (planes) LF_BABYB_LAUNCH(NCT, true, false);                                                                      \
-    else if (dplanes) LF_BABYB_LAUNCH(NCT, false, true);                                                                     \
-    else LF_BABYB_LAUNCH(NCT, false, false)
-    if (nct == 2) {
-        LF_BABYB_CASE(2);
-    } else {
-        LF_BABYB_CASE(4);
-    }
-#undef LF_BABYB_LAUNCH
-#undef LF_BABYB_CASE
+    ba.ksk = (const i64 *)key.ksk[0], ba.p = (unsigned)p, ba.ell = ell, ba.ext_stride = ((i64)nparts * rows) << logN;
+    for (int t = 0; t < nct; ++t) ba.chat0[t] = (const i64 *)chat0[t], ba.u[t] = (i64 *)u[t];
+    with_count<2, 4>(nct, [&](auto NCT) {
+        with_formats(key.key_format == LF_KEY_PLANES, ks.dplanes, [&](auto PL, auto DPL) {
+            hipLaunchKernelGGL((ks_inner_babyb_kernel<LF_CT(NCT), LF_CT(PL), LF_CT(DPL)>), ks.grid, dim3(256), 0, st, (const i64 *)ext, ba,
+                               (i64)key.part_stride, (i64)key.comp_stride, (i64)key.row_off, nparts, rows, logN, LF_MOD_ARGS(m));
+        });
+    });
     return (int)hipGetLastError();
 }
 
 // cc_mult's product -> digits in one launch behind the tiled pass where it qualifies (ckks_ops.hip: product_digits): 0 = never
 int lf_g_intt_digits = 1;
-extern int lf_g_ws_extra_stage;   // ckks_ntt.hip
 
 extern "C" {
 
@@ -3606,10 +3413,9 @@ int lf_ks_core_batch(const int64_t *state, int64_t state_stride, int nct, int np
     if (!lf_fp64_digits_ok(nparts, rows, q_host)) return LF_ERR_ARG;
     if (int e = lf_set_device(device)) return e;
     hipStream_t st = (hipStream_t)stream;
-    if (int e = ks_forward(state, state_stride, nct, nparts, rows, logN, desc, E, Ed, tmp, psi_br, psi_dp, q_host, ql, qh, kl, kh, st))
-        return e;
-    return ks_tail(nct, nparts, rows, logN, ksk, part_stride, comp_stride, row_off, tmp, s, ipsi_br, ipsi_dp, Ninv, q_host, ql, qh,
-                   kl, kh, st, nullptr, key_format);
+    const LfMod m{ql, qh, kl, kh, q_host};
+    if (int e = ks_forward(state, state_stride, nct, nparts, rows, logN, desc, E, Ed, tmp, {psi_br, psi_dp}, m, st)) return e;
+    return ks_tail(nct, nparts, rows, logN, {&ksk, 1, part_stride, comp_stride, row_off, key_format}, tmp, s, {ipsi_br, ipsi_dp, Ninv}, m, st);
 }
 
 /* The two halves of lf_ks_core as separate calls, so that a limb-sharded engine can start on the digits that have
@@ -3625,7 +3431,7 @@ int lf_ks_fwd(const int64_t *state, int nparts, int rows, int logN, const int64_
         return LF_ERR_ARG;
     if (nparts == 0) return 0;
     if (int e = lf_set_device(device)) return e;
-    return ks_forward(state, 0, 1, nparts, rows, logN, desc, E, Ed, tmp, psi_br, psi_dp, q_host, ql, qh, kl, kh, (hipStream_t)stream);
+    return ks_forward(state, 0, 1, nparts, rows, logN, desc, E, Ed, tmp, {psi_br, psi_dp}, {ql, qh, kl, kh, q_host}, (hipStream_t)stream);
 }
 
 int lf_ks_tail(int nparts, int rows, int logN, const int64_t *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off,
@@ -3637,8 +3443,8 @@ int lf_ks_tail(int nparts, int rows, int logN, const int64_t *ksk, int64_t part_
         return LF_ERR_ARG;
     if (!lf_fp64_digits_ok(nparts, rows, q_host)) return LF_ERR_ARG;
     if (int e = lf_set_device(device)) return e;
-    return ks_tail(1, nparts, rows, logN, ksk, part_stride, comp_stride, row_off, tmp, s, ipsi_br, ipsi_dp, Ninv, q_host, ql, qh, kl,
-                   kh, (hipStream_t)stream, nullptr, key_format);
+    return ks_tail(1, nparts, rows, logN, {&ksk, 1, part_stride, comp_stride, row_off, key_format}, tmp, s, {ipsi_br, ipsi_dp, Ninv},
+                   {ql, qh, kl, kh, q_host}, (hipStream_t)stream);
 }
 
 /* Relinearisation inside cc_mult (see RelinFold): lf_ks_core_batch / lf_ks_fwd / lf_ks_tail whose sums additionally
@@ -3656,15 +3462,15 @@ int lf_relin_core_batch(const int64_t *state, int64_t state_stride, int nct, int
     if (!lf_fp64_digits_ok(nparts, rows, q_host)) return LF_ERR_ARG;
     if (int e = lf_set_device(device)) return e;
     hipStream_t st = (hipStream_t)stream;
-    if (int e = ks_forward(state, state_stride, nct, nparts, rows, logN, desc, E, Ed, tmp, psi_br, psi_dp, q_host, ql, qh, kl, kh, st,
-                           (const unsigned char *)own, 0))
+    const LfMod m{ql, qh, kl, kh, q_host};
+    if (int e = ks_forward(state, state_stride, nct, nparts, rows, logN, desc, E, Ed, tmp, {psi_br, psi_dp}, m, st, (const unsigned char *)own, 0))
         return e;
     const int xpl = (key_format & LF_STACK_PLANES) ? 1 : 0;
     for (int t = 0; t < nct; ++t)   // the operand stacks must be in the format the caller says (see lf_fmt_expect)
         if (int e = lf_fmt_expect(x + t * x_ct_stride, ((size_t)4 * ell << logN) * 8, xpl ? LF_FMT_PLANES : LF_FMT_RAW)) return e;
     const RelinFold fold{(const i64 *)x, (i64)x_ct_stride, (const i64 *)PR, ell, (const unsigned char *)own, xpl};
-    return ks_tail(nct, nparts, rows, logN, ksk, part_stride, comp_stride, row_off, tmp, s, ipsi_br, ipsi_dp, Ninv, q_host, ql, qh,
-                   kl, kh, st, &fold, key_format & ~LF_STACK_PLANES);
+    return ks_tail(nct, nparts, rows, logN, {&ksk, 1, part_stride, comp_stride, row_off, key_format & ~LF_STACK_PLANES}, tmp, s,
+                   {ipsi_br, ipsi_dp, Ninv}, m, st, &fold);
 }
 
 int lf_relin_fwd(const int64_t *state, int first, int nparts, int rows, int logN, const int64_t *desc, const int64_t *E,
@@ -3676,8 +3482,8 @@ int lf_relin_fwd(const int64_t *state, int first, int nparts, int rows, int logN
         return LF_ERR_ARG;
     if (nparts == 0) return 0;
     if (int e = lf_set_device(device)) return e;
-    return ks_forward(state, 0, 1, nparts, rows, logN, desc + 3 * (int64_t)first, E, Ed, tmp + (((int64_t)first * rows) << logN), psi_br,
-                      psi_dp, q_host, ql, qh, kl, kh, (hipStream_t)stream, (const unsigned char *)own, first);
+    return ks_forward(state, 0, 1, nparts, rows, logN, desc + 3 * (int64_t)first, E, Ed, tmp + (((int64_t)first * rows) << logN),
+                      {psi_br, psi_dp}, {ql, qh, kl, kh, q_host}, (hipStream_t)stream, (const unsigned char *)own, first);
 }
 
 int lf_relin_tail(int nparts, int rows, int logN, const int64_t *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off,
@@ -3692,8 +3498,8 @@ int lf_relin_tail(int nparts, int rows, int logN, const int64_t *ksk, int64_t pa
     const int xpl = (key_format & LF_STACK_PLANES) ? 1 : 0;
     if (int e = lf_fmt_expect(x, ((size_t)4 * ell << logN) * 8, xpl ? LF_FMT_PLANES : LF_FMT_RAW)) return e;
     const RelinFold fold{(const i64 *)x, 0, (const i64 *)PR, ell, (const unsigned char *)own, xpl};
-    return ks_tail(1, nparts, rows, logN, ksk, part_stride, comp_stride, row_off, tmp, s, ipsi_br, ipsi_dp, Ninv, q_host, ql, qh, kl,
-                   kh, (hipStream_t)stream, &fold, key_format & ~LF_STACK_PLANES);
+    return ks_tail(1, nparts, rows, logN, {&ksk, 1, part_stride, comp_stride, row_off, key_format & ~LF_STACK_PLANES}, tmp, s,
+                   {ipsi_br, ipsi_dp, Ninv}, {ql, qh, kl, kh, q_host}, (hipStream_t)stream, &fold);
 }
 
 int lf_ks_core(const int64_t *state, int nparts, int rows, int logN, const int64_t *desc, const int64_t *E,

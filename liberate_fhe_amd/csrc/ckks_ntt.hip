@@ -35,6 +35,7 @@
 #include "../../include/ckks_hip.h"
 #include "ckks_ntt_core.h"
 #include "ckks_ntt_tile16.h"
+#include "ckks_launch.h"
 #include <stdlib.h>
 
 int lf_g_ws_extra_stage = 1;   // lf_ntt_ws: the column pass takes the tiles' first stage too (ntt_forward; lf_tune in ckks_ks.hip)

@@ -9,117 +9,14 @@
 // results); they apply when every limb of the level lives on this device (no exchange step in the middle).
 #include "../../include/ckks_hip.h"
 #include "ckks_common.h"
+#include "ckks_launch.h"
 
 #include <vector>
 
-extern int lf_g_intt_digits;   // ckks_ks.hip (lf_tune)
-// ckks_ks.hip: false when a row is of the fp64 class and nparts exceeds LF_FP64_MAX_DIGITS (reads q_host[0 .. rows))
-bool lf_fp64_digits_ok(int nparts, int rows, const int64_t *q_host);
-// ckks_ks.hip: the key-dependent half of lf_rotate_hoisted (gathered inner product of up to 4 keys + inverse NTT of their sums)
-int lf_ks_tail_hoisted(int nr, const unsigned *p, int nparts, int rows, int logN, const int64_t *const *ksk, int64_t part_stride,
-                       int64_t comp_stride, int64_t row_off, int key_format, const int64_t *ext, int64_t *s, int64_t *scratch,
-                       int64_t scratch_words, const int64_t *ipsi_br, const double *ipsi_dp, const int64_t *Ninv, const int64_t *q_host,
-                       const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st);
-
-// ckks_ks.hip: the key-dependent part of lf_linear_transform (the groups' launches into one pair of sums + its inverse NTT)
-int lf_ks_tail_lt(int nr, const int64_t *p_host, int nparts, int rows, int ell, int logN, const int64_t *const *ksk, int64_t part_stride,
-                  int64_t comp_stride, int64_t row_off, int key_format, const int64_t *pt, int64_t pt_stride, const int64_t *pt0,
-                  const int64_t *chat, const int64_t *ext, int64_t *s, int64_t *scratch, int64_t scratch_words, const int64_t *ipsi_br,
-                  const double *ipsi_dp, const int64_t *Ninv, const int64_t *q_host, const int64_t *ql, const int64_t *qh,
-                  const int64_t *kl, const int64_t *kh, hipStream_t st);
-
-// ckks_ks.hip: the key-dependent part of lf_linear_transform_batch for a group of 2 or 4 ciphertexts (the launches into the
-// group's pairs of sums + their one inverse NTT)
-int lf_ks_tail_ltb(int nct, int nr, const int64_t *p_host, int nparts, int rows, int ell, int logN, const int64_t *const *ksk,
-                   int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format, const int64_t *pt, int64_t pt_stride,
-                   const int64_t *pt0, const int64_t *chat, int64_t chat_stride, const int64_t *ext, int64_t *s, int64_t *scratch,
-                   int64_t scratch_words, const int64_t *ipsi_br, const double *ipsi_dp, const int64_t *Ninv, const int64_t *q_host,
-                   const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st);
-
-// ckks_ks.hip: the launches of lf_linear_transform_bsgs
-int lf_ks_tail_rsum(int nr, const int64_t *p_host, int nparts, int rows, int ell, int logN, const int64_t *const *ksk, int64_t part_stride,
-                    int64_t comp_stride, int64_t row_off, int key_format, int with_self, const int64_t *chat, const int64_t *ext,
-                    int64_t *s, int64_t *scratch, int64_t scratch_words, const int64_t *ipsi_br, const double *ipsi_dp,
-                    const int64_t *Ninv, const int64_t *q_host, const int64_t *ql, const int64_t *qh, const int64_t *kl,
-                    const int64_t *kh, hipStream_t st);
-int lf_ks_baby_sums(int nr, const int64_t *p_host, int nparts, int rows, int ell, int logN, const int64_t *const *ksk, int64_t part_stride,
-                    int64_t comp_stride, int64_t row_off, int key_format, const int64_t *chat0, const int64_t *ext, int64_t *u,
-                    const int64_t *q_host, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st);
-// ckks_ks.hip: the key-dependent part of lf_rotate_sum_batch for a group of 2 or 4 ciphertexts (the launches into the group's
-// pairs of sums + their one inverse NTT)
-int lf_ks_tail_rsumb(int nct, int nr, const int64_t *p_host, int nparts, int rows, int ell, int logN, const int64_t *const *ksk,
-                     int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format, int with_self, const int64_t *chat,
-                     int64_t chat_stride, const int64_t *ext, int64_t *s, int64_t *scratch, int64_t scratch_words,
-                     const int64_t *ipsi_br, const double *ipsi_dp, const int64_t *Ninv, const int64_t *q_host, const int64_t *ql,
-                     const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st);
-int lf_lt_diag_products(int ng, const int64_t *u, int nslots, const int64_t *const *pt, const unsigned long long *slots, int64_t pt_stride,
-                        int64_t *const *out, int rows, int logN, const int64_t *ql, const int64_t *qh, const int64_t *kl,
-                        const int64_t *kh, hipStream_t st);
-int lf_ks_giant_sums(int64_t p, int nparts, int rows, int logN, const int64_t *ksk, int64_t part_stride, int64_t comp_stride,
-                     int64_t row_off, int key_format, const int64_t *ext, const int64_t *s0, int64_t *acc, const int64_t *q_host,
-                     const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st);
-
-// ckks_ks.hip: the launch of lf_lt_matmul that is its own
-int lf_lt_block_products(int no, const int64_t *u, int nslots, const int64_t *const *pt, const unsigned long long *slots,
-                         const int64_t *pt_stride, int64_t *const *out, const int *fresh, int rows, int logN, const int64_t *ql,
-                         const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st);
-
-// ckks_ks.hip: the launch of lf_lt_matmul_batch that is its own
-int lf_lt_block_productsb(int nt, int no, const int64_t *u, int64_t u_tstride, int nslots, const int64_t *const *pt,
-                          const unsigned long long *slots, const int64_t *pt_stride, int64_t *const *out, int64_t out_tstride,
-                          const int *fresh, int rows, int logN, const int64_t *ql, const int64_t *qh, const int64_t *kl,
-                          const int64_t *kh, hipStream_t st);
-
-// ckks_ks.hip: the launches of lf_lt_matmul_bsgs that are its own
-int lf_ks_fwd_batch(const int64_t *state, int64_t state_stride, int nct, int nparts, int rows, int logN, const int64_t *desc,
-                    const int64_t *E, const double *Ed, int64_t *tmp, const int64_t *psi_br, const double *psi_dp, const int64_t *q_host,
-                    const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st);
-int lf_ks_giant_sums_batch(int nct, int64_t p, int nparts, int rows, int logN, const int64_t *ksk, int64_t part_stride, int64_t comp_stride,
-                           int64_t row_off, int key_format, const int64_t *ext, const int64_t *const *s0, int64_t *const *acc,
-                           const int64_t *q_host, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh,
-                           hipStream_t st);
-
-// ckks_ks.hip: the launch of lf_linear_transform_bsgs_batch that is its own
-int lf_ks_baby_sums_batch(int nct, int64_t p, int nparts, int rows, int ell, int logN, const int64_t *ksk, int64_t part_stride,
-                          int64_t comp_stride, int64_t row_off, int key_format, const int64_t *ext, const int64_t *const *chat0,
-                          int64_t *const *u, const int64_t *q_host, const int64_t *ql, const int64_t *qh, const int64_t *kl,
-                          const int64_t *kh, hipStream_t st);
-
-// ckks_ks.hip: the launches of lf_cc_dot that are its own
-int lf_dot_tensor(int g, const int64_t *x, int64_t *T, int64_t *t2, int ell, int logN, int xpl, int first, const int64_t *ql,
-                  const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st);
-int lf_dot_relin(const int64_t *state, int nparts, int rows, int logN, const int64_t *desc, const int64_t *E, const double *Ed,
-                 const int64_t *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format, int64_t *tmp, int64_t *s,
-                 const int64_t *psi_br, const double *psi_dp, const int64_t *ipsi_br, const double *ipsi_dp, const int64_t *Ninv,
-                 const int64_t *T, const int64_t *PR, int ell, const uint8_t *own, const int64_t *q_host, const int64_t *ql,
-                 const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st);
-
-int lf_dot_relin_batch(const int64_t *state, int nct, int nparts, int rows, int logN, const int64_t *desc, const int64_t *E,
-                       const double *Ed, const int64_t *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format,
-                       int64_t *tmp, int64_t *s, const int64_t *psi_br, const double *psi_dp, const int64_t *ipsi_br,
-                       const double *ipsi_dp, const int64_t *Ninv, const int64_t *T, const int64_t *PR, int ell, const uint8_t *own,
-                       const int64_t *q_host, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st);
-
-// ckks_ks.hip: the launches of lf_pc_dot that are its own
-int lf_pc_dot_products(int g, const int64_t *x, const int64_t *const *pt, int64_t *S, int rows, int logN, int xpl, int first,
-                       const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st);
-int lf_pc_bias(int64_t *c0, const int64_t *pt, const int64_t *Rs, int rows, int logN, const int64_t *ql, const int64_t *qh,
-               const int64_t *kl, const int64_t *kh, hipStream_t st);
-
-// ckks_ks.hip: the launch of lf_pc_matmul that is its own
-int lf_pc_matmul_products(int go, int n, const int64_t *x, const int64_t *const *pt, int pt_stride, int64_t *S, int rows, int logN,
-                          int xpl, int first, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st);
-
-// ckks_ks.hip: the launch of lf_pc_matmul_batch that is its own, and the tile of tokens it takes
-int lf_pc_matmul_batch_tile(int go, int left);
-int lf_pc_matmul_batch_outputs(int left, int nt);
-int lf_pc_matmulb_products(int go, int gt, int n, const int64_t *x, int64_t xtok, const int64_t *const *pt, int pt_stride, int64_t *S,
-                           int64_t stok, int rows, int logN, int xpl, int first, const int64_t *ql, const int64_t *qh, const int64_t *kl,
-                           const int64_t *kh, hipStream_t st);
-
-// ckks_ks.hip: the launch of lf_cc_matmul that is its own
-int lf_matmul_tensor(int R, int C, int k, int nu, const int64_t *x, const int *ta, const int *tb, int64_t *T, int64_t *t2, int ell,
-                     int logN, int xpl, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, hipStream_t st);
+// what always travels together into the launchers of ckks_ks.hip (ckks_launch.h), from the plan
+static LfMod plan_mod(const lf_ks_plan *p) { return {p->ql, p->qh, p->kl, p->kh, p->q_host}; }
+static LfFwdTab plan_fwd(const lf_ks_plan *p) { return {p->psi, p->psi_dp}; }
+static LfInvTab plan_inv(const lf_ks_plan *p) { return {p->ipsi, p->ipsi_dp, p->Ninv}; }
 
 extern "C" {
 
@@ -152,6 +49,66 @@ static int moddown_any(const lf_ks_plan *p, const int64_t *const *ss, int64_t *c
                                  p->ql, p->qh, p->kl, p->kh, p->device, stream);
     return lf_ks_moddown_ws(ss, outs, adds, count, p->ell, p->K, N, p->md_ws, p->md_ws_words, p->PiR, p->PiP, p->Rs, gal_pinv, g2q, p->ql,
                             p->qh, p->kl, p->kh, p->device, stream);
+}
+
+// one mod-down of n (<= 4) pairs of sums [n][2][rows][N] at `sums` into the pairs out0[t], out1[t]; c0 (may be NULL): c0[t] (may be
+// NULL) joins component 0 of pair t, through the Galois map gal_pinv where that is set
+static int moddown_pairs(const lf_ks_plan *p, const int64_t *sums, int n, int64_t *const *out0, int64_t *const *out1,
+                         const int64_t *const *c0, int64_t gal_pinv, const int64_t *g2q, void *stream) {
+    const int64_t half = (int64_t)(p->ell + p->K) << p->logN;
+    const int64_t *ss[8], *adds[8];
+    int64_t *outs[8];
+    for (int t = 0; t < n; ++t) {
+        ss[2 * t] = sums + (2 * t) * half, ss[2 * t + 1] = sums + (2 * t + 1) * half;
+        outs[2 * t] = out0[t], outs[2 * t + 1] = out1[t];
+        adds[2 * t] = c0 ? c0[t] : nullptr, adds[2 * t + 1] = nullptr;
+    }
+    return moddown_any(p, ss, outs, c0 ? adds : nullptr, 2 * n, gal_pinv, g2q, stream);
+}
+
+// .. into md [n][2][ell][N] instead, then ONE rescale of the 2 n polynomials into the pairs out0[t], out1[t] of [ell - 1][N]; the
+// mod-down runs in the workspace mdws (a count the plan's own is not primed for), or in the plan's own where mdws is NULL
+static int moddown_rescale_pairs(const lf_ks_plan *p, const int64_t *sums, int n, int64_t *md, int64_t *mdws, int64_t mdws_words,
+                                 int64_t *const *out0, int64_t *const *out1, const int64_t *rescale_scales, int64_t round_at,
+                                 void *stream) {
+    const int ell = p->ell;
+    const int64_t N = (int64_t)1 << p->logN, poly = (int64_t)ell * N, half = (int64_t)(ell + p->K) * N;
+    const int64_t *ss[8], *ins[8], *row0[8];
+    int64_t *mds[8], *outs[8];
+    for (int t = 0; t < 2 * n; ++t) {
+        ss[t] = sums + t * half;
+        mds[t] = md + t * poly, row0[t] = mds[t], ins[t] = mds[t] + N;
+        outs[t] = (t & 1) ? out1[t / 2] : out0[t / 2];
+    }
+    if (int e = mdws ? lf_ks_moddown_ws(ss, mds, nullptr, 2 * n, ell, p->K, N, mdws, mdws_words, p->PiR, p->PiP, p->Rs, 0, nullptr, p->ql,
+                                        p->qh, p->kl, p->kh, p->device, stream)
+                     : moddown_any(p, ss, mds, nullptr, 2 * n, 0, nullptr, stream))
+        return e;
+    return lf_rescale_batch(ins, row0, outs, 2 * n, ell - 1, N, rescale_scales, round_at, p->ql + 1, p->qh + 1, p->kl + 1, p->kh + 1,
+                            p->device, stream);
+}
+
+// P NTT(c) of n (<= 8) polynomials srcs[i] on the plan's ordinary rows into base + i * stride: a canonical copy, enter_ntt (exact:
+// lazy Montgomery words below 2q on rows of both classes, what the kernels add unreduced), times P R.  ONE forward transform
+// where the results lie back to back (stride = ell N), one per polynomial otherwise
+static int p_ntt(const lf_ks_plan *p, const int64_t *const *srcs, int n, int64_t *base, int64_t stride, void *stream) {
+    const int ell = p->ell, logN = p->logN, dev = p->device;
+    const int64_t N = (int64_t)1 << logN;
+    const bool packed = stride == (int64_t)ell * N;
+    int64_t *dsts[8];
+    if (n < 1 || n > 8) return LF_ERR_ARG;
+    for (int i = 0; i < n; ++i) dsts[i] = base + i * stride;
+    if (int e = lf_galois_batch(srcs, dsts, n, ell, logN, 1, p->_2q, dev, stream)) return e;
+    if (packed)
+        if (int e = lf_ntt(base, n, ell, logN, p->psi, p->psi_dp, p->q_host, p->Rs, 0, p->_2q, p->ql, p->qh, p->kl, p->kh, dev, stream))
+            return e;
+    for (int i = 0; i < n; ++i) {
+        if (!packed)
+            if (int e = lf_ntt(dsts[i], 1, ell, logN, p->psi, p->psi_dp, p->q_host, p->Rs, 0, p->_2q, p->ql, p->qh, p->kl, p->kh, dev, stream))
+                return e;
+        if (int e = lf_mont_enter(dsts[i], p->PR, ell, N, p->ql, p->qh, p->kl, p->kh, dev, stream)) return e;
+    }
+    return 0;
 }
 
 // d2 = x1 * y1 -> inverse transform -> digits of the plan's `nct` operand stacks: in ONE launch behind the tiled pass where a
@@ -194,9 +151,7 @@ int lf_cc_mult_evk(const lf_ks_plan *p, const int64_t *const *in, const int64_t 
                                     row_off, key_format | (xpl ? LF_STACK_PLANES : 0), p->ext, p->sum, p->psi, p->psi_dp, p->ipsi, p->ipsi_dp, p->Ninv, p->x4, 0, p->PR, ell,
                                     p->own, p->q_host, p->ql, p->qh, p->kl, p->kh, dev, stream))
         return e;
-    const int64_t *ss[2] = {p->sum, p->sum + (int64_t)rows * N};
-    int64_t *outs[2] = {out0, out1};
-    return moddown_any(p, ss, outs, nullptr, 2, 0, nullptr, stream);
+    return moddown_pairs(p, p->sum, 1, &out0, &out1, nullptr, 0, nullptr, stream);
 }
 
 /* ---- cc_dot: sum_i a_i * b_i under ONE relinearisation (include/ckks_hip.h).  Everything of a cc_mult but the tensor products is
@@ -230,45 +185,52 @@ static int dot_triplet(const lf_ks_plan *p, int np, const int64_t *const *in, co
                 return e;
         }
         // 2. their tensor products into the one triplet; the last launch leaves a copy of T2 where its inverse transform runs
-        if (int e = lf_dot_tensor(g, p->x4, T, i0 + g == np ? t2 : nullptr, ell, logN, xpl, i0 == 0, p->ql, p->qh, p->kl, p->kh,
-                                  (hipStream_t)stream))
-            return e;
+        if (int e = lf_dot_tensor(g, p->x4, T, i0 + g == np ? t2 : nullptr, ell, logN, xpl, i0 == 0, plan_mod(p), (hipStream_t)stream)) return e;
         i0 += g;
     }
     return 0;
 }
 
+// steps 3 to 5 of lf_cc_dot (nd = 1) resp. lf_cc_dot_batch (nd = 2, 4) on nd summed triplets at T, their T2 copies in plan->d2
+static int dot_tail(const lf_ks_plan *p, int nd, const int64_t *T, const LfKeys &key, int64_t *const *out0, int64_t *const *out1,
+                    void *stream) {
+    const int ell = p->ell, rows = p->ell + p->K, logN = p->logN, dev = p->device;
+    const int64_t N = (int64_t)1 << logN, poly = (int64_t)ell * N;
+    // 3. the nd copies of T2 -> canonical coefficients in one inverse transform (the words lf_intt_mul leaves), their digits in one launch
+    if (int e = lf_intt(p->d2, nd, ell, logN, p->ipsi, p->ipsi_dp, p->q_host, p->Ninv, 2, LF_NTT_RELAXED | LF_NTT_PLAIN, p->_2q, p->ql, p->qh,
+                        p->kl, p->kh, dev, stream))
+        return e;
+    if (nd == 1) {
+        if (int e = lf_ks_digits(p->d2, p->state, p->dig_nparts, p->dig_desc, p->dig_tab, N, p->ql, p->qh, p->kl, p->kh, dev, stream)) return e;
+    } else {
+        const int64_t *srcs[4];
+        int64_t *states[4];
+        for (int d = 0; d < nd; ++d) srcs[d] = p->d2 + d * poly, states[d] = p->state + d * poly;
+        if (int e = lf_ks_digits_batch(srcs, states, nd, p->dig_nparts, p->dig_desc, p->dig_tab, N, 0, nullptr, p->ql, p->qh, p->kl, p->kh,
+                                       dev, stream))
+            return e;
+    }
+    // 4. the key switch of the nd T2 with P T0, P T1 folded into their sums, own-limb digit words from T2: every key word read once
+    if (int e = lf_dot_relin(p->state, nd, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, key, p->ext, p->sum, plan_fwd(p), plan_inv(p), T,
+                             p->PR, ell, p->own, plan_mod(p), (hipStream_t)stream))
+        return e;
+    // 5. one mod-down of the 2 nd sums, no addend
+    return moddown_pairs(p, p->sum, nd, out0, out1, nullptr, 0, nullptr, stream);
+}
+
 int lf_cc_dot(const lf_ks_plan *p, int np, const int64_t *const *in, const int64_t *const *row0, const int64_t *ksk,
               int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format, int64_t *ws, int64_t ws_words, int64_t *out0,
               int64_t *out1, void *stream) {
-    if (!dot_ok(p) || np < 1 || !in || !row0 || !ksk || !out0 || !out1 || (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES))
-        return LF_ERR_ARG;
-    if (key_format == LF_KEY_PLANES && ((((uintptr_t)ksk | (uintptr_t)(part_stride * 8) | (uintptr_t)(comp_stride * 8)) & 15)))
-        return LF_ERR_ARG;
+    const LfKeys key{&ksk, 1, part_stride, comp_stride, row_off, key_format};
+    if (!dot_ok(p) || np < 1 || !in || !row0 || !out0 || !out1 || !lf_keys_ok(key)) return LF_ERR_ARG;
     for (int64_t i = 0; i < (int64_t)4 * np; ++i)
         if (!in[i] || !row0[i]) return LF_ERR_ARG;
     const int64_t need = lf_cc_dot_ws_words(p);
     if (need && (!ws || ws_words < need)) return LF_ERR_ARG;
-    const int ell = p->ell, rows = p->ell + p->K, logN = p->logN, dev = p->device;
-    const int64_t N = (int64_t)1 << logN;
-    if (int e = lf_set_device(dev)) return e;
-    int64_t *T = ws;
+    if (int e = lf_set_device(p->device)) return e;
     // 1., 2. the pairs' tensor products into the one triplet
-    if (int e = dot_triplet(p, np, in, row0, T, p->d2, stream)) return e;
-    // 3. T2 -> canonical coefficients (the words lf_intt_mul leaves for one pair), its digits
-    if (int e = lf_intt(p->d2, 1, ell, logN, p->ipsi, p->ipsi_dp, p->q_host, p->Ninv, 2, LF_NTT_RELAXED | LF_NTT_PLAIN, p->_2q, p->ql, p->qh,
-                        p->kl, p->kh, dev, stream))
-        return e;
-    if (int e = lf_ks_digits(p->d2, p->state, p->dig_nparts, p->dig_desc, p->dig_tab, N, p->ql, p->qh, p->kl, p->kh, dev, stream)) return e;
-    // 4. the key switch of T2 with P T0, P T1 folded into its sums, own-limb digit words from T2
-    if (int e = lf_dot_relin(p->state, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, ksk, part_stride, comp_stride, row_off, key_format,
-                             p->ext, p->sum, p->psi, p->psi_dp, p->ipsi, p->ipsi_dp, p->Ninv, T, p->PR, ell, p->own, p->q_host, p->ql,
-                             p->qh, p->kl, p->kh, (hipStream_t)stream))
-        return e;
-    // 5. one mod-down, no addend
-    const int64_t *ss[2] = {p->sum, p->sum + (int64_t)rows * N};
-    int64_t *outs[2] = {out0, out1};
-    return moddown_any(p, ss, outs, nullptr, 2, 0, nullptr, stream);
+    if (int e = dot_triplet(p, np, in, row0, ws, p->d2, stream)) return e;
+    return dot_tail(p, 1, ws, key, &out0, &out1, stream);
 }
 
 /* ---- cc_dot_batch: nd = 1, 2 or 4 independent dots under ONE key (include/ckks_hip.h): lf_cc_dot's launches with everything behind
@@ -281,11 +243,8 @@ int64_t lf_cc_dot_batch_ws_words(const lf_ks_plan *p, int nd) {
 int lf_cc_dot_batch(const lf_ks_plan *p, int nd, const int64_t *np_host, const int64_t *const *in, const int64_t *const *row0,
                     const int64_t *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format, int64_t *ws,
                     int64_t ws_words, int64_t *const *out0, int64_t *const *out1, void *stream) {
-    if (!dot_ok(p) || !batch_ok(p, nd) || !np_host || !in || !row0 || !ksk || !out0 || !out1 ||
-        (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES))
-        return LF_ERR_ARG;
-    if (key_format == LF_KEY_PLANES && ((((uintptr_t)ksk | (uintptr_t)(part_stride * 8) | (uintptr_t)(comp_stride * 8)) & 15)))
-        return LF_ERR_ARG;
+    const LfKeys key{&ksk, 1, part_stride, comp_stride, row_off, key_format};
+    if (!dot_ok(p) || !batch_ok(p, nd) || !np_host || !in || !row0 || !out0 || !out1 || !lf_keys_ok(key)) return LF_ERR_ARG;
     int64_t pairs = 0;
     for (int d = 0; d < nd; ++d) {
         if (np_host[d] < 1 || np_host[d] > INT32_MAX || !out0[d] || !out1[d]) return LF_ERR_ARG;
@@ -298,38 +257,15 @@ int lf_cc_dot_batch(const lf_ks_plan *p, int nd, const int64_t *np_host, const i
     if (nd == 1)
         return lf_cc_dot(p, (int)np_host[0], in, row0, ksk, part_stride, comp_stride, row_off, key_format, ws, ws_words, out0[0], out1[0],
                          stream);
-    const int ell = p->ell, rows = p->ell + p->K, logN = p->logN, dev = p->device;
-    const int64_t N = (int64_t)1 << logN, poly = (int64_t)ell * N;
-    if (int e = lf_set_device(dev)) return e;
+    const int64_t poly = (int64_t)p->ell << p->logN;
+    if (int e = lf_set_device(p->device)) return e;
     // 1., 2. per dot: its pairs' tensor products into its triplet T_d; the copy of T2_d into slot d of plan->d2
     int64_t first = 0;
     for (int d = 0; d < nd; ++d) {
         if (int e = dot_triplet(p, (int)np_host[d], in + 4 * first, row0 + 4 * first, ws + d * 3 * poly, p->d2 + d * poly, stream)) return e;
         first += np_host[d];
     }
-    // 3. the nd copies -> canonical coefficients in one inverse transform, their digits in one launch
-    if (int e = lf_intt(p->d2, nd, ell, logN, p->ipsi, p->ipsi_dp, p->q_host, p->Ninv, 2, LF_NTT_RELAXED | LF_NTT_PLAIN, p->_2q, p->ql, p->qh,
-                        p->kl, p->kh, dev, stream))
-        return e;
-    const int64_t *srcs[4];
-    int64_t *states[4];
-    for (int d = 0; d < nd; ++d) srcs[d] = p->d2 + d * poly, states[d] = p->state + d * poly;
-    if (int e = lf_ks_digits_batch(srcs, states, nd, p->dig_nparts, p->dig_desc, p->dig_tab, N, 0, nullptr, p->ql, p->qh, p->kl, p->kh, dev,
-                                   stream))
-        return e;
-    // 4. the key switch of the nd T2 with P T0, P T1 folded into their sums: every key word read once for all of them
-    if (int e = lf_dot_relin_batch(p->state, nd, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, ksk, part_stride, comp_stride, row_off,
-                                   key_format, p->ext, p->sum, p->psi, p->psi_dp, p->ipsi, p->ipsi_dp, p->Ninv, ws, p->PR, ell, p->own,
-                                   p->q_host, p->ql, p->qh, p->kl, p->kh, (hipStream_t)stream))
-        return e;
-    // 5. one mod-down of the 2 nd sums, no addend
-    const int64_t *ss[8];
-    int64_t *outs[8];
-    for (int d = 0; d < nd; ++d) {
-        ss[2 * d] = p->sum + (int64_t)(2 * d) * rows * N, ss[2 * d + 1] = p->sum + (int64_t)(2 * d + 1) * rows * N;
-        outs[2 * d] = out0[d], outs[2 * d + 1] = out1[d];
-    }
-    return moddown_any(p, ss, outs, nullptr, 2 * nd, 0, nullptr, stream);
+    return dot_tail(p, nd, ws, key, out0, out1, stream);
 }
 
 /* ---- cc_matmul: C = A B over ciphertexts under ONE key (include/ckks_hip.h): every distinct operand transformed once into a
@@ -371,50 +307,14 @@ static void matmul_tiles(std::vector<MatmulTile> &tiles, int m, int n, int gmax)
     }
 }
 
-// steps 3 to 5 of lf_cc_dot (nd = 1) resp. lf_cc_dot_batch (nd = 2, 4) on nd summed triplets at T, their T2 copies in plan->d2
-static int dot_tail(const lf_ks_plan *p, int nd, const int64_t *T, const int64_t *ksk, int64_t part_stride, int64_t comp_stride,
-                    int64_t row_off, int key_format, int64_t *const *out0, int64_t *const *out1, void *stream) {
-    const int ell = p->ell, rows = p->ell + p->K, logN = p->logN, dev = p->device;
-    const int64_t N = (int64_t)1 << logN, poly = (int64_t)ell * N;
-    if (int e = lf_intt(p->d2, nd, ell, logN, p->ipsi, p->ipsi_dp, p->q_host, p->Ninv, 2, LF_NTT_RELAXED | LF_NTT_PLAIN, p->_2q, p->ql, p->qh,
-                        p->kl, p->kh, dev, stream))
-        return e;
-    if (nd == 1) {
-        if (int e = lf_ks_digits(p->d2, p->state, p->dig_nparts, p->dig_desc, p->dig_tab, N, p->ql, p->qh, p->kl, p->kh, dev, stream)) return e;
-        if (int e = lf_dot_relin(p->state, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, ksk, part_stride, comp_stride, row_off,
-                                 key_format, p->ext, p->sum, p->psi, p->psi_dp, p->ipsi, p->ipsi_dp, p->Ninv, T, p->PR, ell, p->own,
-                                 p->q_host, p->ql, p->qh, p->kl, p->kh, (hipStream_t)stream))
-            return e;
-    } else {
-        const int64_t *srcs[4];
-        int64_t *states[4];
-        for (int d = 0; d < nd; ++d) srcs[d] = p->d2 + d * poly, states[d] = p->state + d * poly;
-        if (int e = lf_ks_digits_batch(srcs, states, nd, p->dig_nparts, p->dig_desc, p->dig_tab, N, 0, nullptr, p->ql, p->qh, p->kl, p->kh,
-                                       dev, stream))
-            return e;
-        if (int e = lf_dot_relin_batch(p->state, nd, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, ksk, part_stride, comp_stride,
-                                       row_off, key_format, p->ext, p->sum, p->psi, p->psi_dp, p->ipsi, p->ipsi_dp, p->Ninv, T, p->PR, ell,
-                                       p->own, p->q_host, p->ql, p->qh, p->kl, p->kh, (hipStream_t)stream))
-            return e;
-    }
-    const int64_t *ss[8];
-    int64_t *outs[8];
-    for (int d = 0; d < nd; ++d) {
-        ss[2 * d] = p->sum + (int64_t)(2 * d) * rows * N, ss[2 * d + 1] = p->sum + (int64_t)(2 * d + 1) * rows * N;
-        outs[2 * d] = out0[d], outs[2 * d + 1] = out1[d];
-    }
-    return moddown_any(p, ss, outs, nullptr, 2 * nd, 0, nullptr, stream);
-}
-
 int lf_cc_matmul(const lf_ks_plan *p, int m, int k, int n, int nu, const int64_t *const *in, const int64_t *const *row0,
                  const int64_t *ia, const int64_t *ib, const int64_t *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off,
                  int key_format, int64_t *ws, int64_t ws_words, int64_t *const *out0, int64_t *const *out1, void *stream) {
+    const LfKeys key{&ksk, 1, part_stride, comp_stride, row_off, key_format};
     if (!dot_ok(p) || m < 1 || k < 1 || n < 1 || k > LF_CC_MATMUL_MAX_INNER || nu < 1 || nu > LF_CC_MATMUL_MAX_OPERANDS || !in || !row0 ||
-        !ia || !ib || !ksk || !out0 || !out1 || (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES))
+        !ia || !ib || !out0 || !out1 || !lf_keys_ok(key))
         return LF_ERR_ARG;
     if ((int64_t)m * k > INT32_MAX || (int64_t)k * n > INT32_MAX || (int64_t)m * n > INT32_MAX) return LF_ERR_ARG;
-    if (key_format == LF_KEY_PLANES && ((((uintptr_t)ksk | (uintptr_t)(part_stride * 8) | (uintptr_t)(comp_stride * 8)) & 15)))
-        return LF_ERR_ARG;
     std::vector<char> used((size_t)nu, 0);
     for (int64_t i = 0; i < (int64_t)m * k; ++i) {
         if (ia[i] < -1 || ia[i] >= nu) return LF_ERR_ARG;
@@ -456,16 +356,14 @@ int lf_cc_matmul(const lf_ks_plan *p, int m, int k, int n, int nu, const int64_t
             for (int i = 0; i < tl.R; ++i) ta[t * tl.R + i] = (int)ia[(int64_t)(tl.i0 + i) * k + t];
             for (int j = 0; j < tl.C; ++j) tb[t * tl.C + j] = (int)ib[(int64_t)t * n + tl.j0 + j];
         }
-        if (int e = lf_matmul_tensor(tl.R, tl.C, k, nu, store, ta, tb, T, p->d2, ell, logN, xpl, p->ql, p->qh, p->kl, p->kh,
-                                     (hipStream_t)stream))
-            return e;
+        if (int e = lf_matmul_tensor(tl.R, tl.C, k, nu, store, ta, tb, T, p->d2, ell, logN, xpl, plan_mod(p), (hipStream_t)stream)) return e;
         int64_t *o0[4], *o1[4];
         for (int i = 0; i < tl.R; ++i)
             for (int j = 0; j < tl.C; ++j) {
                 const int64_t at = (int64_t)(tl.i0 + i) * n + tl.j0 + j;
                 o0[i * tl.C + j] = out0[at], o1[i * tl.C + j] = out1[at];
             }
-        if (int e = dot_tail(p, tl.R * tl.C, T, ksk, part_stride, comp_stride, row_off, key_format, o0, o1, stream)) return e;
+        if (int e = dot_tail(p, tl.R * tl.C, T, key, o0, o1, stream)) return e;
     }
     return 0;
 }
@@ -508,7 +406,7 @@ int lf_pc_dot(int k, const int64_t *const *in, const int64_t *const *pt, const i
                                    nullptr, ql, qh, kl, kh, device, stream))
             return e;
         // 2. their products with the plaintexts into the one pair S
-        if (int e = lf_pc_dot_products(g, x, pt + i0, S, rows, logN, xpl, i0 == 0, ql, qh, kl, kh, (hipStream_t)stream)) return e;
+        if (int e = lf_pc_dot_products(g, x, pt + i0, S, rows, logN, xpl, i0 == 0, {ql, qh, kl, kh, q_host}, (hipStream_t)stream)) return e;
         i0 += g;
     }
     // 3. S -> canonical coefficients (intt_exit_reduce's words)
@@ -521,7 +419,7 @@ int lf_pc_dot(int k, const int64_t *const *in, const int64_t *const *pt, const i
     if (int e = lf_rescale_batch(ins, row0, outs, 2, rows - 1, N, rescale_scales, round_at, ql + 1, qh + 1, kl + 1, kh + 1, device, stream))
         return e;
     if (!bias) return 0;
-    return lf_pc_bias(out0, bias, Rs + 1, rows - 1, logN, ql + 1, qh + 1, kl + 1, kh + 1, (hipStream_t)stream);
+    return lf_pc_bias(out0, bias, Rs + 1, rows - 1, logN, {ql + 1, qh + 1, kl + 1, kh + 1, q_host + 1}, (hipStream_t)stream);
 }
 
 /* ---- pc_matmul: k_out sums of plaintext-ciphertext products over the SAME k_in ciphertexts (include/ckks_hip.h): lf_pc_dot's
@@ -572,6 +470,7 @@ static int pc_matmul_tokens(int nt, int64_t need, int k_in, int k_out, const int
     const int xpl = lf_stack_planes(logN, rows, q_host);
     const int relaxed_plain = LF_NTT_RELAXED | LF_NTT_PLAIN | (xpl ? LF_NTT_PLANES : 0);
     if (int e = lf_set_device(device)) return e;
+    const LfMod mod{ql, qh, kl, kh, q_host};
     const int64_t xtok = 2 * (int64_t)(k_in < LF_PC_MATMUL_CI ? k_in : LF_PC_MATMUL_CI) * poly, stok = 2 * (int64_t)k_out * poly;
     int64_t *x = ws, *S = ws + nt * xtok;
     const int64_t *zeros[8];
@@ -602,10 +501,9 @@ static int pc_matmul_tokens(int nt, int64_t need, int k_in, int k_out, const int
             for (int tk = 0; tk < nt;) {
                 const int gt = lf_pc_matmul_batch_tile(go, nt - tk);
                 int64_t *Sg = S + tk * stok + (int64_t)o0 * 2 * poly;
-                const int e = gt == 1 ? lf_pc_matmul_products(go, n, x + tk * xtok, tab, 4, Sg, rows, logN, xpl, a0 == 0, ql, qh, kl, kh,
-                                                              (hipStream_t)stream)
+                const int e = gt == 1 ? lf_pc_matmul_products(go, n, x + tk * xtok, tab, 4, Sg, rows, logN, xpl, a0 == 0, mod, (hipStream_t)stream)
                                       : lf_pc_matmulb_products(go, gt, n, x + tk * xtok, xtok, tab, 4, Sg, stok, rows, logN, xpl, a0 == 0,
-                                                               ql, qh, kl, kh, (hipStream_t)stream);
+                                                               mod, (hipStream_t)stream);
                 if (e) return e;
                 tk += gt;
             }
@@ -640,7 +538,8 @@ static int pc_matmul_tokens(int nt, int64_t need, int k_in, int k_out, const int
         if (!bias) continue;
         for (int o = 0; o < k_out; ++o)
             if (bias[o])
-                if (int e = lf_pc_bias(o0s[o], bias[o], Rs + 1, rows - 1, logN, ql + 1, qh + 1, kl + 1, kh + 1, (hipStream_t)stream)) return e;
+                if (int e = lf_pc_bias(o0s[o], bias[o], Rs + 1, rows - 1, logN, {ql + 1, qh + 1, kl + 1, kh + 1, q_host + 1}, (hipStream_t)stream))
+                    return e;
     }
     return 0;
 }
@@ -682,10 +581,7 @@ int lf_switch_key(const lf_ks_plan *p, const int64_t *c0, const int64_t *c1, int
     if (int e = lf_ks_core(p->state, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, ksk, part_stride, comp_stride, row_off, key_format, p->ext,
                            p->sum, p->psi, p->psi_dp, p->ipsi, p->ipsi_dp, p->Ninv, p->q_host, p->ql, p->qh, p->kl, p->kh, dev, stream))
         return e;
-    const int64_t *ss[2] = {p->sum, p->sum + (int64_t)rows * N};
-    int64_t *outs[2] = {out0, out1};
-    const int64_t *adds[2] = {c0, nullptr};
-    return moddown_any(p, ss, outs, adds, 2, gal_pinv, g2q, stream);
+    return moddown_pairs(p, p->sum, 1, &out0, &out1, &c0, gal_pinv, g2q, stream);
 }
 
 /* ---- hoisted rotations: ONE ciphertext under nr keys, the digits of c1 extended and transformed once (include/ckks_hip.h) ---- */
@@ -704,15 +600,13 @@ int64_t lf_rotate_hoisted_ws_words(const lf_ks_plan *p) {
 int lf_rotate_hoisted(const lf_ks_plan *p, const int64_t *c0, const int64_t *c1, int nr, const int64_t *p_host, int gal_canonical,
                       const int64_t *const *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format, int64_t *ws,
                       int64_t ws_words, int64_t *const *out0, int64_t *const *out1, void *stream) {
-    if (!plan_ok(p) || nr < 1 || !c0 || !c1 || !p_host || !ksk || !out0 || !out1 || (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES))
+    if (!plan_ok(p) || nr < 1 || !c0 || !c1 || !out0 || !out1 || !lf_keys_ok({ksk, nr, part_stride, comp_stride, row_off, key_format}) ||
+        !lf_exponents_ok(p_host, nr, p->logN))
         return LF_ERR_ARG;
     const int rows = p->ell + p->K, logN = p->logN, dev = p->device;
     const int64_t N = (int64_t)1 << logN, twoN = 2 * N;
-    for (int i = 0; i < nr; ++i) {
-        if (!ksk[i] || !out0[i] || !out1[i] || p_host[i] <= 0 || p_host[i] >= twoN || !(p_host[i] & 1)) return LF_ERR_ARG;
-        if (key_format == LF_KEY_PLANES && ((((uintptr_t)ksk[i] | (uintptr_t)(part_stride * 8) | (uintptr_t)(comp_stride * 8)) & 15)))
-            return LF_ERR_ARG;   // (the planes loads are 16 bytes wide)
-    }
+    for (int i = 0; i < nr; ++i)
+        if (!out0[i] || !out1[i]) return LF_ERR_ARG;
     const int64_t need = lf_rotate_hoisted_ws_words(p);
     if (need && (!ws || ws_words < need)) return LF_ERR_ARG;
     int64_t *scratch = need ? ws : p->ext + ((int64_t)p->nparts * rows << logN);
@@ -730,20 +624,14 @@ int lf_rotate_hoisted(const lf_ks_plan *p, const int64_t *c0, const int64_t *c1,
     for (int i0 = 0; i0 < nr;) {
         const int left = nr - i0, gmax = hoist_group_max(p);
         const int g = left >= 4 && gmax >= 4 ? 4 : left >= 2 && gmax >= 2 ? 2 : 1;
-        unsigned pe[4];
-        for (int t = 0; t < g; ++t) pe[t] = (unsigned)p_host[i0 + t];
-        if (int e = lf_ks_tail_hoisted(g, pe, p->nparts, rows, logN, ksk + i0, part_stride, comp_stride, row_off, key_format, p->ext, p->sum,
-                                       scratch, scratch_words, p->ipsi, p->ipsi_dp, p->Ninv, p->q_host, p->ql, p->qh, p->kl, p->kh,
-                                       (hipStream_t)stream))
+        if (int e = lf_ks_tail_hoisted(p_host + i0, p->nparts, rows, logN, {ksk + i0, g, part_stride, comp_stride, row_off, key_format}, p->ext,
+                                       p->sum, scratch, scratch_words, plan_inv(p), plan_mod(p), (hipStream_t)stream))
             return e;
         for (int t = 0; t < g; ++t) {
             uint64_t x = (uint64_t)p_host[i0 + t], inv = x;   // p^-1 mod 2^64 by Newton's iteration (p odd), then mod 2N
             for (int k = 0; k < 6; ++k) inv *= 2 - x * inv;
             const int64_t pinv = (int64_t)(inv & (uint64_t)(twoN - 1));
-            const int64_t *ss[2] = {p->sum + (int64_t)(2 * t) * rows * N, p->sum + (int64_t)(2 * t + 1) * rows * N};
-            int64_t *outs[2] = {out0[i0 + t], out1[i0 + t]};
-            const int64_t *adds[2] = {c0, nullptr};
-            if (int e = moddown_any(p, ss, outs, adds, 2, pinv, g2q, stream)) return e;
+            if (int e = moddown_pairs(p, p->sum + (int64_t)(2 * t) * rows * N, 1, out0 + i0 + t, out1 + i0 + t, &c0, pinv, g2q, stream)) return e;
         }
         i0 += g;
     }
@@ -762,32 +650,19 @@ int lf_linear_transform(const lf_ks_plan *p, const int64_t *c0, const int64_t *c
                         const int64_t *const *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format,
                         const int64_t *pt, int64_t pt_stride, const int64_t *pt0, const int64_t *rescale_scales, int64_t round_at,
                         int64_t *ws, int64_t ws_words, int64_t *out0, int64_t *out1, void *stream) {
-    if (!plan_ok(p) || !p->PR || p->ell < 2 || nr < 0 || (nr == 0 && !pt0) || !c0 || !c1 || !rescale_scales || !out0 || !out1 ||
-        (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES))
+    const LfKeys key{ksk, nr, part_stride, comp_stride, row_off, key_format};
+    if (!plan_ok(p) || !p->PR || p->ell < 2 || (nr == 0 && !pt0) || !c0 || !c1 || !rescale_scales || !out0 || !out1 || !lf_keys_ok(key) ||
+        !lf_exponents_ok(p_host, nr, p->logN))
         return LF_ERR_ARG;
     const int ell = p->ell, rows = p->ell + p->K, logN = p->logN, dev = p->device;
-    const int64_t N = (int64_t)1 << logN, twoN = 2 * N, poly = (int64_t)ell * N;
-    if (nr && (!p_host || !ksk || !pt || pt_stride < (int64_t)rows * N)) return LF_ERR_ARG;
-    for (int i = 0; i < nr; ++i) {
-        if (!ksk[i] || p_host[i] <= 0 || p_host[i] >= twoN || !(p_host[i] & 1)) return LF_ERR_ARG;
-        if (key_format == LF_KEY_PLANES && ((((uintptr_t)ksk[i] | (uintptr_t)(part_stride * 8) | (uintptr_t)(comp_stride * 8)) & 15)))
-            return LF_ERR_ARG;
-    }
+    const int64_t N = (int64_t)1 << logN, poly = (int64_t)ell * N;
+    if (nr && (!pt || pt_stride < (int64_t)rows * N)) return LF_ERR_ARG;
     const int64_t need = lf_linear_transform_ws_words(p);
     if (need && (!ws || ws_words < need)) return LF_ERR_ARG;
     int64_t *chat = need ? ws : p->x4, *md = chat + 2 * poly;
-    // 1. P NTT(c0) (and P NTT(c1) for the step-0 term) on the ordinary rows: canonical copy, enter_ntt (exact: lazy Montgomery
-    //    words below 2q on rows of both classes, what the kernel adds unreduced), times P R
-    const int nc = pt0 ? 2 : 1;
-    {
-        const int64_t *srcs[2] = {c0, c1};
-        int64_t *dsts[2] = {chat, chat + poly};
-        if (int e = lf_galois_batch(srcs, dsts, nc, ell, logN, 1, p->_2q, dev, stream)) return e;
-        if (int e = lf_ntt(chat, nc, ell, logN, p->psi, p->psi_dp, p->q_host, p->Rs, 0, p->_2q, p->ql, p->qh, p->kl, p->kh, dev, stream))
-            return e;
-        for (int c = 0; c < nc; ++c)
-            if (int e = lf_mont_enter(chat + c * poly, p->PR, ell, N, p->ql, p->qh, p->kl, p->kh, dev, stream)) return e;
-    }
+    // 1. P NTT(c0) (and P NTT(c1) for the step-0 term) on the ordinary rows
+    const int64_t *srcs[2] = {c0, c1};
+    if (int e = p_ntt(p, srcs, pt0 ? 2 : 1, chat, poly, stream)) return e;
     // 2. digits of c1 (canonical, no permutation), their extension + forward NTT: once, as lf_rotate_hoisted
     if (nr) {
         if (int e = lf_ks_digits_galois(c1, p->state, p->dig_nparts, p->dig_desc, p->dig_tab, N, 1, p->_2q, p->ql, p->qh, p->kl, p->kh, dev,
@@ -799,17 +674,11 @@ int lf_linear_transform(const lf_ks_plan *p, const int64_t *c0, const int64_t *c
     }
     // 3. the groups' launches into the one pair of sums, its inverse NTT (planes through the spent digits, two slots or more)
     const int64_t spare = p->nparts >= 2 ? ((int64_t)p->nparts * rows) << logN : 0;
-    if (int e = lf_ks_tail_lt(nr, p_host, p->nparts, rows, ell, logN, ksk, part_stride, comp_stride, row_off, key_format, pt, pt_stride, pt0,
-                              chat, p->ext, p->sum, spare ? p->ext : nullptr, spare, p->ipsi, p->ipsi_dp, p->Ninv, p->q_host, p->ql, p->qh,
-                              p->kl, p->kh, (hipStream_t)stream))
+    if (int e = lf_ks_tail_lt(p_host, p->nparts, rows, ell, logN, key, pt, pt_stride, pt0, chat, p->ext, p->sum, spare ? p->ext : nullptr, spare,
+                              plan_inv(p), plan_mod(p), (hipStream_t)stream))
         return e;
     // 4. one mod-down, one rescale into the caller's [ell - 1][N] pair
-    const int64_t *ss[2] = {p->sum, p->sum + (int64_t)rows * N};
-    int64_t *mds[2] = {md, md + poly};
-    if (int e = moddown_any(p, ss, mds, nullptr, 2, 0, nullptr, stream)) return e;
-    const int64_t *ins[2] = {md + N, md + poly + N}, *row0[2] = {md, md + poly};
-    int64_t *outs[2] = {out0, out1};
-    return lf_rescale_batch(ins, row0, outs, 2, ell - 1, N, rescale_scales, round_at, p->ql + 1, p->qh + 1, p->kl + 1, p->kh + 1, dev, stream);
+    return moddown_rescale_pairs(p, p->sum, 1, md, nullptr, 0, &out0, &out1, rescale_scales, round_at, stream);
 }
 
 /* ---- linear transform of many ciphertexts under the same diagonals and keys (include/ckks_hip.h): groups of 4, 2 or 1; a group
@@ -830,17 +699,13 @@ int lf_linear_transform_batch(const lf_ks_plan *p, int nct, const int64_t *const
                               int64_t row_off, int key_format, const int64_t *pt, int64_t pt_stride, const int64_t *pt0,
                               const int64_t *rescale_scales, int64_t round_at, int64_t *ws, int64_t ws_words, int64_t *const *out0,
                               int64_t *const *out1, void *stream) {
-    if (!plan_ok(p) || !p->PR || p->ell < 2 || nct < 1 || nct > LF_LT_BATCH_MAX_CTS || nr < 0 || (nr == 0 && !pt0) || !c0 || !c1 ||
-        !rescale_scales || !out0 || !out1 || (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES))
+    const LfKeys key{ksk, nr, part_stride, comp_stride, row_off, key_format};
+    if (!plan_ok(p) || !p->PR || p->ell < 2 || nct < 1 || nct > LF_LT_BATCH_MAX_CTS || (nr == 0 && !pt0) || !c0 || !c1 || !rescale_scales ||
+        !out0 || !out1 || !lf_keys_ok(key) || !lf_exponents_ok(p_host, nr, p->logN))
         return LF_ERR_ARG;
     const int ell = p->ell, rows = p->ell + p->K, logN = p->logN, dev = p->device;
-    const int64_t N = (int64_t)1 << logN, twoN = 2 * N, poly = (int64_t)ell * N;
-    if (nr && (!p_host || !ksk || !pt || pt_stride < (int64_t)rows * N)) return LF_ERR_ARG;
-    for (int i = 0; i < nr; ++i) {
-        if (!ksk[i] || p_host[i] <= 0 || p_host[i] >= twoN || !(p_host[i] & 1)) return LF_ERR_ARG;
-        if (key_format == LF_KEY_PLANES && ((((uintptr_t)ksk[i] | (uintptr_t)(part_stride * 8) | (uintptr_t)(comp_stride * 8)) & 15)))
-            return LF_ERR_ARG;
-    }
+    const int64_t N = (int64_t)1 << logN, poly = (int64_t)ell * N;
+    if (nr && (!pt || pt_stride < (int64_t)rows * N)) return LF_ERR_ARG;
     for (int t = 0; t < nct; ++t)
         if (!c0[t] || !c1[t] || !out0[t] || !out1[t]) return LF_ERR_ARG;
     const int64_t need = lf_linear_transform_batch_ws_words(p, nct);
@@ -861,14 +726,9 @@ int lf_linear_transform_batch(const lf_ks_plan *p, int nct, const int64_t *const
         int64_t *chat = base, *md = base + 2 * g * poly;
         {
             const int64_t *srcs[8];
-            int64_t *dsts[8];
             for (int t = 0; t < g; ++t)
-                for (int c = 0; c < nc; ++c) srcs[t * nc + c] = c ? c1[t0 + t] : c0[t0 + t], dsts[t * nc + c] = chat + (t * nc + c) * poly;
-            if (int e = lf_galois_batch(srcs, dsts, g * nc, ell, logN, 1, p->_2q, dev, stream)) return e;
-            if (int e = lf_ntt(chat, g * nc, ell, logN, p->psi, p->psi_dp, p->q_host, p->Rs, 0, p->_2q, p->ql, p->qh, p->kl, p->kh, dev, stream))
-                return e;
-            for (int i = 0; i < g * nc; ++i)
-                if (int e = lf_mont_enter(chat + i * poly, p->PR, ell, N, p->ql, p->qh, p->kl, p->kh, dev, stream)) return e;
+                for (int c = 0; c < nc; ++c) srcs[t * nc + c] = c ? c1[t0 + t] : c0[t0 + t];
+            if (int e = p_ntt(p, srcs, g * nc, chat, poly, stream)) return e;
         }
         // 2. the digits of the g c1 (canonical, no permutation), ONE extension + forward NTT of all of them
         if (nr) {
@@ -878,28 +738,17 @@ int lf_linear_transform_batch(const lf_ks_plan *p, int nct, const int64_t *const
             if (int e = lf_ks_digits_batch(srcs, states, g, p->dig_nparts, p->dig_desc, p->dig_tab, N, 1, p->_2q, p->ql, p->qh, p->kl, p->kh, dev,
                                            stream))
                 return e;
-            if (int e = lf_ks_fwd_batch(p->state, poly, g, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, p->ext, p->psi, p->psi_dp, p->q_host,
-                                        p->ql, p->qh, p->kl, p->kh, (hipStream_t)stream))
+            if (int e = lf_ks_fwd_batch(p->state, poly, g, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, p->ext, plan_fwd(p), plan_mod(p),
+                                        (hipStream_t)stream))
                 return e;
         }
         // 3. the launches into the g pairs of sums, ONE inverse NTT of the 2 g polynomials (planes through the spent digits)
         const int64_t spare = p->nparts >= 2 ? ((int64_t)g * p->nparts * rows) << logN : 0;
-        if (int e = lf_ks_tail_ltb(g, nr, p_host, p->nparts, rows, ell, logN, ksk, part_stride, comp_stride, row_off, key_format, pt, pt_stride, pt0,
-                                   chat, nc * poly, p->ext, p->sum, spare ? p->ext : nullptr, spare, p->ipsi, p->ipsi_dp, p->Ninv, p->q_host,
-                                   p->ql, p->qh, p->kl, p->kh, (hipStream_t)stream))
+        if (int e = lf_ks_tail_ltb(g, p_host, p->nparts, rows, ell, logN, key, pt, pt_stride, pt0, chat, nc * poly, p->ext, p->sum,
+                                   spare ? p->ext : nullptr, spare, plan_inv(p), plan_mod(p), (hipStream_t)stream))
             return e;
         // 4. one mod-down and one rescale of the 2 g polynomials into the callers' [ell - 1][N] pairs
-        const int64_t *ss[8], *ins[8], *row0[8];
-        int64_t *mds[8], *outs[8];
-        for (int t = 0; t < 2 * g; ++t) {
-            ss[t] = p->sum + t * (int64_t)rows * N;
-            mds[t] = md + t * poly, row0[t] = mds[t], ins[t] = mds[t] + N;
-            outs[t] = (t & 1) ? out1[t0 + t / 2] : out0[t0 + t / 2];
-        }
-        if (int e = moddown_any(p, ss, mds, nullptr, 2 * g, 0, nullptr, stream)) return e;
-        if (int e = lf_rescale_batch(ins, row0, outs, 2 * g, ell - 1, N, rescale_scales, round_at, p->ql + 1, p->qh + 1, p->kl + 1, p->kh + 1,
-                                     dev, stream))
-            return e;
+        if (int e = moddown_rescale_pairs(p, p->sum, g, md, nullptr, 0, out0 + t0, out1 + t0, rescale_scales, round_at, stream)) return e;
         t0 += g;
     }
     return 0;
@@ -916,31 +765,18 @@ int64_t lf_rotate_sum_ws_words(const lf_ks_plan *p) {
 int lf_rotate_sum(const lf_ks_plan *p, const int64_t *c0, const int64_t *c1, int nr, const int64_t *p_host,
                   const int64_t *const *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format,
                   int with_self, int64_t *ws, int64_t ws_words, int64_t *out0, int64_t *out1, void *stream) {
-    if (!plan_ok(p) || !p->PR || nr < 0 || (nr == 0 && !with_self) || !c0 || !c1 || !out0 || !out1 ||
-        (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES))
+    const LfKeys key{ksk, nr, part_stride, comp_stride, row_off, key_format};
+    if (!plan_ok(p) || !p->PR || (nr == 0 && !with_self) || !c0 || !c1 || !out0 || !out1 || !lf_keys_ok(key) ||
+        !lf_exponents_ok(p_host, nr, p->logN))
         return LF_ERR_ARG;
     const int ell = p->ell, rows = p->ell + p->K, logN = p->logN, dev = p->device;
-    const int64_t N = (int64_t)1 << logN, twoN = 2 * N, poly = (int64_t)ell * N;
-    if (nr && (!p_host || !ksk)) return LF_ERR_ARG;
-    for (int i = 0; i < nr; ++i) {
-        if (!ksk[i] || p_host[i] <= 0 || p_host[i] >= twoN || !(p_host[i] & 1)) return LF_ERR_ARG;
-        if (key_format == LF_KEY_PLANES && ((((uintptr_t)ksk[i] | (uintptr_t)(part_stride * 8) | (uintptr_t)(comp_stride * 8)) & 15)))
-            return LF_ERR_ARG;
-    }
+    const int64_t N = (int64_t)1 << logN, poly = (int64_t)ell * N;
     const int64_t need = lf_rotate_sum_ws_words(p);
     if (need && (!ws || ws_words < need)) return LF_ERR_ARG;
     int64_t *chat = need ? ws : p->x4;
     // 1. P NTT(c0) (and P NTT(c1) for the self term) on the ordinary rows, as lf_linear_transform forms them
-    const int nc = with_self ? 2 : 1;
-    {
-        const int64_t *srcs[2] = {c0, c1};
-        int64_t *dsts[2] = {chat, chat + poly};
-        if (int e = lf_galois_batch(srcs, dsts, nc, ell, logN, 1, p->_2q, dev, stream)) return e;
-        if (int e = lf_ntt(chat, nc, ell, logN, p->psi, p->psi_dp, p->q_host, p->Rs, 0, p->_2q, p->ql, p->qh, p->kl, p->kh, dev, stream))
-            return e;
-        for (int c = 0; c < nc; ++c)
-            if (int e = lf_mont_enter(chat + c * poly, p->PR, ell, N, p->ql, p->qh, p->kl, p->kh, dev, stream)) return e;
-    }
+    const int64_t *srcs[2] = {c0, c1};
+    if (int e = p_ntt(p, srcs, with_self ? 2 : 1, chat, poly, stream)) return e;
     // 2. digits of c1 (canonical, no permutation), their extension + forward NTT: once, as lf_rotate_hoisted
     if (nr) {
         if (int e = lf_ks_digits_galois(c1, p->state, p->dig_nparts, p->dig_desc, p->dig_tab, N, 1, p->_2q, p->ql, p->qh, p->kl, p->kh, dev,
@@ -952,14 +788,11 @@ int lf_rotate_sum(const lf_ks_plan *p, const int64_t *c0, const int64_t *c1, int
     }
     // 3. the groups' launches into the one pair of sums, its inverse NTT (planes through the spent digits, two slots or more)
     const int64_t spare = p->nparts >= 2 ? ((int64_t)p->nparts * rows) << logN : 0;
-    if (int e = lf_ks_tail_rsum(nr, p_host, p->nparts, rows, ell, logN, ksk, part_stride, comp_stride, row_off, key_format, with_self, chat,
-                                p->ext, p->sum, spare ? p->ext : nullptr, spare, p->ipsi, p->ipsi_dp, p->Ninv, p->q_host, p->ql, p->qh,
-                                p->kl, p->kh, (hipStream_t)stream))
+    if (int e = lf_ks_tail_rsum(p_host, p->nparts, rows, ell, logN, key, with_self, chat, p->ext, p->sum, spare ? p->ext : nullptr, spare,
+                                plan_inv(p), plan_mod(p), (hipStream_t)stream))
         return e;
     // 4. one mod-down, straight into the caller's [ell][N] pair: no rescale, the level stays
-    const int64_t *ss[2] = {p->sum, p->sum + (int64_t)rows * N};
-    int64_t *outs[2] = {out0, out1};
-    return moddown_any(p, ss, outs, nullptr, 2, 0, nullptr, stream);
+    return moddown_pairs(p, p->sum, 1, &out0, &out1, nullptr, 0, nullptr, stream);
 }
 
 /* ---- rotation sum of many ciphertexts under the same keys (include/ckks_hip.h): groups of 4, 2 or 1 as lt_batch_group takes
@@ -974,17 +807,12 @@ int lf_rotate_sum_batch(const lf_ks_plan *p, int nct, const int64_t *const *c0, 
                         const int64_t *p_host, const int64_t *const *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off,
                         int key_format, int with_self, int64_t *ws, int64_t ws_words, int64_t *const *out0, int64_t *const *out1,
                         void *stream) {
-    if (!plan_ok(p) || !p->PR || nct < 1 || nct > LF_LT_BATCH_MAX_CTS || nr < 0 || (nr == 0 && !with_self) || !c0 || !c1 || !out0 ||
-        !out1 || (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES))
+    const LfKeys key{ksk, nr, part_stride, comp_stride, row_off, key_format};
+    if (!plan_ok(p) || !p->PR || nct < 1 || nct > LF_LT_BATCH_MAX_CTS || (nr == 0 && !with_self) || !c0 || !c1 || !out0 || !out1 ||
+        !lf_keys_ok(key) || !lf_exponents_ok(p_host, nr, p->logN))
         return LF_ERR_ARG;
     const int ell = p->ell, rows = p->ell + p->K, logN = p->logN, dev = p->device;
-    const int64_t N = (int64_t)1 << logN, twoN = 2 * N, poly = (int64_t)ell * N;
-    if (nr && (!p_host || !ksk)) return LF_ERR_ARG;
-    for (int i = 0; i < nr; ++i) {
-        if (!ksk[i] || p_host[i] <= 0 || p_host[i] >= twoN || !(p_host[i] & 1)) return LF_ERR_ARG;
-        if (key_format == LF_KEY_PLANES && ((((uintptr_t)ksk[i] | (uintptr_t)(part_stride * 8) | (uintptr_t)(comp_stride * 8)) & 15)))
-            return LF_ERR_ARG;
-    }
+    const int64_t N = (int64_t)1 << logN, poly = (int64_t)ell * N;
     for (int t = 0; t < nct; ++t)
         if (!c0[t] || !c1[t] || !out0[t] || !out1[t]) return LF_ERR_ARG;
     const int64_t need = lf_rotate_sum_batch_ws_words(p, nct);
@@ -1004,14 +832,9 @@ int lf_rotate_sum_batch(const lf_ks_plan *p, int nct, const int64_t *const *c0, 
         //    chat [g][nc][ell][N], one canonical copy and one forward transform for the group
         {
             const int64_t *srcs[8];
-            int64_t *dsts[8];
             for (int t = 0; t < g; ++t)
-                for (int c = 0; c < nc; ++c) srcs[t * nc + c] = c ? c1[t0 + t] : c0[t0 + t], dsts[t * nc + c] = chat + (t * nc + c) * poly;
-            if (int e = lf_galois_batch(srcs, dsts, g * nc, ell, logN, 1, p->_2q, dev, stream)) return e;
-            if (int e = lf_ntt(chat, g * nc, ell, logN, p->psi, p->psi_dp, p->q_host, p->Rs, 0, p->_2q, p->ql, p->qh, p->kl, p->kh, dev, stream))
-                return e;
-            for (int i = 0; i < g * nc; ++i)
-                if (int e = lf_mont_enter(chat + i * poly, p->PR, ell, N, p->ql, p->qh, p->kl, p->kh, dev, stream)) return e;
+                for (int c = 0; c < nc; ++c) srcs[t * nc + c] = c ? c1[t0 + t] : c0[t0 + t];
+            if (int e = p_ntt(p, srcs, g * nc, chat, poly, stream)) return e;
         }
         // 2. the digits of the g c1 (canonical, no permutation), ONE extension + forward NTT of all of them
         if (nr) {
@@ -1021,24 +844,17 @@ int lf_rotate_sum_batch(const lf_ks_plan *p, int nct, const int64_t *const *c0, 
             if (int e = lf_ks_digits_batch(srcs, states, g, p->dig_nparts, p->dig_desc, p->dig_tab, N, 1, p->_2q, p->ql, p->qh, p->kl, p->kh, dev,
                                            stream))
                 return e;
-            if (int e = lf_ks_fwd_batch(p->state, poly, g, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, p->ext, p->psi, p->psi_dp, p->q_host,
-                                        p->ql, p->qh, p->kl, p->kh, (hipStream_t)stream))
+            if (int e = lf_ks_fwd_batch(p->state, poly, g, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, p->ext, plan_fwd(p), plan_mod(p),
+                                        (hipStream_t)stream))
                 return e;
         }
         // 3. the launches into the g pairs of sums, ONE inverse NTT of the 2 g polynomials (planes through the spent digits)
         const int64_t spare = p->nparts >= 2 ? ((int64_t)g * p->nparts * rows) << logN : 0;
-        if (int e = lf_ks_tail_rsumb(g, nr, p_host, p->nparts, rows, ell, logN, ksk, part_stride, comp_stride, row_off, key_format, with_self,
-                                     chat, nc * poly, p->ext, p->sum, spare ? p->ext : nullptr, spare, p->ipsi, p->ipsi_dp, p->Ninv,
-                                     p->q_host, p->ql, p->qh, p->kl, p->kh, (hipStream_t)stream))
+        if (int e = lf_ks_tail_rsumb(g, p_host, p->nparts, rows, ell, logN, key, with_self, chat, nc * poly, p->ext, p->sum,
+                                     spare ? p->ext : nullptr, spare, plan_inv(p), plan_mod(p), (hipStream_t)stream))
             return e;
         // 4. one mod-down of the 2 g polynomials, straight into the callers' [ell][N] pairs: no rescale, the level stays
-        const int64_t *ss[8];
-        int64_t *outs[8];
-        for (int t = 0; t < 2 * g; ++t) {
-            ss[t] = p->sum + t * (int64_t)rows * N;
-            outs[t] = (t & 1) ? out1[t0 + t / 2] : out0[t0 + t / 2];
-        }
-        if (int e = moddown_any(p, ss, outs, nullptr, 2 * g, 0, nullptr, stream)) return e;
+        if (int e = moddown_pairs(p, p->sum, g, out0 + t0, out1 + t0, nullptr, 0, nullptr, stream)) return e;
         t0 += g;
     }
     return 0;
@@ -1056,6 +872,12 @@ int64_t lf_linear_transform_bsgs_ws_words(const lf_ks_plan *p, int nb) {
     return pair * (nb + 1 + LF_BSGS_S_PAIRS + 1) + poly + 2 * poly + lf_ks_moddown_ws_words(1, p->ell, p->K, N);
 }
 
+// n keyed steps of a baby-step / giant-step op: their keys (lf_keys_ok) and their exponents (lf_exponents_ok)
+static bool keyed_steps_ok(const int64_t *const *ksk, const int64_t *p_host, int n, int64_t part_stride, int64_t comp_stride, int key_format,
+                           int logN) {
+    return lf_keys_ok({ksk, n, part_stride, comp_stride, 0, key_format}) && lf_exponents_ok(p_host, n, logN);
+}
+
 // what lf_linear_transform_bsgs refuses in its keys, giant steps and diagonals (everything but the ciphertext, the outputs and the
 // workspace): 0 or LF_ERR_ARG, nothing launched
 static int bsgs_args_ok(const lf_ks_plan *p, int nb, const int64_t *bp_host, const int64_t *const *bksk, int ng, const int64_t *gp_host,
@@ -1064,17 +886,13 @@ static int bsgs_args_ok(const lf_ks_plan *p, int nb, const int64_t *bp_host, con
     if (!plan_ok(p) || !p->PR || p->ell < 2 || nb < 0 || nb > LF_BSGS_MAX_BABY_KEYS || ng < 1 || !rescale_scales || !pt || !gp_host ||
         !gksk || !gcount || !bidx || (nb && (!bp_host || !bksk)) || (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES))
         return LF_ERR_ARG;
-    const int64_t N = (int64_t)1 << p->logN, twoN = 2 * N;
+    const int64_t N = (int64_t)1 << p->logN;
     if (pt_stride < (int64_t)(p->ell + p->K) * N) return LF_ERR_ARG;
-    auto key_ok = [&](const int64_t *k, int64_t e) {
-        if (!k || e <= 0 || e >= twoN || !(e & 1)) return false;
-        return key_format != LF_KEY_PLANES || !((((uintptr_t)k | (uintptr_t)(part_stride * 8) | (uintptr_t)(comp_stride * 8)) & 15));
-    };
-    for (int i = 0; i < nb; ++i)
-        if (!key_ok(bksk[i], bp_host[i])) return LF_ERR_ARG;
+    if (!keyed_steps_ok(bksk, bp_host, nb, part_stride, comp_stride, key_format, p->logN)) return LF_ERR_ARG;
     int64_t ndiag = 0;
     for (int i = 0; i < ng; ++i) {
-        if (gp_host[i] == 0 ? i != 0 : !key_ok(gksk[i], gp_host[i])) return LF_ERR_ARG;   // (giant step 0: first, so at most once)
+        // (giant step 0: first, so at most once)
+        if (gp_host[i] == 0 ? i != 0 : !keyed_steps_ok(gksk + i, gp_host + i, 1, part_stride, comp_stride, key_format, p->logN)) return LF_ERR_ARG;
         if (gcount[i] < 1 || gcount[i] > nb + 1) return LF_ERR_ARG;
         for (int64_t k = 0; k < gcount[i]; ++k) {
             const int64_t slot = bidx[ndiag + k];
@@ -1105,14 +923,9 @@ int lf_linear_transform_bsgs(const lf_ks_plan *p, const int64_t *c0, const int64
     // 1. slot 0 = P NTT(c0), P NTT(c1) on the ordinary rows (canonical copy, enter_ntt, times P R), zero on the special rows
     {
         const int64_t *srcs[2] = {c0, c1};
-        int64_t *dsts[2] = {u, u + (int64_t)rows * N};
-        if (int e = lf_galois_batch(srcs, dsts, 2, ell, logN, 1, p->_2q, dev, stream)) return e;
-        for (int c = 0; c < 2; ++c) {
-            if (int e = lf_ntt(dsts[c], 1, ell, logN, p->psi, p->psi_dp, p->q_host, p->Rs, 0, p->_2q, p->ql, p->qh, p->kl, p->kh, dev, stream))
-                return e;
-            if (int e = lf_mont_enter(dsts[c], p->PR, ell, N, p->ql, p->qh, p->kl, p->kh, dev, stream)) return e;
-            if (hipError_t e = hipMemsetAsync(dsts[c] + poly, 0, (size_t)p->K * N * 8, st)) return (int)e;
-        }
+        if (int e = p_ntt(p, srcs, 2, u, (int64_t)rows * N, stream)) return e;
+        for (int c = 0; c < 2; ++c)
+            if (hipError_t e = hipMemsetAsync(u + c * (int64_t)rows * N + poly, 0, (size_t)p->K * N * 8, st)) return (int)e;
     }
     // 2. baby steps: the digits of c1 extended and transformed once, per group of keys one launch into the slots 1 .. nb
     if (nb) {
@@ -1122,8 +935,8 @@ int lf_linear_transform_bsgs(const lf_ks_plan *p, const int64_t *c0, const int64
         if (int e = lf_ks_fwd(p->state, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, p->ext, p->psi, p->psi_dp, p->q_host, p->ql, p->qh,
                               p->kl, p->kh, dev, stream))
             return e;
-        if (int e = lf_ks_baby_sums(nb, bp_host, p->nparts, rows, ell, logN, bksk, part_stride, comp_stride, row_off, key_format, u, p->ext,
-                                    u + pair, p->q_host, p->ql, p->qh, p->kl, p->kh, st))
+        if (int e = lf_ks_baby_sums(bp_host, p->nparts, rows, ell, logN, {bksk, nb, part_stride, comp_stride, row_off, key_format}, u, p->ext,
+                                    u + pair, plan_mod(p), st))
             return e;
     }
     // 3. giant steps, LF_BSGS_S_PAIRS per launch of the diagonal products; giant step 0 writes the accumulator itself
@@ -1142,7 +955,7 @@ int lf_linear_transform_bsgs(const lf_ks_plan *p, const int64_t *c0, const int64
             outs[t] = gp_host[i0 + t] == 0 ? A : S + t * pair;
             first += gcount[i0 + t];
         }
-        if (int e = lf_lt_diag_products(g, u, nb + 1, pts, slots, pt_stride, outs, rows, logN, p->ql, p->qh, p->kl, p->kh, st)) return e;
+        if (int e = lf_lt_diag_products(g, u, nb + 1, pts, slots, pt_stride, outs, rows, logN, plan_mod(p), st)) return e;
         for (int t = 0; t < g; ++t) {
             if (gp_host[i0 + t] == 0) continue;
             int64_t *S0 = S + t * pair, *S1 = S0 + (int64_t)rows * N;
@@ -1160,8 +973,8 @@ int lf_linear_transform_bsgs(const lf_ks_plan *p, const int64_t *c0, const int64
             if (int e = lf_ks_fwd(p->state, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, p->ext, p->psi, p->psi_dp, p->q_host, p->ql,
                                   p->qh, p->kl, p->kh, dev, stream))
                 return e;
-            if (int e = lf_ks_giant_sums(gp_host[i0 + t], p->nparts, rows, logN, gksk[i0 + t], part_stride, comp_stride, row_off, key_format,
-                                         p->ext, S0, A, p->q_host, p->ql, p->qh, p->kl, p->kh, st))
+            if (int e = lf_ks_giant_sums(gp_host[i0 + t], p->nparts, rows, logN, {gksk + i0 + t, 1, part_stride, comp_stride, row_off, key_format},
+                                         p->ext, S0, A, plan_mod(p), st))
                 return e;
         }
         i0 += g;
@@ -1169,12 +982,7 @@ int lf_linear_transform_bsgs(const lf_ks_plan *p, const int64_t *c0, const int64
     // 4. one exact inverse NTT of the accumulator (intt_exit_reduce), one mod-down, one rescale into the caller's [ell - 1][N] pair
     if (int e = lf_intt(A, 2, rows, logN, p->ipsi, p->ipsi_dp, p->q_host, p->Ninv, 2, 0, p->_2q, p->ql, p->qh, p->kl, p->kh, dev, stream))
         return e;
-    const int64_t *ss[2] = {A, A + (int64_t)rows * N};
-    int64_t *mds[2] = {md, md + poly};
-    if (int e = moddown_any(p, ss, mds, nullptr, 2, 0, nullptr, stream)) return e;
-    const int64_t *ins[2] = {md + N, md + poly + N}, *row0[2] = {md, md + poly};
-    int64_t *outs[2] = {out0, out1};
-    return lf_rescale_batch(ins, row0, outs, 2, ell - 1, N, rescale_scales, round_at, p->ql + 1, p->qh + 1, p->kl + 1, p->kh + 1, dev, stream);
+    return moddown_rescale_pairs(p, A, 1, md, nullptr, 0, &out0, &out1, rescale_scales, round_at, stream);
 }
 
 /* ---- a matrix of linear transforms times a vector of ciphertexts: y_o = sum_i sum_step diag_{o,i,step} * rot(x_i, step)
@@ -1204,7 +1012,7 @@ static int lt_matmul_args(const lf_ks_plan *p, int nt, int k_in, int k_out, cons
         (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES))
         return LF_ERR_ARG;
     const int rows = p->ell + p->K;
-    const int64_t N = (int64_t)1 << p->logN, twoN = 2 * N;
+    const int64_t N = (int64_t)1 << p->logN;
     // the columns: keyed steps per input, the inputs some output uses, their keys
     koff.assign(k_in + 1, 0);
     used.assign(k_in, 0);
@@ -1217,11 +1025,8 @@ static int lt_matmul_args(const lf_ks_plan *p, int nt, int k_in, int k_out, cons
         for (int t = 0; t < nt; ++t)
             if (!in[2 * ((int64_t)t * k_in + i)] || !in[2 * ((int64_t)t * k_in + i) + 1]) return LF_ERR_ARG;
         if (ncol[i] && (!p_host || !ksk)) return LF_ERR_ARG;
-        for (int64_t k = koff[i]; k < koff[i + 1]; ++k) {
-            if (!ksk[k] || p_host[k] <= 0 || p_host[k] >= twoN || !(p_host[k] & 1)) return LF_ERR_ARG;
-            if (key_format == LF_KEY_PLANES && ((((uintptr_t)ksk[k] | (uintptr_t)(part_stride * 8) | (uintptr_t)(comp_stride * 8)) & 15)))
-                return LF_ERR_ARG;
-        }
+        if (ncol[i] && !keyed_steps_ok(ksk + koff[i], p_host + koff[i], (int)ncol[i], part_stride, comp_stride, key_format, p->logN))
+            return LF_ERR_ARG;
         if (ncol[i] > nb_max) nb_max = (int)ncol[i];
     }
     // the blocks: per output at least one; per block its slots inside the column's set, ascending
@@ -1249,6 +1054,38 @@ static int lt_matmul_args(const lf_ks_plan *p, int nt, int k_in, int k_out, cons
         if (!any) return LF_ERR_ARG;
     }
     return 0;
+}
+
+// the tail of the lf_lt_matmul family: n sums [n][2][rows][N] at S in Q P, in groups of up to LF_LT_MATMUL_GROUP: one exact inverse
+// NTT (intt_exit_reduce) of the group's 2 g polynomials, one mod-down in mdws, one rescale into the pairs out0[s], out1[s]
+static int matmul_tail(const lf_ks_plan *p, int64_t *S, int n, int64_t *md, int64_t *mdws, int64_t mdws_words, int64_t *const *out0,
+                       int64_t *const *out1, const int64_t *rescale_scales, int64_t round_at, void *stream) {
+    const int rows = p->ell + p->K;
+    const int64_t pair = (2 * (int64_t)rows) << p->logN;
+    for (int s0 = 0; s0 < n; s0 += LF_LT_MATMUL_GROUP) {
+        const int g = n - s0 < LF_LT_MATMUL_GROUP ? n - s0 : LF_LT_MATMUL_GROUP;
+        int64_t *Sg = S + s0 * pair;
+        if (int e = lf_intt(Sg, 2 * g, rows, p->logN, p->ipsi, p->ipsi_dp, p->q_host, p->Ninv, 2, 0, p->_2q, p->ql, p->qh, p->kl, p->kh,
+                            p->device, stream))
+            return e;
+        if (int e = moddown_rescale_pairs(p, Sg, g, md, mdws, mdws_words, out0 + s0, out1 + s0, rescale_scales, round_at, stream)) return e;
+    }
+    return 0;
+}
+
+// steps 1 and 2 of lf_lt_matmul for one input c = {c0, c1}: slot 0 of u = P NTT(c0), P NTT(c1) on the ordinary rows; the digits of
+// c1 extended and transformed once, per group of the column's keys one launch into the slots 1 .. key.n
+static int column_pairs(const lf_ks_plan *p, const int64_t *const *c, const int64_t *p_host, const LfKeys &key, int64_t *u, void *stream) {
+    const int ell = p->ell, rows = p->ell + p->K, logN = p->logN, dev = p->device;
+    const int64_t N = (int64_t)1 << logN, half = (int64_t)rows * N;
+    if (int e = p_ntt(p, c, 2, u, half, stream)) return e;
+    if (!key.n) return 0;
+    if (int e = lf_ks_digits_galois(c[1], p->state, p->dig_nparts, p->dig_desc, p->dig_tab, N, 1, p->_2q, p->ql, p->qh, p->kl, p->kh, dev, stream))
+        return e;
+    if (int e = lf_ks_fwd(p->state, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, p->ext, p->psi, p->psi_dp, p->q_host, p->ql, p->qh, p->kl,
+                          p->kh, dev, stream))
+        return e;
+    return lf_ks_baby_sums(p_host, p->nparts, rows, ell, logN, key, u, p->ext, u + 2 * half, plan_mod(p), (hipStream_t)stream);
 }
 
 int lf_lt_matmul(const lf_ks_plan *p, int k_in, int k_out, const int64_t *const *in, const int64_t *ncol, const int64_t *p_host,
@@ -1279,29 +1116,10 @@ int lf_lt_matmul(const lf_ks_plan *p, int k_in, int k_out, const int64_t *const 
     for (int i = 0; i < k_in; ++i) {
         if (!used[i]) continue;
         const int nb = (int)ncol[i];
-        // 1. slot 0 = P NTT(c0), P NTT(c1) on the ordinary rows (canonical copy, enter_ntt, times P R)
-        {
-            const int64_t *srcs[2] = {in[2 * i], in[2 * i + 1]};
-            int64_t *dsts[2] = {u, u + (int64_t)rows * N};
-            if (int e = lf_galois_batch(srcs, dsts, 2, ell, logN, 1, p->_2q, dev, stream)) return e;
-            for (int c = 0; c < 2; ++c) {
-                if (int e = lf_ntt(dsts[c], 1, ell, logN, p->psi, p->psi_dp, p->q_host, p->Rs, 0, p->_2q, p->ql, p->qh, p->kl, p->kh, dev, stream))
-                    return e;
-                if (int e = lf_mont_enter(dsts[c], p->PR, ell, N, p->ql, p->qh, p->kl, p->kh, dev, stream)) return e;
-            }
-        }
-        // 2. the digits of c1 extended and transformed once, per group of the column's keys one launch into the slots 1 .. nb
-        if (nb) {
-            if (int e = lf_ks_digits_galois(in[2 * i + 1], p->state, p->dig_nparts, p->dig_desc, p->dig_tab, N, 1, p->_2q, p->ql, p->qh,
-                                            p->kl, p->kh, dev, stream))
-                return e;
-            if (int e = lf_ks_fwd(p->state, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, p->ext, p->psi, p->psi_dp, p->q_host, p->ql, p->qh,
-                                  p->kl, p->kh, dev, stream))
-                return e;
-            if (int e = lf_ks_baby_sums(nb, p_host + koff[i], p->nparts, rows, ell, logN, ksk + koff[i], part_stride, comp_stride, row_off,
-                                        key_format, u, p->ext, u + pair, p->q_host, p->ql, p->qh, p->kl, p->kh, st))
-                return e;
-        }
+        // 1., 2. slot 0 = P NTT(c0), P NTT(c1) on the ordinary rows; the column's baby sums into the slots 1 .. nb
+        if (int e = column_pairs(p, in + 2 * i, nb ? p_host + koff[i] : nullptr,
+                                 {nb ? ksk + koff[i] : nullptr, nb, part_stride, comp_stride, row_off, key_format}, u, stream))
+            return e;
         // 3. the outputs that have a block in this column, 4, 2 or 1 per launch over the input's pairs
         std::vector<int> os;
         for (int o = 0; o < k_out; ++o)
@@ -1319,33 +1137,12 @@ int lf_lt_matmul(const lf_ks_plan *p, int k_in, int k_out, const int64_t *const 
                 pts[t] = pt[b], strides[t] = pt_stride[b], slots[t] = masks[b], outs[t] = S + o * pair, fresh[t] = !written[o];
                 written[o] = 1;
             }
-            if (int e = lf_lt_block_products(g, u, nb + 1, pts, slots, strides, outs, fresh, rows, logN, p->ql, p->qh, p->kl, p->kh, st))
-                return e;
+            if (int e = lf_lt_block_products(g, u, nb + 1, pts, slots, strides, outs, fresh, rows, logN, plan_mod(p), st)) return e;
             a0 += g;
         }
     }
     // 4. per group of outputs one exact inverse NTT (intt_exit_reduce) of its 2 g polynomials, one mod-down, one rescale
-    for (int o0 = 0; o0 < k_out; o0 += LF_LT_MATMUL_GROUP) {
-        const int g = k_out - o0 < LF_LT_MATMUL_GROUP ? k_out - o0 : LF_LT_MATMUL_GROUP;
-        int64_t *Sg = S + o0 * pair;
-        if (int e = lf_intt(Sg, 2 * g, rows, logN, p->ipsi, p->ipsi_dp, p->q_host, p->Ninv, 2, 0, p->_2q, p->ql, p->qh, p->kl, p->kh, dev, stream))
-            return e;
-        const int64_t *ss[2 * LF_LT_MATMUL_GROUP], *ins[2 * LF_LT_MATMUL_GROUP], *row0[2 * LF_LT_MATMUL_GROUP];
-        int64_t *mds[2 * LF_LT_MATMUL_GROUP], *outs[2 * LF_LT_MATMUL_GROUP];
-        for (int t = 0; t < 2 * g; ++t) {
-            ss[t] = Sg + t * (int64_t)rows * N;
-            mds[t] = md + t * poly;
-            row0[t] = mds[t], ins[t] = mds[t] + N;
-            outs[t] = (t & 1) ? out1[o0 + t / 2] : out0[o0 + t / 2];
-        }
-        if (int e = lf_ks_moddown_ws(ss, mds, nullptr, 2 * g, ell, p->K, N, mdws, mdws_words, p->PiR, p->PiP, p->Rs, 0, nullptr, p->ql, p->qh,
-                                     p->kl, p->kh, dev, stream))
-            return e;
-        if (int e = lf_rescale_batch(ins, row0, outs, 2 * g, ell - 1, N, rescale_scales, round_at, p->ql + 1, p->qh + 1, p->kl + 1, p->kh + 1,
-                                     dev, stream))
-            return e;
-    }
-    return 0;
+    return matmul_tail(p, S, k_out, md, mdws, mdws_words, out0, out1, rescale_scales, round_at, stream);
 }
 
 /* ---- lf_lt_matmul over nt token vectors under one matrix and one key set (include/ckks_hip.h): a group of nt = 2 or 4 tokens
@@ -1402,17 +1199,12 @@ int lf_lt_matmul_batch(const lf_ks_plan *p, int nt, int k_in, int k_out, const i
         //    polynomials in `md` (free until the tail; nt <= gmax), times P R, then into the slots
         {
             const int64_t *srcs[2 * LF_LT_MATMUL_BATCH_MAX_TOKENS];
-            int64_t *dsts[2 * LF_LT_MATMUL_BATCH_MAX_TOKENS];
             for (int t = 0; t < nt; ++t)
-                for (int c = 0; c < 2; ++c) srcs[2 * t + c] = in[2 * ((int64_t)t * k_in + i) + c], dsts[2 * t + c] = md + (2 * t + c) * poly;
-            if (int e = lf_galois_batch(srcs, dsts, 2 * nt, ell, logN, 1, p->_2q, dev, stream)) return e;
-            if (int e = lf_ntt(md, 2 * nt, ell, logN, p->psi, p->psi_dp, p->q_host, p->Rs, 0, p->_2q, p->ql, p->qh, p->kl, p->kh, dev, stream))
-                return e;
-            for (int k = 0; k < 2 * nt; ++k) {
-                if (int e = lf_mont_enter(dsts[k], p->PR, ell, N, p->ql, p->qh, p->kl, p->kh, dev, stream)) return e;
-                if (hipError_t e = hipMemcpyAsync(U(k / 2) + (k & 1) * half, dsts[k], (size_t)poly * 8, hipMemcpyDeviceToDevice, st))
+                for (int c = 0; c < 2; ++c) srcs[2 * t + c] = in[2 * ((int64_t)t * k_in + i) + c];
+            if (int e = p_ntt(p, srcs, 2 * nt, md, poly, stream)) return e;
+            for (int k = 0; k < 2 * nt; ++k)
+                if (hipError_t e = hipMemcpyAsync(U(k / 2) + (k & 1) * half, md + k * poly, (size_t)poly * 8, hipMemcpyDeviceToDevice, st))
                     return (int)e;
-            }
         }
         // 2. the digits of the nt c1 (canonical, no permutation), ONE extension + forward NTT of all of them, per key of the column
         //    ONE launch into slot 1 + j of every member: the key crosses HBM once for the group
@@ -1423,13 +1215,13 @@ int lf_lt_matmul_batch(const lf_ks_plan *p, int nt, int k_in, int k_out, const i
             if (int e = lf_ks_digits_batch(srcs, states, nt, p->dig_nparts, p->dig_desc, p->dig_tab, N, 1, p->_2q, p->ql, p->qh, p->kl, p->kh, dev,
                                            stream))
                 return e;
-            if (int e = lf_ks_fwd_batch(p->state, poly, nt, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, p->ext, p->psi, p->psi_dp, p->q_host,
-                                        p->ql, p->qh, p->kl, p->kh, st))
+            if (int e = lf_ks_fwd_batch(p->state, poly, nt, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, p->ext, plan_fwd(p), plan_mod(p), st))
                 return e;
             for (int j = 0; j < nb; ++j) {
                 for (int t = 0; t < nt; ++t) us[t] = U(t) + (j + 1) * pair;
-                if (int e = lf_ks_baby_sums_batch(nt, p_host[koff[i] + j], p->nparts, rows, ell, logN, ksk[koff[i] + j], part_stride, comp_stride,
-                                                  row_off, key_format, p->ext, chat0, us, p->q_host, p->ql, p->qh, p->kl, p->kh, st))
+                if (int e = lf_ks_baby_sums_batch(nt, p_host[koff[i] + j], p->nparts, rows, ell, logN,
+                                                  {ksk + koff[i] + j, 1, part_stride, comp_stride, row_off, key_format}, p->ext, chat0, us,
+                                                  plan_mod(p), st))
                     return e;
             }
         }
@@ -1450,35 +1242,13 @@ int lf_lt_matmul_batch(const lf_ks_plan *p, int nt, int k_in, int k_out, const i
                 pts[t] = pt[b], strides[t] = pt_stride[b], slots[t] = masks[b], outs[t] = S + o * pair, fresh[t] = !written[o];
                 written[o] = 1;
             }
-            if (int e = lf_lt_block_productsb(nt, g, U(0), member, nb + 1, pts, slots, strides, outs, k_out * pair, fresh, rows, logN, p->ql,
-                                              p->qh, p->kl, p->kh, st))
+            if (int e = lf_lt_block_productsb(nt, g, U(0), member, nb + 1, pts, slots, strides, outs, k_out * pair, fresh, rows, logN, plan_mod(p), st))
                 return e;
             a0 += g;
         }
     }
-    // 4. the nt k_out sums in groups of up to 4: one exact inverse NTT (intt_exit_reduce) of the group's 2 g polynomials, one
-    //    mod-down, one rescale into the callers' [ell - 1][N] pairs
-    for (int s0 = 0; s0 < ns; s0 += LF_LT_MATMUL_GROUP) {
-        const int g = ns - s0 < LF_LT_MATMUL_GROUP ? ns - s0 : LF_LT_MATMUL_GROUP;
-        int64_t *Sg = S + s0 * pair;
-        if (int e = lf_intt(Sg, 2 * g, rows, logN, p->ipsi, p->ipsi_dp, p->q_host, p->Ninv, 2, 0, p->_2q, p->ql, p->qh, p->kl, p->kh, dev, stream))
-            return e;
-        const int64_t *ss[2 * LF_LT_MATMUL_GROUP], *ins[2 * LF_LT_MATMUL_GROUP], *row0[2 * LF_LT_MATMUL_GROUP];
-        int64_t *mds[2 * LF_LT_MATMUL_GROUP], *outs[2 * LF_LT_MATMUL_GROUP];
-        for (int t = 0; t < 2 * g; ++t) {
-            ss[t] = Sg + t * half;
-            mds[t] = md + t * poly;
-            row0[t] = mds[t], ins[t] = mds[t] + N;
-            outs[t] = (t & 1) ? out1[s0 + t / 2] : out0[s0 + t / 2];
-        }
-        if (int e = lf_ks_moddown_ws(ss, mds, nullptr, 2 * g, ell, p->K, N, mdws, mdws_words, p->PiR, p->PiP, p->Rs, 0, nullptr, p->ql, p->qh,
-                                     p->kl, p->kh, dev, stream))
-            return e;
-        if (int e = lf_rescale_batch(ins, row0, outs, 2 * g, ell - 1, N, rescale_scales, round_at, p->ql + 1, p->qh + 1, p->kl + 1, p->kh + 1,
-                                     dev, stream))
-            return e;
-    }
-    return 0;
+    // 4. the nt k_out sums in groups of up to 4 (a group may span two tokens): into the callers' [ell - 1][N] pairs
+    return matmul_tail(p, S, ns, md, mdws, mdws_words, out0, out1, rescale_scales, round_at, stream);
 }
 
 /* ---- a matrix of baby-step / giant-step transforms: y_o = sum_g rot(sum_i sum_b pt_{o,i,g+b} * rot(x_i, b), g)
@@ -1491,9 +1261,8 @@ static int bsgs_giant_group(const lf_ks_plan *p) { return p->max_nct < 4 ? p->ma
 // the giant step of n (4, 2 or 1) pairs S^g under ONE key, added into their accumulators: per pair the inverse NTT of S^g_1 (the pair
 // layout stays), then for the group ONE mod-down into w, ONE digit launch, ONE extension + forward pass and ONE launch of the key
 // switch, with each pair's S^g_0 gathered on all rows.  w: n [ell][N] polynomials; mdws: the workspace of a mod-down of n
-static int bsgs_giant_step(const lf_ks_plan *p, int n, int64_t *const *S, int64_t *const *accs, int64_t gp, const int64_t *gksk,
-                           int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format, int64_t *w, int64_t *mdws,
-                           int64_t mdws_words, void *stream) {
+static int bsgs_giant_step(const lf_ks_plan *p, int n, int64_t *const *S, int64_t *const *accs, int64_t gp, const LfKeys &key, int64_t *w,
+                           int64_t *mdws, int64_t mdws_words, void *stream) {
     const int ell = p->ell, rows = p->ell + p->K, logN = p->logN, dev = p->device;
     const int64_t N = (int64_t)1 << logN, poly = (int64_t)ell * N;
     hipStream_t st = (hipStream_t)stream;
@@ -1515,14 +1284,11 @@ static int bsgs_giant_step(const lf_ks_plan *p, int n, int64_t *const *S, int64_
         if (int e = lf_ks_fwd(p->state, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, p->ext, p->psi, p->psi_dp, p->q_host, p->ql, p->qh,
                               p->kl, p->kh, dev, stream))
             return e;
-        return lf_ks_giant_sums(gp, p->nparts, rows, logN, gksk, part_stride, comp_stride, row_off, key_format, p->ext, s0s[0], accs[0],
-                                p->q_host, p->ql, p->qh, p->kl, p->kh, st);
+        return lf_ks_giant_sums(gp, p->nparts, rows, logN, key, p->ext, s0s[0], accs[0], plan_mod(p), st);
     }
-    if (int e = lf_ks_fwd_batch(p->state, poly, n, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, p->ext, p->psi, p->psi_dp, p->q_host,
-                                p->ql, p->qh, p->kl, p->kh, st))
+    if (int e = lf_ks_fwd_batch(p->state, poly, n, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, p->ext, plan_fwd(p), plan_mod(p), st))
         return e;
-    return lf_ks_giant_sums_batch(n, gp, p->nparts, rows, logN, gksk, part_stride, comp_stride, row_off, key_format, p->ext, s0s, accs,
-                                  p->q_host, p->ql, p->qh, p->kl, p->kh, st);
+    return lf_ks_giant_sums_batch(n, gp, p->nparts, rows, logN, key, p->ext, s0s, accs, plan_mod(p), st);
 }
 
 int64_t lf_lt_matmul_bsgs_ws_words(const lf_ks_plan *p, int nb_max, int k_out, int keyed_sums) {
@@ -1547,14 +1313,10 @@ int lf_lt_matmul_bsgs(const lf_ks_plan *p, int k_in, int k_out, const int64_t *c
         !rescale_scales || !out0 || !out1 || (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES))
         return LF_ERR_ARG;
     const int ell = p->ell, rows = p->ell + p->K, logN = p->logN, dev = p->device;
-    const int64_t N = (int64_t)1 << logN, twoN = 2 * N, poly = (int64_t)ell * N, pair = 2 * (int64_t)rows * N;
-    auto key_ok = [&](const int64_t *k, int64_t e) {
-        if (!k || e <= 0 || e >= twoN || !(e & 1)) return false;
-        return key_format != LF_KEY_PLANES || !((((uintptr_t)k | (uintptr_t)(part_stride * 8) | (uintptr_t)(comp_stride * 8)) & 15));
-    };
+    const int64_t N = (int64_t)1 << logN, poly = (int64_t)ell * N, pair = 2 * (int64_t)rows * N;
     auto block = [&](int o, int i, int j) { return ((int64_t)o * k_in + i) * ng + j; };
-    for (int j = 0; j < ng; ++j)
-        if (gp_host[j] == 0 ? j != 0 : !key_ok(gksk[j], gp_host[j])) return LF_ERR_ARG;   // (giant step 0: first, so at most once)
+    for (int j = 0; j < ng; ++j)   // (giant step 0: first, so at most once)
+        if (gp_host[j] == 0 ? j != 0 : !keyed_steps_ok(gksk + j, gp_host + j, 1, part_stride, comp_stride, key_format, logN)) return LF_ERR_ARG;
     // the columns: keyed baby steps per input, the inputs some output uses, their keys
     std::vector<int64_t> koff(k_in + 1, 0);
     std::vector<char> used(k_in, 0);
@@ -1567,8 +1329,8 @@ int lf_lt_matmul_bsgs(const lf_ks_plan *p, int k_in, int k_out, const int64_t *c
         if (!used[i]) continue;
         if (!in[2 * i] || !in[2 * i + 1]) return LF_ERR_ARG;
         if (ncol[i] && (!bp_host || !bksk)) return LF_ERR_ARG;
-        for (int64_t k = koff[i]; k < koff[i + 1]; ++k)
-            if (!key_ok(bksk[k], bp_host[k])) return LF_ERR_ARG;
+        if (ncol[i] && !keyed_steps_ok(bksk + koff[i], bp_host + koff[i], (int)ncol[i], part_stride, comp_stride, key_format, logN))
+            return LF_ERR_ARG;
         if (ncol[i] > nb_max) nb_max = (int)ncol[i];
     }
     // the diagonals: per (output, input, giant step) its slots inside the column's set, ascending; per (output, giant step) the
@@ -1628,27 +1390,9 @@ int lf_lt_matmul_bsgs(const lf_ks_plan *p, int k_in, int k_out, const int64_t *c
     for (int i = 0; i < k_in; ++i) {
         if (!used[i]) continue;
         const int nb = (int)ncol[i];
-        {
-            const int64_t *srcs[2] = {in[2 * i], in[2 * i + 1]};
-            int64_t *dsts[2] = {u, u + (int64_t)rows * N};
-            if (int e = lf_galois_batch(srcs, dsts, 2, ell, logN, 1, p->_2q, dev, stream)) return e;
-            for (int c = 0; c < 2; ++c) {
-                if (int e = lf_ntt(dsts[c], 1, ell, logN, p->psi, p->psi_dp, p->q_host, p->Rs, 0, p->_2q, p->ql, p->qh, p->kl, p->kh, dev, stream))
-                    return e;
-                if (int e = lf_mont_enter(dsts[c], p->PR, ell, N, p->ql, p->qh, p->kl, p->kh, dev, stream)) return e;
-            }
-        }
-        if (nb) {
-            if (int e = lf_ks_digits_galois(in[2 * i + 1], p->state, p->dig_nparts, p->dig_desc, p->dig_tab, N, 1, p->_2q, p->ql, p->qh,
-                                            p->kl, p->kh, dev, stream))
-                return e;
-            if (int e = lf_ks_fwd(p->state, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, p->ext, p->psi, p->psi_dp, p->q_host, p->ql, p->qh,
-                                  p->kl, p->kh, dev, stream))
-                return e;
-            if (int e = lf_ks_baby_sums(nb, bp_host + koff[i], p->nparts, rows, ell, logN, bksk + koff[i], part_stride, comp_stride, row_off,
-                                        key_format, u, p->ext, u + pair, p->q_host, p->ql, p->qh, p->kl, p->kh, st))
-                return e;
-        }
+        if (int e = column_pairs(p, in + 2 * i, nb ? bp_host + koff[i] : nullptr,
+                                 {nb ? bksk + koff[i] : nullptr, nb, part_stride, comp_stride, row_off, key_format}, u, stream))
+            return e;
         std::vector<int> ts;   // the targets o * ng + j with a diagonal in this column
         for (int o = 0; o < k_out; ++o)
             for (int j = 0; j < ng; ++j)
@@ -1666,8 +1410,7 @@ int lf_lt_matmul_bsgs(const lf_ks_plan *p, int k_in, int k_out, const int64_t *c
                 pts[t] = pt[b], strides[t] = pt_stride[b], slots[t] = masks[b], outs[t] = target(o, j), fresh[t] = !written[ts[a0 + t]];
                 written[ts[a0 + t]] = 1;
             }
-            if (int e = lf_lt_block_products(g, u, nb + 1, pts, slots, strides, outs, fresh, rows, logN, p->ql, p->qh, p->kl, p->kh, st))
-                return e;
+            if (int e = lf_lt_block_products(g, u, nb + 1, pts, slots, strides, outs, fresh, rows, logN, plan_mod(p), st)) return e;
             a0 += g;
         }
     }
@@ -1682,35 +1425,15 @@ int lf_lt_matmul_bsgs(const lf_ks_plan *p, int k_in, int k_out, const int64_t *c
             const int n = (left >= 4 && gw >= 4) ? 4 : (left >= 2 && gw >= 2) ? 2 : 1;
             int64_t *Ss[4], *accs[4];
             for (int t = 0; t < n; ++t) Ss[t] = target(os[a0 + t], j), accs[t] = A + os[a0 + t] * pair;
-            if (int e = bsgs_giant_step(p, n, Ss, accs, gp_host[j], gksk[j], part_stride, comp_stride, row_off, key_format, w, mdws, mdws_words,
-                                        stream))
+            if (int e = bsgs_giant_step(p, n, Ss, accs, gp_host[j], {gksk + j, 1, part_stride, comp_stride, row_off, key_format}, w, mdws,
+                                        mdws_words, stream))
                 return e;
             a0 += n;
         }
     }
     // 3. the tail (step 4 of lf_lt_matmul): per group of outputs one exact inverse NTT of its 2 g accumulator polynomials, one
     // mod-down, one rescale
-    for (int o0 = 0; o0 < k_out; o0 += LF_LT_MATMUL_GROUP) {
-        const int g = k_out - o0 < LF_LT_MATMUL_GROUP ? k_out - o0 : LF_LT_MATMUL_GROUP;
-        int64_t *Ag = A + o0 * pair;
-        if (int e = lf_intt(Ag, 2 * g, rows, logN, p->ipsi, p->ipsi_dp, p->q_host, p->Ninv, 2, 0, p->_2q, p->ql, p->qh, p->kl, p->kh, dev, stream))
-            return e;
-        const int64_t *ss[2 * LF_LT_MATMUL_GROUP], *ins[2 * LF_LT_MATMUL_GROUP], *row0[2 * LF_LT_MATMUL_GROUP];
-        int64_t *mds[2 * LF_LT_MATMUL_GROUP], *outs[2 * LF_LT_MATMUL_GROUP];
-        for (int t = 0; t < 2 * g; ++t) {
-            ss[t] = Ag + t * (int64_t)rows * N;
-            mds[t] = md + t * poly;
-            row0[t] = mds[t], ins[t] = mds[t] + N;
-            outs[t] = (t & 1) ? out1[o0 + t / 2] : out0[o0 + t / 2];
-        }
-        if (int e = lf_ks_moddown_ws(ss, mds, nullptr, 2 * g, ell, p->K, N, mdws, mdws_words, p->PiR, p->PiP, p->Rs, 0, nullptr, p->ql, p->qh,
-                                     p->kl, p->kh, dev, stream))
-            return e;
-        if (int e = lf_rescale_batch(ins, row0, outs, 2 * g, ell - 1, N, rescale_scales, round_at, p->ql + 1, p->qh + 1, p->kl + 1, p->kh + 1,
-                                     dev, stream))
-            return e;
-    }
-    return 0;
+    return matmul_tail(p, A, k_out, md, mdws, mdws_words, out0, out1, rescale_scales, round_at, stream);
 }
 
 /* ---- baby-step / giant-step linear transform of many ciphertexts under the same diagonals and keys (include/ckks_hip.h): groups
@@ -1766,16 +1489,11 @@ int lf_linear_transform_bsgs_batch(const lf_ks_plan *p, int nct, const int64_t *
         //    forward NTT of the 2 g polynomials in `md` (free until the tail), times P R, then into the slots
         {
             const int64_t *srcs[8];
-            int64_t *dsts[8];
             for (int t = 0; t < g; ++t) srcs[2 * t] = c0[t0 + t], srcs[2 * t + 1] = c1[t0 + t];
-            for (int i = 0; i < 2 * g; ++i) dsts[i] = md + i * poly;
-            if (int e = lf_galois_batch(srcs, dsts, 2 * g, ell, logN, 1, p->_2q, dev, stream)) return e;
-            if (int e = lf_ntt(md, 2 * g, ell, logN, p->psi, p->psi_dp, p->q_host, p->Rs, 0, p->_2q, p->ql, p->qh, p->kl, p->kh, dev, stream))
-                return e;
+            if (int e = p_ntt(p, srcs, 2 * g, md, poly, stream)) return e;
             for (int i = 0; i < 2 * g; ++i) {
                 int64_t *slot = U(i / 2) + (i & 1) * half;
-                if (int e = lf_mont_enter(dsts[i], p->PR, ell, N, p->ql, p->qh, p->kl, p->kh, dev, stream)) return e;
-                if (hipError_t e = hipMemcpyAsync(slot, dsts[i], (size_t)poly * 8, hipMemcpyDeviceToDevice, st)) return (int)e;
+                if (hipError_t e = hipMemcpyAsync(slot, md + i * poly, (size_t)poly * 8, hipMemcpyDeviceToDevice, st)) return (int)e;
                 if (hipError_t e = hipMemsetAsync(slot + poly, 0, (size_t)p->K * N * 8, st)) return (int)e;
             }
         }
@@ -1788,13 +1506,12 @@ int lf_linear_transform_bsgs_batch(const lf_ks_plan *p, int nct, const int64_t *
             if (int e = lf_ks_digits_batch(srcs, states, g, p->dig_nparts, p->dig_desc, p->dig_tab, N, 1, p->_2q, p->ql, p->qh, p->kl, p->kh, dev,
                                            stream))
                 return e;
-            if (int e = lf_ks_fwd_batch(p->state, poly, g, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, p->ext, p->psi, p->psi_dp, p->q_host,
-                                        p->ql, p->qh, p->kl, p->kh, st))
+            if (int e = lf_ks_fwd_batch(p->state, poly, g, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, p->ext, plan_fwd(p), plan_mod(p), st))
                 return e;
             for (int b = 0; b < nb; ++b) {
                 for (int t = 0; t < g; ++t) us[t] = U(t) + (b + 1) * pair;
-                if (int e = lf_ks_baby_sums_batch(g, bp_host[b], p->nparts, rows, ell, logN, bksk[b], part_stride, comp_stride, row_off, key_format,
-                                                  p->ext, chat0, us, p->q_host, p->ql, p->qh, p->kl, p->kh, st))
+                if (int e = lf_ks_baby_sums_batch(g, bp_host[b], p->nparts, rows, ell, logN, {bksk + b, 1, part_stride, comp_stride, row_off, key_format},
+                                                  p->ext, chat0, us, plan_mod(p), st))
                     return e;
             }
         }
@@ -1815,15 +1532,14 @@ int lf_linear_transform_bsgs_batch(const lf_ks_plan *p, int nct, const int64_t *
             for (int t = 0; t < g; ++t) {
                 int64_t *outs[4];
                 for (int i = 0; i < gc; ++i) outs[i] = gp_host[i0 + i] == 0 ? A + t * pair : S(t) + i * pair;
-                if (int e = lf_lt_diag_products(gc, U(t), nb + 1, pts, slots, pt_stride, outs, rows, logN, p->ql, p->qh, p->kl, p->kh, st))
-                    return e;
+                if (int e = lf_lt_diag_products(gc, U(t), nb + 1, pts, slots, pt_stride, outs, rows, logN, plan_mod(p), st)) return e;
             }
             for (int i = 0; i < gc; ++i) {
                 if (gp_host[i0 + i] == 0) continue;
                 int64_t *Ss[4], *accs[4];
                 for (int t = 0; t < g; ++t) Ss[t] = S(t) + i * pair, accs[t] = A + t * pair;
-                if (int e = bsgs_giant_step(p, g, Ss, accs, gp_host[i0 + i], gksk[i0 + i], part_stride, comp_stride, row_off, key_format, w, mdws,
-                                            mdws_words, stream))
+                if (int e = bsgs_giant_step(p, g, Ss, accs, gp_host[i0 + i], {gksk + i0 + i, 1, part_stride, comp_stride, row_off, key_format}, w,
+                                            mdws, mdws_words, stream))
                     return e;
             }
             i0 += gc;
@@ -1832,19 +1548,7 @@ int lf_linear_transform_bsgs_batch(const lf_ks_plan *p, int nct, const int64_t *
         //    callers' [ell - 1][N] pairs
         if (int e = lf_intt(A, 2 * g, rows, logN, p->ipsi, p->ipsi_dp, p->q_host, p->Ninv, 2, 0, p->_2q, p->ql, p->qh, p->kl, p->kh, dev, stream))
             return e;
-        const int64_t *ss[8], *ins[8], *row0[8];
-        int64_t *mds[8], *outs[8];
-        for (int t = 0; t < 2 * g; ++t) {
-            ss[t] = A + t * half;
-            mds[t] = md + t * poly, row0[t] = mds[t], ins[t] = mds[t] + N;
-            outs[t] = (t & 1) ? out1[t0 + t / 2] : out0[t0 + t / 2];
-        }
-        if (int e = lf_ks_moddown_ws(ss, mds, nullptr, 2 * g, ell, p->K, N, mdws, mdws_words, p->PiR, p->PiP, p->Rs, 0, nullptr, p->ql, p->qh,
-                                     p->kl, p->kh, dev, stream))
-            return e;
-        if (int e = lf_rescale_batch(ins, row0, outs, 2 * g, ell - 1, N, rescale_scales, round_at, p->ql + 1, p->qh + 1, p->kl + 1, p->kh + 1,
-                                     dev, stream))
-            return e;
+        if (int e = moddown_rescale_pairs(p, A, g, md, mdws, mdws_words, out0 + t0, out1 + t0, rescale_scales, round_at, stream)) return e;
         t0 += g;
     }
     return 0;
@@ -1869,14 +1573,8 @@ int lf_switch_key_batch(const lf_ks_plan *p, int nct, const int64_t *const *c0, 
                                  row_off, key_format, p->ext, p->sum, p->psi, p->psi_dp, p->ipsi, p->ipsi_dp, p->Ninv, p->q_host, p->ql,
                                  p->qh, p->kl, p->kh, dev, stream))
         return e;
-    const int64_t *ss[8], *adds[8];
-    int64_t *outs[8];
-    for (int t = 0; t < nct; ++t) {
-        ss[2 * t] = p->sum + (int64_t)(2 * t) * rows * N, ss[2 * t + 1] = p->sum + (int64_t)(2 * t + 1) * rows * N;
-        outs[2 * t] = out0[t], outs[2 * t + 1] = out1[t];
-        adds[2 * t] = c0 ? c0[t] : nullptr, adds[2 * t + 1] = nullptr;
-    }
-    return moddown_any(p, ss, outs, adds, 2 * nct, gal_pinv, g2q, stream);
+    const int64_t *const none[4] = {};   // (without c0 the mod-down still takes a list of addends, all NULL)
+    return moddown_pairs(p, p->sum, nct, out0, out1, c0 ? c0 : none, gal_pinv, g2q, stream);
 }
 
 int lf_cc_mult_evk_batch(const lf_ks_plan *p, int nct, const int64_t *const *in, const int64_t *const *row0, const int64_t *ksk,
@@ -1900,13 +1598,7 @@ int lf_cc_mult_evk_batch(const lf_ks_plan *p, int nct, const int64_t *const *in,
                                     row_off, key_format | (xpl ? LF_STACK_PLANES : 0), p->ext, p->sum, p->psi, p->psi_dp, p->ipsi, p->ipsi_dp, p->Ninv, p->x4, 4 * poly,
                                     p->PR, ell, p->own, p->q_host, p->ql, p->qh, p->kl, p->kh, dev, stream))
         return e;
-    const int64_t *ss[8];
-    int64_t *outs[8];
-    for (int t = 0; t < nct; ++t) {
-        ss[2 * t] = p->sum + (int64_t)(2 * t) * rows * N, ss[2 * t + 1] = p->sum + (int64_t)(2 * t + 1) * rows * N;
-        outs[2 * t] = out0[t], outs[2 * t + 1] = out1[t];
-    }
-    return moddown_any(p, ss, outs, nullptr, 2 * nct, 0, nullptr, stream);
+    return moddown_pairs(p, p->sum, nct, out0, out1, nullptr, 0, nullptr, stream);
 }
 
 /* ---- the halves of an op around the digit exchange of a limb-sharded engine (one process per GPU; ckks_engine.py:746-904:
@@ -1959,7 +1651,6 @@ int lf_cc_mult_evk_post(const lf_ks_plan *p, const int64_t *ksk, int64_t part_st
     if (!plan_ok(p) || !p->PR || !p->x4 || !(which & 3) || (which & ~3) || ((which & 1) && !ksk) || ((which & 2) && (!out0 || !out1)))
         return LF_ERR_ARG;
     const int rows = p->ell + p->K;
-    const int64_t N = (int64_t)1 << p->logN;
     // which: 1 = inner product + inverse NTT (fixed addresses: plan scratch and the key), 2 = the mod-down that writes out0 / out1
     if (which & 1)
         if (int e = lf_relin_tail(p->nparts, rows, p->logN, ksk, part_stride, comp_stride, row_off,
@@ -1967,9 +1658,7 @@ int lf_cc_mult_evk_post(const lf_ks_plan *p, const int64_t *ksk, int64_t part_st
                                   p->ipsi_dp, p->Ninv, p->x4, p->PR, p->ell, p->own, p->q_host, p->ql, p->qh, p->kl, p->kh, p->device, stream))
             return e;
     if (!(which & 2)) return 0;
-    const int64_t *ss[2] = {p->sum, p->sum + (int64_t)rows * N};
-    int64_t *outs[2] = {out0, out1};
-    return moddown_any(p, ss, outs, nullptr, 2, 0, nullptr, stream);
+    return moddown_pairs(p, p->sum, 1, &out0, &out1, nullptr, 0, nullptr, stream);
 }
 
 int lf_switch_key_post(const lf_ks_plan *p, const int64_t *c0, int64_t gal_pinv, int gal_canonical, const int64_t *ksk,
@@ -1977,17 +1666,13 @@ int lf_switch_key_post(const lf_ks_plan *p, const int64_t *c0, int64_t gal_pinv,
                        int which, void *stream) {
     if (!plan_ok(p) || !(which & 3) || (which & ~3) || ((which & 1) && !ksk) || ((which & 2) && (!out0 || !out1))) return LF_ERR_ARG;
     const int rows = p->ell + p->K;
-    const int64_t N = (int64_t)1 << p->logN;
     const int64_t *g2q = (gal_pinv && gal_canonical) ? p->_2q : nullptr;
     if (which & 1)   // see lf_cc_mult_evk_post
         if (int e = lf_ks_tail(p->nparts, rows, p->logN, ksk, part_stride, comp_stride, row_off, key_format, p->ext, p->sum, p->ipsi, p->ipsi_dp,
                                p->Ninv, p->q_host, p->ql, p->qh, p->kl, p->kh, p->device, stream))
             return e;
     if (!(which & 2)) return 0;
-    const int64_t *ss[2] = {p->sum, p->sum + (int64_t)rows * N};
-    int64_t *outs[2] = {out0, out1};
-    const int64_t *adds[2] = {c0, nullptr};
-    return moddown_any(p, ss, outs, adds, 2, gal_pinv, g2q, stream);
+    return moddown_pairs(p, p->sum, 1, &out0, &out1, &c0, gal_pinv, g2q, stream);
 }
 
 }  // extern "C"

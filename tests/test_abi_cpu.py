@@ -85,6 +85,42 @@ def test_every_include_and_every_source_file_is_part_of_the_library_digest():
             assert target in known, f"{f} includes {inc}, which library_sources() does not list"
 
 
+def test_no_hip_file_declares_what_another_hip_file_defines():
+    """What one .hip file of csrc/ defines and another uses is declared ONCE, in a header both include (csrc/ckks_launch.h, or
+    include/ckks_hip.h for the exported entries): no .hip file carries a file-scope prototype or an `extern` declaration of a
+    function or variable that another .hip file defines, so a signature cannot drift between a hand-copied prototype and the
+    definition it links against."""
+    csrc = os.path.join(ROOT, "liberate_fhe_amd", "csrc")
+    text = {}
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith(".hip"):
+            src = open(os.path.join(csrc, f)).read()
+            src = re.sub(r"/\*.*?\*/", lambda m: "\n" * m.group(0).count("\n"), src, flags=re.S)
+            text[f] = re.sub(r"//[^\n]*", "", src)
+    assert len(text) >= 7
+    proto = re.compile(r"^(?!static\b|typedef\b|using\b|template\b)[A-Za-z_][\w \t]*[\s\*&]+(\w+)\s*\(([^;{}]*)\)\s*;", re.M)
+    ext = re.compile(r"^extern\s+(?!\"C\")[^;=(]*?(\w+)\s*(?:\[[^\]]*\])?\s*;", re.M)
+    seen = 0
+    for f, src in text.items():
+        for kind, names in (("prototype", [m.group(1) for m in proto.finditer(src)]), ("extern", ext.findall(src))):
+            for name in names:
+                seen += 1
+                for g, other in text.items():
+                    if g == f:
+                        continue
+                    body = re.search(rf"^[A-Za-z_][\w \t]*[\s\*&]+{name}\s*\([^;{{}}]*\)\s*{{", other, re.M)
+                    var = re.search(rf"^(?!extern\b)[A-Za-z_][\w \t]*[\s\*&]+{name}\s*(?:\[[^\]]*\])?\s*(?:=[^;]*)?;", other, re.M)
+                    assert not (body if kind == "prototype" else var), f"{f} declares {name} ({kind}), which {g} defines: declare it in a header"
+    # the shared declarations exist, in the header both sides include
+    header = open(os.path.join(csrc, "ckks_launch.h")).read()
+    for name in ("lf_ks_tail_lt", "lf_fp64_digits_ok", "lf_g_intt_digits", "lf_g_ws_extra_stage"):
+        assert re.search(rf"\b{name}\b", header), name
+        users = [f for f, src in text.items() if re.search(rf"\b{name}\b", src)]
+        assert len(users) >= 2, name
+        for f in users:
+            assert '#include "ckks_launch.h"' in text[f], (f, name)
+
+
 def test_library_reads_no_environment_variables():
     """A drop-in library's results must not depend on ambient env vars: no getenv anywhere in the C sources."""
     csrc = os.path.join(ROOT, "liberate_fhe_amd", "csrc")

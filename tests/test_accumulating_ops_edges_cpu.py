@@ -133,7 +133,8 @@ def test_checker_cc_dot_equals_its_composition_on_the_edge_operands(name, last):
 
 
 def launch_groups(n):
-    """the keys per launch of lf_ks_tail_lt / lf_ks_baby_sums (csrc/ckks_ks.hip): 4 while 4 are left, then 2, then 1"""
+    """the keys per launch of lf_ks_tail_lt / lf_ks_tail_rsum / lf_ks_baby_sums (key_group, csrc/ckks_ks.hip): 4 while 4 are left, then
+    2, then 1"""
     out = []
     while n:
         g = 4 if n >= 4 else 2 if n >= 2 else 1

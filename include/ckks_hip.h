@@ -566,7 +566,8 @@ int lf_rotate_hoisted(const lf_ks_plan *plan, const int64_t *c0, const int64_t *
  * out0 / out1 [ell - 1][N].  P c^ and the mod-down's [2][ell][N] result live in plan->x4 (free during this op) or, with
  * plan->x4 = NULL, in `ws` of at least lf_linear_transform_ws_words(plan) words (0: ws may be NULL).
  * LF_ERR_ARG before any launch for everything lf_rotate_hoisted refuses (nr < 0 instead of nr < 1), a NULL pt with nr > 0,
- * nr = 0 without pt0, a NULL rescale_scales, plan->PR = NULL and ell < 2 (no level left to rescale into). */
+ * nr = 0 without pt0, a NULL rescale_scales, plan->PR = NULL, ell < 2 (no level left to rescale into) and, where words are needed,
+ * a workspace not 16-byte aligned (ks_inner_lt_kernel reads P c^ in 16-byte column pairs). */
 int64_t lf_linear_transform_ws_words(const lf_ks_plan *plan);
 int lf_linear_transform(const lf_ks_plan *plan, const int64_t *c0, const int64_t *c1, int nr, const int64_t *p_host,
                         const int64_t *const *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format,
@@ -613,7 +614,8 @@ int lf_linear_transform_batch(const lf_ks_plan *plan, int nct, const int64_t *co
  * [ell][N], canonical.  No rescale.  P c^ lives in plan->x4 (free during this op) or, with plan->x4 = NULL, in `ws` of at least
  * lf_rotate_sum_ws_words(plan) words (0: ws may be NULL).
  * LF_ERR_ARG before any launch for everything lf_rotate_hoisted refuses (nr < 0 instead of nr < 1), nr = 0 without with_self,
- * plan->PR = NULL and a workspace too small. */
+ * plan->PR = NULL and a workspace too small or, where words are needed, not 16-byte aligned (ks_inner_rsum_kernel reads P c^ in
+ * 16-byte column pairs). */
 int64_t lf_rotate_sum_ws_words(const lf_ks_plan *plan);
 int lf_rotate_sum(const lf_ks_plan *plan, const int64_t *c0, const int64_t *c1, int nr, const int64_t *p_host,
                   const int64_t *const *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format,
@@ -665,7 +667,8 @@ int lf_rotate_sum_batch(const lf_ks_plan *plan, int nct, const int64_t *const *c
  * The baby pairs, four S pairs, A, w and the mod-down's buffers do not fit the plan's scratch: `ws` of at least
  * lf_linear_transform_bsgs_ws_words(plan, nb) words is lent by the caller (0 for a plan or an nb the entry refuses).
  * LF_ERR_ARG before any launch for everything lf_linear_transform refuses, nb < 0 or > 63, ng < 1, a baby slot out of range or
- * not ascending inside its giant step, a giant step without diagonals, a second or a late giant step 0, a workspace too small. */
+ * not ascending inside its giant step, a giant step without diagonals, a second or a late giant step 0, a workspace too small
+ * or not 16-byte aligned (lt_diag_products_kernel reads the baby pairs and writes S and A in 16-byte column pairs). */
 int64_t lf_linear_transform_bsgs_ws_words(const lf_ks_plan *plan, int nb);
 int lf_linear_transform_bsgs(const lf_ks_plan *plan, const int64_t *c0, const int64_t *c1, int nb, const int64_t *bp_host,
                              const int64_t *const *bksk, int ng, const int64_t *gp_host, const int64_t *const *gksk,
@@ -845,7 +848,8 @@ int lf_lt_matmul_bsgs(const lf_ks_plan *plan, int k_in, int k_out, const int64_t
  * the ordinary rows and whose own-limb digit words are T2's — with the inverse NTT of plan->sum; one mod-down, no addend.
  * T lives in `ws` of at least lf_cc_dot_ws_words(plan) = 3 ell N words, lent by the caller (0 for a plan the entry refuses).
  * LF_ERR_ARG before any launch for everything lf_cc_mult_evk refuses, np < 1, a NULL among the 4 np pointers of in or row0, a
- * key_format that is neither LF_KEY_RAW nor LF_KEY_PLANES (or a planes key not 16-byte aligned), ws NULL or too small. */
+ * key_format that is neither LF_KEY_RAW nor LF_KEY_PLANES (or a planes key not 16-byte aligned), ws NULL, not 16-byte aligned (dot_tensor_kernel reads and writes T in
+ * 16-byte column pairs) or too small. */
 int64_t lf_cc_dot_ws_words(const lf_ks_plan *plan);
 int lf_cc_dot(const lf_ks_plan *plan, int np, const int64_t *const *in, const int64_t *const *row0, const int64_t *ksk,
               int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format, int64_t *ws, int64_t ws_words, int64_t *out0,
@@ -864,7 +868,7 @@ int lf_cc_dot(const lf_ks_plan *plan, int np, const int64_t *const *in, const in
  * The triplets live in `ws` of at least lf_cc_dot_batch_ws_words(plan, nd) = 3 nd ell N words, lent by the caller (0 for a plan
  * or an nd the entry refuses).
  * LF_ERR_ARG before any launch for everything lf_cc_dot refuses, nd not 1, 2 or 4 or above plan->max_nct, np_host NULL or an entry
- * below 1, a NULL among the 4 sum np pointers of in or row0 or among the nd of out0 or out1, ws NULL or too small. */
+ * below 1, a NULL among the 4 sum np pointers of in or row0 or among the nd of out0 or out1, ws NULL, not 16-byte aligned or too small. */
 int64_t lf_cc_dot_batch_ws_words(const lf_ks_plan *plan, int nd);
 int lf_cc_dot_batch(const lf_ks_plan *plan, int nd, const int64_t *np_host, const int64_t *const *in, const int64_t *const *row0,
                     const int64_t *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format, int64_t *ws,

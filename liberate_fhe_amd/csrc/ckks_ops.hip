@@ -226,7 +226,7 @@ int lf_cc_dot(const lf_ks_plan *p, int np, const int64_t *const *in, const int64
     for (int64_t i = 0; i < (int64_t)4 * np; ++i)
         if (!in[i] || !row0[i]) return LF_ERR_ARG;
     const int64_t need = lf_cc_dot_ws_words(p);
-    if (need && (!ws || ws_words < need)) return LF_ERR_ARG;
+    if (need && (!ws || ws_words < need || ((uintptr_t)ws & 15))) return LF_ERR_ARG;   // (dot_tensor_kernel: 16-byte column pairs of T)
     if (int e = lf_set_device(p->device)) return e;
     // 1., 2. the pairs' tensor products into the one triplet
     if (int e = dot_triplet(p, np, in, row0, ws, p->d2, stream)) return e;
@@ -253,7 +253,7 @@ int lf_cc_dot_batch(const lf_ks_plan *p, int nd, const int64_t *np_host, const i
     for (int64_t i = 0; i < 4 * pairs; ++i)
         if (!in[i] || !row0[i]) return LF_ERR_ARG;
     const int64_t need = lf_cc_dot_batch_ws_words(p, nd);
-    if (!ws || ws_words < need) return LF_ERR_ARG;
+    if (!ws || ws_words < need || ((uintptr_t)ws & 15)) return LF_ERR_ARG;
     if (nd == 1)
         return lf_cc_dot(p, (int)np_host[0], in, row0, ksk, part_stride, comp_stride, row_off, key_format, ws, ws_words, out0[0], out1[0],
                          stream);
@@ -658,7 +658,7 @@ int lf_linear_transform(const lf_ks_plan *p, const int64_t *c0, const int64_t *c
     const int64_t N = (int64_t)1 << logN, poly = (int64_t)ell * N;
     if (nr && (!pt || pt_stride < (int64_t)rows * N)) return LF_ERR_ARG;
     const int64_t need = lf_linear_transform_ws_words(p);
-    if (need && (!ws || ws_words < need)) return LF_ERR_ARG;
+    if (need && (!ws || ws_words < need || ((uintptr_t)ws & 15))) return LF_ERR_ARG;   // (ks_inner_lt_kernel: 16-byte column pairs of c^)
     int64_t *chat = need ? ws : p->x4, *md = chat + 2 * poly;
     // 1. P NTT(c0) (and P NTT(c1) for the step-0 term) on the ordinary rows
     const int64_t *srcs[2] = {c0, c1};
@@ -772,7 +772,7 @@ int lf_rotate_sum(const lf_ks_plan *p, const int64_t *c0, const int64_t *c1, int
     const int ell = p->ell, rows = p->ell + p->K, logN = p->logN, dev = p->device;
     const int64_t N = (int64_t)1 << logN, poly = (int64_t)ell * N;
     const int64_t need = lf_rotate_sum_ws_words(p);
-    if (need && (!ws || ws_words < need)) return LF_ERR_ARG;
+    if (need && (!ws || ws_words < need || ((uintptr_t)ws & 15))) return LF_ERR_ARG;   // (ks_inner_rsum_kernel: 16-byte column pairs of c^)
     int64_t *chat = need ? ws : p->x4;
     // 1. P NTT(c0) (and P NTT(c1) for the self term) on the ordinary rows, as lf_linear_transform forms them
     const int64_t *srcs[2] = {c0, c1};
@@ -915,7 +915,7 @@ int lf_linear_transform_bsgs(const lf_ks_plan *p, const int64_t *c0, const int64
     const int ell = p->ell, rows = p->ell + p->K, logN = p->logN, dev = p->device;
     const int64_t N = (int64_t)1 << logN, poly = (int64_t)ell * N, pair = 2 * (int64_t)rows * N;
     const int64_t need = lf_linear_transform_bsgs_ws_words(p, nb);
-    if (!ws || ws_words < need) return LF_ERR_ARG;
+    if (!ws || ws_words < need || ((uintptr_t)ws & 15)) return LF_ERR_ARG;   // (lt_diag_products_kernel: 16-byte column pairs of u, S, A)
     hipStream_t st = (hipStream_t)stream;
     int64_t *u = ws, *S = u + (nb + 1) * pair, *A = S + LF_BSGS_S_PAIRS * pair, *w = A + pair, *md = w + poly, *md1 = md + 2 * poly;
     const int64_t md1_words = lf_ks_moddown_ws_words(1, ell, p->K, N);

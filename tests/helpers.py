@@ -742,3 +742,248 @@ def step_operands(T, pattern, key_pattern, seed, N=None):
             hi[r] = sign * (DIGIT_WORD_BOUND if small else 2 * m - 1)
     op["state_hi"] = hi
     return op
+
+
+# ---- fenced scratch and outputs of the native op entries (tests/test_fenced_ops_*.py) ------------------------------------
+# every HipBackend method that takes `out` or `outs`: the whole ops behind one native call
+NATIVE_ENTRIES = ("switch_key_native", "cc_mult_evk", "switch_key_batch_native", "cc_mult_evk_batch_native", "cc_dot_native",
+                  "cc_dot_batch_native", "cc_matmul_native", "weighted_sums_native", "pc_dot_native", "pc_matmul_native",
+                  "pc_matmul_batch_native", "rotate_hoisted_native", "linear_transform_native", "linear_transform_batch_native",
+                  "rotate_sum_native", "rotate_sum_batch_native", "linear_transform_bsgs_native",
+                  "linear_transform_bsgs_batch_native", "lt_matmul_native", "lt_matmul_batch_native", "lt_matmul_bsgs_native")
+# the hostile fills of scratch bodies and outputs: every bit set (-1 as a word, a NaN as fp64, 0xFF in every plane byte), the
+# largest word, seeded uniform 64-bit words.  Zero — what a fresh process often finds in new pages — is the friendly case.
+FENCE_FILLS = {"ones": -1, "max": (1 << 63) - 1, "random": "random"}
+
+
+class FenceError(AssertionError):
+    pass
+
+
+class _Fenced:
+    """guard | body | guard inside one allocation; `flat` is the body's span of words, `body` the view the code under test gets"""
+    __slots__ = ("key", "buf", "flat", "body", "salts", "target")
+
+    def __init__(self, key, buf, flat, body, salts, target=None):
+        self.key, self.buf, self.flat, self.body, self.salts, self.target = key, buf, flat, body, salts, target
+
+
+class Fence:
+    """Guards around every scratch tensor and every output of an engine's native op entries, and a hostile fill inside them.
+    Installed on a FRESH engine (before its first op; the engine and its backend keep the wrappers for good):
+
+      scratch   engine._ws is wrapped: every scratch tensor the engine ever asks for — the plan's state / ext / sum / md_ws / x4 /
+                d2 and every op workspace, of every lane — is the middle view(shape) of a larger allocation.  cc_matmul keeps its
+                growing workspace outside _ws: backend.cc_matmul_native is handed a fenced one of exactly
+                cc_matmul_ws_words(plan, nu) words instead.
+      outputs   every method of NATIVE_ENTRIES the backend has is wrapped: the tensors of its `out` / `outs` argument (found by
+                name in the signature, nested lists walked) are replaced by fenced views of the same shape and strides; after the
+                call the guards of the outputs AND of all scratch are checked and the bodies copied into the engine's own tensors.
+                `calls` lists the entries that ran, in order.
+      guards    `guard` words before and behind each body: one polynomial of level 0's full row count, (ell + K) N words, an even
+                count (the body stays 16-byte aligned).  They hold a seeded, position-dependent 64-bit pattern XORed with a salt of
+                their own; check() compares them with the kept pattern and raises FenceError naming the buffer's key, the side
+                ("before": offset 1 is the word next to the body; "behind": offset 0 is) and the first changed word.
+      fill      bodies are pre-filled with `fill` (an int, or "random": seeded uniform 64-bit words); refill() puts it back into
+                every scratch body before a case — except the buffers that hold constants across calls: whatever is handed to
+                backend.moddown_consts and the md_ws of backend.make_plan (both wrapped to learn them).  The scratch part of those
+                keeps what the previous call left.
+      ws_hook   None, or f(name, arguments: dict) called after the outputs are fenced and before the entry runs: it may replace
+                arguments (tests/test_fenced_ops_gpu.py: a workspace one word short, a misaligned one)."""
+
+    def __init__(self, engine, fill, seed=20240229):
+        import inspect
+
+        import torch
+        self.torch, self.eng, self.be, self.fill = torch, engine, engine.backend, fill
+        assert not engine._workspace and not any(k[0] == "plan" for k in engine._tables if isinstance(k, tuple)), \
+            "Fence: the engine has run an op already"
+        N = engine.ctx.N
+        self.guard = max(engine._rows(d, 0, True) for d in range(engine.ntt.num_devices)) * N
+        assert self.guard >= 2 and self.guard % 2 == 0
+        self._rng, self._seed = {}, seed     # device -> its generator
+        self._pattern = {}            # device -> the [guard] words every guard is a salted copy of
+        self._salt = 0
+        self.scratch, self.calls, self.const_ptrs, self.ws_hook = {}, [], set(), None
+        self.last_outputs, self.never_written = [], []     # of the last call / of every call since the list was emptied
+        self._matmul_ws = {}
+        real_ws = engine._ws
+
+        def fenced_ws(key, shape, dev_id):
+            k = (key, tuple(shape), dev_id, engine._lane)
+            if k not in engine._workspace:
+                f = self.alloc(k, tuple(shape), None, engine.ntt.devices[dev_id])
+                self.scratch[k] = f
+                engine._workspace[k] = f.body
+            return real_ws(key, shape, dev_id)
+
+        engine._ws = fenced_ws
+        for name in ("moddown_consts", "make_plan"):
+            if hasattr(self.be, name):
+                setattr(self.be, name, self._learn_consts(name, getattr(self.be, name)))
+        for name in NATIVE_ENTRIES:
+            if hasattr(self.be, name):
+                real = getattr(self.be, name)
+                setattr(self.be, name, self._fenced_entry(name, real, inspect.signature(real)))
+
+    # -- allocation, fill, check ------------------------------------------------------------------------------------------
+    def _words(self, n, device):
+        """n seeded uniform 64-bit words, drawn on `device`"""
+        rng = self._rng.get(str(device))
+        if rng is None:
+            rng = self._rng[str(device)] = self.torch.Generator(device=device).manual_seed(self._seed)
+        return self.torch.randint(-(1 << 63), (1 << 63) - 1, (n,), dtype=self.torch.int64, device=device, generator=rng)
+
+    def pattern(self, device):
+        p = self._pattern.get(str(device))
+        if p is None:
+            p = self._pattern[str(device)] = self._words(self.guard, device)
+        return p
+
+    def _put_fill(self, flat):
+        if self.fill == "random":
+            flat.copy_(self._words(flat.numel(), flat.device))
+        else:
+            flat.fill_(self.fill)
+
+    def alloc(self, key, shape, strides, device, target=None):
+        """a fenced tensor of `shape` (strides None: contiguous), the body pre-filled with the fill"""
+        torch, G = self.torch, self.guard
+        if strides is None:
+            strides, n = [], 1
+            for s in reversed(shape):
+                strides.insert(0, n)
+                n *= s
+        span = 0 if any(s == 0 for s in shape) else 1 + sum((s - 1) * st for s, st in zip(shape, strides))
+        buf = torch.empty(2 * G + span, dtype=torch.int64, device=device)
+        salts = []
+        for lo in (0, G + span):
+            self._salt += 1
+            salt = (self._salt * 0x9E3779B97F4A7C15) & ((1 << 64) - 1)
+            salts.append(salt - (1 << 64) if salt >> 63 else salt)
+            buf[lo:lo + G] = self.pattern(device) ^ salts[-1]
+        flat = buf[G:G + span]
+        self._put_fill(flat)
+        return _Fenced(key, buf, flat, buf.as_strided(tuple(shape), tuple(strides), G), salts, target)
+
+    def check_one(self, f):
+        G, pat = self.guard, self.pattern(f.buf.device)
+        for side, lo, salt in (("before", 0, f.salts[0]), ("behind", f.buf.numel() - G, f.salts[1])):
+            got = f.buf[lo:lo + G] ^ salt
+            if not self.torch.equal(got, pat):
+                at = int((got != pat).nonzero()[0])
+                off = G - at if side == "before" else at
+                raise FenceError(f"{f.key}: the guard {side} the buffer was written, first changed word at offset {off} "
+                                 f"({int((got != pat).sum())} of {G} words changed)")
+
+    def check(self, outputs=()):
+        """the guards of `outputs` and of every scratch buffer"""
+        for f in list(outputs) + list(self.scratch.values()):
+            self.check_one(f)
+
+    def refill(self):
+        for f in self.scratch.values():
+            if f.body.data_ptr() not in self.const_ptrs:
+                self._put_fill(f.flat)
+
+    def holds_fill(self, f):
+        """whether a body still holds an int fill everywhere (nothing was written: the refusal tests)"""
+        assert self.fill != "random"
+        return bool((f.flat == self.fill).all())
+
+    def unwritten(self):
+        """the keys of the last call's outputs that still hold an int fill in EVERY word: the entry never wrote them (no result
+        is -1 or 2^63 - 1 everywhere); [] under the random fill, where the comparison across fills shows it"""
+        return [] if self.fill == "random" else [f.key for f in self.last_outputs if self.holds_fill(f)]
+
+    # -- the wrappers -----------------------------------------------------------------------------------------------------
+    def _learn_consts(self, name, real):
+        def learning(*args, **kw):
+            if name == "moddown_consts":
+                self.const_ptrs.add((kw["ws"] if "ws" in kw else args[0]).data_ptr())
+            else:
+                md = (kw["tensors"] if "tensors" in kw else args[1]).get("md_ws")
+                if md is not None:
+                    self.const_ptrs.add(md.data_ptr())
+            return real(*args, **kw)
+        return learning
+
+    def _fence_outputs(self, name, x, path, made):
+        """the nested lists / tuples of `x` with every tensor replaced by a fenced view of the same shape and strides"""
+        if isinstance(x, self.torch.Tensor):
+            f = self.alloc((name, "out") + path, tuple(x.shape), tuple(x.stride()), x.device, target=x)
+            made.append(f)
+            return f.body
+        if isinstance(x, (list, tuple)):
+            return type(x)(self._fence_outputs(name, v, path + (i,), made) for i, v in enumerate(x))
+        return x
+
+    def _fenced_entry(self, name, real, sig):
+        which = [p for p in ("out", "outs") if p in sig.parameters]
+        assert len(which) == 1, (name, which)
+
+        def entry(*args, **kw):
+            bound = sig.bind(*args, **kw)
+            bound.apply_defaults()
+            a = bound.arguments
+            self.calls.append(name)
+            made = []
+            a[which[0]] = self._fence_outputs(name, a[which[0]], (), made)
+            if name == "cc_matmul_native":      # its workspace only grows: a fenced one of exactly the words this call needs
+                words = self.be.cc_matmul_ws_words(a["plan"], len(a["ins"]) // 2)
+                k = ("cc_matmul_ws", words, str(a["ws"].device))
+                if k not in self.scratch:
+                    self.scratch[k] = self.alloc(k, (words,), None, a["ws"].device)
+                a["ws"] = self.scratch[k].body
+            self.last_outputs = made
+            if self.ws_hook is not None:
+                self.ws_hook(name, a)
+            ret = real(*bound.args, **bound.kwargs)
+            self.check(made)
+            self.never_written += self.unwritten()
+            for f in made:
+                f.target.copy_(f.body)
+            return ret
+        return entry
+
+
+def tensors_of(x, out=None):
+    """every tensor reachable from x through lists, tuples, dicts and the `data` of data_struct objects, in order"""
+    import torch
+    out = [] if out is None else out
+    if isinstance(x, torch.Tensor):
+        out.append(x)
+    elif hasattr(x, "origin") and hasattr(x, "data"):
+        tensors_of(x.data, out)
+    elif isinstance(x, dict):
+        for k in sorted(x, key=str):
+            tensors_of(x[k], out)
+    elif isinstance(x, (list, tuple)):
+        for v in x:
+            tensors_of(v, out)
+    return out
+
+
+class Untouched:
+    """Clones of every tensor of the operands (ciphertext components, key parts, diagonals, plaintexts) taken before a call;
+    check(what) afterwards fails with the operand's name and the first changed word."""
+
+    def __init__(self, **operands):
+        self.kept = {}
+        for name, x in operands.items():
+            self.add(name, x)
+
+    def add(self, name, x):
+        seen = {}
+        for t in tensors_of(x):
+            seen.setdefault((t.data_ptr(), tuple(t.shape), tuple(t.stride())), t)
+        self.kept[name] = [(t, t.clone()) for t in seen.values()]
+
+    def check(self, what=""):
+        import torch
+        for name, pairs in self.kept.items():
+            for i, (t, c) in enumerate(pairs):
+                if not torch.equal(t, c):
+                    bad = (t != c).nonzero()
+                    raise AssertionError(f"{what}: operand {name!r} was modified (tensor {i}): {len(bad)} words, first at "
+                                         f"{tuple(int(v) for v in bad[0])}")

@@ -35,6 +35,7 @@ class CcMatmulOps:
         encdec.CC_MATMUL_MAX_OPERANDS distinct operands (encdec.cc_matmul_plan): usually one for the whole product.
         ValueError for an empty matrix, ragged rows, mismatched inner dimensions, an output with no term; the entries' checks
         are cc_dot's."""
+        self._enter()
         A, B = [list(r) for r in A], [list(r) for r in B]
         m, k, n, calls = encdec.cc_matmul_plan(A, B)
         distinct = list({id(x): x for M in (A, B) for row in M for x in row if x is not None}.values())
@@ -71,6 +72,8 @@ class CcMatmulOps:
         words, key = self.backend.cc_matmul_ws_words(plan, nu), ("matmul_ws", d, self._lane)
         ws = self._workspace.get(key)
         if ws is None or ws.numel() < words:
+            if ws is not None:
+                self._retire([ws], d)       # the smaller store may still be read by a call pending on another stream
             ws = self._workspace[key] = torch.empty((words,), dtype=torch.int64, device=self.ntt.devices[d])
         outs = [torch.empty((2, plan.ell, N), dtype=torch.int64, device=self.ntt.devices[d]) for _ in range(nout)]
         self.backend.cc_matmul_native(plan, rows, k, n, ins, row0s, call["ia"], call["ib"], kpack, first_part, row_off, outs, ws)

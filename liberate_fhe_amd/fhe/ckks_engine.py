@@ -23,6 +23,7 @@ from __future__ import annotations
 import ctypes
 import math
 import os
+import sys
 import weakref
 from collections import OrderedDict
 from hashlib import sha256
@@ -44,6 +45,8 @@ from .polyeval import PolyOps
 from .presets import errors, types
 from .slotsum import SlotSumOps
 from .version import VERSION
+
+_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)   # the current stream's handle without a Stream object per call
 
 
 class _OneShard:
@@ -140,6 +143,7 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMa
         self.galois_deltas = [2 ** i for i in range(self.ctx.logN - 1)]
         self._tables = {}
         self._wsum_tables = OrderedDict()   # polyeval.py: device tables of weighted_sums' integers, least recently used of 64 dropped
+        self._scalar_rows = OrderedDict()   # evaluator.py: _row_scalars' device vectors, least recently used of 256 dropped
         self._key_packs = {}
         self._workspace = {}
         self._md_ready = set()
@@ -152,6 +156,8 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMa
         self.ks_horner = True
         self._lane_streams = {}
         self._last_stream = {}  # (device, lane) -> the torch stream its last op was enqueued on (_same_stream)
+        self._last_raw = {}     # (device, lane) -> that stream's raw handle; _cuda_index: device id -> CUDA device index, -1: not one
+        self._cuda_index = {}
         self._check_kernel_limits()
 
         ds, nd, ls = data_struct, np.ndarray, list
@@ -225,16 +231,63 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMa
     def _same_stream(self, dev_id):
         """The scratch of (device, lane) is ordered by the stream its ops run on.  An op enqueued on ANOTHER current stream than the
         lane's previous op first makes that stream wait for the previous one (a device-side dependency, no host block): a caller
-        that alternates streams between ops of one engine gets serialised scratch instead of a race.  One pointer compare per op."""
-        dev = self.ntt.devices[dev_id]
-        if not str(dev).startswith("cuda"):
+        that alternates streams between ops of one engine gets serialised scratch instead of a race.  One compare of raw stream
+        handles per call (no Stream object unless the stream changed: an op asks first thing, through _enter, and again with its
+        scratch); the Stream kept in _last_stream keeps the handle from being reused."""
+        index = self._cuda_index.get(dev_id)
+        if index is None:
+            dev = self.ntt.psi[dev_id].device       # (where the tables live: an index even where the engine was given "cuda")
+            index = self._cuda_index[dev_id] = dev.index if dev.type == "cuda" else -1
+        if index < 0:
             return
-        cur = torch.cuda.current_stream(dev)
         k = (dev_id, self._lane)
+        if _raw_stream is not None and self._last_raw.get(k) == _raw_stream(index):
+            return
+        cur = torch.cuda.current_stream(index)
         last = self._last_stream.get(k)
         if last is not None and last.cuda_stream != cur.cuda_stream:
             cur.wait_stream(last)
         self._last_stream[k] = cur
+        self._last_raw[k] = cur.cuda_stream
+
+    def _enter(self):
+        """First line of every public op that uses engine scratch or a key, and of rescale, pc_mult and pc_add: _same_stream on
+        every local device, BEFORE the op reads engine state or launches anything (an op that orders itself only when it first
+        asks for scratch has launched on its operands by then).  The element-wise ops without scratch (cc_add, cc_sub, level_up,
+        negate, the scalar ops, mc_mult, mc_add, encrypt, decrypt) do not call it: their operands are the caller's to order."""
+        for d in self.local_ids:
+            self._same_stream(d)
+
+    def _retire(self, tensors, dev_id=None):
+        """Engine-owned device tensors about to be dropped (a replaced workspace, an evicted table, a key's planes copy, a raw
+        pack whose storage is freed): the caching allocator returns a block to the pool of the stream it was ALLOCATED on, where
+        the next allocation may overwrite it at once — while work this engine enqueued on another stream still reads it.  Every
+        stream that can have such work (the last stream of each lane, the side lanes' streams, the current stream; earlier ones
+        are ordered before these by _same_stream and the joins of _run_groups) is recorded on the block, which the allocator
+        then holds back until that work is done.  No host block; only ever on the rare paths that drop a tensor."""
+        self._record_streams(self._last_stream, self._lane_streams, tensors, dev_id, current=True)
+
+    @staticmethod
+    def _record_streams(last_stream, lane_streams, tensors, dev_id=None, current=False):
+        tensors = [t for t in tensors if isinstance(t, torch.Tensor) and t.is_cuda and t.untyped_storage().nbytes()]
+        if not tensors:
+            return
+        streams = {}
+        for (d, _), s in last_stream.items():
+            if dev_id is None or d == dev_id:
+                streams[(s.device, s.cuda_stream)] = s
+        for d, sides in lane_streams.items():
+            if dev_id is None or d == dev_id:
+                for s in sides:
+                    streams[(s.device, s.cuda_stream)] = s
+        if current:
+            for dev in {t.device for t in tensors}:
+                s = torch.cuda.current_stream(dev)
+                streams[(s.device, s.cuda_stream)] = s
+        for t in tensors:
+            for (dev, _), s in streams.items():
+                if dev == t.device:
+                    t.record_stream(s)
 
     def _ws(self, key, shape, dev_id):
         """Reusable scratch tensor (never returned to the caller); one set per pipeline lane (see _lanes).
@@ -526,7 +579,7 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMa
         # rebuilt when any of its tensors has been modified in place since (torch's version counters)
         self._key_packs[key] = {"ref": weakref.ref(anchor), "packs": packs, "own": own,
                                 "versions": None if own else self._key_versions(ksk)}
-        weakref.finalize(anchor, self._forget_key, self._key_packs, self._tables, key)
+        weakref.finalize(anchor, self._forget_key, self._key_packs, self._tables, key, self._last_stream, self._lane_streams)
         return packs
 
     @staticmethod
@@ -538,10 +591,14 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMa
             del tables[k]
 
     @staticmethod
-    def _forget_key(key_packs, tables, key):
-        """A key's anchor tensor died: its pack, its planes copy and the graphs captured on either go with it."""
+    def _forget_key(key_packs, tables, key, last_stream=None, lane_streams=None):
+        """A key's anchor tensor died: its pack, its planes copy and the graphs captured on either go with it (held back by the
+        allocator until the engine's pending key switches have read them: _retire)."""
         gone = key_packs.pop(key, None)
         if gone:
+            if last_stream is not None and not sys.is_finalizing():
+                held = list(gone.get("planes") or []) + ([] if gone.get("own") else list(gone.get("packs") or []))
+                ckks_engine._record_streams(last_stream, lane_streams, held)
             ckks_engine._purge_graphs(tables, list(gone.get("packs") or []) + list(gone.get("planes") or []))
 
     def _planes_wanted(self):
@@ -578,12 +635,14 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMa
                 ver = tuple(p._version for p in hit["packs"])
                 if hit.get("planes_ver") != ver:
                     self._purge_graphs(self._tables, hit.get("planes") or [])     # graphs captured on the copy being replaced
+                    self._retire(hit.get("planes") or [])
                     hit["planes"] = [self._planes_of([(pk[q_, 0], pk[q_, 1]) for q_ in range(pk.size(0))], i, d)
                                      for i, (d, pk) in enumerate(zip(loc, hit["packs"]))]
                     hit["planes_ver"] = ver
                 return hit["planes"]
             if hit["versions"] == self._key_versions(ksk):
                 return hit["packs"]
+            self._retire(hit["packs"])                  # a foreign key edited in place: the copy being replaced
         packs = []
         for i, d in enumerate(loc):
             if planes:
@@ -610,6 +669,8 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMa
         if hit is None or hit["ref"]() is not self._key_anchor(ksk) or not hit.get("own"):
             raise ValueError("compact_key: not a key made by this engine (a foreign key's tensors are the caller's)")
         self._key_pack(ksk)                       # the planes copy, current
+        # (built from the raw pack by launches on the CURRENT stream, which may not be the stream the pack was allocated on)
+        self._retire(hit["packs"])
         freed = 0
         for pk in hit["packs"]:
             st = pk.untyped_storage()
@@ -664,6 +725,7 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMa
         else:
             gone = self._key_packs.pop(id(self._key_anchor(ksk)), None)
             dropped = (gone or {}).get("packs", [])
+        self._retire(dropped)
         self._purge_graphs(self._tables, dropped)
 
     def invalidate_key(self, ksk):
@@ -967,6 +1029,7 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMa
                                        self._consts(d, nxt, False))
 
     def rescale(self, ct: data_struct, exact_rounding=True) -> data_struct:
+        self._enter()
         if ct.origin != types.origins["ct"]:
             raise errors.NotMatchType(origin=ct.origin, to=types.origins["ct"])
         nxt = ct.level + 1
@@ -1232,6 +1295,7 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMa
     # multiplication (eng.py:1072-1151)
     # =============================================================================================
     def cc_mult(self, a: data_struct, b: data_struct, evk: data_struct, relin=True) -> data_struct:
+        self._enter()
         if a.origin != types.origins["ct"]:
             raise errors.NotMatchType(origin=a.origin, to=types.origins["sk"])
         if b.origin != types.origins["ct"]:
@@ -1297,6 +1361,7 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMa
         return t
 
     def relinearize(self, ct_triplet: data_struct, evk: data_struct) -> data_struct:
+        self._enter()
         if ct_triplet.origin != types.origins["ctt"]:
             raise errors.NotMatchType(origin=ct_triplet.origin, to=types.origins["ctt"])
         if not ct_triplet.ntt_state or not ct_triplet.montgomery_state:
@@ -1386,6 +1451,7 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMa
         backend, relin=False).  One native call (lf_cc_dot) where every limb of both levels is on one device of this process.
         All operands: ciphertexts of one level, coefficient domain, no special limbs; the same object may appear in any number
         of pairs and on both sides of one."""
+        self._enter()
         pairs, l = self._cc_dot_pairs(pairs)
         level = l + 1
         d = self._cc_dot_device(pairs, level) if relin else None
@@ -1414,6 +1480,7 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMa
         per group: ks_dotb_inner_kernel), the sums' inverse transforms and the mod-down — covers the group's summed triplets
         at once.  A leftover single dot goes through cc_dot, and so does every dot for which cc_dot itself would not go native
         (several devices or ranks, a checker backend, operands that are not contiguous, relin_fold off, logN outside 13..17)."""
+        self._enter()
         dots = [self._cc_dot_pairs(pairs) for pairs in dots]
         out = [None] * len(dots)
         sizes = getattr(self.backend, "ks_batch_sizes", ())
@@ -1750,6 +1817,7 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMa
         return d0[0], d1[0]
 
     def switch_key(self, ct: data_struct, ksk: data_struct) -> data_struct:
+        self._enter()
         if ct.origin != types.origins["ct"]:
             raise errors.NotMatchType(origin=ct.origin, to=types.origins["ct"])
         level = ct.level
@@ -1813,6 +1881,7 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMa
         return self.switch_key(permuted, key)
 
     def rotate_single(self, ct: data_struct, rotk: data_struct) -> data_struct:
+        self._enter()
         if ct.origin != types.origins["ct"]:
             raise errors.NotMatchType(origin=ct.origin, to=types.origins["ct"])
         if types.origins["rotk"] not in rotk.origin:
@@ -1826,6 +1895,7 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMa
         [rotate_single(ct, rotk) for ct in cts], bit for bit.  On one GPU, groups of up to 4 coefficient-domain
         ciphertexts of one level go through the key switch together: one launch set per group (4x the blocks per
         launch) and the key — two thirds of the inner product's HBM bytes — is read once per group."""
+        self._enter()
         if types.origins["rotk"] not in rotk.origin:
             raise errors.NotMatchType(origin=rotk.origin, to=types.origins["rotk"])
         for ct in cts:
@@ -1869,6 +1939,7 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMa
         does not commute with the sign flips of X -> X^p; both decrypt to the rotated message), except for a step-0 key.
         One native call (lf_rotate_hoisted) where every limb of the level is on one device of this process; otherwise the same
         words through the engine's steps.  Coefficient-domain ciphertexts without special limbs only."""
+        self._enter()
         if ct.origin != types.origins["ct"]:
             raise errors.NotMatchType(origin=ct.origin, to=types.origins["ct"])
         for k in rotks:
@@ -2052,6 +2123,7 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMa
         otherwise the same words through the engine's steps.  Coefficient-domain ciphertexts without special limbs only.
         Diagonals from encode_diagonals(.., bsgs=n1) take the baby-step / giant-step form (_linear_transform_bsgs): the same
         transform from the keys of the non-zero baby and giant steps (bsgs_steps) alone, with words of its own."""
+        self._enter()
         if ct.origin != types.origins["ct"]:
             raise errors.NotMatchType(origin=ct.origin, to=types.origins["ct"])
         keys = list(rotks.values()) if isinstance(rotks, dict) else list(rotks)
@@ -2211,6 +2283,7 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMa
         through ONE native call.  A group shares every launch but the diagonal products: each baby key (ks_inner_babyb_kernel)
         and each giant key is read once per group, and the tails of every giant step (inverse NTT, mod-down, digits, forward
         pass) run once per group.  Everything else takes linear_transform one by one and keeps its place in the result."""
+        self._enter()
         cts = list(cts)
         if not cts:
             return []
@@ -2626,6 +2699,7 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMa
         [cc_mult(a, b, evk) for a, b in pairs], bit for bit.  On one GPU, groups of up to 4 pairs of one level share
         the inverse transforms of their triplets (one launch) and the key switch (lf_ks_core_batch: one launch set,
         the key read once per group)."""
+        self._enter()
         out = [None] * len(pairs)
         sizes = getattr(self.backend, "ks_batch_sizes", ())
         groups = {}
@@ -2712,6 +2786,7 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMa
         return [self._new(([out[t][0]], [out[t][1]]), types.origins["ct"], level=level) for t in range(nct)]
 
     def rotate_galois(self, ct: data_struct, gk: data_struct, delta: int, return_circuit=False) -> data_struct:
+        self._enter()
         if ct.origin != types.origins["ct"]:
             raise errors.NotMatchType(origin=ct.origin, to=types.origins["ct"])
         if gk.origin != types.origins["galk"]:
@@ -2728,6 +2803,7 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMa
         return (out, circuit) if return_circuit else out
 
     def conjugate(self, ct: data_struct, conjk: data_struct):
+        self._enter()
         return self._automorphism(ct, encdec.conjugation_exponent(self.ctx.N), conjk, canonical=False)
 
     # =============================================================================================
@@ -2797,8 +2873,7 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMa
                 t = new_ct.data[comp][loc_src.index(d)]
                 rows.append(t[t.size(0) - self._rows(d, dst_level, False):].clone())
             data.append(rows)
-        mult = [self._t64([delta * self.ctx.R % self.ctx.q[i] for i in self.ntt.p.destination_arrays[dst_level][d]], d)
-                for d in loc_dst]
+        mult = self._row_scalars(delta, dst_level, True)     # (kept per scalar and level: no host-blocking copy per call)
         for comp in range(2):
             self.ntt.mont_enter_scalar(data[comp], mult, dst_level)
             self.ntt.reduce_2q(data[comp], dst_level)

@@ -261,10 +261,22 @@ class EvaluatorOps:
         return out
 
     def _row_scalars(self, value, level, montgomery):
-        """value (a Python int) as one residue per local row, times R when `montgomery`."""
+        """value (a Python int) as one residue per local row, times R when `montgomery`.  Read-only device vectors, kept (the
+        least recently used of 256 dropped): building one is a copy from pageable host memory, which blocks the host until the
+        current stream has drained — once per scalar and level, not once per op (the constants of a polynomial come back with
+        every evaluation)."""
+        cache = self._scalar_rows
+        key = (value, level, montgomery)
+        hit = cache.get(key)
+        if hit is not None:
+            cache.move_to_end(key)
+            return hit
         v = value * self.ctx.R if montgomery else value
-        return [self._t64([v % self.ctx.q[i] for i in self.ntt.p.destination_arrays[level][d]], d)
-                for d in self._loc(level)]
+        hit = cache[key] = [self._t64([v % self.ctx.q[i] for i in self.ntt.p.destination_arrays[level][d]], d)
+                            for d in self._loc(level)]
+        if len(cache) > 256:
+            self._retire(cache.popitem(last=False)[1])
+        return hit
 
     def _scale_rows(self, ct, scalars):
         out = self.clone(ct)

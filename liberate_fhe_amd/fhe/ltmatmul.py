@@ -132,6 +132,7 @@ class LtMatmulOps:
         One native call (lf_lt_matmul) per 64 outputs where every limb of the level is on one device of this process — each call
         repeats the rotations of its inputs, so more than 64 outputs pay them again; otherwise the same words through the
         engine's steps, the rotated sums formed once per input and step and accumulated into every output that uses them."""
+        self._enter()
         W, steps = self._lt_matmul_blocks(W)
         k_out, k_in = len(W), len(W[0])
         cts, by_step, level = self._lt_matmul_operands("lt_matmul", W, cts, rotks)
@@ -208,6 +209,7 @@ class LtMatmulOps:
         read each rotation key and the block products each diagonal once for the tokens of a launch instead of once per token.
         A token that does not qualify, the one the groups leave over, and every token on a backend without the entry or on a
         sharded or multi-device engine take lt_matmul and keep their place."""
+        self._enter()
         X = [list(cts) for cts in X]
         if not X:
             return []
@@ -464,6 +466,7 @@ class LtMatmulOps:
         is on one device of this process (more outputs or keyed sums are split over calls, each of which repeats the baby steps);
         otherwise the same words through the engine's steps (_lt_matmul_bsgs_steps) — which is also where a matrix goes that has
         a single row beyond the caps of one call, more than 64 giant steps in one row: it is not run natively."""
+        self._enter()
         W, steps, n1 = self._lt_matmul_bsgs_blocks(W, n1)
         cts, by_step, level = self._lt_matmul_operands("lt_matmul_bsgs", W, cts, rotks)
         flat = [s for srow in steps for b in srow if b is not None for s in b]

@@ -69,6 +69,7 @@ class PlainOps:
     def pc_mult(self, pt, ct):
         """mc_mult(m, ct) for pt = encode_plain(m, ct.level): mc_mult's body behind its encode, the same words whenever encode
         returns the same polynomial."""
+        self._enter()
         self._check_plain_pair(pt, ct, "mult")
         l = ct.level
         if l + 1 >= self.num_levels:
@@ -84,6 +85,7 @@ class PlainOps:
 
     def pc_add(self, pt, ct):
         """mc_add(m, ct) for pt = encode_plain(m, ct.level, "add"): mc_add's body behind its encode."""
+        self._enter()
         self._check_plain_pair(pt, ct, "add")
         l = ct.level
         out = self.clone(ct)
@@ -104,6 +106,7 @@ class PlainOps:
         (one pair without bias: pc_mult), which is also what runs where the native call does not apply: several devices or ranks,
         logN outside 13..17, a checker backend, operands that are not contiguous or not 16-byte aligned.  Otherwise ONE native call
         (lf_pc_dot)."""
+        self._enter()
         pairs = [tuple(p) for p in pairs]
         if not pairs:
             raise ValueError("pc_dot: at least one (plaintext, ciphertext) pair")
@@ -188,6 +191,7 @@ class PlainOps:
         and that loop is what runs where the native call does not apply (pc_dot's conditions).  Otherwise ONE native call
         (lf_pc_matmul) per 64 outputs: every ciphertext is transformed once, whatever k_out, and every transformed word is read
         once per group of four outputs."""
+        self._enter()
         W = [list(row) for row in W]
         cts = list(cts)
         k_out = len(W)
@@ -250,6 +254,7 @@ class PlainOps:
         which reads each plaintext word — the larger stream of pc_matmul's products — once per group instead of once per token.  A token
         that does not qualify (a component that is not contiguous, not 16-byte aligned or on the host), the one the groups leave
         over, and every token on a backend without the entry take pc_matmul and keep their place."""
+        self._enter()
         X = [list(cts) for cts in X]
         if not X:
             return []

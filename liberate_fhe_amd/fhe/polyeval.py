@@ -67,6 +67,7 @@ class PolyOps:
     def _weighted_sums_int(self, cts, int_matrix, const_ints=None) -> list:
         """weighted_sums on the Python integers themselves: int_matrix[g][t] multiplies cts[t] (any sign and size: only its
         residues count), const_ints[g] is added to coefficient 0 of c0 after the rescale (the integer add_scalar forms)."""
+        self._enter()
         cts = list(cts)
         l = self._check_sum_operands(cts, "weighted_sums")
         k, G = len(cts), len(int_matrix)
@@ -126,7 +127,7 @@ class PolyOps:
                 cst = None if cpart is None else self._t64([[c % q[i] for i in primes[1:]] for c in cpart], d)
                 hit = cache[key] = (tab, cst)
                 if len(cache) > 64:
-                    cache.popitem(last=False)
+                    self._retire(cache.popitem(last=False)[1], d)     # (today the blocking copy above has drained its readers)
             else:
                 cache.move_to_end(key)
             tab, cst = hit
@@ -207,6 +208,7 @@ class PolyOps:
           giants: y = p_n1 by the same rule from p_{n1 / 2}, y^g (plain powers in both bases) by the power rule
           q_g, y^g level_up'd to L_c = max(level of y^(G - 1), L_b + 1);  r = cc_dot([(q_g, y^g) g >= 1], evk)
           result = cc_add(r, level_up(q_0, L_c + 1));  G = 1: q_0."""
+        self._enter()
         if not is_struct(ct) or ct.origin != types.origins["ct"]:
             raise errors.NotMatchType(origin=getattr(ct, "origin", type(ct).__name__), to=types.origins["ct"])
         if ct.ntt_state or ct.include_special:
@@ -263,6 +265,7 @@ class PolyOps:
         cc_mult_batch and cc_dot_batch return the words of cc_mult and cc_dot, so each result has the words of poly_eval's
         composition.  An empty list: ValueError; ciphertexts of different levels: NotMatchDataStructState; the other refusals are
         poly_eval's, before any work."""
+        self._enter()
         cts = list(cts)
         if not cts:
             raise ValueError("poly_eval_batch: at least one ciphertext")

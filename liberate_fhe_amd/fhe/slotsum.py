@@ -37,6 +37,7 @@ class SlotSumOps:
         on the special rows; S_c = sum of the t_c; intt_exit_reduce, mod-down without addend.  No rescale.  One native call
         (lf_rotate_sum) where every limb of the level is on one device of this process; otherwise the same words through the
         engine's steps.  Coefficient-domain ciphertexts without special limbs only."""
+        self._enter()
         if ct.origin != types.origins["ct"]:
             raise errors.NotMatchType(origin=ct.origin, to=types.origins["ct"])
         keys = list(keys)
@@ -159,6 +160,7 @@ class SlotSumOps:
         of the op — reads each key word once per group instead of once per ciphertext, looping over the keys inside the
         kernel (ks_inner_rsumb_kernel) with one accumulator pair per ciphertext.  Ciphertexts that do not qualify, the one left
         over by the groups, and every ciphertext on a backend without the entry take rotate_sum one by one."""
+        self._enter()
         cts = list(cts)
         if not cts:
             return []
@@ -223,6 +225,7 @@ class SlotSumOps:
         cts], word for word and in order.  It validates like inner_sum, for the whole list before anything runs, and then chains
         one rotate_sum_batch(.., include_self=True) per stage of encdec.inner_sum_plan, so every stage reads its keys once per
         group of ciphertexts (inner_sum_steps lists the steps a key is needed for).  An empty list gives []."""
+        self._enter()
         cts = list(cts)
         if not cts:
             return []
@@ -257,6 +260,7 @@ class SlotSumOps:
         rotate_sum(.., include_self=True) per stage, chained — a radix-r stage adds r shifted copies for r - 1 gathered inner
         products and ONE set of digits, inverse NTT and mod-down; radix=2 is the classic log fold in hoisted words.  rotks: a
         list or mapping of rotation keys, looked up by the step in their origin (inner_sum_steps lists the steps needed)."""
+        self._enter()
         if ct.origin != types.origins["ct"]:
             raise errors.NotMatchType(origin=ct.origin, to=types.origins["ct"])
         plan = encdec.inner_sum_plan(n, stride, self.num_slots, radix)

@@ -987,3 +987,153 @@ class Untouched:
                     bad = (t != c).nonzero()
                     raise AssertionError(f"{what}: operand {name!r} was modified (tensor {i}): {len(bad)} words, first at "
                                          f"{tuple(int(v) for v in bad[0])}")
+
+
+# ---- held streams (tests/test_stream_contract_gpu.py) -------------------------------------------------------------------------
+# The engine's stream contract is about what happens while a stream is BUSY: a test that enqueues ops back to back on idle
+# streams passes whenever the kernels happen not to overlap.  hold() makes a stream busy for a known time with the project's own
+# one-wave spin kernel (lf_clock_probe: bounded, one wave, 16 bytes of output), so "B waited for A" and "B did not wait for A"
+# become two event queries.
+_HOLD_OUT, _INDEPENDENT = {}, {}
+
+
+def hold(stream, ms):
+    """Keeps `stream` busy for `ms` milliseconds (ms * 100_000 ticks of the constant 100 MHz counter) from the moment the
+    spin kernel starts; returns an event recorded right behind it."""
+    import torch
+
+    from liberate_fhe_amd._native import check, lib
+    dev = stream.device
+    out = _HOLD_OUT.get(dev)
+    if out is None:
+        out = _HOLD_OUT[dev] = torch.zeros(2, dtype=torch.int64, device=dev)      # (every hold writes the same 16 bytes)
+        torch.cuda.synchronize(dev)
+    check(lib.lf_clock_probe(out.data_ptr(), 1, int(ms * 100_000), dev.index, stream.cuda_stream), "lf_clock_probe")
+    ev = torch.cuda.Event()
+    ev.record(stream)
+    return ev
+
+
+def still_held(ev):
+    return not ev.query()
+
+
+def independent_streams(device, hold_ms=5):
+    """Two torch streams of `device` that this process's hardware queues run independently: a trivial kernel on the second
+    completes while the first is held.  Streams that share a hardware queue would make every ordering check pass whatever the
+    engine does.  At most 8 candidates; AssertionError (never a skip) if no pair is found.  One pair per device and process."""
+    import time
+
+    import torch
+    device = torch.device(device)
+    if device in _INDEPENDENT:
+        return _INDEPENDENT[device]
+    first = torch.cuda.Stream(device=device)
+    probe = torch.zeros(64, dtype=torch.int64, device=device)
+    torch.cuda.synchronize(device)
+    tried = []
+    for _ in range(7):
+        second = torch.cuda.Stream(device=device)
+        ev = hold(first, hold_ms)
+        with torch.cuda.stream(second):
+            probe.add_(1)
+        done = torch.cuda.Event()
+        done.record(second)
+        t0 = time.perf_counter()
+        while not done.query() and still_held(ev):
+            pass
+        ok = done.query() and still_held(ev)
+        tried.append((second.cuda_stream, ok, round(1e3 * (time.perf_counter() - t0), 2)))
+        torch.cuda.synchronize(device)
+        if ok:
+            _INDEPENDENT[device] = (first, second)
+            return first, second
+    raise AssertionError(f"independent_streams: no stream of {device} ran while another was held for {hold_ms} ms "
+                         f"(stream, ran beside the hold, ms waited): {tried}; the ordering checks cannot tell anything here")
+
+
+def zeroed_free_memory(device, nbytes):
+    """Allocates and zero-fills about `nbytes` in blocks of mixed sizes and drops them WITHOUT empty_cache: what the next lazily
+    built table or key pack gets from the caching allocator is then zeros (best effort), not a stale correct copy left by an
+    earlier engine of the same parameters.  Zeros, not the hostile fills of Fence: an index table read before it is built must
+    stay in range, so that a defect shows as wrong words and never as a wild access."""
+    import torch
+    sizes = (512, 4096, 1 << 16, 1 << 20, 1 << 22, 1 << 24)
+    blocks, total, i = [], 0, 0
+    while total < nbytes:
+        n = min(sizes[i % len(sizes)], max(512, nbytes - total))
+        blocks.append(torch.zeros(n, dtype=torch.uint8, device=device))
+        total += n
+        i += 1
+    torch.cuda.synchronize(device)
+    del blocks
+    return total
+
+
+class BackendSpy:
+    """Wraps every method of a backend instance that can launch (its public instance methods) and
+    torch.cuda.Stream.wait_stream while the block runs.  `log` is the sequence of
+    ("call", name) and ("wait", waiting stream handle, awaited stream handle); `before(name)` — if given — runs ahead of
+    every wrapped call (tests hold a stream there).  `also`: further launchers — objects or modules whose public callables
+    (those named in `__all__`, where there is one) are wrapped and logged in the same way: the engine's element-wise ops go
+    through `engine.ntt.ops`, not through the backend.  Plain torch ops are not seen."""
+    def __init__(self, backend, before=None, also=()):
+        self.backend, self.before, self.log, self._names, self._wait = backend, before, [], [], None
+        self.also, self._also = tuple(also), []
+
+    def launchers(self):
+        """the backend's public instance methods (the static ones — the *_ws_words sizes, mark_planes — run on the host)"""
+        import inspect
+        cls = type(self.backend)
+        return [n for n in dir(cls) if not n.startswith("_") and inspect.isfunction(inspect.getattr_static(cls, n))]
+
+    def calls(self):
+        return [e[1] for e in self.log if e[0] == "call"]
+
+    def __enter__(self):
+        import torch
+        for name in self.launchers():
+            if name in self.backend.__dict__:         # (already wrapped by someone else: leave it)
+                continue
+            real = getattr(self.backend, name)
+
+            def spied(*args, _real=real, _name=name, **kw):
+                if self.before is not None:
+                    self.before(_name)
+                self.log.append(("call", _name))
+                return _real(*args, **kw)
+
+            setattr(self.backend, name, spied)
+            self._names.append(name)
+        for obj in self.also:
+            for name in getattr(obj, "__all__", None) or [n for n in dir(obj) if not n.startswith("_")]:
+                real = getattr(obj, name)
+                if not callable(real) or isinstance(real, type):
+                    continue
+
+                def spied(*args, _real=real, _name=name, **kw):
+                    if self.before is not None:
+                        self.before(_name)
+                    self.log.append(("call", _name))
+                    return _real(*args, **kw)
+
+                setattr(obj, name, spied)
+                self._also.append((obj, name, real))
+        self._wait = torch.cuda.Stream.wait_stream
+        spy = self
+
+        def wait_stream(stream, other):
+            spy.log.append(("wait", stream.cuda_stream, other.cuda_stream))
+            return spy._wait(stream, other)
+
+        torch.cuda.Stream.wait_stream = wait_stream
+        return self
+
+    def __exit__(self, *exc):
+        import torch
+        torch.cuda.Stream.wait_stream = self._wait
+        for name in self._names:
+            delattr(self.backend, name)
+        for obj, name, real in self._also:
+            setattr(obj, name, real)
+        self._names, self._also = [], []

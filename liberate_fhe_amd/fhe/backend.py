@@ -355,6 +355,13 @@ class HipBackend:
               "lf_cc_mult_evk_batch")
 
     # ---- the halves of an op around the digit exchange (one process per GPU) -----------------------------------------
+    @staticmethod
+    def format_knobs():
+        """(LF_TUNE_DIGIT_PLANES, LF_TUNE_MORE_PLANES) as they stand: the knobs that decide the FORMAT of the scratch between
+        the halves of an op.  Whatever bakes launches of the halves (a captured graph) is only valid under the pair it was
+        made under; two reads of process-wide integers, no launch."""
+        return lib.lf_tune(3, -1), lib.lf_tune(5, -1)
+
     def cc_mult_pre(self, plan, ins, row0s, st, which=3):
         """which: 1 = the launch that reads the operands, 2 = the rest of the half (plan addresses only), 3 = both."""
         check(lib.lf_cc_mult_evk_pre(ctypes.byref(plan), ins, row0s, which, st), "lf_cc_mult_evk_pre")

@@ -1174,7 +1174,7 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMa
 
     def _sharded_segments(self, kind, level, d, plan, kpack, first_part, row_off, capture=False):
         """The launches of a rank's half-ops that only touch the plan's scratch, the tables and the key, captured ONCE per
-        (op kind, level, lane, key pack) into three HIP graphs around the digit exchange:
+        (op kind, level, lane, key pack, format knobs) into three HIP graphs around the digit exchange:
             a1  cc_mult: the rest of `pre` (tiled pass of the operands, x1 * y1, inverse NTT, digits); both kinds: this rank's
                 digit rows into the storage-order exchange buffer;
             a2  extension + forward NTT of the digits it owns (runs beside the exchange);
@@ -1190,7 +1190,12 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMa
         if not self.graph_sharded or not str(dev).startswith("cuda") or not hasattr(torch.cuda, "CUDAGraph"):
             return None
         fmt = getattr(kpack, "lf_key_format", 0)
-        key = ("sgraph", kind, level, d, self._lane, kpack.data_ptr(), tuple(kpack.stride()), fmt, first_part, row_off)
+        # the scratch formats are baked into the graphs, and the LF_ERR_STATE guard of the halves works at launch time on the
+        # host, which a replay never reaches: the two format knobs (lf_tune, process-wide) are part of the key, so that the
+        # eager launches of an op (pre(which=1): the operand stack) never meet segments captured under other formats — the
+        # first op under a new setting runs eagerly and captures its own
+        key = ("sgraph", kind, level, d, self._lane, kpack.data_ptr(), tuple(kpack.stride()), fmt, first_part, row_off,
+               self.backend.format_knobs())
         hit = self._tables.get(key)
         if hit is not None or not capture:
             return hit

@@ -751,6 +751,9 @@ NATIVE_ENTRIES = ("switch_key_native", "cc_mult_evk", "switch_key_batch_native",
                   "pc_matmul_batch_native", "rotate_hoisted_native", "linear_transform_native", "linear_transform_batch_native",
                   "rotate_sum_native", "rotate_sum_batch_native", "linear_transform_bsgs_native",
                   "linear_transform_bsgs_batch_native", "lt_matmul_native", "lt_matmul_batch_native", "lt_matmul_bsgs_native")
+# the halves of a limb-sharded op around the digit exchange (one process per GPU): the two that take `out` get fenced outputs (out
+# may be None: which = 1 writes plan scratch only), the three that take none get the guard check of all scratch on the way out
+HALF_ENTRIES = ("cc_mult_pre", "switch_key_pre", "plan_fwd", "cc_mult_post", "switch_key_post")
 # the hostile fills of scratch bodies and outputs: every bit set (-1 as a word, a NaN as fp64, 0xFF in every plane byte), the
 # largest word, seeded uniform 64-bit words.  Zero — what a fresh process often finds in new pages — is the friendly case.
 FENCE_FILLS = {"ones": -1, "max": (1 << 63) - 1, "random": "random"}
@@ -776,10 +779,12 @@ class Fence:
                 d2 and every op workspace, of every lane — is the middle view(shape) of a larger allocation.  cc_matmul keeps its
                 growing workspace outside _ws: backend.cc_matmul_native is handed a fenced one of exactly
                 cc_matmul_ws_words(plan, nu) words instead.
-      outputs   every method of NATIVE_ENTRIES the backend has is wrapped: the tensors of its `out` / `outs` argument (found by
+      outputs   every method of NATIVE_ENTRIES and HALF_ENTRIES the backend has is wrapped: the tensors of its `out` / `outs` argument (found by
                 name in the signature, nested lists walked) are replaced by fenced views of the same shape and strides; after the
                 call the guards of the outputs AND of all scratch are checked and the bodies copied into the engine's own tensors.
-                `calls` lists the entries that ran, in order.
+                `calls` lists the entries that ran, in order.  A half without `out`, or handed out = None, gets the guard check of
+                all scratch on the way out.  A half called inside a stream capture is passed through unchecked (a guard check
+                reads the device, which a capture forbids).
       guards    `guard` words before and behind each body: one polynomial of level 0's full row count, (ell + K) N words, an even
                 count (the body stays 16-byte aligned).  They hold a seeded, position-dependent 64-bit pattern XORed with a salt of
                 their own; check() compares them with the kept pattern and raises FenceError naming the buffer's key, the side
@@ -821,7 +826,7 @@ class Fence:
         for name in ("moddown_consts", "make_plan"):
             if hasattr(self.be, name):
                 setattr(self.be, name, self._learn_consts(name, getattr(self.be, name)))
-        for name in NATIVE_ENTRIES:
+        for name in NATIVE_ENTRIES + HALF_ENTRIES:
             if hasattr(self.be, name):
                 real = getattr(self.be, name)
                 setattr(self.be, name, self._fenced_entry(name, real, inspect.signature(real)))
@@ -897,6 +902,10 @@ class Fence:
         return [] if self.fill == "random" else [f.key for f in self.last_outputs if self.holds_fill(f)]
 
     # -- the wrappers -----------------------------------------------------------------------------------------------------
+    def _capturing(self):
+        cuda = self.torch.cuda
+        return bool(cuda.is_available() and hasattr(cuda, "is_current_stream_capturing") and cuda.is_current_stream_capturing())
+
     def _learn_consts(self, name, real):
         def learning(*args, **kw):
             if name == "moddown_consts":
@@ -920,15 +929,20 @@ class Fence:
 
     def _fenced_entry(self, name, real, sig):
         which = [p for p in ("out", "outs") if p in sig.parameters]
-        assert len(which) == 1, (name, which)
+        assert len(which) == (0 if name in HALF_ENTRIES[:3] else 1), (name, which)
 
         def entry(*args, **kw):
+            if name in HALF_ENTRIES and self._capturing():
+                # a half inside a stream capture (ckks_engine._sharded_segments: plan addresses only, out is None): a guard
+                # check reads the device, which a capture forbids; the replays are checked by whoever issued them (check())
+                return real(*args, **kw)
             bound = sig.bind(*args, **kw)
             bound.apply_defaults()
             a = bound.arguments
             self.calls.append(name)
             made = []
-            a[which[0]] = self._fence_outputs(name, a[which[0]], (), made)
+            if which:
+                a[which[0]] = self._fence_outputs(name, a[which[0]], (), made)
             if name == "cc_matmul_native":      # its workspace only grows: a fenced one of exactly the words this call needs
                 words = self.be.cc_matmul_ws_words(a["plan"], len(a["ins"]) // 2)
                 k = ("cc_matmul_ws", words, str(a["ws"].device))
@@ -1018,6 +1032,30 @@ def still_held(ev):
     return not ev.query()
 
 
+def hold_report(stream, ms):
+    """One hold of `ms` on `stream`, taken apart, as text for a failure message: how long the enqueue kept the host, when the event
+    behind the spin kernel reported completion, and what the kernel itself counted.  A pair of streams on one hardware queue shows
+    waits of about `ms`; waits near zero mean the hold did not hold, and these three figures say which way: the enqueue blocked the
+    host for the hold (host ms about `ms`); the kernel ran short (ticks below ms x 100 000: the constant counter is not 100 MHz
+    here); or the event completed ahead of the kernel (ticks right, event ms far below `ms`)."""
+    import time
+
+    import torch
+    torch.cuda.synchronize(stream.device)
+    t0 = time.perf_counter()
+    ev = hold(stream, ms)
+    t1 = time.perf_counter()
+    first = ev.query()
+    while not ev.query() and time.perf_counter() - t1 < 1.0:
+        pass
+    t2 = time.perf_counter()
+    torch.cuda.synchronize(stream.device)
+    cycles, ticks = (int(v) for v in _HOLD_OUT[stream.device].tolist())
+    return (f"one more hold of {ms} ms taken apart: hold() kept the host {1e3 * (t1 - t0):.3f} ms, its event was "
+            f"{'already complete' if first else 'pending'} at the first query and complete {1e3 * (t2 - t0):.3f} ms after the enqueue began, "
+            f"the kernel counted {ticks} ticks of the constant counter (asked: {int(ms * 100_000)}) in {cycles} core cycles")
+
+
 def independent_streams(device, hold_ms=5):
     """Two torch streams of `device` that this process's hardware queues run independently: a trivial kernel on the second
     completes while the first is held.  Streams that share a hardware queue would make every ordering check pass whatever the
@@ -1049,7 +1087,8 @@ def independent_streams(device, hold_ms=5):
             _INDEPENDENT[device] = (first, second)
             return first, second
     raise AssertionError(f"independent_streams: no stream of {device} ran while another was held for {hold_ms} ms "
-                         f"(stream, ran beside the hold, ms waited): {tried}; the ordering checks cannot tell anything here")
+                         f"(stream, ran beside the hold, ms waited): {tried}; the ordering checks cannot tell anything here; "
+                         f"{hold_report(first, hold_ms)}")
 
 
 def zeroed_free_memory(device, nbytes):

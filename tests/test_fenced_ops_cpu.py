@@ -6,7 +6,7 @@ import pytest
 import torch
 
 from liberate_fhe_amd.utils import synth
-from tests.helpers import FENCE_FILLS, NATIVE_ENTRIES, Fence, FenceError, Untouched
+from tests.helpers import FENCE_FILLS, HALF_ENTRIES, NATIVE_ENTRIES, Fence, FenceError, Untouched
 
 SMALL = dict(logN=12, num_scales=3, num_special_primes=2, is_secured=False)
 
@@ -27,7 +27,8 @@ def words(ct):
 
 def test_the_list_of_entries_is_the_backends():
     """NATIVE_ENTRIES is every HipBackend method with an `out` or `outs` parameter that stands for a whole op: the 21 from
-    switch_key_native / cc_mult_evk to lt_matmul_bsgs_native (the step methods and the sharded halves are out of scope)."""
+    switch_key_native / cc_mult_evk to lt_matmul_bsgs_native (the step methods are out of scope; the sharded halves are
+    HALF_ENTRIES, below)."""
     import inspect
     src = inspect.getsource(__import__("liberate_fhe_amd.fhe.backend", fromlist=["x"]))
     import re
@@ -149,3 +150,36 @@ def test_refill_skips_what_holds_constants():
     fence.refill()
     assert a[:4].tolist() == [11] * 4 and b[:4].tolist() == [12] * 4 and bool((c == FENCE_FILLS["max"]).all())
     fence.check()
+
+
+def test_the_halves_of_a_sharded_op_are_the_backends_and_are_fenced():
+    """HALF_ENTRIES is every method of the backend's section "the halves of an op around the digit exchange" that launches; the
+    fence wraps each one a backend has.  A stub plan_fwd (no `out`: the guard check of all scratch on the way out) that writes
+    one word behind the exchange buffer ks_digits_all is reported at that buffer; a stub cc_mult_post handed out = None
+    (which = 1: plan scratch only) runs, and with an `out` it gets a fenced one whose words arrive."""
+    import inspect
+    from liberate_fhe_amd.fhe import backend as B
+    src = inspect.getsource(B.HipBackend)
+    section = src[src.index("the halves of an op around the digit exchange"):src.index("def cc_mult_evk(")]
+    import re
+    assert sorted(re.findall(r"^    def (\w+)\(self", section, re.M)) == sorted(HALF_ENTRIES)
+
+    def plan_fwd(plan, digits, first, count, relin):
+        scribble(digits, digits.numel())
+
+    def cc_mult_post(plan, key, first_part, row_off, out, which=3):
+        if out is not None:
+            out.fill_(7)
+
+    eng = engine({"plan_fwd": plan_fwd, "cc_mult_post": cc_mult_post})
+    fence = Fence(eng, -1)
+    N = eng.ctx.N
+    buf = eng._ws("ks_digits_all", (3, N), 0)
+    eng.backend.cc_mult_post(None, None, 0, 0, None, which=1)
+    out = torch.empty((2, 3, N), dtype=torch.int64)
+    eng.backend.cc_mult_post(None, None, 0, 0, out)
+    assert fence.calls == ["cc_mult_post", "cc_mult_post"] and bool((out == 7).all()) and not fence.unwritten()
+    with pytest.raises(FenceError) as e:
+        eng.backend.plan_fwd(None, buf, 0, 1, True)
+    msg = str(e.value)
+    assert msg.startswith("('ks_digits_all', ") and "guard behind the buffer" in msg and "at offset 0 (1 of" in msg, msg

@@ -21,8 +21,11 @@ Refusals, on sb41_K2 through the same wrappers: each of the sixteen entries with
 *_ws_words says, and each entry whose header promises it refuses a misaligned one (LF_ERR_ARG, every fenced body still at its fill:
 nothing was launched).  The knob walk (LF_TUNE_DIGIT_PLANES x LF_TUNE_MORE_PLANES) runs in a child process.
 
-Not covered here: the limb-sharded halves (lf_*_pre / lf_*_post, lf_ks_plan_fwd), their graph-replayed segments, two logical
-devices and anything that crosses xGMI; the NTT workspace and the step kernels have fences of their own."""
+The limb-sharded halves (lf_*_pre / lf_*_post, lf_ks_plan_fwd) and their graph-replayed segments run under the same fence in the
+ranks of tests/test_sharded_edges_gpu.py (Fence wraps HALF_ENTRIES too: fenced outputs for the post halves, the guard check of all
+scratch behind the others; sb41_K2 and sb40_K1, two ranks and a solo rank, the three fills, refill() before every case, between
+a capture and its replays included).  Not covered: the in-process engine over two logical devices under the fence, and anything that
+crosses xGMI; the NTT workspace and the step kernels have fences of their own."""
 import os
 import warnings
 

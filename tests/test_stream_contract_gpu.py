@@ -29,8 +29,11 @@ hardware queues first (tests/helpers.independent_streams): on a shared queue eve
 
 All words are torch.equal to the same call on one stream with nothing held.  Operands: liberate_fhe_amd.utils.synth.
 
-Not covered: the sharded halves and their graph-replayed segments (_sharded_segments), two logical devices, ntt_cuda's
-per-stream workspace (tests/test_ntt_cuda_gpu.py), the samplers' generator state under two streams."""
+The sharded halves and their graph-replayed segments (_sharded_segments) are held in a solo-rank child process by
+tests/test_sharded_edges_gpu.py (a replay behind a held replay and behind a held eager op of the other kind, both ways round).
+Not covered: the ordering of two ranks' EXCHANGE against the graphs on device streams (the gloo staging transport of a one-GPU box
+blocks the host; tools/rccl_world1.py's stream_ordering is what there is), the in-process engine over two logical devices,
+ntt_cuda's per-stream workspace (tests/test_ntt_cuda_gpu.py), the samplers' generator state under two streams."""
 import time
 import warnings
 

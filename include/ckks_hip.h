@@ -829,6 +829,44 @@ int lf_lt_matmul_bsgs(const lf_ks_plan *plan, int k_in, int k_out, const int64_t
                       const int64_t *gcount, const int64_t *bidx, const int64_t *rescale_scales, int64_t round_at, int64_t *ws,
                       int64_t ws_words, int64_t *const *out0, int64_t *const *out1, void *stream);
 
+/* lf_lt_matmul_bsgs over nt token vectors that share the matrix, the baby keys and the giant keys: for t < nt, o < k_out,
+ * out_{t,o} decrypts to sum_i sum_step diag_{o,i,step} * rot(m_{t,i}, step).  ONE call is one group of nt in {1, 2, 4} tokens,
+ * nt <= plan->max_nct.  in: HOST array of nt 2 k_in device pointers, [token][input][component] (the pointers of an input no block
+ * uses are not read, for any token); out0 / out1: HOST arrays of nt k_out pointers, [token][output]; everything else is
+ * lf_lt_matmul_bsgs's, shared by all tokens; keyed_sums and the caps (LF_LT_MATMUL_MAX_OUTPUTS, LF_LT_MATMUL_BSGS_MAX_GIANTS,
+ * LF_LT_MATMUL_BSGS_MAX_SUMS) count per token.  The same polynomial may appear any number of times among `in`.
+ * Output (t, o) has exactly the words of lf_lt_matmul_bsgs on token t: only residues of u, S, v and A reach the result, and the
+ * transforms act on each polynomial by itself.  nt = 1 IS lf_lt_matmul_bsgs (the same launches).
+ * Enqueued for nt = 2 | 4: (1) input-major, per input some block uses, steps 1 - 2 of lf_lt_matmul_batch: the canonical copies
+ * and ONE forward NTT of the 2 nt polynomials into slot 0 of every token (zero on the special rows); where the column has baby
+ * keys ONE lf_ks_digits_batch, ONE extension + forward NTT of the nt nparts digits and per baby key ONE launch of
+ * ks_inner_babyb_kernel<nt> into slot 1 + j of every token.  Then lf_lt_matmul_bsgs's products: the pairs (o, j) that have a
+ * diagonal in the column, those of giant step 0 and the keyed ones apart (the accumulators A [nt][k_out] and the keyed sums
+ * S [nt][keyed_sums] have different token strides and a launch takes one), each kind in groups of 4, 2 or 1 through
+ * lt_block_productsb_kernel<4 | 2 | 1, 2>, one launch per tile of 2 tokens; the target of (o, giant step 0) is token t's
+ * accumulator A^{t,o} itself, an accumulator without giant step 0 is zeroed by one hipMemsetAsync.  (2) giant-step-major: per
+ * keyed giant step the members (t, o) that have it, output-major with the tokens of an output adjacent, in chunks of n = 4, 2 or 1
+ * (n <= plan->max_nct), each through lf_lt_matmul_bsgs's giant step: per member one lf_intt of S_1, then for the chunk ONE
+ * lf_ks_moddown_ws, ONE lf_ks_digits_batch, ONE extension + forward NTT and ONE launch of ks_inner_giantb_kernel<n> — with
+ * nt = 4 a chunk is the four tokens of one output, with nt = 2 a chunk of 4 is two outputs x two tokens: the giant key is read
+ * once for 4 members whatever k_out is.  (3) the nt k_out accumulators, token-major, in groups of up to 4 (a group may span two
+ * tokens): one lf_intt of the group's 2 g polynomials, one lf_ks_moddown_ws, one lf_rescale_batch.
+ * ws: lf_lt_matmul_bsgs_batch_ws_words(plan, nb_max, k_out, keyed_sums, nt) words, 16-byte aligned, lent by the caller:
+ *     nt (nb_max + 1 + k_out + keyed_sums) pairs [2][ell + K][N] + gw [ell][N] + 2 g4 [ell][N]
+ *         + max(lf_ks_moddown_ws_words(gw, ..), lf_ks_moddown_ws_words(2 g4, ..)),   g4 = min(nt k_out, 4), gw = min(4, plan->max_nct)
+ * — it does not grow with k_in; for nt = 1 it is lf_lt_matmul_bsgs_ws_words(plan, nb_max, k_out, keyed_sums); 0 for what the
+ * entry refuses.
+ * LF_ERR_ARG before any launch for everything lf_lt_matmul_bsgs refuses, nt not in {1, 2, 4} or above plan->max_nct, a NULL among
+ * the entries of in (used inputs) / out0 / out1 of any token, ws NULL, misaligned or too small. */
+#define LF_LT_MATMUL_BSGS_BATCH_MAX_TOKENS 4
+int64_t lf_lt_matmul_bsgs_batch_ws_words(const lf_ks_plan *plan, int nb_max, int k_out, int keyed_sums, int nt);
+int lf_lt_matmul_bsgs_batch(const lf_ks_plan *plan, int nt, int k_in, int k_out, const int64_t *const *in, /* [token][input][component] */
+                            const int64_t *ncol, const int64_t *bp_host, const int64_t *const *bksk, int ng, const int64_t *gp_host,
+                            const int64_t *const *gksk, int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format,
+                            const int64_t *const *pt, const int64_t *pt_stride, const int64_t *gcount, const int64_t *bidx,
+                            const int64_t *rescale_scales, int64_t round_at, int64_t *ws, int64_t ws_words,
+                            int64_t *const *out0, int64_t *const *out1 /* [token][output] */, void *stream);
+
 /* Sum of ciphertext products under ONE relinearisation ("lazy relinearisation"): out decrypts to sum_i a_i * b_i, level l -> l + 1.
  * np >= 1 pairs; in / row0: HOST arrays of 4 np device pointers, four per pair in the order of lf_cc_mult_evk (first surviving
  * row resp. dropped row of a_i.c0, a_i.c1, b_i.c0, b_i.c1; the same polynomial may appear any number of times); the plan

@@ -139,6 +139,9 @@ _SIGNATURES["lf_lt_matmul_batch_ws_words"] = [_PL, _I, _I, _I]
 _SIGNATURES["lf_lt_matmul_batch"] = [_PL, _I, _I, _I, _P, _P, _P, _P, _L, _L, _L, _I, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _P]
 _SIGNATURES["lf_lt_matmul_bsgs_ws_words"] = [_PL, _I, _I, _I]
 _SIGNATURES["lf_lt_matmul_bsgs"] = [_PL, _I, _I, _P, _P, _P, _P, _I, _P, _P, _L, _L, _L, _I, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _P]
+_SIGNATURES["lf_lt_matmul_bsgs_batch_ws_words"] = [_PL, _I, _I, _I, _I]
+_SIGNATURES["lf_lt_matmul_bsgs_batch"] = [_PL, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _L, _L, _L, _I, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P,
+                                          _P]
 
 # the 30-bit / int32 word mode of the ntt_cuda surface (csrc/ckks_w30.hip)
 _SIGNATURES.update({
@@ -192,6 +195,7 @@ LF_LT_MATMUL_MAX_OUTPUTS = 64  # .. and outputs per call
 LF_LT_MATMUL_BATCH_MAX_TOKENS = 4   # include/ckks_hip.h: token vectors per lf_lt_matmul_batch call
 LF_LT_MATMUL_BSGS_MAX_GIANTS = 64   # include/ckks_hip.h: giant steps per lf_lt_matmul_bsgs call
 LF_LT_MATMUL_BSGS_MAX_SUMS = 256    # .. and keyed inner sums (pairs of an output and a keyed giant step)
+LF_LT_MATMUL_BSGS_BATCH_MAX_TOKENS = 4   # include/ckks_hip.h: token vectors per lf_lt_matmul_bsgs_batch call
 LF_LT_BATCH_MAX_CTS = 64            # include/ckks_hip.h: ciphertexts per lf_linear_transform_batch call
 LF_CC_MATMUL_MAX_INNER = 64         # include/ckks_hip.h: inner dimension of an lf_cc_matmul call
 LF_CC_MATMUL_MAX_OPERANDS = 256     # .. and distinct operands per call

@@ -1088,6 +1088,46 @@ static int column_pairs(const lf_ks_plan *p, const int64_t *const *c, const int6
     return lf_ks_baby_sums(p_host, p->nparts, rows, ell, logN, key, u, p->ext, u + 2 * half, plan_mod(p), (hipStream_t)stream);
 }
 
+// steps 1 and 2 of lf_lt_matmul_batch for one input of nt (2 or 4) tokens, c[t * c_tstride + comp] token t's polynomials, u + t *
+// u_tstride its pairs:
+// 1. slot 0 of every token = P NTT(c0), P NTT(c1) on the ordinary rows: canonical copies and ONE forward NTT of the 2 nt polynomials
+//    in `tmp` (2 nt [ell][N]), times P R, then into the slots
+// 2. the digits of the nt c1 (canonical, no permutation), ONE extension + forward NTT of all of them, per key of the column ONE
+//    launch into slot 1 + j of every token: the key crosses HBM once for the group
+static int column_pairs_batch(const lf_ks_plan *p, int nt, const int64_t *const *c, int64_t c_tstride, const int64_t *p_host,
+                              const LfKeys &key, int64_t *u, int64_t u_tstride, int64_t *tmp, void *stream) {
+    const int ell = p->ell, rows = p->ell + p->K, logN = p->logN, dev = p->device;
+    const int64_t N = (int64_t)1 << logN, poly = (int64_t)ell * N, half = (int64_t)rows * N, pair = 2 * half;
+    hipStream_t st = (hipStream_t)stream;
+    {
+        const int64_t *srcs[2 * LF_LT_MATMUL_BATCH_MAX_TOKENS];
+        for (int t = 0; t < nt; ++t)
+            for (int k = 0; k < 2; ++k) srcs[2 * t + k] = c[t * c_tstride + k];
+        if (int e = p_ntt(p, srcs, 2 * nt, tmp, poly, stream)) return e;
+        for (int k = 0; k < 2 * nt; ++k)
+            if (hipError_t e = hipMemcpyAsync(u + (k / 2) * u_tstride + (k & 1) * half, tmp + k * poly, (size_t)poly * 8,
+                                              hipMemcpyDeviceToDevice, st))
+                return (int)e;
+    }
+    if (!key.n) return 0;
+    const int64_t *srcs[LF_LT_MATMUL_BATCH_MAX_TOKENS], *chat0[LF_LT_MATMUL_BATCH_MAX_TOKENS];
+    int64_t *states[LF_LT_MATMUL_BATCH_MAX_TOKENS], *us[LF_LT_MATMUL_BATCH_MAX_TOKENS];
+    for (int t = 0; t < nt; ++t) srcs[t] = c[t * c_tstride + 1], states[t] = p->state + t * poly, chat0[t] = u + t * u_tstride;
+    if (int e = lf_ks_digits_batch(srcs, states, nt, p->dig_nparts, p->dig_desc, p->dig_tab, N, 1, p->_2q, p->ql, p->qh, p->kl, p->kh, dev,
+                                   stream))
+        return e;
+    if (int e = lf_ks_fwd_batch(p->state, poly, nt, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, p->ext, plan_fwd(p), plan_mod(p), st))
+        return e;
+    for (int j = 0; j < key.n; ++j) {
+        for (int t = 0; t < nt; ++t) us[t] = u + t * u_tstride + (j + 1) * pair;
+        if (int e = lf_ks_baby_sums_batch(nt, p_host[j], p->nparts, rows, ell, logN,
+                                          {key.ksk + j, 1, key.part_stride, key.comp_stride, key.row_off, key.key_format}, p->ext, chat0, us,
+                                          plan_mod(p), st))
+            return e;
+    }
+    return 0;
+}
+
 int lf_lt_matmul(const lf_ks_plan *p, int k_in, int k_out, const int64_t *const *in, const int64_t *ncol, const int64_t *p_host,
                  const int64_t *const *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format,
                  const int64_t *const *pt, const int64_t *pt_stride, const int64_t *bcount, const int64_t *bidx,
@@ -1195,36 +1235,11 @@ int lf_lt_matmul_batch(const lf_ks_plan *p, int nt, int k_in, int k_out, const i
     for (int i = 0; i < k_in; ++i) {
         if (!used[i]) continue;
         const int nb = (int)ncol[i];
-        // 1. slot 0 of every member = P NTT(c0), P NTT(c1) on the ordinary rows: canonical copies and ONE forward NTT of the 2 nt
-        //    polynomials in `md` (free until the tail; nt <= gmax), times P R, then into the slots
-        {
-            const int64_t *srcs[2 * LF_LT_MATMUL_BATCH_MAX_TOKENS];
-            for (int t = 0; t < nt; ++t)
-                for (int c = 0; c < 2; ++c) srcs[2 * t + c] = in[2 * ((int64_t)t * k_in + i) + c];
-            if (int e = p_ntt(p, srcs, 2 * nt, md, poly, stream)) return e;
-            for (int k = 0; k < 2 * nt; ++k)
-                if (hipError_t e = hipMemcpyAsync(U(k / 2) + (k & 1) * half, md + k * poly, (size_t)poly * 8, hipMemcpyDeviceToDevice, st))
-                    return (int)e;
-        }
-        // 2. the digits of the nt c1 (canonical, no permutation), ONE extension + forward NTT of all of them, per key of the column
-        //    ONE launch into slot 1 + j of every member: the key crosses HBM once for the group
-        if (nb) {
-            const int64_t *srcs[LF_LT_MATMUL_BATCH_MAX_TOKENS], *chat0[LF_LT_MATMUL_BATCH_MAX_TOKENS];
-            int64_t *states[LF_LT_MATMUL_BATCH_MAX_TOKENS], *us[LF_LT_MATMUL_BATCH_MAX_TOKENS];
-            for (int t = 0; t < nt; ++t) srcs[t] = in[2 * ((int64_t)t * k_in + i) + 1], states[t] = p->state + t * poly, chat0[t] = U(t);
-            if (int e = lf_ks_digits_batch(srcs, states, nt, p->dig_nparts, p->dig_desc, p->dig_tab, N, 1, p->_2q, p->ql, p->qh, p->kl, p->kh, dev,
-                                           stream))
-                return e;
-            if (int e = lf_ks_fwd_batch(p->state, poly, nt, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, p->ext, plan_fwd(p), plan_mod(p), st))
-                return e;
-            for (int j = 0; j < nb; ++j) {
-                for (int t = 0; t < nt; ++t) us[t] = U(t) + (j + 1) * pair;
-                if (int e = lf_ks_baby_sums_batch(nt, p_host[koff[i] + j], p->nparts, rows, ell, logN,
-                                                  {ksk + koff[i] + j, 1, part_stride, comp_stride, row_off, key_format}, p->ext, chat0, us,
-                                                  plan_mod(p), st))
-                    return e;
-            }
-        }
+        // 1., 2. slot 0 of every member and the column's baby sums into the slots 1 .. nb (`md` is free until the tail; nt <= gmax)
+        if (int e = column_pairs_batch(p, nt, in + 2 * i, 2 * k_in, nb ? p_host + koff[i] : nullptr,
+                                       {nb ? ksk + koff[i] : nullptr, nb, part_stride, comp_stride, row_off, key_format}, U(0), member, md,
+                                       stream))
+            return e;
         // 3. the outputs that have a block in this column, 4, 2 or 1 per launch over the pairs of a tile of tokens
         std::vector<int> os;
         for (int o = 0; o < k_out; ++o)
@@ -1303,43 +1318,57 @@ int64_t lf_lt_matmul_bsgs_ws_words(const lf_ks_plan *p, int nb_max, int k_out, i
     return pair * (nb_max + 1 + k_out + keyed_sums) + gw * poly + 2 * g4 * poly + (md_w > md_t ? md_w : md_t);
 }
 
-int lf_lt_matmul_bsgs(const lf_ks_plan *p, int k_in, int k_out, const int64_t *const *in, const int64_t *ncol, const int64_t *bp_host,
-                      const int64_t *const *bksk, int ng, const int64_t *gp_host, const int64_t *const *gksk, int64_t part_stride,
-                      int64_t comp_stride, int64_t row_off, int key_format, const int64_t *const *pt, const int64_t *pt_stride,
-                      const int64_t *gcount, const int64_t *bidx, const int64_t *rescale_scales, int64_t round_at, int64_t *ws,
-                      int64_t ws_words, int64_t *const *out0, int64_t *const *out1, void *stream) {
+// what lf_lt_matmul_bsgs(_batch) learns of its arguments while it checks them: the first key of every column, the inputs some
+// output uses, the blocks' slot masks, the pairs (o, j) that have a diagonal, the index of every keyed inner sum (giant step after
+// giant step), the longest used column and the number of keyed sums
+struct BsgsShape {
+    std::vector<int64_t> koff;
+    std::vector<char> used, has;
+    std::vector<unsigned long long> masks;
+    std::vector<int> sidx;
+    int nb_max = 0, keyed_sums = 0;
+};
+
+// the checks of lf_lt_matmul_bsgs on everything but the workspace, for nt tokens (in: [token][input][component], those of a used
+// input are checked for every token; out0 / out1: [token][output])
+static int lt_matmul_bsgs_args(const lf_ks_plan *p, int nt, int k_in, int k_out, const int64_t *const *in, const int64_t *ncol,
+                               const int64_t *bp_host, const int64_t *const *bksk, int ng, const int64_t *gp_host,
+                               const int64_t *const *gksk, int64_t part_stride, int64_t comp_stride, int key_format,
+                               const int64_t *const *pt, const int64_t *pt_stride, const int64_t *gcount, const int64_t *bidx,
+                               const int64_t *rescale_scales, int64_t *const *out0, int64_t *const *out1, BsgsShape &sh) {
     if (!plan_ok(p) || !p->PR || p->ell < 2 || k_in < 1 || k_in > LF_LT_MATMUL_MAX_INPUTS || k_out < 1 || k_out > LF_LT_MATMUL_MAX_OUTPUTS ||
         ng < 1 || ng > LF_LT_MATMUL_BSGS_MAX_GIANTS || !in || !ncol || !gp_host || !gksk || !pt || !pt_stride || !gcount || !bidx ||
         !rescale_scales || !out0 || !out1 || (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES))
         return LF_ERR_ARG;
-    const int ell = p->ell, rows = p->ell + p->K, logN = p->logN, dev = p->device;
-    const int64_t N = (int64_t)1 << logN, poly = (int64_t)ell * N, pair = 2 * (int64_t)rows * N;
+    const int rows = p->ell + p->K, logN = p->logN;
+    const int64_t N = (int64_t)1 << logN;
     auto block = [&](int o, int i, int j) { return ((int64_t)o * k_in + i) * ng + j; };
     for (int j = 0; j < ng; ++j)   // (giant step 0: first, so at most once)
         if (gp_host[j] == 0 ? j != 0 : !keyed_steps_ok(gksk + j, gp_host + j, 1, part_stride, comp_stride, key_format, logN)) return LF_ERR_ARG;
     // the columns: keyed baby steps per input, the inputs some output uses, their keys
-    std::vector<int64_t> koff(k_in + 1, 0);
-    std::vector<char> used(k_in, 0);
-    int nb_max = 0;
+    sh.koff.assign(k_in + 1, 0);
+    sh.used.assign(k_in, 0);
+    sh.nb_max = 0;
     for (int i = 0; i < k_in; ++i) {
         if (ncol[i] < 0 || ncol[i] > LF_BSGS_MAX_BABY_KEYS) return LF_ERR_ARG;
-        koff[i + 1] = koff[i] + ncol[i];
-        for (int o = 0; o < k_out && !used[i]; ++o)
-            for (int j = 0; j < ng && !used[i]; ++j) used[i] = pt[block(o, i, j)] != nullptr;
-        if (!used[i]) continue;
-        if (!in[2 * i] || !in[2 * i + 1]) return LF_ERR_ARG;
+        sh.koff[i + 1] = sh.koff[i] + ncol[i];
+        for (int o = 0; o < k_out && !sh.used[i]; ++o)
+            for (int j = 0; j < ng && !sh.used[i]; ++j) sh.used[i] = pt[block(o, i, j)] != nullptr;
+        if (!sh.used[i]) continue;
+        for (int t = 0; t < nt; ++t)
+            if (!in[2 * ((int64_t)t * k_in + i)] || !in[2 * ((int64_t)t * k_in + i) + 1]) return LF_ERR_ARG;
         if (ncol[i] && (!bp_host || !bksk)) return LF_ERR_ARG;
-        if (ncol[i] && !keyed_steps_ok(bksk + koff[i], bp_host + koff[i], (int)ncol[i], part_stride, comp_stride, key_format, logN))
+        if (ncol[i] && !keyed_steps_ok(bksk + sh.koff[i], bp_host + sh.koff[i], (int)ncol[i], part_stride, comp_stride, key_format, logN))
             return LF_ERR_ARG;
-        if (ncol[i] > nb_max) nb_max = (int)ncol[i];
+        if (ncol[i] > sh.nb_max) sh.nb_max = (int)ncol[i];
     }
-    // the diagonals: per (output, input, giant step) its slots inside the column's set, ascending; per (output, giant step) the
-    // target of its inner sum: the accumulator A^o itself for giant step 0, else the next pair of S (giant step after giant step)
-    std::vector<unsigned long long> masks((size_t)k_out * k_in * ng, 0);
-    std::vector<char> has((size_t)k_out * ng, 0);
+    // the diagonals: per (output, input, giant step) its slots inside the column's set, ascending
+    sh.masks.assign((size_t)k_out * k_in * ng, 0);
+    sh.has.assign((size_t)k_out * ng, 0);
     int64_t first = 0;
     for (int o = 0; o < k_out; ++o) {
-        if (!out0[o] || !out1[o]) return LF_ERR_ARG;
+        for (int t = 0; t < nt; ++t)
+            if (!out0[(int64_t)t * k_out + o] || !out1[(int64_t)t * k_out + o]) return LF_ERR_ARG;
         bool any = false;
         for (int i = 0; i < k_in; ++i)
             for (int j = 0; j < ng; ++j) {
@@ -1348,27 +1377,47 @@ int lf_lt_matmul_bsgs(const lf_ks_plan *p, int k_in, int k_out, const int64_t *c
                     if (gcount[b] != 0) return LF_ERR_ARG;
                     continue;
                 }
-                any = true, has[(size_t)o * ng + j] = 1;
+                any = true, sh.has[(size_t)o * ng + j] = 1;
                 if (gcount[b] < 1 || gcount[b] > ncol[i] + 1 || pt_stride[b] < (int64_t)rows * N) return LF_ERR_ARG;
                 for (int64_t k = 0; k < gcount[b]; ++k) {
                     const int64_t slot = bidx[first + k];
                     if (slot < 0 || slot > ncol[i] || (k && slot <= bidx[first + k - 1])) return LF_ERR_ARG;
-                    masks[b] |= 1ull << slot;
+                    sh.masks[b] |= 1ull << slot;
                 }
                 first += gcount[b];
             }
         if (!any) return LF_ERR_ARG;
     }
-    std::vector<int> sidx((size_t)k_out * ng, -1);
-    int keyed_sums = 0;
+    sh.sidx.assign((size_t)k_out * ng, -1);
+    sh.keyed_sums = 0;
     for (int j = 0; j < ng; ++j) {
         if (gp_host[j] == 0) continue;
         bool any = false;
         for (int o = 0; o < k_out; ++o)
-            if (has[(size_t)o * ng + j]) sidx[(size_t)o * ng + j] = keyed_sums++, any = true;
+            if (sh.has[(size_t)o * ng + j]) sh.sidx[(size_t)o * ng + j] = sh.keyed_sums++, any = true;
         if (!any) return LF_ERR_ARG;   // a keyed giant step no output uses
     }
-    if (keyed_sums > LF_LT_MATMUL_BSGS_MAX_SUMS) return LF_ERR_ARG;
+    return sh.keyed_sums > LF_LT_MATMUL_BSGS_MAX_SUMS ? LF_ERR_ARG : 0;
+}
+
+int lf_lt_matmul_bsgs(const lf_ks_plan *p, int k_in, int k_out, const int64_t *const *in, const int64_t *ncol, const int64_t *bp_host,
+                      const int64_t *const *bksk, int ng, const int64_t *gp_host, const int64_t *const *gksk, int64_t part_stride,
+                      int64_t comp_stride, int64_t row_off, int key_format, const int64_t *const *pt, const int64_t *pt_stride,
+                      const int64_t *gcount, const int64_t *bidx, const int64_t *rescale_scales, int64_t round_at, int64_t *ws,
+                      int64_t ws_words, int64_t *const *out0, int64_t *const *out1, void *stream) {
+    BsgsShape sh;
+    if (int e = lt_matmul_bsgs_args(p, 1, k_in, k_out, in, ncol, bp_host, bksk, ng, gp_host, gksk, part_stride, comp_stride, key_format, pt,
+                                    pt_stride, gcount, bidx, rescale_scales, out0, out1, sh))
+        return e;
+    const int ell = p->ell, rows = p->ell + p->K, logN = p->logN, dev = p->device;
+    const int64_t N = (int64_t)1 << logN, poly = (int64_t)ell * N, pair = 2 * (int64_t)rows * N;
+    auto block = [&](int o, int i, int j) { return ((int64_t)o * k_in + i) * ng + j; };
+    // per (output, giant step) the target of its inner sum: the accumulator A^o itself for giant step 0, else its pair of S
+    const std::vector<int64_t> &koff = sh.koff;
+    const std::vector<char> &used = sh.used, &has = sh.has;
+    const std::vector<unsigned long long> &masks = sh.masks;
+    const std::vector<int> &sidx = sh.sidx;
+    const int nb_max = sh.nb_max, keyed_sums = sh.keyed_sums;
     const int64_t need = lf_lt_matmul_bsgs_ws_words(p, nb_max, k_out, keyed_sums);
     if (!need || !ws || ws_words < need || ((uintptr_t)ws & 15)) return LF_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
@@ -1434,6 +1483,123 @@ int lf_lt_matmul_bsgs(const lf_ks_plan *p, int k_in, int k_out, const int64_t *c
     // 3. the tail (step 4 of lf_lt_matmul): per group of outputs one exact inverse NTT of its 2 g accumulator polynomials, one
     // mod-down, one rescale
     return matmul_tail(p, A, k_out, md, mdws, mdws_words, out0, out1, rescale_scales, round_at, stream);
+}
+
+/* ---- lf_lt_matmul_bsgs over nt token vectors under one matrix and one key set (include/ckks_hip.h): a group of nt = 2 or 4 tokens
+ * shares every launch of the baby sums (each baby key read once for the group), the block products read each diagonal word once
+ * per pair of tokens, and the tokens of one output fill the giant step's group, so a giant key is read once for up to 4 members
+ * whatever k_out is.  nt = 1 is lf_lt_matmul_bsgs. ---- */
+int64_t lf_lt_matmul_bsgs_batch_ws_words(const lf_ks_plan *p, int nb_max, int k_out, int keyed_sums, int nt) {
+    if (!batch_ok(p, nt) || nt > LF_LT_MATMUL_BSGS_BATCH_MAX_TOKENS || nb_max < 0 || nb_max > LF_BSGS_MAX_BABY_KEYS || k_out < 1 ||
+        k_out > LF_LT_MATMUL_MAX_OUTPUTS || keyed_sums < 0 || keyed_sums > LF_LT_MATMUL_BSGS_MAX_SUMS)
+        return 0;
+    const int64_t N = (int64_t)1 << p->logN, pair = 2 * (int64_t)(p->ell + p->K) * N, poly = (int64_t)p->ell * N;
+    const int g4 = nt * k_out < LF_LT_MATMUL_GROUP ? nt * k_out : LF_LT_MATMUL_GROUP, gw = bsgs_giant_group(p);
+    const int64_t md_w = lf_ks_moddown_ws_words(gw, p->ell, p->K, N), md_t = lf_ks_moddown_ws_words(2 * g4, p->ell, p->K, N);
+    // per token one input's pairs, the k_out accumulators and the keyed inner sums; w of one giant group, the mod-down's results of
+    // one group of accumulators, and the workspace of either mod-down
+    return pair * nt * (nb_max + 1 + k_out + keyed_sums) + gw * poly + 2 * g4 * poly + (md_w > md_t ? md_w : md_t);
+}
+
+int lf_lt_matmul_bsgs_batch(const lf_ks_plan *p, int nt, int k_in, int k_out, const int64_t *const *in, const int64_t *ncol,
+                            const int64_t *bp_host, const int64_t *const *bksk, int ng, const int64_t *gp_host,
+                            const int64_t *const *gksk, int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format,
+                            const int64_t *const *pt, const int64_t *pt_stride, const int64_t *gcount, const int64_t *bidx,
+                            const int64_t *rescale_scales, int64_t round_at, int64_t *ws, int64_t ws_words, int64_t *const *out0,
+                            int64_t *const *out1, void *stream) {
+    if (!batch_ok(p, nt) || nt > LF_LT_MATMUL_BSGS_BATCH_MAX_TOKENS) return LF_ERR_ARG;
+    if (nt == 1)
+        return lf_lt_matmul_bsgs(p, k_in, k_out, in, ncol, bp_host, bksk, ng, gp_host, gksk, part_stride, comp_stride, row_off, key_format, pt,
+                                 pt_stride, gcount, bidx, rescale_scales, round_at, ws, ws_words, out0, out1, stream);
+    BsgsShape sh;
+    if (int e = lt_matmul_bsgs_args(p, nt, k_in, k_out, in, ncol, bp_host, bksk, ng, gp_host, gksk, part_stride, comp_stride, key_format, pt,
+                                    pt_stride, gcount, bidx, rescale_scales, out0, out1, sh))
+        return e;
+    const int ell = p->ell, rows = p->ell + p->K, logN = p->logN;
+    const int64_t N = (int64_t)1 << logN, poly = (int64_t)ell * N, half = (int64_t)rows * N, pair = 2 * half;
+    const int nb_max = sh.nb_max, keyed_sums = sh.keyed_sums;
+    const int64_t need = lf_lt_matmul_bsgs_batch_ws_words(p, nb_max, k_out, keyed_sums, nt);
+    if (!need || !ws || ws_words < need || ((uintptr_t)ws & 15)) return LF_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    // token t: its input's pairs U(t) [nb_max + 1]; then the accumulators A [nt][k_out] (one run: a group of the tail may span two
+    // tokens) and the keyed inner sums S [nt][keyed_sums]; w of one giant group, the mod-down's results of one group and the
+    // workspace of either mod-down.  A and S have different token strides, and a launch of the block products takes one: the
+    // targets of giant step 0 and the keyed ones go in launches of their own
+    const int na = nt * k_out, g4 = na < LF_LT_MATMUL_GROUP ? na : LF_LT_MATMUL_GROUP, gw = bsgs_giant_group(p);
+    const int64_t member = (nb_max + 1) * pair;
+    int64_t *A = ws + nt * member, *S = A + na * pair, *w = S + (int64_t)nt * keyed_sums * pair, *md = w + gw * poly, *mdws = md + 2 * g4 * poly;
+    const int64_t md_w = lf_ks_moddown_ws_words(gw, ell, p->K, N), md_t = lf_ks_moddown_ws_words(2 * g4, ell, p->K, N);
+    const int64_t mdws_words = md_w > md_t ? md_w : md_t;
+    auto block = [&](int o, int i, int j) { return ((int64_t)o * k_in + i) * ng + j; };
+    auto U = [&](int t) { return ws + t * member; };
+    auto acc = [&](int t, int o) { return A + ((int64_t)t * k_out + o) * pair; };
+    auto sum = [&](int t, int o, int j) { return S + ((int64_t)t * keyed_sums + sh.sidx[(size_t)o * ng + j]) * pair; };
+    if (int e = lf_set_device(p->device)) return e;
+    // slot 0 holds nothing on the special rows, for every input and token; an output without giant step 0 starts from zero accumulators
+    for (int t = 0; t < nt; ++t)
+        for (int c = 0; c < 2; ++c)
+            if (hipError_t e = hipMemsetAsync(U(t) + c * half + poly, 0, (size_t)p->K * N * 8, st)) return (int)e;
+    for (int o = 0; o < k_out; ++o)
+        if (!(gp_host[0] == 0 && sh.has[(size_t)o * ng]))
+            for (int t = 0; t < nt; ++t)
+                if (hipError_t e = hipMemsetAsync(acc(t, o), 0, (size_t)pair * 8, st)) return (int)e;
+    // 1. input-major: steps 1 - 2 of lf_lt_matmul_batch, then lf_lt_matmul_bsgs's products over the pairs of a tile of tokens
+    std::vector<char> written((size_t)k_out * ng, 0);
+    for (int i = 0; i < k_in; ++i) {
+        if (!sh.used[i]) continue;
+        const int nb = (int)ncol[i];
+        if (int e = column_pairs_batch(p, nt, in + 2 * i, 2 * k_in, nb ? bp_host + sh.koff[i] : nullptr,
+                                       {nb ? bksk + sh.koff[i] : nullptr, nb, part_stride, comp_stride, row_off, key_format}, U(0), member, md,
+                                       stream))
+            return e;
+        // the targets o * ng + j with a diagonal in this column: those of giant step 0 (the accumulators), then the keyed ones
+        for (int keyed = 0; keyed < 2; ++keyed) {
+            std::vector<int> ts;
+            for (int o = 0; o < k_out; ++o)
+                for (int j = 0; j < ng; ++j)
+                    if (pt[block(o, i, j)] && (gp_host[j] != 0) == (keyed != 0)) ts.push_back(o * ng + j);
+            for (size_t a0 = 0; a0 < ts.size();) {
+                const size_t left = ts.size() - a0;
+                const int g = left >= 4 ? 4 : left >= 2 ? 2 : 1;
+                const int64_t *pts[4];
+                int64_t *outs[4], strides[4];
+                unsigned long long slots[4];
+                int fresh[4];
+                for (int k = 0; k < g; ++k) {
+                    const int o = ts[a0 + k] / ng, j = ts[a0 + k] % ng;
+                    const int64_t b = block(o, i, j);
+                    pts[k] = pt[b], strides[k] = pt_stride[b], slots[k] = sh.masks[b], fresh[k] = !written[ts[a0 + k]];
+                    outs[k] = keyed ? sum(0, o, j) : acc(0, o);
+                    written[ts[a0 + k]] = 1;
+                }
+                if (int e = lf_lt_block_productsb(nt, g, U(0), member, nb + 1, pts, slots, strides, outs, (keyed ? keyed_sums : k_out) * pair,
+                                                  fresh, rows, logN, plan_mod(p), st))
+                    return e;
+                a0 += g;
+            }
+        }
+    }
+    // 2. giant-step-major: the members (t, o) that have the giant step, output-major with the tokens of an output adjacent, 4, 2 or 1
+    //    per key stream
+    for (int j = 0; j < ng; ++j) {
+        if (gp_host[j] == 0) continue;
+        std::vector<int> ms;   // o * nt + t
+        for (int o = 0; o < k_out; ++o)
+            if (sh.has[(size_t)o * ng + j])
+                for (int t = 0; t < nt; ++t) ms.push_back(o * nt + t);
+        for (size_t a0 = 0; a0 < ms.size();) {
+            const size_t left = ms.size() - a0;
+            const int n = (left >= 4 && gw >= 4) ? 4 : (left >= 2 && gw >= 2) ? 2 : 1;
+            int64_t *Ss[4], *accs[4];
+            for (int k = 0; k < n; ++k) Ss[k] = sum(ms[a0 + k] % nt, ms[a0 + k] / nt, j), accs[k] = acc(ms[a0 + k] % nt, ms[a0 + k] / nt);
+            if (int e = bsgs_giant_step(p, n, Ss, accs, gp_host[j], {gksk + j, 1, part_stride, comp_stride, row_off, key_format}, w, mdws,
+                                        mdws_words, stream))
+                return e;
+            a0 += n;
+        }
+    }
+    // 3. the tail: the nt k_out accumulators, token-major, in groups of up to 4 (a group may span two tokens)
+    return matmul_tail(p, A, na, md, mdws, mdws_words, out0, out1, rescale_scales, round_at, stream);
 }
 
 /* ---- baby-step / giant-step linear transform of many ciphertexts under the same diagonals and keys (include/ckks_hip.h): groups

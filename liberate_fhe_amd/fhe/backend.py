@@ -12,7 +12,7 @@ import ctypes
 import torch
 
 from .._native import lib, check, KsPlan, LF_KEY_PLANES, LF_LT_MATMUL_BSGS_MAX_GIANTS, LF_LT_MATMUL_BSGS_MAX_SUMS, LF_LT_BATCH_MAX_CTS, \
-    LF_LT_MATMUL_BATCH_MAX_TOKENS
+    LF_LT_MATMUL_BATCH_MAX_TOKENS, LF_LT_MATMUL_BSGS_BATCH_MAX_TOKENS
 from ..ntt import ntt_cuda, twiddles
 
 
@@ -813,10 +813,26 @@ class HipBackend:
         ascending; outs: k_out tensors [2, ell - 1, N]; ws: at least lt_matmul_bsgs_ws_words(..) words."""
         dev, st = _ds(outs[0])
         k_in, k_out, ng = len(ins), len(blocks), len(giant_keys)
+        kb, gb, ps, cs, fmt, pts, strides, counts, slots = self._lt_matmul_bsgs_marshal("lt_matmul_bsgs_native", col_keys, giant_keys,
+                                                                                        first_part, blocks, k_in)
+        i64 = lambda v: (ctypes.c_int64 * max(len(v), 1))(*v)
+        inp = (ctypes.c_void_p * (2 * k_in))()
+        for i, pair in enumerate(ins):
+            if pair is not None:
+                inp[2 * i], inp[2 * i + 1] = pair[0].data_ptr(), pair[1].data_ptr()
+        check(lib.lf_lt_matmul_bsgs(ctypes.byref(plan), k_in, k_out, inp, i64([len(c) for c in col_keys]),
+                                    i64([e for c in col_exps for e in c]), kb, ng, i64(giant_exps), gb, ps, cs, row_off,
+                                    fmt, pts, i64(strides), i64(counts), i64(slots), _p(scales), round_at, _p(ws),
+                                    ws.numel(), _parr([o[0] for o in outs]), _parr([o[1] for o in outs]), st), "lf_lt_matmul_bsgs")
+
+    def _lt_matmul_bsgs_marshal(self, name, col_keys, giant_keys, first_part, blocks, k_in):
+        """(baby key pointers, giant key pointers, part stride, component stride, key format, pack pointers, strides, counts,
+        slots): the keys and the blocks of lt_matmul_bsgs_native / lt_matmul_bsgs_batch_call as the C ABI takes them."""
+        k_out, ng = len(blocks), len(giant_keys)
         babies = [k for col in col_keys for k in col]
         fmt = {self._kfmt(k) for k in babies + [k for k in giant_keys if k is not None]}
         if len(fmt) > 1:
-            raise ValueError("lt_matmul_bsgs_native: the keys of one call must share one format")
+            raise ValueError(f"{name}: the keys of one call must share one format")
         ps = cs = 0
         kb, gb = (ctypes.c_void_p * max(len(babies), 1))(), (ctypes.c_void_p * max(ng, 1))()
         for j, key in enumerate(babies):
@@ -824,11 +840,6 @@ class HipBackend:
         for j, key in enumerate(giant_keys):
             if key is not None:
                 gb[j], ps, cs = self._key_args(key, first_part)
-        i64 = lambda v: (ctypes.c_int64 * max(len(v), 1))(*v)
-        inp = (ctypes.c_void_p * (2 * k_in))()
-        for i, pair in enumerate(ins):
-            if pair is not None:
-                inp[2 * i], inp[2 * i + 1] = pair[0].data_ptr(), pair[1].data_ptr()
         pts = (ctypes.c_void_p * (k_out * k_in * ng))()
         strides, counts, slots = [0] * (k_out * k_in * ng), [0] * (k_out * k_in * ng), []
         for o, row in enumerate(blocks):
@@ -844,10 +855,40 @@ class HipBackend:
                     pts[e] = pack.data_ptr() + first * pack.stride(0) * 8
                     strides[e], counts[e] = pack.stride(0), len(sl)
                     slots += list(sl)
-        check(lib.lf_lt_matmul_bsgs(ctypes.byref(plan), k_in, k_out, inp, i64([len(c) for c in col_keys]),
-                                    i64([e for c in col_exps for e in c]), kb, ng, i64(giant_exps), gb, ps, cs, row_off,
-                                    fmt.pop() if fmt else 0, pts, i64(strides), i64(counts), i64(slots), _p(scales), round_at, _p(ws),
-                                    ws.numel(), _parr([o[0] for o in outs]), _parr([o[1] for o in outs]), st), "lf_lt_matmul_bsgs")
+        return kb, gb, ps, cs, (fmt.pop() if fmt else 0), pts, strides, counts, slots
+
+    # include/ckks_hip.h: LF_LT_MATMUL_BSGS_BATCH_MAX_TOKENS through _native.py's copy (tests/test_lt_matmul_bsgs_batch_cpu.py holds
+    # both to the header); the group sizes lf_lt_matmul_bsgs_batch takes beside 1
+    lt_matmul_bsgs_batch_max_tokens = LF_LT_MATMUL_BSGS_BATCH_MAX_TOKENS
+    lt_matmul_bsgs_batch_sizes = (4, 2)
+
+    @staticmethod
+    def lt_matmul_bsgs_batch_ws_words(plan, nb_max, k_out, keyed_sums, nt):
+        return int(lib.lf_lt_matmul_bsgs_batch_ws_words(ctypes.byref(plan), nb_max, k_out, keyed_sums, nt))
+
+    def lt_matmul_bsgs_batch_call(self, plan, toks, col_exps, col_keys, giant_exps, giant_keys, first_part, row_off, blocks, scales,
+                                  round_at, outs, ws):
+        """lt_matmul_bsgs_native for a group of nt = 1, 2 or 4 token vectors under one matrix and one key set as ONE native call
+        (lf_lt_matmul_bsgs_batch; the plan sized for nt).  toks: per token what lt_matmul_bsgs_native takes as `ins` (an input no
+        block uses may be None); outs: per token k_out tensors [2, ell - 1, N]; ws: at least lt_matmul_bsgs_batch_ws_words(plan,
+        the longest used column, k_out, the keyed inner sums of one token, nt) words; everything else as lt_matmul_bsgs_native.
+        (The name: the engine's *_native entries are a closed list the fenced and the stream-contract suites go through one by one;
+        this entry has tests of its own for both.)"""
+        dev, st = _ds(outs[0][0])
+        nt, k_in, k_out, ng = len(toks), len(toks[0]), len(blocks), len(giant_keys)
+        kb, gb, ps, cs, fmt, pts, strides, counts, slots = self._lt_matmul_bsgs_marshal("lt_matmul_bsgs_batch_call", col_keys, giant_keys,
+                                                                                        first_part, blocks, k_in)
+        i64 = lambda v: (ctypes.c_int64 * max(len(v), 1))(*v)
+        inp = (ctypes.c_void_p * (nt * 2 * k_in))()
+        for t, ins in enumerate(toks):
+            for i, pair in enumerate(ins):
+                if pair is not None:
+                    inp[2 * (t * k_in + i)], inp[2 * (t * k_in + i) + 1] = pair[0].data_ptr(), pair[1].data_ptr()
+        check(lib.lf_lt_matmul_bsgs_batch(ctypes.byref(plan), nt, k_in, k_out, inp, i64([len(c) for c in col_keys]),
+                                          i64([e for c in col_exps for e in c]), kb, ng, i64(giant_exps), gb, ps, cs, row_off, fmt, pts,
+                                          i64(strides), i64(counts), i64(slots), _p(scales), round_at, _p(ws), ws.numel(),
+                                          _parr([o[0] for tok in outs for o in tok]), _parr([o[1] for tok in outs for o in tok]), st),
+              "lf_lt_matmul_bsgs_batch")
 
     def ks_gather(self, ext, dst, index, rows, logN, c: Consts):
         """dst[p][r][k] = ext[p][r][index[k]] for extended digits as ks_fwd leaves them: fp64-class rows of a mixed stack in the

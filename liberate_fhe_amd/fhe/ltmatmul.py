@@ -15,6 +15,10 @@ of 4 and 2 through one native call (lf_lt_matmul_batch) that reads every key onc
 lt_matmul_bsgs is the same matrix over baby-step / giant-step blocks (encode_diagonals(.., bsgs=n1)): the baby rotations are formed
 once per input, the inner sums of all inputs of one output are added in Q P before the giant key switch, and the outputs that share
 a giant step share the stream of its key (lf_lt_matmul_bsgs).
+
+lt_matmul_bsgs_batch is lt_matmul_bsgs over many token vectors under one matrix and one key set: the loop's words, the tokens in
+groups of 4 and 2 through one native call (lf_lt_matmul_bsgs_batch) that reads every baby key once per group, every diagonal once per
+pair, and every giant key once per 4 (token, output) members.
 """
 from __future__ import annotations
 
@@ -513,23 +517,23 @@ class LtMatmulOps:
         calls.append((o0, len(steps)))
         return calls
 
-    def _lt_matmul_bsgs_native(self, W, steps, n1, cts, by_step, level, d):
-        N, k_in = self.ctx.N, len(cts)
+    def _lt_matmul_bsgs_native_args(self, W, steps, n1, by_step, level, d):
+        """What a native call takes of the matrix and the keys alone: (per input whether some block uses it, col_exps, col_keys,
+        giant_exps, giant_keys, blocks, the longest column's keyed baby steps, the keyed inner sums, whether two outputs share a
+        keyed giant step, round_at), as HipBackend.lt_matmul_bsgs_native names them."""
+        N, k_in = self.ctx.N, len(W[0])
         giants = sorted({s - s % n1 for srow in steps for b in srow if b is not None for s in b})   # (0 sorts first)
         rows_of = {g: sum(any(b is not None and any(s - s % n1 == g for s in b) for b in srow) for srow in steps) for g in giants}
         shared = any(g and rows_of[g] >= 2 for g in giants)
-        if self.lt_matmul_bsgs_group not in (1, 2, 4):
-            raise ValueError("lt_matmul_bsgs_group: 1, 2 or 4")
-        plan, _, first_part, row_off = self._op_plan(level, d, self.lt_matmul_bsgs_group if shared else 1)
         i0 = self._loc(0, special=True).index(d)
         li = self.local_ids.index(d)
         owner = self.ntt.p.rescaler_loc[level]
         round_at = self.ctx.q[self.ntt.p.destination_arrays[level][owner][0]] // 2
-        ins, col_exps, col_keys, slot = [], [], [], []
+        used, col_exps, col_keys, slot = [], [], [], []
         for i in range(k_in):
             col = [s for s in steps if s[i] is not None]
             keyed = sorted({t % n1 for s in col for t in s[i] if t % n1})
-            ins.append((cts[i].data[0][0], cts[i].data[1][0]) if col else None)
+            used.append(bool(col))
             col_exps.append([encdec.galois_exponent(N, t) for t in keyed])
             col_keys.append([self._key_pack(by_step[t])[i0] for t in keyed])
             slot.append({0: 0, **{t: 1 + j for j, t in enumerate(keyed)}})
@@ -544,14 +548,111 @@ class LtMatmulOps:
 
         blocks = [[None if b is None else (self._diag_pack(b)[li], per_giant(i, s[i])) for i, b in enumerate(row)]
                   for row, s in zip(W, steps)]
-        nb_max = max(len(c) for c in col_keys)
-        keyed_sums = sum(rows_of[g] for g in giants if g)
+        return (used, col_exps, col_keys, [encdec.galois_exponent(N, g) if g else 0 for g in giants],
+                [self._key_pack(by_step[g])[i0] if g else None for g in giants], blocks, max(len(c) for c in col_keys),
+                sum(rows_of[g] for g in giants if g), shared, round_at)
+
+    def _lt_matmul_bsgs_native(self, W, steps, n1, cts, by_step, level, d):
+        N = self.ctx.N
+        used, col_exps, col_keys, giant_exps, giant_keys, blocks, nb_max, keyed_sums, shared, round_at = \
+            self._lt_matmul_bsgs_native_args(W, steps, n1, by_step, level, d)
+        if self.lt_matmul_bsgs_group not in (1, 2, 4):
+            raise ValueError("lt_matmul_bsgs_group: 1, 2 or 4")
+        plan, _, first_part, row_off = self._op_plan(level, d, self.lt_matmul_bsgs_group if shared else 1)
+        ins = [(ct.data[0][0], ct.data[1][0]) if u else None for ct, u in zip(cts, used)]
         ws = self._ws("lt_matmul_bsgs_ws", (self.backend.lt_matmul_bsgs_ws_words(plan, nb_max, len(W), keyed_sums),), d)
         outs = [torch.empty((2, plan.ell - 1, N), dtype=torch.int64, device=self.ntt.devices[d]) for _ in W]
-        self.backend.lt_matmul_bsgs_native(plan, ins, col_exps, col_keys, [encdec.galois_exponent(N, g) if g else 0 for g in giants],
-                                           [self._key_pack(by_step[g])[i0] if g else None for g in giants], first_part, row_off,
+        self.backend.lt_matmul_bsgs_native(plan, ins, col_exps, col_keys, giant_exps, giant_keys, first_part, row_off,
                                            blocks, self.rescale_scales[level][d], round_at, outs, ws)
         return [self._new(([o[0]], [o[1]]), types.origins["ct"], level=level + 1) for o in outs]
+
+    # group sizes of lt_matmul_bsgs_batch's native path, largest first (filtered by backend.lt_matmul_bsgs_batch_sizes), as
+    # lt_matmul_batch_sizes: a size that does not beat the loop of lt_matmul_bsgs is left out here and its tokens take lt_matmul_bsgs
+    # one by one — the words are the same (DESIGN.md §4.2 has the numbers; tools/lt_matmul_bsgs_batch.py --ab measures every size)
+    lt_matmul_bsgs_batch_sizes = (4, 2)
+
+    def lt_matmul_bsgs_batch(self, W, X, rotks, n1=None) -> list:
+        """lt_matmul_bsgs of many token vectors under the SAME matrix and keys (a layer of large blocks over the tokens of a
+        sequence): returns exactly [lt_matmul_bsgs(W, cts, rotks, n1) for cts in X], word for word and in order — B lists of k_out
+        ciphertexts at level + 1; an empty X gives [].  W, rotks, n1: as lt_matmul_bsgs takes them (lt_matmul_bsgs_steps(W, n1)
+        names the keys); X: B token vectors of k_in ciphertexts each (the same object may appear in any number of tokens and
+        positions; tokens may sit at different levels).  What lt_matmul_bsgs refuses for any token is refused for the whole call
+        before anything is encoded, allocated or launched, with the error the loop would have raised first.  A mapping block is
+        encoded once per level of the tokens with bsgs=n1, not once per token: encode draws its rounding at random, so a loop would
+        multiply every token by other words; here the tokens of a level share ONE encoding of each mapping object, and the words
+        are those of the loop over these encoded objects.
+        Where lt_matmul_bsgs's own native call applies (every limb of the level on one device of this process, ascending steps,
+        contiguous operands of the used inputs, no row beyond the caps of one call) and the backend has lf_lt_matmul_bsgs_batch,
+        the tokens of one level that qualify go, in order, in groups of lt_matmul_bsgs_batch_sizes through ONE native call per
+        group and per range of outputs (the caps count per token): a group shares every launch of the baby sums (each baby key
+        read once for the group), the block products read each diagonal once per pair of tokens, and the tokens of an output
+        fill the giant step's chunk of 4, so a giant key is read once per 4 members whatever k_out is.  A token that does not
+        qualify, the one the groups leave over, and every token on a backend without the entry or on a sharded or multi-device
+        engine take lt_matmul_bsgs and keep their place."""
+        self._enter()
+        X = [list(cts) for cts in X]
+        if not X:
+            return []
+        W, steps, n1 = self._lt_matmul_bsgs_blocks(W, n1)
+        if not isinstance(rotks, dict):
+            rotks = list(rotks)
+        flat = [s for srow in steps for b in srow if b is not None for s in b]
+        need = sorted({s % n1 for s in flat} | {s - s % n1 for s in flat})
+        levels = []
+        for t, cts in enumerate(X):                  # the loop's order: token 0's operands, the keys, then the other tokens' operands
+            X[t], by_step, level = self._lt_matmul_operands("lt_matmul_bsgs", W, cts, rotks)
+            levels.append(level)
+            if t == 0:
+                for s in need:
+                    if s and s not in by_step:
+                        raise errors.NotMatchType(origin=f"no key for step {s}", to=types.origins["rotk"] + str(s))
+        # (every refusal is behind us: from here on things are encoded, allocated and launched)
+        out = [None] * len(X)
+        sizes = [k for k in self.lt_matmul_bsgs_batch_sizes if k in getattr(self.backend, "lt_matmul_bsgs_batch_sizes", ())]
+        for level in sorted(set(levels)):
+            encoded, Wl = {}, [list(row) for row in W]
+            for row in Wl:
+                for i, b in enumerate(row):
+                    if b is not None and not is_struct(b):
+                        if id(b) not in encoded:
+                            encoded[id(b)] = self.encode_diagonals(b, level, bsgs=n1)
+                        row[i] = encoded[id(b)]
+            toks = [t for t, l in enumerate(levels) if l == level]
+            lsteps = [[None if b is None else self.diagonal_steps(b) for b in row] for row in Wl]
+            d = self._native_level(level)
+            ready, calls = [], None
+            if sizes and d is not None and hasattr(self.backend, "lt_matmul_bsgs_native") and \
+                    hasattr(self.backend, "lt_matmul_bsgs_batch_call") and all(s is None or s == sorted(s) for srow in lsteps for s in srow):
+                calls = self._lt_matmul_bsgs_calls(lsteps, n1)
+                if calls is not None:
+                    used = [i for i in range(len(W[0])) if any(s[i] is not None for s in lsteps)]
+                    ready = [t for t in toks if all(X[t][i].data[c][0].is_contiguous() for i in used for c in range(2))]
+            while ready:
+                g = next((k for k in sizes if k <= len(ready)), None)
+                if g is None:
+                    break
+                group, ready = ready[:g], ready[g:]
+                parts = [self._lt_matmul_bsgs_batch_native(Wl[o0:o1], lsteps[o0:o1], n1, [X[t] for t in group], by_step, level, d)
+                         for o0, o1 in calls]
+                for j, t in enumerate(group):
+                    out[t] = [o for part in parts for o in part[j]]
+            for t in toks:
+                if out[t] is None:
+                    out[t] = self.lt_matmul_bsgs(Wl, X[t], rotks, n1)
+        return out
+
+    def _lt_matmul_bsgs_batch_native(self, W, steps, n1, toks, by_step, level, d):
+        N = self.ctx.N
+        plan, _, first_part, row_off = self._op_plan(level, d, nct=4)
+        used, col_exps, col_keys, giant_exps, giant_keys, blocks, nb_max, keyed_sums, _, round_at = \
+            self._lt_matmul_bsgs_native_args(W, steps, n1, by_step, level, d)
+        ins = [[(ct.data[0][0], ct.data[1][0]) if u else None for ct, u in zip(cts, used)] for cts in toks]
+        ws = self._ws("lt_matmul_bsgs_batch_ws",
+                      (self.backend.lt_matmul_bsgs_batch_ws_words(plan, nb_max, len(W), keyed_sums, len(toks)),), d)
+        outs = [[torch.empty((2, plan.ell - 1, N), dtype=torch.int64, device=self.ntt.devices[d]) for _ in W] for _ in toks]
+        self.backend.lt_matmul_bsgs_batch_call(plan, ins, col_exps, col_keys, giant_exps, giant_keys, first_part, row_off, blocks,
+                                               self.rescale_scales[level][d], round_at, outs, ws)
+        return [[self._new(([o[0]], [o[1]]), types.origins["ct"], level=level + 1) for o in tok] for tok in outs]
 
     def _lt_matmul_bsgs_steps(self, W, steps, n1, cts, by_step, level):
         """The same words through the engine's steps — the pieces of _linear_transform_bsgs (_lt_forward, _lt_inner, the
@@ -584,7 +685,8 @@ class LtMatmulOps:
             if not B:
                 continue                                                  # an input no output uses
             keyed = [b for b in B if b]
-            digits = self._ks_digits_exchanged(ct.data[1], level, galois=(1, True)) if keyed else {}
+            c1 = [t if t.is_contiguous() else t.contiguous() for t in ct.data[1]]   # (the digit launch takes a raw pointer)
+            digits = self._ks_digits_exchanged(c1, level, galois=(1, True)) if keyed else {}
             for di, d in enumerate(loc):
                 li = self.local_ids.index(d)
                 rows, ell = self._rows(d, level, True), self._rows(d, level, False)

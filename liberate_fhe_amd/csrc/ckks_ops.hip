@@ -878,6 +878,58 @@ static bool keyed_steps_ok(const int64_t *const *ksk, const int64_t *p_host, int
     return lf_keys_ok({ksk, n, part_stride, comp_stride, 0, key_format}) && lf_exponents_ok(p_host, n, logN);
 }
 
+// steps 1 and 2 of the baby-step / giant-step ops and of the lf_lt_matmul family for one input of nt (1, 2 or 4) ciphertexts,
+// c[t * c_tstride + comp] ciphertext t's polynomials, u + t * u_tstride its pairs: slot 0 = P NTT(c0), P NTT(c1) on the ordinary
+// rows (the special rows of slot 0 are the caller's to zero), slot 1 + j the baby sum under the column's key j.
+// nt = 1: the forward NTT straight into slot 0; the digits of c1 extended and transformed once, ONE launch over all the keys.
+// nt > 1: canonical copies and ONE forward NTT of the 2 nt polynomials in `tmp` (2 nt [ell][N]), times P R, then into the slots;
+//         the digits of the nt c1 (canonical, no permutation), ONE extension + forward NTT of all of them, per key of the column
+//         ONE launch into slot 1 + j of every ciphertext: the key crosses HBM once for the group
+static int column_pairs(const lf_ks_plan *p, int nt, const int64_t *const *c, int64_t c_tstride, const int64_t *p_host, const LfKeys &key,
+                        int64_t *u, int64_t u_tstride, int64_t *tmp, void *stream) {
+    const int ell = p->ell, rows = p->ell + p->K, logN = p->logN, dev = p->device;
+    const int64_t N = (int64_t)1 << logN, poly = (int64_t)ell * N, half = (int64_t)rows * N, pair = 2 * half;
+    hipStream_t st = (hipStream_t)stream;
+    if (nt == 1) {
+        if (int e = p_ntt(p, c, 2, u, half, stream)) return e;
+        if (!key.n) return 0;
+        if (int e = lf_ks_digits_galois(c[1], p->state, p->dig_nparts, p->dig_desc, p->dig_tab, N, 1, p->_2q, p->ql, p->qh, p->kl, p->kh, dev,
+                                        stream))
+            return e;
+        if (int e = lf_ks_fwd(p->state, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, p->ext, p->psi, p->psi_dp, p->q_host, p->ql, p->qh,
+                              p->kl, p->kh, dev, stream))
+            return e;
+        return lf_ks_baby_sums(p_host, p->nparts, rows, ell, logN, key, u, p->ext, u + pair, plan_mod(p), st);
+    }
+    {
+        const int64_t *srcs[2 * LF_LT_MATMUL_BATCH_MAX_TOKENS];
+        for (int t = 0; t < nt; ++t)
+            for (int k = 0; k < 2; ++k) srcs[2 * t + k] = c[t * c_tstride + k];
+        if (int e = p_ntt(p, srcs, 2 * nt, tmp, poly, stream)) return e;
+        for (int k = 0; k < 2 * nt; ++k)
+            if (hipError_t e = hipMemcpyAsync(u + (k / 2) * u_tstride + (k & 1) * half, tmp + k * poly, (size_t)poly * 8,
+                                              hipMemcpyDeviceToDevice, st))
+                return (int)e;
+    }
+    if (!key.n) return 0;
+    const int64_t *srcs[LF_LT_MATMUL_BATCH_MAX_TOKENS], *chat0[LF_LT_MATMUL_BATCH_MAX_TOKENS];
+    int64_t *states[LF_LT_MATMUL_BATCH_MAX_TOKENS], *us[LF_LT_MATMUL_BATCH_MAX_TOKENS];
+    for (int t = 0; t < nt; ++t) srcs[t] = c[t * c_tstride + 1], states[t] = p->state + t * poly, chat0[t] = u + t * u_tstride;
+    if (int e = lf_ks_digits_batch(srcs, states, nt, p->dig_nparts, p->dig_desc, p->dig_tab, N, 1, p->_2q, p->ql, p->qh, p->kl, p->kh, dev,
+                                   stream))
+        return e;
+    if (int e = lf_ks_fwd_batch(p->state, poly, nt, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, p->ext, plan_fwd(p), plan_mod(p), st))
+        return e;
+    for (int j = 0; j < key.n; ++j) {
+        for (int t = 0; t < nt; ++t) us[t] = u + t * u_tstride + (j + 1) * pair;
+        if (int e = lf_ks_baby_sums_batch(nt, p_host[j], p->nparts, rows, ell, logN,
+                                          {key.ksk + j, 1, key.part_stride, key.comp_stride, key.row_off, key.key_format}, p->ext, chat0, us,
+                                          plan_mod(p), st))
+            return e;
+    }
+    return 0;
+}
+
 // what lf_linear_transform_bsgs refuses in its keys, giant steps and diagonals (everything but the ciphertext, the outputs and the
 // workspace): 0 or LF_ERR_ARG, nothing launched
 static int bsgs_args_ok(const lf_ks_plan *p, int nb, const int64_t *bp_host, const int64_t *const *bksk, int ng, const int64_t *gp_host,
@@ -920,23 +972,13 @@ int lf_linear_transform_bsgs(const lf_ks_plan *p, const int64_t *c0, const int64
     int64_t *u = ws, *S = u + (nb + 1) * pair, *A = S + LF_BSGS_S_PAIRS * pair, *w = A + pair, *md = w + poly, *md1 = md + 2 * poly;
     const int64_t md1_words = lf_ks_moddown_ws_words(1, ell, p->K, N);
     if (int e = lf_set_device(dev)) return e;
-    // 1. slot 0 = P NTT(c0), P NTT(c1) on the ordinary rows (canonical copy, enter_ntt, times P R), zero on the special rows
+    // 1., 2. slot 0 = P NTT(c0), P NTT(c1) on the ordinary rows (canonical copy, enter_ntt, times P R), zero on the special rows;
+    // the baby steps: the digits of c1 extended and transformed once, one launch into the slots 1 .. nb
     {
         const int64_t *srcs[2] = {c0, c1};
-        if (int e = p_ntt(p, srcs, 2, u, (int64_t)rows * N, stream)) return e;
         for (int c = 0; c < 2; ++c)
             if (hipError_t e = hipMemsetAsync(u + c * (int64_t)rows * N + poly, 0, (size_t)p->K * N * 8, st)) return (int)e;
-    }
-    // 2. baby steps: the digits of c1 extended and transformed once, per group of keys one launch into the slots 1 .. nb
-    if (nb) {
-        if (int e = lf_ks_digits_galois(c1, p->state, p->dig_nparts, p->dig_desc, p->dig_tab, N, 1, p->_2q, p->ql, p->qh, p->kl, p->kh, dev,
-                                        stream))
-            return e;
-        if (int e = lf_ks_fwd(p->state, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, p->ext, p->psi, p->psi_dp, p->q_host, p->ql, p->qh,
-                              p->kl, p->kh, dev, stream))
-            return e;
-        if (int e = lf_ks_baby_sums(bp_host, p->nparts, rows, ell, logN, {bksk, nb, part_stride, comp_stride, row_off, key_format}, u, p->ext,
-                                    u + pair, plan_mod(p), st))
+        if (int e = column_pairs(p, 1, srcs, 0, bp_host, {bksk, nb, part_stride, comp_stride, row_off, key_format}, u, 0, nullptr, stream))
             return e;
     }
     // 3. giant steps, LF_BSGS_S_PAIRS per launch of the diagonal products; giant step 0 writes the accumulator itself
@@ -985,76 +1027,23 @@ int lf_linear_transform_bsgs(const lf_ks_plan *p, const int64_t *c0, const int64
     return moddown_rescale_pairs(p, A, 1, md, nullptr, 0, &out0, &out1, rescale_scales, round_at, stream);
 }
 
-/* ---- a matrix of linear transforms times a vector of ciphertexts: y_o = sum_i sum_step diag_{o,i,step} * rot(x_i, step)
- * (include/ckks_hip.h).  Input-major: the rotated sums t^{i,step} of one input are formed once, for every output, in the slots
- * of the BSGS path's baby pairs; the outputs' sums S^o stay in Q P over all inputs and come down once each. ---- */
+/* ---- the lf_lt_matmul family (include/ckks_hip.h): a matrix of linear transforms times a vector of ciphertexts,
+ *     y_o = sum_g rot(sum_i sum_b pt_{o,i,g+b} * rot(x_i, b), g),
+ * over nt token vectors and ng giant steps.  ONE body, lt_matmul_body, behind the four entries:
+ *     lf_lt_matmul            nt = 1,          ng = 1 (the giant step 0: every step is its own baby step)
+ *     lf_lt_matmul_batch      nt = 1, 2 or 4,  ng = 1
+ *     lf_lt_matmul_bsgs       nt = 1,          ng giant steps
+ *     lf_lt_matmul_bsgs_batch nt = 1, 2 or 4,  ng giant steps
+ * Input-major: the baby sums of one input are formed once, for every output, in the slots of the BSGS path's baby pairs
+ * (column_pairs); the inner sums S^{o,g} of the pairs (output, giant step) stay in Q P over ALL inputs — giant step 0's is the
+ * accumulator A^o itself — so an output pays one key switch per keyed giant step and the members that share a giant step share the
+ * stream of its key (bsgs_giant_step); every accumulator comes down once (matmul_tail).
+ * nt selects the launches: nt = 1 takes the single-ciphertext kernels (the NTT straight into slot 0, one multi-key launch of the
+ * baby sums, lf_lt_block_products over giant-step-0 and keyed targets alike); nt > 1 shares every launch among the tokens (each key
+ * word read once for the group, each diagonal word once per pair of tokens: lf_lt_block_productsb, whose one token stride puts the
+ * accumulators and the keyed sums in launches of their own), and the tokens of one output fill the giant step's group.
+ * ng = 1 with the giant step 0 has no keyed sum: the giant phase does nothing, and the flat entries leave its scratch out. ---- */
 #define LF_LT_MATMUL_GROUP 4       // outputs per launch of the block products and per inverse NTT / mod-down / rescale
-
-int64_t lf_lt_matmul_ws_words(const lf_ks_plan *p, int nb_max, int k_out) {
-    if (!plan_ok(p) || nb_max < 0 || nb_max > LF_BSGS_MAX_BABY_KEYS || k_out < 1 || k_out > LF_LT_MATMUL_MAX_OUTPUTS) return 0;
-    const int64_t N = (int64_t)1 << p->logN, pair = 2 * (int64_t)(p->ell + p->K) * N, poly = (int64_t)p->ell * N;
-    const int g = k_out < LF_LT_MATMUL_GROUP ? k_out : LF_LT_MATMUL_GROUP;
-    // one input's pairs (slot 0: the ciphertext), the k_out pairs of S, the mod-down's results of one group of outputs and its
-    // workspace (the plan's own is primed for pairs)
-    return pair * (nb_max + 1 + k_out) + 2 * g * poly + lf_ks_moddown_ws_words(2 * g, p->ell, p->K, N);
-}
-
-// the checks of lf_lt_matmul on everything but the ciphertexts', the outputs' and the workspace's pointers (nin: the pointers of
-// `in` per input, 2, times the tokens; those of a used input are checked for every token), and what the launches need of them:
-// the first key of every column, the inputs some output uses, the blocks' slot masks, the longest used column
-static int lt_matmul_args(const lf_ks_plan *p, int nt, int k_in, int k_out, const int64_t *const *in, const int64_t *ncol,
-                          const int64_t *p_host, const int64_t *const *ksk, int64_t part_stride, int64_t comp_stride, int key_format,
-                          const int64_t *const *pt, const int64_t *pt_stride, const int64_t *bcount, const int64_t *bidx,
-                          const int64_t *rescale_scales, int64_t *const *out0, int64_t *const *out1, std::vector<int64_t> &koff,
-                          std::vector<char> &used, std::vector<unsigned long long> &masks, int &nb_max) {
-    if (!plan_ok(p) || !p->PR || p->ell < 2 || k_in < 1 || k_in > LF_LT_MATMUL_MAX_INPUTS || k_out < 1 || k_out > LF_LT_MATMUL_MAX_OUTPUTS ||
-        !in || !ncol || !pt || !pt_stride || !bcount || !bidx || !rescale_scales || !out0 || !out1 ||
-        (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES))
-        return LF_ERR_ARG;
-    const int rows = p->ell + p->K;
-    const int64_t N = (int64_t)1 << p->logN;
-    // the columns: keyed steps per input, the inputs some output uses, their keys
-    koff.assign(k_in + 1, 0);
-    used.assign(k_in, 0);
-    nb_max = 0;
-    for (int i = 0; i < k_in; ++i) {
-        if (ncol[i] < 0 || ncol[i] > LF_BSGS_MAX_BABY_KEYS) return LF_ERR_ARG;
-        koff[i + 1] = koff[i] + ncol[i];
-        for (int o = 0; o < k_out && !used[i]; ++o) used[i] = pt[(int64_t)o * k_in + i] != nullptr;
-        if (!used[i]) continue;
-        for (int t = 0; t < nt; ++t)
-            if (!in[2 * ((int64_t)t * k_in + i)] || !in[2 * ((int64_t)t * k_in + i) + 1]) return LF_ERR_ARG;
-        if (ncol[i] && (!p_host || !ksk)) return LF_ERR_ARG;
-        if (ncol[i] && !keyed_steps_ok(ksk + koff[i], p_host + koff[i], (int)ncol[i], part_stride, comp_stride, key_format, p->logN))
-            return LF_ERR_ARG;
-        if (ncol[i] > nb_max) nb_max = (int)ncol[i];
-    }
-    // the blocks: per output at least one; per block its slots inside the column's set, ascending
-    masks.assign((size_t)k_out * k_in, 0);
-    int64_t first = 0;
-    for (int o = 0; o < k_out; ++o) {
-        for (int t = 0; t < nt; ++t)
-            if (!out0[(int64_t)t * k_out + o] || !out1[(int64_t)t * k_out + o]) return LF_ERR_ARG;
-        bool any = false;
-        for (int i = 0; i < k_in; ++i) {
-            const int64_t b = (int64_t)o * k_in + i;
-            if (!pt[b]) {
-                if (bcount[b] != 0) return LF_ERR_ARG;
-                continue;
-            }
-            any = true;
-            if (bcount[b] < 1 || bcount[b] > ncol[i] + 1 || pt_stride[b] < (int64_t)rows * N) return LF_ERR_ARG;
-            for (int64_t k = 0; k < bcount[b]; ++k) {
-                const int64_t slot = bidx[first + k];
-                if (slot < 0 || slot > ncol[i] || (k && slot <= bidx[first + k - 1])) return LF_ERR_ARG;
-                masks[b] |= 1ull << slot;
-            }
-            first += bcount[b];
-        }
-        if (!any) return LF_ERR_ARG;
-    }
-    return 0;
-}
 
 // the tail of the lf_lt_matmul family: n sums [n][2][rows][N] at S in Q P, in groups of up to LF_LT_MATMUL_GROUP: one exact inverse
 // NTT (intt_exit_reduce) of the group's 2 g polynomials, one mod-down in mdws, one rescale into the pairs out0[s], out1[s]
@@ -1073,203 +1062,6 @@ static int matmul_tail(const lf_ks_plan *p, int64_t *S, int n, int64_t *md, int6
     return 0;
 }
 
-// steps 1 and 2 of lf_lt_matmul for one input c = {c0, c1}: slot 0 of u = P NTT(c0), P NTT(c1) on the ordinary rows; the digits of
-// c1 extended and transformed once, per group of the column's keys one launch into the slots 1 .. key.n
-static int column_pairs(const lf_ks_plan *p, const int64_t *const *c, const int64_t *p_host, const LfKeys &key, int64_t *u, void *stream) {
-    const int ell = p->ell, rows = p->ell + p->K, logN = p->logN, dev = p->device;
-    const int64_t N = (int64_t)1 << logN, half = (int64_t)rows * N;
-    if (int e = p_ntt(p, c, 2, u, half, stream)) return e;
-    if (!key.n) return 0;
-    if (int e = lf_ks_digits_galois(c[1], p->state, p->dig_nparts, p->dig_desc, p->dig_tab, N, 1, p->_2q, p->ql, p->qh, p->kl, p->kh, dev, stream))
-        return e;
-    if (int e = lf_ks_fwd(p->state, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, p->ext, p->psi, p->psi_dp, p->q_host, p->ql, p->qh, p->kl,
-                          p->kh, dev, stream))
-        return e;
-    return lf_ks_baby_sums(p_host, p->nparts, rows, ell, logN, key, u, p->ext, u + 2 * half, plan_mod(p), (hipStream_t)stream);
-}
-
-// steps 1 and 2 of lf_lt_matmul_batch for one input of nt (2 or 4) tokens, c[t * c_tstride + comp] token t's polynomials, u + t *
-// u_tstride its pairs:
-// 1. slot 0 of every token = P NTT(c0), P NTT(c1) on the ordinary rows: canonical copies and ONE forward NTT of the 2 nt polynomials
-//    in `tmp` (2 nt [ell][N]), times P R, then into the slots
-// 2. the digits of the nt c1 (canonical, no permutation), ONE extension + forward NTT of all of them, per key of the column ONE
-//    launch into slot 1 + j of every token: the key crosses HBM once for the group
-static int column_pairs_batch(const lf_ks_plan *p, int nt, const int64_t *const *c, int64_t c_tstride, const int64_t *p_host,
-                              const LfKeys &key, int64_t *u, int64_t u_tstride, int64_t *tmp, void *stream) {
-    const int ell = p->ell, rows = p->ell + p->K, logN = p->logN, dev = p->device;
-    const int64_t N = (int64_t)1 << logN, poly = (int64_t)ell * N, half = (int64_t)rows * N, pair = 2 * half;
-    hipStream_t st = (hipStream_t)stream;
-    {
-        const int64_t *srcs[2 * LF_LT_MATMUL_BATCH_MAX_TOKENS];
-        for (int t = 0; t < nt; ++t)
-            for (int k = 0; k < 2; ++k) srcs[2 * t + k] = c[t * c_tstride + k];
-        if (int e = p_ntt(p, srcs, 2 * nt, tmp, poly, stream)) return e;
-        for (int k = 0; k < 2 * nt; ++k)
-            if (hipError_t e = hipMemcpyAsync(u + (k / 2) * u_tstride + (k & 1) * half, tmp + k * poly, (size_t)poly * 8,
-                                              hipMemcpyDeviceToDevice, st))
-                return (int)e;
-    }
-    if (!key.n) return 0;
-    const int64_t *srcs[LF_LT_MATMUL_BATCH_MAX_TOKENS], *chat0[LF_LT_MATMUL_BATCH_MAX_TOKENS];
-    int64_t *states[LF_LT_MATMUL_BATCH_MAX_TOKENS], *us[LF_LT_MATMUL_BATCH_MAX_TOKENS];
-    for (int t = 0; t < nt; ++t) srcs[t] = c[t * c_tstride + 1], states[t] = p->state + t * poly, chat0[t] = u + t * u_tstride;
-    if (int e = lf_ks_digits_batch(srcs, states, nt, p->dig_nparts, p->dig_desc, p->dig_tab, N, 1, p->_2q, p->ql, p->qh, p->kl, p->kh, dev,
-                                   stream))
-        return e;
-    if (int e = lf_ks_fwd_batch(p->state, poly, nt, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, p->ext, plan_fwd(p), plan_mod(p), st))
-        return e;
-    for (int j = 0; j < key.n; ++j) {
-        for (int t = 0; t < nt; ++t) us[t] = u + t * u_tstride + (j + 1) * pair;
-        if (int e = lf_ks_baby_sums_batch(nt, p_host[j], p->nparts, rows, ell, logN,
-                                          {key.ksk + j, 1, key.part_stride, key.comp_stride, key.row_off, key.key_format}, p->ext, chat0, us,
-                                          plan_mod(p), st))
-            return e;
-    }
-    return 0;
-}
-
-int lf_lt_matmul(const lf_ks_plan *p, int k_in, int k_out, const int64_t *const *in, const int64_t *ncol, const int64_t *p_host,
-                 const int64_t *const *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format,
-                 const int64_t *const *pt, const int64_t *pt_stride, const int64_t *bcount, const int64_t *bidx,
-                 const int64_t *rescale_scales, int64_t round_at, int64_t *ws, int64_t ws_words, int64_t *const *out0,
-                 int64_t *const *out1, void *stream) {
-    std::vector<int64_t> koff;
-    std::vector<char> used;
-    std::vector<unsigned long long> masks;
-    int nb_max = 0;
-    if (int e = lt_matmul_args(p, 1, k_in, k_out, in, ncol, p_host, ksk, part_stride, comp_stride, key_format, pt, pt_stride, bcount, bidx,
-                               rescale_scales, out0, out1, koff, used, masks, nb_max))
-        return e;
-    const int ell = p->ell, rows = p->ell + p->K, logN = p->logN, dev = p->device;
-    const int64_t N = (int64_t)1 << logN, poly = (int64_t)ell * N, pair = 2 * (int64_t)rows * N;
-    const int64_t need = lf_lt_matmul_ws_words(p, nb_max, k_out);
-    if (!need || !ws || ws_words < need || ((uintptr_t)ws & 15)) return LF_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    const int gmax = k_out < LF_LT_MATMUL_GROUP ? k_out : LF_LT_MATMUL_GROUP;
-    int64_t *u = ws, *S = u + (nb_max + 1) * pair, *md = S + k_out * pair, *mdws = md + 2 * gmax * poly;
-    const int64_t mdws_words = lf_ks_moddown_ws_words(2 * gmax, ell, p->K, N);
-    if (int e = lf_set_device(dev)) return e;
-    // slot 0 holds nothing on the special rows, for every input
-    for (int c = 0; c < 2; ++c)
-        if (hipError_t e = hipMemsetAsync(u + c * (int64_t)rows * N + poly, 0, (size_t)p->K * N * 8, st)) return (int)e;
-    std::vector<char> written(k_out, 0);
-    for (int i = 0; i < k_in; ++i) {
-        if (!used[i]) continue;
-        const int nb = (int)ncol[i];
-        // 1., 2. slot 0 = P NTT(c0), P NTT(c1) on the ordinary rows; the column's baby sums into the slots 1 .. nb
-        if (int e = column_pairs(p, in + 2 * i, nb ? p_host + koff[i] : nullptr,
-                                 {nb ? ksk + koff[i] : nullptr, nb, part_stride, comp_stride, row_off, key_format}, u, stream))
-            return e;
-        // 3. the outputs that have a block in this column, 4, 2 or 1 per launch over the input's pairs
-        std::vector<int> os;
-        for (int o = 0; o < k_out; ++o)
-            if (pt[(int64_t)o * k_in + i]) os.push_back(o);
-        for (size_t a0 = 0; a0 < os.size();) {
-            const size_t left = os.size() - a0;
-            const int g = left >= 4 ? 4 : left >= 2 ? 2 : 1;
-            const int64_t *pts[4];
-            int64_t *outs[4], strides[4];
-            unsigned long long slots[4];
-            int fresh[4];
-            for (int t = 0; t < g; ++t) {
-                const int o = os[a0 + t];
-                const int64_t b = (int64_t)o * k_in + i;
-                pts[t] = pt[b], strides[t] = pt_stride[b], slots[t] = masks[b], outs[t] = S + o * pair, fresh[t] = !written[o];
-                written[o] = 1;
-            }
-            if (int e = lf_lt_block_products(g, u, nb + 1, pts, slots, strides, outs, fresh, rows, logN, plan_mod(p), st)) return e;
-            a0 += g;
-        }
-    }
-    // 4. per group of outputs one exact inverse NTT (intt_exit_reduce) of its 2 g polynomials, one mod-down, one rescale
-    return matmul_tail(p, S, k_out, md, mdws, mdws_words, out0, out1, rescale_scales, round_at, stream);
-}
-
-/* ---- lf_lt_matmul over nt token vectors under one matrix and one key set (include/ckks_hip.h): a group of nt = 2 or 4 tokens
- * shares every launch; the baby sums read each key word and the block products each diagonal word once for the tokens of a
- * launch.  nt = 1 is lf_lt_matmul. ---- */
-int64_t lf_lt_matmul_batch_ws_words(const lf_ks_plan *p, int nb_max, int k_out, int nt) {
-    if (!batch_ok(p, nt) || nt > LF_LT_MATMUL_BATCH_MAX_TOKENS || nb_max < 0 || nb_max > LF_BSGS_MAX_BABY_KEYS || k_out < 1 ||
-        k_out > LF_LT_MATMUL_MAX_OUTPUTS)
-        return 0;
-    const int64_t N = (int64_t)1 << p->logN, pair = 2 * (int64_t)(p->ell + p->K) * N, poly = (int64_t)p->ell * N;
-    const int g = nt * k_out < LF_LT_MATMUL_GROUP ? nt * k_out : LF_LT_MATMUL_GROUP;
-    // per token one input's pairs and the k_out pairs of S; the mod-down's results of one group of sums and its workspace
-    return pair * nt * (nb_max + 1 + k_out) + 2 * g * poly + lf_ks_moddown_ws_words(2 * g, p->ell, p->K, N);
-}
-
-int lf_lt_matmul_batch(const lf_ks_plan *p, int nt, int k_in, int k_out, const int64_t *const *in, const int64_t *ncol,
-                       const int64_t *p_host, const int64_t *const *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off,
-                       int key_format, const int64_t *const *pt, const int64_t *pt_stride, const int64_t *bcount, const int64_t *bidx,
-                       const int64_t *rescale_scales, int64_t round_at, int64_t *ws, int64_t ws_words, int64_t *const *out0,
-                       int64_t *const *out1, void *stream) {
-    if (!batch_ok(p, nt) || nt > LF_LT_MATMUL_BATCH_MAX_TOKENS) return LF_ERR_ARG;
-    if (nt == 1)
-        return lf_lt_matmul(p, k_in, k_out, in, ncol, p_host, ksk, part_stride, comp_stride, row_off, key_format, pt, pt_stride, bcount, bidx,
-                            rescale_scales, round_at, ws, ws_words, out0, out1, stream);
-    std::vector<int64_t> koff;
-    std::vector<char> used;
-    std::vector<unsigned long long> masks;
-    int nb_max = 0;
-    if (int e = lt_matmul_args(p, nt, k_in, k_out, in, ncol, p_host, ksk, part_stride, comp_stride, key_format, pt, pt_stride, bcount, bidx,
-                               rescale_scales, out0, out1, koff, used, masks, nb_max))
-        return e;
-    const int ell = p->ell, rows = p->ell + p->K, logN = p->logN, dev = p->device;
-    const int64_t N = (int64_t)1 << logN, poly = (int64_t)ell * N, half = (int64_t)rows * N, pair = 2 * half;
-    const int64_t need = lf_lt_matmul_batch_ws_words(p, nb_max, k_out, nt);
-    if (!need || !ws || ws_words < need || ((uintptr_t)ws & 15)) return LF_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    // token t: its input's pairs U(t) [nb_max + 1]; then the sums S [nt][k_out] (one run: a group of the tail may span two tokens), the
-    // mod-down's results of one group and its workspace
-    const int ns = nt * k_out, gmax = ns < LF_LT_MATMUL_GROUP ? ns : LF_LT_MATMUL_GROUP;
-    const int64_t member = (nb_max + 1) * pair;
-    int64_t *S = ws + nt * member, *md = S + ns * pair, *mdws = md + 2 * gmax * poly;
-    const int64_t mdws_words = lf_ks_moddown_ws_words(2 * gmax, ell, p->K, N);
-    auto U = [&](int t) { return ws + t * member; };
-    if (int e = lf_set_device(dev)) return e;
-    // slot 0 holds nothing on the special rows, for every input and token
-    for (int t = 0; t < nt; ++t)
-        for (int c = 0; c < 2; ++c)
-            if (hipError_t e = hipMemsetAsync(U(t) + c * half + poly, 0, (size_t)p->K * N * 8, st)) return (int)e;
-    std::vector<char> written(k_out, 0);
-    for (int i = 0; i < k_in; ++i) {
-        if (!used[i]) continue;
-        const int nb = (int)ncol[i];
-        // 1., 2. slot 0 of every member and the column's baby sums into the slots 1 .. nb (`md` is free until the tail; nt <= gmax)
-        if (int e = column_pairs_batch(p, nt, in + 2 * i, 2 * k_in, nb ? p_host + koff[i] : nullptr,
-                                       {nb ? ksk + koff[i] : nullptr, nb, part_stride, comp_stride, row_off, key_format}, U(0), member, md,
-                                       stream))
-            return e;
-        // 3. the outputs that have a block in this column, 4, 2 or 1 per launch over the pairs of a tile of tokens
-        std::vector<int> os;
-        for (int o = 0; o < k_out; ++o)
-            if (pt[(int64_t)o * k_in + i]) os.push_back(o);
-        for (size_t a0 = 0; a0 < os.size();) {
-            const size_t left = os.size() - a0;
-            const int g = left >= 4 ? 4 : left >= 2 ? 2 : 1;
-            const int64_t *pts[4];
-            int64_t *outs[4], strides[4];
-            unsigned long long slots[4];
-            int fresh[4];
-            for (int t = 0; t < g; ++t) {
-                const int o = os[a0 + t];
-                const int64_t b = (int64_t)o * k_in + i;
-                pts[t] = pt[b], strides[t] = pt_stride[b], slots[t] = masks[b], outs[t] = S + o * pair, fresh[t] = !written[o];
-                written[o] = 1;
-            }
-            if (int e = lf_lt_block_productsb(nt, g, U(0), member, nb + 1, pts, slots, strides, outs, k_out * pair, fresh, rows, logN, plan_mod(p), st))
-                return e;
-            a0 += g;
-        }
-    }
-    // 4. the nt k_out sums in groups of up to 4 (a group may span two tokens): into the callers' [ell - 1][N] pairs
-    return matmul_tail(p, S, ns, md, mdws, mdws_words, out0, out1, rescale_scales, round_at, stream);
-}
-
-/* ---- a matrix of baby-step / giant-step transforms: y_o = sum_g rot(sum_i sum_b pt_{o,i,g+b} * rot(x_i, b), g)
- * (include/ckks_hip.h).  Input-major as lf_lt_matmul, with the pairs (output, giant step) in the place of the outputs: the inner
- * sums S^{o,g} stay in Q P over ALL inputs, so an output pays one key switch per giant step, and the outputs that share a giant
- * step share the stream of its key. ---- */
 // polynomials the giant phase brings down at once: groups of 4, 2 or 1 outputs within the batch the plan is sized for
 static int bsgs_giant_group(const lf_ks_plan *p) { return p->max_nct < 4 ? p->max_nct : 4; }
 
@@ -1306,21 +1098,9 @@ static int bsgs_giant_step(const lf_ks_plan *p, int n, int64_t *const *S, int64_
     return lf_ks_giant_sums_batch(n, gp, p->nparts, rows, logN, key, p->ext, s0s, accs, plan_mod(p), st);
 }
 
-int64_t lf_lt_matmul_bsgs_ws_words(const lf_ks_plan *p, int nb_max, int k_out, int keyed_sums) {
-    if (!plan_ok(p) || nb_max < 0 || nb_max > LF_BSGS_MAX_BABY_KEYS || k_out < 1 || k_out > LF_LT_MATMUL_MAX_OUTPUTS || keyed_sums < 0 ||
-        keyed_sums > LF_LT_MATMUL_BSGS_MAX_SUMS)
-        return 0;
-    const int64_t N = (int64_t)1 << p->logN, pair = 2 * (int64_t)(p->ell + p->K) * N, poly = (int64_t)p->ell * N;
-    const int g4 = k_out < LF_LT_MATMUL_GROUP ? k_out : LF_LT_MATMUL_GROUP, gw = bsgs_giant_group(p);
-    const int64_t md_w = lf_ks_moddown_ws_words(gw, p->ell, p->K, N), md_t = lf_ks_moddown_ws_words(2 * g4, p->ell, p->K, N);
-    // one input's pairs (slot 0: the ciphertext), the k_out accumulators, the keyed inner sums, w of one giant group, the mod-down's
-    // results of one group of outputs, and the workspace of either mod-down (the plan's own is primed for pairs)
-    return pair * (nb_max + 1 + k_out + keyed_sums) + gw * poly + 2 * g4 * poly + (md_w > md_t ? md_w : md_t);
-}
-
-// what lf_lt_matmul_bsgs(_batch) learns of its arguments while it checks them: the first key of every column, the inputs some
-// output uses, the blocks' slot masks, the pairs (o, j) that have a diagonal, the index of every keyed inner sum (giant step after
-// giant step), the longest used column and the number of keyed sums
+// what the family learns of its arguments while it checks them: the first key of every column, the inputs some output uses, the
+// blocks' slot masks, the pairs (o, j) that have a diagonal, the index of every keyed inner sum (giant step after giant step), the
+// longest used column and the number of keyed sums
 struct BsgsShape {
     std::vector<int64_t> koff;
     std::vector<char> used, has;
@@ -1329,16 +1109,16 @@ struct BsgsShape {
     int nb_max = 0, keyed_sums = 0;
 };
 
-// the checks of lf_lt_matmul_bsgs on everything but the workspace, for nt tokens (in: [token][input][component], those of a used
-// input are checked for every token; out0 / out1: [token][output])
+// the family's checks on everything but the workspace, for nt tokens (in: [token][input][component], those of a used input are
+// checked for every token; out0 / out1: [token][output]).  gp_host is the caller's to check for NULL; gksk is read for keyed giant
+// steps alone (the flat entries have none and pass NULL)
 static int lt_matmul_bsgs_args(const lf_ks_plan *p, int nt, int k_in, int k_out, const int64_t *const *in, const int64_t *ncol,
                                const int64_t *bp_host, const int64_t *const *bksk, int ng, const int64_t *gp_host,
                                const int64_t *const *gksk, int64_t part_stride, int64_t comp_stride, int key_format,
                                const int64_t *const *pt, const int64_t *pt_stride, const int64_t *gcount, const int64_t *bidx,
                                const int64_t *rescale_scales, int64_t *const *out0, int64_t *const *out1, BsgsShape &sh) {
     if (!plan_ok(p) || !p->PR || p->ell < 2 || k_in < 1 || k_in > LF_LT_MATMUL_MAX_INPUTS || k_out < 1 || k_out > LF_LT_MATMUL_MAX_OUTPUTS ||
-        ng < 1 || ng > LF_LT_MATMUL_BSGS_MAX_GIANTS || !in || !ncol || !gp_host || !gksk || !pt || !pt_stride || !gcount || !bidx ||
-        !rescale_scales || !out0 || !out1 || (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES))
+        ng < 1 || ng > LF_LT_MATMUL_BSGS_MAX_GIANTS || !in || !ncol || !pt || !pt_stride || !gcount || !bidx || !rescale_scales || !out0 || !out1 || (key_format != LF_KEY_RAW && key_format != LF_KEY_PLANES))
         return LF_ERR_ARG;
     const int rows = p->ell + p->K, logN = p->logN;
     const int64_t N = (int64_t)1 << logN;
@@ -1400,140 +1180,73 @@ static int lt_matmul_bsgs_args(const lf_ks_plan *p, int nt, int k_in, int k_out,
     return sh.keyed_sums > LF_LT_MATMUL_BSGS_MAX_SUMS ? LF_ERR_ARG : 0;
 }
 
-int lf_lt_matmul_bsgs(const lf_ks_plan *p, int k_in, int k_out, const int64_t *const *in, const int64_t *ncol, const int64_t *bp_host,
-                      const int64_t *const *bksk, int ng, const int64_t *gp_host, const int64_t *const *gksk, int64_t part_stride,
-                      int64_t comp_stride, int64_t row_off, int key_format, const int64_t *const *pt, const int64_t *pt_stride,
-                      const int64_t *gcount, const int64_t *bidx, const int64_t *rescale_scales, int64_t round_at, int64_t *ws,
-                      int64_t ws_words, int64_t *const *out0, int64_t *const *out1, void *stream) {
-    BsgsShape sh;
-    if (int e = lt_matmul_bsgs_args(p, 1, k_in, k_out, in, ncol, bp_host, bksk, ng, gp_host, gksk, part_stride, comp_stride, key_format, pt,
-                                    pt_stride, gcount, bidx, rescale_scales, out0, out1, sh))
-        return e;
-    const int ell = p->ell, rows = p->ell + p->K, logN = p->logN, dev = p->device;
-    const int64_t N = (int64_t)1 << logN, poly = (int64_t)ell * N, pair = 2 * (int64_t)rows * N;
-    auto block = [&](int o, int i, int j) { return ((int64_t)o * k_in + i) * ng + j; };
-    // per (output, giant step) the target of its inner sum: the accumulator A^o itself for giant step 0, else its pair of S
-    const std::vector<int64_t> &koff = sh.koff;
-    const std::vector<char> &used = sh.used, &has = sh.has;
-    const std::vector<unsigned long long> &masks = sh.masks;
-    const std::vector<int> &sidx = sh.sidx;
-    const int nb_max = sh.nb_max, keyed_sums = sh.keyed_sums;
-    const int64_t need = lf_lt_matmul_bsgs_ws_words(p, nb_max, k_out, keyed_sums);
-    if (!need || !ws || ws_words < need || ((uintptr_t)ws & 15)) return LF_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    const int g4 = k_out < LF_LT_MATMUL_GROUP ? k_out : LF_LT_MATMUL_GROUP, gw = bsgs_giant_group(p);
-    int64_t *u = ws, *A = u + (nb_max + 1) * pair, *S = A + k_out * pair, *w = S + keyed_sums * pair, *md = w + gw * poly,
-            *mdws = md + 2 * g4 * poly;
-    const int64_t md_w = lf_ks_moddown_ws_words(gw, ell, p->K, N), md_t = lf_ks_moddown_ws_words(2 * g4, ell, p->K, N);
-    const int64_t mdws_words = md_w > md_t ? md_w : md_t;
-    auto target = [&](int o, int j) { return gp_host[j] == 0 ? A + o * pair : S + sidx[(size_t)o * ng + j] * pair; };
-    if (int e = lf_set_device(dev)) return e;
-    // slot 0 holds nothing on the special rows, for every input; an output without giant step 0 starts from a zero accumulator
-    for (int c = 0; c < 2; ++c)
-        if (hipError_t e = hipMemsetAsync(u + c * (int64_t)rows * N + poly, 0, (size_t)p->K * N * 8, st)) return (int)e;
-    for (int o = 0; o < k_out; ++o)
-        if (!(gp_host[0] == 0 && has[(size_t)o * ng]))
-            if (hipError_t e = hipMemsetAsync(A + o * pair, 0, (size_t)pair * 8, st)) return (int)e;
-    // 1. input-major (steps 1 - 3 of lf_lt_matmul, the pairs (o, j) in the place of the outputs)
-    std::vector<char> written((size_t)k_out * ng, 0);
-    for (int i = 0; i < k_in; ++i) {
-        if (!used[i]) continue;
-        const int nb = (int)ncol[i];
-        if (int e = column_pairs(p, in + 2 * i, nb ? bp_host + koff[i] : nullptr,
-                                 {nb ? bksk + koff[i] : nullptr, nb, part_stride, comp_stride, row_off, key_format}, u, stream))
-            return e;
-        std::vector<int> ts;   // the targets o * ng + j with a diagonal in this column
-        for (int o = 0; o < k_out; ++o)
-            for (int j = 0; j < ng; ++j)
-                if (pt[block(o, i, j)]) ts.push_back(o * ng + j);
-        for (size_t a0 = 0; a0 < ts.size();) {
-            const size_t left = ts.size() - a0;
-            const int g = left >= 4 ? 4 : left >= 2 ? 2 : 1;
-            const int64_t *pts[4];
-            int64_t *outs[4], strides[4];
-            unsigned long long slots[4];
-            int fresh[4];
-            for (int t = 0; t < g; ++t) {
-                const int o = ts[a0 + t] / ng, j = ts[a0 + t] % ng;
-                const int64_t b = block(o, i, j);
-                pts[t] = pt[b], strides[t] = pt_stride[b], slots[t] = masks[b], outs[t] = target(o, j), fresh[t] = !written[ts[a0 + t]];
-                written[ts[a0 + t]] = 1;
-            }
-            if (int e = lf_lt_block_products(g, u, nb + 1, pts, slots, strides, outs, fresh, rows, logN, plan_mod(p), st)) return e;
-            a0 += g;
-        }
-    }
-    // 2. giant-step-major: the outputs that have the giant step, 4, 2 or 1 per key stream
-    for (int j = 0; j < ng; ++j) {
-        if (gp_host[j] == 0) continue;
-        std::vector<int> os;
-        for (int o = 0; o < k_out; ++o)
-            if (has[(size_t)o * ng + j]) os.push_back(o);
-        for (size_t a0 = 0; a0 < os.size();) {
-            const size_t left = os.size() - a0;
-            const int n = (left >= 4 && gw >= 4) ? 4 : (left >= 2 && gw >= 2) ? 2 : 1;
-            int64_t *Ss[4], *accs[4];
-            for (int t = 0; t < n; ++t) Ss[t] = target(os[a0 + t], j), accs[t] = A + os[a0 + t] * pair;
-            if (int e = bsgs_giant_step(p, n, Ss, accs, gp_host[j], {gksk + j, 1, part_stride, comp_stride, row_off, key_format}, w, mdws,
-                                        mdws_words, stream))
-                return e;
-            a0 += n;
-        }
-    }
-    // 3. the tail (step 4 of lf_lt_matmul): per group of outputs one exact inverse NTT of its 2 g accumulator polynomials, one
-    // mod-down, one rescale
-    return matmul_tail(p, A, k_out, md, mdws, mdws_words, out0, out1, rescale_scales, round_at, stream);
-}
+// the family's workspace, in words from its start (total = 0: an argument out of range): per token one input's pairs U [nt][nb_max
+// + 1] (slot 0: the ciphertext; `member` words a token), the accumulators A [nt][k_out] (one run: a group of the tail may span two
+// tokens), the keyed inner sums S [nt][keyed_sums], w of one giant group, the mod-down's results md of one group of accumulators,
+// and the workspace of either mod-down (the plan's own is primed for pairs).  The flat entries (bsgs = false, keyed_sums = 0) have no
+// giant phase: no w, and mdws sized for the tail alone
+struct LtMatmulLayout {
+    int64_t member, A, S, w, md, mdws, mdws_words, total;
+};
 
-/* ---- lf_lt_matmul_bsgs over nt token vectors under one matrix and one key set (include/ckks_hip.h): a group of nt = 2 or 4 tokens
- * shares every launch of the baby sums (each baby key read once for the group), the block products read each diagonal word once
- * per pair of tokens, and the tokens of one output fill the giant step's group, so a giant key is read once for up to 4 members
- * whatever k_out is.  nt = 1 is lf_lt_matmul_bsgs. ---- */
-int64_t lf_lt_matmul_bsgs_batch_ws_words(const lf_ks_plan *p, int nb_max, int k_out, int keyed_sums, int nt) {
-    if (!batch_ok(p, nt) || nt > LF_LT_MATMUL_BSGS_BATCH_MAX_TOKENS || nb_max < 0 || nb_max > LF_BSGS_MAX_BABY_KEYS || k_out < 1 ||
-        k_out > LF_LT_MATMUL_MAX_OUTPUTS || keyed_sums < 0 || keyed_sums > LF_LT_MATMUL_BSGS_MAX_SUMS)
-        return 0;
+static LtMatmulLayout lt_matmul_layout(const lf_ks_plan *p, int nt, int nb_max, int k_out, int keyed_sums, bool bsgs) {
+    LtMatmulLayout L = {};
+    if (!plan_ok(p) || nb_max < 0 || nb_max > LF_BSGS_MAX_BABY_KEYS || k_out < 1 || k_out > LF_LT_MATMUL_MAX_OUTPUTS || keyed_sums < 0 ||
+        keyed_sums > LF_LT_MATMUL_BSGS_MAX_SUMS)
+        return L;
     const int64_t N = (int64_t)1 << p->logN, pair = 2 * (int64_t)(p->ell + p->K) * N, poly = (int64_t)p->ell * N;
-    const int g4 = nt * k_out < LF_LT_MATMUL_GROUP ? nt * k_out : LF_LT_MATMUL_GROUP, gw = bsgs_giant_group(p);
-    const int64_t md_w = lf_ks_moddown_ws_words(gw, p->ell, p->K, N), md_t = lf_ks_moddown_ws_words(2 * g4, p->ell, p->K, N);
-    // per token one input's pairs, the k_out accumulators and the keyed inner sums; w of one giant group, the mod-down's results of
-    // one group of accumulators, and the workspace of either mod-down
-    return pair * nt * (nb_max + 1 + k_out + keyed_sums) + gw * poly + 2 * g4 * poly + (md_w > md_t ? md_w : md_t);
+    const int na = nt * k_out, g4 = na < LF_LT_MATMUL_GROUP ? na : LF_LT_MATMUL_GROUP, gw = bsgs ? bsgs_giant_group(p) : 0;
+    const int64_t md_w = bsgs ? lf_ks_moddown_ws_words(gw, p->ell, p->K, N) : 0, md_t = lf_ks_moddown_ws_words(2 * g4, p->ell, p->K, N);
+    L.member = (nb_max + 1) * pair;
+    L.A = nt * L.member;
+    L.S = L.A + na * pair;
+    L.w = L.S + (int64_t)nt * keyed_sums * pair;
+    L.md = L.w + gw * poly;
+    L.mdws = L.md + 2 * g4 * poly;
+    L.mdws_words = md_w > md_t ? md_w : md_t;
+    L.total = L.mdws + L.mdws_words;
+    return L;
 }
 
-int lf_lt_matmul_bsgs_batch(const lf_ks_plan *p, int nt, int k_in, int k_out, const int64_t *const *in, const int64_t *ncol,
-                            const int64_t *bp_host, const int64_t *const *bksk, int ng, const int64_t *gp_host,
-                            const int64_t *const *gksk, int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format,
-                            const int64_t *const *pt, const int64_t *pt_stride, const int64_t *gcount, const int64_t *bidx,
-                            const int64_t *rescale_scales, int64_t round_at, int64_t *ws, int64_t ws_words, int64_t *const *out0,
-                            int64_t *const *out1, void *stream) {
-    if (!batch_ok(p, nt) || nt > LF_LT_MATMUL_BSGS_BATCH_MAX_TOKENS) return LF_ERR_ARG;
-    if (nt == 1)
-        return lf_lt_matmul_bsgs(p, k_in, k_out, in, ncol, bp_host, bksk, ng, gp_host, gksk, part_stride, comp_stride, row_off, key_format, pt,
-                                 pt_stride, gcount, bidx, rescale_scales, round_at, ws, ws_words, out0, out1, stream);
+int64_t lf_lt_matmul_ws_words(const lf_ks_plan *p, int nb_max, int k_out) { return lt_matmul_layout(p, 1, nb_max, k_out, 0, false).total; }
+
+int64_t lf_lt_matmul_batch_ws_words(const lf_ks_plan *p, int nb_max, int k_out, int nt) {
+    if (!batch_ok(p, nt) || nt > LF_LT_MATMUL_BATCH_MAX_TOKENS) return 0;
+    return lt_matmul_layout(p, nt, nb_max, k_out, 0, false).total;
+}
+
+int64_t lf_lt_matmul_bsgs_ws_words(const lf_ks_plan *p, int nb_max, int k_out, int keyed_sums) {
+    return lt_matmul_layout(p, 1, nb_max, k_out, keyed_sums, true).total;
+}
+
+int64_t lf_lt_matmul_bsgs_batch_ws_words(const lf_ks_plan *p, int nb_max, int k_out, int keyed_sums, int nt) {
+    if (!batch_ok(p, nt) || nt > LF_LT_MATMUL_BSGS_BATCH_MAX_TOKENS) return 0;
+    return lt_matmul_layout(p, nt, nb_max, k_out, keyed_sums, true).total;
+}
+
+// the body of the family (the comment at its head): nt tokens, ng giant steps; bsgs: the layout of the BSGS entries
+static int lt_matmul_body(const lf_ks_plan *p, bool bsgs, int nt, int k_in, int k_out, const int64_t *const *in, const int64_t *ncol,
+                          const int64_t *bp_host, const int64_t *const *bksk, int ng, const int64_t *gp_host, const int64_t *const *gksk,
+                          int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format, const int64_t *const *pt,
+                          const int64_t *pt_stride, const int64_t *gcount, const int64_t *bidx, const int64_t *rescale_scales,
+                          int64_t round_at, int64_t *ws, int64_t ws_words, int64_t *const *out0, int64_t *const *out1, void *stream) {
     BsgsShape sh;
     if (int e = lt_matmul_bsgs_args(p, nt, k_in, k_out, in, ncol, bp_host, bksk, ng, gp_host, gksk, part_stride, comp_stride, key_format, pt,
                                     pt_stride, gcount, bidx, rescale_scales, out0, out1, sh))
         return e;
-    const int ell = p->ell, rows = p->ell + p->K, logN = p->logN;
-    const int64_t N = (int64_t)1 << logN, poly = (int64_t)ell * N, half = (int64_t)rows * N, pair = 2 * half;
-    const int nb_max = sh.nb_max, keyed_sums = sh.keyed_sums;
-    const int64_t need = lf_lt_matmul_bsgs_batch_ws_words(p, nb_max, k_out, keyed_sums, nt);
-    if (!need || !ws || ws_words < need || ((uintptr_t)ws & 15)) return LF_ERR_ARG;
+    const int rows = p->ell + p->K, logN = p->logN;
+    const int64_t N = (int64_t)1 << logN, poly = (int64_t)p->ell * N, half = (int64_t)rows * N, pair = 2 * half;
+    const int keyed_sums = sh.keyed_sums;
+    const LtMatmulLayout L = lt_matmul_layout(p, nt, sh.nb_max, k_out, keyed_sums, bsgs);
+    if (!L.total || !ws || ws_words < L.total || ((uintptr_t)ws & 15)) return LF_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    // token t: its input's pairs U(t) [nb_max + 1]; then the accumulators A [nt][k_out] (one run: a group of the tail may span two
-    // tokens) and the keyed inner sums S [nt][keyed_sums]; w of one giant group, the mod-down's results of one group and the
-    // workspace of either mod-down.  A and S have different token strides, and a launch of the block products takes one: the
-    // targets of giant step 0 and the keyed ones go in launches of their own
-    const int na = nt * k_out, g4 = na < LF_LT_MATMUL_GROUP ? na : LF_LT_MATMUL_GROUP, gw = bsgs_giant_group(p);
-    const int64_t member = (nb_max + 1) * pair;
-    int64_t *A = ws + nt * member, *S = A + na * pair, *w = S + (int64_t)nt * keyed_sums * pair, *md = w + gw * poly, *mdws = md + 2 * g4 * poly;
-    const int64_t md_w = lf_ks_moddown_ws_words(gw, ell, p->K, N), md_t = lf_ks_moddown_ws_words(2 * g4, ell, p->K, N);
-    const int64_t mdws_words = md_w > md_t ? md_w : md_t;
+    int64_t *w = ws + L.w, *md = ws + L.md, *mdws = ws + L.mdws;
     auto block = [&](int o, int i, int j) { return ((int64_t)o * k_in + i) * ng + j; };
-    auto U = [&](int t) { return ws + t * member; };
-    auto acc = [&](int t, int o) { return A + ((int64_t)t * k_out + o) * pair; };
-    auto sum = [&](int t, int o, int j) { return S + ((int64_t)t * keyed_sums + sh.sidx[(size_t)o * ng + j]) * pair; };
+    auto U = [&](int t) { return ws + t * L.member; };
+    auto acc = [&](int t, int o) { return ws + L.A + ((int64_t)t * k_out + o) * pair; };
+    auto sum = [&](int t, int o, int j) { return ws + L.S + ((int64_t)t * keyed_sums + sh.sidx[(size_t)o * ng + j]) * pair; };
+    // per (output, giant step) the target of its inner sum: the accumulator A^o itself for giant step 0, else its pair of S
+    auto target = [&](int o, int j) { return gp_host[j] == 0 ? acc(0, o) : sum(0, o, j); };
     if (int e = lf_set_device(p->device)) return e;
     // slot 0 holds nothing on the special rows, for every input and token; an output without giant step 0 starts from zero accumulators
     for (int t = 0; t < nt; ++t)
@@ -1543,21 +1256,23 @@ int lf_lt_matmul_bsgs_batch(const lf_ks_plan *p, int nt, int k_in, int k_out, co
         if (!(gp_host[0] == 0 && sh.has[(size_t)o * ng]))
             for (int t = 0; t < nt; ++t)
                 if (hipError_t e = hipMemsetAsync(acc(t, o), 0, (size_t)pair * 8, st)) return (int)e;
-    // 1. input-major: steps 1 - 2 of lf_lt_matmul_batch, then lf_lt_matmul_bsgs's products over the pairs of a tile of tokens
+    // 1. input-major
     std::vector<char> written((size_t)k_out * ng, 0);
     for (int i = 0; i < k_in; ++i) {
         if (!sh.used[i]) continue;
         const int nb = (int)ncol[i];
-        if (int e = column_pairs_batch(p, nt, in + 2 * i, 2 * k_in, nb ? bp_host + sh.koff[i] : nullptr,
-                                       {nb ? bksk + sh.koff[i] : nullptr, nb, part_stride, comp_stride, row_off, key_format}, U(0), member, md,
-                                       stream))
+        // slot 0 of every token and the column's baby sums into the slots 1 .. nb (`md` is free until the tail; nt <= its group)
+        if (int e = column_pairs(p, nt, in + 2 * i, 2 * k_in, nb ? bp_host + sh.koff[i] : nullptr,
+                                 {nb ? bksk + sh.koff[i] : nullptr, nb, part_stride, comp_stride, row_off, key_format}, U(0), L.member, md, stream))
             return e;
-        // the targets o * ng + j with a diagonal in this column: those of giant step 0 (the accumulators), then the keyed ones
-        for (int keyed = 0; keyed < 2; ++keyed) {
+        // the targets o * ng + j with a diagonal in this column, 4, 2 or 1 per launch over the input's pairs.  nt = 1: all of them in
+        // one grouping.  nt > 1: A and S have different token strides and a launch takes one, so those of giant step 0 (the
+        // accumulators) are grouped first, then the keyed ones
+        for (int keyed = 0; keyed < (nt == 1 ? 1 : 2); ++keyed) {
             std::vector<int> ts;
             for (int o = 0; o < k_out; ++o)
                 for (int j = 0; j < ng; ++j)
-                    if (pt[block(o, i, j)] && (gp_host[j] != 0) == (keyed != 0)) ts.push_back(o * ng + j);
+                    if (pt[block(o, i, j)] && (nt == 1 || (gp_host[j] != 0) == (keyed != 0))) ts.push_back(o * ng + j);
             for (size_t a0 = 0; a0 < ts.size();) {
                 const size_t left = ts.size() - a0;
                 const int g = left >= 4 ? 4 : left >= 2 ? 2 : 1;
@@ -1568,19 +1283,20 @@ int lf_lt_matmul_bsgs_batch(const lf_ks_plan *p, int nt, int k_in, int k_out, co
                 for (int k = 0; k < g; ++k) {
                     const int o = ts[a0 + k] / ng, j = ts[a0 + k] % ng;
                     const int64_t b = block(o, i, j);
-                    pts[k] = pt[b], strides[k] = pt_stride[b], slots[k] = sh.masks[b], fresh[k] = !written[ts[a0 + k]];
-                    outs[k] = keyed ? sum(0, o, j) : acc(0, o);
+                    pts[k] = pt[b], strides[k] = pt_stride[b], slots[k] = sh.masks[b], outs[k] = target(o, j), fresh[k] = !written[ts[a0 + k]];
                     written[ts[a0 + k]] = 1;
                 }
-                if (int e = lf_lt_block_productsb(nt, g, U(0), member, nb + 1, pts, slots, strides, outs, (keyed ? keyed_sums : k_out) * pair,
-                                                  fresh, rows, logN, plan_mod(p), st))
+                if (int e = nt == 1 ? lf_lt_block_products(g, U(0), nb + 1, pts, slots, strides, outs, fresh, rows, logN, plan_mod(p), st)
+                                    : lf_lt_block_productsb(nt, g, U(0), L.member, nb + 1, pts, slots, strides, outs,
+                                                            (keyed ? keyed_sums : k_out) * pair, fresh, rows, logN, plan_mod(p), st))
                     return e;
                 a0 += g;
             }
         }
     }
-    // 2. giant-step-major: the members (t, o) that have the giant step, output-major with the tokens of an output adjacent, 4, 2 or 1
-    //    per key stream
+    // 2. giant-step-major: the members (o, t) that have the giant step, output-major with the tokens of an output adjacent, 4, 2 or 1
+    //    per key stream within the batch the plan is sized for (nothing where no giant step is keyed)
+    const int gw = bsgs_giant_group(p);
     for (int j = 0; j < ng; ++j) {
         if (gp_host[j] == 0) continue;
         std::vector<int> ms;   // o * nt + t
@@ -1593,13 +1309,56 @@ int lf_lt_matmul_bsgs_batch(const lf_ks_plan *p, int nt, int k_in, int k_out, co
             int64_t *Ss[4], *accs[4];
             for (int k = 0; k < n; ++k) Ss[k] = sum(ms[a0 + k] % nt, ms[a0 + k] / nt, j), accs[k] = acc(ms[a0 + k] % nt, ms[a0 + k] / nt);
             if (int e = bsgs_giant_step(p, n, Ss, accs, gp_host[j], {gksk + j, 1, part_stride, comp_stride, row_off, key_format}, w, mdws,
-                                        mdws_words, stream))
+                                        L.mdws_words, stream))
                 return e;
             a0 += n;
         }
     }
-    // 3. the tail: the nt k_out accumulators, token-major, in groups of up to 4 (a group may span two tokens)
-    return matmul_tail(p, A, na, md, mdws, mdws_words, out0, out1, rescale_scales, round_at, stream);
+    // 3. the tail: the nt k_out accumulators, token-major, in groups of up to 4 (a group may span two tokens): per group one exact
+    //    inverse NTT (intt_exit_reduce) of its 2 g polynomials, one mod-down, one rescale into the callers' [ell - 1][N] pairs
+    return matmul_tail(p, acc(0, 0), nt * k_out, md, mdws, L.mdws_words, out0, out1, rescale_scales, round_at, stream);
+}
+
+static const int64_t lt_flat_giant = 0;   // the flat entries' giant steps: the one step 0, which has no key
+
+int lf_lt_matmul_batch(const lf_ks_plan *p, int nt, int k_in, int k_out, const int64_t *const *in, const int64_t *ncol,
+                       const int64_t *p_host, const int64_t *const *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off,
+                       int key_format, const int64_t *const *pt, const int64_t *pt_stride, const int64_t *bcount, const int64_t *bidx,
+                       const int64_t *rescale_scales, int64_t round_at, int64_t *ws, int64_t ws_words, int64_t *const *out0,
+                       int64_t *const *out1, void *stream) {
+    if (!batch_ok(p, nt) || nt > LF_LT_MATMUL_BATCH_MAX_TOKENS) return LF_ERR_ARG;
+    return lt_matmul_body(p, false, nt, k_in, k_out, in, ncol, p_host, ksk, 1, &lt_flat_giant, nullptr, part_stride, comp_stride, row_off,
+                          key_format, pt, pt_stride, bcount, bidx, rescale_scales, round_at, ws, ws_words, out0, out1, stream);
+}
+
+int lf_lt_matmul(const lf_ks_plan *p, int k_in, int k_out, const int64_t *const *in, const int64_t *ncol, const int64_t *p_host,
+                 const int64_t *const *ksk, int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format,
+                 const int64_t *const *pt, const int64_t *pt_stride, const int64_t *bcount, const int64_t *bidx,
+                 const int64_t *rescale_scales, int64_t round_at, int64_t *ws, int64_t ws_words, int64_t *const *out0,
+                 int64_t *const *out1, void *stream) {
+    return lt_matmul_body(p, false, 1, k_in, k_out, in, ncol, p_host, ksk, 1, &lt_flat_giant, nullptr, part_stride, comp_stride, row_off,
+                          key_format, pt, pt_stride, bcount, bidx, rescale_scales, round_at, ws, ws_words, out0, out1, stream);
+}
+
+int lf_lt_matmul_bsgs_batch(const lf_ks_plan *p, int nt, int k_in, int k_out, const int64_t *const *in, const int64_t *ncol,
+                            const int64_t *bp_host, const int64_t *const *bksk, int ng, const int64_t *gp_host,
+                            const int64_t *const *gksk, int64_t part_stride, int64_t comp_stride, int64_t row_off, int key_format,
+                            const int64_t *const *pt, const int64_t *pt_stride, const int64_t *gcount, const int64_t *bidx,
+                            const int64_t *rescale_scales, int64_t round_at, int64_t *ws, int64_t ws_words, int64_t *const *out0,
+                            int64_t *const *out1, void *stream) {
+    if (!batch_ok(p, nt) || nt > LF_LT_MATMUL_BSGS_BATCH_MAX_TOKENS || !gp_host || !gksk) return LF_ERR_ARG;
+    return lt_matmul_body(p, true, nt, k_in, k_out, in, ncol, bp_host, bksk, ng, gp_host, gksk, part_stride, comp_stride, row_off, key_format, pt,
+                          pt_stride, gcount, bidx, rescale_scales, round_at, ws, ws_words, out0, out1, stream);
+}
+
+int lf_lt_matmul_bsgs(const lf_ks_plan *p, int k_in, int k_out, const int64_t *const *in, const int64_t *ncol, const int64_t *bp_host,
+                      const int64_t *const *bksk, int ng, const int64_t *gp_host, const int64_t *const *gksk, int64_t part_stride,
+                      int64_t comp_stride, int64_t row_off, int key_format, const int64_t *const *pt, const int64_t *pt_stride,
+                      const int64_t *gcount, const int64_t *bidx, const int64_t *rescale_scales, int64_t round_at, int64_t *ws,
+                      int64_t ws_words, int64_t *const *out0, int64_t *const *out1, void *stream) {
+    if (!gp_host || !gksk) return LF_ERR_ARG;
+    return lt_matmul_body(p, true, 1, k_in, k_out, in, ncol, bp_host, bksk, ng, gp_host, gksk, part_stride, comp_stride, row_off, key_format, pt,
+                          pt_stride, gcount, bidx, rescale_scales, round_at, ws, ws_words, out0, out1, stream);
 }
 
 /* ---- baby-step / giant-step linear transform of many ciphertexts under the same diagonals and keys (include/ckks_hip.h): groups
@@ -1651,35 +1410,15 @@ int lf_linear_transform_bsgs_batch(const lf_ks_plan *p, int nct, const int64_t *
         const int64_t mdws_words = md_w > md_t ? md_w : md_t;
         auto U = [&](int t) { return ws + t * member; };
         auto S = [&](int t) { return ws + t * member + (nb + 1) * pair; };
-        // 1. slot 0 of every member = P NTT(c0), P NTT(c1) on the ordinary rows, zero on the special rows: canonical copies and ONE
-        //    forward NTT of the 2 g polynomials in `md` (free until the tail), times P R, then into the slots
+        // 1., 2. slot 0 of every member = P NTT(c0), P NTT(c1) on the ordinary rows (through `md`, free until the tail), zero on the
+        //    special rows; the baby steps: per baby key ONE launch into the g slots of that key
         {
             const int64_t *srcs[8];
             for (int t = 0; t < g; ++t) srcs[2 * t] = c0[t0 + t], srcs[2 * t + 1] = c1[t0 + t];
-            if (int e = p_ntt(p, srcs, 2 * g, md, poly, stream)) return e;
-            for (int i = 0; i < 2 * g; ++i) {
-                int64_t *slot = U(i / 2) + (i & 1) * half;
-                if (hipError_t e = hipMemcpyAsync(slot, md + i * poly, (size_t)poly * 8, hipMemcpyDeviceToDevice, st)) return (int)e;
-                if (hipError_t e = hipMemsetAsync(slot + poly, 0, (size_t)p->K * N * 8, st)) return (int)e;
-            }
-        }
-        // 2. baby steps: the digits of the g c1 (canonical, no permutation), ONE extension + forward NTT of all of them, per baby key
-        //    ONE launch into the g slots of that key
-        if (nb) {
-            const int64_t *srcs[4], *chat0[4];
-            int64_t *states[4], *us[4];
-            for (int t = 0; t < g; ++t) srcs[t] = c1[t0 + t], states[t] = p->state + t * poly, chat0[t] = U(t);
-            if (int e = lf_ks_digits_batch(srcs, states, g, p->dig_nparts, p->dig_desc, p->dig_tab, N, 1, p->_2q, p->ql, p->qh, p->kl, p->kh, dev,
-                                           stream))
+            for (int i = 0; i < 2 * g; ++i)
+                if (hipError_t e = hipMemsetAsync(U(i / 2) + (i & 1) * half + poly, 0, (size_t)p->K * N * 8, st)) return (int)e;
+            if (int e = column_pairs(p, g, srcs, 2, bp_host, {bksk, nb, part_stride, comp_stride, row_off, key_format}, U(0), member, md, stream))
                 return e;
-            if (int e = lf_ks_fwd_batch(p->state, poly, g, p->nparts, rows, logN, p->ext_desc, p->E, p->Ed, p->ext, plan_fwd(p), plan_mod(p), st))
-                return e;
-            for (int b = 0; b < nb; ++b) {
-                for (int t = 0; t < g; ++t) us[t] = U(t) + (b + 1) * pair;
-                if (int e = lf_ks_baby_sums_batch(g, bp_host[b], p->nparts, rows, ell, logN, {bksk + b, 1, part_stride, comp_stride, row_off, key_format},
-                                                  p->ext, chat0, us, plan_mod(p), st))
-                    return e;
-            }
         }
         // 3. giant steps, LF_BSGS_S_PAIRS per launch of each member's diagonal products; giant step 0 writes the accumulators
         if (gp_host[0] != 0)

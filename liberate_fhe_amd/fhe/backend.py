@@ -729,41 +729,61 @@ class HipBackend:
         k_in entries, None or (pack [k, rows, N], slots): the block's encoded diagonals and the column slot of each, ascending;
         outs: k_out tensors [2, ell - 1, N]; ws: at least lt_matmul_ws_words(plan, the longest used column, k_out) words."""
         dev, st = _ds(outs[0])
-        k_in, k_out = len(ins), len(blocks)
-        kb, ps, cs, fmt, pts, strides, counts, slots = self._lt_matmul_marshal("lt_matmul_native", col_keys, first_part, blocks, k_in)
-        i64 = lambda v: (ctypes.c_int64 * max(len(v), 1))(*v)
-        inp = (ctypes.c_void_p * (2 * k_in))()
-        for i, pair in enumerate(ins):
-            if pair is not None:
-                inp[2 * i], inp[2 * i + 1] = pair[0].data_ptr(), pair[1].data_ptr()
-        check(lib.lf_lt_matmul(ctypes.byref(plan), k_in, k_out, inp, i64([len(c) for c in col_keys]), i64([e for c in col_exps for e in c]),
-                               kb, ps, cs, row_off, fmt, pts, i64(strides), i64(counts), i64(slots), _p(scales),
-                               round_at, _p(ws), ws.numel(), _parr([o[0] for o in outs]), _parr([o[1] for o in outs]), st),
+        cols, _, ps, cs, fmt, blk = self._lt_matmul_marshal("lt_matmul_native", col_exps, col_keys, None, first_part, blocks, len(ins))
+        check(lib.lf_lt_matmul(ctypes.byref(plan), len(ins), len(blocks), self._lt_matmul_inputs([ins]), *cols, ps, cs, row_off, fmt, *blk,
+                               _p(scales), round_at, _p(ws), ws.numel(), _parr([o[0] for o in outs]), _parr([o[1] for o in outs]), st),
               "lf_lt_matmul")
 
-    def _lt_matmul_marshal(self, name, col_keys, first_part, blocks, k_in):
-        """(key pointers, part stride, component stride, key format, pack pointers, strides, counts, slots): the keys and the
-        blocks of lt_matmul_native / lt_matmul_batch_native as the C ABI takes them."""
-        keyed = [k for col in col_keys for k in col]
-        fmt = {self._kfmt(k) for k in keyed}
+    @staticmethod
+    def _lt_matmul_inputs(toks):
+        """The `in` array of the lf_lt_matmul family: [token][input][component], NULL for an input given as None."""
+        k_in = len(toks[0])
+        inp = (ctypes.c_void_p * (len(toks) * 2 * k_in))()
+        for t, ins in enumerate(toks):
+            for i, pair in enumerate(ins):
+                if pair is not None:
+                    inp[2 * (t * k_in + i)], inp[2 * (t * k_in + i) + 1] = pair[0].data_ptr(), pair[1].data_ptr()
+        return inp
+
+    def _lt_matmul_marshal(self, name, col_exps, col_keys, giants, first_part, blocks, k_in):
+        """((keyed steps per column, their exponents, baby key pointers), (giant steps, their exponents, giant key pointers), part
+        stride, component stride, key format, (pack pointers, strides, counts, slots)): the keys and the blocks of the four
+        lt_matmul bindings as the C ABI takes them, the tuples in the order of its arguments.  giants: (giant_exps, giant_keys), or
+        None for the flat bindings, whose block (pack, slots) is the baby-step / giant-step block (pack, [(0, slots)]) under the one
+        giant step 0."""
+        flat = giants is None
+        giant_exps, giant_keys = ([0], [None]) if flat else giants
+        k_out, ng = len(blocks), len(giant_keys)
+        babies = [k for col in col_keys for k in col]
+        fmt = {self._kfmt(k) for k in babies + [k for k in giant_keys if k is not None]}
         if len(fmt) > 1:
             raise ValueError(f"{name}: the keys of one call must share one format")
         ps = cs = 0
-        kb = (ctypes.c_void_p * max(len(keyed), 1))()
-        for j, key in enumerate(keyed):
+        kb, gb = (ctypes.c_void_p * max(len(babies), 1))(), (ctypes.c_void_p * max(ng, 1))()
+        for j, key in enumerate(babies):
             kb[j], ps, cs = self._key_args(key, first_part)
-        pts = (ctypes.c_void_p * (len(blocks) * k_in))()
-        strides, counts, slots = [], [], []
+        for j, key in enumerate(giant_keys):
+            if key is not None:
+                gb[j], ps, cs = self._key_args(key, first_part)
+        pts = (ctypes.c_void_p * (k_out * k_in * ng))()
+        strides, counts, slots = [0] * (k_out * k_in * ng), [0] * (k_out * k_in * ng), []
         for o, row in enumerate(blocks):
             for i, blk in enumerate(row):
                 if blk is None:
-                    strides.append(0), counts.append(0)
                     continue
-                pack, sl = blk
-                pts[o * k_in + i] = pack.data_ptr()
-                strides.append(pack.stride(0)), counts.append(len(sl))
-                slots += list(sl)
-        return kb, ps, cs, (fmt.pop() if fmt else 0), pts, strides, counts, slots
+                pack, per_giant = blk
+                for j, part in enumerate([(0, per_giant)] if flat else per_giant):
+                    if part is None:
+                        continue
+                    first, sl = part
+                    e = (o * k_in + i) * ng + j
+                    pts[e] = pack.data_ptr() + first * pack.stride(0) * 8
+                    strides[e], counts[e] = pack.stride(0), len(sl)
+                    slots += list(sl)
+        i64 = lambda v: (ctypes.c_int64 * max(len(v), 1))(*v)
+        return ((i64([len(c) for c in col_keys]), i64([e for c in col_exps for e in c]), kb), (ng, i64(giant_exps), gb), ps, cs,
+                (fmt.pop() if fmt else 0), (pts, i64(strides), i64(counts), i64(slots)))
+
 
     # include/ckks_hip.h: LF_LT_MATMUL_BATCH_MAX_TOKENS through _native.py's copy (tests/test_lt_matmul_batch_cpu.py holds both to
     # the header); the group sizes lf_lt_matmul_batch takes beside 1
@@ -780,17 +800,9 @@ class HipBackend:
         may be None); outs: per token k_out tensors [2, ell - 1, N]; ws: at least lt_matmul_batch_ws_words(plan, the longest used
         column, k_out, nt) words; everything else as lt_matmul_native."""
         dev, st = _ds(outs[0][0])
-        nt, k_in, k_out = len(toks), len(toks[0]), len(blocks)
-        kb, ps, cs, fmt, pts, strides, counts, slots = self._lt_matmul_marshal("lt_matmul_batch_native", col_keys, first_part, blocks, k_in)
-        i64 = lambda v: (ctypes.c_int64 * max(len(v), 1))(*v)
-        inp = (ctypes.c_void_p * (nt * 2 * k_in))()
-        for t, ins in enumerate(toks):
-            for i, pair in enumerate(ins):
-                if pair is not None:
-                    inp[2 * (t * k_in + i)], inp[2 * (t * k_in + i) + 1] = pair[0].data_ptr(), pair[1].data_ptr()
-        check(lib.lf_lt_matmul_batch(ctypes.byref(plan), nt, k_in, k_out, inp, i64([len(c) for c in col_keys]),
-                                     i64([e for c in col_exps for e in c]), kb, ps, cs, row_off, fmt, pts, i64(strides), i64(counts),
-                                     i64(slots), _p(scales), round_at, _p(ws), ws.numel(), _parr([o[0] for tok in outs for o in tok]),
+        cols, _, ps, cs, fmt, blk = self._lt_matmul_marshal("lt_matmul_batch_native", col_exps, col_keys, None, first_part, blocks, len(toks[0]))
+        check(lib.lf_lt_matmul_batch(ctypes.byref(plan), len(toks), len(toks[0]), len(blocks), self._lt_matmul_inputs(toks), *cols, ps, cs,
+                                     row_off, fmt, *blk, _p(scales), round_at, _p(ws), ws.numel(), _parr([o[0] for tok in outs for o in tok]),
                                      _parr([o[1] for tok in outs for o in tok]), st),
               "lf_lt_matmul_batch")
 
@@ -812,50 +824,11 @@ class HipBackend:
         in (giant, baby) order, per giant step the index of its first diagonal in the pack and the column slot of each,
         ascending; outs: k_out tensors [2, ell - 1, N]; ws: at least lt_matmul_bsgs_ws_words(..) words."""
         dev, st = _ds(outs[0])
-        k_in, k_out, ng = len(ins), len(blocks), len(giant_keys)
-        kb, gb, ps, cs, fmt, pts, strides, counts, slots = self._lt_matmul_bsgs_marshal("lt_matmul_bsgs_native", col_keys, giant_keys,
-                                                                                        first_part, blocks, k_in)
-        i64 = lambda v: (ctypes.c_int64 * max(len(v), 1))(*v)
-        inp = (ctypes.c_void_p * (2 * k_in))()
-        for i, pair in enumerate(ins):
-            if pair is not None:
-                inp[2 * i], inp[2 * i + 1] = pair[0].data_ptr(), pair[1].data_ptr()
-        check(lib.lf_lt_matmul_bsgs(ctypes.byref(plan), k_in, k_out, inp, i64([len(c) for c in col_keys]),
-                                    i64([e for c in col_exps for e in c]), kb, ng, i64(giant_exps), gb, ps, cs, row_off,
-                                    fmt, pts, i64(strides), i64(counts), i64(slots), _p(scales), round_at, _p(ws),
-                                    ws.numel(), _parr([o[0] for o in outs]), _parr([o[1] for o in outs]), st), "lf_lt_matmul_bsgs")
-
-    def _lt_matmul_bsgs_marshal(self, name, col_keys, giant_keys, first_part, blocks, k_in):
-        """(baby key pointers, giant key pointers, part stride, component stride, key format, pack pointers, strides, counts,
-        slots): the keys and the blocks of lt_matmul_bsgs_native / lt_matmul_bsgs_batch_call as the C ABI takes them."""
-        k_out, ng = len(blocks), len(giant_keys)
-        babies = [k for col in col_keys for k in col]
-        fmt = {self._kfmt(k) for k in babies + [k for k in giant_keys if k is not None]}
-        if len(fmt) > 1:
-            raise ValueError(f"{name}: the keys of one call must share one format")
-        ps = cs = 0
-        kb, gb = (ctypes.c_void_p * max(len(babies), 1))(), (ctypes.c_void_p * max(ng, 1))()
-        for j, key in enumerate(babies):
-            kb[j], ps, cs = self._key_args(key, first_part)
-        for j, key in enumerate(giant_keys):
-            if key is not None:
-                gb[j], ps, cs = self._key_args(key, first_part)
-        pts = (ctypes.c_void_p * (k_out * k_in * ng))()
-        strides, counts, slots = [0] * (k_out * k_in * ng), [0] * (k_out * k_in * ng), []
-        for o, row in enumerate(blocks):
-            for i, blk in enumerate(row):
-                if blk is None:
-                    continue
-                pack, per_giant = blk
-                for j, part in enumerate(per_giant):
-                    if part is None:
-                        continue
-                    first, sl = part
-                    e = (o * k_in + i) * ng + j
-                    pts[e] = pack.data_ptr() + first * pack.stride(0) * 8
-                    strides[e], counts[e] = pack.stride(0), len(sl)
-                    slots += list(sl)
-        return kb, gb, ps, cs, (fmt.pop() if fmt else 0), pts, strides, counts, slots
+        cols, giants, ps, cs, fmt, blk = self._lt_matmul_marshal("lt_matmul_bsgs_native", col_exps, col_keys, (giant_exps, giant_keys),
+                                                                 first_part, blocks, len(ins))
+        check(lib.lf_lt_matmul_bsgs(ctypes.byref(plan), len(ins), len(blocks), self._lt_matmul_inputs([ins]), *cols, *giants, ps, cs, row_off,
+                                    fmt, *blk, _p(scales), round_at, _p(ws), ws.numel(), _parr([o[0] for o in outs]),
+                                    _parr([o[1] for o in outs]), st), "lf_lt_matmul_bsgs")
 
     # include/ckks_hip.h: LF_LT_MATMUL_BSGS_BATCH_MAX_TOKENS through _native.py's copy (tests/test_lt_matmul_bsgs_batch_cpu.py holds
     # both to the header); the group sizes lf_lt_matmul_bsgs_batch takes beside 1
@@ -875,18 +848,10 @@ class HipBackend:
         (The name: the engine's *_native entries are a closed list the fenced and the stream-contract suites go through one by one;
         this entry has tests of its own for both.)"""
         dev, st = _ds(outs[0][0])
-        nt, k_in, k_out, ng = len(toks), len(toks[0]), len(blocks), len(giant_keys)
-        kb, gb, ps, cs, fmt, pts, strides, counts, slots = self._lt_matmul_bsgs_marshal("lt_matmul_bsgs_batch_call", col_keys, giant_keys,
-                                                                                        first_part, blocks, k_in)
-        i64 = lambda v: (ctypes.c_int64 * max(len(v), 1))(*v)
-        inp = (ctypes.c_void_p * (nt * 2 * k_in))()
-        for t, ins in enumerate(toks):
-            for i, pair in enumerate(ins):
-                if pair is not None:
-                    inp[2 * (t * k_in + i)], inp[2 * (t * k_in + i) + 1] = pair[0].data_ptr(), pair[1].data_ptr()
-        check(lib.lf_lt_matmul_bsgs_batch(ctypes.byref(plan), nt, k_in, k_out, inp, i64([len(c) for c in col_keys]),
-                                          i64([e for c in col_exps for e in c]), kb, ng, i64(giant_exps), gb, ps, cs, row_off, fmt, pts,
-                                          i64(strides), i64(counts), i64(slots), _p(scales), round_at, _p(ws), ws.numel(),
+        cols, giants, ps, cs, fmt, blk = self._lt_matmul_marshal("lt_matmul_bsgs_batch_call", col_exps, col_keys, (giant_exps, giant_keys),
+                                                                 first_part, blocks, len(toks[0]))
+        check(lib.lf_lt_matmul_bsgs_batch(ctypes.byref(plan), len(toks), len(toks[0]), len(blocks), self._lt_matmul_inputs(toks), *cols,
+                                          *giants, ps, cs, row_off, fmt, *blk, _p(scales), round_at, _p(ws), ws.numel(),
                                           _parr([o[0] for tok in outs for o in tok]), _parr([o[1] for tok in outs for o in tok]), st),
               "lf_lt_matmul_bsgs_batch")
 

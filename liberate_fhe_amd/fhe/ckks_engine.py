@@ -2449,11 +2449,7 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMa
             return self._new(([out[0]], [out[1]]), types.origins["ct"], level=level + 1)
 
         # orchestrated: the same words through the engine's steps (see linear_transform's own orchestration for the pieces)
-        tabs = self._ks_tables(level)
-        loc = self._loc(level)
-        K, n = self.ntt.num_special_primes, self.ntt
-        forward = lambda d, digits: self._lt_forward(level, d, digits)
-        inner = lambda d, idx, key: self._lt_inner(level, d, idx, key)
+        loc, n = self._loc(level), self.ntt
 
         # baby steps: u^b per device, kept for every giant step
         c1 = [t if t.is_contiguous() else t.contiguous() for t in ct.data[1]]   # (the digit kernels take a raw pointer and a row pitch of N)
@@ -2462,24 +2458,17 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMa
         for i, d in enumerate(loc):
             li = self.local_ids.index(d)
             rows, ell = self._rows(d, level, True), self._rows(d, level, False)
-            cso, g2q = self._consts(d, level, False), self._vec("_2q", d, level, False)
-            dev = self.ntt.devices[d]
-            chat = torch.empty((2, ell, N), dtype=torch.int64, device=dev)
-            for comp in range(2):
-                src = ct.data[comp][i] if ct.data[comp][i].is_contiguous() else ct.data[comp][i].contiguous()
-                self.backend.galois(src, chat[comp], ell, logN, 1, g2q)
-                self.backend.ntt(chat[comp], 1, ell, logN, self._tw(d, level, False), self._vec("Rs", d, level, False), cso)
-                n.ops.mont_enter([chat[comp]], [self._PR(d, level)], *[x[li:li + 1] for x in n.mont_prepack[-1][level][0]])
+            chat = self._lt_chat(level, d, ct, i)
             ud = {}
             if 0 in babies:
-                ud[0] = torch.zeros((2, rows, N), dtype=torch.int64, device=dev)
+                ud[0] = torch.zeros((2, rows, N), dtype=torch.int64, device=self.ntt.devices[d])
                 ud[0][:, :ell] = chat
             if kb:
-                forward(d, digits)
+                self._lt_forward(level, d, digits)
                 _2q = n._2q_prepack[-2][level][0][li]
                 for b in kb:
                     idx = self._galois_index(encdec.galois_exponent(N, b), d)
-                    t = inner(d, idx, by_step[b])
+                    t = self._lt_inner(level, d, idx, by_step[b])
                     t[0, :ell] = n.ops.mont_add([t[0, :ell]], [chat[0].index_select(1, idx)], [_2q[:ell]])[0]
                     ud[b] = t
             u.append(ud)
@@ -2499,33 +2488,64 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMa
                         S[comp] = prod if S[comp] is None else n.ops.mont_add([S[comp]], [prod], _2q)[0]
                 Sg.append(S)
             if g:
-                w = []
-                for i, d in enumerate(loc):
-                    rows, ell = self._rows(d, level, True), self._rows(d, level, False)
-                    cs = self._consts(d, level, True)
-                    s1 = Sg[i][1].contiguous()
-                    self.backend.intt(s1, 1, rows, logN, self._tw(d, level, True, True), self._vec("Ninv", d, level, True), 2, cs)
-                    wd = torch.empty((ell, N), dtype=torch.int64, device=self.ntt.devices[d])
-                    ws, one = self._moddown_ws("ks_moddown_one_poly", 1, ell, K, d, tabs, cs)
-                    mkw = {"one_launch": True} if one else {}
-                    self.backend.ks_moddown_ws([s1], [wd], [None], ell, K, ws, tabs[("pir", d)], self._vec("Rs", d, level, True), cs,
-                                               PiP=tabs[("pip", d)], **mkw)
-                    w.append(wd)
-                digits = self._ks_digits_exchanged(w, level, galois=(1, True))
-                for i, d in enumerate(loc):
-                    li = self.local_ids.index(d)
-                    forward(d, digits)
-                    idx = self._galois_index(encdec.galois_exponent(N, g), d)
-                    v = inner(d, idx, by_step[g])
-                    v0 = n.ops.mont_add([v[0]], [Sg[i][0].index_select(1, idx)], [n._2q_prepack[-2][level][0][li]])[0]
-                    Sg[i] = [v0, v[1]]
+                Sg = self._lt_giant(level, Sg, g, by_step[g])
             for i, d in enumerate(loc):
                 _2q = [n._2q_prepack[-2][level][0][self.local_ids.index(d)]]
                 for comp in range(2):
                     A[i][comp] = Sg[i][comp] if A[i][comp] is None else n.ops.mont_add([A[i][comp]], [Sg[i][comp]], _2q)[0]
+        return self._lt_tail(level, A)
 
-        c0o, c1o = [], []
+    def _lt_chat(self, level, d, ct, di):
+        """c^0, c^1 = P * enter_ntt(canonical c) on the ordinary rows of device d, the di-th of the level: a fresh [2, ell, N]"""
+        N, logN, n = self.ctx.N, self.ctx.logN, self.ntt
+        li = self.local_ids.index(d)
+        ell = self._rows(d, level, False)
+        cso, g2q = self._consts(d, level, False), self._vec("_2q", d, level, False)
+        chat = torch.empty((2, ell, N), dtype=torch.int64, device=self.ntt.devices[d])
+        for comp in range(2):
+            src = ct.data[comp][di] if ct.data[comp][di].is_contiguous() else ct.data[comp][di].contiguous()
+            self.backend.galois(src, chat[comp], ell, logN, 1, g2q)
+            self.backend.ntt(chat[comp], 1, ell, logN, self._tw(d, level, False), self._vec("Rs", d, level, False), cso)
+            n.ops.mont_enter([chat[comp]], [self._PR(d, level)], *[x[li:li + 1] for x in n.mont_prepack[-1][level][0]])
+        return chat
+
+    def _lt_giant(self, level, Sg, g, key):
+        """The giant step g != 0 of one inner sum Sg (per device [S_0, S_1], in Q P): w = mod-down of intt_exit_reduce(S_1), its
+        digits exchanged, extended and transformed, v_c = their inner product with `key` gathered by pi_g, v_0 += S_0 gathered on
+        all rows; per device [v_0, v_1]"""
+        N, logN = self.ctx.N, self.ctx.logN
+        tabs, loc = self._ks_tables(level), self._loc(level)
+        K, n = self.ntt.num_special_primes, self.ntt
+        w = []
         for i, d in enumerate(loc):
+            rows, ell = self._rows(d, level, True), self._rows(d, level, False)
+            cs = self._consts(d, level, True)
+            s1 = Sg[i][1].contiguous()
+            self.backend.intt(s1, 1, rows, logN, self._tw(d, level, True, True), self._vec("Ninv", d, level, True), 2, cs)
+            wd = torch.empty((ell, N), dtype=torch.int64, device=self.ntt.devices[d])
+            ws, one = self._moddown_ws("ks_moddown_one_poly", 1, ell, K, d, tabs, cs)
+            mkw = {"one_launch": True} if one else {}
+            self.backend.ks_moddown_ws([s1], [wd], [None], ell, K, ws, tabs[("pir", d)], self._vec("Rs", d, level, True), cs,
+                                       PiP=tabs[("pip", d)], **mkw)
+            w.append(wd)
+        digits = self._ks_digits_exchanged(w, level, galois=(1, True))
+        out = []
+        for i, d in enumerate(loc):
+            li = self.local_ids.index(d)
+            self._lt_forward(level, d, digits)
+            idx = self._galois_index(encdec.galois_exponent(N, g), d)
+            v = self._lt_inner(level, d, idx, key)
+            v0 = n.ops.mont_add([v[0]], [Sg[i][0].index_select(1, idx)], [n._2q_prepack[-2][level][0][li]])[0]
+            out.append([v0, v[1]])
+        return out
+
+    def _lt_tail(self, level, A):
+        """The ciphertext at level + 1 of one accumulator A (per device [A_0, A_1], in Q P): stacked, ONE exact inverse NTT
+        (intt_exit_reduce), mod-down without addend, rescale"""
+        N, logN = self.ctx.N, self.ctx.logN
+        tabs, K = self._ks_tables(level), self.ntt.num_special_primes
+        c0o, c1o = [], []
+        for i, d in enumerate(self._loc(level)):
             rows, ell = self._rows(d, level, True), self._rows(d, level, False)
             cs = self._consts(d, level, True)
             s2 = torch.stack(A[i]).contiguous()
@@ -2540,7 +2560,7 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMa
 
     def _lt_forward(self, level, d, digits):
         """extension + forward NTT of the exchanged digits on device d, kept aside in the buffer the keys gather from (the shared
-        half of the orchestrated baby-step / giant-step forms: _linear_transform_bsgs, _lt_matmul_bsgs_steps)"""
+        half of the orchestrated baby-step / giant-step forms: _linear_transform_bsgs, _lt_matmul_steps)"""
         N, logN = self.ctx.N, self.ctx.logN
         tabs = self._ks_tables(level)
         nparts = len(tabs["order"])

@@ -115,9 +115,9 @@ def test_refusals_come_before_anything_is_computed(checker, monkeypatch):
             raise AssertionError(name + " reached")
         return f
 
-    for name in ("lt_matmul_bsgs", "linear_transform", "encode_diagonals", "_lt_matmul_bsgs_native", "_lt_matmul_bsgs_batch_native",
-                 "_lt_matmul_bsgs_native_args", "_lt_matmul_bsgs_steps", "_lt_matmul_native", "_lt_matmul_steps", "rescale", "clone", "_ws",
-                 "_op_plan", "_ks_tables", "_ks_digits_exchanged", "_diag_pack", "_key_pack", "_lt_forward", "_lt_inner"):
+    for name in ("lt_matmul_bsgs", "linear_transform", "encode_diagonals", "_lt_matmul_encode", "_lt_matmul_native_args",
+                 "_lt_matmul_native", "_lt_matmul_steps", "rescale", "clone", "_ws", "_op_plan", "_ks_tables", "_ks_digits_exchanged",
+                 "_diag_pack", "_key_pack", "_lt_chat", "_lt_forward", "_lt_inner", "_lt_giant", "_lt_tail"):
         monkeypatch.setattr(eng, name, boom(name))
     for name in ("lt_matmul_bsgs_native", "lt_matmul_bsgs_batch_call", "lt_matmul_bsgs_ws_words", "lt_matmul_bsgs_batch_ws_words",
                  "lt_matmul_native", "galois", "ntt", "intt", "ks_fwd", "ks_tail", "ks_inner", "ks_moddown_ws"):

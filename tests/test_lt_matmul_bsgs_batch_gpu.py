@@ -420,6 +420,43 @@ def test_the_op_on_another_stream_waits_for_the_lanes_previous_op(lt_engine):
     assert all_same(rb, want)
 
 
+@pytest.mark.parametrize("last", [False, True], ids=["level0", "last"])
+def test_one_token_through_the_batch_bindings_gives_the_single_bindings_words(last):
+    """nt = 1 of the family's one body: ONE token through lt_matmul_batch_native and through lt_matmul_bsgs_batch_call against the
+    single bindings lt_matmul_native and lt_matmul_bsgs_native, every word, on a fresh engine under tests.helpers.Fence with every
+    bit set in scratch and outputs.  2 x 3: the 2 x 2 matrix with one None block beside an input no block uses; level 0 and the
+    last level the ops take (the results still have ell = 2).  The engine's drivers send one token to the single bindings, so the
+    batch bindings are reached through _lt_matmul_native here."""
+    from liberate_fhe_amd.fhe import ckks_engine
+    eng = ckks_engine(devices=["cuda:0"], **LT)
+    fence = Fence(eng, FENCE_FILLS["ones"])
+    real = getattr(eng.backend, ENTRY)
+    setattr(eng.backend, ENTRY, fence._fenced_entry(ENTRY, real, inspect.signature(real)))
+    level = eng.num_levels - 2 if last else 0
+    d = eng._native_level(level)
+    assert d is not None and eng._rows(d, level + 1, False) >= 2 and (not last or level + 2 == eng.num_levels)
+    keys = keys_for(eng)
+    cts = tokens(eng, level, 3, 1)[0]
+    layouts = {"lt_matmul": ([[(0, 1, 3), None, None], [(2,), (0, 1), None]], eng.num_slots),
+               "lt_matmul_bsgs": ([[(0, 1, 4, 6), None, None], [(5,), (0, 3, 8), None]], N1)}
+    entries = {"lt_matmul": ("lt_matmul_native", "lt_matmul_batch_native"), "lt_matmul_bsgs": ("lt_matmul_bsgs_native", ENTRY)}
+    for name, (layout, n1) in layouts.items():
+        W = [[None if st is None else synth.diagonals(eng, 7 + 8 * o + i, level, st) if name == "lt_matmul" else
+              synth.diagonals_bsgs(eng, 7 + 8 * o + i, level, st, n1) for i, st in enumerate(row)] for o, row in enumerate(layout)]
+        steps = [[None if b is None else eng.diagonal_steps(b) for b in row] for row in W]
+        got = {}
+        for batch in (False, True):
+            fence.refill()
+            del fence.calls[:], fence.never_written[:]
+            out = eng._lt_matmul_native(name, W, steps, n1, [cts], keys, level, d, batch=batch)
+            fence.check()
+            assert fence.calls == [entries[name][batch]], (name, batch, fence.calls)
+            assert not fence.never_written, (name, batch, fence.never_written)
+            assert len(out) == 1 and len(out[0]) == 2 and all(o.level == level + 1 for o in out[0])
+            got[batch] = [w for o in out[0] for w in words(o)]
+        assert all(torch.equal(a, b) for a, b in zip(got[False], got[True])), (name, level)
+
+
 def test_block_matrix_times_three_token_vectors_with_real_keys():
     """logN 13, real keys: 2 x 2 blocks from random 8 x 8 block-diagonal matrices (15 diagonals, steps -7 .. 7, n1 = 4), three token
     vectors of two fresh ciphertexts.  The words are the loop's; the decryption error against the plain product is printed and held

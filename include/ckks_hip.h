@@ -962,6 +962,34 @@ int lf_weighted_sums(const int64_t *const *in, const int64_t *const *row0, int64
                      const int64_t *tab, const int64_t *consts, const int64_t *scales, int64_t round_at, const int64_t *ql,
                      const int64_t *qh, const int64_t *kl, const int64_t *kh, int device, void *stream);
 
+/* A sum of ciphertexts that stand at different levels, brought to ONE level L (a residual connection, the corrections of a
+ * Chebyshev recurrence, level_up itself): for each of nsets sets, out_s = sum_{t < k_s} s_t u_t (+ a constant), where u_t is
+ * ct_t itself if it stands at L and level_up(ct_t, L) if it stands above it (level l < L: one rescale, the rows of L kept, times
+ * level_up's integer delta).  ONE launch for all sets and both components; every surviving input word is read once, every
+ * output word written once.
+ * k: HOST array of nsets term counts.  The per-term arrays are HOST arrays packed set after set, term after term (n = sum k_s
+ * terms in all): in / row0 hold 2 n device pointers, [term][component]: the first row of ct_t.c0, ct_t.c1 that survives at L
+ * ([rows][N]; L - l rows into a tensor at level l) and the dropped row (the tensor's first row), NULL for a term at L; scales
+ * holds n device pointers: the term's rescale constants of the rows at L (the tail of lf_rescale_batch's table at level l), NULL
+ * for a term at L; round_at holds n words, as lf_rescale_batch takes it (ignored for a term at L).  Input words are lazy words
+ * in [0, 2q) or what a rescale leaves; the same polynomial may appear any number of times.
+ * tab: HOST array of nsets device pointers, each a DEVICE table [k_s][rows] of s_t R^2 mod q_row (a term at L) or
+ * s_t delta_t R^2 mod q_row (a levelled one), R = 2^62: the kernel sums word * tab in 128 bits and reduces twice.  consts: NULL,
+ * or a HOST array of nsets device pointers, each NULL or a DEVICE table [rows] of plain residues added to coefficient 0 of
+ * component 0.  out: HOST array of 2 nsets device pointers, [set][component], [rows][N] each, canonical.  rows = limbs of level
+ * L; ql .. kh hold its rows entries.
+ * The result has exactly the words of ckks_engine's
+ *     u_t = ct_t or level_up(ct_t, L);  v_t = u_t or mult_int_scalar(u_t, s_t);  acc = v_0;  acc = cc_add(acc, v_t);  add_scalar
+ * for every prime below 2^60 (a single term with s = 1 at L is a copy: the engine refuses it).
+ * LF_ERR_ARG before any device call for nsets < 1 or > LF_LSUM_MAX_SETS, a k_s < 1 or > LF_LSUM_MAX_TERMS, rows < 0 or
+ * > lf_limits(LF_LIMIT_ROWS), logN outside 13 .. 17, a NULL among k / in / row0 / scales / round_at / tab / out / ql .. kh, among
+ * the entries of in, tab and out, and a term whose two dropped rows and scales are not all NULL or all given. */
+#define LF_LSUM_MAX_TERMS 8
+#define LF_LSUM_MAX_SETS 8
+int lf_level_sum(int nsets, const int64_t *k, const int64_t *const *in, const int64_t *const *row0, const int64_t *const *scales,
+                 const int64_t *round_at, const int64_t *const *tab, const int64_t *const *consts, int64_t *const *out, int rows,
+                 int logN, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, int device, void *stream);
+
 /* Sum of plaintext-ciphertext products under ONE rescale, for plaintexts encoded once (ckks_engine.encode_plain): out decrypts to
  * sum_i pt_i * ct_i (+ bias), level l -> l + 1.  Plan-free: no key, no digits.
  * k >= 1 terms; in: HOST array of 2 k device pointers, [term][component]: ct_i.c0, ct_i.c1, each [rows][N] at level l (all its

@@ -147,6 +147,92 @@ __global__ void __launch_bounds__(256) weighted_sums_kernel(WsumBatch pb, int k,
     }
 }
 
+// ---- sums of ciphertexts at mixed levels (levelsum.py: level_sum, level_up; no counterpart in the reference) ----------------------
+// out_s = sum_t s_t * u_t [+ const_s on coefficient 0 of component 0] at level L, for up to LF_LSUM_MAX_SETS sets per launch
+// (blockIdx.z = 2 set + component).  u_t is the operand itself where it stands at L already, and level_up(ct_t, L) where it
+// stands at l < L: with y = rescale_kernel's word on the thread's row and the dropped row, word for word,
+//     y = reduce_q( REDC((x - z) * scales_r) + [z > round_at] ),
+// level_up leaves reduce_2q(REDC(y * delta R)), the canonical residue of delta * y.  The composition that defines the words
+// (level_up, mult_int_scalar, cc_add, add_scalar) ends every step in reduce_2q, so each output word is the canonical residue of
+// sum_t s_t u_t on its row: behind y a function of residues alone, formed here with ONE reduction, as weighted_sums_kernel does:
+//     w_t = y (a levelled term) or x_t (a term at L), taken with its residue in [0, 2q): REDC of a negative product leaves a
+//           word in (-q/2, 0) about once in 2^22 words, which enters as w + q;
+//     F_t = s_t [delta_t] R^2 mod q < q, one table entry per set, term and row;
+//     X = sum_t w_t * F_t  in 128 bits:  X < k * 2q * q <= 8 * 2^61 * 2^60 = 2^124 for q < 2^60 (the engine takes the
+//         composition for a larger prime), inside wsum_canon's range (X < 2^125, the comment above weighted_sums_kernel);
+//     wsum_canon(X) = X R^-2 mod q in [0, q), then the const's residue and one conditional subtraction.
+// One block walks LSUM_ROWS rows of a column pair: the dropped rows' words (re-read by every row of a column) are loaded once
+// per LSUM_ROWS rows and kept in registers; every surviving word is read once per launch, every output word written once.
+// KT = the term slots kept in registers (1, 2, 4, 8: the launch takes the smallest that holds every set's count).
+#define LSUM_ROWS 4
+struct LsumBatch {
+    const i64 *in[2 * LF_LSUM_MAX_SETS * LF_LSUM_MAX_TERMS];     // [set][term][component]: first row that survives at L
+    const i64 *row0[2 * LF_LSUM_MAX_SETS * LF_LSUM_MAX_TERMS];   // [set][term][component]: the dropped row, NULL for a term at L
+    const i64 *scales[LF_LSUM_MAX_SETS * LF_LSUM_MAX_TERMS];     // [set][term]: the term's rescale constants of the rows at L
+    i64 round_at[LF_LSUM_MAX_SETS * LF_LSUM_MAX_TERMS];
+    const i64 *tab[LF_LSUM_MAX_SETS];                            // [term][rows] of the set
+    const i64 *cst[LF_LSUM_MAX_SETS];                            // NULL or [rows]
+    i64 *out[2 * LF_LSUM_MAX_SETS];                              // [set][component]
+    int k[LF_LSUM_MAX_SETS];
+};
+
+template <int KT>
+__global__ void __launch_bounds__(256) level_sum_kernel(LsumBatch pb, int rows, i64 N, const i64 *__restrict__ ql,
+                                                        const i64 *__restrict__ qh, const i64 *__restrict__ kl,
+                                                        const i64 *__restrict__ kh) {
+    const int set = blockIdx.z >> 1, c = blockIdx.z & 1;
+    const i64 j = ((i64)blockIdx.x * 256 + threadIdx.x) * 2;
+    if (j >= N) return;
+    const int k = pb.k[set];
+    const int base = set * LF_LSUM_MAX_TERMS;
+    const i64 *__restrict__ tab = pb.tab[set];
+    const i64 *__restrict__ cst = pb.cst[set];
+    i64 *__restrict__ out = pb.out[2 * set + c];
+    longlong2 z[KT];
+#pragma unroll
+    for (int t = 0; t < KT; ++t) {
+        z[t].x = z[t].y = 0;
+        if (t < k) {
+            const i64 *r0 = pb.row0[2 * (base + t) + c];
+            if (r0) z[t] = *reinterpret_cast<const longlong2 *>(r0 + j);
+        }
+    }
+    const int r0 = blockIdx.y * LSUM_ROWS;
+    const int r1 = r0 + LSUM_ROWS < rows ? r0 + LSUM_ROWS : rows;
+    for (int r = r0; r < r1; ++r) {
+        const RowMod m = load_mod(ql, qh, kl, kh, r);
+        const i64 off = (i64)r * N + j;
+        u128 a0 = 0, a1 = 0;
+#pragma unroll
+        for (int t = 0; t < KT; ++t) {
+            if (t < k) {
+                longlong2 w = *reinterpret_cast<const longlong2 *>(pb.in[2 * (base + t) + c] + off);
+                const i64 *sc = pb.scales[base + t];
+                if (sc) {   // rescale_kernel on (w, z[t]), word for word
+                    const i64 s = sc[r], ra = pb.round_at[base + t];
+                    i64 v = mm62s(w.x - z[t].x, s, m.q, m.k) + (i64)(z[t].x > ra);
+                    w.x = v < (i64)m.q ? v : v - (i64)m.q;
+                    v = mm62s(w.y - z[t].y, s, m.q, m.k) + (i64)(z[t].y > ra);
+                    w.y = v < (i64)m.q ? v : v - (i64)m.q;
+                }
+                w.x += (w.x >> 63) & (i64)m.q;
+                w.y += (w.y >> 63) & (i64)m.q;
+                const u64 f = (u64)tab[(i64)t * rows + r];
+                a0 += (u128)(u64)w.x * f;
+                a1 += (u128)(u64)w.y * f;
+            }
+        }
+        longlong2 o;
+        o.x = wsum_canon(a0, m.q, m.k);
+        o.y = wsum_canon(a1, m.q, m.k);
+        if (cst && c == 0 && j == 0) {   // add_scalar: the const's residue on coefficient 0 of c0, one reduction
+            const i64 v = o.x + cst[r];
+            o.x = v < (i64)m.q ? v : v - (i64)m.q;
+        }
+        *reinterpret_cast<longlong2 *>(out + off) = o;
+    }
+}
+
 // ---- tensor product (ckks_engine.py:1095-1101) ---------------------------------------------------
 __global__ void __launch_bounds__(256) tensor_kernel(const i64 *__restrict__ x0, const i64 *__restrict__ x1,
                                                      const i64 *__restrict__ y0, const i64 *__restrict__ y1,
@@ -665,6 +751,59 @@ int lf_weighted_sums(const int64_t *const *in, const int64_t *const *row0, int64
         g0 += n;
     }
     return 0;
+}
+
+int lf_level_sum(int nsets, const int64_t *k, const int64_t *const *in, const int64_t *const *row0, const int64_t *const *scales,
+                 const int64_t *round_at, const int64_t *const *tab, const int64_t *const *consts, int64_t *const *out, int rows,
+                 int logN, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, int device, void *stream) {
+    if (nsets < 1 || nsets > LF_LSUM_MAX_SETS || rows < 0 || rows > MAX_LIST_ROWS) return LF_ERR_ARG;
+    if (logN < 13 || logN > KS_LOGN_MAX) return LF_ERR_ARG;
+    if (!k || !in || !row0 || !scales || !round_at || !tab || !out || !ql || !qh || !kl || !kh) return LF_ERR_ARG;
+    LsumBatch pb;
+    int kmax = 0, n = 0;
+    for (int s = 0; s < nsets; ++s) {
+        if (k[s] < 1 || k[s] > LF_LSUM_MAX_TERMS || !tab[s] || !out[2 * s] || !out[2 * s + 1]) return LF_ERR_ARG;
+        for (int t = 0; t < LF_LSUM_MAX_TERMS; ++t) {
+            const int at = s * LF_LSUM_MAX_TERMS + t;
+            const bool live = t < (int)k[s];
+            if (live) {
+                if (!in[2 * n] || !in[2 * n + 1]) return LF_ERR_ARG;
+                // a levelled term has both dropped rows and its rescale constants, a term at L none of the three
+                if ((row0[2 * n] != nullptr) != (scales[n] != nullptr) || (row0[2 * n + 1] != nullptr) != (scales[n] != nullptr))
+                    return LF_ERR_ARG;
+            }
+            for (int c = 0; c < 2; ++c) {
+                pb.in[2 * at + c] = live ? (const i64 *)in[2 * n + c] : nullptr;
+                pb.row0[2 * at + c] = live ? (const i64 *)row0[2 * n + c] : nullptr;
+            }
+            pb.scales[at] = live ? (const i64 *)scales[n] : nullptr;
+            pb.round_at[at] = live ? (i64)round_at[n] : 0;
+            n += live;
+        }
+        pb.tab[s] = (const i64 *)tab[s];
+        pb.cst[s] = consts ? (const i64 *)consts[s] : nullptr;
+        pb.out[2 * s] = (i64 *)out[2 * s], pb.out[2 * s + 1] = (i64 *)out[2 * s + 1];
+        pb.k[s] = (int)k[s];
+        kmax = (int)k[s] > kmax ? (int)k[s] : kmax;
+    }
+    for (int s = nsets; s < LF_LSUM_MAX_SETS; ++s) {
+        for (int i = 2 * s * LF_LSUM_MAX_TERMS; i < 2 * (s + 1) * LF_LSUM_MAX_TERMS; ++i) pb.in[i] = pb.row0[i] = nullptr;
+        for (int i = s * LF_LSUM_MAX_TERMS; i < (s + 1) * LF_LSUM_MAX_TERMS; ++i) pb.scales[i] = nullptr, pb.round_at[i] = 0;
+        pb.tab[s] = pb.cst[s] = nullptr, pb.out[2 * s] = pb.out[2 * s + 1] = nullptr, pb.k[s] = 0;
+    }
+    if (rows == 0) return 0;
+    if (int e = lf_set_device(device)) return e;
+    const i64 N = (i64)1 << logN;
+    dim3 grid((unsigned)((N / 2 + 255) / 256), (unsigned)((rows + LSUM_ROWS - 1) / LSUM_ROWS), 2u * (unsigned)nsets);
+#define LF_LSUM_LAUNCH(KT)                                                                                                  \
+    hipLaunchKernelGGL((level_sum_kernel<KT>), grid, dim3(256), 0, (hipStream_t)stream, pb, rows, N, (const i64 *)ql,        \
+                       (const i64 *)qh, (const i64 *)kl, (const i64 *)kh)
+    if (kmax == 1) LF_LSUM_LAUNCH(1);
+    else if (kmax == 2) LF_LSUM_LAUNCH(2);
+    else if (kmax <= 4) LF_LSUM_LAUNCH(4);
+    else LF_LSUM_LAUNCH(8);
+#undef LF_LSUM_LAUNCH
+    return (int)hipGetLastError();
 }
 
 int lf_tensor(const int64_t *x0, const int64_t *x1, const int64_t *y0, const int64_t *y1, int64_t *d0, int64_t *d1,

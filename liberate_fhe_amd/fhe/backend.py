@@ -466,6 +466,42 @@ class HipBackend:
         check(lib.lf_weighted_sums(ins, row0s, _parr(outs), k, G, rows, logN, _p(tab), _p(consts), _p(scales), round_at, *c.mont(),
                                    dev, st), "lf_weighted_sums")
 
+    # include/ckks_hip.h: LF_LSUM_MAX_TERMS / LF_LSUM_MAX_SETS (tests/test_level_sum_cpu.py holds these copies to the header)
+    lsum_max_terms = 8
+    lsum_max_sets = 8
+
+    def level_sum_call(self, sets, outs, rows, logN, c: Consts):
+        """len(sets) <= lsum_max_sets sums of ciphertexts brought to ONE level as ONE native call (lf_level_sum).  sets: one
+        (terms, tab, const) per sum; terms: up to lsum_max_terms entries (c0, c1, skip, scales, round_at) — the term's two
+        component tensors, the rows of them that do not survive at the target level (0: the term stands there) and, for
+        skip >= 1, the rescale constants of the term's level (skip - 1 entries ahead of those of the target's rows) and its
+        rounding threshold, None and 0 otherwise; tab [len(terms), rows] and const ([rows] or None) device tables.  outs: one pair
+        of [rows, N] tensors per set; c: the constants of the target level (rows entries)."""
+        dev, st = _ds(outs[0][0])
+        N = outs[0][0].size(-1)
+        n = sum(len(terms) for terms, _, _ in sets)
+        ks = (ctypes.c_int64 * len(sets))(*[len(terms) for terms, _, _ in sets])
+        ins, row0s = (ctypes.c_void_p * (2 * n))(), (ctypes.c_void_p * (2 * n))()
+        scs, ras = (ctypes.c_void_p * n)(), (ctypes.c_int64 * n)()
+        i = 0
+        for terms, _, _ in sets:
+            for c0, c1, skip, scales, round_at in terms:
+                if (skip == 0) != (scales is None) or skip < 0 or c0.size(0) != rows + skip or c1.size(0) != rows + skip:
+                    raise ValueError("HipBackend.level_sum_call: a term's rows, skipped rows and rescale constants disagree")
+                for comp, t in enumerate((c0, c1)):
+                    ptr = _p(t)
+                    ins[2 * i + comp] = ptr + skip * N * 8
+                    row0s[2 * i + comp] = ptr if skip else None     # the dropped limb is the tensor's first row
+                if skip:
+                    if scales.numel() != rows + skip - 1:
+                        raise ValueError("HipBackend.level_sum_call: rescale constants of another level than the term's")
+                    scs[i] = _p(scales) + (skip - 1) * 8
+                ras[i] = round_at
+                i += 1
+        check(lib.lf_level_sum(len(sets), ks, ins, row0s, scs, ras, _parr([tab for _, tab, _ in sets]),
+                               _parr([cst for _, _, cst in sets]), _parr([o for pair in outs for o in pair]), rows, logN, *c.mont(),
+                               dev, st), "lf_level_sum")
+
     @staticmethod
     def pc_dot_ws_words(k, rows, logN):
         return int(lib.lf_pc_dot_ws_words(k, rows, logN))

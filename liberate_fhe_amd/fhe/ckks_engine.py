@@ -43,6 +43,7 @@ from .ltmatmul import LtMatmulOps
 from .plainops import PlainOps
 from .polyeval import PolyOps
 from .presets import errors, types
+from .levelsum import LevelSumOps
 from .slotsum import SlotSumOps
 from .version import VERSION
 
@@ -82,7 +83,7 @@ class _OneShard:
         return ckks_engine._decrypt_rows_on(self, ct, sk, self.li, self.dev)
 
 
-class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMatmulOps):
+class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMatmulOps, LevelSumOps):
     @errors.log_error
     def __init__(self, devices: list[int] = None, verbose: bool = False, bias_guard: bool = True,
                  norm: str = "forward", backend=None, comm=None, balanced_limb_map: bool = False, **ctx_params):
@@ -143,6 +144,7 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMa
         self.galois_deltas = [2 ** i for i in range(self.ctx.logN - 1)]
         self._tables = {}
         self._wsum_tables = OrderedDict()   # polyeval.py: device tables of weighted_sums' integers, least recently used of 64 dropped
+        self._lsum_tables = OrderedDict()   # levelsum.py: device tables of level_sum's folded integers, least recently used of 256 dropped
         self._scalar_rows = OrderedDict()   # evaluator.py: _row_scalars' device vectors, least recently used of 256 dropped
         self._key_packs = {}
         self._workspace = {}
@@ -253,8 +255,9 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMa
     def _enter(self):
         """First line of every public op that uses engine scratch or a key, and of rescale, pc_mult and pc_add: _same_stream on
         every local device, BEFORE the op reads engine state or launches anything (an op that orders itself only when it first
-        asks for scratch has launched on its operands by then).  The element-wise ops without scratch (cc_add, cc_sub, level_up,
-        negate, the scalar ops, mc_mult, mc_add, encrypt, decrypt) do not call it: their operands are the caller's to order."""
+        asks for scratch has launched on its operands by then).  level_sum, its batches and the native level_up call it too (they
+        read the engine's cached tables).  The element-wise ops without scratch (cc_add, cc_sub, negate, the scalar ops, mc_mult,
+        mc_add, encrypt, decrypt) do not call it: their operands are the caller's to order."""
         for d in self.local_ids:
             self._same_stream(d)
 
@@ -2887,6 +2890,9 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMa
     def level_up(self, ct: data_struct, dst_level: int):
         if types.origins["ct"] != ct.origin:
             raise errors.NotMatchType(origin=ct.origin, to=types.origins["ct"])
+        out = self._level_up_native(ct, dst_level)    # levelsum.py: one launch, the rows of dst_level only; None: the chain below
+        if out is not None:
+            return out
         new_ct = self.rescale(ct)
         src_level = ct.level + 1
         delta = round(self.scale * (self.deviations[dst_level] / np.sqrt(self.deviations[src_level])))

@@ -157,7 +157,7 @@ class PolyOps:
         hi = 1
         while 2 * hi <= top:
             sq = self.square(powers[hi], evk)
-            powers[2 * hi] = self.add_scalar(self.mult_int_scalar(sq, 2), -1) if cheb else sq
+            powers[2 * hi] = self.level_sum([(sq, 2)], const=-1) if cheb else sq
             hi *= 2
         hi = 2
         while hi < top:
@@ -166,12 +166,22 @@ class PolyOps:
                 pairs = [self.auto_level(powers[hi], powers[lo]) for lo in los]
                 prods = self.cc_mult_batch(pairs, evk) if len(pairs) > 1 else [self.cc_mult(pairs[0][0], pairs[0][1], evk)]
                 for lo, p in zip(los, prods):
-                    powers[hi + lo] = self.auto_cc_sub(self.mult_int_scalar(p, 2), powers[hi - lo]) if cheb else p
+                    powers[hi + lo] = self.level_sum([(p, 2), (powers[hi - lo], -1)]) if cheb else p
             hi *= 2
         return powers
 
-    def _at_level(self, ct, level):
-        return ct if ct.level == level else self.level_up(ct, level)
+    def _at_level(self, cts, level):
+        """[ct if ct.level == level else level_up(ct, level) for ct in cts]: the level_ups as ONE level_up_batch"""
+        cts = list(cts)
+        low = [i for i, ct in enumerate(cts) if ct.level != level]
+        for i, up in zip(low, self.level_up_batch([cts[i] for i in low], level) if low else []):
+            cts[i] = up
+        return cts
+
+    # The glue between the products goes through level_sum (levelsum.py), whose words are those of the chains the docstrings
+    # below write out: add_scalar(mult_int_scalar(sq, 2), -1) = level_sum([(sq, 2)], const=-1);
+    # auto_cc_sub(mult_int_scalar(prod, 2), p) = level_sum([(prod, 2), (p, -1)]) (prod stands deeper than p, and both forms leave
+    # the canonical residue of 2 prod - level_up(p)); cc_add(r, level_up(q_0, L)) = level_sum([(r, 1), (q_0, 1)]).
 
     def _power_tree_batch(self, trees: list, top: int, evk, cheb: bool):
         """_power_tree on one dictionary per ciphertext, walked once: the squares of a step, and the products of one hi, of ALL
@@ -179,18 +189,22 @@ class PolyOps:
         hi = 1
         while 2 * hi <= top:
             sqs = self.cc_mult_batch([(t[hi], t[hi]) for t in trees], evk)
+            if cheb:
+                sqs = self.level_sum_batch([([(sq, 2)], -1) for sq in sqs])
             for t, sq in zip(trees, sqs):
-                t[2 * hi] = self.add_scalar(self.mult_int_scalar(sq, 2), -1) if cheb else sq
+                t[2 * hi] = sq
             hi *= 2
         hi = 2
         while hi < top:
             los = [b - hi for b in range(hi + 1, min(2 * hi, top + 1))]
             if los:
                 prods = self.cc_mult_batch([self.auto_level(t[hi], t[lo]) for t in trees for lo in los], evk)
+                if cheb:
+                    prods = self.level_sum_batch([([(prods[i * len(los) + j], 2), (t[hi - lo], -1)], None)
+                                                  for i, t in enumerate(trees) for j, lo in enumerate(los)])
                 for i, t in enumerate(trees):
                     for j, lo in enumerate(los):
-                        p = prods[i * len(los) + j]
-                        t[hi + lo] = self.auto_cc_sub(self.mult_int_scalar(p, 2), t[hi - lo]) if cheb else p
+                        t[hi + lo] = prods[i * len(los) + j]
             hi *= 2
         return trees
 
@@ -237,18 +251,19 @@ class PolyOps:
         base = ct.level
         powers = self._power_tree({1: ct}, n1 - 1, evk, cheb)
         Lb = base + sched["baby"]
-        babies = [self._at_level(powers[b], Lb) for b in range(1, n1)]
+        babies = self._at_level([powers[b] for b in range(1, n1)], Lb)
         q = self.weighted_sums(babies, blocks[:, 1:], consts=blocks[:, 0])
         if G == 1:
             return q[0]
         half = powers[n1 // 2]
         y = self.square(half, evk)
         if cheb:
-            y = self.add_scalar(self.mult_int_scalar(y, 2), -1)
+            y = self.level_sum([(y, 2)], const=-1)
         ys = self._power_tree({1: y}, G - 1, evk, False)
         Lc = base + sched["common"]
-        r = self.cc_dot([(self._at_level(q[g], Lc), self._at_level(ys[g], Lc)) for g in range(1, G)], evk)
-        return self.cc_add(r, self.level_up(q[0], Lc + 1))
+        ups = self._at_level([q[g] for g in range(1, G)] + [ys[g] for g in range(1, G)], Lc)
+        r = self.cc_dot(list(zip(ups[:G - 1], ups[G - 1:])), evk)
+        return self.level_sum([(r, 1), (q[0], 1)])
 
     def poly_eval_batch(self, cts: list, coeffs, evk, basis="power", interval=None, n1=None) -> list:
         """The same polynomial on B ciphertexts of one level (an activation over a layer's outputs): returns
@@ -256,11 +271,11 @@ class PolyOps:
         ciphertexts, so that the key is streamed once per group of up to 4 ciphertexts instead of once per ciphertext:
           chebyshev, interval != (-1, 1):  the change of variable per ciphertext, as poly_eval makes it
           babies: every square p_2h = square(p_h) of all B ciphertexts in ONE cc_mult_batch per step h, every product
-              p_hi * p_{b - hi} of one hi of all B ciphertexts in ONE cc_mult_batch; the Chebyshev corrections and the level_ups per
-              ciphertext
+              p_hi * p_{b - hi} of one hi of all B ciphertexts in ONE cc_mult_batch; the Chebyshev corrections of a step and the
+              level_ups of all ciphertexts through level_sum_batch / level_up_batch (levelsum.py: the words of the chains above)
           q_g: weighted_sums per ciphertext (the sets share nothing: a batched entry would only save launches)
           giants: y = p_n1 from p_{n1 / 2} in ONE cc_mult_batch of B squares, y^g by the same batched tree
-          r = cc_dot_batch of B dots [(q_g, y^g) g >= 1], ONE call;  result = cc_add(r, level_up(q_0, L_c + 1)) per ciphertext;
+          r = cc_dot_batch of B dots [(q_g, y^g) g >= 1], ONE call;  result = cc_add(r, level_up(q_0, L_c + 1)), ONE level_sum_batch;
           G = 1: q_0, no dot.
         cc_mult_batch and cc_dot_batch return the words of cc_mult and cc_dot, so each result has the words of poly_eval's
         composition.  An empty list: ValueError; ciphertexts of different levels: NotMatchDataStructState; the other refusals are
@@ -302,14 +317,16 @@ class PolyOps:
         base = cts[0].level
         trees = self._power_tree_batch([{1: ct} for ct in cts], n1 - 1, evk, cheb)
         Lb = base + sched["baby"]
-        qs = [self.weighted_sums([self._at_level(t[b], Lb) for b in range(1, n1)], blocks[:, 1:], consts=blocks[:, 0]) for t in trees]
+        babies = self._at_level([t[b] for t in trees for b in range(1, n1)], Lb)
+        qs = [self.weighted_sums(babies[i * (n1 - 1):(i + 1) * (n1 - 1)], blocks[:, 1:], consts=blocks[:, 0]) for i in range(len(trees))]
         if G == 1:
             return [q[0] for q in qs]
         ys = self.cc_mult_batch([(t[n1 // 2], t[n1 // 2]) for t in trees], evk)
         if cheb:
-            ys = [self.add_scalar(self.mult_int_scalar(y, 2), -1) for y in ys]
+            ys = self.level_sum_batch([([(y, 2)], -1) for y in ys])
         giants = self._power_tree_batch([{1: y} for y in ys], G - 1, evk, False)
         Lc = base + sched["common"]
-        rs = self.cc_dot_batch([[(self._at_level(q[g], Lc), self._at_level(yt[g], Lc)) for g in range(1, G)]
-                                for q, yt in zip(qs, giants)], evk)
-        return [self.cc_add(r, self.level_up(q[0], Lc + 1)) for r, q in zip(rs, qs)]
+        ups = self._at_level([x[g] for q, yt in zip(qs, giants) for x in (q, yt) for g in range(1, G)], Lc)
+        n = G - 1
+        rs = self.cc_dot_batch([list(zip(ups[2 * n * i:2 * n * i + n], ups[2 * n * i + n:2 * n * (i + 1)])) for i in range(len(qs))], evk)
+        return self.level_sum_batch([([(r, 1), (q[0], 1)], None) for r, q in zip(rs, qs)])

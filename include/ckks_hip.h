@@ -45,12 +45,16 @@ int lf_abi_version(void);
 /* Compile-time capacities of the fused kernels, so that callers can refuse a parameter set BEFORE any launch
  * (the digit width alpha and K live in device-side descriptors the ABI cannot check):
  *   which = 0: limbs per key-switch digit (alpha), 1: special primes K, 2: limb rows per call (`rows`),
- *           3: operand sets per batched call (count), 4: largest logN of the NTT family.  Other: -1. */
+ *           3: operand sets per batched call (count), 4: largest logN of the NTT family,
+ *           6: log2 of the bound of the fp64 class — a row whose prime is below 2^41 is computed in fp64 and, where a format keeps
+ *              such rows as 6-byte planes (lf_key_planes, lf_plain_planes), stored so; a caller that lays such a format out reads the
+ *              bound here.  Other (5 among them): -1. */
 #define LF_LIMIT_DIGIT_LIMBS 0
 #define LF_LIMIT_SPECIAL_PRIMES 1
 #define LF_LIMIT_ROWS 2
 #define LF_LIMIT_BATCH 3
 #define LF_LIMIT_LOGN 4
+#define LF_LIMIT_SMALL_PRIME_BITS 6
 int lf_limits(int which);
 
 /* Key-switch digits (`nparts`) where a limb row is of the fp64 class (prime below 2^41): a constant of the ABI, not a capacity
@@ -1080,6 +1084,42 @@ int lf_pc_matmul_batch(int nt, int k_in, int k_out, const int64_t *const *in, co
                        const int64_t *mont_one, const int64_t *zero_row, const int64_t *rescale_scales, int64_t round_at, int64_t *ws,
                        int64_t ws_words, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, int device,
                        void *stream);
+
+/* "Plain planes": the compact form of a "mult" plaintext (the [rows][N] tensor mc_mult builds: NTT domain, Montgomery form, lazy words
+ * below 2q) — the operand in which a layer's memory and the product launches' stream go.  Rows lie back to back in row order:
+ *   fp64-class row (prime below 2^lf_limits(LF_LIMIT_SMALL_PRIME_BITS))   6 N bytes: u32 lo[N], then u16 hi[N], the low 32 bits and
+ *       bits 32 .. 47 of v = REDC62(w) — the plain residue in [0, q] pc_matmul_kernel forms from the Montgomery word w on every read;
+ *   integer-class row                                                     8 N bytes: the word as it is.
+ * 6 N and 8 N are multiples of 16, so every row starts 16-byte aligned; the row offsets follow from the primes alone.
+ * lf_plain_planes_words(rows, N, q_host): the size in 8-byte words, rows N - N / 4 per fp64-class row; 0 for what the format refuses:
+ * rows < 1 or > LF_PLAIN_PLANES_MAX_ROWS (the kernels take the classes as a 64-bit mask), N no power of two in 2^13 .. 2^17, q_host NULL.
+ * lf_plain_planes: src [rows][N] -> dst (lf_plain_planes_words words), ONE launch.  lf_plain_unplanes: the inverse, ONE launch, writes
+ * the CANONICAL Montgomery residue w mod q on every row (v R mod q on fp64-class rows, the stored word reduced once on the others).
+ * q_host: HOST primes of the rows; ql .. kh: their device constants.  LF_ERR_ARG before any device call for a size the format refuses,
+ * a NULL pointer, src == dst, src or dst not 16-byte aligned. */
+#define LF_PLAIN_PLANES_MAX_ROWS 64
+int64_t lf_plain_planes_words(int rows, int64_t N, const int64_t *q_host);
+int lf_plain_planes(const int64_t *src, int64_t *dst, int rows, int64_t N, const int64_t *q_host, const int64_t *ql, const int64_t *qh,
+                    const int64_t *kl, const int64_t *kh, int device, void *stream);
+int lf_plain_unplanes(const int64_t *src, int64_t *dst, int rows, int64_t N, const int64_t *q_host, const int64_t *ql, const int64_t *qh,
+                      const int64_t *kl, const int64_t *kh, int device, void *stream);
+
+/* lf_pc_matmul_batch with every non-NULL entry of pt a compact plaintext (lf_plain_planes of the rows of q_host): signature, semantics,
+ * chunking, output groups, token tiles, transforms, rescales and biases are lf_pc_matmul_batch's (nt = 1: lf_pc_matmul; nt = 1,
+ * k_out = 1: lf_pc_dot's sum), and so are the words of every output — those of lf_pc_matmul_batch on the plaintexts the planes were
+ * packed from: the stored fp64-class word is the one the raw kernels compute on load.  The product launches are
+ * pc_planes_matmul_kernel<GO, GT> (GT = 1, 2: the tiles of lf_pc_matmul_batch; 4 under LF_TUNE_PC_MATMUL_TILE): per plaintext and pair of
+ * coefficients an 8-byte and a 4-byte nontemporal load on fp64-class rows and no REDC, the 16-byte pair at the row's compact offset
+ * on integer-class rows; the offset is derived in the kernel from a bit mask of the fp64-class rows (a kernel argument built from
+ * q_host: no table, no copy).  ws: lf_pc_matmul_batch_planes_ws_words = lf_pc_matmul_batch_ws_words, 0 also for rows >
+ * LF_PLAIN_PLANES_MAX_ROWS.  LF_ERR_ARG / LF_ERR_STATE as lf_pc_matmul_batch. */
+int64_t lf_pc_matmul_batch_planes_ws_words(int nt, int k_in, int k_out, int rows, int logN);
+int lf_pc_matmul_batch_planes(int nt, int k_in, int k_out, const int64_t *const *in, const int64_t *const *pt, const int64_t *const *bias,
+                              int64_t *const *out0, int64_t *const *out1, int rows, int logN, const int64_t *psi_br, const double *psi_dp,
+                              const int64_t *ipsi_br, const double *ipsi_dp, const int64_t *q_host, const int64_t *Rs, const int64_t *Ninv,
+                              const int64_t *mont_one, const int64_t *zero_row, const int64_t *rescale_scales, int64_t round_at, int64_t *ws,
+                              int64_t ws_words, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, int device,
+                              void *stream);
 
 /* The halves of an op around the digit exchange of a limb-sharded engine (one process per GPU; the reference gathers every
  * digit on every GPU through the host before it extends any, ckks_engine.py:778-829).  The plan describes THIS rank's rows

@@ -122,6 +122,11 @@ _SIGNATURES["lf_pc_matmul_ws_words"] = [_I, _I, _I, _I]
 _SIGNATURES["lf_pc_matmul"] = [_I, _I, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _I, _P]
 _SIGNATURES["lf_pc_matmul_batch_ws_words"] = [_I, _I, _I, _I, _I]
 _SIGNATURES["lf_pc_matmul_batch"] = [_I] + _SIGNATURES["lf_pc_matmul"]
+_SIGNATURES["lf_pc_matmul_batch_planes_ws_words"] = _SIGNATURES["lf_pc_matmul_batch_ws_words"]
+_SIGNATURES["lf_pc_matmul_batch_planes"] = _SIGNATURES["lf_pc_matmul_batch"]
+_SIGNATURES["lf_plain_planes_words"] = [_I, _L, _P]
+_SIGNATURES["lf_plain_planes"] = [_P, _P, _I, _L, _P, _P, _P, _P, _P, _I, _P]
+_SIGNATURES["lf_plain_unplanes"] = _SIGNATURES["lf_plain_planes"]
 _SIGNATURES["lf_linear_transform_ws_words"] = [_PL]
 _SIGNATURES["lf_linear_transform"] = [_PL, _P, _P, _I, _P, _P, _L, _L, _L, _I, _P, _L, _P, _P, _L, _P, _L, _P, _P, _P]
 _SIGNATURES["lf_linear_transform_batch_ws_words"] = [_PL, _I]
@@ -193,6 +198,8 @@ LF_LSUM_MAX_SETS = 8        # .. and sets per call
 LF_PC_MATMUL_CI = 16           # include/ckks_hip.h: inputs per chunk of lf_pc_matmul
 LF_PC_MATMUL_MAX_OUTPUTS = 64  # .. and outputs per call
 LF_PC_MATMUL_BATCH_MAX_TOKENS = 4   # include/ckks_hip.h: token vectors per lf_pc_matmul_batch call
+LF_PLAIN_PLANES_MAX_ROWS = 64       # include/ckks_hip.h: rows of a compact plaintext (lf_plain_planes)
+LF_LIMIT_SMALL_PRIME_BITS = 6       # include/ckks_hip.h: lf_limits' index of the fp64 class bound (log2)
 LF_LT_MATMUL_MAX_INPUTS = 64   # include/ckks_hip.h: inputs per lf_lt_matmul call
 LF_LT_MATMUL_MAX_OUTPUTS = 64  # .. and outputs per call
 LF_LT_MATMUL_BATCH_MAX_TOKENS = 4   # include/ckks_hip.h: token vectors per lf_lt_matmul_batch call

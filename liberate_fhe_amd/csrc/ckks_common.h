@@ -26,6 +26,8 @@ typedef __int128 i128;
 // largest ring degree whose column pass has at most 5 stages: the planes stack (lf_stack_planes), the key-switch entries
 // (lf_ks_* / lf_relin_*) and the engine ops (lf_cc_mult_evk*, lf_switch_key*) go up to it and refuse larger ones
 #define KS_LOGN_MAX (NTT_TILE_LOG_MAX + 5)
+// log2 of the bound of the fp64 class: a row whose prime is below 2^41 is computed in fp64 (SMALL_PRIME_LIMIT, ckks_ntt_core.h)
+#define SMALL_PRIME_BITS 41
 
 // ------------------------------------------------------------------------------------------------
 // Scalar arithmetic

@@ -220,6 +220,7 @@ int lf_limits(int which) {
         case LF_LIMIT_ROWS: return MAX_LIST_ROWS;
         case LF_LIMIT_BATCH: return LF_BATCH_MAX;
         case LF_LIMIT_LOGN: return 2 * NTT_TILE_LOG_MAX;
+        case LF_LIMIT_SMALL_PRIME_BITS: return SMALL_PRIME_BITS;
         default: return -1;
     }
 }

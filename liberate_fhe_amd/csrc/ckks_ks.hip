@@ -945,6 +945,173 @@ __global__ void __launch_bounds__(256) pc_matmulb_kernel(const i64 *__restrict__
     }
 }
 
+// ---- plain planes: a "mult" plaintext with its fp64-class rows as 6-byte planes (lf_plain_planes, include/ckks_hip.h) ----------
+// Rows back to back in row order: an fp64-class row is 6 N bytes — u32 lo[N], then u16 hi[N] — of v = mm62u(w, 1, q, k), the plain
+// word in [0, q] pc_matmul_kernel forms from the Montgomery word w on every read; an integer-class row is its 8 N bytes as they
+// are.  `small`: bit r set where row r is fp64-class (from the host primes: the offsets follow from it alone, and so does every
+// address below).  Row r starts N / 4 words earlier for every fp64-class row before it.
+static __device__ __forceinline__ i64 plain_planes_row(unsigned long long small, int r, i64 N) {
+    return (i64)r * N - (i64)__popcll(small & ((1ull << r) - 1ull)) * (N >> 2);
+}
+
+// lf_plain_planes / lf_plain_unplanes: one row per blockIdx.y, two coefficients per thread (grid.x = N / 512)
+__global__ void __launch_bounds__(256) plain_planes_kernel(const i64 *__restrict__ src, i64 *__restrict__ dst, i64 N, unsigned long long small,
+                                                           const i64 *__restrict__ ql, const i64 *__restrict__ qh,
+                                                           const i64 *__restrict__ kl, const i64 *__restrict__ kh) {
+    const int r = blockIdx.y;
+    const i64 j = ((i64)blockIdx.x * 256 + threadIdx.x) * 2;
+    if (j >= N) return;
+    const longlong2 w = *reinterpret_cast<const longlong2 *>(src + (i64)r * N + j);
+    i64 *row = dst + plain_planes_row(small, r, N);
+    if (!((small >> r) & 1ull)) {
+        *reinterpret_cast<longlong2 *>(row + j) = w;
+        return;
+    }
+    const RowMod m = load_mod(ql, qh, kl, kh, r);
+    const u64 v0 = (u64)mm62u((u64)w.x, 1ull, m.q, m.k), v1 = (u64)mm62u((u64)w.y, 1ull, m.q, m.k);   // in [0, q], q < 2^41
+    const lf_u2_t l = {(unsigned)v0, (unsigned)v1};
+    *reinterpret_cast<lf_u2_t *>(reinterpret_cast<unsigned *>(row) + j) = l;
+    *reinterpret_cast<unsigned *>(reinterpret_cast<unsigned short *>(row + (N >> 1)) + j) = (unsigned)(v0 >> 32) | ((unsigned)(v1 >> 32) << 16);
+}
+
+// the inverse: the canonical Montgomery residue on every row — v R mod q on fp64-class rows (R = 2^62: 62 doublings, once per
+// plaintext), the stored word reduced once on integer-class rows (a lazy word below 2q)
+__global__ void __launch_bounds__(256) plain_unplanes_kernel(const i64 *__restrict__ src, i64 *__restrict__ dst, i64 N, unsigned long long small,
+                                                             const i64 *__restrict__ ql, const i64 *__restrict__ qh) {
+    const int r = blockIdx.y;
+    const i64 j = ((i64)blockIdx.x * 256 + threadIdx.x) * 2;
+    if (j >= N) return;
+    const i64 q = (qh[r] << 31) | ql[r];
+    const i64 *row = src + plain_planes_row(small, r, N);
+    longlong2 o;
+    if (!((small >> r) & 1ull)) {
+        const longlong2 w = *reinterpret_cast<const longlong2 *>(row + j);
+        o.x = csub(w.x, q), o.y = csub(w.y, q);
+    } else {
+        const lf_u2_t l = *reinterpret_cast<const lf_u2_t *>(reinterpret_cast<const unsigned *>(row) + j);
+        const unsigned h = *reinterpret_cast<const unsigned *>(reinterpret_cast<const unsigned short *>(row + (N >> 1)) + j);
+        i64 a = csub((i64)(((u64)(h & 0xffffu) << 32) | l.x), q), b = csub((i64)(((u64)(h >> 16) << 32) | l.y), q);
+        for (int s = 0; s < 62; ++s) a = csub(a << 1, q), b = csub(b << 1, q);
+        o.x = a, o.y = b;
+    }
+    *reinterpret_cast<longlong2 *>(dst + (i64)r * N + j) = o;
+}
+
+// ---- pc_matmul / pc_matmul_batch over plain planes (lf_pc_matmul_batch_planes): pc_matmul_kernel<GO> (GT = 1) and
+// pc_matmulb_kernel<GO, GT> with every plaintext in the format above.  x, S, pa, grid and thread as pc_matmulb_kernel's.  On
+// fp64-class rows a thread loads the lo pair (8 bytes) and the hi pair (4 bytes) of a plaintext, nontemporal as the raw word
+// is, and assembles the plain word with dp_from_planes: the REDC of the raw kernels ran once, in the packer.  On integer-class
+// rows it reads the 16-byte pair at the row's compact offset.  The words that enter the sums are those of the raw kernels, so
+// their accumulation, bounds (fp64 rows: at most LF_PC_MATMUL_CI balanced products plus the word read back, <= 9 q; integer rows: a
+// conditional subtraction after every addition), read-add-write of S and stores stand as they are, and output (t, g) has the
+// words pc_matmul_kernel<GO> gives on token t with the plaintexts the planes were packed from.
+template <int GO, int GT>
+__global__ void __launch_bounds__(256) pc_planes_matmul_kernel(const i64 *__restrict__ x, i64 xtok, PcMatTerms pa, i64 *__restrict__ S, i64 stok,
+                                                               int n, int rows, i64 N, int xpl, int first, unsigned long long small,
+                                                               const i64 *__restrict__ ql, const i64 *__restrict__ qh,
+                                                               const i64 *__restrict__ kl, const i64 *__restrict__ kh) {
+    const int r = blockIdx.y;
+    const i64 j0 = (i64)blockIdx.x * 512 + threadIdx.x * 2;
+    if (j0 >= N) return;
+    const RowMod m = load_mod(ql, qh, kl, kh, r);
+    const i64 pstride = (i64)rows * N, o0 = (i64)r * N + j0;
+    const i64 po = plain_planes_row(small, r, N);   // (uniform over the block)
+    i64 *s = S + o0;
+    if ((small >> r) & 1ull) {
+        const RowDp d = make_dp(m);
+        double a[GT][GO][2][2];
+#pragma unroll
+        for (int t = 0; t < GT; ++t)
+#pragma unroll
+            for (int g = 0; g < GO; ++g) a[t][g][0][0] = a[t][g][0][1] = a[t][g][1][0] = a[t][g][1][1] = 0.0;
+        for (int i = 0; i < n; ++i) {
+            double c0[GT][2], c1[GT][2];
+#pragma unroll
+            for (int t = 0; t < GT; ++t) {
+                const i64 *xs = x + t * xtok + (i64)i * 2 * pstride + (i64)r * N;
+                ld_pair_dp(xs, j0, N, xpl, c0[t][0], c0[t][1]);
+                ld_pair_dp(xs + pstride, j0, N, xpl, c1[t][0], c1[t][1]);
+            }
+#pragma unroll
+            for (int g = 0; g < GO; ++g) {
+                const i64 *p = pa.pt[i][g];
+                if (p == nullptr) continue;   // (uniform: a kernel argument)
+                const lf_u2_t l = __builtin_nontemporal_load(reinterpret_cast<const lf_u2_t *>(reinterpret_cast<const unsigned *>(p + po) + j0));
+                const unsigned h = __builtin_nontemporal_load(
+                    reinterpret_cast<const unsigned *>(reinterpret_cast<const unsigned short *>(p + po + (N >> 1)) + j0));
+                const double wp[2] = {dp_from_planes(l.x, h & 0xffffu), dp_from_planes(l.y, h >> 16)};
+#pragma unroll
+                for (int t = 0; t < GT; ++t)
+#pragma unroll
+                    for (int e = 0; e < 2; ++e) {
+                        a[t][g][0][e] += dp_mulmod_bal(c0[t][e], wp[e], d);
+                        a[t][g][1][e] += dp_mulmod_bal(c1[t][e], wp[e], d);
+                    }
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < GT; ++t)
+#pragma unroll
+            for (int g = 0; g < GO; ++g)
+#pragma unroll
+                for (int c = 0; c < 2; ++c) {
+                    i64 *at = s + t * stok + (2 * g + c) * pstride;
+                    if (!first) {
+                        const longlong2 v = *reinterpret_cast<const longlong2 *>(at);
+                        a[t][g][c][0] += dp_from_word(v.x), a[t][g][c][1] += dp_from_word(v.y);
+                    }
+                    longlong2 o;
+                    o.x = dp_to_word(dp_reduce(a[t][g][c][0], d.q, d.qinv));
+                    o.y = dp_to_word(dp_reduce(a[t][g][c][1], d.q, d.qinv));
+                    *reinterpret_cast<longlong2 *>(at) = o;
+                }
+    } else {
+        i64 a[GT][GO][2][2];
+#pragma unroll
+        for (int t = 0; t < GT; ++t)
+#pragma unroll
+            for (int g = 0; g < GO; ++g) a[t][g][0][0] = a[t][g][0][1] = a[t][g][1][0] = a[t][g][1][1] = 0;
+        for (int i = 0; i < n; ++i) {
+            u64 c0[GT][2], c1[GT][2];
+#pragma unroll
+            for (int t = 0; t < GT; ++t) {
+                const i64 *xs = x + t * xtok + (i64)i * 2 * pstride + o0;
+                const longlong2 C0 = *reinterpret_cast<const longlong2 *>(xs), C1 = *reinterpret_cast<const longlong2 *>(xs + pstride);
+                c0[t][0] = (u64)C0.x, c0[t][1] = (u64)C0.y, c1[t][0] = (u64)C1.x, c1[t][1] = (u64)C1.y;
+            }
+#pragma unroll
+            for (int g = 0; g < GO; ++g) {
+                const i64 *p = pa.pt[i][g];
+                if (p == nullptr) continue;
+                const longlong2 w = ld_nt(p + po + j0);
+                const u64 wm[2] = {(u64)w.x, (u64)w.y};
+#pragma unroll
+                for (int t = 0; t < GT; ++t)
+#pragma unroll
+                    for (int e = 0; e < 2; ++e) {
+                        a[t][g][0][e] = csub(a[t][g][0][e] + mm62u(c0[t][e], wm[e], m.q, m.k), m.q2);
+                        a[t][g][1][e] = csub(a[t][g][1][e] + mm62u(c1[t][e], wm[e], m.q, m.k), m.q2);
+                    }
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < GT; ++t)
+#pragma unroll
+            for (int g = 0; g < GO; ++g)
+#pragma unroll
+                for (int c = 0; c < 2; ++c) {
+                    i64 *at = s + t * stok + (2 * g + c) * pstride;
+                    if (!first) {
+                        const longlong2 v = *reinterpret_cast<const longlong2 *>(at);
+                        a[t][g][c][0] = csub(a[t][g][c][0] + v.x, m.q2), a[t][g][c][1] = csub(a[t][g][c][1] + v.y, m.q2);
+                    }
+                    longlong2 o;
+                    o.x = a[t][g][c][0], o.y = a[t][g][c][1];
+                    *reinterpret_cast<longlong2 *>(at) = o;
+                }
+    }
+}
+
 // ---- cc_matmul: the summed triplets of an R x C tile of C = A B, every operand of the tile read once per inner index ----------
 // x = [nu][2][ell][N]: the resident store of the DISTINCT operands, c0, c1 of each as lf_rescale_ntt(RELAXED | PLAIN) leaves them
 // (xpl: fp64-class rows as planes).  ix.a[t][i] / ix.b[t][j]: the operand that is A[i0 + i][t] resp. B[t][j0 + j], or -1 for a zero
@@ -2948,6 +3115,44 @@ int lf_pc_matmulb_products(int go, int gt, int n, const int64_t *x, int64_t xtok
     return (int)hipGetLastError();
 }
 
+// lf_plain_planes_mask: bit r set where row r of a compact plaintext is fp64-class; false for more rows than the mask has bits
+bool lf_plain_planes_mask(int rows, const int64_t *q_host, uint64_t *mask) {
+    if (rows < 1 || rows > LF_PLAIN_PLANES_MAX_ROWS || !q_host) return false;
+    uint64_t m = 0;
+    for (int r = 0; r < rows; ++r)
+        if ((uint64_t)q_host[r] < SMALL_PRIME_LIMIT) m |= 1ull << r;
+    *mask = m;
+    return true;
+}
+
+// lf_pc_planes_products: lf_pc_matmul_products (gt = 1) resp. lf_pc_matmulb_products (gt = 2 or 4) with every non-NULL pt a compact
+// plaintext (lf_plain_planes) whose fp64-class rows `small` marks.
+int lf_pc_planes_products(int go, int gt, int n, const int64_t *x, int64_t xtok, const int64_t *const *pt, int pt_stride, int64_t *S,
+                          int64_t stok, int rows, int logN, int xpl, int first, uint64_t small, const LfMod &m, hipStream_t st) {
+    if ((go != 1 && go != 2 && go != 4) || (gt != 1 && gt != 2 && gt != 4) || n < 1 || n > LF_PC_MATMUL_CI || !x || !pt || pt_stride < go ||
+        !S || rows < 1 || rows > LF_PLAIN_PLANES_MAX_ROWS || logN < 9 || xtok < ((int64_t)2 * n * rows << logN) ||
+        stok < ((int64_t)2 * go * rows << logN) || (xtok & 1) || (stok & 1))
+        return LF_ERR_ARG;
+    const i64 N = (i64)1 << logN;
+    for (int t = 0; t < gt; ++t)
+        if (int e = lf_fmt_expect(x + t * xtok, ((size_t)2 * n * rows << logN) * 8, xpl ? LF_FMT_PLANES : LF_FMT_RAW)) return e;
+    PcMatTerms pa{};
+    for (int i = 0; i < n; ++i)
+        for (int g = 0; g < go; ++g) pa.pt[i][g] = (const i64 *)pt[(size_t)i * pt_stride + g];
+    const dim3 grid((unsigned)(N / 512), (unsigned)rows);
+#define LF_PCPL_CASE(GG, TT)                                                                                                      \
+    case GG * 8 + TT:                                                                                                             \
+        hipLaunchKernelGGL((pc_planes_matmul_kernel<GG, TT>), grid, dim3(256), 0, st, (const i64 *)x, (i64)xtok, pa, (i64 *)S,     \
+                           (i64)stok, n, rows, N, xpl, first, (unsigned long long)small, LF_MOD_ARGS(m));                          \
+        break;
+    switch (go * 8 + gt) {
+        LF_PCPL_CASE(1, 1) LF_PCPL_CASE(2, 1) LF_PCPL_CASE(4, 1) LF_PCPL_CASE(1, 2) LF_PCPL_CASE(2, 2) LF_PCPL_CASE(4, 2)
+        LF_PCPL_CASE(1, 4) LF_PCPL_CASE(2, 4) LF_PCPL_CASE(4, 4)
+    }
+#undef LF_PCPL_CASE
+    return (int)hipGetLastError();
+}
+
 // The launch of lf_cc_matmul that is its own (ckks_ops.hip checks the arguments).
 // lf_matmul_tensor: the summed triplets of an R x C tile (R C = 1, 2 or 4) over the inner dimension k <= LF_CC_MATMUL_MAX_INNER from the
 // store x = [nu][2][ell][N] of transformed operands (xpl: fp64-class rows as planes — refused where the library's note of that range
@@ -3400,6 +3605,39 @@ int lf_key_planes(const int64_t *src_b, const int64_t *src_a, int64_t *dst_b, in
     hipLaunchKernelGGL(key_planes_kernel, dim3((unsigned)((N / 2 + 255) / 256), (unsigned)rows), dim3(256), 0, (hipStream_t)stream,
                        (const i64 *)src_b, (const i64 *)src_a, (i64 *)dst_b, (i64 *)dst_a, (i64)N, (const i64 *)ql, (const i64 *)qh);
     return (int)hipGetLastError();
+}
+
+int64_t lf_plain_planes_words(int rows, int64_t N, const int64_t *q_host) {
+    uint64_t small;
+    if (N < ((int64_t)1 << 13) || N > ((int64_t)1 << KS_LOGN_MAX) || (N & (N - 1)) || !lf_plain_planes_mask(rows, q_host, &small)) return 0;
+    return (int64_t)rows * N - (int64_t)__builtin_popcountll(small) * (N >> 2);
+}
+
+static int plain_planes_launch(bool pack, const int64_t *src, int64_t *dst, int rows, int64_t N, const int64_t *q_host, const int64_t *ql,
+                               const int64_t *qh, const int64_t *kl, const int64_t *kh, int device, void *stream) {
+    uint64_t small;
+    if (!lf_plain_planes_words(rows, N, q_host) || !src || !dst || src == dst || !ql || !qh || !kl || !kh ||
+        (((uintptr_t)src | (uintptr_t)dst) & 15) || !lf_plain_planes_mask(rows, q_host, &small))
+        return LF_ERR_ARG;
+    if (int e = lf_set_device(device)) return e;
+    const dim3 grid((unsigned)(N / 512), (unsigned)rows);
+    if (pack)
+        hipLaunchKernelGGL(plain_planes_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const i64 *)src, (i64 *)dst, (i64)N,
+                           (unsigned long long)small, (const i64 *)ql, (const i64 *)qh, (const i64 *)kl, (const i64 *)kh);
+    else
+        hipLaunchKernelGGL(plain_unplanes_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const i64 *)src, (i64 *)dst, (i64)N,
+                           (unsigned long long)small, (const i64 *)ql, (const i64 *)qh);
+    return (int)hipGetLastError();
+}
+
+int lf_plain_planes(const int64_t *src, int64_t *dst, int rows, int64_t N, const int64_t *q_host, const int64_t *ql, const int64_t *qh,
+                    const int64_t *kl, const int64_t *kh, int device, void *stream) {
+    return plain_planes_launch(true, src, dst, rows, N, q_host, ql, qh, kl, kh, device, stream);
+}
+
+int lf_plain_unplanes(const int64_t *src, int64_t *dst, int rows, int64_t N, const int64_t *q_host, const int64_t *ql, const int64_t *qh,
+                      const int64_t *kl, const int64_t *kh, int device, void *stream) {
+    return plain_planes_launch(false, src, dst, rows, N, q_host, ql, qh, kl, kh, device, stream);
 }
 
 int lf_ks_core_batch(const int64_t *state, int64_t state_stride, int nct, int nparts, int rows, int logN, const int64_t *desc,

@@ -113,3 +113,8 @@ int lf_pc_matmul_batch_tile(int go, int left);
 int lf_pc_matmul_batch_outputs(int left, int nt);
 int lf_pc_matmulb_products(int go, int gt, int n, const int64_t *x, int64_t xtok, const int64_t *const *pt, int pt_stride, int64_t *S,
                            int64_t stok, int rows, int logN, int xpl, int first, const LfMod &m, hipStream_t st);
+// .. of lf_pc_matmul_batch_planes: the fp64-class rows of a compact plaintext as a bit mask (false: more rows than it has bits),
+// and the products over compact plaintexts (gt = 1, 2 or 4 tokens per launch)
+bool lf_plain_planes_mask(int rows, const int64_t *q_host, uint64_t *mask);
+int lf_pc_planes_products(int go, int gt, int n, const int64_t *x, int64_t xtok, const int64_t *const *pt, int pt_stride, int64_t *S,
+                          int64_t stok, int rows, int logN, int xpl, int first, uint64_t small, const LfMod &m, hipStream_t st);

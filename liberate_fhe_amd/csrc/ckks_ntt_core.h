@@ -10,7 +10,7 @@
                            // were measured slower)
 #define NTT_LDS_WORDS ((1 << NTT_TILE_LOG_MAX) + (1 << (NTT_TILE_LOG_MAX - 3)))
 #define TAIL_NONE (-1)
-#define SMALL_PRIME_LIMIT (1ull << 41)
+#define SMALL_PRIME_LIMIT (1ull << SMALL_PRIME_BITS)
 
 #define PAD(L) ((L) + ((L) >> 3))
 // PAD(p + (e << LOGDL)) for LOGDL >= 3 and a p whose bits LOGDL .. LOGDL + K - 1 are clear: the element stride of the

@@ -438,8 +438,9 @@ int64_t lf_pc_matmul_batch_ws_words(int nt, int k_in, int k_out, int rows, int l
 
 // lf_pc_matmul (nt = 1) and lf_pc_matmul_batch: `in` [token][input][component], out0 / out1 [token][output]; `need`: the words
 // of the workspace the entry asks for (0: a refused shape).  x = [nt][ci][2][rows][N] with ci = min(k_in, LF_PC_MATMUL_CI) slots
-// per token, S = [nt][k_out][2][rows][N] behind it.
-static int pc_matmul_tokens(int nt, int64_t need, int k_in, int k_out, const int64_t *const *in, const int64_t *const *pt,
+// per token, S = [nt][k_out][2][rows][N] behind it.  planes: every non-NULL pt a compact plaintext (lf_plain_planes) — the products
+// read it through pc_planes_matmul_kernel; everything else is the same.
+static int pc_matmul_tokens(bool planes, int nt, int64_t need, int k_in, int k_out, const int64_t *const *in, const int64_t *const *pt,
                             const int64_t *const *bias, int64_t *const *out0, int64_t *const *out1, int rows, int logN,
                             const int64_t *psi_br, const double *psi_dp, const int64_t *ipsi_br, const double *ipsi_dp,
                             const int64_t *q_host, const int64_t *Rs, const int64_t *Ninv, const int64_t *mont_one,
@@ -469,6 +470,8 @@ static int pc_matmul_tokens(int nt, int64_t need, int k_in, int k_out, const int
     const int64_t N = (int64_t)1 << logN, poly = (int64_t)rows * N;
     const int xpl = lf_stack_planes(logN, rows, q_host);
     const int relaxed_plain = LF_NTT_RELAXED | LF_NTT_PLAIN | (xpl ? LF_NTT_PLANES : 0);
+    uint64_t small = 0;
+    if (planes && !lf_plain_planes_mask(rows, q_host, &small)) return LF_ERR_ARG;
     if (int e = lf_set_device(device)) return e;
     const LfMod mod{ql, qh, kl, kh, q_host};
     const int64_t xtok = 2 * (int64_t)(k_in < LF_PC_MATMUL_CI ? k_in : LF_PC_MATMUL_CI) * poly, stok = 2 * (int64_t)k_out * poly;
@@ -501,7 +504,9 @@ static int pc_matmul_tokens(int nt, int64_t need, int k_in, int k_out, const int
             for (int tk = 0; tk < nt;) {
                 const int gt = lf_pc_matmul_batch_tile(go, nt - tk);
                 int64_t *Sg = S + tk * stok + (int64_t)o0 * 2 * poly;
-                const int e = gt == 1 ? lf_pc_matmul_products(go, n, x + tk * xtok, tab, 4, Sg, rows, logN, xpl, a0 == 0, mod, (hipStream_t)stream)
+                const int e = planes  ? lf_pc_planes_products(go, gt, n, x + tk * xtok, xtok, tab, 4, Sg, stok, rows, logN, xpl, a0 == 0, small,
+                                                              mod, (hipStream_t)stream)
+                              : gt == 1 ? lf_pc_matmul_products(go, n, x + tk * xtok, tab, 4, Sg, rows, logN, xpl, a0 == 0, mod, (hipStream_t)stream)
                                       : lf_pc_matmulb_products(go, gt, n, x + tk * xtok, xtok, tab, 4, Sg, stok, rows, logN, xpl, a0 == 0,
                                                                mod, (hipStream_t)stream);
                 if (e) return e;
@@ -549,7 +554,7 @@ int lf_pc_matmul(int k_in, int k_out, const int64_t *const *in, const int64_t *c
                  const int64_t *ipsi_br, const double *ipsi_dp, const int64_t *q_host, const int64_t *Rs, const int64_t *Ninv,
                  const int64_t *mont_one, const int64_t *zero_row, const int64_t *rescale_scales, int64_t round_at, int64_t *ws,
                  int64_t ws_words, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, int device, void *stream) {
-    return pc_matmul_tokens(1, lf_pc_matmul_ws_words(k_in, k_out, rows, logN), k_in, k_out, in, pt, bias, out0, out1, rows, logN, psi_br,
+    return pc_matmul_tokens(false, 1, lf_pc_matmul_ws_words(k_in, k_out, rows, logN), k_in, k_out, in, pt, bias, out0, out1, rows, logN, psi_br,
                             psi_dp, ipsi_br, ipsi_dp, q_host, Rs, Ninv, mont_one, zero_row, rescale_scales, round_at, ws, ws_words, ql, qh,
                             kl, kh, device, stream);
 }
@@ -563,8 +568,27 @@ int lf_pc_matmul_batch(int nt, int k_in, int k_out, const int64_t *const *in, co
                        int64_t ws_words, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, int device,
                        void *stream) {
     if (nt < 1 || nt > LF_PC_MATMUL_BATCH_MAX_TOKENS) return LF_ERR_ARG;
-    return pc_matmul_tokens(nt, lf_pc_matmul_batch_ws_words(nt, k_in, k_out, rows, logN), k_in, k_out, in, pt, bias, out0, out1, rows,
+    return pc_matmul_tokens(false, nt, lf_pc_matmul_batch_ws_words(nt, k_in, k_out, rows, logN), k_in, k_out, in, pt, bias, out0, out1, rows,
                             logN, psi_br, psi_dp, ipsi_br, ipsi_dp, q_host, Rs, Ninv, mont_one, zero_row, rescale_scales, round_at, ws,
+                            ws_words, ql, qh, kl, kh, device, stream);
+}
+
+/* ---- pc_matmul_batch over compact plaintexts (include/ckks_hip.h: lf_plain_planes): lf_pc_matmul_batch with the plaintext stream of
+ * the product launches at 6 bytes per word on fp64-class rows and no REDC per word read. ---- */
+int64_t lf_pc_matmul_batch_planes_ws_words(int nt, int k_in, int k_out, int rows, int logN) {
+    if (rows > LF_PLAIN_PLANES_MAX_ROWS) return 0;
+    return lf_pc_matmul_batch_ws_words(nt, k_in, k_out, rows, logN);
+}
+
+int lf_pc_matmul_batch_planes(int nt, int k_in, int k_out, const int64_t *const *in, const int64_t *const *pt, const int64_t *const *bias,
+                              int64_t *const *out0, int64_t *const *out1, int rows, int logN, const int64_t *psi_br, const double *psi_dp,
+                              const int64_t *ipsi_br, const double *ipsi_dp, const int64_t *q_host, const int64_t *Rs, const int64_t *Ninv,
+                              const int64_t *mont_one, const int64_t *zero_row, const int64_t *rescale_scales, int64_t round_at, int64_t *ws,
+                              int64_t ws_words, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, int device,
+                              void *stream) {
+    if (nt < 1 || nt > LF_PC_MATMUL_BATCH_MAX_TOKENS) return LF_ERR_ARG;
+    return pc_matmul_tokens(true, nt, lf_pc_matmul_batch_planes_ws_words(nt, k_in, k_out, rows, logN), k_in, k_out, in, pt, bias, out0, out1,
+                            rows, logN, psi_br, psi_dp, ipsi_br, ipsi_dp, q_host, Rs, Ninv, mont_one, zero_row, rescale_scales, round_at, ws,
                             ws_words, ql, qh, kl, kh, device, stream);
 }
 

@@ -12,9 +12,12 @@ import ctypes
 import torch
 
 from .._native import lib, check, KsPlan, LF_KEY_PLANES, LF_LT_MATMUL_BSGS_MAX_GIANTS, LF_LT_MATMUL_BSGS_MAX_SUMS, LF_LT_BATCH_MAX_CTS, \
-    LF_LT_MATMUL_BATCH_MAX_TOKENS, LF_LT_MATMUL_BSGS_BATCH_MAX_TOKENS
+    LF_LT_MATMUL_BATCH_MAX_TOKENS, LF_LT_MATMUL_BSGS_BATCH_MAX_TOKENS, LF_LIMIT_SMALL_PRIME_BITS, LF_PLAIN_PLANES_MAX_ROWS
 from ..ntt import ntt_cuda, twiddles
 
+# the bound of the fp64 class, from the library (include/ckks_hip.h: LF_LIMIT_SMALL_PRIME_BITS): a row whose prime is below it is
+# kept as 6-byte planes where a format has them
+SMALL_PRIME_LIMIT = 1 << int(lib.lf_limits(LF_LIMIT_SMALL_PRIME_BITS))
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)   # the stream handle without a Stream object per call
 
@@ -563,6 +566,42 @@ class HipBackend:
                                      c.qptr(True), _p(Rs), _p(Ninv), _p(mont_one), _p(zero_row), _p(scales), round_at, _p(ws), ws.numel(),
                                      *c.mont(), dev, st), "lf_pc_matmul_batch")
 
+    # include/ckks_hip.h: LF_PLAIN_PLANES_MAX_ROWS (tests/test_compact_plain_cpu.py holds this copy to the header)
+    plain_planes_max_rows = LF_PLAIN_PLANES_MAX_ROWS
+
+    @staticmethod
+    def plain_planes_words(rows, N, c: Consts):
+        """8-byte words of the compact form of a [rows, N] "mult" plaintext (lf_plain_planes_words; 0: a size the format refuses)."""
+        return int(lib.lf_plain_planes_words(rows, N, c.qptr(True)))
+
+    def plain_planes(self, src, dst, c: Consts):
+        """src [rows, N] (a "mult" plaintext's tensor: Montgomery form, lazy words) -> dst, flat, plain_planes_words words: fp64-class
+        rows as 6-byte planes of the plain word, integer-class rows as they are (lf_plain_planes, one launch)."""
+        dev, st = _ds(dst)
+        check(lib.lf_plain_planes(_p(src), _p(dst), src.size(0), src.size(1), c.qptr(True), *c.mont(), dev, st), "lf_plain_planes")
+
+    def plain_unplanes(self, src, dst, c: Consts):
+        """The inverse: dst [rows, N] <- the canonical Montgomery residue of every word of the compact src (lf_plain_unplanes)."""
+        dev, st = _ds(dst)
+        check(lib.lf_plain_unplanes(_p(src), _p(dst), dst.size(0), dst.size(1), c.qptr(True), *c.mont(), dev, st), "lf_plain_unplanes")
+
+    @staticmethod
+    def pc_matmul_batch_planes_ws_words(nt, k_in, k_out, rows, logN):
+        return int(lib.lf_pc_matmul_batch_planes_ws_words(nt, k_in, k_out, rows, logN))
+
+    def pc_matmul_batch_planes_call(self, ins, pts, biases, outs, nt, k_in, k_out, rows, logN, psi, ipsi, Rs, Ninv, mont_one, zero_row,
+                                    scales, round_at, ws, c: Consts):
+        """pc_matmul_batch_native with every plaintext of pts a compact one (plain_planes) as ONE native call
+        (lf_pc_matmul_batch_planes); nt = 1 is pc_matmul, nt = 1 and k_out = 1 pc_dot.  ws: at least
+        pc_matmul_batch_planes_ws_words(nt, k_in, k_out, rows, logN) words."""
+        dev, st = _ds(outs[0][0][0])
+        psi_dp = twiddles.dp_pointer(psi, c.ql, c.qh, c.kl, c.kh, dev, st)
+        ipsi_dp = twiddles.dp_pointer(ipsi, c.ql, c.qh, c.kl, c.kh, dev, st)
+        out0, out1 = _parr([o[0] for tok in outs for o in tok]), _parr([o[1] for tok in outs for o in tok])
+        check(lib.lf_pc_matmul_batch_planes(nt, k_in, k_out, ins, pts, biases, out0, out1, rows, logN, _p(psi), psi_dp, _p(ipsi), ipsi_dp,
+                                            c.qptr(True), _p(Rs), _p(Ninv), _p(mont_one), _p(zero_row), _p(scales), round_at, _p(ws),
+                                            ws.numel(), *c.mont(), dev, st), "lf_pc_matmul_batch_planes")
+
     @staticmethod
     def rotate_hoisted_ws_words(plan):
         return int(lib.lf_rotate_hoisted_ws_words(ctypes.byref(plan)))
@@ -896,7 +935,7 @@ class HipBackend:
         planes format (u32 low words at byte 0, u16 high halves at byte 4 N of the row: LF_TUNE_DIGIT_PLANES), other rows raw
         words.  torch gathers, no kernel of its own (the orchestrated form of hoisted rotations; the native op gathers in registers)."""
         q = c.q_host[:rows]
-        small = torch.as_tensor(q < (1 << 41))
+        small = torch.as_tensor(q < SMALL_PRIME_LIMIT)
         planes = logN > 12 and bool(small.any()) and not bool(small.all()) and lib.lf_tune(3, -1) == 1
         if not planes:
             torch.index_select(ext, ext.dim() - 1, index, out=dst)

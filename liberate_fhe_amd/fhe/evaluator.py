@@ -181,6 +181,8 @@ class EvaluatorOps:
         return [func(part, level, include_special) for part in data]
 
     def move_to(self, text, direction="gpu2cpu"):
+        if text.origin == types.origins["pt_mult_planes"]:        # a compact plaintext: its rows are not [rows, N] tensors
+            return self._move_plain_planes(text, direction)
         if not is_struct(text.data[0]):
             return text._replace(data=self.move_tensors(text.data, text.level, text.include_special, direction))
         return text._replace(data=[self.move_to(d, direction) for d in text.data])

@@ -2,7 +2,9 @@
 or summed against ciphertexts any number of times (pc_mult, pc_add, pc_dot, pc_matmul, pc_matmul_batch) — per-channel weights, masks, biases,
 convolution taps, layers.  The reference only has mc_mult / mc_add, which encode on every call; like the engine's other options beyond it, the words
 of these ops are DEFINED as compositions of ops the engine already has (written out in the docstrings), and that composition is
-what runs wherever the native call (lf_pc_dot, lf_pc_matmul, lf_pc_matmul_batch) does not apply.  DESIGN.md §4.2.
+what runs wherever the native call (lf_pc_dot, lf_pc_matmul, lf_pc_matmul_batch) does not apply.  A "mult" plaintext also has a
+compact form (compact_plain: fp64-class rows as 6-byte planes, three quarters of the memory at level 0 of the presets), which the
+four product ops take wherever they take the raw one (lf_pc_matmul_batch_planes).  DESIGN.md §4.2.
 """
 from __future__ import annotations
 
@@ -11,6 +13,7 @@ import ctypes
 import numpy as np
 import torch
 
+from .backend import SMALL_PRIME_LIMIT
 from .evaluator import is_struct
 from .presets import errors, types
 
@@ -19,13 +22,16 @@ class PlainOps:
     # =============================================================================================
     # the encoded object
     # =============================================================================================
-    def encode_plain(self, m, level: int, op: str = "mult"):
+    def encode_plain(self, m, level: int, op: str = "mult", compact: bool = False):
         """The plaintext mc_mult (op="mult") resp. mc_add (op="add") builds from the message `m` for a ciphertext at `level`, as
         a data_struct of its own (one [rows, N] tensor per local device) that save / load / cpu / cuda / clone treat like any other:
           "mult"  enter_ntt(tile_unsigned(encode(m * sqrt(deviations[level + 1]), 0), level)): NTT domain, Montgomery form;
-          "add"   mont_enter_scale(tile_unsigned(encode(m, level), level)): coefficient domain, Montgomery form."""
+          "add"   mont_enter_scale(tile_unsigned(encode(m, level), level)): coefficient domain, Montgomery form.
+        compact=True ("mult" only): compact_plain of that plaintext."""
         if op not in ("mult", "add"):
             raise ValueError(f"encode_plain: op must be 'mult' or 'add', got {op!r}")
+        if compact and op != "mult":
+            raise ValueError("encode_plain: only a 'mult' plaintext has a compact form")
         if not 0 <= level < self.num_levels:
             raise errors.MaximumLevelError(level=level, level_max=self.num_levels)
         if op == "mult":
@@ -34,18 +40,182 @@ class PlainOps:
             m = np.array(m) * np.sqrt(self.deviations[level + 1])
             pt = self.ntt.tile_unsigned(self.encode(m, 0), level)
             self.ntt.enter_ntt(pt, level)
-            return self._new(pt, types.origins["pt_mult"], level=level, ntt_state=True, montgomery_state=True)
+            pt = self._new(pt, types.origins["pt_mult"], level=level, ntt_state=True, montgomery_state=True)
+            return self.compact_plain(pt) if compact else pt
         pt = self.ntt.tile_unsigned(self.encode(m, level), level)
         self.ntt.mont_enter_scale(pt, level)
         return self._new(pt, types.origins["pt_add"], level=level, montgomery_state=True)
 
     # =============================================================================================
+    # the compact form of a "mult" plaintext ("plain planes", include/ckks_hip.h: lf_plain_planes)
+    # =============================================================================================
+    # One flat int64 tensor per local device, the rows of pt.data[i] back to back in their order: a row whose prime is below
+    # SMALL_PRIME_LIMIT (fp64 class) is 6 N bytes — u32 lo[N], then u16 hi[N] — of v = REDC(w), the plain word in [0, q] the product
+    # kernels form from the Montgomery word w on every read; any other row is its 8 N bytes as they are.
+    def _plain_primes(self, level, d):
+        return [int(self.ctx.q[i]) for i in self.ntt.p.destination_arrays[level][d]]
+
+    @staticmethod
+    def plain_planes_offsets(primes, N):
+        """Word offset of every row of a compact plaintext over `primes`, and the total behind them: rows + 1 entries."""
+        off = [0]
+        for q in primes:
+            off.append(off[-1] + (3 * N // 4 if q < SMALL_PRIME_LIMIT else N))
+        return off
+
+    @staticmethod
+    def _mulmod41(a, b, q):
+        """a b mod q for a tensor a in [0, q), Python ints b in [0, q) and q < 2^41 per row ([rows, 1] columns): b in three 14-bit
+        digits, every intermediate below 2^56."""
+        col = lambda v: torch.tensor(v, dtype=torch.int64, device=a.device).view(-1, 1)
+        qc = col(q)
+        acc = (a * col([x >> 28 for x in b])) % qc
+        acc = ((acc << 14) + a * col([(x >> 14) & 0x3fff for x in b])) % qc
+        return ((acc << 14) + a * col([x & 0x3fff for x in b])) % qc
+
+    def _planes_pack_rows(self, words, primes):
+        """[rows, N] stored words (v on fp64-class rows, w on the others) -> the flat compact tensor: pure byte moves."""
+        N = words.size(1)
+        off = self.plain_planes_offsets(primes, N)
+        flat = torch.empty(off[-1], dtype=torch.int64, device=words.device)
+        for r, q in enumerate(primes):
+            if q >= SMALL_PRIME_LIMIT:
+                flat[off[r]:off[r + 1]] = words[r]
+                continue
+            halves = words[r].contiguous().view(torch.int16).view(N, 4)          # little-endian: bits 0-15, 16-31, 32-47, 48-63
+            flat[off[r]:off[r] + N // 2].view(torch.int16).view(N, 2).copy_(halves[:, 0:2])
+            flat[off[r] + N // 2:off[r + 1]].view(torch.int16).copy_(halves[:, 2])
+        return flat
+
+    def _planes_unpack_rows(self, flat, primes, N):
+        """The inverse of _planes_pack_rows: the stored words as [rows, N]."""
+        off = self.plain_planes_offsets(primes, N)
+        if flat.dim() != 1 or flat.numel() != off[-1]:
+            raise errors.NotMatchDataStructState(origin=types.origins["pt_mult_planes"])
+        words = torch.zeros((len(primes), N), dtype=torch.int64, device=flat.device)
+        for r, q in enumerate(primes):
+            if q >= SMALL_PRIME_LIMIT:
+                words[r] = flat[off[r]:off[r + 1]]
+                continue
+            halves = words[r].view(torch.int16).view(N, 4)
+            halves[:, 0:2] = flat[off[r]:off[r] + N // 2].view(torch.int16).view(N, 2)
+            halves[:, 2] = flat[off[r] + N // 2:off[r + 1]].view(torch.int16)
+        return words
+
+    def _planes_host(self, t, primes):
+        """compact_plain's words in torch, on whatever device t is: REDC(w) = w R^-1 mod q as the representative REDC62 returns for a
+        lazy w < 2q — the canonical residue, except that w = q gives q itself."""
+        small = [r for r, q in enumerate(primes) if q < SMALL_PRIME_LIMIT]
+        words = t.clone()
+        if small:
+            q = [primes[r] for r in small]
+            qc = torch.tensor(q, dtype=torch.int64, device=t.device).view(-1, 1)
+            w = t[small]
+            v = self._mulmod41(w % qc, [pow(self.ctx.R, -1, x) for x in q], q)
+            words[small] = torch.where(w == qc, qc, v)
+        return self._planes_pack_rows(words, primes)
+
+    def _unplanes_host(self, flat, primes, N):
+        words = self._planes_unpack_rows(flat, primes, N)
+        qall = torch.tensor(primes, dtype=torch.int64, device=flat.device).view(-1, 1)
+        small = [r for r, q in enumerate(primes) if q < SMALL_PRIME_LIMIT]
+        out = words % qall
+        if small:
+            q = [primes[r] for r in small]
+            out[small] = self._mulmod41(out[small], [self.ctx.R % x for x in q], q)
+        return out
+
+    def _planes_native_ok(self, t, rows):
+        return t.is_cuda and hasattr(self.backend, "plain_planes") and 13 <= self.ctx.logN <= 17 and t.dtype == torch.int64 \
+            and rows <= self.backend.plain_planes_max_rows and t.is_contiguous() and t.data_ptr() % 16 == 0
+
+    def compact_plain(self, pt):
+        """The compact form of a "mult" plaintext: same level, same hash, ONE flat tensor per local device with the fp64-class rows
+        as 6-byte planes (8 rows N -> (6 n_small + 8 n_int) N bytes; level 0 of the presets: about three quarters).  pc_mult, pc_dot,
+        pc_matmul and pc_matmul_batch take it wherever they take pt; clone, cpu, cuda, save and load treat it like pt.  A compact
+        plaintext is returned as it is; anything else than a "mult" plaintext raises NotMatchType.  One native launch per device where
+        the tensor is on the GPU (logN 13 .. 17), the same words in torch elsewhere."""
+        if is_struct(pt) and pt.origin == types.origins["pt_mult_planes"]:
+            return pt
+        self._check_plain(pt, "mult")
+        self._enter()
+        data = []
+        for d, t in zip(self._loc(pt.level), pt.data):
+            primes = self._plain_primes(pt.level, d)
+            if self._planes_native_ok(t, len(primes)):
+                c = self._consts(d, pt.level, False)
+                flat = torch.empty(self.backend.plain_planes_words(len(primes), self.ctx.N, c), dtype=torch.int64, device=t.device)
+                self.backend.plain_planes(t, flat, c)
+            else:
+                flat = self._planes_host(t, primes)
+            data.append(flat)
+        return pt._replace(data=data, origin=types.origins["pt_mult_planes"])
+
+    def expand_plain(self, pt):
+        """The inverse of compact_plain: a "mult" plaintext that holds the canonical Montgomery residue w mod q of every word the
+        compact one was made from (the same residues: every product op gives the same words).  A raw "mult" plaintext is returned
+        as it is."""
+        self._check_plain(pt, "mult", planes_ok=True)
+        if pt.origin == types.origins["pt_mult"]:
+            return pt
+        self._enter()
+        N, data = self.ctx.N, []
+        for d, flat in zip(self._loc(pt.level), pt.data):
+            primes = self._plain_primes(pt.level, d)
+            if flat.dim() == 1 and flat.numel() == self.plain_planes_offsets(primes, N)[-1] and self._planes_native_ok(flat, len(primes)):
+                t = torch.empty((len(primes), N), dtype=torch.int64, device=flat.device)
+                self.backend.plain_unplanes(flat, t, self._consts(d, pt.level, False))
+            else:
+                t = self._unplanes_host(flat, primes, N)
+            data.append(t)
+        return pt._replace(data=data, origin=types.origins["pt_mult"])
+
+    def _move_plain_planes(self, pt, direction):
+        """cpu() / cuda() of a compact plaintext: the stored words as rows, moved like any other rows, packed again over the primes
+        of where they arrive (the host form: every row of the level, in the order of the prime chain).  Byte moves only."""
+        N, lvl = self.ctx.N, pt.level
+        dest = self.ntt.p.destination_arrays[lvl]
+        chain = [int(self.ctx.q[i]) for i in sorted(i for d in dest for i in d)]
+        if direction == "gpu2cpu":
+            rows = [self._planes_unpack_rows(t, self._plain_primes(lvl, d), N) for d, t in zip(self._loc(lvl), pt.data)]
+            host = self.download_to_cpu(rows, lvl, False)[0]
+            return pt._replace(data=[self._planes_pack_rows(host[:len(chain)], chain)])
+        host = self._planes_unpack_rows(pt.data[0], chain, N)
+        rows = self.upload_to_gpu([host], lvl, False)
+        return pt._replace(data=[self._planes_pack_rows(t, self._plain_primes(lvl, d)) for d, t in zip(self._loc(lvl), rows)])
+
+    @staticmethod
+    def _plain_kind(pts, op):
+        """True where the "mult" plaintexts of a call are all compact, False where none is; a mix is refused."""
+        kinds = {pt.origin == types.origins["pt_mult_planes"] for pt in pts}
+        if len(kinds) > 1:
+            raise ValueError(f"{op}: compact and raw plaintexts in one call (compact_plain or expand_plain them all)")
+        return kinds == {True}
+
+    def _expanded(self, pts):
+        """{id: expand_plain} of the distinct objects among pts (None skipped)."""
+        out = {}
+        for pt in pts:
+            if pt is not None and id(pt) not in out:
+                out[id(pt)] = self.expand_plain(pt)
+        return out
+
+    def _pc_planes_native(self, l):
+        """The device where lf_pc_matmul_batch_planes applies at level l -> l + 1 (the native conditions of the raw ops), or None."""
+        d = self._native_level(l + 1)
+        if d is None or self._native_level(l) != d or not hasattr(self.backend, "pc_matmul_batch_planes_call") \
+                or not 13 <= self.ctx.logN <= 17 or len(self.ntt.p.destination_arrays[l][d]) > self.backend.plain_planes_max_rows \
+                or list(self.ntt.p.destination_arrays[l][d][1:]) != list(self.ntt.p.destination_arrays[l + 1][d]):
+            return None
+        return d
+
+    # =============================================================================================
     # checks (all before any launch)
     # =============================================================================================
     @staticmethod
-    def _check_plain(pt, kind):
+    def _check_plain(pt, kind, planes_ok=False):
         want = types.origins["pt_" + kind]
-        if not is_struct(pt) or pt.origin != want:
+        if not is_struct(pt) or (pt.origin != want and not (planes_ok and pt.origin == types.origins["pt_mult_planes"])):
             raise errors.NotMatchType(origin=getattr(pt, "origin", type(pt).__name__), to=want)
         if pt.include_special or not pt.montgomery_state or pt.ntt_state != (kind == "mult"):
             raise errors.NotMatchDataStructState(origin=pt.origin)
@@ -58,7 +228,7 @@ class PlainOps:
             raise errors.NotMatchDataStructState(origin=ct.origin)
 
     def _check_plain_pair(self, pt, ct, kind):
-        self._check_plain(pt, kind)
+        self._check_plain(pt, kind, planes_ok=kind == "mult")
         self._check_plain_operand(ct)
         if pt.level != ct.level:
             raise errors.NotMatchDataStructState(origin=f"{pt.origin} at level {pt.level} beside level {ct.level}")
@@ -68,12 +238,14 @@ class PlainOps:
     # =============================================================================================
     def pc_mult(self, pt, ct):
         """mc_mult(m, ct) for pt = encode_plain(m, ct.level): mc_mult's body behind its encode, the same words whenever encode
-        returns the same polynomial."""
+        returns the same polynomial.  A compact pt (compact_plain) goes through pc_dot's one-pair path: the same words."""
         self._enter()
         self._check_plain_pair(pt, ct, "mult")
         l = ct.level
         if l + 1 >= self.num_levels:
             raise errors.MaximumLevelError(level=l, level_max=self.num_levels)
+        if pt.origin == types.origins["pt_mult_planes"]:
+            return self.pc_dot([(pt, ct)])
         out = self.clone(ct)
         self.ntt.enter_ntt(out.data[0], l)
         self.ntt.enter_ntt(out.data[1], l)
@@ -105,7 +277,9 @@ class PlainOps:
             intt_exit_reduce(S_c);  out = rescale((S_0, S_1));  out = pc_add(bias, out)  if bias is given
         (one pair without bias: pc_mult), which is also what runs where the native call does not apply: several devices or ranks,
         logN outside 13..17, a checker backend, operands that are not contiguous or not 16-byte aligned.  Otherwise ONE native call
-        (lf_pc_dot)."""
+        (lf_pc_dot).  The pt_i may all be compact (compact_plain; a mix raises ValueError): the result has exactly the words of the
+        call on expand_plain of each — which are those of the call on the plaintexts they were compacted from — through ONE
+        lf_pc_matmul_batch_planes call under the same conditions, and through expand_plain and the paths above elsewhere."""
         self._enter()
         pairs = [tuple(p) for p in pairs]
         if not pairs:
@@ -113,8 +287,9 @@ class PlainOps:
         for pair in pairs:
             if len(pair) != 2:
                 raise ValueError("pc_dot: pairs of an encoded plaintext and a ciphertext")
-            self._check_plain(pair[0], "mult")
+            self._check_plain(pair[0], "mult", planes_ok=True)
             self._check_plain_operand(pair[1])
+        compact = self._plain_kind([pt for pt, _ in pairs], "pc_dot")
         l = pairs[0][1].level
         for pt, ct in pairs:
             for x in (pt, ct):
@@ -126,6 +301,13 @@ class PlainOps:
                 raise errors.NotMatchDataStructState(origin=f"{bias.origin} at level {bias.level} beside level {l + 1}")
         if l + 1 >= self.num_levels:
             raise errors.MaximumLevelError(level=l, level_max=self.num_levels)
+        if compact:
+            d = self._pc_planes_native(l)
+            if d is not None and all(self._pc_operand_ok(t) for pt, ct in pairs for t in (pt.data[0], ct.data[0][0], ct.data[1][0])) \
+                    and (bias is None or self._pc_operand_ok(bias.data[0])):
+                return self._pc_matmul_batch_native([[pt for pt, _ in pairs]], [[ct for _, ct in pairs]], [bias], l, d, planes=True)[0][0]
+            raw = self._expanded(pt for pt, _ in pairs)
+            return self.pc_dot([(raw[id(pt)], ct) for pt, ct in pairs], bias)
         d = self._native_level(l + 1)
         # (16-byte loads: a contiguous view at an odd word offset takes the composition, as do rows in another order than the
         # dropped limb first and the survivors behind it)
@@ -160,7 +342,8 @@ class PlainOps:
                 raise ValueError("pc_matmul: a row without a plaintext")
             for pt in row:
                 if pt is not None:
-                    self._check_plain(pt, "mult")
+                    self._check_plain(pt, "mult", planes_ok=True)
+        self._plain_kind([pt for row in W for pt in row if pt is not None], "pc_matmul")
         for ct in cts:
             self._check_plain_operand(ct)
         l = cts[0].level
@@ -190,12 +373,24 @@ class PlainOps:
             pc_dot([(W[o][i], cts[i]) for i in range(k_in) if W[o][i] is not None], bias[o])
         and that loop is what runs where the native call does not apply (pc_dot's conditions).  Otherwise ONE native call
         (lf_pc_matmul) per 64 outputs: every ciphertext is transformed once, whatever k_out, and every transformed word is read
-        once per group of four outputs."""
+        once per group of four outputs.  The entries of W may all be compact (compact_plain; a mix raises ValueError): the same
+        words as on expand_plain of each, through ONE lf_pc_matmul_batch_planes call per 64 outputs under the same conditions, and
+        through expand_plain and the paths above elsewhere."""
         self._enter()
         W = [list(row) for row in W]
         cts = list(cts)
         k_out = len(W)
         bias, l = self._pc_matmul_checked(W, cts, None if bias is None else list(bias))
+        if next(pt for pt in W[0] if pt is not None).origin == types.origins["pt_mult_planes"]:
+            d = self._pc_planes_native(l)
+            tensors = [t for ct in cts for t in (ct.data[0][0], ct.data[1][0])]
+            tensors += [x.data[0] for x in {id(x): x for x in [pt for row in W for pt in row] + bias if x is not None}.values()]
+            if d is not None and all(self._pc_operand_ok(t) for t in tensors):
+                step = self.backend.pc_matmul_max_outputs
+                return [out for o0 in range(0, k_out, step)
+                        for out in self._pc_matmul_batch_native(W[o0:o0 + step], [cts], bias[o0:o0 + step], l, d, planes=True)[0]]
+            raw = self._expanded(pt for row in W for pt in row)
+            return self.pc_matmul([[None if pt is None else raw[id(pt)] for pt in row] for row in W], cts, bias)
         d = self._native_level(l + 1)
         if d is not None and self._native_level(l) == d and hasattr(self.backend, "pc_matmul_native") and self.ctx.logN <= 17 \
                 and list(self.ntt.p.destination_arrays[l][d][1:]) == list(self.ntt.p.destination_arrays[l + 1][d]):
@@ -253,7 +448,10 @@ class PlainOps:
         pc_matmul_batch_sizes (pairs) through ONE native call per group and per 64 outputs: a group shares every product launch,
         which reads each plaintext word — the larger stream of pc_matmul's products — once per group instead of once per token.  A token
         that does not qualify (a component that is not contiguous, not 16-byte aligned or on the host), the one the groups leave
-        over, and every token on a backend without the entry take pc_matmul and keep their place."""
+        over, and every token on a backend without the entry take pc_matmul and keep their place.  The entries of W may all be
+        compact (compact_plain; a mix raises ValueError): the same group sizes and the same left-over rule, every native call
+        lf_pc_matmul_batch_planes; where that entry does not apply to W (several devices or ranks, a checker backend, logN outside
+        13..17) the plaintexts are expanded once for the call and the paths above run."""
         self._enter()
         X = [list(cts) for cts in X]
         if not X:
@@ -267,8 +465,13 @@ class PlainOps:
         out = [None] * len(X)
         ready = []
         sizes = [k for k in self.pc_matmul_batch_sizes if k in getattr(self.backend, "pc_matmul_batch_sizes", ())]
+        planes = next(pt for pt in W[0] if pt is not None).origin == types.origins["pt_mult_planes"]
+        if planes and self._pc_planes_native(l) is None:
+            raw = self._expanded(pt for row in W for pt in row)
+            return self.pc_matmul_batch([[None if pt is None else raw[id(pt)] for pt in row] for row in W], X, bias)
         d = self._native_level(l + 1)
-        if sizes and d is not None and self._native_level(l) == d and hasattr(self.backend, "pc_matmul_batch_native") \
+        if sizes and d is not None and self._native_level(l) == d \
+                and hasattr(self.backend, "pc_matmul_batch_planes_call" if planes else "pc_matmul_batch_native") \
                 and 13 <= self.ctx.logN <= 17 \
                 and list(self.ntt.p.destination_arrays[l][d][1:]) == list(self.ntt.p.destination_arrays[l + 1][d]) \
                 and all(self._pc_operand_ok(x.data[0])
@@ -280,7 +483,7 @@ class PlainOps:
             if g is None:
                 break
             group, ready = ready[:g], ready[g:]
-            parts = [self._pc_matmul_batch_native(W[o0:o0 + step], [X[t] for t in group], bias[o0:o0 + step], l, d)
+            parts = [self._pc_matmul_batch_native(W[o0:o0 + step], [X[t] for t in group], bias[o0:o0 + step], l, d, planes=planes)
                      for o0 in range(0, k_out, step)]
             for j, t in enumerate(group):
                 out[t] = [o for part in parts for o in part[j]]
@@ -289,8 +492,12 @@ class PlainOps:
                 out[t] = self.pc_matmul(W, cts, bias)
         return out
 
-    def _pc_matmul_batch_native(self, W, toks, bias, l, d):
+    def _pc_matmul_batch_native(self, W, toks, bias, l, d, planes=False):
+        """One lf_pc_matmul_batch call, or (planes: every plaintext of W compact) one lf_pc_matmul_batch_planes call, of any nt >= 1."""
         N, k_out, k_in, nt = self.ctx.N, len(W), len(toks[0]), len(toks)
+        be = self.backend
+        ws_words, native = (be.pc_matmul_batch_planes_ws_words, be.pc_matmul_batch_planes_call) if planes else \
+            (be.pc_matmul_batch_ws_words, be.pc_matmul_batch_native)
         rows = len(self.ntt.p.destination_arrays[l][d])          # the dropped limb first
         owner = self.ntt.p.rescaler_loc[l]
         round_at = self.ctx.q[self.ntt.p.destination_arrays[l][owner][0]] // 2
@@ -310,11 +517,11 @@ class PlainOps:
         dev = self.ntt.devices[d]
         ident = self._pc_identity(l, d)
         chunk = min(k_in, self.backend.pc_matmul_chunk)
-        ws = self._ws("pc_matmul_batch_ws", (self.backend.pc_matmul_batch_ws_words(nt, chunk, k_out, rows, self.ctx.logN),), d)
+        ws = self._ws("pc_matmul_batch_ws", (ws_words(nt, chunk, k_out, rows, self.ctx.logN),), d)
         outs = [[[torch.empty((rows - 1, N), dtype=torch.int64, device=dev) for _ in range(2)] for _ in range(k_out)] for _ in range(nt)]
-        self.backend.pc_matmul_batch_native(ins, pts, biases, outs, nt, k_in, k_out, rows, self.ctx.logN, self._tw(d, l, False),
-                                            self._tw(d, l, False, True), self._vec("Rs", d, l, False), self._vec("Ninv", d, l, False),
-                                            ident[0], ident[1], self.rescale_scales[l][d], round_at, ws, self._consts(d, l, False))
+        native(ins, pts, biases, outs, nt, k_in, k_out, rows, self.ctx.logN, self._tw(d, l, False),
+               self._tw(d, l, False, True), self._vec("Rs", d, l, False), self._vec("Ninv", d, l, False),
+               ident[0], ident[1], self.rescale_scales[l][d], round_at, ws, self._consts(d, l, False))
         return [[self._new(([o[0]], [o[1]]), types.origins["ct"], level=l + 1) for o in tok] for tok in outs]
 
     def _pc_identity(self, l, d):

@@ -1038,8 +1038,9 @@ int lf_pc_dot(int k, const int64_t *const *in, const int64_t *const *pt, const i
  * transformed) their forward transforms as lf_pc_dot runs them — lf_rescale_ntt with the identity rescale, RELAXED | PLAIN,
  * PLANES where lf_stack_planes says so, 4, 2 or 1 ciphertexts per call — into consecutive slots of the workspace: every input is
  * transformed ONCE per call of the entry, whatever k_out; per chunk and per group of 4, 2 or 1 outputs ONE launch of
- * pc_matmul_kernel<4 | 2 | 1> (grid N / 512 x rows; a thread reads the two transformed pairs of an input once for its group's
- * outputs and each plaintext pair once) adding the chunk's products into the group's pairs of S = [k_out][2][rows][N] (the first
+ * pc_matmul_kernel<4 | 2 | 1> (the product body shared with lf_pc_matmul_batch and lf_pc_matmul_batch_planes, at one token and raw
+ * plaintexts; grid N / 512 x rows; a thread reads the two transformed pairs of an input once for its group's outputs and each
+ * plaintext pair once) adding the chunk's products into the group's pairs of S = [k_out][2][rows][N] (the first
  * chunk writes); ONE lf_intt (tail 2, relaxed, plain) of the 2 k_out polynomials of S; lf_rescale_batch per 4 outputs; one
  * pc_bias_kernel launch per output that has a bias.
  * ws: lf_pc_matmul_ws_words(k_in, k_out, rows, logN) = (2 min(k_in, LF_PC_MATMUL_CI) + 2 k_out) rows N words (0 for shapes the
@@ -1067,8 +1068,8 @@ int lf_pc_matmul(int k_in, int k_out, const int64_t *const *in, const int64_t *c
  * Enqueued, for the inputs some output uses, in chunks of at most LF_PC_MATMUL_CI: per token the chunk's forward transforms as
  * lf_pc_matmul runs them, into x = [nt][n][2][rows][N] (a token's slots 2 min(k_in, LF_PC_MATMUL_CI) polynomials apart): every
  * (token, input) is transformed once per call; per chunk and per group of 4, 2 or 1 outputs ONE launch of pc_matmulb_kernel<GO, 2>
- * per tile of 2 tokens (a thread reads the two transformed pairs of each of its tokens once and each plaintext pair ONCE for both)
- * and lf_pc_matmul's own pc_matmul_kernel<GO> for an odd token left (3 tokens: 2 + 1; 4: 2 + 2 — one launch of <GO, 4> measured
+ * per tile of 2 tokens (the same body with two accumulator sets: a thread reads the two transformed pairs of each of its tokens
+ * once and each plaintext pair ONCE for both) and lf_pc_matmul's pc_matmul_kernel<GO> for an odd token left (3 tokens: 2 + 1; 4: 2 + 2 — one launch of <GO, 4> measured
  * slower, LF_TUNE_PC_MATMUL_TILE), into S = [nt][k_out][2][rows][N] (the first chunk writes); lf_intt (tail
  * 2, relaxed, plain) of the 2 k_out nt polynomials of S in ONE call up to 128 polynomials (the largest batch lf_pc_matmul hands
  * it), per token beyond; lf_rescale_batch per 4 outputs and pc_bias_kernel per output with a bias, per token.  nt = 1 enqueues
@@ -1108,7 +1109,8 @@ int lf_plain_unplanes(const int64_t *src, int64_t *dst, int rows, int64_t N, con
  * chunking, output groups, token tiles, transforms, rescales and biases are lf_pc_matmul_batch's (nt = 1: lf_pc_matmul; nt = 1,
  * k_out = 1: lf_pc_dot's sum), and so are the words of every output — those of lf_pc_matmul_batch on the plaintexts the planes were
  * packed from: the stored fp64-class word is the one the raw kernels compute on load.  The product launches are
- * pc_planes_matmul_kernel<GO, GT> (GT = 1, 2: the tiles of lf_pc_matmul_batch; 4 under LF_TUNE_PC_MATMUL_TILE): per plaintext and pair of
+ * pc_planes_matmul_kernel<GO, GT> (the body of the raw kernels with the plaintext side chosen at compile time; GT = 1, 2: the tiles
+ * of lf_pc_matmul_batch; 4 under LF_TUNE_PC_MATMUL_TILE): per plaintext and pair of
  * coefficients an 8-byte and a 4-byte nontemporal load on fp64-class rows and no REDC, the 16-byte pair at the row's compact offset
  * on integer-class rows; the offset is derived in the kernel from a bit mask of the fp64-class rows (a kernel argument built from
  * q_host: no table, no copy).  ws: lf_pc_matmul_batch_planes_ws_words = lf_pc_matmul_batch_ws_words, 0 also for rows >

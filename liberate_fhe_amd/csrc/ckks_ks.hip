@@ -732,219 +732,6 @@ __global__ void __launch_bounds__(256) pc_bias_kernel(i64 *__restrict__ c0, cons
     *reinterpret_cast<longlong2 *>(c0 + off) = o;
 }
 
-// ---- pc_matmul: GO outputs' sums over the SAME n transformed ciphertexts (a plaintext matrix times a vector of ciphertexts) ----
-// x = [n][2][rows][N]: the chunk's transformed pairs as pc_dot_kernel reads them; pt[i][g]: the plaintext of input i for output g
-// of the group, or nullptr for an absent term (kernel arguments: the test is uniform over the launch);
-// S = [GO][2][rows][N]: the group's pairs (first: written without being read, zeros where an output has no term in the chunk).
-//     S0_g += sum_i pt_{i,g} c0_i,   S1_g += sum_i pt_{i,g} c1_i
-// grid and thread as pc_dot_kernel; the loop over the inputs is a run-time one: a thread reads the two transformed pairs of an
-// input ONCE for its GO outputs (ordinary loads: the next group reads them again) and every plaintext pair once per call
-// (nontemporal).  The arithmetic is pc_dot_kernel's; only the residues of S reach the result, so the grouping of the additions
-// is free.  Bounds over a chunk of n <= LF_PC_MATMUL_CI inputs:
-//   fp64-class rows  n balanced products (|.| <= q / 2 each) plus the one canonical word read back:
-//                    |.| <= LF_PC_MATMUL_CI q / 2 + q <= 9 q < 2^45 for q < 2^41 — inside dp_reduce's |x| < 64 q (which holds up to
-//                    a chunk of 125) and the exact range of fp64; stored as the plain canonical residue;
-//   integer rows     a conditional subtraction after every addition: Montgomery form below 2q throughout.
-struct PcMatTerms {
-    const i64 *pt[LF_PC_MATMUL_CI][4];   // [input of the chunk][output of the group], [rows][N] each or nullptr
-};
-static_assert(LF_PC_MATMUL_CI >= 1 && LF_PC_MATMUL_CI / 2 + 1 < 64, "pc_matmul_kernel: a chunk's sum must stay inside dp_reduce's |x| < 64 q");
-
-template <int GO>
-__global__ void __launch_bounds__(256) pc_matmul_kernel(const i64 *__restrict__ x, PcMatTerms pa, i64 *__restrict__ S, int n, int rows, i64 N,
-                                                        int xpl, int first, const i64 *__restrict__ ql, const i64 *__restrict__ qh,
-                                                        const i64 *__restrict__ kl, const i64 *__restrict__ kh) {
-    const int r = blockIdx.y;
-    const i64 j0 = (i64)blockIdx.x * 512 + threadIdx.x * 2;
-    if (j0 >= N) return;
-    const RowMod m = load_mod(ql, qh, kl, kh, r);
-    const i64 pstride = (i64)rows * N, o0 = (i64)r * N + j0;
-    i64 *s = S + o0;
-    longlong2 o[GO][2];
-    if (m.q < SMALL_PRIME_LIMIT) {
-        const RowDp d = make_dp(m);
-        double a[GO][2][2];
-#pragma unroll
-        for (int g = 0; g < GO; ++g) a[g][0][0] = a[g][0][1] = a[g][1][0] = a[g][1][1] = 0.0;
-        for (int i = 0; i < n; ++i) {
-            const i64 *xs = x + (i64)i * 2 * pstride + (i64)r * N;
-            double c0[2], c1[2];
-            ld_pair_dp(xs, j0, N, xpl, c0[0], c0[1]);
-            ld_pair_dp(xs + pstride, j0, N, xpl, c1[0], c1[1]);
-#pragma unroll
-            for (int g = 0; g < GO; ++g) {
-                const i64 *p = pa.pt[i][g];
-                if (p == nullptr) continue;   // (uniform: a kernel argument)
-                const longlong2 w = ld_nt(p + o0);
-                const double wp[2] = {dp_from_word(mm62u((u64)w.x, 1ull, m.q, m.k)), dp_from_word(mm62u((u64)w.y, 1ull, m.q, m.k))};
-#pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    a[g][0][e] += dp_mulmod_bal(c0[e], wp[e], d);
-                    a[g][1][e] += dp_mulmod_bal(c1[e], wp[e], d);
-                }
-            }
-        }
-#pragma unroll
-        for (int g = 0; g < GO; ++g)
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                if (!first) {
-                    const longlong2 v = *reinterpret_cast<const longlong2 *>(s + (2 * g + c) * pstride);
-                    a[g][c][0] += dp_from_word(v.x), a[g][c][1] += dp_from_word(v.y);
-                }
-                o[g][c].x = dp_to_word(dp_reduce(a[g][c][0], d.q, d.qinv));
-                o[g][c].y = dp_to_word(dp_reduce(a[g][c][1], d.q, d.qinv));
-            }
-    } else {
-        i64 a[GO][2][2];
-#pragma unroll
-        for (int g = 0; g < GO; ++g) a[g][0][0] = a[g][0][1] = a[g][1][0] = a[g][1][1] = 0;
-        for (int i = 0; i < n; ++i) {
-            const i64 *xs = x + (i64)i * 2 * pstride + o0;
-            const longlong2 C0 = *reinterpret_cast<const longlong2 *>(xs), C1 = *reinterpret_cast<const longlong2 *>(xs + pstride);
-            const u64 c0[2] = {(u64)C0.x, (u64)C0.y}, c1[2] = {(u64)C1.x, (u64)C1.y};
-#pragma unroll
-            for (int g = 0; g < GO; ++g) {
-                const i64 *p = pa.pt[i][g];
-                if (p == nullptr) continue;
-                const longlong2 w = ld_nt(p + o0);
-                const u64 wm[2] = {(u64)w.x, (u64)w.y};
-#pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    a[g][0][e] = csub(a[g][0][e] + mm62u(c0[e], wm[e], m.q, m.k), m.q2);
-                    a[g][1][e] = csub(a[g][1][e] + mm62u(c1[e], wm[e], m.q, m.k), m.q2);
-                }
-            }
-        }
-#pragma unroll
-        for (int g = 0; g < GO; ++g)
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                if (!first) {
-                    const longlong2 v = *reinterpret_cast<const longlong2 *>(s + (2 * g + c) * pstride);
-                    a[g][c][0] = csub(a[g][c][0] + v.x, m.q2), a[g][c][1] = csub(a[g][c][1] + v.y, m.q2);
-                }
-                o[g][c].x = a[g][c][0], o[g][c].y = a[g][c][1];
-            }
-    }
-#pragma unroll
-    for (int g = 0; g < GO; ++g)
-#pragma unroll
-        for (int c = 0; c < 2; ++c) *reinterpret_cast<longlong2 *>(s + (2 * g + c) * pstride) = o[g][c];
-}
-
-// ---- pc_matmul_batch: pc_matmul_kernel over GT token vectors that share the plaintexts (lf_pc_matmul_batch) -----------------
-// x: token t's chunk [n][2][rows][N] at x + t * xtok; S: token t's group [GO][2][rows][N] at S + t * stok; pa: the SAME table for
-// every token.  grid and thread as pc_matmul_kernel.  Per input of the run-time loop a thread loads the two transformed pairs of
-// each of its GT tokens once and, per non-NULL output of its group, the plaintext pair ONCE (nontemporal) — on fp64-class rows it
-// is converted to the plain word once, not once per token — and forms the GO GT 2 2 products from registers: the plaintext
-// stream, the larger one of pc_matmul_kernel, is divided by GT.  Arithmetic and bounds are pc_matmul_kernel's per (token, output)
-// accumulator (fp64 rows: at most LF_PC_MATMUL_CI balanced products plus the word read back, <= 9 q; integer rows: a conditional
-// subtraction after every addition), so output (t, g) has the words pc_matmul_kernel<GO> gives on token t.
-template <int GO, int GT>
-__global__ void __launch_bounds__(256) pc_matmulb_kernel(const i64 *__restrict__ x, i64 xtok, PcMatTerms pa, i64 *__restrict__ S, i64 stok,
-                                                         int n, int rows, i64 N, int xpl, int first, const i64 *__restrict__ ql,
-                                                         const i64 *__restrict__ qh, const i64 *__restrict__ kl,
-                                                         const i64 *__restrict__ kh) {
-    const int r = blockIdx.y;
-    const i64 j0 = (i64)blockIdx.x * 512 + threadIdx.x * 2;
-    if (j0 >= N) return;
-    const RowMod m = load_mod(ql, qh, kl, kh, r);
-    const i64 pstride = (i64)rows * N, o0 = (i64)r * N + j0;
-    i64 *s = S + o0;
-    if (m.q < SMALL_PRIME_LIMIT) {
-        const RowDp d = make_dp(m);
-        double a[GT][GO][2][2];
-#pragma unroll
-        for (int t = 0; t < GT; ++t)
-#pragma unroll
-            for (int g = 0; g < GO; ++g) a[t][g][0][0] = a[t][g][0][1] = a[t][g][1][0] = a[t][g][1][1] = 0.0;
-        for (int i = 0; i < n; ++i) {
-            double c0[GT][2], c1[GT][2];
-#pragma unroll
-            for (int t = 0; t < GT; ++t) {
-                const i64 *xs = x + t * xtok + (i64)i * 2 * pstride + (i64)r * N;
-                ld_pair_dp(xs, j0, N, xpl, c0[t][0], c0[t][1]);
-                ld_pair_dp(xs + pstride, j0, N, xpl, c1[t][0], c1[t][1]);
-            }
-#pragma unroll
-            for (int g = 0; g < GO; ++g) {
-                const i64 *p = pa.pt[i][g];
-                if (p == nullptr) continue;   // (uniform: a kernel argument)
-                const longlong2 w = ld_nt(p + o0);
-                const double wp[2] = {dp_from_word(mm62u((u64)w.x, 1ull, m.q, m.k)), dp_from_word(mm62u((u64)w.y, 1ull, m.q, m.k))};
-#pragma unroll
-                for (int t = 0; t < GT; ++t)
-#pragma unroll
-                    for (int e = 0; e < 2; ++e) {
-                        a[t][g][0][e] += dp_mulmod_bal(c0[t][e], wp[e], d);
-                        a[t][g][1][e] += dp_mulmod_bal(c1[t][e], wp[e], d);
-                    }
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < GT; ++t)
-#pragma unroll
-            for (int g = 0; g < GO; ++g)
-#pragma unroll
-                for (int c = 0; c < 2; ++c) {
-                    i64 *at = s + t * stok + (2 * g + c) * pstride;
-                    if (!first) {
-                        const longlong2 v = *reinterpret_cast<const longlong2 *>(at);
-                        a[t][g][c][0] += dp_from_word(v.x), a[t][g][c][1] += dp_from_word(v.y);
-                    }
-                    longlong2 o;
-                    o.x = dp_to_word(dp_reduce(a[t][g][c][0], d.q, d.qinv));
-                    o.y = dp_to_word(dp_reduce(a[t][g][c][1], d.q, d.qinv));
-                    *reinterpret_cast<longlong2 *>(at) = o;
-                }
-    } else {
-        i64 a[GT][GO][2][2];
-#pragma unroll
-        for (int t = 0; t < GT; ++t)
-#pragma unroll
-            for (int g = 0; g < GO; ++g) a[t][g][0][0] = a[t][g][0][1] = a[t][g][1][0] = a[t][g][1][1] = 0;
-        for (int i = 0; i < n; ++i) {
-            u64 c0[GT][2], c1[GT][2];
-#pragma unroll
-            for (int t = 0; t < GT; ++t) {
-                const i64 *xs = x + t * xtok + (i64)i * 2 * pstride + o0;
-                const longlong2 C0 = *reinterpret_cast<const longlong2 *>(xs), C1 = *reinterpret_cast<const longlong2 *>(xs + pstride);
-                c0[t][0] = (u64)C0.x, c0[t][1] = (u64)C0.y, c1[t][0] = (u64)C1.x, c1[t][1] = (u64)C1.y;
-            }
-#pragma unroll
-            for (int g = 0; g < GO; ++g) {
-                const i64 *p = pa.pt[i][g];
-                if (p == nullptr) continue;
-                const longlong2 w = ld_nt(p + o0);
-                const u64 wm[2] = {(u64)w.x, (u64)w.y};
-#pragma unroll
-                for (int t = 0; t < GT; ++t)
-#pragma unroll
-                    for (int e = 0; e < 2; ++e) {
-                        a[t][g][0][e] = csub(a[t][g][0][e] + mm62u(c0[t][e], wm[e], m.q, m.k), m.q2);
-                        a[t][g][1][e] = csub(a[t][g][1][e] + mm62u(c1[t][e], wm[e], m.q, m.k), m.q2);
-                    }
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < GT; ++t)
-#pragma unroll
-            for (int g = 0; g < GO; ++g)
-#pragma unroll
-                for (int c = 0; c < 2; ++c) {
-                    i64 *at = s + t * stok + (2 * g + c) * pstride;
-                    if (!first) {
-                        const longlong2 v = *reinterpret_cast<const longlong2 *>(at);
-                        a[t][g][c][0] = csub(a[t][g][c][0] + v.x, m.q2), a[t][g][c][1] = csub(a[t][g][c][1] + v.y, m.q2);
-                    }
-                    longlong2 o;
-                    o.x = a[t][g][c][0], o.y = a[t][g][c][1];
-                    *reinterpret_cast<longlong2 *>(at) = o;
-                }
-    }
-}
-
 // ---- plain planes: a "mult" plaintext with its fp64-class rows as 6-byte planes (lf_plain_planes, include/ckks_hip.h) ----------
 // Rows back to back in row order: an fp64-class row is 6 N bytes — u32 lo[N], then u16 hi[N] — of v = mm62u(w, 1, q, k), the plain
 // word in [0, q] pc_matmul_kernel forms from the Montgomery word w on every read; an integer-class row is its 8 N bytes as they
@@ -997,27 +784,51 @@ __global__ void __launch_bounds__(256) plain_unplanes_kernel(const i64 *__restri
     *reinterpret_cast<longlong2 *>(dst + (i64)r * N + j) = o;
 }
 
-// ---- pc_matmul / pc_matmul_batch over plain planes (lf_pc_matmul_batch_planes): pc_matmul_kernel<GO> (GT = 1) and
-// pc_matmulb_kernel<GO, GT> with every plaintext in the format above.  x, S, pa, grid and thread as pc_matmulb_kernel's.  On
-// fp64-class rows a thread loads the lo pair (8 bytes) and the hi pair (4 bytes) of a plaintext, nontemporal as the raw word
-// is, and assembles the plain word with dp_from_planes: the REDC of the raw kernels ran once, in the packer.  On integer-class
-// rows it reads the 16-byte pair at the row's compact offset.  The words that enter the sums are those of the raw kernels, so
-// their accumulation, bounds (fp64 rows: at most LF_PC_MATMUL_CI balanced products plus the word read back, <= 9 q; integer rows: a
-// conditional subtraction after every addition), read-add-write of S and stores stand as they are, and output (t, g) has the
-// words pc_matmul_kernel<GO> gives on token t with the plaintexts the planes were packed from.
-template <int GO, int GT>
-__global__ void __launch_bounds__(256) pc_planes_matmul_kernel(const i64 *__restrict__ x, i64 xtok, PcMatTerms pa, i64 *__restrict__ S, i64 stok,
-                                                               int n, int rows, i64 N, int xpl, int first, unsigned long long small,
-                                                               const i64 *__restrict__ ql, const i64 *__restrict__ qh,
-                                                               const i64 *__restrict__ kl, const i64 *__restrict__ kh) {
+// ---- pc_matmul, pc_matmul_batch and both over plain planes: GO outputs' sums over the SAME n transformed ciphertexts, for each of
+// GT token vectors that share the plaintexts (a plaintext matrix times a vector resp. a matrix of ciphertexts) --------------------
+// x: token t's chunk [n][2][rows][N] at x + t * xtok, the transformed pairs as pc_dot_kernel reads them (xpl: fp64-class rows as
+// planes); pa.pt[i][g]: the plaintext of input i for output g of the group, the SAME table for every token, nullptr for an absent
+// term (kernel arguments: the test is uniform over the launch); S: token t's group [GO][2][rows][N] at S + t * stok (first: written
+// without being read, zeros where an output has no term in the chunk).
+//     S0_{t,g} += sum_i pt_{i,g} c0_{t,i},   S1_{t,g} += sum_i pt_{i,g} c1_{t,i}
+// grid and thread as pc_dot_kernel; the loop over the inputs is a run-time one.  Per input a thread loads the two transformed pairs
+// of each of its GT tokens ONCE for its GO outputs (ordinary loads: the next group reads them again) and, per non-NULL output of
+// its group, the plaintext pair ONCE (nontemporal), and forms the GO GT 2 2 products from registers: the plaintext stream, the
+// larger one at GT = 1, is divided by GT.  The plaintext side:
+//   PLANES = false  pt = [rows][N] Montgomery words (lazy, below 2q), one 16-byte pair per thread; a row is fp64-class where its
+//                   prime is below SMALL_PRIME_LIMIT, and there the pair goes through one REDC to the plain word (mm62u(w, 1)) — once
+//                   per read, not once per token;
+//   PLANES = true   pt in the format above, `small` marking its fp64-class rows: the class is bit r of `small` and the row starts at
+//                   plain_planes_row.  On fp64-class rows a thread loads the lo pair (8 bytes) and the hi pair (4 bytes) and
+//                   assembles the plain word with dp_from_planes: the REDC ran once, in the packer.  On integer-class rows it reads
+//                   the 16-byte pair at the row's compact offset.  The words that enter the sums are those of PLANES = false on the
+//                   plaintexts the planes were packed from.
+// The arithmetic is pc_dot_kernel's; only the residues of S reach the result, so the grouping of the additions is free.  Bounds per
+// (token, output) accumulator over a chunk of n <= LF_PC_MATMUL_CI inputs:
+//   fp64-class rows  n balanced products (|.| <= q / 2 each) plus the one canonical word read back:
+//                    |.| <= LF_PC_MATMUL_CI q / 2 + q <= 9 q < 2^45 for q < 2^41 — inside dp_reduce's |x| < 64 q (which holds up to
+//                    a chunk of 125) and the exact range of fp64; stored as the plain canonical residue;
+//   integer rows     a conditional subtraction after every addition: Montgomery form below 2q throughout.
+// So output (t, g) of any (GT, PLANES) has the words GT = 1, PLANES = false gives on token t.
+struct PcMatTerms {
+    const i64 *pt[LF_PC_MATMUL_CI][4];   // [input of the chunk][output of the group], [rows][N] each or nullptr
+};
+static_assert(LF_PC_MATMUL_CI >= 1 && LF_PC_MATMUL_CI / 2 + 1 < 64, "pc_products: a chunk's sum must stay inside dp_reduce's |x| < 64 q");
+
+template <int GO, int GT, bool PLANES>
+static __device__ __forceinline__ void pc_products(const i64 *__restrict__ x, i64 xtok, PcMatTerms pa, i64 *__restrict__ S, i64 stok, int n,
+                                                   int rows, i64 N, int xpl, int first, unsigned long long small,
+                                                   const i64 *__restrict__ ql, const i64 *__restrict__ qh, const i64 *__restrict__ kl,
+                                                   const i64 *__restrict__ kh) {
     const int r = blockIdx.y;
     const i64 j0 = (i64)blockIdx.x * 512 + threadIdx.x * 2;
     if (j0 >= N) return;
     const RowMod m = load_mod(ql, qh, kl, kh, r);
     const i64 pstride = (i64)rows * N, o0 = (i64)r * N + j0;
-    const i64 po = plain_planes_row(small, r, N);   // (uniform over the block)
+    i64 po = (i64)r * N;   // where row r of a plaintext starts (uniform over the block)
+    if constexpr (PLANES) po = plain_planes_row(small, r, N);
     i64 *s = S + o0;
-    if ((small >> r) & 1ull) {
+    if (PLANES ? (small >> r) & 1ull : m.q < SMALL_PRIME_LIMIT) {
         const RowDp d = make_dp(m);
         double a[GT][GO][2][2];
 #pragma unroll
@@ -1036,10 +847,16 @@ __global__ void __launch_bounds__(256) pc_planes_matmul_kernel(const i64 *__rest
             for (int g = 0; g < GO; ++g) {
                 const i64 *p = pa.pt[i][g];
                 if (p == nullptr) continue;   // (uniform: a kernel argument)
-                const lf_u2_t l = __builtin_nontemporal_load(reinterpret_cast<const lf_u2_t *>(reinterpret_cast<const unsigned *>(p + po) + j0));
-                const unsigned h = __builtin_nontemporal_load(
-                    reinterpret_cast<const unsigned *>(reinterpret_cast<const unsigned short *>(p + po + (N >> 1)) + j0));
-                const double wp[2] = {dp_from_planes(l.x, h & 0xffffu), dp_from_planes(l.y, h >> 16)};
+                double wp[2];
+                if constexpr (PLANES) {
+                    const lf_u2_t l = __builtin_nontemporal_load(reinterpret_cast<const lf_u2_t *>(reinterpret_cast<const unsigned *>(p + po) + j0));
+                    const unsigned h = __builtin_nontemporal_load(
+                        reinterpret_cast<const unsigned *>(reinterpret_cast<const unsigned short *>(p + po + (N >> 1)) + j0));
+                    wp[0] = dp_from_planes(l.x, h & 0xffffu), wp[1] = dp_from_planes(l.y, h >> 16);
+                } else {
+                    const longlong2 w = ld_nt(p + po + j0);
+                    wp[0] = dp_from_word(mm62u((u64)w.x, 1ull, m.q, m.k)), wp[1] = dp_from_word(mm62u((u64)w.y, 1ull, m.q, m.k));
+                }
 #pragma unroll
                 for (int t = 0; t < GT; ++t)
 #pragma unroll
@@ -1110,6 +927,32 @@ __global__ void __launch_bounds__(256) pc_planes_matmul_kernel(const i64 *__rest
                     *reinterpret_cast<longlong2 *>(at) = o;
                 }
     }
+}
+
+// The kernels under the names profiles, traces and the tracked resource table know them by: one token and raw plaintexts
+// (lf_pc_matmul), GT = 2 | 4 tokens and raw plaintexts (lf_pc_matmul_batch), GT = 1 | 2 | 4 tokens and compact plaintexts
+// (lf_pc_matmul_batch_planes).
+template <int GO>
+__global__ void __launch_bounds__(256) pc_matmul_kernel(const i64 *__restrict__ x, PcMatTerms pa, i64 *__restrict__ S, int n, int rows, i64 N,
+                                                        int xpl, int first, const i64 *__restrict__ ql, const i64 *__restrict__ qh,
+                                                        const i64 *__restrict__ kl, const i64 *__restrict__ kh) {
+    pc_products<GO, 1, false>(x, 0, pa, S, 0, n, rows, N, xpl, first, 0ull, ql, qh, kl, kh);
+}
+
+template <int GO, int GT>
+__global__ void __launch_bounds__(256) pc_matmulb_kernel(const i64 *__restrict__ x, i64 xtok, PcMatTerms pa, i64 *__restrict__ S, i64 stok,
+                                                         int n, int rows, i64 N, int xpl, int first, const i64 *__restrict__ ql,
+                                                         const i64 *__restrict__ qh, const i64 *__restrict__ kl,
+                                                         const i64 *__restrict__ kh) {
+    pc_products<GO, GT, false>(x, xtok, pa, S, stok, n, rows, N, xpl, first, 0ull, ql, qh, kl, kh);
+}
+
+template <int GO, int GT>
+__global__ void __launch_bounds__(256) pc_planes_matmul_kernel(const i64 *__restrict__ x, i64 xtok, PcMatTerms pa, i64 *__restrict__ S, i64 stok,
+                                                               int n, int rows, i64 N, int xpl, int first, unsigned long long small,
+                                                               const i64 *__restrict__ ql, const i64 *__restrict__ qh,
+                                                               const i64 *__restrict__ kl, const i64 *__restrict__ kh) {
+    pc_products<GO, GT, true>(x, xtok, pa, S, stok, n, rows, N, xpl, first, small, ql, qh, kl, kh);
 }
 
 // ---- cc_matmul: the summed triplets of an R x C tile of C = A B, every operand of the tile read once per inner index ----------
@@ -3046,35 +2889,11 @@ int lf_pc_bias(int64_t *c0, const int64_t *pt, const int64_t *Rs, int rows, int 
     return (int)hipGetLastError();
 }
 
-// The launch of lf_pc_matmul that is its own (ckks_ops.hip checks the arguments).
-// lf_pc_matmul_products: go (1, 2 or 4) outputs over the n <= LF_PC_MATMUL_CI transformed pairs x = [n][2][rows][N] (xpl: fp64-class
-// rows as planes — refused where the library's note of that range says another format); pt[i * pt_stride + g]: the plaintext of
-// input i for output g, or NULL; added into S = [go][2][rows][N] (first: written).
-int lf_pc_matmul_products(int go, int n, const int64_t *x, const int64_t *const *pt, int pt_stride, int64_t *S, int rows, int logN,
-                          int xpl, int first, const LfMod &m, hipStream_t st) {
-    if ((go != 1 && go != 2 && go != 4) || n < 1 || n > LF_PC_MATMUL_CI || !x || !pt || pt_stride < go || !S || rows < 1 || rows > 65535 ||
-        logN < 9)
-        return LF_ERR_ARG;
-    const i64 N = (i64)1 << logN;
-    if (int e = lf_fmt_expect(x, ((size_t)2 * n * rows << logN) * 8, xpl ? LF_FMT_PLANES : LF_FMT_RAW)) return e;
-    PcMatTerms pa{};
-    for (int i = 0; i < n; ++i)
-        for (int g = 0; g < go; ++g) pa.pt[i][g] = (const i64 *)pt[(size_t)i * pt_stride + g];
-    const dim3 grid((unsigned)(N / 512), (unsigned)rows);
-#define LF_PCMM_CASE(GG)                                                                                                          \
-    case GG:                                                                                                                      \
-        hipLaunchKernelGGL((pc_matmul_kernel<GG>), grid, dim3(256), 0, st, (const i64 *)x, pa, (i64 *)S, n, rows, N, xpl, first,   \
-                           LF_MOD_ARGS(m));                                                                                       \
-        break;
-    switch (go) { LF_PCMM_CASE(1) LF_PCMM_CASE(2) LF_PCMM_CASE(4) }
-#undef LF_PCMM_CASE
-    return (int)hipGetLastError();
-}
-
-// The launch of lf_pc_matmul_batch that is its own (ckks_ops.hip checks the arguments).
+// The launches of lf_pc_matmul, lf_pc_matmul_batch and lf_pc_matmul_batch_planes that are their own (ckks_ops.hip checks the
+// arguments).
 // lf_pc_matmul_batch_tile: the tile of tokens (2 or 1; 4 under LF_TUNE_PC_MATMUL_TILE) one launch takes for `left` tokens still to
-// go; 1 is lf_pc_matmul_products itself.  Every (go, gt) with gt > 1 this can return is instantiated below
-// (tests/test_pc_matmul_batch_cpu.py holds each of them to scratch 0 and no spill).  Measured on MI355X: a tile
+// go.  Every (go, gt) this can return is instantiated below for raw and for compact plaintexts (tests/test_pc_matmul_batch_cpu.py
+// and tests/test_compact_plain_cpu.py hold each of them to scratch 0 and no spill).  Measured on MI355X: a tile
 // of 4 tokens — 246 VGPRs at 4 outputs, 2 waves per SIMD — is slower than two tiles of 2, so the default never takes it.
 static int g_pc_matmul_tile = 0;   // LF_TUNE_PC_MATMUL_TILE
 int lf_pc_matmul_batch_tile(int go, int left) {
@@ -3088,33 +2907,6 @@ int lf_pc_matmul_batch_outputs(int left, int nt) {
     return left >= 4 ? 4 : left >= 2 ? 2 : 1;
 }
 
-// lf_pc_matmulb_products: lf_pc_matmul_products over gt (2 or 4) tokens in one launch: token t's transformed pairs at x + t * xtok,
-// its group's pairs of S at S + t * stok (strides in words, multiples of 2: 16-byte accesses); pt shared by the tokens.
-int lf_pc_matmulb_products(int go, int gt, int n, const int64_t *x, int64_t xtok, const int64_t *const *pt, int pt_stride, int64_t *S,
-                           int64_t stok, int rows, int logN, int xpl, int first, const LfMod &m, hipStream_t st) {
-    if ((go != 1 && go != 2 && go != 4) || (gt != 2 && gt != 4) || n < 1 || n > LF_PC_MATMUL_CI || !x || !pt || pt_stride < go || !S ||
-        rows < 1 || rows > 65535 || logN < 9 || xtok < ((int64_t)2 * n * rows << logN) || stok < ((int64_t)2 * go * rows << logN) ||
-        (xtok & 1) || (stok & 1))
-        return LF_ERR_ARG;
-    const i64 N = (i64)1 << logN;
-    for (int t = 0; t < gt; ++t)
-        if (int e = lf_fmt_expect(x + t * xtok, ((size_t)2 * n * rows << logN) * 8, xpl ? LF_FMT_PLANES : LF_FMT_RAW)) return e;
-    PcMatTerms pa{};
-    for (int i = 0; i < n; ++i)
-        for (int g = 0; g < go; ++g) pa.pt[i][g] = (const i64 *)pt[(size_t)i * pt_stride + g];
-    const dim3 grid((unsigned)(N / 512), (unsigned)rows);
-#define LF_PCMMB_CASE(GG, TT)                                                                                                     \
-    case GG * 8 + TT:                                                                                                             \
-        hipLaunchKernelGGL((pc_matmulb_kernel<GG, TT>), grid, dim3(256), 0, st, (const i64 *)x, (i64)xtok, pa, (i64 *)S, (i64)stok, n, \
-                           rows, N, xpl, first, LF_MOD_ARGS(m));                                                                  \
-        break;
-    switch (go * 8 + gt) {
-        LF_PCMMB_CASE(1, 2) LF_PCMMB_CASE(2, 2) LF_PCMMB_CASE(4, 2) LF_PCMMB_CASE(1, 4) LF_PCMMB_CASE(2, 4) LF_PCMMB_CASE(4, 4)
-    }
-#undef LF_PCMMB_CASE
-    return (int)hipGetLastError();
-}
-
 // lf_plain_planes_mask: bit r set where row r of a compact plaintext is fp64-class; false for more rows than the mask has bits
 bool lf_plain_planes_mask(int rows, const int64_t *q_host, uint64_t *mask) {
     if (rows < 1 || rows > LF_PLAIN_PLANES_MAX_ROWS || !q_host) return false;
@@ -3125,13 +2917,19 @@ bool lf_plain_planes_mask(int rows, const int64_t *q_host, uint64_t *mask) {
     return true;
 }
 
-// lf_pc_planes_products: lf_pc_matmul_products (gt = 1) resp. lf_pc_matmulb_products (gt = 2 or 4) with every non-NULL pt a compact
-// plaintext (lf_plain_planes) whose fp64-class rows `small` marks.
-int lf_pc_planes_products(int go, int gt, int n, const int64_t *x, int64_t xtok, const int64_t *const *pt, int pt_stride, int64_t *S,
-                          int64_t stok, int rows, int logN, int xpl, int first, uint64_t small, const LfMod &m, hipStream_t st) {
+// lf_pc_matmul_products: go (1, 2 or 4) outputs over the n <= LF_PC_MATMUL_CI transformed pairs of each of gt (1, 2 or 4) tokens in
+// one launch: token t's pairs [n][2][rows][N] at x + t * xtok (xpl: fp64-class rows as planes — refused where the library's note of
+// that range says another format), its group's pairs [go][2][rows][N] of S at S + t * stok (first: written; otherwise added into);
+// pt[i * pt_stride + g]: the plaintext of input i for output g, or NULL, shared by the tokens.  planes: every non-NULL pt a compact
+// plaintext (lf_plain_planes) whose fp64-class rows `small` marks.  The token strides are in words, multiples of 2 (16-byte
+// accesses); one token over raw plaintexts (pc_matmul_kernel) takes none, so there they are not looked at.
+int lf_pc_matmul_products(bool planes, int go, int gt, int n, const int64_t *x, int64_t xtok, const int64_t *const *pt, int pt_stride,
+                          int64_t *S, int64_t stok, int rows, int logN, int xpl, int first, uint64_t small, const LfMod &m, hipStream_t st) {
     if ((go != 1 && go != 2 && go != 4) || (gt != 1 && gt != 2 && gt != 4) || n < 1 || n > LF_PC_MATMUL_CI || !x || !pt || pt_stride < go ||
-        !S || rows < 1 || rows > LF_PLAIN_PLANES_MAX_ROWS || logN < 9 || xtok < ((int64_t)2 * n * rows << logN) ||
-        stok < ((int64_t)2 * go * rows << logN) || (xtok & 1) || (stok & 1))
+        !S || rows < 1 || rows > (planes ? LF_PLAIN_PLANES_MAX_ROWS : 65535) || logN < 9)
+        return LF_ERR_ARG;
+    if ((planes || gt > 1) &&
+        (xtok < ((int64_t)2 * n * rows << logN) || stok < ((int64_t)2 * go * rows << logN) || (xtok & 1) || (stok & 1)))
         return LF_ERR_ARG;
     const i64 N = (i64)1 << logN;
     for (int t = 0; t < gt; ++t)
@@ -3140,15 +2938,29 @@ int lf_pc_planes_products(int go, int gt, int n, const int64_t *x, int64_t xtok,
     for (int i = 0; i < n; ++i)
         for (int g = 0; g < go; ++g) pa.pt[i][g] = (const i64 *)pt[(size_t)i * pt_stride + g];
     const dim3 grid((unsigned)(N / 512), (unsigned)rows);
-#define LF_PCPL_CASE(GG, TT)                                                                                                      \
+#define LF_PCMM_CASE(GG)                                                                                                          \
+    case GG * 8 + 1:                                                                                                              \
+        hipLaunchKernelGGL((pc_matmul_kernel<GG>), grid, dim3(256), 0, st, (const i64 *)x, pa, (i64 *)S, n, rows, N, xpl, first,   \
+                           LF_MOD_ARGS(m));                                                                                       \
+        break;
+#define LF_PCMMB_CASE(GG, TT)                                                                                                     \
     case GG * 8 + TT:                                                                                                             \
+        hipLaunchKernelGGL((pc_matmulb_kernel<GG, TT>), grid, dim3(256), 0, st, (const i64 *)x, (i64)xtok, pa, (i64 *)S, (i64)stok, n, \
+                           rows, N, xpl, first, LF_MOD_ARGS(m));                                                                  \
+        break;
+#define LF_PCPL_CASE(GG, TT)                                                                                                      \
+    case 64 + GG * 8 + TT:                                                                                                        \
         hipLaunchKernelGGL((pc_planes_matmul_kernel<GG, TT>), grid, dim3(256), 0, st, (const i64 *)x, (i64)xtok, pa, (i64 *)S,     \
                            (i64)stok, n, rows, N, xpl, first, (unsigned long long)small, LF_MOD_ARGS(m));                          \
         break;
-    switch (go * 8 + gt) {
+    switch ((planes ? 64 : 0) + go * 8 + gt) {
+        LF_PCMM_CASE(1) LF_PCMM_CASE(2) LF_PCMM_CASE(4)
+        LF_PCMMB_CASE(1, 2) LF_PCMMB_CASE(2, 2) LF_PCMMB_CASE(4, 2) LF_PCMMB_CASE(1, 4) LF_PCMMB_CASE(2, 4) LF_PCMMB_CASE(4, 4)
         LF_PCPL_CASE(1, 1) LF_PCPL_CASE(2, 1) LF_PCPL_CASE(4, 1) LF_PCPL_CASE(1, 2) LF_PCPL_CASE(2, 2) LF_PCPL_CASE(4, 2)
         LF_PCPL_CASE(1, 4) LF_PCPL_CASE(2, 4) LF_PCPL_CASE(4, 4)
     }
+#undef LF_PCMM_CASE
+#undef LF_PCMMB_CASE
 #undef LF_PCPL_CASE
     return (int)hipGetLastError();
 }

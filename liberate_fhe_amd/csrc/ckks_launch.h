@@ -103,18 +103,14 @@ int lf_dot_relin(const int64_t *state, int nct, int nparts, int rows, int logN, 
                  int ell, const uint8_t *own, const LfMod &m, hipStream_t st);
 int lf_matmul_tensor(int R, int C, int k, int nu, const int64_t *x, const int *ta, const int *tb, int64_t *T, int64_t *t2, int ell,
                      int logN, int xpl, const LfMod &m, hipStream_t st);
-// the launches of lf_pc_dot, lf_pc_matmul and lf_pc_matmul_batch that are their own, and the tile of tokens / outputs the last takes
+// the launches of lf_pc_dot, lf_pc_matmul, lf_pc_matmul_batch and lf_pc_matmul_batch_planes that are their own: the tile of tokens /
+// outputs a product launch takes, the fp64-class rows of a compact plaintext as a bit mask (false: more rows than it has bits), and
+// the products of go outputs x gt tokens (1, 2 or 4 each) over raw or (planes) compact plaintexts
 int lf_pc_dot_products(int g, const int64_t *x, const int64_t *const *pt, int64_t *S, int rows, int logN, int xpl, int first,
                        const LfMod &m, hipStream_t st);
 int lf_pc_bias(int64_t *c0, const int64_t *pt, const int64_t *Rs, int rows, int logN, const LfMod &m, hipStream_t st);
-int lf_pc_matmul_products(int go, int n, const int64_t *x, const int64_t *const *pt, int pt_stride, int64_t *S, int rows, int logN,
-                          int xpl, int first, const LfMod &m, hipStream_t st);
 int lf_pc_matmul_batch_tile(int go, int left);
 int lf_pc_matmul_batch_outputs(int left, int nt);
-int lf_pc_matmulb_products(int go, int gt, int n, const int64_t *x, int64_t xtok, const int64_t *const *pt, int pt_stride, int64_t *S,
-                           int64_t stok, int rows, int logN, int xpl, int first, const LfMod &m, hipStream_t st);
-// .. of lf_pc_matmul_batch_planes: the fp64-class rows of a compact plaintext as a bit mask (false: more rows than it has bits),
-// and the products over compact plaintexts (gt = 1, 2 or 4 tokens per launch)
 bool lf_plain_planes_mask(int rows, const int64_t *q_host, uint64_t *mask);
-int lf_pc_planes_products(int go, int gt, int n, const int64_t *x, int64_t xtok, const int64_t *const *pt, int pt_stride, int64_t *S,
-                          int64_t stok, int rows, int logN, int xpl, int first, uint64_t small, const LfMod &m, hipStream_t st);
+int lf_pc_matmul_products(bool planes, int go, int gt, int n, const int64_t *x, int64_t xtok, const int64_t *const *pt, int pt_stride,
+                          int64_t *S, int64_t stok, int rows, int logN, int xpl, int first, uint64_t small, const LfMod &m, hipStream_t st);

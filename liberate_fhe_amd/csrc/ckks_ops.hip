@@ -494,8 +494,8 @@ static int pc_matmul_tokens(bool planes, int nt, int64_t need, int k_in, int k_o
                 t0 += g;
             }
         }
-        // 2. per group of 4, 2 or 1 outputs ONE launch over the chunk per tile of 2 tokens (an odd token left: lf_pc_matmul's own
-        //    launch): the group's pairs of S
+        // 2. per group of 4, 2 or 1 outputs ONE launch over the chunk per tile of 2 tokens (an odd token left: a tile of 1, which
+        //    is lf_pc_matmul's launch): the group's pairs of S
         for (int o0 = 0; o0 < k_out;) {
             const int go = lf_pc_matmul_batch_outputs(k_out - o0, nt);   // (one token: 4, 2 or 1 of the outputs left, as ever)
             const int64_t *tab[LF_PC_MATMUL_CI * 4];
@@ -504,12 +504,9 @@ static int pc_matmul_tokens(bool planes, int nt, int64_t need, int k_in, int k_o
             for (int tk = 0; tk < nt;) {
                 const int gt = lf_pc_matmul_batch_tile(go, nt - tk);
                 int64_t *Sg = S + tk * stok + (int64_t)o0 * 2 * poly;
-                const int e = planes  ? lf_pc_planes_products(go, gt, n, x + tk * xtok, xtok, tab, 4, Sg, stok, rows, logN, xpl, a0 == 0, small,
-                                                              mod, (hipStream_t)stream)
-                              : gt == 1 ? lf_pc_matmul_products(go, n, x + tk * xtok, tab, 4, Sg, rows, logN, xpl, a0 == 0, mod, (hipStream_t)stream)
-                                      : lf_pc_matmulb_products(go, gt, n, x + tk * xtok, xtok, tab, 4, Sg, stok, rows, logN, xpl, a0 == 0,
-                                                               mod, (hipStream_t)stream);
-                if (e) return e;
+                if (int e = lf_pc_matmul_products(planes, go, gt, n, x + tk * xtok, xtok, tab, 4, Sg, stok, rows, logN, xpl, a0 == 0, small, mod,
+                                                  (hipStream_t)stream))
+                    return e;
                 tk += gt;
             }
             o0 += go;

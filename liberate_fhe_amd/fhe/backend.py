@@ -522,6 +522,18 @@ class HipBackend:
                             _p(Rs), _p(Ninv), _p(mont_one), _p(zero_row), _p(scales), round_at, _p(ws), ws.numel(), *c.mont(), dev, st),
               "lf_pc_dot")
 
+    @staticmethod
+    def _pc_matmul_entry(name, shape, ins, pts, biases, pairs, rows, logN, psi, ipsi, Rs, Ninv, mont_one, zero_row, scales, round_at, ws,
+                         c: Consts):
+        """lf_pc_matmul, lf_pc_matmul_batch or lf_pc_matmul_batch_planes (`name`): shape = its leading (nt,) k_in, k_out; pairs: the
+        output pairs in the entry's order, [token][output]."""
+        dev, st = _ds(pairs[0][0])
+        psi_dp = twiddles.dp_pointer(psi, c.ql, c.qh, c.kl, c.kh, dev, st)
+        ipsi_dp = twiddles.dp_pointer(ipsi, c.ql, c.qh, c.kl, c.kh, dev, st)
+        out0, out1 = _parr([o[0] for o in pairs]), _parr([o[1] for o in pairs])
+        check(getattr(lib, name)(*shape, ins, pts, biases, out0, out1, rows, logN, _p(psi), psi_dp, _p(ipsi), ipsi_dp, c.qptr(True), _p(Rs),
+                                 _p(Ninv), _p(mont_one), _p(zero_row), _p(scales), round_at, _p(ws), ws.numel(), *c.mont(), dev, st), name)
+
     # include/ckks_hip.h: LF_PC_MATMUL_CI / LF_PC_MATMUL_MAX_OUTPUTS (tests/test_pc_matmul_cpu.py holds these copies to the header)
     pc_matmul_chunk = 16
     pc_matmul_max_outputs = 64
@@ -536,13 +548,8 @@ class HipBackend:
         ins: ctypes array of 2 k_in device pointers ([input][component]); pts: ctypes array of k_out k_in device pointers, row-major,
         None for an absent term; biases: None or a ctypes array of k_out pointers (None: no bias); outs: k_out pairs of output
         tensors [rows - 1, N]; the rest as pc_dot_native; ws: at least pc_matmul_ws_words(k_in, k_out, rows, logN) words."""
-        dev, st = _ds(outs[0][0])
-        psi_dp = twiddles.dp_pointer(psi, c.ql, c.qh, c.kl, c.kh, dev, st)
-        ipsi_dp = twiddles.dp_pointer(ipsi, c.ql, c.qh, c.kl, c.kh, dev, st)
-        out0, out1 = _parr([o[0] for o in outs]), _parr([o[1] for o in outs])
-        check(lib.lf_pc_matmul(k_in, k_out, ins, pts, biases, out0, out1, rows, logN, _p(psi), psi_dp, _p(ipsi), ipsi_dp, c.qptr(True),
-                               _p(Rs), _p(Ninv), _p(mont_one), _p(zero_row), _p(scales), round_at, _p(ws), ws.numel(), *c.mont(), dev, st),
-              "lf_pc_matmul")
+        self._pc_matmul_entry("lf_pc_matmul", (k_in, k_out), ins, pts, biases, outs, rows, logN, psi, ipsi, Rs, Ninv, mont_one, zero_row,
+                              scales, round_at, ws, c)
 
     # include/ckks_hip.h: LF_PC_MATMUL_BATCH_MAX_TOKENS (tests/test_pc_matmul_batch_cpu.py holds this copy to the header); the
     # group sizes lf_pc_matmul_batch has a tile of tokens for, largest first
@@ -558,13 +565,8 @@ class HipBackend:
         """pc_matmul_native over nt token vectors that share the matrix as ONE native call (lf_pc_matmul_batch).  ins: ctypes array
         of nt 2 k_in device pointers ([token][input][component]); pts, biases: as pc_matmul_native, shared by the tokens; outs: nt
         lists of k_out pairs of output tensors [rows - 1, N]; ws: at least pc_matmul_batch_ws_words(nt, k_in, k_out, rows, logN) words."""
-        dev, st = _ds(outs[0][0][0])
-        psi_dp = twiddles.dp_pointer(psi, c.ql, c.qh, c.kl, c.kh, dev, st)
-        ipsi_dp = twiddles.dp_pointer(ipsi, c.ql, c.qh, c.kl, c.kh, dev, st)
-        out0, out1 = _parr([o[0] for tok in outs for o in tok]), _parr([o[1] for tok in outs for o in tok])
-        check(lib.lf_pc_matmul_batch(nt, k_in, k_out, ins, pts, biases, out0, out1, rows, logN, _p(psi), psi_dp, _p(ipsi), ipsi_dp,
-                                     c.qptr(True), _p(Rs), _p(Ninv), _p(mont_one), _p(zero_row), _p(scales), round_at, _p(ws), ws.numel(),
-                                     *c.mont(), dev, st), "lf_pc_matmul_batch")
+        self._pc_matmul_entry("lf_pc_matmul_batch", (nt, k_in, k_out), ins, pts, biases, [o for tok in outs for o in tok], rows, logN, psi,
+                              ipsi, Rs, Ninv, mont_one, zero_row, scales, round_at, ws, c)
 
     # include/ckks_hip.h: LF_PLAIN_PLANES_MAX_ROWS (tests/test_compact_plain_cpu.py holds this copy to the header)
     plain_planes_max_rows = LF_PLAIN_PLANES_MAX_ROWS
@@ -594,13 +596,8 @@ class HipBackend:
         """pc_matmul_batch_native with every plaintext of pts a compact one (plain_planes) as ONE native call
         (lf_pc_matmul_batch_planes); nt = 1 is pc_matmul, nt = 1 and k_out = 1 pc_dot.  ws: at least
         pc_matmul_batch_planes_ws_words(nt, k_in, k_out, rows, logN) words."""
-        dev, st = _ds(outs[0][0][0])
-        psi_dp = twiddles.dp_pointer(psi, c.ql, c.qh, c.kl, c.kh, dev, st)
-        ipsi_dp = twiddles.dp_pointer(ipsi, c.ql, c.qh, c.kl, c.kh, dev, st)
-        out0, out1 = _parr([o[0] for tok in outs for o in tok]), _parr([o[1] for tok in outs for o in tok])
-        check(lib.lf_pc_matmul_batch_planes(nt, k_in, k_out, ins, pts, biases, out0, out1, rows, logN, _p(psi), psi_dp, _p(ipsi), ipsi_dp,
-                                            c.qptr(True), _p(Rs), _p(Ninv), _p(mont_one), _p(zero_row), _p(scales), round_at, _p(ws),
-                                            ws.numel(), *c.mont(), dev, st), "lf_pc_matmul_batch_planes")
+        self._pc_matmul_entry("lf_pc_matmul_batch_planes", (nt, k_in, k_out), ins, pts, biases, [o for tok in outs for o in tok], rows, logN,
+                              psi, ipsi, Rs, Ninv, mont_one, zero_row, scales, round_at, ws, c)
 
     @staticmethod
     def rotate_hoisted_ws_words(plan):

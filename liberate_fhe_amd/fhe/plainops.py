@@ -200,14 +200,33 @@ class PlainOps:
                 out[id(pt)] = self.expand_plain(pt)
         return out
 
-    def _pc_planes_native(self, l):
-        """The device where lf_pc_matmul_batch_planes applies at level l -> l + 1 (the native conditions of the raw ops), or None."""
+    def _pc_native(self, l, entry):
+        """The device where the backend's one-call `entry` (pc_dot_native, pc_matmul_native, pc_matmul_batch_native or
+        pc_matmul_batch_planes_call) applies at level l -> l + 1, or None: both levels on that ONE device of this process, a
+        backend that has the entry, logN 13 .. 17 (below 13 _native_level says None for every backend with native ops), the rows of
+        l + 1 those of l in their order behind the dropped limb and, for compact plaintexts, no more rows than their mask has bits."""
         d = self._native_level(l + 1)
-        if d is None or self._native_level(l) != d or not hasattr(self.backend, "pc_matmul_batch_planes_call") \
-                or not 13 <= self.ctx.logN <= 17 or len(self.ntt.p.destination_arrays[l][d]) > self.backend.plain_planes_max_rows \
-                or list(self.ntt.p.destination_arrays[l][d][1:]) != list(self.ntt.p.destination_arrays[l + 1][d]):
+        dest = self.ntt.p.destination_arrays
+        if d is None or self._native_level(l) != d or not hasattr(self.backend, entry) or not 13 <= self.ctx.logN <= 17 \
+                or (entry == "pc_matmul_batch_planes_call" and len(dest[l][d]) > self.backend.plain_planes_max_rows) \
+                or list(dest[l][d][1:]) != list(dest[l + 1][d]):
             return None
         return d
+
+    def _pc_planes_native(self, l):
+        """The device where lf_pc_matmul_batch_planes applies at level l -> l + 1, or None."""
+        return self._pc_native(l, "pc_matmul_batch_planes_call")
+
+    @staticmethod
+    def _pc_operand_ok(t):
+        """What the native calls ask of an operand's tensor (16-byte loads: a contiguous view at an odd word offset takes the
+        composition; so does a tensor moved to the host, which the level cannot see)."""
+        return t.is_contiguous() and t.dtype == torch.int64 and t.data_ptr() % 16 == 0 and t.is_cuda
+
+    def _pc_operands_ok(self, cts, plains):
+        """_pc_operand_ok of both components of every ciphertext and of every distinct plaintext / bias (None skipped)."""
+        return all(self._pc_operand_ok(t) for ct in cts for t in (ct.data[0][0], ct.data[1][0])) \
+            and all(self._pc_operand_ok(x.data[0]) for x in {id(x): x for x in plains if x is not None}.values())
 
     # =============================================================================================
     # checks (all before any launch)
@@ -301,22 +320,14 @@ class PlainOps:
                 raise errors.NotMatchDataStructState(origin=f"{bias.origin} at level {bias.level} beside level {l + 1}")
         if l + 1 >= self.num_levels:
             raise errors.MaximumLevelError(level=l, level_max=self.num_levels)
-        if compact:
-            d = self._pc_planes_native(l)
-            if d is not None and all(self._pc_operand_ok(t) for pt, ct in pairs for t in (pt.data[0], ct.data[0][0], ct.data[1][0])) \
-                    and (bias is None or self._pc_operand_ok(bias.data[0])):
+        d = self._pc_native(l, "pc_matmul_batch_planes_call" if compact else "pc_dot_native")
+        if d is not None and self._pc_operands_ok([ct for _, ct in pairs], [pt for pt, _ in pairs] + [bias]):
+            if compact:
                 return self._pc_matmul_batch_native([[pt for pt, _ in pairs]], [[ct for _, ct in pairs]], [bias], l, d, planes=True)[0][0]
+            return self._pc_dot_native(pairs, bias, l, d)
+        if compact:
             raw = self._expanded(pt for pt, _ in pairs)
             return self.pc_dot([(raw[id(pt)], ct) for pt, ct in pairs], bias)
-        d = self._native_level(l + 1)
-        # (16-byte loads: a contiguous view at an odd word offset takes the composition, as do rows in another order than the
-        # dropped limb first and the survivors behind it)
-        if d is not None and self._native_level(l) == d and hasattr(self.backend, "pc_dot_native") and self.ctx.logN <= 17 \
-                and list(self.ntt.p.destination_arrays[l][d][1:]) == list(self.ntt.p.destination_arrays[l + 1][d]) \
-                and all(t.is_contiguous() and t.dtype == torch.int64 and t.data_ptr() % 16 == 0
-                        for pt, ct in pairs for t in (pt.data[0], ct.data[0][0], ct.data[1][0])) \
-                and (bias is None or (bias.data[0].is_contiguous() and bias.data[0].dtype == torch.int64 and bias.data[0].data_ptr() % 16 == 0)):
-            return self._pc_dot_native(pairs, bias, l, d)
         S = None
         for pt, ct in pairs:
             x = self.clone(ct)
@@ -381,62 +392,28 @@ class PlainOps:
         cts = list(cts)
         k_out = len(W)
         bias, l = self._pc_matmul_checked(W, cts, None if bias is None else list(bias))
-        if next(pt for pt in W[0] if pt is not None).origin == types.origins["pt_mult_planes"]:
-            d = self._pc_planes_native(l)
-            tensors = [t for ct in cts for t in (ct.data[0][0], ct.data[1][0])]
-            tensors += [x.data[0] for x in {id(x): x for x in [pt for row in W for pt in row] + bias if x is not None}.values()]
-            if d is not None and all(self._pc_operand_ok(t) for t in tensors):
-                step = self.backend.pc_matmul_max_outputs
+        planes = next(pt for pt in W[0] if pt is not None).origin == types.origins["pt_mult_planes"]
+        d = self._pc_native(l, "pc_matmul_batch_planes_call" if planes else "pc_matmul_native")
+        if d is not None and self._pc_operands_ok(cts, [pt for row in W for pt in row] + bias):
+            step = self.backend.pc_matmul_max_outputs
+            if planes:
                 return [out for o0 in range(0, k_out, step)
                         for out in self._pc_matmul_batch_native(W[o0:o0 + step], [cts], bias[o0:o0 + step], l, d, planes=True)[0]]
+            return [out for o0 in range(0, k_out, step) for out in self._pc_matmul_native(W[o0:o0 + step], cts, bias[o0:o0 + step], l, d)]
+        if planes:
             raw = self._expanded(pt for row in W for pt in row)
             return self.pc_matmul([[None if pt is None else raw[id(pt)] for pt in row] for row in W], cts, bias)
-        d = self._native_level(l + 1)
-        if d is not None and self._native_level(l) == d and hasattr(self.backend, "pc_matmul_native") and self.ctx.logN <= 17 \
-                and list(self.ntt.p.destination_arrays[l][d][1:]) == list(self.ntt.p.destination_arrays[l + 1][d]):
-            tensors = [t for ct in cts for t in (ct.data[0][0], ct.data[1][0])]
-            tensors += [x.data[0] for x in {id(x): x for x in [pt for row in W for pt in row] + bias if x is not None}.values()]
-            if all(t.is_contiguous() and t.dtype == torch.int64 and t.data_ptr() % 16 == 0 and t.is_cuda for t in tensors):
-                step = self.backend.pc_matmul_max_outputs
-                return [out for o0 in range(0, k_out, step) for out in self._pc_matmul_native(W[o0:o0 + step], cts, bias[o0:o0 + step], l, d)]
         return [self.pc_dot([(pt, ct) for pt, ct in zip(row, cts) if pt is not None], b) for row, b in zip(W, bias)]
 
     def _pc_matmul_native(self, W, cts, bias, l, d):
-        N, k_out, k_in = self.ctx.N, len(W), len(cts)
-        rows = len(self.ntt.p.destination_arrays[l][d])          # the dropped limb first
-        owner = self.ntt.p.rescaler_loc[l]
-        round_at = self.ctx.q[self.ntt.p.destination_arrays[l][owner][0]] // 2
-        ins, pts = (ctypes.c_void_p * (2 * k_in))(), (ctypes.c_void_p * (k_out * k_in))()
-        for i, ct in enumerate(cts):
-            for comp in range(2):
-                ins[2 * i + comp] = ct.data[comp][0].data_ptr()
-        for o, row in enumerate(W):
-            for i, pt in enumerate(row):
-                pts[o * k_in + i] = None if pt is None else pt.data[0].data_ptr()
-        biases = None
-        if any(b is not None for b in bias):
-            biases = (ctypes.c_void_p * k_out)()
-            for o, b in enumerate(bias):
-                biases[o] = None if b is None else b.data[0].data_ptr()
-        dev = self.ntt.devices[d]
-        ident = self._pc_identity(l, d)
-        chunk = min(k_in, self.backend.pc_matmul_chunk)
-        ws = self._ws("pc_matmul_ws", (self.backend.pc_matmul_ws_words(chunk, k_out, rows, self.ctx.logN),), d)   # (per device and level: the shape)
-        outs = [[torch.empty((rows - 1, N), dtype=torch.int64, device=dev) for _ in range(2)] for _ in range(k_out)]
-        self.backend.pc_matmul_native(ins, pts, biases, outs, k_in, k_out, rows, self.ctx.logN, self._tw(d, l, False),
-                                      self._tw(d, l, False, True), self._vec("Rs", d, l, False), self._vec("Ninv", d, l, False), ident[0],
-                                      ident[1], self.rescale_scales[l][d], round_at, ws, self._consts(d, l, False))
-        return [self._new(([o[0]], [o[1]]), types.origins["ct"], level=l + 1) for o in outs]
+        """One lf_pc_matmul call."""
+        return self._pc_matmul_call("pc_matmul_native", W, [cts], bias, l, d)[0]
 
     # group sizes of pc_matmul_batch's native path, largest first (filtered by backend.pc_matmul_batch_sizes), as rsum_batch_sizes: a
     # size that does not beat the loop is left out here and its tokens take pc_matmul one by one — the words are the same.
     # Groups of 4 are left out: on MI355X they lose to groups of 2 everywhere and to the loop at silver (DESIGN.md §4.2 has the
     # numbers); the backend still takes them (tools/pc_matmul_batch.py --ab measures them).
     pc_matmul_batch_sizes = (2,)
-
-    @staticmethod
-    def _pc_operand_ok(t):
-        return t.is_contiguous() and t.dtype == torch.int64 and t.data_ptr() % 16 == 0 and t.is_cuda
 
     def pc_matmul_batch(self, W, X, bias=None):
         """pc_matmul of many token vectors under the SAME matrix (a dense layer over the tokens of a sequence or the samples of a
@@ -466,17 +443,12 @@ class PlainOps:
         ready = []
         sizes = [k for k in self.pc_matmul_batch_sizes if k in getattr(self.backend, "pc_matmul_batch_sizes", ())]
         planes = next(pt for pt in W[0] if pt is not None).origin == types.origins["pt_mult_planes"]
-        if planes and self._pc_planes_native(l) is None:
+        d = self._pc_native(l, "pc_matmul_batch_planes_call" if planes else "pc_matmul_batch_native")
+        if planes and d is None:
             raw = self._expanded(pt for row in W for pt in row)
             return self.pc_matmul_batch([[None if pt is None else raw[id(pt)] for pt in row] for row in W], X, bias)
-        d = self._native_level(l + 1)
-        if sizes and d is not None and self._native_level(l) == d \
-                and hasattr(self.backend, "pc_matmul_batch_planes_call" if planes else "pc_matmul_batch_native") \
-                and 13 <= self.ctx.logN <= 17 \
-                and list(self.ntt.p.destination_arrays[l][d][1:]) == list(self.ntt.p.destination_arrays[l + 1][d]) \
-                and all(self._pc_operand_ok(x.data[0])
-                        for x in {id(x): x for x in [pt for row in W for pt in row] + bias if x is not None}.values()):
-            ready = [t for t, cts in enumerate(X) if all(self._pc_operand_ok(c) for ct in cts for c in (ct.data[0][0], ct.data[1][0]))]
+        if sizes and d is not None and self._pc_operands_ok([], [pt for row in W for pt in row] + bias):
+            ready = [t for t, cts in enumerate(X) if self._pc_operands_ok(cts, [])]
         step = getattr(self.backend, "pc_matmul_max_outputs", k_out)
         while ready:
             g = next((k for k in sizes if k <= len(ready)), None)
@@ -494,14 +466,23 @@ class PlainOps:
 
     def _pc_matmul_batch_native(self, W, toks, bias, l, d, planes=False):
         """One lf_pc_matmul_batch call, or (planes: every plaintext of W compact) one lf_pc_matmul_batch_planes call, of any nt >= 1."""
-        N, k_out, k_in, nt = self.ctx.N, len(W), len(toks[0]), len(toks)
-        be = self.backend
-        ws_words, native = (be.pc_matmul_batch_planes_ws_words, be.pc_matmul_batch_planes_call) if planes else \
-            (be.pc_matmul_batch_ws_words, be.pc_matmul_batch_native)
+        return self._pc_matmul_call("pc_matmul_batch_planes_call" if planes else "pc_matmul_batch_native", W, toks, bias, l, d)
+
+    # backend entry -> (its workspace query, the key its workspace is cached under, whether it takes the number of tokens)
+    _pc_matmul_entries = {"pc_matmul_native": ("pc_matmul_ws_words", "pc_matmul_ws", False),
+                          "pc_matmul_batch_native": ("pc_matmul_batch_ws_words", "pc_matmul_batch_ws", True),
+                          "pc_matmul_batch_planes_call": ("pc_matmul_batch_planes_ws_words", "pc_matmul_batch_ws", True)}
+
+    def _pc_matmul_call(self, entry, W, toks, bias, l, d):
+        """ONE call of the backend's `entry` on the matrix W, the token vectors toks (exactly one where the entry takes no number of
+        tokens) and the biases: the lists of output ciphertexts, one per token."""
+        N, k_out, k_in = self.ctx.N, len(W), len(toks[0])
+        ws_words, ws_key, batched = self._pc_matmul_entries[entry]
+        nt = (len(toks),) if batched else ()
         rows = len(self.ntt.p.destination_arrays[l][d])          # the dropped limb first
         owner = self.ntt.p.rescaler_loc[l]
         round_at = self.ctx.q[self.ntt.p.destination_arrays[l][owner][0]] // 2
-        ins, pts = (ctypes.c_void_p * (nt * 2 * k_in))(), (ctypes.c_void_p * (k_out * k_in))()
+        ins, pts = (ctypes.c_void_p * (len(toks) * 2 * k_in))(), (ctypes.c_void_p * (k_out * k_in))()
         for t, cts in enumerate(toks):
             for i, ct in enumerate(cts):
                 for comp in range(2):
@@ -517,11 +498,12 @@ class PlainOps:
         dev = self.ntt.devices[d]
         ident = self._pc_identity(l, d)
         chunk = min(k_in, self.backend.pc_matmul_chunk)
-        ws = self._ws("pc_matmul_batch_ws", (ws_words(nt, chunk, k_out, rows, self.ctx.logN),), d)
-        outs = [[[torch.empty((rows - 1, N), dtype=torch.int64, device=dev) for _ in range(2)] for _ in range(k_out)] for _ in range(nt)]
-        native(ins, pts, biases, outs, nt, k_in, k_out, rows, self.ctx.logN, self._tw(d, l, False),
-               self._tw(d, l, False, True), self._vec("Rs", d, l, False), self._vec("Ninv", d, l, False),
-               ident[0], ident[1], self.rescale_scales[l][d], round_at, ws, self._consts(d, l, False))
+        ws = self._ws(ws_key, (getattr(self.backend, ws_words)(*nt, chunk, k_out, rows, self.ctx.logN),), d)   # (per device and level: the shape)
+        outs = [[[torch.empty((rows - 1, N), dtype=torch.int64, device=dev) for _ in range(2)] for _ in range(k_out)] for _ in toks]
+        getattr(self.backend, entry)(ins, pts, biases, outs if batched else outs[0], *nt, k_in, k_out, rows, self.ctx.logN,
+                                     self._tw(d, l, False), self._tw(d, l, False, True), self._vec("Rs", d, l, False),
+                                     self._vec("Ninv", d, l, False), ident[0], ident[1], self.rescale_scales[l][d], round_at, ws,
+                                     self._consts(d, l, False))
         return [[self._new(([o[0]], [o[1]]), types.origins["ct"], level=l + 1) for o in tok] for tok in outs]
 
     def _pc_identity(self, l, d):

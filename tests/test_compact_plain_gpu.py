@@ -279,3 +279,41 @@ def test_real_keys_decrypt_within_twice_the_loop_on_silver():
         print(f"silver, 4 x 3 + bias, level 0, output {o}: max abs error compact pc_matmul {e_mm:.3e}, mc_mult / cc_add / mc_add loop "
               f"{e_loop:.3e}, largest entry {np.abs(want).max():.2f}")
         assert e_mm <= 2 * e_loop and e_loop < 1e-5
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k_in", ["2", "CI+1"])
+def test_every_tile_of_the_product_body_equals_the_pc_dots(k_in, monkeypatch):
+    """The one product body through all its tiles, raw and compact: logN 13, level 0 (rows of both classes), k_out = 7 — output
+    groups 4 + 2 + 1, under LF_TUNE_PC_MATMUL_TILE = 2 over four tokens 2 + 2 + 2 + 1 — over k_in = 2 and CI + 1 inputs (a second
+    chunk: the read - add - write of S), with holes and a partly-None bias.  Four tokens as ONE native call (tiles 2 + 2; 4 under
+    the knob's values 1 and 2) and three as one (2 + 1).  Every output has exactly the words of pc_dot over the row's non-None
+    entries on the raw plaintexts, token by token."""
+    from liberate_fhe_amd._native import lib
+    from liberate_fhe_amd.fhe.backend import SMALL_PRIME_LIMIT
+    eng = engine("logN13")
+    q0 = primes_of(eng, 0)
+    assert any(q < SMALL_PRIME_LIMIT for q in q0) and any(q >= SMALL_PRIME_LIMIT for q in q0)
+    k_in, k_out = {"2": 2, "CI+1": chunk() + 1}[k_in], 7
+    W, cts, bias = layer_of(pool_of(eng, 0, 61), k_in, k_out)
+    assert any(pt is None for row in W for pt in row) and any(b is None for b in bias) and any(b is not None for b in bias)
+    K = compact_layer(eng, W)
+    X = [[cts[(i + t) % k_in] for i in range(k_in)] for t in range(4)]
+    want = [[eng.pc_dot([(pt, ct) for pt, ct in zip(row, tok) if pt is not None], b) for row, b in zip(W, bias)] for tok in X]
+    d = eng._pc_planes_native(0)
+    assert d is not None
+    monkeypatch.setattr(eng, "pc_matmul_batch_sizes", (4, 2))            # (ONE native call of four tokens: what the tile knob acts on)
+    calls = count_calls(eng, monkeypatch)
+    try:
+        for tile in (0, 1, 2):
+            lib.lf_tune(6, tile)
+            for M, entry, planes in ((W, "pc_matmul_batch_native", False), (K, "pc_matmul_batch_planes_call", True)):
+                got = eng.pc_matmul_batch(M, X, bias)
+                got3 = eng._pc_matmul_batch_native(M, X[:3], bias, 0, d, planes=planes)
+                assert calls == [(entry, 4), (entry, 3)]
+                calls.clear()
+                for res in (got, got3):
+                    assert all(len(tok) == k_out for tok in res)
+                    assert all(same(g, w) for gs, ws in zip(res, want) for g, w in zip(gs, ws)), (tile, entry, len(res))
+    finally:
+        lib.lf_tune(6, 0)

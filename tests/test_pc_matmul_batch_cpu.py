@@ -392,15 +392,19 @@ def test_the_tile_knob_is_a_tuning_knob():
 
 def test_pc_matmulb_kernels_use_no_scratch():
     """Every tile the launch code can select (GO = 1 | 2 | 4 outputs x GT = 2 tokens; GT = 4 under LF_TUNE_PC_MATMUL_TILE) exists
-    under its own name with scratch 0 and no spill, the default ones (GT = 2) with at least 4 waves per SIMD, and the tracked table lists it as built; pc_matmul_kernel<1 | 2 | 4> keep the figures the table had for them
-    before the batched kernels were added (VGPRs 53 / 67 / 83, 8 / 7 / 5 waves per SIMD)."""
+    under its own name with scratch 0 and no spill, the default ones (GT = 2) with at least 4 waves per SIMD, and the tracked table lists it as built; pc_matmul_kernel<1 | 2 | 4> are held to
+    their figures, VGPRs 53 / 69 / 85 at 8 / 7 / 5 waves per SIMD (53 / 67 / 83 at the same waves until the three product bodies became
+    one: the same instructions to within two, LAB_NOTES has the timings); the launch table selects exactly the three of them."""
     import __graft_entry__ as g
     res = {r["kernel"]: r for r in g.kernel_resources()}
     want = [f"pc_matmulb_kernel<{go}, {gt}>" for go in (1, 2, 4) for gt in (2, 4)]
     assert sorted(k for k in res if k.startswith("pc_matmulb_kernel")) == sorted(want)
     src = open(os.path.join(ROOT, "liberate_fhe_amd", "csrc", "ckks_ks.hip")).read()
-    launched = re.findall(r"LF_PCMMB_CASE\((\d), (\d)\)", src.split("switch (go * 8 + gt)")[1].split("}")[0])
+    table = src.split("switch ((planes ? 64 : 0) + go * 8 + gt)")[1].split("}")[0]      # (the one dispatch of lf_pc_matmul_products)
+    launched = re.findall(r"LF_PCMMB_CASE\((\d), (\d)\)", table)
     assert sorted(f"pc_matmulb_kernel<{go}, {gt}>" for go, gt in launched) == sorted(want)
+    one = [f"pc_matmul_kernel<{go}>" for go in re.findall(r"LF_PCMM_CASE\((\d)\)", table)]
+    assert sorted(one) == sorted(k for k in res if k.startswith("pc_matmul_kernel")) == [f"pc_matmul_kernel<{go}>" for go in (1, 2, 4)]
     tracked = open(os.path.join(ROOT, "profiles", "r06_kernel_resources.txt")).read()
     for k in want:
         r = res[k]
@@ -409,5 +413,5 @@ def test_pc_matmulb_kernels_use_no_scratch():
         line = next(ln for ln in tracked.splitlines() if ln[18:76].strip() == k)
         f = line.split()
         assert (int(f[-7]), int(f[-3]), int(f[-1])) == (r["vgprs"], r["scratch"], r["occupancy"]), line
-    for k, vgprs, occ in (("pc_matmul_kernel<1>", 53, 8), ("pc_matmul_kernel<2>", 67, 7), ("pc_matmul_kernel<4>", 83, 5)):
+    for k, vgprs, occ in (("pc_matmul_kernel<1>", 53, 8), ("pc_matmul_kernel<2>", 69, 7), ("pc_matmul_kernel<4>", 85, 5)):
         assert (res[k]["vgprs"], res[k]["occupancy"], res[k]["scratch"]) == (vgprs, occ, 0), res[k]

@@ -994,6 +994,21 @@ int lf_level_sum(int nsets, const int64_t *k, const int64_t *const *in, const in
                  const int64_t *round_at, const int64_t *const *tab, const int64_t *const *consts, int64_t *const *out, int rows,
                  int logN, const int64_t *ql, const int64_t *qh, const int64_t *kl, const int64_t *kh, int device, void *stream);
 
+/* mod_raise: the base-prime residue of `count` ciphertexts lifted to every limb of level 0 — the first step of a bootstrap.  ONE
+ * launch for both components of all of them.
+ * in0 / in1: HOST arrays of count device pointers: the base-prime row (N words) of c0 / c1 of ciphertext i, at whatever level it
+ * stands; a word w is a lazy word in [0, 2 q_b) or what a rescale leaves, -q_b < w < 2 q_b.  out0 / out1: HOST arrays of count
+ * device pointers, [rows][N] each.  rows = limbs of level 0 on this device; mont_one[r] = R mod q_r (R = 2^62) and ql .. kh hold
+ * its rows entries (DEVICE).  Every pointer of in / out 16-byte aligned.  Per coefficient, with r = w mod q_b in [0, q_b) and
+ * v = r - q_b if r > (q_b - 1) / 2 else r, row i of the output holds v mod q_i in [0, q_i): exactly the words of int64
+ * remainder(v, q_i).  The same polynomial may appear any number of times among the inputs; outputs must be distinct.
+ * LF_ERR_ARG before any device call for count < 1 or > LF_MOD_RAISE_MAX_CTS, rows < 0 or > lf_limits(LF_LIMIT_ROWS), N < 2 or
+ * odd, q_b < 3 or >= 2^62, a NULL among the arrays, their entries, mont_one, ql .. kh, and a misaligned entry of in / out. */
+#define LF_MOD_RAISE_MAX_CTS 64
+int lf_mod_raise(int count, const int64_t *const *in0, const int64_t *const *in1, int64_t *const *out0, int64_t *const *out1,
+                 int rows, int64_t N, int64_t q_b, const int64_t *mont_one, const int64_t *ql, const int64_t *qh,
+                 const int64_t *kl, const int64_t *kh, int device, void *stream);
+
 /* Sum of plaintext-ciphertext products under ONE rescale, for plaintexts encoded once (ckks_engine.encode_plain): out decrypts to
  * sum_i pt_i * ct_i (+ bias), level l -> l + 1.  Plan-free: no key, no digits.
  * k >= 1 terms; in: HOST array of 2 k device pointers, [term][component]: ct_i.c0, ct_i.c1, each [rows][N] at level l (all its

@@ -116,6 +116,7 @@ _SIGNATURES["lf_cc_matmul_ws_words"] = [_PL, _I]
 _SIGNATURES["lf_cc_matmul"] = [_PL, _I, _I, _I, _I, _P, _P, _P, _P, _P, _L, _L, _L, _I, _P, _L, _P, _P, _P]
 _SIGNATURES["lf_weighted_sums"] =[_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _L, _P, _P, _P, _P, _I, _P]
 _SIGNATURES["lf_level_sum"] = [_I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _I, _P]
+_SIGNATURES["lf_mod_raise"] = [_I, _P, _P, _P, _P, _I, _L, _L, _P, _P, _P, _P, _P, _I, _P]
 _SIGNATURES["lf_pc_dot_ws_words"] = [_I, _I, _I]
 _SIGNATURES["lf_pc_dot"] = [_I, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _I, _P]
 _SIGNATURES["lf_pc_matmul_ws_words"] = [_I, _I, _I, _I]
@@ -195,7 +196,8 @@ LF_WSUM_MAX_TERMS = 16      # include/ckks_hip.h: terms per lf_weighted_sums cal
 LF_WSUM_MAX_OUTPUTS = 64    # .. and outputs
 LF_LSUM_MAX_TERMS = 8       # include/ckks_hip.h: terms per set of an lf_level_sum call
 LF_LSUM_MAX_SETS = 8        # .. and sets per call
-LF_PC_MATMUL_CI = 16           # include/ckks_hip.h: inputs per chunk of lf_pc_matmul
+LF_MOD_RAISE_MAX_CTS = 64   # include/ckks_hip.h: ciphertexts per lf_mod_raise call
+LF_PC_MATMUL_CI = 16          # include/ckks_hip.h: inputs per chunk of lf_pc_matmul
 LF_PC_MATMUL_MAX_OUTPUTS = 64  # .. and outputs per call
 LF_PC_MATMUL_BATCH_MAX_TOKENS = 4   # include/ckks_hip.h: token vectors per lf_pc_matmul_batch call
 LF_PLAIN_PLANES_MAX_ROWS = 64       # include/ckks_hip.h: rows of a compact plaintext (lf_plain_planes)

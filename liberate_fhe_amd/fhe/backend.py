@@ -505,6 +505,29 @@ class HipBackend:
                                _parr([cst for _, _, cst in sets]), _parr([o for pair in outs for o in pair]), rows, logN, *c.mont(),
                                dev, st), "lf_level_sum")
 
+    # include/ckks_hip.h: LF_MOD_RAISE_MAX_CTS (tests/test_mod_raise_cpu.py holds this copy to the header)
+    mod_raise_max_cts = 64
+
+    def mod_raise_call(self, base_rows, outs, rows, q_b, mont_one, c: Consts):
+        """len(base_rows) <= mod_raise_max_cts ciphertexts raised from their base-prime rows to level 0 as ONE native call
+        (lf_mod_raise).  base_rows: one pair of [N] views (the base row of c0, of c1) per ciphertext; outs: one pair of [rows, N]
+        tensors per ciphertext; mont_one [rows] = R mod q and c: the constants of level 0 (rows entries)."""
+        dev, st = _ds(outs[0][0])
+        N = outs[0][0].size(-1)
+        for pair in base_rows:
+            for t in pair:
+                if t.dim() != 1 or t.size(0) != N:
+                    raise ValueError("HipBackend.mod_raise_call: a base row is one row of N words")
+        for pair in outs:
+            for t in pair:
+                if tuple(t.shape) != (rows, N):
+                    raise ValueError("HipBackend.mod_raise_call: an output is [rows, N]")
+        if mont_one.numel() != rows:
+            raise ValueError("HipBackend.mod_raise_call: constants of another level than the outputs'")
+        check(lib.lf_mod_raise(len(base_rows), _parr([p[0] for p in base_rows]), _parr([p[1] for p in base_rows]),
+                               _parr([o[0] for o in outs]), _parr([o[1] for o in outs]), rows, N, int(q_b), _p(mont_one), *c.mont(),
+                               dev, st), "lf_mod_raise")
+
     @staticmethod
     def pc_dot_ws_words(k, rows, logN):
         return int(lib.lf_pc_dot_ws_words(k, rows, logN))

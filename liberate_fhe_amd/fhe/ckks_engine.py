@@ -44,6 +44,7 @@ from .plainops import PlainOps
 from .polyeval import PolyOps
 from .presets import errors, types
 from .levelsum import LevelSumOps
+from .modraise import ModRaiseOps
 from .slotsum import SlotSumOps
 from .version import VERSION
 
@@ -83,7 +84,7 @@ class _OneShard:
         return ckks_engine._decrypt_rows_on(self, ct, sk, self.li, self.dev)
 
 
-class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMatmulOps, LevelSumOps):
+class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMatmulOps, LevelSumOps, ModRaiseOps):
     @errors.log_error
     def __init__(self, devices: list[int] = None, verbose: bool = False, bias_guard: bool = True,
                  norm: str = "forward", backend=None, comm=None, balanced_limb_map: bool = False, **ctx_params):
@@ -445,9 +446,31 @@ class ckks_engine(EvaluatorOps, PolyOps, PlainOps, LtMatmulOps, SlotSumOps, CcMa
     def _live(self, xs):
         return [x for x in xs if x is not None]
 
+    def _sparse_ternary(self, h):
+        """[1, N] per local device, exactly h entries +-1: ONE draw w = rng.randint(amax=2^62, repeats=1) — N words of the
+        repeating channel, the same on every device, as the dense key's draw.  Coefficient j has the rank w_j >> 1 and the sign
+        +1 if bit 0 of w_j is clear, -1 if it is set; the h coefficients of the smallest rank are the non-zero ones, equal ranks
+        (2^-61 per pair) in the order of j (a stable sort).  A uniform h-subset with independent uniform signs; a seeded sampler
+        reproduces it."""
+        if isinstance(h, bool) or not isinstance(h, (int, np.integer)) or not 1 <= h <= self.ctx.N:
+            raise ValueError(f"create_secret_key: hamming_weight must be an integer in 1 .. N = {self.ctx.N}, got {h!r}")
+        out = []
+        for w in self._live(self.rng.randint(amax=1 << 62, shift=0, repeats=1)):
+            flat = w.reshape(-1)
+            picked = torch.sort(flat >> 1, stable=True).indices[:int(h)]
+            key = torch.zeros_like(flat)
+            key[picked] = 1 - 2 * (flat[picked] & 1)
+            out.append(key.view(1, -1))
+        return out
+
     @errors.log_error
-    def create_secret_key(self, include_special: bool = True) -> data_struct:
-        ternary = self._live(self.rng.randint(amax=3, shift=-1, repeats=1))
+    def create_secret_key(self,include_special: bool = True, hamming_weight=None) -> data_struct:
+        """hamming_weight=None: the reference's uniform ternary key.  hamming_weight=h, 1 <= h <= N: a ternary key with exactly h
+        non-zero coefficients (the sparse key that bounds mod_raise's overflow), from ONE draw of the sampler (_sparse_ternary)."""
+        if hamming_weight is None:
+            ternary = self._live(self.rng.randint(amax=3, shift=-1, repeats=1))
+        else:
+            ternary = self._sparse_ternary(hamming_weight)
         mult_type = -2 if include_special else -1
         sk = self.ntt.tile_unsigned(ternary, lvl=0, mult_type=mult_type)
         self.ntt.enter_ntt(sk, 0, mult_type)

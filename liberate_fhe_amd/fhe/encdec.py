@@ -116,6 +116,53 @@ def conjugation_exponent(N: int) -> int:
     return 2 * N - 1
 
 
+_coeff_slot_cache = {}
+
+
+def coeff_slot_matrices(N: int, norm: str = "forward") -> tuple:
+    """(B, C, E, F), complex [n, n] with n = N / 2: the maps between the slots z of a REAL coefficient vector t of length N (what
+    decode(t, return_without_scaling=True)[:n] gives) and its coefficients packed two to a slot, u = t[:n] + 1j * t[n:]:
+        u = B z + C conj(z),        z = E u + F conj(u).
+    Only real-linear: with this slot order (generator 3, galois_exponent) the evaluation points zeta_k satisfy
+    zeta_k^(N/2) = +i or -i alternating from slot to slot, so neither map is a complex matrix alone — C and F are not zero.
+    In closed form from the transforms encode and decode apply, on all unit vectors at once (host numpy, no engine); kept per
+    (N, norm).  Read-only: callers share the cached arrays."""
+    key = (int(N), norm)
+    hit = _coeff_slot_cache.get(key)
+    if hit is not None:
+        return hit
+    if N < 4 or N & (N - 1):
+        raise ValueError(f"coeff_slot_matrices: N must be a power of two >= 4, got {N}")
+    n = N // 2
+    pre, post = _slot_permutation(N)
+    k = np.arange(N)
+    # decode on the unit vectors: column k of V is decode(e_k)[:n];  z = V t = V_lo Re(u) + V_hi Im(u)
+    vals = np.fft.ifft(np.eye(N) * np.exp(1j * np.pi * k / N)[:, None], axis=0, norm=norm)
+    V = np.zeros((N, N), dtype=np.complex128)
+    V[post] = vals
+    V = V[:n]
+    E = (V[:, :n] - 1j * V[:, n:]) / 2
+    F = (V[:, :n] + 1j * V[:, n:]) / 2
+    del V, vals
+    # encode without scaling on the unit vectors: t = W z + conj(W) conj(z) with column k of W = (t(e_k) - i t(i e_k)) / 2, where
+    # t(m) = Re(fft(spread(m)) * twister) and spread(e_k) has a one at pre[k] and at N - 1 - pre[k]
+    twist = np.exp(-1j * np.pi * k / N)[:, None]
+    S = np.zeros((N, n), dtype=np.complex128)
+    S[pre, np.arange(n)] = 1.0
+    fa = np.fft.fft(S, axis=0, norm=norm) * twist                 # the slot's own term
+    fb = np.fft.fft(S[::-1], axis=0, norm=norm) * twist           # its mirrored conjugate
+    del S
+    t_one = (fa + fb).real
+    t_i = (1j * fa - 1j * fb).real
+    W = (t_one - 1j * t_i) / 2
+    B = W[:n] + 1j * W[n:]
+    C = W[:n].conj() + 1j * W[n:].conj()
+    out = _coeff_slot_cache[key] = (B, C, E, F)
+    for M in out:
+        M.setflags(write=False)
+    return out
+
+
 def matrix_diagonals(M) -> dict:
     """The non-zero generalized diagonals of a square matrix, {step: vector} with diag_step[i] = M[i][(i - step) mod n]: the
     convention in which M @ v = sum_step diag_step * np.roll(v, step), i.e. what ckks_engine.linear_transform evaluates."""
